@@ -33,10 +33,12 @@ Pipelining inside a step, all of it real work of that step or the next (nothing 
 (`--gpus N` spawns the ranks itself when not already under torchrun); ranks take different scenes of one global
 scene list (weak scaling: per-GPU work fixed); the only collective is the gradient all-reduce.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the kernel instance with the largest share of the step among
-the convolution launches of this very workload, found and timed live (HIP events on the launching stream);
-`cpu_baseline` is the oracle (CPU port of the reference path) on a bounded sample of the same workload with the
-per-stage split of SURVEY 8(d).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times exactly --steps steps and prints the headline
+(`value`, `ms_per_step`); `--dump-outputs DIR` also writes what the last timed step computed (step_outputs).
+`--full` adds everything else: `timing.extended`, and `roofline`, the kernel instance with the largest share of the
+step among the convolution launches of this very workload, found and timed live (HIP events on the launching stream),
+with the per-stage figures and the other legs (`extras`); `cpu_baseline` is the oracle (CPU port of the reference
+path) on a bounded sample of the same workload with the per-stage split of SURVEY 8(d).
 """
 import argparse
 import importlib
@@ -187,6 +189,7 @@ class Workload(object):
         self.label_generation = os.environ.get("AABR_BENCH_LABELS", "1") != "0"
         self.grad_buckets = int(os.environ.get("AABR_BENCH_GRAD_BUCKETS", "4"))
         self.last = None
+        self.last_head = None
         self.marks = None            # tools/tools_step_timeline.py: [(name, host time, HIP event on the main stream)]
         # AABR_BENCH_SIDE_PRIORITY=1: higher queue priority for the proposal / label streams (chains of small launches
         # beside the backward pass's long workgroups); measured 14.47 -> 14.78 ms, off
@@ -321,6 +324,7 @@ class Workload(object):
                 main.wait_stream(self.side)
             self._mark("main waits for the proposal stream")
         self.last = (rpn_maps, props, labels)
+        self.last_head = (loss.detach(), objs, regs)      # for --dump-outputs
         return loss
 
     def _update_now(self):
@@ -906,13 +910,17 @@ def _region(torch, dist, wl, n, i0, world, dev):
     return el, dev_ms, host_ms
 
 
-def timed_steps(torch, dist, wl, steps, warmup, world, dev, min_timed_s=0.0, prewarm=True):
+def timed_steps(torch, dist, wl, steps, warmup, world, dev, min_timed_s=0.0, prewarm=True, after_region=None):
     """`warmup` untimed steps, the disclosed settle loop, then EXACTLY `steps` timed steps between barrier +
     synchronize on both sides, MAX over ranks (the contract's region: `value` comes from it).  Every timed step also
     gets a host timestamp and a HIP event at its end on the launching stream (no synchronisation inside the
-    region), so the line shows the distribution of step times and the first five.  When that region is shorter
-    than `min_timed_s`, a SECOND region long enough to fill it is timed the same way right after and reported
-    beside the first (`timing.extended`): a cross-check of a 0.3 s headline against >= 1 s of the same steps."""
+    region), so the line shows the distribution of step times and the first five.  `after_region()` is called right
+    after that region, before anything else runs.  When that region is shorter than `min_timed_s`, a SECOND region
+    long enough to fill it is timed the same way right after and reported beside the first (`timing.extended`): a
+    cross-check of a 0.3 s headline against >= 1 s of the same steps.
+    The settle loop runs as many steps as the clocks need, so it is padded to whole cycles of the resident batches and
+    the parameters are put back to where the warm-up left them: the timed steps see the same batches and weights
+    whatever the settle loop ran, and the last step's outputs are the same from run to run."""
     import gc
     for i in range(warmup):
         wl.step(i)
@@ -940,12 +948,21 @@ def timed_steps(torch, dist, wl, steps, warmup, world, dev, min_timed_s=0.0, pre
     gc.callbacks.append(_gc_cb)
     i0 = warmup
     if prewarm:
+        params = wl.flat.flat.clone()
         n, sec, est, log = settle(torch, dist, wl, i0, world, dev)
-        i0 += n
-        info.update(prewarm_steps=n, prewarm_s=round(sec, 3),
+        pad = -n % len(wl.batches)
+        for k in range(pad):
+            wl.step(i0 + n + k)
+        torch.cuda.synchronize()
+        wl.flat.flat.copy_(params)
+        del params
+        i0 += n + pad
+        info.update(prewarm_steps=n, prewarm_pad_steps=pad, prewarm_s=round(sec, 3),
                     prewarm_group_ms=log if len(log) <= 10 else log[:6] + ["..."] + log[-3:])
     el_local, dev_ms, host_ms = _region(torch, dist, wl, steps, i0, world, dev)
     i0 += steps
+    if after_region is not None:
+        after_region()
     el = el_local
     if world > 1:
         t = torch.tensor([el, -el], device=dev, dtype=torch.float64)
@@ -987,6 +1004,76 @@ def timed_steps(torch, dist, wl, steps, warmup, world, dev, min_timed_s=0.0, pre
     return el, info
 
 
+DUMP_MAX_BYTES = 60 * 10 ** 6        # under 64 MB with the .npy headers
+DUMP_PARAM_SAMPLE = 1 << 20
+
+
+def step_outputs(torch, wl):
+    """What the last step computed, as host arrays (float32; integers and the loss as float64): the loss; per RPN map
+    the site coordinates (x, y, z, scene), features, objectness logits [sites, yaws] and box regression
+    [sites, yaws, 7]; per scene the proposals (boxes, scores: NMS order) and the anchor labels (matched ground-truth
+    index and IoU, anchors of every map in map order); the parameters after the update and their gradients at
+    the entries np.sort(np.random.default_rng(0).choice(n, DUMP_PARAM_SAMPLE, replace=False)) of the flat parameter
+    vector (n entries).  Map rows and anchors are put in coordinate order (scene, x, y, z), so the arrays do not
+    depend on the internal site order."""
+    import numpy as np
+    rpn_maps, props, labels = wl.last
+    loss, objs, regs = wl.last_head
+    out = {"loss": np.array([float(loss)], np.float64)}
+    local = []                 # per map and scene: the scene's rows in coordinate order, counted from its first row
+    for m, (t, o, r) in enumerate(zip(rpn_maps, objs, regs)):
+        c = t.get_spatial_locations().numpy()
+        order = np.lexsort((c[:, 2], c[:, 1], c[:, 0], c[:, 3]))
+        assert (np.diff(c[:, 3]) >= 0).all(), "map %d: rows not grouped by scene" % m
+        V = c.shape[0]
+        out["map%d_coords" % m] = c[order].astype(np.float64)
+        out["map%d_features" % m] = t.features.detach().float().cpu().numpy()[order]
+        out["map%d_objectness" % m] = o.detach().float().cpu().numpy().reshape(V, -1)[order]
+        out["map%d_box_regression" % m] = r.detach().float().cpu().numpy().reshape(V, -1, 7)[order]
+        starts = np.searchsorted(c[:, 3], np.arange(len(props) + 1))
+        local.append([order[(order >= starts[b]) & (order < starts[b + 1])] - starts[b] for b in range(len(props))])
+    for b, (boxes, scores) in enumerate(props):
+        out["scene%d_proposal_boxes" % b] = boxes.float().cpu().numpy()
+        out["scene%d_proposal_scores" % b] = scores.float().cpu().numpy()
+    A = len(YAWS)
+    for b, lab in enumerate(labels or []):
+        idx, val = lab[0].cpu().numpy(), lab[1].float().cpu().numpy()
+        pieces_i, pieces_v, o = [], [], 0
+        for m in range(len(rpn_maps)):
+            n = len(local[m][b])
+            rows = (o + local[m][b][:, None] * A + np.arange(A)).reshape(-1)
+            pieces_i.append(idx[rows])
+            pieces_v.append(val[rows])
+            o += n * A
+        assert o == idx.shape[0], "scene %d: %d labels for %d anchors" % (b, idx.shape[0], o)
+        out["scene%d_matched_idxs" % b] = np.concatenate(pieces_i).astype(np.float64)
+        out["scene%d_matched_iou" % b] = np.concatenate(pieces_v)
+    flat = wl.flat
+    n = flat.flat.numel()
+    sel = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_PARAM_SAMPLE), replace=False))
+    sel_t = torch.as_tensor(sel, device=flat.flat.device)
+    grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1) for p in flat.params])
+    out["param_sample"] = flat.flat[sel_t].float().cpu().numpy()
+    out["param_grad_sample"] = grads[sel_t].float().cpu().numpy()
+    return out
+
+
+def write_outputs(arrays, path, max_bytes=DUMP_MAX_BYTES):
+    """`arrays` as path/<name>.npy; when they add up to more than `max_bytes`, every array is cut to the same
+    fraction of its rows, a fixed seeded sample in row order"""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    keep = min(1.0, max_bytes / float(max(total, 1)))
+    for name, a in sorted(arrays.items()):
+        a = np.ascontiguousarray(a)
+        if keep < 1.0 and a.ndim and a.shape[0] > 1:
+            k = max(1, int(a.shape[0] * keep))
+            a = a[np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.shape[0], k, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -999,15 +1086,26 @@ def main():
                     help="BASELINE.json configs index: 2 (default, the headline) = 4 x S80k @ 2 cm per GPU and step; "
                          "4 = one 1.5 M-point scene @ 2 cm per step (the rule-book stress; bf16 storage unless --dtype "
                          "f32), same network and step")
-    ap.add_argument("--min-timed-s", type=float, default=1.0,
+    ap.add_argument("--min-timed-s", type=float, default=None,
                     help="when the --steps region is shorter than this, a second region of at least this many "
-                         "seconds is timed right after it and reported as `timing.extended` (0 = off)")
+                         "seconds is timed right after it and reported as `timing.extended` (0 = off; default: 1 "
+                         "with --full, else 0)")
     ap.add_argument("--no-prewarm", action="store_true", help="skip the disclosed settle loop before the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the `timing.extended` cross-check, the "
+                         "dominant-kernel roofline and convolution table, voxel scatter, per-stage rooflines, label "
+                         "generation, the other storage type / site order / pruned legs and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave everything but the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (step_outputs; rank 0)")
     ap.add_argument("--dtype", default=None, choices=["f32", "bf16"],
                     help="feature storage of the HEADLINE loop (default: f32 for --config 2, bf16 for --config 4)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.min_timed_s is None:
+        args.min_timed_s = 1.0 if args.full else 0.0
     global SCENES_PER_STEP, N_POINTS
     if args.config == 4:
         SCENES_PER_STEP, N_POINTS = 1, 1500000
@@ -1061,11 +1159,16 @@ def main():
     if main_prio:
         torch.cuda.synchronize()
         torch.cuda.set_stream(torch.cuda.Stream(device=dev, priority=-1))
+    dumped = {}
+    grab = (lambda: dumped.update(step_outputs(torch, wl))) if (args.dump_outputs and rank == 0) else None
     el, tinfo = timed_steps(torch, dist, wl, args.steps, args.warmup, world, dev,
-                            min_timed_s=args.min_timed_s, prewarm=not args.no_prewarm)
+                            min_timed_s=args.min_timed_s, prewarm=not args.no_prewarm, after_region=grab)
     n_timed = args.steps
 
     if rank == 0:
+        if args.dump_outputs:
+            write_outputs(dumped, args.dump_outputs)
+            dumped.clear()
         n_pts = int(wl.batches[0][0].shape[0])
         V0 = int(wl.last[0][0].metadata.input["V"])
         n_prop = [int(b.shape[0]) for b, _ in wl.last[1]]
@@ -1108,7 +1211,7 @@ def main():
                                        rank_ms_per_step_max=tinfo.get("rank_ms_per_step_max"))
         if el < MIN_TIMED_S:
             line["timed_region_short"] = True
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             rf, table = roofline_block(torch, wl, head_dtype, el / n_timed * 1e6)
             line["roofline"] = rf
             line["conv_kernels"] = [{k: v for k, v in r.items() if k not in ("flops_per_launch", "grid_threads")}
@@ -1228,7 +1331,7 @@ def main():
                 finally:
                     wl.net.prune_unused_levels = False
                 line["extras"] = extras
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(wl, torch)
         print(json.dumps(line))
         sys.stdout.flush()

@@ -212,8 +212,8 @@ def test_bench_gpus2_rehearsal_on_one_gpu():
     cuda:0 and the collective goes through gloo -- the launcher, sharding and all-reduce path are the real ones."""
     env = dict(os.environ, AABR_BENCH_SHARE_GPU="1", AABR_BENCH_BACKEND="gloo", AABR_BENCH_PIN="0")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--batches", "1", "--no-cpu-baseline", "--no-extras", "--min-timed-s", "0.2"], env=env,
-                       capture_output=True, text=True, timeout=900)
+                        "--batches", "1", "--full", "--no-cpu-baseline", "--no-extras", "--min-timed-s", "0.2"],
+                       env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
