@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libaabr_hip.so")
 
 _lib = None
 META_WORDS = 16
-ABI_VERSION = 600      # include/aabr_hip.h AABR_ABI_VERSION this binding (_SIGS) was written for
+ABI_VERSION = 610      # include/aabr_hip.h AABR_ABI_VERSION this binding (_SIGS) was written for
 
 _vp, _i64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 _i32p = C.POINTER(C.c_int32)
@@ -165,6 +165,16 @@ _SIGS = {
                                            _f32, _f32, _vp, _i64, _vp, _vp, _vp, _f32, _i32, _i64, _vp, _vp, _vp, _vp]),
     "aabr_rotate_nms_sorted": (C.c_int, [_vp, _i64, _f32, _i32, _i64, _vp, _vp, _vp, _vp]),
     "aabr_nms_sorted": (C.c_int, [_vp, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "aabr_rpn_loss_scratch_words": (C.c_int64, [_i32]),
+    "aabr_rpn_loss_forward": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32p, _i32p, _vp, _vp, C.c_uint32, _i32,
+                                        _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aabr_rpn_loss_backward": (C.c_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32p, _i32p, _vp, _i32, _f32, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp]),
+    "aabr_sample_list": (C.c_int, [_i32, _vp, C.POINTER(C.c_int64), C.c_uint32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                   _vp]),
+    "aabr_smooth_l1_scratch_floats": (C.c_int64, []),
+    "aabr_smooth_l1_forward": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp]),
+    "aabr_smooth_l1_backward": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))
 
@@ -373,6 +383,11 @@ def i32xn(v):
 def ptrs(ts):
     """host array of device pointers"""
     return (C.c_void_p * len(ts))(*[t.data_ptr() if t is not None and t.numel() else None for t in ts])
+
+
+def i64xn(v):
+    v = [int(x) for x in v]
+    return (C.c_int64 * len(v))(*v)
 
 
 def f32x4(v):

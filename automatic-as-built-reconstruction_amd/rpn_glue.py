@@ -367,3 +367,134 @@ def cat_scales_obj_reg(objectness, rpn_box_regression, examples_idxscope):
     obj = torch.cat([torch.cat(o, 0) for o in obj_new], 0)
     reg = torch.cat([torch.cat(r, 0) for r in reg_new], 0)
     return obj, reg
+
+
+def parse_yaw_loss_mode(yaw_loss_mode):
+    """`'Diff'` / `'Diff_<w>'` (layers/smooth_l1_loss.py:7-14,19-25: the weight of 'Diff' is parsed and never applied, so
+    every column is the plain smooth L1 of |pred - target|).  `'SinDiff'` is refused: the reference reads
+    `anchor.bbox3d` in it (smooth_l1_loss.py:27) while RPNLossComputation passes a plain tensor as `anchor`
+    (loss_3d.py:238-241), so that mode can never run through the RPN loss."""
+    mode = str(yaw_loss_mode).split("_")[0]
+    if mode == "SinDiff":
+        raise ValueError("yaw_loss_mode %r: 'SinDiff' is not supported (the reference's RPN loss cannot run it: it passes a "
+                         "tensor where smooth_l1_loss reads anchor.bbox3d)" % (yaw_loss_mode,))
+    if mode != "Diff":
+        raise ValueError("yaw_loss_mode %r: expected 'Diff' or 'Diff_<weight>'" % (yaw_loss_mode,))
+    return mode
+
+
+def draw_seed():
+    """one 31-bit seed from torch's default CPU generator: no device work, reproduced by torch.manual_seed"""
+    return int(torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int64).item())
+
+
+_BF16_OR_F32 = (torch.float32, torch.bfloat16)
+
+
+class _RpnLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cfg, *tensors):
+        lib = _hip.load()
+        n_maps = cfg["n_maps"]
+        obj, reg = tensors[:n_maps], tensors[n_maps:]
+        dev = obj[0].device
+        bf16 = int(obj[0].dtype == torch.bfloat16)
+        nb, B = cfg["nb"], cfg["B"]
+        obj_c = [o.reshape(-1).contiguous() for o in obj]
+        reg_c = [r.reshape(-1, 7).contiguous() for r in reg]
+        sel = torch.empty((nb, B), dtype=torch.int64, device=dev)
+        info = torch.empty((nb, 8), dtype=torch.int32, device=dev)
+        obj_loss = torch.empty((), dtype=torch.float32, device=dev)
+        box_loss = torch.empty((), dtype=torch.float32, device=dev)
+        scr = _hip.workspace("rpn_loss", int(lib.aabr_rpn_loss_scratch_words(nb)) + 2, torch.int32, dev)
+        so = (-scr.data_ptr() // 4) % 2
+        check(lib.aabr_rpn_loss_forward(
+            n_maps, _hip.ptrs(cfg["coords"]), _hip.ptrs(obj_c), _hip.ptrs(reg_c), bf16, cfg["A"], nb, cfg["seg"],
+            cfg["site"], _hip.ptrs(cfg["labels"]), _hip.ptrs(cfg["targets"]), cfg["seed"], B, cfg["num_pos"], cfg["beta"],
+            ptr(sel), ptr(info), ptr(obj_loss), ptr(box_loss), scr.data_ptr() + 4 * so, stream()))
+        ctx.cfg = cfg
+        ctx.save_for_backward(sel, info, *obj_c, *reg_c)
+        ctx.shapes = [t.shape for t in tensors]
+        ctx.mark_non_differentiable(sel, info)
+        return obj_loss, box_loss, sel, info
+
+    @staticmethod
+    def backward(ctx, g_obj, g_box, _g_sel, _g_info):
+        lib = _hip.load()
+        cfg = ctx.cfg
+        n_maps = cfg["n_maps"]
+        saved = ctx.saved_tensors
+        sel, info, obj_c, reg_c = saved[0], saved[1], saved[2:2 + n_maps], saved[2 + n_maps:]
+        dev, dt = obj_c[0].device, obj_c[0].dtype
+        g_obj = (g_obj if g_obj is not None else torch.zeros((), device=dev)).float().contiguous()
+        g_box = (g_box if g_box is not None else torch.zeros((), device=dev)).float().contiguous()
+        sizes = [o.numel() for o in obj_c] + [r.numel() for r in reg_c]
+        flat = torch.zeros(sum(sizes), dtype=dt, device=dev)       # one fill for every gradient
+        grads = list(torch.split(flat, sizes))
+        check(lib.aabr_rpn_loss_backward(
+            n_maps, _hip.ptrs(obj_c), _hip.ptrs(reg_c), int(dt == torch.bfloat16), cfg["A"], cfg["nb"], cfg["seg"],
+            cfg["site"], _hip.ptrs(cfg["targets"]), cfg["B"], cfg["beta"], ptr(sel), ptr(info), ptr(g_obj), ptr(g_box),
+            _hip.ptrs(grads[:n_maps]), _hip.ptrs(grads[n_maps:]), stream()))
+        return (None,) + tuple(g.view(s) for g, s in zip(grads, ctx.shapes))
+
+
+def rpn_loss(maps, objectness, box_regression, labels, base_anchors, batch_size_per_image=256, positive_fraction=0.5,
+             yaw_loss_mode="Diff", seed=None, return_samples=False):
+    """The RPN loss of the training step, RPNLossComputation.__call__ (modeling/rpn/loss_3d.py:201-251) for one objectness
+    group, on the device with no host read: per example BalancedPositiveNegativeSampler(batch_size_per_image,
+    positive_fraction) over the labels (matched index >= 0 positive, -1 negative, -2 ignored; loss_3d.py:180-187), then
+    `smooth_l1_loss(box_regression[pos], regression_targets[pos], ., beta=1/9, size_average=False) / N_s` and
+    `binary_cross_entropy_with_logits(objectness[sampled], labels[sampled])` (mean), N_s = the anchors sampled over the
+    batch.  An empty sample gives NaN losses (the reference's mean of nothing) and zero gradients.
+
+    maps / base_anchors as in `rpn_proposals` (base_anchors gives A); objectness[m] [V_m*A] (any shape of that size) and
+    box_regression[m] [V_m*A, 7], fp32 or bf16, read where they lie (nothing concatenated, `cat_scales_obj_reg` is not
+    called); labels = the list `rpn_label_matches(..., regression_targets=True)` returns.  The random subset is the one
+    of the rule in include/aabr_hip.h (aabr_rpn_loss_forward): a hash of (seed, example, map, x, y, z, anchor) -- the same
+    anchors whatever the grid's row order; `seed=None` draws one from torch's default CPU generator.
+    `yaw_loss_mode`: 'Diff' / 'Diff_<w>' ('SinDiff' raises ValueError, see parse_yaw_loss_mode).
+    Returns (objectness_loss, box_loss), 0-dim fp32 device tensors with autograd to objectness / box_regression; with
+    `return_samples` also the int64 [nb, batch_size_per_image] selected indices into the concatenated label lists
+    (example-major), positives then negatives, -1 padded."""
+    parse_yaw_loss_mode(yaw_loss_mode)
+    n_maps = len(maps)
+    if not (n_maps == len(objectness) == len(box_regression) == len(base_anchors)):
+        raise ValueError("maps, objectness, box_regression and base_anchors differ in length")
+    nb = len(labels)
+    if nb == 0:
+        raise ValueError("no examples")
+    if any(len(l) < 4 or l[3] is None for l in labels):
+        raise ValueError("labels need the regression targets: rpn_label_matches(..., regression_targets=True)")
+    dt = objectness[0].dtype
+    if dt not in _BF16_OR_F32 or any(t.dtype != dt for t in list(objectness) + list(box_regression)):
+        raise TypeError("objectness and box_regression must all be float32, or all bfloat16")
+    grids = [t.metadata.grids[_SCN._key(t.spatial_size)] for t in maps]
+    dev = objectness[0].device
+    A = int(base_anchors[0].shape[0])
+    counts = [g.sample_counts(nb) for g in grids]
+    if any(c is None for c in counts):
+        counts = torch.stack([torch.bincount(g.coords[:, 3].long(), minlength=nb)[:nb] if g.V else
+                              torch.zeros(nb, dtype=torch.int64, device=dev) for g in grids]).tolist()
+    for m in range(n_maps):
+        V = sum(counts[m])
+        if objectness[m].numel() != V * A or box_regression[m].numel() != V * A * 7:
+            raise ValueError("map %d: objectness / box_regression do not hold %d sites x %d anchors" % (m, V, A))
+    seg, site, s0 = [], [], [0] * n_maps
+    for bi in range(nb):
+        s_ = [0]
+        for m in range(n_maps):
+            s_.append(s_[-1] + counts[m][bi] * A)
+        if labels[bi][0].numel() != s_[-1] or labels[bi][3].shape[0] != s_[-1]:
+            raise ValueError("example %d: the labels do not match the maps' anchors" % bi)
+        seg += s_
+        site += s0
+        s0 = [s0[m] + counts[m][bi] for m in range(n_maps)]
+    lab = [l[0] if l[0].dtype == torch.int64 else l[0].long() for l in labels]
+    tgt = [l[3].float().contiguous() for l in labels]
+    cfg = {"n_maps": n_maps, "nb": nb, "A": A, "B": int(batch_size_per_image),
+           "num_pos": int(batch_size_per_image * positive_fraction), "beta": 1.0 / 9,
+           "seed": int(draw_seed() if seed is None else seed) & 0xffffffff,
+           "coords": [g.coords for g in grids], "seg": _hip.i32xn(seg), "site": _hip.i32xn(site),
+           "labels": [l.contiguous() for l in lab], "targets": tgt}
+    obj_loss, box_loss, sel, _ = _RpnLoss.apply(cfg, *objectness, *box_regression)
+    return (obj_loss, box_loss, sel) if return_samples else (obj_loss, box_loss)

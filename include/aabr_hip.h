@@ -34,8 +34,9 @@ extern "C" {
 const char *aabr_last_error(void);
 /* ABI version: bumped whenever a signature, a record layout or AABR_META_WORDS changes; a binding written for one value
  * must refuse a library that reports another (`_hip.load()` does).  500 = round 5 (16-word meta blocks, brick grids);
- * 600 = round 6 (regression targets out of the label kernel, list encode / decode, fused small-map records). */
-#define AABR_ABI_VERSION 600
+ * 600 = round 6 (regression targets out of the label kernel, list encode / decode, fused small-map records);
+ * 610 = the RPN loss (aabr_rpn_loss_*, aabr_sample_list, aabr_smooth_l1_*). */
+#define AABR_ABI_VERSION 610
 int aabr_version(void);
 /* Tuning knobs for experiments and tests (no counterpart in the reference; the defaults are what ships): CONV_WIDE,
  * CONV_WIDE_BF16 (0 = never / 1 = whenever supported), WIDE_ROWS, WIDE_NBUF, CONV_WLDS,
@@ -828,6 +829,70 @@ int aabr_roi_align_rotated_3d_sparse_backward(const float *grad_output, int chan
                                               const float *rois, int64_t num_rois, float spatial_scale,
                                               int pooled_h, int pooled_w, int pooled_z, int sampling_ratio,
                                               int64_t V, float *d_feats, void *stream);
+
+/* ---- RPN loss (csrc/rpn_loss.hip): RPNLossComputation.__call__ (modeling/rpn/loss_3d.py:201-251), one objectness group.
+ * Per example the BalancedPositiveNegativeSampler (modeling/balanced_positive_negative_sampler.py:19-68):
+ *   num_pos = min(P, num_pos_max), num_neg = min(N, batch_size_per_image - num_pos), num_pos_max = int(B * f);
+ * then, over the batch's N_s = sum of num_pos + num_neg sampled anchors,
+ *   box_loss = sum over sampled positives and 7 components of smoothL1(|pred - target|) / N_s,
+ *              smoothL1(d) = 0.5 d^2 / beta if d < beta else d - 0.5 beta  (layers/smooth_l1_loss.py:34-52, 'Diff'),
+ *   obj_loss = sum over sampled anchors of max(x,0) - x y + log1p(exp(-|x|)) / N_s  (y = 1 positive, 0 negative).
+ * N_s == 0 gives NaN for both (0 / 0, the reference's mean of nothing) and zero gradients.
+ *
+ * Labels: matched indices as aabr_rpn_label_generation writes them, >= 0 positive, -1 negative, -2 ignored.
+ * Index mapping (nothing concatenated): anchor (example b, map m, row r of b's sites in m, yaw a) is
+ *   objectness / regression element (site_begin[b][m] + r) * A + a of map m ([V_m * A] / [V_m * A, 7], the grid's row order),
+ *   label / regression-target element seg_begin[b][m] + r * A + a of example b's lists (label_ptrs[b] int64 [N_b],
+ *   target_ptrs[b] fp32 [N_b, 7]),
+ * with seg_begin_host [nb][n_maps + 1] / site_begin_host [nb][n_maps] the tables aabr_rpn_label_generation_targets takes.
+ *
+ * Selection rule.  fmix32 = murmur3's 32-bit finaliser (h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35;
+ * h ^= h >> 16).  Anchor key: h = fmix32(seed ^ 0x9E3779B9), then h = fmix32(h ^ v) for v in (example, map, x, y, z, a)
+ * in that order, x y z = the site's coordinates (columns 0..2 of the map's coords), example = index in the call.  The
+ * sample of a class is its k anchors with the smallest (key, map, x, y, z, a), compared lexicographically: a uniform
+ * random subset per seed, the same anchors whatever the grid's row order.
+ *
+ * Outputs: selected int64 [nb][batch_size_per_image] = indices into the concatenation of the examples' label lists
+ * (example-major), positives then negatives, each in selection order, -1 padded; info int32 [nb][8] = num_pos, num_neg,
+ * P, N, candidates pos / neg, overflow (never set for a list of < 2^31 hashed keys unless > 1024 - B keys share the
+ * 24-bit prefix at the cut; the sample is then not exact), N_s of the batch; obj_loss / box_loss one fp32 each.
+ * Inputs fp32 (input_bf16 = 0) or bf16 (1), every map alike; arithmetic fp32.  1 <= batch_size_per_image <= 512.
+ * Launches: 1 memset + 4 per chunk of 16 examples + 1; sums in fixed order (no float atomics): bit-identical run to run.
+ * scratch: aabr_rpn_loss_scratch_words(nb) int32, 8-byte aligned.                                                     */
+int64_t aabr_rpn_loss_scratch_words(int nb);
+int aabr_rpn_loss_forward(int n_maps, const void *const *coords_ptrs, const void *const *obj_ptrs,
+                          const void *const *reg_ptrs, int input_bf16, int num_anchors, int nb,
+                          const int32_t *seg_begin_host, const int32_t *site_begin_host, const void *const *label_ptrs,
+                          const void *const *target_ptrs, uint32_t seed, int batch_size_per_image, int num_pos_max,
+                          float beta, int64_t *selected, int32_t *info, float *obj_loss, float *box_loss,
+                          int32_t *scratch, void *stream);
+/* Gradients of the two losses: the caller zeroes grad_obj_ptrs[m] / grad_reg_ptrs[m] (input dtype, the maps' shapes);
+ * one launch per chunk of 16 examples writes (sigmoid(x) - y) / N_s * g_obj at every sampled anchor and
+ * smoothL1'(d) sign(pred - target) / N_s * g_box at every sampled positive.  g_obj / g_box: device fp32 scalars (the
+ * upstream gradients); selected / info: the forward's.                                                                */
+int aabr_rpn_loss_backward(int n_maps, const void *const *obj_ptrs, const void *const *reg_ptrs, int input_bf16,
+                           int num_anchors, int nb, const int32_t *seg_begin_host, const int32_t *site_begin_host,
+                           const void *const *target_ptrs, int batch_size_per_image, float beta,
+                           const int64_t *selected, const int32_t *info, const float *grad_obj_loss,
+                           const float *grad_box_loss, void *const *grad_obj_ptrs, void *const *grad_reg_ptrs,
+                           void *stream);
+/* List form of the sampler (BalancedPositiveNegativeSampler.__call__): label_ptrs[b] int64 [n_host[b]] with >= 1 positive,
+ * 0 negative, anything else ignored.  Same kernels and rule with key h = fmix32(seed ^ 0x9E3779B9), h = fmix32(h ^ v) for
+ * v in (example, index), ties by index.  selected / info as above (indices into the concatenated lists; info[7] = 0);
+ * pos_masks[b] / neg_masks[b] (optional, uint8 [n_host[b]], zeroed by the caller) get a 1 at every selected entry.
+ * scratch: aabr_rpn_loss_scratch_words(nb).                                                                            */
+int aabr_sample_list(int nb, const void *const *label_ptrs, const int64_t *n_host, uint32_t seed,
+                     int batch_size_per_image, int num_pos_max, int64_t *selected, int32_t *info,
+                     void *const *pos_masks, void *const *neg_masks, int32_t *scratch, void *stream);
+/* smooth_l1_loss (layers/smooth_l1_loss.py:34-52, yaw mode 'Diff': the same term on all 7 columns) on n elements:
+ * out = sum smoothL1(|input - target|) / divisor (n for size_average, 1 for the sum), fixed-order reduction;
+ * backward: grad_input = smoothL1'(d) sign(input - target) * grad_out / divisor.  input fp32 / bf16, target fp32.
+ * scratch: aabr_smooth_l1_scratch_floats() fp32.                                                                      */
+int64_t aabr_smooth_l1_scratch_floats(void);
+int aabr_smooth_l1_forward(const void *input, const float *target, int64_t n, int input_bf16, float beta, float divisor,
+                           float *out, float *scratch, void *stream);
+int aabr_smooth_l1_backward(const void *input, const float *target, int64_t n, int input_bf16, float beta, float divisor,
+                            const float *grad_out, void *grad_input, void *stream);
 
 #ifdef __cplusplus
 }
