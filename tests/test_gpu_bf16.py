@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import fp64_yardstick as Y
 import oracle_lib as O
 import synth_scenes as S
 
@@ -129,6 +130,9 @@ def test_strided_conv_and_deconv_bf16(fs, st, nIn, nOut):
 
 @pytest.mark.parametrize("planes,leak", [(32, 0.0), (64, 0.333), (256, 0.0), (10, 0.1)])
 def test_batchnorm_bf16_forward_backward(planes, leak):
+    """against the fp64 yardstick (tests/fp64_yardstick.py) on the bf16 values the device read: every stored output and
+    input gradient the round-to-nearest-even bf16 of a value within the kernel's counted fp32 slack of exact; the
+    statistics, running statistics and parameter gradients (fp32 from fp64 sums) within their counted fp32 roundings"""
     scn = _scn()
     rng = np.random.default_rng(250 + planes)
     coords, feats = _rand_scene(rng, 6000, (24, 24, 8), 2, planes)
@@ -140,20 +144,22 @@ def test_batchnorm_bf16_forward_backward(planes, leak):
     w, b = bn.weight.detach().cpu().numpy(), bn.bias.detach().cpu().numpy()
     y = bn(x)
     assert y.features.dtype == torch.bfloat16
-    il = O.input_layer(coords, feats, 4)
-    xin = _bf(il["out"])
-    out, sm, si, rm, rv = O.bn_fwd(xin, w, b, np.zeros(planes), np.ones(planes), 1e-4, 0.95, True, leak)
+    xin = leaf.detach().double().cpu().numpy()
+    assert xin.shape[0] > 2048                                    # the three-launch path
+    sm, si = (t.cpu().numpy() for t in y.features.grad_fn.saved_tensors[6:8])
+    ex = Y.bn_forward_exact(xin, w, b, 1e-4, 0.95, leak)
+    Y.assert_bf16_rounded(y.features, ex["out"], ex["slack"], "forward")
+    for got, want, tol in ((sm, ex["mean"], ex["tol_mean"]), (si, ex["invstd"], ex["tol_invstd"]),
+                           (bn.running_mean.cpu().numpy(), ex["running_mean"], ex["tol_rm"]),
+                           (bn.running_var.cpu().numpy(), ex["running_var"], ex["tol_rv"])):
+        assert (np.abs(got - want) <= tol).all(), np.abs(got - want).max()
     yd = y.features.detach().float().cpu().numpy()
-    # statistics: fp64 partials on the device vs sequential fp32 in the oracle; then one bf16 rounding
-    np.testing.assert_allclose(yd, out, rtol=1.1 * BF16_EPS + 1e-3, atol=3e-4)
-    np.testing.assert_allclose(bn.running_mean.cpu().numpy(), rm, rtol=1e-4, atol=1e-5)
-    np.testing.assert_allclose(bn.running_var.cpu().numpy(), rv, rtol=1e-3)
-    g = _bf(rng.standard_normal(out.shape).astype(np.float32))
+    g = _bf(rng.standard_normal(yd.shape).astype(np.float32))
     y.features.backward(_t(g).to(torch.bfloat16))
-    d_in, dw, db, _ = O.bn_bwd(xin, yd, g, sm, si, w, leak)  # masks from the device's stored output
-    np.testing.assert_allclose(bn.weight.grad.cpu().numpy(), dw, rtol=2e-3, atol=2e-3)
-    np.testing.assert_allclose(bn.bias.grad.cpu().numpy(), db, rtol=2e-3, atol=2e-3)
-    np.testing.assert_allclose(leaf.grad.float().cpu().numpy(), d_in, rtol=1.1 * BF16_EPS + 2e-3, atol=6e-4)
+    exb = Y.bn_backward_exact(xin, yd, g, sm, si, w, leak)      # masks from the device's stored output
+    Y.assert_bf16_rounded(leaf.grad, exb["d_in"], exb["slack"], "d_in")
+    assert (np.abs(bn.weight.grad.cpu().numpy() - exb["dw"]) <= exb["tol_dw"]).all()
+    assert (np.abs(bn.bias.grad.cpu().numpy() - exb["db"]) <= exb["tol_db"]).all()
 
 
 def test_bf16_rejects_unaligned_planes_and_mixed_dtypes():
