@@ -9,6 +9,7 @@ pre-zeroed.  What differs by design: all grid state (hash tables, site lists, ru
 lives in HBM inside `Metadata_3`, nothing is rebuilt or copied per layer, and every kernel
 runs on the current PyTorch HIP stream.
 """
+import collections
 import ctypes as C
 
 import torch
@@ -1271,12 +1272,13 @@ def _conv_fwd(inp, out, n_rows_out, gather, weight, bias, flags, pack_t=None):
     if w.dtype != torch.float32:
         raise TypeError("convolution weights are fp32 master parameters, got %s" % w.dtype)
     bf16 = inp.dtype == torch.bfloat16
-    if narrow_ok(n_in, n_out, inp.size(0), n_rows_out, gather.vol, bf16):
+    route = conv_route(n_in, n_out, inp.size(0), n_rows_out, gather.vol, bf16)
+    if route.kind == "narrow":
         # 32 -> 32 planes: all offsets' weights in LDS, 16 output rows per wave in registers, straight from the gather
         # table (csrc/conv_narrow.hip) -- no weight pack, no block stream
         fn = lib.aabr_conv_forward_narrow_bf16 if bf16 else lib.aabr_conv_forward_narrow
-        check(fn(ptr(inp), inp.size(0), ptr(out), n_rows_out, ptr(gather.table), gather.vol, ptr(w), ptr(_opt(bias)),
-                 flags & 3, stream()))
+        check(fn(ptr(inp), inp.size(0), ptr(out), n_rows_out, ptr(route.stream(gather)), gather.vol, ptr(w),
+                 ptr(_opt(bias)), flags & 3, stream()))
         if trace is not None:
             trace.append(("fwd", n_in, n_out, gather, inp.size(0), flags & 3, inp.dtype))
         return n_out
@@ -1306,33 +1308,30 @@ def _conv_fwd(inp, out, n_rows_out, gather, weight, bias, flags, pack_t=None):
             flags |= 4
     if not (flags & 4) and n_rows_out > 0:
         pack_stats["own"] += 1                               # this call packs its weights itself
-    tile_rows = wide_tile_rows(n_in, n_out, inp.size(0), n_rows_out, gather.vol, bf16, bool(flags & 4))
-    if tile_rows and bf16:
-        check(lib.aabr_conv_forward_wide_bf16(ptr(inp), n_in, inp.size(0), ptr(out), n_out, n_rows_out,
-                                              ptr(gather.blocks_wide(tile_rows)), tile_rows, gather.vol,
-                                              ptr(_opt(bias)), flags & 3, ptr(wpack), stream()))
-    elif tile_rows:
+        # (the route above was asked for a packed weight: ahead of the pack, as the narrow kernel takes none)
+        route = conv_route(n_in, n_out, inp.size(0), n_rows_out, gather.vol, bf16, prepacked=False)
+    T, P = route.tile_rows, route.parts
+    if route.kind in ("wide", "split") and not (flags & 4):      # (fp32 storage: bf16 comes here packed only)
+        # the LAUNCH's (n_in, n_out): for a transposed launch these are (w.size(3), w.size(2))
+        check(lib.aabr_conv_pack_weights(ptr(w), gather.vol, n_in, n_out, flags & 1, ptr(wpack), stream()))
+    blocks = ptr(route.stream(gather))
+    if route.kind == "wide":
         # wide layer: big tiles, weights shared per offset (csrc/conv_wide.hip)
-        if not (flags & 4):   # the LAUNCH's (n_in, n_out): for a transposed launch these are (w.size(3), w.size(2))
-            check(lib.aabr_conv_pack_weights(ptr(w), gather.vol, n_in, n_out, flags & 1, ptr(wpack), stream()))
-        check(lib.aabr_conv_forward_wide(ptr(inp), n_in, inp.size(0), ptr(out), n_out, n_rows_out,
-                                         ptr(gather.blocks_wide(tile_rows)), tile_rows, gather.vol, ptr(_opt(bias)),
-                                         flags & 3, ptr(wpack), stream()))
-    elif (not bf16 or (flags & 4)) and wide_split(n_in, n_out, inp.size(0), n_rows_out, gather.vol, bf16):
-        T, P = wide_split(n_in, n_out, inp.size(0), n_rows_out, gather.vol, bf16)
+        fn = lib.aabr_conv_forward_wide_bf16 if bf16 else lib.aabr_conv_forward_wide
+        check(fn(ptr(inp), n_in, inp.size(0), ptr(out), n_out, n_rows_out, blocks, T, gather.vol, ptr(_opt(bias)),
+                 flags & 3, ptr(wpack), stream()))
+    elif route.kind == "split":
         scratch = _hip.workspace("wide_split", P * n_rows_out * n_out, torch.float32, inp.device)
         if bf16:
             check(lib.aabr_conv_forward_wide_split_bf16(ptr(inp), n_in, inp.size(0), ptr(out), n_out, n_rows_out,
-                                                        ptr(gather.blocks_wide(T)), T, gather.vol, ptr(_opt(bias)),
-                                                        flags & 3, ptr(wpack), P, ptr(scratch), stream()))
+                                                        blocks, T, gather.vol, ptr(_opt(bias)), flags & 3, ptr(wpack),
+                                                        P, ptr(scratch), stream()))
         else:
-            if not (flags & 4):
-                check(lib.aabr_conv_pack_weights(ptr(w), gather.vol, n_in, n_out, flags & 1, ptr(wpack), stream()))
-            check(lib.aabr_conv_forward_wide_split(ptr(inp), n_in, inp.size(0), ptr(out), n_out, n_rows_out,
-                                                   ptr(gather.blocks_wide(T)), T, gather.vol, ptr(_opt(bias)), flags & 3,
-                                                   ptr(wpack), None, P, ptr(scratch), stream()))
+            check(lib.aabr_conv_forward_wide_split(ptr(inp), n_in, inp.size(0), ptr(out), n_out, n_rows_out, blocks,
+                                                   T, gather.vol, ptr(_opt(bias)), flags & 3, ptr(wpack), None, P,
+                                                   ptr(scratch), stream()))
     else:
-        check(conv(ptr(inp), n_in, inp.size(0), ptr(out), n_out, n_rows_out, ptr(gather.blocks()), gather.vol,
+        check(conv(ptr(inp), n_in, inp.size(0), ptr(out), n_out, n_rows_out, blocks, gather.vol,
                    ptr(w), ptr(_opt(bias)), flags, ptr(wpack), stream()))
     if trace is not None:
         trace.append(("fwd", n_in, n_out, gather, inp.size(0), flags & 3, inp.dtype))
@@ -1415,9 +1414,8 @@ class WeightPackPlan:
 
 
 def wide_tile_rows(n_in, n_out, rows_in, rows_out, vol, bf16=False, prepacked=True):
-    """rows per tile when this launch goes to the wide-layer kernel (csrc/conv_wide.hip), else 0 -- the one place the
-    layer code, the stream pre-builder and the graph executor take that decision from.  bf16 storage: only with a
-    prepacked weight (the training path always has one; a stand-alone call packs inside the 64-row-tile entry)."""
+    """rows per tile when this launch can go to the wide-layer kernel (csrc/conv_wide.hip), else 0.  bf16 storage: only
+    with a prepacked weight (the training path always has one; a stand-alone call packs inside the 64-row-tile entry)."""
     if rows_out == 0:
         return 0
     lib = _hip.load()
@@ -1427,22 +1425,64 @@ def wide_tile_rows(n_in, n_out, rows_in, rows_out, vol, bf16=False, prepacked=Tr
 
 
 def narrow_ok(n_in, n_out, rows_in, rows_out, vol, bf16):
-    """True when this launch goes to the 32 -> 32 kernel (csrc/conv_narrow.hip); asked FIRST by the layer code, the stream
-    pre-builder and the graph executor alike"""
+    """True when this launch can go to the 32 -> 32 kernel (csrc/conv_narrow.hip); asked first by `conv_route`"""
     if rows_out == 0:
         return False
     return bool(_hip.load().aabr_conv_narrow_ok(n_in, n_out, rows_in, rows_out, vol, 1 if bf16 else 0))
 
 
 def wide_split(n_in, n_out, rows_in, rows_out, vol, bf16=False):
-    """(tile_rows, parts) when this launch goes to the offset-split form of the wide kernel (coarse maps: too few
-    (tile, slab) items to fill the chip; csrc/conv_wide.hip aabr_conv_forward_wide_split), else None.  Asked after
-    `wide_tile_rows` declined; bf16 storage: with a prepacked weight only (as for the wide kernel)."""
+    """(tile_rows, parts) when this launch can go to the offset-split form of the wide kernel (coarse maps: too few
+    (tile, slab) items to fill the chip; csrc/conv_wide.hip aabr_conv_forward_wide_split), else None"""
     if rows_out == 0:
         return None
     lib = _hip.load()
     v = (lib.aabr_conv_wide_split_bf16 if bf16 else lib.aabr_conv_wide_split)(n_in, n_out, rows_in, rows_out, vol)
     return (v & 0xffff, v >> 16) if v else None
+
+
+class ConvRoute(collections.namedtuple("ConvRoute", "kind tile_rows parts bf16")):
+    """What `conv_route` decided for one forward-form launch: `kind` None (no output rows), "narrow", "wide", "split"
+    or "tiles"; `tile_rows` T of "wide" / "split" and `parts` P of "split", else 0; `bf16` the feature storage."""
+    __slots__ = ()
+
+    def stream(self, gather):
+        """the structure of `gather` the launch reads, built on first use (a launch without rows: the tile blocks)"""
+        if self.kind == "narrow":
+            return gather.table
+        if self.kind in ("wide", "split"):
+            return gather.blocks_wide(self.tile_rows)
+        return gather.blocks()
+
+    @property
+    def takes_residual(self):
+        """the launch can add a residual in its write-out (the split's second stage, k_split_reduce, adds it)"""
+        return self.kind in ("wide", "split")
+
+    def stats_parts(self, rows_out):
+        """BatchNorm partial sums the launch's write-out can form over its `rows_out` rows -- one per tile of >= 64
+        rows (a smaller WIDE_ROWS tile does not), one per workgroup of the bf16 narrow kernel -- or 0"""
+        if self.kind == "wide" and self.tile_rows >= 64:
+            return (rows_out + self.tile_rows - 1) // self.tile_rows
+        if self.kind == "narrow" and self.bf16:
+            return int(_hip.load().aabr_conv_narrow_parts(rows_out))
+        return 0
+
+
+def conv_route(n_in, n_out, rows_in, rows_out, vol, bf16, prepacked=True, residual=False):
+    """The kernel family of a forward-form launch, read by `_conv_fwd`, `compile_streams` and planExecutor alike.  In
+    order: "narrow" (the 32 -> 32 kernel, csrc/conv_narrow.hip; not when a `residual` is to ride in the write-out),
+    "wide" (k_conv_cs, csrc/conv_wide.hip), "split" (its offset-split form), "tiles" (the 64-row-tile kernels of
+    aabr_conv_forward[_bf16]); bf16 storage takes "wide" or "split" only with a `prepacked` weight."""
+    if rows_out == 0:
+        return ConvRoute(None, 0, 0, bf16)
+    if not residual and narrow_ok(n_in, n_out, rows_in, rows_out, vol, bf16):
+        return ConvRoute("narrow", 0, 0, bf16)
+    T = wide_tile_rows(n_in, n_out, rows_in, rows_out, vol, bf16, prepacked)
+    if T:
+        return ConvRoute("wide", T, 0, bf16)
+    sp = wide_split(n_in, n_out, rows_in, rows_out, vol, bf16) if (prepacked or not bf16) else None
+    return ConvRoute("split", sp[0], sp[1], bf16) if sp else ConvRoute("tiles", 0, 0, bf16)
 
 
 def _conv_dw(inp, d_out, gather, d_weight, d_bias):
@@ -1474,21 +1514,10 @@ def _conv_dw(inp, d_out, gather, d_weight, d_bias):
 
 def compile_streams(gather, rows_in, n_in, n_out, dtype, weight_grad=False):
     """Build, ahead of their first use, the block stream the forward-form launch (n_in -> n_out over `gather`) will
-    read -- the same choice `_conv_fwd` makes -- and, with `weight_grad`, the offset-pair lists of the dW kernel."""
+    read (its `conv_route`, for a prepacked weight) -- and, with `weight_grad`, the offset-pair lists of the dW kernel."""
     if gather is None or gather.rows == 0:
         return
-    if narrow_ok(n_in, n_out, rows_in, gather.rows, gather.vol, dtype == torch.bfloat16):   # reads the gather table itself
-        if weight_grad:
-            gather.pairs()
-        return
-    tile_rows = wide_tile_rows(n_in, n_out, rows_in, gather.rows, gather.vol, dtype == torch.bfloat16)
-    sp = None if tile_rows else wide_split(n_in, n_out, rows_in, gather.rows, gather.vol, dtype == torch.bfloat16)
-    if tile_rows:
-        gather.blocks_wide(tile_rows)
-    elif sp:
-        gather.blocks_wide(sp[0])
-    else:
-        gather.blocks()
+    conv_route(n_in, n_out, rows_in, gather.rows, gather.vol, dtype == torch.bfloat16).stream(gather)
     if weight_grad:
         gather.pairs()
 

@@ -20,6 +20,7 @@ Two stages, so that a pass costs little Python:
 What it buys: the ~25 us of interpreter + autograd work per layer and direction leave the critical path.  What it
 does not do: change any number -- `tests/test_gpu_fpn.py` holds it bit-equal to the module path.  Falls back
 (returns None) when a module of the graph carries hooks or is of a type it does not know."""
+import functools
 import struct
 
 import torch
@@ -456,64 +457,37 @@ class _Pass(object):
                 tb = md.getSubmanifoldRuleBook(*args) if kind == "s" else md.getRuleBook(*args)
             bk.append((tb.out, tb.inn if tb.inn is not None else tb.out, tb))
         self.books = bk
-        self._wide = {}
+        self.route = functools.lru_cache(maxsize=None)(SCN.conv_route)   # {launch shape: its ConvRoute} of the pass
         self._tmp = []
 
-    def wide_rows(self, n_in, n_out, rows_in, rows_out, vol, bf=False):
-        key = (n_in, n_out, rows_in, rows_out, vol, bf)
-        T = self._wide.get(key)
-        if T is None:
-            T = self._wide[key] = SCN.wide_tile_rows(n_in, n_out, rows_in, rows_out, vol, bf)
-        return T
-
-    def split_of(self, n_in, n_out, rows_in, rows_out, vol, bf=False):
-        key = ("split", n_in, n_out, rows_in, rows_out, vol, bf)
-        v = self._wide.get(key, 0)
-        if v == 0:
-            v = self._wide[key] = SCN.wide_split(n_in, n_out, rows_in, rows_out, vol, bf) or ()
-        return v or None
-
-    def res_ok(self, n_in, n_out, rows_in, rows_out, vol, bf=False):
-        """a launch that can add a residual in its write-out: the wide kernel, or the offset split (its second stage,
-        k_split_reduce, adds it)"""
-        return bool(self.wide_rows(n_in, n_out, rows_in, rows_out, vol, bf) or
-                    self.split_of(n_in, n_out, rows_in, rows_out, vol, bf))
-
-    def conv_launch(self, pack, buf, off, src, rows_in, n_in, dst, rows_out, n_out, gather, p_w, p_pack, flags, bf,
+    def conv_launch(self, route, pack, buf, off, src, rows_in, n_in, dst, rows_out, n_out, gather, p_w, p_pack, flags,
                     xf=0, res=0):
-        """the record of the launch SCN._conv_fwd makes for a prepacked weight; returns the new write offset"""
-        self._lw = 0      # tile rows when the record is a K_WIDE one (its write-out can form BatchNorm statistics)
-        if rows_out == 0:
-            return off
-        if not res and SCN.narrow_ok(n_in, n_out, rows_in, rows_out, gather.vol, bf):
-            # 32 -> 32 planes from the gather table, raw weights (csrc/conv_narrow.hip): the choice SCN._conv_fwd makes first
-            pack(buf, off, K_NARROW, xf | (F_BF16 if bf else 0), n_in, n_out, gather.vol, flags & 3, 0, 0, 0.0, 0.0, 0.0,
-                 0.0, rows_in, rows_out, 0, 0, src, dst, gather.table.data_ptr(), p_w, 0, 0, 0, 0, 0, 0, 0, 0)
-            if bf and narrow_stats:   # its write-out can form BatchNorm statistics too: one part per workgroup (negative = a part COUNT)
-                self._lw = -int(self.lib.aabr_conv_narrow_parts(rows_out))
-            return off + 176
-        T = self.wide_rows(n_in, n_out, rows_in, rows_out, gather.vol, bf)
-        self._lw = T
-        sp = None if T else self.split_of(n_in, n_out, rows_in, rows_out, gather.vol, bf)
-        assert T or sp or not res
-        if T:
-            pack(buf, off, K_WIDE, xf | (F_BF16 if bf else 0), n_in, n_out, gather.vol, flags & 3, T, 0, 0.0, 0.0, 0.0,
-                 0.0, rows_in, rows_out, 0, 0, src, dst, gather.blocks_wide(T).data_ptr(), res, 0, p_pack, 0, 0, 0, 0,
-                 0, 0)
-        elif sp:       # coarse map: the wide kernel cut into parts over the filter offsets (fp32 storage)
-            Ts, P = sp
+        """the record of the launch SCN._conv_fwd makes for a prepacked weight along `route`; returns the new write
+        offset and the BatchNorm partial sums its write-out can form for the record behind it (the narrow kernel's
+        with AABR_PLAN_NARROW_STATS only), or 0"""
+        assert route.takes_residual or not res
+        if route.kind is None:
+            return off, 0
+        xf |= F_BF16 if route.bf16 else 0
+        blocks = route.stream(gather).data_ptr()
+        if route.kind == "narrow":        # from the gather table, raw weights
+            pack(buf, off, K_NARROW, xf, n_in, n_out, gather.vol, flags & 3, 0, 0, 0.0, 0.0, 0.0, 0.0, rows_in, rows_out,
+                 0, 0, src, dst, blocks, p_w, 0, 0, 0, 0, 0, 0, 0, 0)
+        elif route.kind == "wide":
+            pack(buf, off, K_WIDE, xf, n_in, n_out, gather.vol, flags & 3, route.tile_rows, 0, 0.0, 0.0, 0.0, 0.0,
+                 rows_in, rows_out, 0, 0, src, dst, blocks, res, 0, p_pack, 0, 0, 0, 0, 0, 0)
+        elif route.kind == "split":       # coarse map: the wide kernel cut into parts over the filter offsets
             # its own scratch per record: the list is launched later in ONE call, so a shared grow-only workspace could
             # be reallocated under records already written (the allocator frees it in stream order once the pass's
             # next list is built)
-            tmp = torch.empty(P * rows_out * n_out, dtype=torch.float32, device=self.dev)
+            tmp = torch.empty(route.parts * rows_out * n_out, dtype=torch.float32, device=self.dev)
             self._tmp.append(tmp)
-            ws = tmp.data_ptr()
-            pack(buf, off, K_WSPLIT, xf | (F_BF16 if bf else 0), n_in, n_out, gather.vol, flags & 3, Ts, P, 0.0, 0.0, 0.0, 0.0, rows_in, rows_out,
-                 0, 0, src, dst, gather.blocks_wide(Ts).data_ptr(), res, 0, p_pack, ws, 0, 0, 0, 0, 0)
+            pack(buf, off, K_WSPLIT, xf, n_in, n_out, gather.vol, flags & 3, route.tile_rows, route.parts, 0.0, 0.0,
+                 0.0, 0.0, rows_in, rows_out, 0, 0, src, dst, blocks, res, 0, p_pack, tmp.data_ptr(), 0, 0, 0, 0, 0)
         else:
-            pack(buf, off, K_CONV, (F_BF16 if bf else 0) | xf, n_in, n_out, gather.vol, flags | 4, 0, 0, 0.0, 0.0, 0.0, 0.0,
-                 rows_in, rows_out, 0, 0, src, dst, gather.blocks().data_ptr(), p_w, 0, p_pack, 0, 0, 0, 0, 0, 0)
-        return off + 176
+            pack(buf, off, K_CONV, xf, n_in, n_out, gather.vol, flags | 4, 0, 0, 0.0, 0.0, 0.0, 0.0, rows_in, rows_out,
+                 0, 0, src, dst, blocks, p_w, 0, p_pack, 0, 0, 0, 0, 0, 0)
+        return off + 176, route.stats_parts(rows_out) if (narrow_stats or route.kind != "narrow") else 0
 
     def _live_offsets(self):
         """arena offsets for a pass nobody will differentiate (torch.no_grad): a buffer's bytes are handed on once its
@@ -529,8 +503,8 @@ class _Pass(object):
             if kind == "conv":
                 x, y, lvl, lo, n_in, n_out, book, side = op[1:9]
                 fz = fuse.get(id(op))
-                if fz is not None and V[lo] and self.res_ok(n_in, n_out, V[lvl], V[lo], books[book][side].vol,
-                                                            fbufs[x][2] == BF16):
+                if fz is not None and self.route(n_in, n_out, V[lvl], V[lo], books[book][side].vol, fbufs[x][2] == BF16,
+                                                 residual=True).takes_residual:
                     add_op, other = fz
                     skip.add(id(add_op))
                     steps.append(((x, other), add_op[3]))
@@ -612,7 +586,7 @@ class _Pass(object):
         # BatchNorm statistics from the producing convolution's write-out: a training-mode BatchNorm that is the NEXT
         # record on its stream after the k_conv_cs launch that wrote its input gets the per-tile partial sums from
         # that launch (record p6 -> BatchNorm p9) and skips its own statistics pass over the matrix
-        last = {0: None, F_SIDE: None}     # per stream: (buffer index written, record offset, tile rows, planes)
+        last = {0: None, F_SIDE: None}     # per stream: (buffer index written, record offset, parts, planes)
         cstat = {}
         part, start, strm = pipeline_records * 176, 0, stream()
         for op, xf in t.emit:
@@ -631,26 +605,24 @@ class _Pass(object):
             if kind == "conv":
                 x, y, lvl, lo, n_in, n_out, book, side, p_w, pf = op[1:11]
                 fz = fuse.get(id(op))
-                bfx = fbufs[x][2] == BF16
-                if fz is not None and V[lo] and self.res_ok(n_in, n_out, V[lvl], V[lo], books[book][side].vol, bfx):
+                g, bfx, off0 = books[book][side], fbufs[x][2] == BF16, off
+                r = self.route(n_in, n_out, V[lvl], V[lo], g.vol, bfx, residual=True) if fz is not None else None
+                if r is not None and r.takes_residual:
                     add_op, other = fz           # out = conv + other, written where the add would have written
                     skip.add(id(add_op))
-                    off0 = off
-                    off = self.conv_launch(pack, buf, off, A[x], V[lvl], n_in, A[add_op[3]], V[lo], n_out,
-                                           books[book][side], p_w, pf, 0, bfx, xf, A[other])
-                    last[sk] = (add_op[3], off0, self._lw, n_out) if (self._lw >= 64 or self._lw < 0) else None
+                    y, res = add_op[3], A[other]
                 else:
-                    off0 = off
-                    off = self.conv_launch(pack, buf, off, A[x], V[lvl], n_in, A[y], V[lo], n_out, books[book][side],
-                                           p_w, pf, 0, fbufs[x][2] == BF16, xf)
-                    last[sk] = (y, off0, self._lw, n_out) if (self._lw >= 64 or self._lw < 0) else None
+                    r, res = self.route(n_in, n_out, V[lvl], V[lo], g.vol, bfx), 0
+                off, nparts = self.conv_launch(r, pack, buf, off, A[x], V[lvl], n_in, A[y], V[lo], n_out, g, p_w, pf, 0,
+                                               xf, res)
+                last[sk] = (y, off0, nparts, n_out) if nparts else None
                 continue
             elif kind == "bn":
                 _, x, y, lvl, planes, flg, train, eps, mom, leak, st, p_rm, p_rv, p_w, p_b, m = op
                 if V[lvl]:
                     parts, nparts, lw = 0, 0, last[sk]
                     if conv_bn_stats and train and lw is not None and lw[0] == x and lw[3] == planes:
-                        nparts = -lw[2] if lw[2] < 0 else (V[lvl] + lw[2] - 1) // lw[2]
+                        nparts = lw[2]
                         ws = cstat.get(sk)
                         if ws is None:   # one buffer per stream: written by the convolution, read by the very next record
                             ws = cstat[sk] = _hip.workspace("conv_stats%d" % sk, (max(V) // 64 + 1) * 2 * t.max_planes,
@@ -779,22 +751,19 @@ class _Pass(object):
             if kind == "din":
                 _, gy, gx, lo, lvl, n_in, n_out, book, side, flags, p_w, pt, flg, res, tmp = op
                 g = books[book][side]
-                last_din = None
-                if res is None:
+                last_din, bf = None, flg == F_BF16
+                r = self.route(n_in, n_out, V[lo], V[lvl], g.vol, bf, residual=res is not None)
+                if res is None or r.takes_residual:
                     off0 = off
-                    off = self.conv_launch(pack, buf, off, AD[gy[0]][gy[1]], V[lo], n_in, AD[gx[0]][gx[1]], V[lvl],
-                                           n_out, g, p_w, pt, flags, flg == F_BF16)
-                    if (self._lw >= 64 or self._lw < 0) and off > off0:
-                        last_din = (gx, off0, self._lw, n_out)
-                elif V[lvl] and self.res_ok(n_in, n_out, V[lo], V[lvl], g.vol, flg == F_BF16):
-                    off0 = off
-                    off = self.conv_launch(pack, buf, off, AD[gy[0]][gy[1]], V[lo], n_in, AD[gx[0]][gx[1]], V[lvl],
-                                           n_out, g, p_w, pt, flags, flg == F_BF16, 0, AD[res[0]][res[1]])
-                    if (self._lw >= 64 or self._lw < 0) and off > off0:
-                        last_din = (gx, off0, self._lw, n_out)
+                    off, nparts = self.conv_launch(r, pack, buf, off, AD[gy[0]][gy[1]], V[lo], n_in, AD[gx[0]][gx[1]],
+                                                   V[lvl], n_out, g, p_w, pt, flags, 0,
+                                                   AD[res[0]][res[1]] if res is not None else 0)
+                    if nparts:
+                        last_din = (gx, off0, nparts, n_out)
                 else:                    # not a wide launch: d_in into the spare buffer, then the sum
-                    off = self.conv_launch(pack, buf, off, AD[gy[0]][gy[1]], V[lo], n_in, AD[tmp[0]][tmp[1]], V[lvl],
-                                           n_out, g, p_w, pt, flags, flg == F_BF16)
+                    off, _ = self.conv_launch(self.route(n_in, n_out, V[lo], V[lvl], g.vol, bf), pack, buf, off,
+                                              AD[gy[0]][gy[1]], V[lo], n_in, AD[tmp[0]][tmp[1]], V[lvl], n_out, g, p_w,
+                                              pt, flags)
                     pack(buf, off, K_ADD, flg, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, V[lvl] * n_out, 0, 0, 0,
                          AD[res[0]][res[1]], AD[tmp[0]][tmp[1]], AD[gx[0]][gx[1]], 0, 0, 0, 0, 0, 0, 0, 0, 0)
                     off += 176
@@ -813,7 +782,7 @@ class _Pass(object):
                         # the BatchNorm's d_out was written by the wide-kernel input-gradient launch right before it (the
                         # weight-gradient record in between runs on the second stream): that launch's write-out forms the
                         # backward statistics (record i32[5] = 1, p6 stats, p7.. the BatchNorm's input and coefficients)
-                        nparts = -ld[2] if ld[2] < 0 else (V[lvl] + ld[2] - 1) // ld[2]
+                        nparts = ld[2]
                         if bstat is None:
                             bstat = _hip.workspace("conv_bwd_stats", (max(V) // 64 + 1) * 2 * t.max_planes,
                                                    torch.float64, self.dev).data_ptr()

@@ -518,7 +518,8 @@ int aabr_conv_forward_wide_split(const float *in_feats, int n_in, int64_t rows_i
                                  int flags, const float *wpack, const float *residual, int parts, float *scratch,
                                  void *stream);
 
-/* the same for bf16 feature storage (in / out / wpack bf16, parts fp32, one rounding in the second stage; no residual) */
+/* the same for bf16 feature storage (in / out / wpack bf16, parts fp32, one rounding in the second stage; the residual
+ * form is aabr_conv_forward_wide_split_bf16_res below) */
 int aabr_conv_wide_split_bf16(int n_in, int n_out, int64_t rows_in, int64_t V_out, int vol);
 int aabr_conv_forward_wide_split_bf16(const uint16_t *in_feats, int n_in, int64_t rows_in, uint16_t *out_feats, int n_out,
                                       int64_t V_out, const int32_t *blocks, int tile_rows, int vol, const float *bias,
@@ -563,10 +564,11 @@ int aabr_conv_forward_narrow_bf16_bwd_stats(const uint16_t *in_feats, int64_t ro
  *                             i64[1] V_out, p2 blocks, i32[2] vol, p3 W, p4 bias, i32[3] flags, p5 wpack)
  *        AABR_PLAN_CONV_WIDE  aabr_conv_forward_wide_stats(p0, i32[0], i64[0], p1, i32[1], i64[1], p2 blocks,
  *                             i32[4] tile_rows, i32[2] vol, p4 bias, i32[3] flags, p5 wpack, p3 residual, p6 stats);
- *                             i32[5] == 1: aabr_conv_forward_wide_bwd_stats(..., p6 stats, p7 bn_in, p8 save_mean,
- *                             p9 save_invstd, p10 bn_weight, p11 bn_bias, f32[0] leakiness); bf16 storage:
- *                             aabr_conv_forward_wide_bf16_bwd_stats(..., p6 stats, p7 bn_in, p9 bn_out, p8 save_mean,
- *                             f32[0] leakiness)
+ *                             i32[5] == 1: aabr_conv_forward_wide_bwd_stats(..., p3 residual, p6 stats, p7 bn_in,
+ *                             p8 save_mean, p9 save_invstd, p10 bn_weight, p11 bn_bias, f32[0] leakiness); bf16
+ *                             storage: aabr_conv_forward_wide_bf16_res(..., p5 wpack, p3 residual, p6 stats), with
+ *                             i32[5] == 1 also p7 bn_in, p9 bn_out, p8 save_mean, f32[0] leakiness (the backward
+ *                             statistics); p3 / p6 NULL: no residual / no statistics, in either storage
  *        AABR_PLAN_CONV_DW    aabr_conv_backward_weight[_bf16](p0 in, i32[0] n_in, p1 d_out, i32[1] n_out,
  *                             i64[0] V_out, p2 pairs, i32[2] vol, i64[1] max_chunks, p3 dW, p4 d_bias, p5 scratch)
  *        AABR_PLAN_BN_FWD     aabr_bn_forward[_bf16](p0 in, p1 out, i64[0] rows, i32[0] planes, p2 save_mean,
@@ -575,9 +577,12 @@ int aabr_conv_forward_narrow_bf16_bwd_stats(const uint16_t *in_feats, int64_t ro
  *                             aabr_bn_forward_parts[_bf16](..., p9 parts, i32[2] nparts, p8 scratch)
  *        AABR_PLAN_BN_BWD     aabr_bn_backward[_bf16](p0 in, p1 d_in, p2 out, p3 d_out, i64[0] rows, i32[0] planes,
  *                             p4 save_mean, p5 save_invstd, p6 weight, p10 bias, p7 d_weight, p8 d_bias,
- *                             f32[2] leakiness, p9 scratch); fp32 with p11 != NULL: aabr_bn_backward_add(..., p11);
- *                             i64[1] != 0: aabr_bn_backward_parts[_bf16](..., parts = (double *)i64[1], i32[1] nparts,
- *                             p9[, p11 in fp32 storage])
+ *                             f32[2] leakiness, p9 scratch) with p11 d_in_add (the gradient sum folded in; NULL: none,
+ *                             in either storage) and, i64[1] != 0, the statistics' partial sums (parts =
+ *                             (double *)i64[1], i32[1] nparts).  fp32: i64[1] != 0 ? aabr_bn_backward_parts(..., p9,
+ *                             p11) : aabr_bn_backward_add(..., p9, p11); bf16: p11 != NULL ?
+ *                             aabr_bn_backward_add_bf16(..., parts or NULL, i32[1], p9, p11) : i64[1] != 0 ?
+ *                             aabr_bn_backward_parts_bf16(..., parts, i32[1], p9) : aabr_bn_backward_bf16(..., p9)
  *        AABR_PLAN_ADD        aabr_add(p0 a, p1 b, p2 out, i64[0] n)
  *        AABR_PLAN_CAST       aabr_cast_storage(p0 in, p1 out, i64[0] n, flags & AABR_PLAN_TO_BF16)
  *   flags & AABR_PLAN_BF16 selects the bf16-storage entry point.  Stops at the first failing record and returns
@@ -589,9 +594,10 @@ int aabr_conv_forward_narrow_bf16_bwd_stats(const uint16_t *in_feats, int64_t ro
 #define AABR_PLAN_BN_BWD 5
 #define AABR_PLAN_ADD 6
 #define AABR_PLAN_CAST 7
-#define AABR_PLAN_CONV_WIDE_SPLIT 9 /* aabr_conv_forward_wide_split[_bf16](p0, i32[0], i64[0], p1, i32[1], i64[1], p2 blocks,
-                                       i32[4] tile_rows, i32[2] vol, p4 bias, i32[3] flags, p5 wpack, p3 residual (fp32
-                                       storage only), i32[5] parts, p6 scratch) */
+#define AABR_PLAN_CONV_WIDE_SPLIT 9 /* aabr_conv_forward_wide_split(p0, i32[0], i64[0], p1, i32[1], i64[1], p2 blocks,
+                                       i32[4] tile_rows, i32[2] vol, p4 bias, i32[3] flags, p5 wpack, p3 residual,
+                                       i32[5] parts, p6 scratch); bf16 storage: aabr_conv_forward_wide_split_bf16_res(
+                                       ..., p3 residual); p3 NULL: no residual, in either storage */
 #define AABR_PLAN_CONV_NARROW 10 /* aabr_conv_forward_narrow[_bf16](p0 in, i64[0] rows_in, p1 out, i64[1] V_out, p2 table,
                                    i32[2] vol, p3 W, p4 bias, i32[3] flags); bf16 storage with p6 != NULL: .._bf16_stats(.., p6
                                    stats); i32[5] == 1: .._bf16_bwd_stats(.., p6 stats, p7 bn_in, p9 bn_out, p8 save_mean,
