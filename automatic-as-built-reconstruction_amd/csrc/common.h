@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <atomic>
 #include "../../include/aabr_hip.h"
+#include "conv_tiles.h"   // kKnobUnset, ceil_div: host-only, shared with the tile-launch decision
 
 namespace aabr {
 
@@ -21,7 +22,6 @@ void set_error(const char *fmt, ...);
 #define AABR_KNOB_ENUM(n) K_##n,
 enum Knob { AABR_KNOB_LIST(AABR_KNOB_ENUM) K_COUNT };
 #undef AABR_KNOB_ENUM
-constexpr int kKnobUnset = -2147483647 - 1;
 int knob(Knob k);            // kKnobUnset when neither the environment nor aabr_set_knob gave a value
 
 #define AABR_CHECK_ARG(cond, msg)                                   \
@@ -164,6 +164,5 @@ struct SampleJob {
 int launch_sample_offsets_jobs(const SampleJob *jobs, int n, hipStream_t st);  // geometry.hip
 
 inline bool is_pow2(int64_t v) { return v > 0 && (v & (v - 1)) == 0; }
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 } // namespace aabr

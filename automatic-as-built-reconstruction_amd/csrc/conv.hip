@@ -25,11 +25,6 @@ namespace aabr {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kKC = 32; // channels per K-chunk: 4 lane groups x 8 consecutive channels
-
-__host__ __device__ inline int nkc_of(int ci) { return (ci + kKC - 1) / kKC; }
-__host__ __device__ inline int nnb_of(int co) { return (co + 15) / 16; }
-
 // Wp[k][kc][nb][lane][s] = Wl[k][kc*32 + (lane>>4)*8 + s][nb*16 + (lane&15)]   (0 outside)
 // Wl[k][c][n] = W[wk][c][n] (plain) or W[wk][n][c] (transpose), wk = flip ? vol-1-k : k.
 __global__ __launch_bounds__(256) void k_pack_weights(const float *__restrict__ W, int vol, int ci, int co,
@@ -2293,6 +2288,67 @@ extern "C" int aabr_build_offset_pairs(const int32_t *table, const int32_t *bloc
   return launch_offset_pairs_jobs(&job, 1, st);
 }
 
+// ---- the 64-row-tile launches: conv_tiles.h decides, these tables carry the decision out ---------------------------
+// One row per kernel instance the decision can return, with the name aabr_conv_last_variant reports for it; no other
+// instance of these kernels is compiled (tests/test_conv_tiles_host.py checks both against the decision).
+template <typename Fn> struct TileInst { TileKernel k; const char *name; Fn fn; };
+typedef decltype(&k_conv_blocks_mfma_wlds<1, 1, true>) WldsFn;
+typedef decltype(&k_conv_blocks_mfma_buf<1, 2, true, true>) StreamFn;   // (small, wpipe, buf)
+typedef decltype(&k_conv_blocks_mfma<1, 2, true>) GenericFn;
+typedef decltype(&k_conv_blocks_mfma_bf16<2, 2, 1, true>) Bf16Fn;
+#define AABR_WLDS(NBW, NKC, AL)                                                                                 \
+  {{kTileWlds, NBW, 0, NKC, 0, AL, false}, "k_conv_blocks_mfma_wlds<" #NBW "," #NKC "," #AL ">",                 \
+   k_conv_blocks_mfma_wlds<NBW, NKC, AL>}
+#define AABR_SMALL(WPB)                                                                                         \
+  {{kTileSmall, 0, WPB, 0, 0, false, false}, "k_conv_blocks_mfma_small<" #WPB ">", k_conv_blocks_mfma_small<WPB>}
+#define AABR_WPIPE(WPB)                                                                                         \
+  {{kTileWpipe, 4, WPB, 0, 0, false, false}, "k_conv_blocks_mfma_wpipe<4," #WPB ",true,false>",                  \
+   k_conv_blocks_mfma_wpipe<4, WPB, true, false>}
+#define AABR_BUF(NBW, WPB, AL)                                                                                  \
+  {{kTileBuf, NBW, WPB, 0, 0, AL, true}, "k_conv_blocks_mfma_buf<" #NBW "," #WPB ",true," #AL ">",               \
+   k_conv_blocks_mfma_buf<NBW, WPB, true, AL>}
+#define AABR_GENERIC(NBW, WPB, AL)                                                                              \
+  {{kTileGeneric, NBW, WPB, 0, 0, AL, false}, "k_conv_blocks_mfma<" #NBW "," #WPB "," #AL ">",                   \
+   k_conv_blocks_mfma<NBW, WPB, AL>}
+#define AABR_BF16(NBW, WPB, KG)                                                                                 \
+  {{kTileBf16, NBW, WPB, 0, KG, false, true}, "k_conv_blocks_mfma_bf16<" #NBW "," #WPB "," #KG ",true>",         \
+   k_conv_blocks_mfma_bf16<NBW, WPB, KG, true>}
+static const TileInst<WldsFn> kWlds[] = {
+    AABR_WLDS(1, 1, true), AABR_WLDS(1, 1, false), AABR_WLDS(1, 2, true), AABR_WLDS(1, 2, false),
+    AABR_WLDS(2, 1, true), AABR_WLDS(2, 1, false), AABR_WLDS(2, 2, true), AABR_WLDS(2, 2, false),
+    AABR_WLDS(4, 1, true), AABR_WLDS(4, 1, false), AABR_WLDS(4, 2, true), AABR_WLDS(4, 2, false)};
+static const TileInst<StreamFn> kStream[] = {
+    AABR_SMALL(8), AABR_SMALL(16), AABR_WPIPE(2), AABR_WPIPE(3),
+    AABR_BUF(1, 2, true), AABR_BUF(1, 3, true), AABR_BUF(1, 4, true), AABR_BUF(2, 2, true), AABR_BUF(2, 3, true),
+    AABR_BUF(2, 4, true), AABR_BUF(1, 2, false), AABR_BUF(1, 3, false), AABR_BUF(1, 4, false), AABR_BUF(2, 2, false),
+    AABR_BUF(2, 3, false), AABR_BUF(2, 4, false), AABR_BUF(4, 2, false), AABR_BUF(4, 3, false)};
+static const TileInst<GenericFn> kGeneric[] = {
+    AABR_GENERIC(1, 2, true), AABR_GENERIC(1, 3, true), AABR_GENERIC(1, 4, true), AABR_GENERIC(2, 2, true),
+    AABR_GENERIC(2, 3, true), AABR_GENERIC(2, 4, true), AABR_GENERIC(4, 2, true), AABR_GENERIC(4, 3, true),
+    AABR_GENERIC(1, 2, false), AABR_GENERIC(1, 3, false), AABR_GENERIC(1, 4, false), AABR_GENERIC(2, 2, false),
+    AABR_GENERIC(2, 3, false), AABR_GENERIC(2, 4, false), AABR_GENERIC(4, 2, false), AABR_GENERIC(4, 3, false)};
+static const TileInst<Bf16Fn> kBf16[] = {
+    AABR_BF16(2, 2, 1), AABR_BF16(2, 2, 2), AABR_BF16(2, 2, 4), AABR_BF16(2, 3, 1), AABR_BF16(2, 3, 2),
+    AABR_BF16(2, 3, 4), AABR_BF16(2, 4, 1), AABR_BF16(2, 4, 2), AABR_BF16(2, 4, 4), AABR_BF16(4, 2, 1),
+    AABR_BF16(4, 2, 2), AABR_BF16(4, 2, 4), AABR_BF16(4, 3, 1), AABR_BF16(4, 3, 2), AABR_BF16(4, 3, 4)};
+
+template <typename Fn, size_t N>
+static const TileInst<Fn> *tile_inst(const TileInst<Fn> (&tab)[N], const TileLaunch &t) {
+  for (const TileInst<Fn> &e : tab)
+    if (e.k == t.k) return &e;
+  return nullptr;
+}
+
+template <typename Fn, typename... A>
+static void launch_tile(const TileInst<Fn> &e, const TileLaunch &t, hipStream_t st, A... args) {
+  g_last_variant = e.name;
+  hipLaunchKernelGGL(e.fn, dim3((unsigned)t.grid_x, (unsigned)t.grid_y), dim3(t.block), (size_t)t.lds, st, args...);
+}
+
+static TileKnobs tile_knobs() {
+  return {knob(K_CONV_WLDS), knob(K_CONV_SMALL), knob(K_SMALL_WPB), knob(K_SMALL_MAX), knob(K_CONV_NBW), knob(K_CONV_WPB)};
+}
+
 extern "C" int aabr_conv_forward(const float *in_feats, int n_in, int64_t rows_in, float *out_feats, int n_out,
                                  int64_t V_out, const int32_t *blocks, int vol, const float *W, const float *bias,
                                  int flags, float *wpack, void *stream_) {
@@ -2305,172 +2361,26 @@ extern "C" int aabr_conv_forward(const float *in_feats, int n_in, int64_t rows_i
                      ((uintptr_t)wpack & 15) == 0,
                  "feature / scratch pointers must be 16-byte aligned");
   const int transpose = flags & 1, flip = ((flags >> 1) & 1) | ((flags >> 8) << 8);
-  const int nkc = nkc_of(n_in), nnb = nnb_of(n_out);
-  int64_t total = (int64_t)vol * nkc * nnb * 512;
+  const int64_t total = (int64_t)vol * nkc_of(n_in) * nnb_of(n_out) * 512;
   if (!(flags & 4)) // bit2: wpack already holds the packed weights of this (W, flags & 1) pair
     hipLaunchKernelGGL(k_pack_weights, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, W, vol, n_in,
                        n_out, transpose, 0, wpack);
-  const bool aligned = (n_in % kKC) == 0;
-  // WPB waves share the blocks of one 64-row tile.  Pick the split that minimises
-  // (rounds of resident workgroups) x (blocks per wave): a grid one workgroup larger than what
-  // fits on the chip at once would otherwise pay a whole second round.
-  // lean buffer-descriptor kernel: aligned channels and every buffer below 2 GiB (32-bit offsets)
   const int64_t in_bytes = rows_in * n_in * 4, wp_bytes = total * 4,
                 words_bytes = aabr_tile_blocks_words(V_out, vol) * 4;
-  const bool lean_any = in_bytes < (1ll << 31) && wp_bytes < (1ll << 31) && words_bytes < (1ll << 31) && !(flags >> 8);
-  const bool lean = aligned && lean_any;
-  // LDS-resident weights: the slab's packed filter bank + enough per-wave output tiles fit in 160 KiB
-  if (nkc <= 2 && in_bytes < (1ll << 31) && words_bytes < (1ll << 31) && !(flags >> 8)) {
-    const int kv = knob(K_CONV_WLDS);          // tuning experiments only: 0 disables, 1/2/4 forces the slab width
-    const int forced = kv == kKnobUnset ? -1 : kv;
-    const int64_t ntiles = ceil_div(V_out, 64);
-    // Measured (tools_conv_bench.py, S80k and 1.5 M points): 16-column slabs with 8 waves per CU beat
-    // wider slabs (fewer waves fit beside the larger filter bank) and beat the streaming kernel when the
-    // layer is at least 64 planes wide; narrow layers (<= 32 output planes) stay on the streaming kernel.
-    int nbw = 0, nw = 0;
-    for (int cand = 1; cand <= 4; cand <<= 1) {
-      if (forced > 0 ? cand != forced : (cand != 1 || nnb < 4)) continue;
-      if (cand > 1 && cand / 2 >= nnb) continue; // no wider than the layer
-      const int64_t w_lds = (int64_t)vol * nkc * cand * 2048, tile_lds = (int64_t)64 * cand * 16 * 4;
-      int64_t fit = (160 * 1024 - w_lds) / tile_lds;
-      if (fit > 8) fit = 8; // 512 threads: two waves per SIMD, 256 VGPRs each
-      if (fit < 4) continue;
-      nbw = cand; nw = (int)fit;
-      break;
-    }
-    if (nbw > 0 && forced != 0) {
-      const int64_t slabs = ceil_div(nnb, nbw);
-      const int64_t w_lds = (int64_t)vol * nkc * nbw * 2048, tile_lds = (int64_t)64 * nbw * 16 * 4;
-      int64_t wgx = ceil_div(ntiles, nw);
-      const int64_t cap = 256 / slabs > 0 ? 256 / slabs : 1; // persistent: about one workgroup per CU
-      if (wgx > cap) wgx = cap;
-      // a small tile count spreads over more CUs with fewer waves each
-      while (nw > 4 && wgx < cap && ceil_div(ntiles, nw - 1) <= cap) { --nw; wgx = ceil_div(ntiles, nw); }
-      const size_t lds = (size_t)(w_lds + nw * tile_lds);
-#define AABR_LAUNCH_WLDS(NBW, NKC, AL)                                                                   \
-  do {                                                                                                   \
-    static DynLdsOnce attr_set;                                                                          \
-    AABR_CHECK_HIP(dyn_lds_once(attr_set, (const void *)k_conv_blocks_mfma_wlds<NBW, NKC, AL>, 160 * 1024)); \
-    g_last_variant = "k_conv_blocks_mfma_wlds<" #NBW "," #NKC "," #AL ">";                                \
-    hipLaunchKernelGGL((k_conv_blocks_mfma_wlds<NBW, NKC, AL>), dim3((unsigned)wgx, (unsigned)slabs),    \
-                       dim3(64 * nw), lds, st, in_feats, n_in, in_bytes, out_feats, n_out, V_out,        \
-                       blocks, words_bytes, vol, flip & 1, wpack, bias);                                 \
-  } while (0)
-#define AABR_LAUNCH_WLDS_K(NBW)                                                                          \
-  do {                                                                                                   \
-    if (nkc == 1) { if (aligned) AABR_LAUNCH_WLDS(NBW, 1, true); else AABR_LAUNCH_WLDS(NBW, 1, false); } \
-    else { if (aligned) AABR_LAUNCH_WLDS(NBW, 2, true); else AABR_LAUNCH_WLDS(NBW, 2, false); }          \
-  } while (0)
-      if (nbw == 1) AABR_LAUNCH_WLDS_K(1);
-      else if (nbw == 2) AABR_LAUNCH_WLDS_K(2);
-      else AABR_LAUNCH_WLDS_K(4);
-#undef AABR_LAUNCH_WLDS_K
-#undef AABR_LAUNCH_WLDS
-      AABR_CHECK_LAUNCH();
-      return AABR_OK;
-    }
-  }
-  // tiny rule books with wide layers (coarse FPN scales): (pair, chunk) items over 8 waves x 16-column slabs
-  {
-    const int smax = knob(K_SMALL_MAX) == kKnobUnset ? 512 : knob(K_SMALL_MAX);
-    if (lean && nkc >= 2 && ceil_div(V_out, 64) * nnb < smax && knob(K_CONV_SMALL) != 0) {   // CONV_SMALL=0 disables
-      // 16 waves per workgroup when the grid alone cannot fill the chip (each wave's chain of dependent (pair,
-      // chunk) items halves; 94 VGPRs: four waves per SIMD fit): SMALL_WPB forces 8 / 16
-      int wpb = ceil_div(V_out, 64) * nnb < 1024 ? 16 : 8;
-      if (knob(K_SMALL_WPB) == 8 || knob(K_SMALL_WPB) == 16) wpb = knob(K_SMALL_WPB);
-      const dim3 grid((unsigned)ceil_div(V_out, 64), (unsigned)nnb);
-      if (wpb == 16) {
-        g_last_variant = "k_conv_blocks_mfma_small<16>";
-        hipLaunchKernelGGL((k_conv_blocks_mfma_small<16>), grid, dim3(64 * 16), (size_t)16 * 64 * 16 * sizeof(float), st,
-                           in_feats, n_in, in_bytes, out_feats, n_out, V_out, blocks, words_bytes, vol, flip & 1, wpack,
-                           wp_bytes, bias);
-      } else {
-        g_last_variant = "k_conv_blocks_mfma_small<8>";
-        hipLaunchKernelGGL((k_conv_blocks_mfma_small<8>), grid, dim3(64 * 8), (size_t)8 * 64 * 16 * sizeof(float), st,
-                           in_feats, n_in, in_bytes, out_feats, n_out, V_out, blocks, words_bytes, vol, flip & 1, wpack,
-                           wp_bytes, bias);
-      }
-      AABR_CHECK_LAUNCH();
-      return AABR_OK;
-    }
-  }
-#define AABR_LAUNCH_CONV(NBW, WPB)                                                                      \
-  do {                                                                                                  \
-    size_t lds = (size_t)(WPB) * 64 * ((NBW)*16) * sizeof(float);                                       \
-    dim3 grid((unsigned)ceil_div(V_out, 64), (unsigned)ceil_div(nnb, (NBW)));                           \
-    g_last_variant = (lean && (NBW) == 4 && wgs >= 8192) ? "k_conv_blocks_mfma_wpipe<" #NBW "," #WPB ",true,true>" \
-                   : (lean && (NBW) == 4) ? "k_conv_blocks_mfma_wpipe<" #NBW "," #WPB ",true,false>"    \
-                   : lean ? "k_conv_blocks_mfma_buf<" #NBW "," #WPB ",true,true>"                       \
-                   : lean_any ? "k_conv_blocks_mfma_buf<" #NBW "," #WPB ",true,false>"                  \
-                   : aligned ? "k_conv_blocks_mfma<" #NBW "," #WPB ",true>"                             \
-                             : "k_conv_blocks_mfma<" #NBW "," #WPB ",false>";                           \
-    if (lean && (NBW) == 4 && wgs >= 8192)                                                              \
-      hipLaunchKernelGGL((k_conv_blocks_mfma_wpipe<NBW, WPB, true, true>), grid, dim3(64 * (WPB)), lds, st, \
-                         in_feats, n_in, in_bytes, out_feats, n_out, V_out, blocks, words_bytes, vol,   \
-                         flip & 1, wpack, wp_bytes, bias);                                              \
-    else if (lean && (NBW) == 4)                                                                        \
-      hipLaunchKernelGGL((k_conv_blocks_mfma_wpipe<NBW, WPB, true, false>), grid, dim3(64 * (WPB)), lds, st, \
-                         in_feats, n_in, in_bytes, out_feats, n_out, V_out, blocks, words_bytes, vol,   \
-                         flip & 1, wpack, wp_bytes, bias);                                              \
-    else if (lean) /* adjacent-pair weight sharing pays at every size in the streaming kernel */        \
-      hipLaunchKernelGGL((k_conv_blocks_mfma_buf<NBW, WPB, true, true>), grid, dim3(64 * (WPB)), lds, st, \
-                         in_feats, n_in, in_bytes, out_feats, n_out, V_out, blocks, words_bytes, vol,   \
-                         flip & 1, wpack, wp_bytes, bias);                                              \
-    else if (lean_any) /* same kernel with element gathers: plane counts that are not multiples of 32 */ \
-      hipLaunchKernelGGL((k_conv_blocks_mfma_buf<NBW, WPB, true, false>), grid, dim3(64 * (WPB)), lds, st, \
-                         in_feats, n_in, in_bytes, out_feats, n_out, V_out, blocks, words_bytes, vol,   \
-                         flip & 1, wpack, wp_bytes, bias);                                              \
-    else if (aligned)                                                                                   \
-      hipLaunchKernelGGL((k_conv_blocks_mfma<NBW, WPB, true>), grid, dim3(64 * (WPB)), lds, st,         \
-                         in_feats, n_in, out_feats, n_out, V_out, blocks, vol, flip, wpack, bias);      \
-    else                                                                                                \
-      hipLaunchKernelGGL((k_conv_blocks_mfma<NBW, WPB, false>), grid, dim3(64 * (WPB)), lds, st,        \
-                         in_feats, n_in, out_feats, n_out, V_out, blocks, vol, flip, wpack, bias);      \
-  } while (0)
-  // widest column slab the layer allows (fewest re-gathers of the input rows) -- unless the rule book is so
-  // small that the launch would leave most CUs idle (the coarse FPN scales: 1-50 tiles): then narrower
-  // slabs, i.e. more and shorter workgroups; at that size the gathers are latency, not bandwidth
-  int nbw = nnb <= 1 ? 1 : (nnb == 2 ? 2 : 4);
-  while (nbw > 1 && ceil_div(V_out, 64) * ceil_div(nnb, nbw) < 512) nbw >>= 1;
-  // throughput-bound launches: 32-column slabs of the streaming kernel (twice the waves per CU beside half
-  // the private LDS tile) edge out the 64-column weight-prefetch kernel: 39.4 -> 40.3 % / 41.9 -> 42.8 % of
-  // the fp32 MFMA peak at 128 / 256 planes, 1.5 M points
-  if (nbw == 4 && ceil_div(V_out, 64) * ceil_div(nnb, 4) >= 8192) nbw = 2;
-  {                                              // tuning experiments only
-    const int v = knob(K_CONV_NBW);
-    if ((v == 1 || v == 2 || v == 4) && v <= nbw) nbw = v;
-  }
-  const int64_t wgs = ceil_div(V_out, 64) * ceil_div(nnb, nbw);
-  int best_wpb = 2;
-  int64_t best_cost = -1;
-  for (int wpb = 2; wpb <= (nbw == 4 ? 3 : 4); ++wpb) {
-    int64_t lds = (int64_t)wpb * 64 * (nbw * 16) * 4;
-    int64_t per_cu = (160 * 1024) / lds;
-    int64_t wave_cap = (nbw == 4 ? 12 : 20) / wpb; // register budget: 3 (164 VGPRs, weight prefetch) resp. 5 waves per SIMD
-    if (per_cu > wave_cap) per_cu = wave_cap;
-    if (per_cu < 1) per_cu = 1;
-    int64_t rounds = ceil_div(wgs, 256 * per_cu);
-    if (lds > 64 * 1024) continue; // default dynamic-LDS limit per workgroup
-    int64_t cost = rounds * ceil_div(vol, wpb);
-    if (best_cost < 0 || cost <= best_cost) { best_cost = cost; best_wpb = wpb; }
-  }
-  {                                              // tuning experiments only
-    const int v = knob(K_CONV_WPB);
-    if (v >= 2 && v <= (nbw == 4 ? 3 : 4)) best_wpb = v;
-  }
-  if (nbw == 1) {
-    if (best_wpb == 2) AABR_LAUNCH_CONV(1, 2);
-    else if (best_wpb == 3) AABR_LAUNCH_CONV(1, 3);
-    else AABR_LAUNCH_CONV(1, 4);
-  } else if (nbw == 2) {
-    if (best_wpb == 2) AABR_LAUNCH_CONV(2, 2);
-    else if (best_wpb == 3) AABR_LAUNCH_CONV(2, 3);
-    else AABR_LAUNCH_CONV(2, 4);
+  const TileLaunch t = conv_tile_launch(n_in, n_out, V_out, vol, flags, in_bytes, wp_bytes, words_bytes, tile_knobs());
+  if (const TileInst<WldsFn> *e = tile_inst(kWlds, t)) {
+    static DynLdsOnce attr_set[sizeof(kWlds) / sizeof(kWlds[0])];
+    AABR_CHECK_HIP(dyn_lds_once(attr_set[e - kWlds], (const void *)e->fn, 160 * 1024));
+    launch_tile(*e, t, st, in_feats, n_in, in_bytes, out_feats, n_out, V_out, blocks, words_bytes, vol, flip & 1, wpack,
+                bias);
+  } else if (const TileInst<StreamFn> *e = tile_inst(kStream, t)) {
+    launch_tile(*e, t, st, in_feats, n_in, in_bytes, out_feats, n_out, V_out, blocks, words_bytes, vol, flip & 1, wpack,
+                wp_bytes, bias);
+  } else if (const TileInst<GenericFn> *e = tile_inst(kGeneric, t)) {
+    launch_tile(*e, t, st, in_feats, n_in, out_feats, n_out, V_out, blocks, vol, flip, wpack, bias);
   } else {
-    if (best_wpb == 2) AABR_LAUNCH_CONV(4, 2);
-    else AABR_LAUNCH_CONV(4, 3);
+    AABR_CHECK_ARG(false, "no kernel instance for this launch");
   }
-#undef AABR_LAUNCH_CONV
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }
@@ -2492,9 +2402,13 @@ static int conv_backward_weight_t(const T *in_feats, int n_in, const T *d_out, i
     if (d_bias) hipMemsetAsync(d_bias, 0, n_out * sizeof(float), st);
     return AABR_OK;
   }
+  // bf16 rows of 32-plane multiples at 16-byte-aligned addresses: bf16 MFMA with LDS-transposed operands
+  const bool mfma16 = sizeof(T) == 2 && n_in % 32 == 0 && n_out % 32 == 0 && ((uintptr_t)in_feats & 15) == 0 &&
+                      ((uintptr_t)d_out & 15) == 0;
+  AABR_CHECK_ARG(!mfma16 || (n_in <= 4096 && n_out <= 4096), "bad sizes");
   AABR_CHECK_ARG(in_feats && d_out && pairs && scratch && max_chunks > 0, "null pointer");
   int cb, nb, tiles;
-  dw_tiling(n_in, n_out, cb, nb, tiles);
+  dw_tiling(n_in, n_out, cb, nb, tiles);                    // (mfma16: 2 or 4 column blocks each way)
   AABR_CHECK_ARG(tiles <= 65535, "too many tiles");
   const int chunk_pairs = dw_chunk(V_out, vol, n_in, n_out);
   // an offset has at most V_out rules: with V_out <= chunk_pairs every offset is one chunk at most, workgroup x is offset
@@ -2502,12 +2416,18 @@ static int conv_backward_weight_t(const T *in_feats, int n_in, const T *d_out, i
   const int direct = V_out <= chunk_pairs ? 1 : 0;
   float *dst = direct ? dW : scratch;
   dim3 grid((unsigned)(direct ? vol : max_chunks), (unsigned)tiles);
-  const int n_wg = direct ? 0 : dw_full_workgroups(n_in, n_out, in_feats, d_out, max_chunks, vol, V_out, false);
-  if (sizeof(T) == 4 && n_wg) {
-    g_last_variant = "k_conv_dw_full_f32";
-    hipLaunchKernelGGL(k_conv_dw_full_f32, dim3((unsigned)n_wg, (unsigned)((n_in >> 7) * (n_out >> 7))), dim3(256), 0, st,
-                       reinterpret_cast<const float *>(in_feats), n_in, reinterpret_cast<const float *>(d_out), n_out,
-                       V_out, pairs, vol, scratch);
+  const int n_wg = direct ? 0 : dw_full_workgroups(n_in, n_out, in_feats, d_out, max_chunks, vol, V_out, sizeof(T) == 2);
+  if (n_wg) {                                               // (bf16: only where mfma16 holds)
+    const dim3 full_grid((unsigned)n_wg, (unsigned)((n_in >> 7) * (n_out >> 7)));
+    if constexpr (sizeof(T) == 4) {
+      g_last_variant = "k_conv_dw_full_f32";
+      hipLaunchKernelGGL(k_conv_dw_full_f32, full_grid, dim3(256), 0, st, in_feats, n_in, d_out, n_out, V_out, pairs, vol,
+                         scratch);
+    } else {
+      g_last_variant = "k_conv_dw_full_bf16";
+      hipLaunchKernelGGL(k_conv_dw_full_bf16, full_grid, dim3(256), 0, st, in_feats, n_in, d_out, n_out, V_out, pairs, vol,
+                         scratch);
+    }
     hipLaunchKernelGGL(k_conv_dw_reduce_ranges, dim3((unsigned)ceil_div(cico, 64), (unsigned)vol), dim3(256), 0, st,
                        scratch, pairs, vol, n_wg, cico, dW);
     if (d_bias) launch_col_sum<T>(d_out, V_out, n_out, d_bias, scratch, max_chunks * cico, st);
@@ -2516,6 +2436,13 @@ static int conv_backward_weight_t(const T *in_feats, int n_in, const T *d_out, i
   }
 #define AABR_LAUNCH_DW(CB, NB)                                                                           \
   do {                                                                                                   \
+    if constexpr (sizeof(T) == 2 && CB > 1 && NB > 1)                                                    \
+      if (mfma16) {                                                                                      \
+        g_last_variant = "k_conv_dw_pairs_bf16<" #CB "," #NB ">";                                        \
+        hipLaunchKernelGGL((k_conv_dw_pairs_bf16<CB, NB>), grid, dim3(256), 0, st, in_feats, n_in, d_out, n_out, \
+                           V_out, pairs, vol, chunk_pairs, dst, direct);                                 \
+        break;                                                                                           \
+      }                                                                                                  \
     g_last_variant = sizeof(T) == 4 ? "k_conv_dw_pairs<" #CB "," #NB ",float>" : "k_conv_dw_pairs<" #CB "," #NB ",bf16>"; \
     hipLaunchKernelGGL((k_conv_dw_pairs<CB, NB, T>), grid, dim3(256), 0, st, in_feats, n_in, d_out, n_out, \
                        V_out, pairs, vol, chunk_pairs, dst, direct);                                     \
@@ -2549,51 +2476,6 @@ extern "C" int aabr_conv_backward_weight_bf16(const uint16_t *in_feats, int n_in
                                               int n_out, int64_t V_out, const int32_t *pairs, int vol,
                                               int64_t max_chunks, float *dW, float *d_bias, float *scratch,
                                               void *stream_) {
-  if (n_in > 0 && n_out > 0 && n_in % 32 == 0 && n_out % 32 == 0 && V_out > 0 && max_chunks > 0 &&
-      ((uintptr_t)in_feats & 15) == 0 && ((uintptr_t)d_out & 15) == 0) {
-    // bf16 MFMA with LDS-transposed operands
-    hipStream_t st = (hipStream_t)stream_;
-    AABR_CHECK_ARG(vol > 0 && vol <= 65535 && n_in <= 4096 && n_out <= 4096, "bad sizes");
-    AABR_CHECK_ARG(in_feats && d_out && pairs && scratch && dW, "null pointer");
-    const __bf16 *in16 = reinterpret_cast<const __bf16 *>(in_feats), *do16 = reinterpret_cast<const __bf16 *>(d_out);
-    const int ncb = nnb_of(n_in), nnb = nnb_of(n_out);
-    const int cb = ncb >= 4 ? 4 : 2, nb = nnb >= 4 ? 4 : 2; // plane counts are multiples of 32
-    const int tiles = (int)(ceil_div(ncb, cb) * ceil_div(nnb, nb));
-    AABR_CHECK_ARG(tiles <= 65535, "too many tiles");
-    const int chunk_pairs = dw_chunk(V_out, vol, n_in, n_out);
-    const int64_t cico = (int64_t)n_in * n_out;
-    const int direct = V_out <= chunk_pairs ? 1 : 0;       // (as in conv_backward_weight_t)
-    float *dst = direct ? dW : scratch;
-    dim3 grid((unsigned)(direct ? vol : max_chunks), (unsigned)tiles);
-    const int n_wg = direct ? 0 : dw_full_workgroups(n_in, n_out, in_feats, d_out, max_chunks, vol, V_out, true);
-    if (n_wg) {
-      g_last_variant = "k_conv_dw_full_bf16";
-      hipLaunchKernelGGL(k_conv_dw_full_bf16, dim3((unsigned)n_wg, (unsigned)((n_in >> 7) * (n_out >> 7))), dim3(256), 0,
-                         st, in16, n_in, do16, n_out, V_out, pairs, vol, scratch);
-      hipLaunchKernelGGL(k_conv_dw_reduce_ranges, dim3((unsigned)ceil_div(cico, 64), (unsigned)vol), dim3(256), 0, st,
-                         scratch, pairs, vol, n_wg, cico, dW);
-      if (d_bias) launch_col_sum<__bf16>(do16, V_out, n_out, d_bias, scratch, max_chunks * cico, st);
-      AABR_CHECK_LAUNCH();
-      return AABR_OK;
-    }
-#define AABR_LAUNCH_DW16(CB, NB)                                                                          \
-  do {                                                                                                    \
-    g_last_variant = "k_conv_dw_pairs_bf16<" #CB "," #NB ">";                                             \
-    hipLaunchKernelGGL((k_conv_dw_pairs_bf16<CB, NB>), grid, dim3(256), 0, st, in16, n_in, do16, n_out, V_out, \
-                       pairs, vol, chunk_pairs, dst, direct);                                             \
-  } while (0)
-    if (cb == 2 && nb == 2) AABR_LAUNCH_DW16(2, 2);
-    else if (cb == 2 && nb == 4) AABR_LAUNCH_DW16(2, 4);
-    else if (cb == 4 && nb == 2) AABR_LAUNCH_DW16(4, 2);
-    else AABR_LAUNCH_DW16(4, 4);
-#undef AABR_LAUNCH_DW16
-    if (!direct)
-      hipLaunchKernelGGL(k_conv_dw_reduce, dim3((unsigned)ceil_div(cico, 64), (unsigned)vol), dim3(256), 0, st,
-                         scratch, pairs, vol, chunk_pairs, cico, dW);
-    if (d_bias) launch_col_sum<__bf16>(do16, V_out, n_out, d_bias, scratch, max_chunks * cico, st);
-    AABR_CHECK_LAUNCH();
-    return AABR_OK;
-  }
   return conv_backward_weight_t<__bf16>(reinterpret_cast<const __bf16 *>(in_feats), n_in,
                                         reinterpret_cast<const __bf16 *>(d_out), n_out, V_out, pairs, vol,
                                         max_chunks, dW, d_bias, scratch, stream_);
@@ -2616,8 +2498,7 @@ extern "C" int aabr_conv_forward_bf16(const uint16_t *in_feats, int n_in, int64_
                      ((uintptr_t)wpack & 15) == 0,
                  "feature / scratch pointers must be 16-byte aligned");
   const int transpose = flags & 1, flip = (flags >> 1) & 1;
-  const int nkc = nkc_of(n_in), nnb = nnb_of(n_out);
-  const int64_t total = (int64_t)vol * nkc * nnb * 512;
+  const int64_t total = (int64_t)vol * nkc_of(n_in) * nnb_of(n_out) * 512;
   const int64_t in_bytes = rows_in * n_in * 2, wp_bytes = total * 2,
                 words_bytes = aabr_tile_blocks_words(V_out, vol) * 4;
   AABR_CHECK_ARG(in_bytes < (1ll << 31) && wp_bytes < (1ll << 31) && words_bytes < (1ll << 31),
@@ -2626,56 +2507,11 @@ extern "C" int aabr_conv_forward_bf16(const uint16_t *in_feats, int n_in, int64_
   if (!(flags & 4))
     hipLaunchKernelGGL(k_pack_weights_bf16, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, st, W, vol, n_in,
                        n_out, transpose, wp);
-  int nbw = nnb == 2 ? 2 : 4;
-  if (nbw == 4 && ceil_div(V_out, 64) * ceil_div(nnb, 4) < 512) nbw = 2; // small rule book: more, shorter workgroups
-  {                                              // tuning experiments only
-    const int v = knob(K_CONV_NBW);
-    if ((v == 2 || v == 4) && v <= nbw) nbw = v;
-  }
-  const int kg = nkc >= 3 ? 4 : nkc;
-  const int64_t wgs = ceil_div(V_out, 64) * ceil_div(nnb, nbw);
-  int best_wpb = 2;
-  int64_t best_cost = -1;
-  for (int wpb = 2; wpb <= (nbw == 4 ? 3 : 4); ++wpb) {
-    int64_t lds = (int64_t)wpb * 64 * (nbw * 16) * 4;
-    int64_t per_cu = (160 * 1024) / lds;
-    int64_t wave_cap = 16 / wpb;
-    if (per_cu > wave_cap) per_cu = wave_cap;
-    if (per_cu < 1) per_cu = 1;
-    int64_t rounds = ceil_div(wgs, 256 * per_cu);
-    int64_t cost = rounds * ceil_div(vol, wpb);
-    if (best_cost < 0 || cost <= best_cost) { best_cost = cost; best_wpb = wpb; }
-  }
-  {                                              // tuning experiments only
-    const int v = knob(K_CONV_WPB);
-    if (v >= 2 && v <= (nbw == 4 ? 3 : 4)) best_wpb = v;
-  }
-#define AABR_LAUNCH_CONV16(NBW, WPB, KG)                                                                 \
-  do {                                                                                                   \
-    size_t lds = (size_t)(WPB) * 64 * ((NBW)*16) * sizeof(float);                                        \
-    dim3 grid((unsigned)ceil_div(V_out, 64), (unsigned)ceil_div(nnb, (NBW)));                            \
-    g_last_variant = "k_conv_blocks_mfma_bf16<" #NBW "," #WPB "," #KG ",true>";                          \
-    hipLaunchKernelGGL((k_conv_blocks_mfma_bf16<NBW, WPB, KG, true>), grid, dim3(64 * (WPB)), lds, st,   \
-                       reinterpret_cast<const __bf16 *>(in_feats), n_in, in_bytes,                       \
-                       reinterpret_cast<__bf16 *>(out_feats), n_out, V_out, blocks, words_bytes, vol,    \
-                       flip, wp, wp_bytes, bias);                                                        \
-  } while (0)
-#define AABR_LAUNCH_CONV16_KG(NBW, WPB)                                                                  \
-  do {                                                                                                   \
-    if (kg == 1) AABR_LAUNCH_CONV16(NBW, WPB, 1);                                                        \
-    else if (kg == 2) AABR_LAUNCH_CONV16(NBW, WPB, 2);                                                   \
-    else AABR_LAUNCH_CONV16(NBW, WPB, 4);                                                                \
-  } while (0)
-  if (nbw == 2) {
-    if (best_wpb == 2) AABR_LAUNCH_CONV16_KG(2, 2);
-    else if (best_wpb == 3) AABR_LAUNCH_CONV16_KG(2, 3);
-    else AABR_LAUNCH_CONV16_KG(2, 4);
-  } else {
-    if (best_wpb == 2) AABR_LAUNCH_CONV16_KG(4, 2);
-    else AABR_LAUNCH_CONV16_KG(4, 3);
-  }
-#undef AABR_LAUNCH_CONV16_KG
-#undef AABR_LAUNCH_CONV16
+  const TileLaunch t = conv_tile_launch_bf16(n_in, n_out, V_out, vol, flags, in_bytes, wp_bytes, words_bytes, tile_knobs());
+  const TileInst<Bf16Fn> *e = tile_inst(kBf16, t);
+  AABR_CHECK_ARG(e, "no kernel instance for this launch");
+  launch_tile(*e, t, st, reinterpret_cast<const __bf16 *>(in_feats), n_in, in_bytes, reinterpret_cast<__bf16 *>(out_feats),
+              n_out, V_out, blocks, words_bytes, vol, flip, (const __bf16 *)wp, wp_bytes, bias);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }
