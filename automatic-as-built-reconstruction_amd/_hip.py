@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libaabr_hip.so")
 
 _lib = None
 META_WORDS = 16
-ABI_VERSION = 610      # include/aabr_hip.h AABR_ABI_VERSION this binding (_SIGS) was written for
+ABI_VERSION = 620      # include/aabr_hip.h AABR_ABI_VERSION this binding (_SIGS) was written for
 
 _vp, _i64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 _i32p = C.POINTER(C.c_int32)
@@ -175,6 +175,10 @@ _SIGS = {
     "aabr_smooth_l1_scratch_floats": (C.c_int64, []),
     "aabr_smooth_l1_forward": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp]),
     "aabr_smooth_l1_backward": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp]),
+    "aabr_roi_post_scratch_words": (C.c_int64, [_i32, _i64, _i32, _i32]),
+    "aabr_roi_post_detections": (C.c_int, [_vp, _vp, _vp, _i32, C.POINTER(C.c_int64), _i32, _i32, _f32p, _f32, _f32,
+                                           _f32, _f32, _f32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))
 

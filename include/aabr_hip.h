@@ -35,8 +35,9 @@ const char *aabr_last_error(void);
 /* ABI version: bumped whenever a signature, a record layout or AABR_META_WORDS changes; a binding written for one value
  * must refuse a library that reports another (`_hip.load()` does).  500 = round 5 (16-word meta blocks, brick grids);
  * 600 = round 6 (regression targets out of the label kernel, list encode / decode, fused small-map records);
- * 610 = the RPN loss (aabr_rpn_loss_*, aabr_sample_list, aabr_smooth_l1_*). */
-#define AABR_ABI_VERSION 610
+ * 610 = the RPN loss (aabr_rpn_loss_*, aabr_sample_list, aabr_smooth_l1_*); 620 = the ROI box post-processor
+ * (aabr_roi_post_*). */
+#define AABR_ABI_VERSION 620
 int aabr_version(void);
 /* Tuning knobs for experiments and tests (no counterpart in the reference; the defaults are what ships): CONV_WIDE,
  * CONV_WIDE_BF16 (0 = never / 1 = whenever supported), WIDE_ROWS, WIDE_NBUF, CONV_WLDS,
@@ -899,6 +900,34 @@ int aabr_smooth_l1_forward(const void *input, const float *target, int64_t n, in
                            float *out, float *scratch, void *stream);
 int aabr_smooth_l1_backward(const void *input, const float *target, int64_t n, int input_bf16, float beta, float divisor,
                             const float *grad_out, void *grad_input, void *stream);
+
+/* ---- ROI box post-processor (csrc/roi_post.hip): PostProcessor.forward of the box head
+ * (modeling/roi_heads/box_head_3d/inference.py:44-162) for a batch of nb scenes in five launches, no host read.
+ * Inputs: class_logits fp32 [N, C] (class 0 = background), box_regression fp32 [N, 7 C] (class_specific != 0) or [N, 7]
+ * (one box per row, shared by its classes, inference.py:102-104), proposals fp32 [N, 7] yx_zb; the scenes' rows are
+ * concatenated scene-major, n_host[nb] rows each, N their sum.
+ *   prob = softmax(class_logits, -1) (:57); boxes = BoxCoder3D.decode (box_coder_3d.py:53-80: weights_host[7], clip) --
+ *   the arithmetic of aabr_box_decode; per scene and class j = 1 .. C-1 (:125-141): the rows with prob[:, j] >
+ *   score_thresh (strict), their boxes clamped for the NMS only (sizes 3:5 >= nms_min_yx, size 5 >= nms_min_z,
+ *   structures/boxlist_ops_3d.py:42-44), the pre_max best in descending score, greedy suppression by the rule of
+ *   aabr_rotate_nms_sorted (its own mask and scan code), the first post_max survivors; per scene the classes in
+ *   ascending order, each in survivor order; if there are M > detections_per_img = D > 0 of them, those with score >=
+ *   the D-th largest stay, in place (:153-161: ties at the cut all stay); D <= 0 keeps all.
+ * Equal scores are ordered by ascending proposal row, in the list and at the pre_max cut (torch.topk leaves that open).
+ * Outputs: prob [N, C] and boxes [N, C, 7] (each optional: NULL keeps it in scratch); per scene b at the fixed stride
+ * cap = (C - 1) * post_max: det_rows int64 (scene-local proposal row), det_labels int64, det_scores fp32, det_boxes
+ * [., 7] (the unclamped boxes); info int32 [nb][8] = detections kept, detections before the cut, candidates over all
+ * classes, largest candidate count of a class, largest survivor count of a class, 0, 0, 0.
+ * Limits: 2 <= C <= 32, 1 <= nb <= 16, 1 <= post_max <= pre_max <= 2048, N * C * 7 < 2^31.  A scene with no row, a class
+ * without a candidate and N = 0 are legal (empty lists).  Bit-identical run to run (no float atomics).
+ * scratch: aabr_roi_post_scratch_words(nb, largest n_host, C, pre_max) int32 words (-1: bad shape), 8-byte aligned.   */
+int64_t aabr_roi_post_scratch_words(int nb, int64_t n_max, int C, int pre_max);
+int aabr_roi_post_detections(const float *class_logits, const float *box_regression, const float *proposals, int nb,
+                             const int64_t *n_host, int C, int class_specific, const float *weights_host, float clip,
+                             float score_thresh, float nms_thresh, float nms_min_yx, float nms_min_z, int only_xy,
+                             int pre_max, int post_max, int detections_per_img, float *prob, float *boxes,
+                             int64_t *det_rows, int64_t *det_labels, float *det_scores, float *det_boxes, int32_t *info,
+                             int32_t *scratch, void *stream);
 
 #ifdef __cplusplus
 }
