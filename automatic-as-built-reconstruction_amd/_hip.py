@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libaabr_hip.so")
 
 _lib = None
 META_WORDS = 16
-ABI_VERSION = 620      # include/aabr_hip.h AABR_ABI_VERSION this binding (_SIGS) was written for
+ABI_VERSION = 630      # include/aabr_hip.h AABR_ABI_VERSION this binding (_SIGS) was written for
 
 _vp, _i64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 _i32p = C.POINTER(C.c_int32)
@@ -141,6 +141,8 @@ _SIGS = {
     "aabr_sparse_to_dense_backward": (C.c_int, [_vp, _i64, _vp, _i32, _i32p, _vp, _vp]),
     "aabr_roi_align_rotated_3d_forward": (C.c_int, [_vp, _vp, _i64, _f32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                                     _i32, _vp, _vp]),
+    "aabr_roi_align_rotated_3d_forward_batch": (C.c_int, [_vp, _vp, _i64, _f32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                                          _i32, _i32, _i32, _vp, _vp]),
     "aabr_roi_align_rotated_3d_backward": (C.c_int, [_vp, _vp, _i64, _f32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                                      _i32, _i32, _vp, _vp]),
     "aabr_roi_cellmap": (C.c_int, [_vp, _i64, _i32p, _i32, _vp, _vp]),

@@ -62,7 +62,7 @@ struct RoiGeom {
 
 template <bool BACKWARD>
 __global__ __launch_bounds__(256) void k_roi_align_rot3d(int64_t nthreads, const float *__restrict__ bottom,
-                                                         const float *__restrict__ rois, RoiGeom g,
+                                                         const float *__restrict__ rois, RoiGeom g, int B,
                                                          float *__restrict__ top, const float *__restrict__ top_diff,
                                                          float *bottom_diff) {
   for (int64_t index = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; index < nthreads;
@@ -74,6 +74,12 @@ __global__ __launch_bounds__(256) void k_roi_align_rot3d(int64_t nthreads, const
     int64_t n = index / g.pz / g.pw / g.ph / g.channels;
     const float *r = rois + n * 8;
     int b = (int)r[0];
+    // an ROI that names no sample of the input (the module crops the batch to the last OCCUPIED sample, so a trailing
+    // empty one has b >= B) is an empty sample, as in the fused kernel's b_ok: zeros forward, nothing backward
+    if (b < 0 || b >= B) {
+      if (!BACKWARD) top[index] = 0.f;
+      continue;
+    }
     float cw = r[1] * g.scale, ch = r[2] * g.scale, cz = r[3] * g.scale;
     float rw = r[4] * g.scale, rh = r[5] * g.scale, rz = r[6] * g.scale;
     float theta = (float)(r[7] * 3.14159265358979323846 / 180.0);
@@ -176,24 +182,34 @@ static int roi_geom(RoiGeom &g, int channels, int height, int width, int zsize, 
   return 0;
 }
 
-extern "C" int aabr_roi_align_rotated_3d_forward(const float *input, const float *rois, int64_t num_rois,
-                                                 float spatial_scale, int channels, int height, int width,
-                                                 int zsize, int pooled_h, int pooled_w, int pooled_z,
-                                                 int sampling_ratio, float *output, void *stream_) {
+extern "C" int aabr_roi_align_rotated_3d_forward_batch(const float *input, const float *rois, int64_t num_rois,
+                                                       float spatial_scale, int batch_size, int channels, int height,
+                                                       int width, int zsize, int pooled_h, int pooled_w, int pooled_z,
+                                                       int sampling_ratio, float *output, void *stream_) {
   RoiGeom g;
-  AABR_CHECK_ARG(num_rois >= 0 &&
+  AABR_CHECK_ARG(num_rois >= 0 && batch_size >= 0 &&
                      roi_geom(g, channels, height, width, zsize, pooled_h, pooled_w, pooled_z, sampling_ratio,
                               spatial_scale) == 0,
                  "bad geometry");
   int64_t n = num_rois * channels * pooled_h * pooled_w * pooled_z;
   if (n == 0) return AABR_OK;
-  AABR_CHECK_ARG(input && rois && output, "null pointer");
+  AABR_CHECK_ARG((input || batch_size == 0) && rois && output, "null pointer"); // empty batch: zeros, input unread
   int64_t blocks = ceil_div(n, 256);
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(k_roi_align_rot3d<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, n,
-                     input, rois, g, output, (const float *)nullptr, (float *)nullptr);
+                     input, rois, g, batch_size, output, (const float *)nullptr, (float *)nullptr);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
+}
+
+// the entry point of ABI <= 620, which is not told the batch size: every non-negative batch index is taken as valid
+extern "C" int aabr_roi_align_rotated_3d_forward(const float *input, const float *rois, int64_t num_rois,
+                                                 float spatial_scale, int channels, int height, int width,
+                                                 int zsize, int pooled_h, int pooled_w, int pooled_z,
+                                                 int sampling_ratio, float *output, void *stream_) {
+  return aabr_roi_align_rotated_3d_forward_batch(input, rois, num_rois, spatial_scale, 0x7fffffff, channels, height,
+                                                 width, zsize, pooled_h, pooled_w, pooled_z, sampling_ratio, output,
+                                                 stream_);
 }
 
 extern "C" int aabr_roi_align_rotated_3d_backward(const float *grad_output, const float *rois, int64_t num_rois,
@@ -217,7 +233,7 @@ extern "C" int aabr_roi_align_rotated_3d_backward(const float *grad_output, cons
   int64_t blocks = ceil_div(n, 256);
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(k_roi_align_rot3d<true>, dim3((unsigned)blocks), dim3(256), 0, st, n, (const float *)nullptr,
-                     rois, g, (float *)nullptr, grad_output, grad_input);
+                     rois, g, batch_size, (float *)nullptr, grad_output, grad_input);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }

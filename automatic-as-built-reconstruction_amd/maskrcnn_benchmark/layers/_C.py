@@ -20,7 +20,7 @@ def nms(dets, scores, threshold):
 def roi_align_rotated_3d_forward(input, rois, spatial_scale, pooled_height, pooled_width, pooled_zsize,
                                  sampling_ratio):
     """csrc/vision.cpp:19, csrc/cuda/ROIAlignRotated3D_cuda.cu:349-398: input [B,C,H,W,Z], rois [n,8] ->
-    [n, C, ph, pw, pz]"""
+    [n, C, ph, pw, pz].  An ROI whose batch index is outside [0, B) names an empty sample: zeros (backward: nothing)"""
     import _hip
     from _hip import ptr, stream, check
     _hip.require_gpu(input)
@@ -29,9 +29,10 @@ def roi_align_rotated_3d_forward(input, rois, spatial_scale, pooled_height, pool
     B, Cc, H, W, Z = inp.shape
     out = torch.empty((r.size(0), Cc, int(pooled_height), int(pooled_width), int(pooled_zsize)), dtype=torch.float32,
                       device=inp.device)
-    check(_hip.load().aabr_roi_align_rotated_3d_forward(ptr(inp), ptr(r), r.size(0), float(spatial_scale), Cc, H, W,
-                                                        Z, int(pooled_height), int(pooled_width), int(pooled_zsize),
-                                                        int(sampling_ratio), ptr(out), stream()))
+    check(_hip.load().aabr_roi_align_rotated_3d_forward_batch(ptr(inp), ptr(r), r.size(0), float(spatial_scale), B, Cc,
+                                                              H, W, Z, int(pooled_height), int(pooled_width),
+                                                              int(pooled_zsize), int(sampling_ratio), ptr(out),
+                                                              stream()))
     return out
 
 

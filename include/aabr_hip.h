@@ -36,8 +36,8 @@ const char *aabr_last_error(void);
  * must refuse a library that reports another (`_hip.load()` does).  500 = round 5 (16-word meta blocks, brick grids);
  * 600 = round 6 (regression targets out of the label kernel, list encode / decode, fused small-map records);
  * 610 = the RPN loss (aabr_rpn_loss_*, aabr_sample_list, aabr_smooth_l1_*); 620 = the ROI box post-processor
- * (aabr_roi_post_*). */
-#define AABR_ABI_VERSION 620
+ * (aabr_roi_post_*); 630 = aabr_roi_align_rotated_3d_forward_batch (the dense ROI-align forward told the batch size). */
+#define AABR_ABI_VERSION 630
 int aabr_version(void);
 /* Tuning knobs for experiments and tests (no counterpart in the reference; the defaults are what ships): CONV_WIDE,
  * CONV_WIDE_BF16 (0 = never / 1 = whenever supported), WIDE_ROWS, WIDE_NBUF, CONV_WLDS,
@@ -808,7 +808,15 @@ int aabr_sparse_to_dense_backward(const int32_t *site_coords, int64_t V, float *
 /* `_C.roi_align_rotated_3d_forward / _backward` (maskrcnn_benchmark/csrc/vision.cpp:19-20,
  * csrc/cuda/ROIAlignRotated3D_cuda.cu:89-346): input [B,C,H,W,Z], rois [n,8] = (batch, center_w,
  * center_h, center_z, width, height, zsize, theta in degrees), output [n,C,ph,pw,pz].  The backward
- * zero-fills grad_input and accumulates with fp32 atomics, as the reference does.                   */
+ * zero-fills grad_input and accumulates with fp32 atomics, as the reference does.
+ * An ROI whose batch index is negative or >= batch_size names an empty sample (ROIAlignRotated3D crops the batch to the
+ * last occupied sample): its outputs are zero, it adds nothing backward, and nothing outside the tensors is touched --
+ * the same rule as the fused sparse form below.  `_forward` without a batch size is the entry point of ABI <= 620: it
+ * applies the rule to negative indices only and takes every other index as valid; new callers use `_forward_batch`. */
+int aabr_roi_align_rotated_3d_forward_batch(const float *input, const float *rois, int64_t num_rois,
+                                            float spatial_scale, int batch_size, int channels, int height, int width,
+                                            int zsize, int pooled_h, int pooled_w, int pooled_z, int sampling_ratio,
+                                            float *output, void *stream);
 int aabr_roi_align_rotated_3d_forward(const float *input, const float *rois, int64_t num_rois,
                                       float spatial_scale, int channels, int height, int width, int zsize,
                                       int pooled_h, int pooled_w, int pooled_z, int sampling_ratio,
