@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libaabr_hip.so")
 
 _lib = None
 META_WORDS = 16
-ABI_VERSION = 630      # include/aabr_hip.h AABR_ABI_VERSION this binding (_SIGS) was written for
+ABI_VERSION = 640      # include/aabr_hip.h AABR_ABI_VERSION this binding (_SIGS) was written for
 
 _vp, _i64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 _i32p = C.POINTER(C.c_int32)
@@ -181,6 +181,13 @@ _SIGS = {
     "aabr_roi_post_detections": (C.c_int, [_vp, _vp, _vp, _i32, C.POINTER(C.c_int64), _i32, _i32, _f32p, _f32, _f32,
                                            _f32, _f32, _f32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp]),
+    "aabr_roi_targets_scratch_words": (C.c_int64, [_i32]),
+    "aabr_roi_targets": (C.c_int, [_vp, _vp, _vp, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _f32p, _i32, _i32,
+                                   _f32, _f32, _f32p, C.c_uint32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp]),
+    "aabr_roi_box_loss_scratch_floats": (C.c_int64, []),
+    "aabr_roi_box_loss_forward": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "aabr_roi_box_loss_backward": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))
 

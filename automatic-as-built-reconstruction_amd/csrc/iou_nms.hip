@@ -420,26 +420,6 @@ struct RpnLabelParams {
 };
 constexpr int kLabelTgtChunk = 128;
 
-// BoxCoder3D.encode_centroid_box (modeling/box_coder_3d.py:46-51) = second_box_encode(targets, anchors, smooth_dim=True)
-// (second/pytorch/core/box_torch_ops.py:82-116; both boxes split positionally as x, y, z, w, l, h, r), the yaw difference
-// wrapped by limit_period(., 0.5, pi) (utils3d/geometric_torch.py:4-10), times the coder's weights -- the same fp32
-// operations in the same order as the torch expressions (no contraction: -ffp-contract=off)
-__device__ __forceinline__ void box_encode7(const float *g, const float *a, const float *w, float *o) {
-  const float diagonal = sqrtf(a[4] * a[4] + a[3] * a[3]);
-  float e[7];
-  e[0] = (g[0] - a[0]) / diagonal;
-  e[1] = (g[1] - a[1]) / diagonal;
-  e[2] = (g[2] - a[2]) / a[5];
-  e[3] = g[3] / a[3] - 1.0f;
-  e[4] = g[4] / a[4] - 1.0f;
-  e[5] = g[5] / a[5] - 1.0f;
-  const float kPi = 3.14159274101257324f;             // (float)math.pi
-  const float rt = g[6] - a[6];
-  e[6] = rt - floorf(rt / kPi + 0.5f) * kPi;
-#pragma unroll
-  for (int d = 0; d < 7; ++d) o[d] = e[d] * w[d];
-}
-
 // order-preserving float -> uint32 key (0 = below every float): the row maxima are reduced with integer atomicMax
 __device__ __forceinline__ uint32_t label_key(float v) {
   const uint32_t u = __float_as_uint(v);

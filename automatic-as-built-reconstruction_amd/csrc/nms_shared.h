@@ -1,7 +1,8 @@
 // nms_shared.h -- device code that more than one translation unit runs and that must give the same bits in each:
-// the tile of the rotated suppression mask, the greedy scan of one sorted list, and the box decode of BoxCoder3D.
-// iou_nms.hip wraps them into the one-list entry points (aabr_rotate_nms_sorted, aabr_box_decode); roi_post.hip runs the
-// same bodies over many (scene, class) lists in one launch.  Nothing here is copied: both files call these functions.
+// the tile of the rotated suppression mask, the greedy scan of one sorted list, and the box decode / encode of BoxCoder3D.
+// iou_nms.hip wraps them into the one-list entry points (aabr_rotate_nms_sorted, aabr_box_decode, aabr_box_encode);
+// roi_post.hip runs the mask, scan and decode over many (scene, class) lists in one launch, roi_loss.hip the encode per
+// proposal.  Nothing here is copied: both files call these functions.
 #pragma once
 #include "common.h"
 #include "iou_math.h"
@@ -29,6 +30,26 @@ __device__ __forceinline__ void box_decode7(const float *__restrict__ enc, const
   const float period = 3.14159274101257324f;
   const float rg = e[6] + an[6];
   o[6] = rg - floorf(rg / period + 0.5f) * period;
+}
+
+// BoxCoder3D.encode_centroid_box (modeling/box_coder_3d.py:46-51) = second_box_encode(targets, anchors, smooth_dim=True)
+// (second/pytorch/core/box_torch_ops.py:82-116; both boxes split positionally as x, y, z, w, l, h, r), the yaw difference
+// wrapped by limit_period(., 0.5, pi) (utils3d/geometric_torch.py:4-10), times the coder's weights -- the same fp32
+// operations in the same order as the torch expressions (no contraction: -ffp-contract=off)
+__device__ __forceinline__ void box_encode7(const float *g, const float *a, const float *w, float *o) {
+  const float diagonal = sqrtf(a[4] * a[4] + a[3] * a[3]);
+  float e[7];
+  e[0] = (g[0] - a[0]) / diagonal;
+  e[1] = (g[1] - a[1]) / diagonal;
+  e[2] = (g[2] - a[2]) / a[5];
+  e[3] = g[3] / a[3] - 1.0f;
+  e[4] = g[4] / a[4] - 1.0f;
+  e[5] = g[5] / a[5] - 1.0f;
+  const float kPi = 3.14159274101257324f;             // (float)math.pi
+  const float rt = g[6] - a[6];
+  e[6] = rt - floorf(rt / kPi + 0.5f) * kPi;
+#pragma unroll
+  for (int d = 0; d < 7; ++d) o[d] = e[d] * w[d];
 }
 
 // Rotated boxes, round 4.  The decision of the reference's loop is `pre-filter matrix > 0 and exact polygon IoU >=

@@ -1,0 +1,431 @@
+// roi_loss.hip -- the training half of the box head: FastRCNNLossComputation (modeling/roi_heads/box_head_3d/loss.py:137-382,
+// the non-separated path) in two stages, mirroring its `subsample` and `__call__`.
+//
+// Stage 1, aabr_roi_targets (loss.py:163-293).  The reference loops over the scenes and, per scene, materialises the
+// [G, n] IoU matrix, takes torch.max, gathers the matched boxes, encodes, runs the sampler (two nonzero + two randperm)
+// and a third nonzero for the compaction.  Here, for the whole batch (<= 16 scenes):
+//   R1 k_roi_match     16 lanes per proposal (wave64, 256 threads = 16 proposals per workgroup, grid.y = scene): the
+//                      scene's ground-truth boxes pass through LDS in chunks of 128 (thickness clamps applied once per
+//                      box when staged), the 16 lanes share a chunk's boxes, every pair goes through iou_eval_entry and
+//                      the z-overlap factor -- the arithmetic of aabr_boxes_iou_3d -- and the lanes' running maxima are
+//                      folded across the wave into the first maximum (a NaN entry wins, as in torch.max); then the
+//                      Matcher's two thresholds, the label and BoxCoder3D.encode (box_encode7, the function behind
+//                      aabr_box_encode) against the matched box.  The matrix is stored only when the caller asks for it.
+//   S1..S4             the sampler over the labels: K1 .. K4 of sample_shared.h, the code aabr_sample_list runs
+//                      (list form: key over (seed, scene, row); >= 1 positive, 0 negative, everything else ignored);
+//   R2 k_roi_compact   one workgroup per scene sorts the <= 512 selected rows ascending in LDS (bitonic) -- the order of
+//                      nonzero(pos | neg), loss.py:279-281 -- and gathers labels, regression targets and boxes.
+// 1 memset + 6 launches whatever nb, G and the class count; no host read; no float atomics.
+//
+// Stage 2, aabr_roi_box_loss_forward / _backward (loss.py:295-382): F.cross_entropy over the sampled rows and the
+// per-class smooth-L1 of the positives, both / N_s.  One thread per row: the C logits are read once (fp32 or bf16),
+// max -> sum of expf in class order -> logf; the row's seven regression columns are those of its label.  Per-thread sums in
+// row order, a fixed tree per workgroup, the workgroups' sums added in order by one thread: bit-identical run to run.
+// The backward writes every element of both gradients (zeros included), so the caller fills nothing.
+// A label outside [0, C) is never used as an index: the row is skipped and a flag word is raised.
+#include "common.h"
+#include "iou_math.h"
+#include "nms_shared.h"
+#include "sample_shared.h"
+
+namespace aabr {
+
+namespace {
+
+using namespace aabr_iou;
+
+constexpr int kRoiMaxBatch = 16;
+constexpr int kRoiTgtChunk = 128;
+constexpr int kRoiInfoWords = 8;
+constexpr int kRoiLossBlocks = 512;
+
+struct RoiTargetParams {
+  int64_t prop_begin[kRoiMaxBatch];   // first proposal row of scene b
+  int64_t gt_begin[kRoiMaxBatch];     // first ground-truth row of scene b
+  int64_t iou_begin[kRoiMaxBatch];    // first float of scene b's [G_b, n_b] matrix
+  int32_t n[kRoiMaxBatch], g[kRoiMaxBatch];
+  float aug[4];                       // target_Y, target_Z, anchor_Y, anchor_Z
+  float w[7];
+  float fg, bg;
+  int criterion, only_xy, B;
+};
+
+// kRoiLanes adjacent lanes of a wave share one proposal: lane j takes the ground-truth boxes j, j + kRoiLanes, ... of
+// every staged chunk, so the serial chain per lane is ceil(G_b / kRoiLanes) pairs and a workgroup of 256 threads serves
+// 256 / kRoiLanes proposals.  Each lane keeps the first maximum of its own ascending subsequence; the lanes' candidates
+// are then folded with roi_better, which prefers the lower index among equal values, so the result is the first maximum
+// over all G_b whatever the lane count.  A NaN entry (0 / 0 in the z factor when only_xy is off: two zero heights at the
+// same z with no thickness clamp) behaves as in torch.max / np.argmax: it wins, the first one by index, matched_val is
+// NaN and, since both threshold comparisons are false for it, the proposal is matched to that box.
+constexpr int kRoiLanes = 16;
+constexpr int kRoiPropsPerBlock = 256 / kRoiLanes;
+
+// is the candidate (ov, og) ahead of (v, g) in the order "NaN first, then larger value; lower index among equals"?
+__device__ inline bool roi_better(float ov, int og, float v, int g) {
+  if (ov != ov) return v == v || og < g;
+  return v == v && (ov > v || (ov == v && og < g));
+}
+
+__global__ __launch_bounds__(256) void k_roi_match(RoiTargetParams p, const float *__restrict__ proposals,
+                                                   const float *__restrict__ targets,
+                                                   const int64_t *__restrict__ target_labels,
+                                                   int64_t *__restrict__ matched_idx, float *__restrict__ matched_val,
+                                                   int64_t *__restrict__ labels, float *__restrict__ reg_targets,
+                                                   float *__restrict__ iou_out) {
+  __shared__ float s_t5[kRoiTgtChunk][5];
+  __shared__ float s_tz[kRoiTgtChunk][2];
+  const int b = blockIdx.y;
+  const int64_t N = p.n[b];
+  if ((int64_t)blockIdx.x * kRoiPropsPerBlock >= N) return;   // grid.x is sized for the largest scene (workgroup-uniform)
+  const int lane = threadIdx.x % kRoiLanes;
+  const int64_t t = (int64_t)blockIdx.x * kRoiPropsPerBlock + threadIdx.x / kRoiLanes;
+  const int G = p.g[b];
+  const float *tg = targets + 7 * p.gt_begin[b];
+  float an[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float a5[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, az0 = 0.f, az1 = 0.f;
+  if (t < N) {
+    const float *pr = proposals + 7 * (p.prop_begin[b] + t);
+#pragma unroll
+    for (int d = 0; d < 7; ++d) an[d] = pr[d];
+    // k_box7_to_2d on the proposal side (rotate_nms_3d_torch.py:59-66)
+    const float th = an[3] < p.aug[2] ? p.aug[2] : an[3];
+    const float h = an[5] < p.aug[3] ? p.aug[3] : an[5];
+    a5[0] = an[0]; a5[1] = an[1]; a5[2] = th; a5[3] = an[4]; a5[4] = an[6];
+    az0 = an[2]; az1 = an[2] + h;
+  }
+  float best = -__builtin_inff();
+  int best_g = 0x7fffffff;                             // (a lane that saw no box loses every fold)
+  for (int g0 = 0; g0 < G; g0 += kRoiTgtChunk) {
+    const int gn = G - g0 < kRoiTgtChunk ? G - g0 : kRoiTgtChunk;
+    __syncthreads();
+    if ((int)threadIdx.x < gn) {
+      const float *tb = tg + 7 * (int64_t)(g0 + threadIdx.x);
+      const float th = tb[3] < p.aug[0] ? p.aug[0] : tb[3];
+      const float h = tb[5] < p.aug[1] ? p.aug[1] : tb[5];
+      s_t5[threadIdx.x][0] = tb[0]; s_t5[threadIdx.x][1] = tb[1]; s_t5[threadIdx.x][2] = th;
+      s_t5[threadIdx.x][3] = tb[4]; s_t5[threadIdx.x][4] = tb[6];
+      s_tz[threadIdx.x][0] = tb[2]; s_tz[threadIdx.x][1] = tb[2] + h;
+    }
+    __syncthreads();
+    if (t < N)
+      for (int g = lane; g < gn; g += kRoiLanes) {
+        float t5[5];
+#pragma unroll
+        for (int d = 0; d < 5; ++d) t5[d] = s_t5[g][d];
+        float v = iou_eval_entry(t5, a5, p.criterion);
+        if (!p.only_xy) {
+          const float t0 = s_tz[g][0], t1 = s_tz[g][1];
+          const float overlap = fminf(az1, t1) - fmaxf(az0, t0);
+          const float common = fmaxf(az1, t1) - fminf(az0, t0);
+          v = v * (overlap / common);
+        }
+        if (iou_out) iou_out[p.iou_begin[b] + (int64_t)(g0 + g) * N + t] = v;
+        if (roi_better(v, g0 + g, best, best_g)) { best = v; best_g = g0 + g; }
+      }
+  }
+  // fold the kRoiLanes candidates of a proposal (every lane of the wave takes part; lane 0 of each group ends with the
+  // group's result, the groups being aligned runs of kRoiLanes lanes)
+#pragma unroll
+  for (int w = kRoiLanes / 2; w > 0; w >>= 1) {
+    const float ov = __shfl_xor(best, w);
+    const int og = __shfl_xor(best_g, w);
+    if (roi_better(ov, og, best, best_g)) { best = ov; best_g = og; }
+  }
+  if (t >= N || lane != 0) return;
+  const int64_t o = p.prop_begin[b] + t;
+  if (G == 0) {                                        // loss.py:200-206
+    matched_idx[o] = -1;
+    matched_val[o] = 0.f;
+    labels[o] = 0;
+#pragma unroll
+    for (int d = 0; d < 7; ++d) reg_targets[7 * o + d] = 0.f;
+    return;
+  }
+  const int64_t mi = best < p.bg ? -1 : (best < p.fg ? -2 : best_g);   // BELOW_LOW_THRESHOLD / BETWEEN_THRESHOLDS
+  matched_idx[o] = mi;
+  matched_val[o] = best;
+  labels[o] = mi >= 0 ? target_labels[p.gt_begin[b] + mi] : (mi == -1 ? 0 : -1);
+  const float *tb = tg + 7 * (mi < 0 ? 0 : mi);        // target[matched_idxs.clamp(min=0)]: the un-thickened boxes
+  float g7[7], e[7];
+#pragma unroll
+  for (int d = 0; d < 7; ++d) g7[d] = tb[d];
+  box_encode7(g7, an, p.w, e);
+#pragma unroll
+  for (int d = 0; d < 7; ++d) reg_targets[7 * o + d] = e[d];
+}
+
+// one workgroup per scene: the sampler's list (positives then negatives, selection order, indices into the batch's
+// concatenated labels) -> ascending scene-local rows, with the rows' labels, regression targets and boxes
+__global__ __launch_bounds__(256) void k_roi_compact(RoiTargetParams p, const int64_t *__restrict__ sel,
+                                                     const int32_t *__restrict__ sinfo,
+                                                     const float *__restrict__ proposals,
+                                                     const int64_t *__restrict__ labels,
+                                                     const float *__restrict__ reg_targets,
+                                                     int64_t *__restrict__ samp_rows, int64_t *__restrict__ samp_labels,
+                                                     float *__restrict__ samp_targets, float *__restrict__ samp_boxes,
+                                                     int32_t *__restrict__ info) {
+  __shared__ uint32_t s[kLossMaxB];
+  __shared__ int s_cnt;
+  const int b = blockIdx.x, t = threadIdx.x, B = p.B;
+  const int32_t *si = sinfo + b * kInfoWords;
+  const int kp = si[0], kn = si[1];
+  int n2 = 2;
+  while (n2 < kp + kn) n2 <<= 1;                       // kp + kn <= B <= 512
+  if (t == 0) s_cnt = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int i = t; i < n2; i += 256) {
+    const int64_t v = i < kp + kn ? sel[(int64_t)b * B + i] : -1;
+    s[i] = v >= 0 ? (uint32_t)(v - p.prop_begin[b]) : 0xffffffffu;   // (-1 only after the sampler's overflow)
+    mine += v >= 0;
+  }
+  if (mine) atomicAdd(&s_cnt, mine);
+  for (int size = 2; size <= n2; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (int i = t; i < n2; i += 256) {
+        const int j = i ^ stride;
+        if (j > i) {
+          const uint32_t x = s[i], y = s[j];
+          if ((y < x) == ((i & size) == 0)) { s[i] = y; s[j] = x; }
+        }
+      }
+    }
+  __syncthreads();
+  const int cnt = s_cnt;
+  for (int i = t; i < B; i += 256) {
+    const int64_t o = (int64_t)b * B + i;
+    if (i < cnt) {
+      const int64_t r = p.prop_begin[b] + s[i];
+      samp_rows[o] = s[i];
+      samp_labels[o] = labels[r];
+#pragma unroll
+      for (int d = 0; d < 7; ++d) {
+        samp_targets[7 * o + d] = reg_targets[7 * r + d];
+        samp_boxes[7 * o + d] = proposals[7 * r + d];
+      }
+    } else {
+      samp_rows[o] = -1;
+      samp_labels[o] = -1;
+#pragma unroll
+      for (int d = 0; d < 7; ++d) { samp_targets[7 * o + d] = 0.f; samp_boxes[7 * o + d] = 0.f; }
+    }
+  }
+  if (t == 0) {
+    int32_t *inf = info + b * kRoiInfoWords;
+    inf[0] = cnt; inf[1] = kp; inf[2] = kn; inf[3] = si[2]; inf[4] = si[3];
+    inf[5] = p.n[b] - si[2] - si[3]; inf[6] = si[6]; inf[7] = 0;
+  }
+}
+
+// ---- stage 2 -------------------------------------------------------------------------------------------------------
+// the softmax statistics of row i of the sampled batch
+struct RoiRow {
+  float m, s;         // maximum logit, sum of expf(x - m) in class order
+};
+__device__ inline RoiRow roi_row_softmax(const void *logits, int64_t i, int C, int bf16) {
+  RoiRow r;
+  r.m = ld(logits, i * C, bf16);
+  for (int k = 1; k < C; ++k) r.m = fmaxf(r.m, ld(logits, i * C + k, bf16));
+  r.s = 0.f;
+  for (int k = 0; k < C; ++k) r.s += expf(ld(logits, i * C + k, bf16) - r.m);
+  return r;
+}
+
+__global__ __launch_bounds__(256) void k_roi_loss_partial(const void *__restrict__ logits, const void *__restrict__ reg,
+                                                          int bf16, int64_t n, int C, int class_specific,
+                                                          const int64_t *__restrict__ labels,
+                                                          const float *__restrict__ targets, float beta,
+                                                          float *__restrict__ partial) {
+  __shared__ float s_red[2][256];
+  __shared__ int s_bad;
+  const int t = threadIdx.x;
+  if (t == 0) s_bad = 0;
+  __syncthreads();
+  float cls = 0.f, box = 0.f;
+  bool bad = false;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n; i += (int64_t)gridDim.x * 256) {
+    const int64_t l = labels[i];
+    if (l < 0 || l >= C) { bad = true; continue; }
+    const RoiRow r = roi_row_softmax(logits, i, C, bf16);
+    cls += (r.m + logf(r.s)) - ld(logits, i * C + l, bf16);
+    if (l > 0) {
+      const int64_t c0 = class_specific ? i * 7 * C + 7 * l : i * 7;
+      float row = 0.f;
+      for (int d = 0; d < 7; ++d) row += smooth_l1_term(fabsf(ld(reg, c0 + d, bf16) - targets[i * 7 + d]), beta);
+      box += row;
+    }
+  }
+  if (bad) s_bad = 1;                                  // (every writer stores the same value)
+  s_red[0][t] = cls;
+  s_red[1][t] = box;
+  for (int w = 128; w > 0; w >>= 1) {
+    __syncthreads();
+    if (t < w) { s_red[0][t] += s_red[0][t + w]; s_red[1][t] += s_red[1][t + w]; }
+  }
+  __syncthreads();
+  if (t == 0) {
+    partial[3 * blockIdx.x] = s_red[0][0];
+    partial[3 * blockIdx.x + 1] = s_red[1][0];
+    partial[3 * blockIdx.x + 2] = s_bad ? 1.f : 0.f;
+  }
+}
+
+// the workgroups' sums in workgroup order, / n (0 / 0 = NaN for an empty sample, like aabr_rpn_loss_forward)
+__global__ __launch_bounds__(64) void k_roi_loss_finalize(int nblocks, const float *__restrict__ partial, int64_t n,
+                                                          float *__restrict__ cls_loss, float *__restrict__ box_loss,
+                                                          int32_t *__restrict__ flag) {
+  if (threadIdx.x != 0) return;
+  float cls = 0.f, box = 0.f;
+  int bad = 0;
+  for (int i = 0; i < nblocks; ++i) {
+    cls += partial[3 * i];
+    box += partial[3 * i + 1];
+    bad |= partial[3 * i + 2] != 0.f;
+  }
+  *cls_loss = cls / (float)n;
+  *box_loss = box / (float)n;
+  *flag = bad;
+}
+
+// one thread per row writes the row's C logit gradients and its 7 C (or 7) regression gradients, zeros included
+__global__ __launch_bounds__(256) void k_roi_loss_backward(const void *__restrict__ logits, const void *__restrict__ reg,
+                                                           int bf16, int64_t n, int C, int class_specific,
+                                                           const int64_t *__restrict__ labels,
+                                                           const float *__restrict__ targets, float beta,
+                                                           const float *__restrict__ g_cls, const float *__restrict__ g_box,
+                                                           void *__restrict__ grad_logits, void *__restrict__ grad_reg) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t l = labels[i];
+  const bool ok = l >= 0 && l < C;
+  const int W = class_specific ? 7 * C : 7;
+  if (ok) {
+    const RoiRow r = roi_row_softmax(logits, i, C, bf16);
+    const float gc = *g_cls / (float)n;
+    for (int k = 0; k < C; ++k) {
+      const float pk = expf(ld(logits, i * C + k, bf16) - r.m) / r.s;
+      st(grad_logits, i * C + k, (pk - (k == l ? 1.f : 0.f)) * gc, bf16);
+    }
+  } else {
+    for (int k = 0; k < C; ++k) st(grad_logits, i * C + k, 0.f, bf16);
+  }
+  const int c0 = ok && l > 0 ? (class_specific ? 7 * (int)l : 0) : -7;   // first column of the row's own box, or none
+  const float gb = *g_box / (float)n;
+  for (int c = 0; c < W; ++c) {
+    float v = 0.f;
+    if (c >= c0 && c < c0 + 7 && c0 >= 0) {
+      const float diff = ld(reg, i * W + c, bf16) - targets[i * 7 + (c - c0)];
+      v = smooth_l1_grad(diff, beta) * gb;
+    }
+    st(grad_reg, i * W + c, v, bf16);
+  }
+}
+
+}  // namespace
+
+}  // namespace aabr
+
+using namespace aabr;
+
+extern "C" int64_t aabr_roi_targets_scratch_words(int nb) {
+  // the sampler's words, its selected list (int64 [nb][512]) and its info block
+  if (nb < 1 || nb > kRoiMaxBatch) return -1;
+  return aabr_rpn_loss_scratch_words(nb) + (int64_t)nb * (2 * kLossMaxB + kInfoWords) + 2;
+}
+
+extern "C" int aabr_roi_targets(const float *proposals, const float *targets, const int64_t *target_labels, int nb,
+                                const int64_t *n_host, const int64_t *g_host, const float *aug_host, int criterion,
+                                int only_xy, float fg_iou, float bg_iou, const float *weights_host, uint32_t seed,
+                                int batch_size_per_image, int num_pos_max, int64_t *matched_idx, float *matched_val,
+                                int64_t *labels, float *regression_targets, float *iou_out, int64_t *samp_rows,
+                                int64_t *samp_labels, float *samp_targets, float *samp_boxes, int32_t *info,
+                                int32_t *scratch, void *stream_) {
+  hipStream_t st = (hipStream_t)stream_;
+  AABR_CHECK_ARG(nb >= 1 && nb <= kRoiMaxBatch, "nb must be 1 .. 16");
+  AABR_CHECK_ARG(batch_size_per_image >= 1 && batch_size_per_image <= kLossMaxB && num_pos_max >= 0 &&
+                     num_pos_max <= batch_size_per_image,
+                 "need 1 <= batch_size_per_image <= 512, 0 <= num_pos_max <= batch_size_per_image");
+  AABR_CHECK_ARG(bg_iou <= fg_iou, "need bg_iou <= fg_iou");
+  AABR_CHECK_ARG(n_host && g_host && aug_host && weights_host && samp_rows && samp_labels && samp_targets && samp_boxes &&
+                     info && scratch, "null pointer");
+  AABR_CHECK_ARG(((uintptr_t)scratch & 7) == 0, "scratch must be 8-byte aligned");
+  RoiTargetParams p = {};
+  int64_t N = 0, G = 0, M = 0, nmax = 0;
+  std::vector<int32_t> seg(2 * (size_t)nb);
+  for (int b = 0; b < nb; ++b) {
+    AABR_CHECK_ARG(n_host[b] >= 0 && g_host[b] >= 0 && n_host[b] < ((int64_t)1 << 31) && g_host[b] < ((int64_t)1 << 31),
+                   "row count out of range");
+    p.prop_begin[b] = N; p.gt_begin[b] = G; p.iou_begin[b] = M;
+    p.n[b] = (int32_t)n_host[b]; p.g[b] = (int32_t)g_host[b];
+    seg[2 * b] = 0; seg[2 * b + 1] = (int32_t)n_host[b];
+    N += n_host[b]; G += g_host[b]; M += n_host[b] * g_host[b];
+    nmax = n_host[b] > nmax ? n_host[b] : nmax;
+  }
+  AABR_CHECK_ARG(N < ((int64_t)1 << 31), "more than 2^31 - 1 proposals per call");
+  AABR_CHECK_ARG(N == 0 || (proposals && matched_idx && matched_val && labels && regression_targets), "null pointer");
+  AABR_CHECK_ARG(G == 0 || (targets && target_labels), "null pointer");
+  for (int d = 0; d < 4; ++d) p.aug[d] = aug_host[d];
+  for (int d = 0; d < 7; ++d) p.w[d] = weights_host[d];
+  p.fg = fg_iou; p.bg = bg_iou; p.criterion = criterion; p.only_xy = only_xy ? 1 : 0; p.B = batch_size_per_image;
+  if (nmax > 0)
+    hipLaunchKernelGGL(k_roi_match, dim3((unsigned)ceil_div(nmax, kRoiPropsPerBlock), (unsigned)nb), dim3(256), 0, st, p,
+                       proposals, targets, target_labels, matched_idx, matched_val, labels, regression_targets, iou_out);
+  // the sampler over the labels just written: the list form of aabr_sample_list, one chunk (nb <= 16)
+  int64_t *sel = reinterpret_cast<int64_t *>(scratch + aabr_rpn_loss_scratch_words(nb) + (aabr_rpn_loss_scratch_words(nb) & 1));
+  int32_t *sinfo = reinterpret_cast<int32_t *>(sel + (int64_t)nb * kLossMaxB);
+  std::vector<const void *> label_ptrs(nb);
+  for (int b = 0; b < nb; ++b) label_ptrs[b] = n_host[b] ? (const void *)(labels + p.prop_begin[b]) : nullptr;
+  LossParams sp = {};
+  sp.n_maps = 1; sp.A = 1; sp.flat = 1; sp.with_loss = 0; sp.label_mode = 1; sp.k_pos0 = num_pos_max;
+  sp.B = batch_size_per_image; sp.seed = seed; sp.beta = 1.f;
+  int rc = run_select_chunks(sp, nb, seg.data(), nullptr, label_ptrs.data(), nullptr, nullptr, nullptr, sel, sinfo, scratch,
+                             st);
+  if (rc != AABR_OK) return rc;
+  hipLaunchKernelGGL(k_roi_compact, dim3((unsigned)nb), dim3(256), 0, st, p, sel, sinfo, proposals, labels,
+                     regression_targets, samp_rows, samp_labels, samp_targets, samp_boxes, info);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+extern "C" int64_t aabr_roi_box_loss_scratch_floats(void) { return 3 * kRoiLossBlocks; }
+
+static int roi_loss_blocks(int64_t n) {
+  int64_t nblk = ceil_div(n, 256);
+  return (int)(nblk < 1 ? 1 : (nblk > kRoiLossBlocks ? kRoiLossBlocks : nblk));
+}
+
+extern "C" int aabr_roi_box_loss_forward(const void *class_logits, const void *box_regression, int input_bf16, int64_t n,
+                                         int C, int class_specific, const int64_t *labels,
+                                         const float *regression_targets, float beta, float *cls_loss, float *box_loss,
+                                         int32_t *flag, float *scratch, void *stream_) {
+  hipStream_t st = (hipStream_t)stream_;
+  AABR_CHECK_ARG(n >= 0 && C >= 1 && beta > 0.f, "need n >= 0, C >= 1, beta > 0");
+  AABR_CHECK_ARG(n * 7 * (int64_t)C < ((int64_t)1 << 31), "n * 7 C must stay below 2^31");
+  AABR_CHECK_ARG(cls_loss && box_loss && flag && scratch, "null pointer");
+  AABR_CHECK_ARG(n == 0 || (class_logits && box_regression && labels && regression_targets), "null pointer");
+  const int nblk = roi_loss_blocks(n);
+  hipLaunchKernelGGL(k_roi_loss_partial, dim3((unsigned)nblk), dim3(256), 0, st, class_logits, box_regression,
+                     input_bf16 ? 1 : 0, n, C, class_specific ? 1 : 0, labels, regression_targets, beta, scratch);
+  hipLaunchKernelGGL(k_roi_loss_finalize, dim3(1), dim3(64), 0, st, nblk, scratch, n, cls_loss, box_loss, flag);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+extern "C" int aabr_roi_box_loss_backward(const void *class_logits, const void *box_regression, int input_bf16, int64_t n,
+                                          int C, int class_specific, const int64_t *labels,
+                                          const float *regression_targets, float beta, const float *grad_cls_loss,
+                                          const float *grad_box_loss, void *grad_logits, void *grad_regression,
+                                          void *stream_) {
+  AABR_CHECK_ARG(n >= 0 && C >= 1 && beta > 0.f, "need n >= 0, C >= 1, beta > 0");
+  AABR_CHECK_ARG(n * 7 * (int64_t)C < ((int64_t)1 << 31), "n * 7 C must stay below 2^31");
+  AABR_CHECK_ARG(grad_cls_loss && grad_box_loss, "null pointer");
+  if (n == 0) return AABR_OK;
+  AABR_CHECK_ARG(class_logits && box_regression && labels && regression_targets && grad_logits && grad_regression,
+                 "null pointer");
+  hipLaunchKernelGGL(k_roi_loss_backward, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream_,
+                     class_logits, box_regression, input_bf16 ? 1 : 0, n, C, class_specific ? 1 : 0, labels,
+                     regression_targets, beta, grad_cls_loss, grad_box_loss, grad_logits, grad_regression);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}

@@ -1,7 +1,9 @@
 """Box-head glue on the device: class logits + box regression + proposals -> final detections
 (csrc/roi_post.hip, aabr_roi_post_detections).  The counterpart of rpn_glue.rpn_proposals for the second stage:
 PostProcessor.forward of the reference (maskrcnn_benchmark/modeling/roi_heads/box_head_3d/inference.py:44-162)
-without its Python loops over scenes and classes."""
+without its Python loops over scenes and classes.  And the training half (csrc/roi_loss.hip): `box_head_targets`
+(proposals -> matched, labelled, encoded, sampled: FastRCNNLossComputation.subsample, box_head_3d/loss.py:163-293) and
+`box_head_loss` (cross-entropy + per-class smooth-L1 with autograd: FastRCNNLossComputation.__call__, loss.py:295-382)."""
 import ctypes as C
 
 import torch
@@ -87,3 +89,159 @@ def box_detections(class_logits, box_regression, proposals, score_thresh=0.05, n
         return out
 
     return finish if defer else finish()
+
+
+def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, aug_thickness=None,
+                     batch_size_per_image=500, positive_fraction=0.25, weights=None, seed=None, defer=False, debug=None):
+    """proposals / targets: lists over scenes of [n_b, 7] / [G_b, 7] yx_zb device tensors, target_labels: list of int64
+    [G_b].  Per scene what FastRCNNLossComputation.subsample does (box_head_3d/loss.py:163-293): IoU of every proposal
+    with the scene's ground truth (`boxlist_iou_3d(target, proposal, aug_thickness, criterion=-1)`), Matcher(fg_iou,
+    bg_iou, allow_low_quality_matches=False), labels (class of the match / 0 background / -1 ignored), regression targets
+    `BoxCoder3D(weights).encode(target[matched.clamp(min=0)], proposal)`, BalancedPositiveNegativeSampler(
+    batch_size_per_image, positive_fraction) by the library's hash rule (include/aabr_hip.h, aabr_sample_list), and the
+    sampled rows in ascending proposal row.  A scene without ground truth has all its proposals background; a scene
+    without proposals yields an empty sample (the reference raises there).
+
+    `aug_thickness`: dict with target_Y / target_Z / anchor_Y / anchor_Z (None: no clamps).  `seed=None` draws one from
+    torch's default CPU generator (rpn_glue.draw_seed).
+    Returns a list over scenes of dicts: rows int64 [m] (scene-local proposal rows), bbox3d [m, 7], labels int64 [m],
+    regression_targets fp32 [m, 7].  One library call (1 memset + 6 launches whatever the batch), no host read until the
+    counts are read at the end -- `defer=True` returns the function that does it, as box_detections does.  `debug` (a
+    dict) receives the per-proposal arrays `matched_idx`, `matched_val`, `labels`, `regression_targets` (scene-major
+    concatenations), `iou` (list of [G_b, n_b] matrices), `info` (after the read) and the padded `samp_*` arrays."""
+    from rpn_glue import draw_seed
+    lib = _hip.load()
+    nb = len(proposals)
+    if not (nb == len(targets) == len(target_labels)):
+        raise ValueError("proposals, targets and target_labels differ in length")
+    if nb == 0:
+        return (lambda: []) if defer else []
+    _hip.require_gpu(proposals[0])
+    dev = proposals[0].device
+    n_b = [int(p.shape[0]) for p in proposals]
+    g_b = [int(t.shape[0]) for t in targets]
+    if any(int(l.numel()) != g for l, g in zip(target_labels, g_b)):
+        raise ValueError("target_labels do not match the targets")
+    props = torch.cat([p.reshape(-1, 7) for p in proposals]).to(device=dev, dtype=torch.float32).contiguous()
+    tg = torch.cat([t.reshape(-1, 7) for t in targets]).to(device=dev, dtype=torch.float32).contiguous()
+    tl = torch.cat([l.reshape(-1) for l in target_labels]).to(device=dev, dtype=torch.int64).contiguous()
+    N, B = sum(n_b), int(batch_size_per_image)
+    aug = aug_thickness or {}
+    aug = [float(aug.get(k, 0.0)) for k in ("target_Y", "target_Z", "anchor_Y", "anchor_Z")]
+    w = (1.0,) * 7 if weights is None else [float(v) for v in torch.as_tensor(weights).reshape(-1).tolist()]
+    words = int(lib.aabr_roi_targets_scratch_words(nb))
+    if words < 0:
+        raise _hip.AabrError("box_head_targets: 1 <= scenes <= 16, got %d" % nb)
+    scratch = _hip.workspace("roi_targets", words + 2, torch.int32, dev)
+    off = (-scratch.data_ptr() // 4) % 2                                  # 8-byte alignment of the first word
+    midx = torch.empty(N, dtype=torch.int64, device=dev)
+    mval = torch.empty(N, dtype=torch.float32, device=dev)
+    labels = torch.empty(N, dtype=torch.int64, device=dev)
+    regt = torch.empty((N, 7), dtype=torch.float32, device=dev)
+    iou = torch.empty(sum(n * g for n, g in zip(n_b, g_b)), dtype=torch.float32, device=dev) if debug is not None else None
+    s_rows = torch.empty((nb, B), dtype=torch.int64, device=dev)
+    s_labels = torch.empty((nb, B), dtype=torch.int64, device=dev)
+    s_targets = torch.empty((nb, B, 7), dtype=torch.float32, device=dev)
+    s_boxes = torch.empty((nb, B, 7), dtype=torch.float32, device=dev)
+    info = torch.empty((nb, INFO_WORDS), dtype=torch.int32, device=dev)
+    seed = int(draw_seed() if seed is None else seed) & 0xffffffff
+    check(lib.aabr_roi_targets(
+        ptr(props), ptr(tg), ptr(tl), nb, _hip.i64xn(n_b), _hip.i64xn(g_b), _hip.f32x4(aug), -1,
+        int(_nms.REFERENCE_DEBUG_ONLY_XY), float(fg_iou), float(bg_iou), _hip.f32xn(w), seed, B,
+        int(B * positive_fraction), ptr(midx), ptr(mval), ptr(labels), ptr(regt), ptr(iou), ptr(s_rows), ptr(s_labels),
+        ptr(s_targets), ptr(s_boxes), ptr(info), scratch.data_ptr() + 4 * off, _hip.stream()))
+    if debug is not None:
+        debug.update(matched_idx=midx, matched_val=mval, labels=labels, regression_targets=regt, samp_rows=s_rows,
+                     samp_labels=s_labels, samp_targets=s_targets, samp_boxes=s_boxes, seed=seed)
+        mats, o = [], 0
+        for n, g in zip(n_b, g_b):
+            mats.append(iou[o:o + n * g].view(g, n))
+            o += n * g
+        debug["iou"] = mats
+
+    def finish():
+        counts = _hip.read_back(info)                                     # the one read of the stage
+        if debug is not None:
+            debug["info"] = counts
+        out = []
+        for b in range(nb):
+            m = counts[b][0]
+            out.append({"rows": s_rows[b, :m], "bbox3d": s_boxes[b, :m], "labels": s_labels[b, :m],
+                        "regression_targets": s_targets[b, :m]})
+        return out
+
+    return finish if defer else finish()
+
+
+class _BoxHeadLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, reg, labels, targets, class_specific, beta):
+        lib = _hip.load()
+        dev = logits.device
+        n, nc = int(logits.shape[0]), int(logits.shape[1])
+        logits_c, reg_c = logits.contiguous(), reg.contiguous()
+        cls_loss = torch.empty((), dtype=torch.float32, device=dev)
+        box_loss = torch.empty((), dtype=torch.float32, device=dev)
+        flag = torch.empty((), dtype=torch.int32, device=dev)
+        scr = _hip.workspace("roi_box_loss", int(lib.aabr_roi_box_loss_scratch_floats()), torch.float32, dev)
+        check(lib.aabr_roi_box_loss_forward(ptr(logits_c), ptr(reg_c), int(logits.dtype == torch.bfloat16), n, nc,
+                                            int(class_specific), ptr(labels), ptr(targets), beta, ptr(cls_loss),
+                                            ptr(box_loss), ptr(flag), ptr(scr), _hip.stream()))
+        ctx.save_for_backward(logits_c, reg_c, labels, targets)
+        ctx.cfg = (n, nc, int(class_specific), beta)
+        ctx.mark_non_differentiable(flag)
+        return cls_loss, box_loss, flag
+
+    @staticmethod
+    def backward(ctx, g_cls, g_box, _g_flag):
+        lib = _hip.load()
+        logits, reg, labels, targets = ctx.saved_tensors
+        n, nc, class_specific, beta = ctx.cfg
+        dev = logits.device
+        g_cls = (g_cls if g_cls is not None else torch.zeros((), device=dev)).float().contiguous()
+        g_box = (g_box if g_box is not None else torch.zeros((), device=dev)).float().contiguous()
+        d_logits, d_reg = torch.empty_like(logits), torch.empty_like(reg)       # the kernel writes every element
+        check(lib.aabr_roi_box_loss_backward(ptr(logits), ptr(reg), int(logits.dtype == torch.bfloat16), n, nc,
+                                             class_specific, ptr(labels), ptr(targets), beta, ptr(g_cls), ptr(g_box),
+                                             ptr(d_logits), ptr(d_reg), _hip.stream()))
+        return d_logits, d_reg, None, None, None, None
+
+
+BOX_LOSS_BETA = 1.0 / 5      # box_head_3d/loss.py:374
+
+
+def box_head_loss(class_logits, box_regression, labels, regression_targets, class_specific=None, yaw_loss_mode="Diff",
+                  return_flag=False):
+    """FastRCNNLossComputation.__call__ (box_head_3d/loss.py:295-382, the non-separated path) on the sampled rows:
+    class_logits [n, C], box_regression [n, 7 C] or [n, 7] (fp32 or bf16 alike), labels int64 [n] (0 = background),
+    regression_targets fp32 [n, 7]:
+      classification_loss = F.cross_entropy(class_logits, labels);
+      box_loss = smooth_l1_loss(box_regression[pos, 7 l .. 7 l + 6], regression_targets[pos], beta=1/5, sum) / n
+    (`labels.numel()`, not the positive count).  n == 0 gives NaN losses.  `class_specific`: None = told from the
+    regression's width.  `yaw_loss_mode`: 'Diff' / 'Diff_<w>'; 'SinDiff' raises (rpn_glue.parse_yaw_loss_mode: the
+    reference's box_loss passes a plain tensor where that mode reads `anchor.bbox3d`, so it cannot run there either).
+    Returns (classification_loss, box_loss), 0-dim fp32 device tensors with autograd to both inputs; no host read.  A
+    label outside [0, C) adds nothing, gets zero gradients and raises the flag: `return_flag=True` appends the 0-dim
+    int32 device tensor (1 = some label was out of range) for the caller to read with the losses
+    (FastRCNNLossComputation.__call__ keeps it as `last_flag`)."""
+    from rpn_glue import parse_yaw_loss_mode
+    parse_yaw_loss_mode(yaw_loss_mode)
+    _hip.require_gpu(class_logits)
+    if class_logits.dim() != 2 or box_regression.dim() != 2:
+        raise ValueError("class_logits and box_regression must be 2-D")
+    n, nc = int(class_logits.shape[0]), int(class_logits.shape[1])
+    if class_logits.dtype not in (torch.float32, torch.bfloat16) or box_regression.dtype != class_logits.dtype:
+        raise TypeError("class_logits and box_regression must both be float32, or both bfloat16")
+    if class_specific is None:
+        class_specific = box_regression.shape[1] == 7 * nc and nc != 1
+    width = 7 * nc if class_specific else 7
+    if box_regression.shape[0] != n or box_regression.shape[1] != width:
+        raise ValueError("box_regression must be [%d, %d], got %s" % (n, width, tuple(box_regression.shape)))
+    if labels.numel() != n or regression_targets.numel() != 7 * n:
+        raise ValueError("labels / regression_targets do not have %d rows" % n)
+    dev = class_logits.device
+    lab = labels.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    tgt = regression_targets.reshape(-1, 7).to(device=dev, dtype=torch.float32).contiguous()
+    cls_loss, box_loss, flag = _BoxHeadLoss.apply(class_logits, box_regression, lab, tgt, bool(class_specific),
+                                                  BOX_LOSS_BETA)
+    return (cls_loss, box_loss, flag) if return_flag else (cls_loss, box_loss)

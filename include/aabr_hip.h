@@ -36,8 +36,9 @@ const char *aabr_last_error(void);
  * must refuse a library that reports another (`_hip.load()` does).  500 = round 5 (16-word meta blocks, brick grids);
  * 600 = round 6 (regression targets out of the label kernel, list encode / decode, fused small-map records);
  * 610 = the RPN loss (aabr_rpn_loss_*, aabr_sample_list, aabr_smooth_l1_*); 620 = the ROI box post-processor
- * (aabr_roi_post_*); 630 = aabr_roi_align_rotated_3d_forward_batch (the dense ROI-align forward told the batch size). */
-#define AABR_ABI_VERSION 630
+ * (aabr_roi_post_*); 630 = aabr_roi_align_rotated_3d_forward_batch (the dense ROI-align forward told the batch size);
+ * 640 = the box head's loss (aabr_roi_targets, aabr_roi_box_loss_*). */
+#define AABR_ABI_VERSION 640
 int aabr_version(void);
 /* Tuning knobs for experiments and tests (no counterpart in the reference; the defaults are what ships): CONV_WIDE,
  * CONV_WIDE_BF16 (0 = never / 1 = whenever supported), WIDE_ROWS, WIDE_NBUF, CONV_WLDS,
@@ -936,6 +937,69 @@ int aabr_roi_post_detections(const float *class_logits, const float *box_regress
                              int pre_max, int post_max, int detections_per_img, float *prob, float *boxes,
                              int64_t *det_rows, int64_t *det_labels, float *det_scores, float *det_boxes, int32_t *info,
                              int32_t *scratch, void *stream);
+
+/* ---- Box-head loss (csrc/roi_loss.hip): FastRCNNLossComputation of the box head
+ * (modeling/roi_heads/box_head_3d/loss.py:137-382, the non-separated path) in two stages, `subsample` and `__call__`.
+ *
+ * Stage 1, aabr_roi_targets: proposals of a batch -> per-proposal match, label and regression target -> the balanced
+ * sample, for nb scenes with no host read.  proposals fp32 [N, 7] yx_zb and targets fp32 [G, 7] / target_labels int64 [G]
+ * are scene-major, n_host[b] / g_host[b] rows per scene.  Per proposal of scene b (one pass; the [G_b, n_b] matrix is
+ * stored only when iou_out is given):
+ *   IoU with every ground-truth box of the scene = boxlist_iou_3d(target, proposal, aug_thickness, criterion), the
+ *   arithmetic of aabr_boxes_iou_3d (aug_host[4] = {target_Y, target_Z, anchor_Y, anchor_Z}; loss.py:164 passes
+ *   criterion -1); the scene's boxes are staged in LDS in chunks of 128, so G_b is unbounded;
+ *   Matcher(fg_iou, bg_iou, allow_low_quality_matches=False), yaw_diff=None (loss.py:578-582, matcher.py:58-106):
+ *   matched_val = the maximum over the ground truths, matched_idx = its scene-local index (the first maximum at ties,
+ *   the rule of aabr_rpn_label_generation), -1 where matched_val < bg_iou, -2 where bg_iou <= matched_val < fg_iou;
+ *   a NaN entry (0 / 0 in the z factor: only_xy off, two zero heights at the same z, no thickness clamp) is the
+ *   maximum of its proposal, the first one by index, as in torch.max: matched_val is NaN and, both comparisons being
+ *   false, the proposal is matched to that box;
+ *   labels (loss.py:213-222) = target_labels[matched_idx] for a match, 0 for -1, -1 for -2;
+ *   regression_targets (loss.py:225-227) = BoxCoder3D.encode(target[max(matched_idx, 0)], proposal) for EVERY proposal,
+ *   bit-equal to aabr_box_encode on the same rows (weights_host[7]).
+ * A scene with G_b == 0 (loss.py:200-206): labels 0, regression targets 0, matched_idx -1, matched_val 0.  A scene with
+ * n_b == 0 is legal here and yields an empty sample (the reference's Matcher raises "No proposal boxes available").
+ * Then BalancedPositiveNegativeSampler over `labels` per scene -- the kernels and the rule of aabr_sample_list (key over
+ * (seed, scene, scene-local row); >= 1 positive, 0 negative, everything else ignored; csrc/sample_shared.h is compiled
+ * into both files) -- and the compaction of loss.py:279-281 (nonzero(pos | neg)): the sampled rows in ASCENDING
+ * proposal row, not in selection order.
+ * Outputs over all N proposals: matched_idx int64, matched_val fp32, labels int64, regression_targets fp32 [N, 7];
+ * iou_out (optional, may be NULL): the unmasked [G_b, n_b] matrices back to back.  Per scene at the fixed stride B =
+ * batch_size_per_image: samp_rows int64 (scene-local proposal rows, -1 padded), samp_labels int64 (-1 padded),
+ * samp_targets fp32 [., 7] and samp_boxes fp32 [., 7] (the proposals' rows; 0 padded); info int32 [nb][8] = sampled
+ * count, num_pos, num_neg, P, N, ignored, the sampler's overflow flag (see aabr_rpn_loss_forward), 0.
+ * Limits: 1 <= nb <= 16, 1 <= batch_size_per_image <= 512 (the sampler's), 0 <= num_pos_max <= batch_size_per_image,
+ * N < 2^31.  Launches: 1 memset + 6 kernels (match, the sampler's 4, compaction), whatever nb, G and the class count.
+ * No float atomics: bit-identical run to run.  scratch: aabr_roi_targets_scratch_words(nb) int32, 8-byte aligned.       */
+int64_t aabr_roi_targets_scratch_words(int nb);
+int aabr_roi_targets(const float *proposals, const float *targets, const int64_t *target_labels, int nb,
+                     const int64_t *n_host, const int64_t *g_host, const float *aug_host, int criterion, int only_xy,
+                     float fg_iou, float bg_iou, const float *weights_host, uint32_t seed, int batch_size_per_image,
+                     int num_pos_max, int64_t *matched_idx, float *matched_val, int64_t *labels,
+                     float *regression_targets, float *iou_out, int64_t *samp_rows, int64_t *samp_labels,
+                     float *samp_targets, float *samp_boxes, int32_t *info, int32_t *scratch, void *stream);
+/* Stage 2 (loss.py:295-382): class_logits [n, C], box_regression [n, 7 C] (class_specific != 0) or [n, 7], both fp32
+ * (input_bf16 = 0) or bf16 (1), arithmetic fp32; labels int64 [n]; regression_targets fp32 [n, 7]; beta > 0 (the
+ * reference: 1 / 5).
+ *   cls_loss = sum over the n rows of (logsumexp(x) - x[label]) / n                      (F.cross_entropy, mean)
+ *   box_loss = sum over the rows with label > 0 and 7 columns of smoothL1(|pred - target|) / n   (loss.py:369-377:
+ *              labels.numel(), not the positive count); pred = columns 7 label .. 7 label + 6 when class specific,
+ *              0 .. 6 otherwise; smoothL1 as in aabr_rpn_loss_forward.
+ * Per-row terms are added per thread in row order, per workgroup in a fixed tree, then in workgroup order: bit-identical
+ * run to run.  n == 0 gives NaN for both (0 / 0) and there is no gradient to write.  A label outside [0, C) reads nothing
+ * out of bounds: the row adds nothing to either loss, gets zero gradients, and *flag (int32) becomes 1 (0 otherwise).
+ * Launches: 2.  scratch: aabr_roi_box_loss_scratch_floats() fp32.
+ * Backward (1 launch) writes EVERY element of grad_logits [n, C] and grad_regression (the input's shape and dtype; no
+ * fill by the caller): (softmax(x) - onehot(label)) * g_cls / n, and smoothL1'(d) sign(pred - target) * g_box / n in
+ * the seven columns of a row with label > 0, exact zeros everywhere else.  g_cls / g_box: device fp32 scalars.       */
+int64_t aabr_roi_box_loss_scratch_floats(void);
+int aabr_roi_box_loss_forward(const void *class_logits, const void *box_regression, int input_bf16, int64_t n, int C,
+                              int class_specific, const int64_t *labels, const float *regression_targets, float beta,
+                              float *cls_loss, float *box_loss, int32_t *flag, float *scratch, void *stream);
+int aabr_roi_box_loss_backward(const void *class_logits, const void *box_regression, int input_bf16, int64_t n, int C,
+                               int class_specific, const int64_t *labels, const float *regression_targets, float beta,
+                               const float *grad_cls_loss, const float *grad_box_loss, void *grad_logits,
+                               void *grad_regression, void *stream);
 
 #ifdef __cplusplus
 }
