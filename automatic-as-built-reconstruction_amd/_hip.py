@@ -19,6 +19,16 @@ _vp, _i64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 _i32p = C.POINTER(C.c_int32)
 _f32p = C.POINTER(C.c_float)
 
+
+
+class AabrRoiLevel(C.Structure):
+    """include/aabr_hip.h AabrRoiLevel: one level of the multi-level ROI pooler"""
+    _fields_ = [("feats", C.c_void_p), ("cellmap", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32),
+                ("zsize", C.c_int32), ("nb", C.c_int32), ("V", C.c_int64), ("row_offset", C.c_int64),
+                ("spatial_scale", C.c_float), ("reserved", C.c_int32)]
+
+
+_lvp = C.POINTER(AabrRoiLevel)
 _SIGS = {
     "aabr_version": (C.c_int, []),
     "aabr_build_flags": (C.c_int, []),
@@ -188,6 +198,10 @@ _SIGS = {
     "aabr_roi_box_loss_scratch_floats": (C.c_int64, []),
     "aabr_roi_box_loss_forward": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
     "aabr_roi_box_loss_backward": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "aabr_roi_pool_prepare": (C.c_int, [_vp, _i32, C.POINTER(C.c_int64), _f32, _i32, _f32p, _f32, _vp, _vp, _vp]),
+    "aabr_roi_pool_forward": (C.c_int, [_lvp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "aabr_roi_pool_backward": (C.c_int, [_lvp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i64,
+                                         _vp]),
 }
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))
 

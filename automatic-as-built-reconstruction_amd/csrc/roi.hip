@@ -7,6 +7,7 @@
 // HBM-bound gathers / scatters; the ROI-align backward accumulates with no-return fp32 atomics
 // exactly like the reference (the one place in this library where summation order is not fixed).
 #include "common.h"
+#include "roi_shared.h" // RoiGeom, RoiCorner / roi_corners, kRoiPlanes, kRoiBins: shared with roi_pool.hip
 
 namespace aabr {
 
@@ -54,11 +55,6 @@ __device__ inline float trilinear(const float *__restrict__ d, int height, int w
   float w5 = hy * hx * lz, w6 = hy * lx * lz, w7 = ly * hx * lz, w8 = ly * lx * lz;
   return (w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4 + w5 * v5 + w6 * v6 + w7 * v7 + w8 * v8);
 }
-
-struct RoiGeom {
-  int channels, height, width, zsize, ph, pw, pz, sampling;
-  float scale;
-};
 
 template <bool BACKWARD>
 __global__ __launch_bounds__(256) void k_roi_align_rot3d(int64_t nthreads, const float *__restrict__ bottom,
@@ -252,44 +248,12 @@ namespace aabr {
 //   backward: same walk; only ACTIVE cells receive (coalesced, no-return) atomics, directly into the sparse
 //             gradient rows: no dense gradient tensor, no fill, ~6x fewer atomics than the dense form
 //             (which the reference also accumulates with atomics: summation order is not fixed there either).
-constexpr int kRoiPlanes = 128; // planes per workgroup (lanes)
-constexpr int kRoiBins = 96;    // bins staged in LDS per pass: 128 x 96 x 4 B = 48 KiB
-
 __global__ __launch_bounds__(256) void k_roi_cellmap(const int32_t *__restrict__ sc, int64_t V, int X, int Y, int Z,
                                                      int B, int32_t *__restrict__ cellmap) {
   int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= V) return;
   int4 c = *reinterpret_cast<const int4 *>(sc + 4 * v);
   if (c.x < X && c.y < Y && c.z < Z && c.w < B) cellmap[(((int64_t)c.w * X + c.x) * Y + c.y) * Z + c.z] = (int32_t)v;
-}
-
-// geometry of one sample point: the 8 corner cells and weights exactly as the dense kernels compute them
-struct RoiCorner { int64_t o[8]; float w[8]; bool ok; };
-
-__device__ inline RoiCorner roi_corners(const RoiGeom &g, float y, float x, float z, bool backward) {
-  RoiCorner r;
-  r.ok = !(y < -1.0f || y > g.height || x < -1.0f || x > g.width || z < -1.0f || (backward && z > g.zsize));
-  if (!r.ok) return r;
-  if (y <= 0) y = 0;
-  if (x <= 0) x = 0;
-  if (z <= 0) z = 0;
-  int y_low = (int)y, x_low = (int)x, z_low = (int)z, y_high, x_high, z_high;
-  if (y_low >= g.height - 1) { y_high = y_low = g.height - 1; y = (float)y_low; } else y_high = y_low + 1;
-  if (x_low >= g.width - 1) { x_high = x_low = g.width - 1; x = (float)x_low; } else x_high = x_low + 1;
-  if (z_low >= g.zsize - 1) { z_high = z_low = g.zsize - 1; z = (float)z_low; } else z_high = z_low + 1;
-  const float ly = y - y_low, lx = x - x_low, lz = z - z_low;
-  const float hy = 1.f - ly, hx = 1.f - lx, hz = 1.f - lz;
-  r.w[0] = hy * hx * hz; r.w[1] = hy * lx * hz; r.w[2] = ly * hx * hz; r.w[3] = ly * lx * hz;
-  r.w[4] = hy * hx * lz; r.w[5] = hy * lx * lz; r.w[6] = ly * hx * lz; r.w[7] = ly * lx * lz;
-  r.o[0] = ((int64_t)y_low * g.width + x_low) * g.zsize + z_low;
-  r.o[1] = ((int64_t)y_low * g.width + x_high) * g.zsize + z_low;
-  r.o[2] = ((int64_t)y_high * g.width + x_low) * g.zsize + z_low;
-  r.o[3] = ((int64_t)y_high * g.width + x_high) * g.zsize + z_low;
-  r.o[4] = ((int64_t)y_low * g.width + x_low) * g.zsize + z_high;
-  r.o[5] = ((int64_t)y_low * g.width + x_high) * g.zsize + z_high;
-  r.o[6] = ((int64_t)y_high * g.width + x_low) * g.zsize + z_high;
-  r.o[7] = ((int64_t)y_high * g.width + x_high) * g.zsize + z_high;
-  return r;
 }
 
 template <bool BACKWARD>

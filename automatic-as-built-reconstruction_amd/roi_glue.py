@@ -3,7 +3,9 @@
 PostProcessor.forward of the reference (maskrcnn_benchmark/modeling/roi_heads/box_head_3d/inference.py:44-162)
 without its Python loops over scenes and classes.  And the training half (csrc/roi_loss.hip): `box_head_targets`
 (proposals -> matched, labelled, encoded, sampled: FastRCNNLossComputation.subsample, box_head_3d/loss.py:163-293) and
-`box_head_loss` (cross-entropy + per-class smooth-L1 with autograd: FastRCNNLossComputation.__call__, loss.py:295-382)."""
+`box_head_loss` (cross-entropy + per-class smooth-L1 with autograd: FastRCNNLossComputation.__call__, loss.py:295-382).
+Between the two, `pool_rois` (csrc/roi_pool.hip): the FPN maps and the sampled proposals -> [N, C, ph, pw, pz] features,
+Pooler.forward (modeling/poolers_3d.py:126-168) without its per-level nonzero / index / indexed write."""
 import ctypes as C
 
 import torch
@@ -245,3 +247,127 @@ def box_head_loss(class_logits, box_regression, labels, regression_targets, clas
     cls_loss, box_loss, flag = _BoxHeadLoss.apply(class_logits, box_regression, lab, tgt, bool(class_specific),
                                                   BOX_LOSS_BETA)
     return (cls_loss, box_loss, flag) if return_flag else (cls_loss, box_loss)
+
+
+POOL_MAX_LEVELS = 8          # csrc/roi_pool.hip kPoolMaxLevels: the level table travels in the kernel arguments
+
+
+def _pool_check(features, proposals, output_size, scales):
+    """the argument errors of pool_rois, raised before the GPU is needed"""
+    if len(features) != len(scales):
+        raise ValueError("%d feature levels, %d scales" % (len(features), len(scales)))
+    if not 1 <= len(features) <= POOL_MAX_LEVELS:
+        raise ValueError("1 .. %d levels, got %d" % (POOL_MAX_LEVELS, len(features)))
+    if len(tuple(output_size)) != 3:
+        raise ValueError("output_size must be (ph, pw, pz)")
+    for x in features:
+        if x.features.dtype != torch.float32:
+            raise TypeError("pool_rois gathers float32 features, got %s (bf16 is not part of this path)" % x.features.dtype)
+        if x.features.dim() != 2:
+            raise ValueError("features must be [V, C]")
+    chans = set(int(x.features.shape[1]) for x in features)
+    if len(chans) != 1:
+        raise ValueError("the levels differ in channel count: %s" % sorted(chans))
+    for p in proposals:
+        if p.dim() != 2 or p.shape[1] != 7:
+            raise ValueError("proposals must be [n, 7] yx_zb boxes, got %s" % (tuple(p.shape),))
+
+
+def roi_rows_and_levels(proposals, scales, canonical_size, box_scale=1.0):
+    """list over scenes of [n_b, 7] yx_zb device tensors -> (rois [N, 8] fp32, levels [N] int32), one launch
+    (k_roi_pool_prepare): convert_metric_to_pixel + Pooler.convert_to_roi_format + LevelMapper_3d of the reference"""
+    lib = _hip.load()
+    if len(proposals) == 0:
+        raise ValueError("no scenes")
+    _hip.require_gpu(proposals[0])
+    dev = proposals[0].device
+    n_b = [int(p.shape[0]) for p in proposals]
+    boxes = (torch.cat([p.reshape(-1, 7) for p in proposals]) if len(proposals) > 1 else proposals[0].reshape(-1, 7))
+    boxes = boxes.detach().to(device=dev, dtype=torch.float32).contiguous()
+    N = sum(n_b)
+    rois = torch.empty((N, 8), dtype=torch.float32, device=dev)
+    levels = torch.empty(N, dtype=torch.int32, device=dev)
+    check(lib.aabr_roi_pool_prepare(ptr(boxes), len(n_b), _hip.i64xn(n_b), float(box_scale), len(scales),
+                                    _hip.f32xn(scales), float(canonical_size), ptr(rois), ptr(levels), _hip.stream()))
+    return rois, levels
+
+
+def _level_table(descs):
+    tab = (_hip.AabrRoiLevel * len(descs))()
+    for t, (feats, cm, ext, V, off, scale) in zip(tab, descs):
+        t.feats, t.cellmap = ptr(feats) if V else None, ptr(cm) if V else None
+        t.height, t.width, t.zsize, t.nb = ext
+        t.V, t.row_offset, t.spatial_scale = V, off, scale
+    return tab
+
+
+class _PoolRois(torch.autograd.Function):
+    """every level's gather in one launch; backward: one gradient allocation for all levels, one memset, one launch"""
+
+    @staticmethod
+    def forward(ctx, rois, levels, geom, cfg, *feats):
+        lib = _hip.load()
+        output_size, sampling, nb = cfg
+        feats = [f.contiguous() for f in feats]
+        C_ = int(feats[0].shape[1])
+        descs, off = [], 0
+        for f, (cm, ext, scale) in zip(feats, geom):
+            V = int(f.shape[0])
+            descs.append((f, cm, ext, V, off, scale))
+            off += V
+        N = int(rois.shape[0])
+        out = torch.empty((N, C_) + tuple(output_size), dtype=torch.float32, device=rois.device)   # every element is written
+        check(lib.aabr_roi_pool_forward(_level_table(descs), len(descs), C_, nb, ptr(rois), ptr(levels), N, output_size[0],
+                                        output_size[1], output_size[2], sampling, ptr(out), _hip.stream()))
+        ctx.descs, ctx.cfg, ctx.total = [(None,) + d[1:] for d in descs], (tuple(output_size), sampling, nb, C_), off
+        ctx.save_for_backward(rois, levels, *feats)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        lib = _hip.load()
+        rois, levels = ctx.saved_tensors[:2]
+        descs = [(f,) + d[1:] for f, d in zip(ctx.saved_tensors[2:], ctx.descs)]
+        output_size, sampling, nb, C_ = ctx.cfg
+        g = grad_output.contiguous()
+        d_all = torch.empty((ctx.total, C_), dtype=torch.float32, device=g.device)                 # zeroed by the library
+        check(lib.aabr_roi_pool_backward(_level_table(descs), len(descs), C_, nb, ptr(rois), ptr(levels),
+                                         int(rois.shape[0]), output_size[0], output_size[1], output_size[2], sampling,
+                                         ptr(g), ptr(d_all), ctx.total, _hip.stream()))
+        grads = tuple(d_all[off:off + V] for (_f, _cm, _ext, V, off, _s) in ctx.descs)
+        return (None, None, None, None) + grads
+
+
+def pool_rois(features, proposals, output_size, scales, sampling_ratio, canonical_size, box_scale=1.0, debug=None):
+    """features: list over levels of SparseConvNetTensor (fp32 [V_l, C] features); proposals: list over scenes of [n_b, 7]
+    yx_zb device tensors; scales: each level's spatial scale relative to the box frame after `box_scale` (the
+    reference's POOLER_SCALES; `box_scale` its SPARSE3D.VOXEL_SCALE, convert_metric_to_pixel).
+
+    What Pooler.forward computes (modeling/poolers_3d.py:126-168): ROI rows from the boxes, a level per box
+    (LevelMapper_3d: the scale closest to sqrt(max(size_x, size_y)) / canonical_size), and each box's rotated 3-D ROI-align
+    from its level's map, gathered straight from the sparse feature rows (ROIAlignRotated3D's fused form, bit-identical).
+    Returns [N, C, ph, pw, pz] fp32 with autograd to every level's features; a level no ROI maps to, and a level without
+    sites, get an all-zero gradient of their own shape.  Two launches forward, a memset and one launch backward, whatever
+    the level count; no host read once each grid's occupied extent and cell map are cached on its metadata (the first
+    call per grid reads 16 bytes, as ROIAlignRotated3D does).  At most 8 levels and 16 scenes.  `debug` (a dict) receives
+    `rois` [N, 8] and `levels` [N] int32."""
+    from maskrcnn_benchmark.layers.roi_align_rotated_3d import _cellmap, _occupied_extent
+    _pool_check(features, proposals, output_size, scales)
+    if len(proposals) == 0:
+        raise ValueError("no scenes")
+    _hip.require_gpu(proposals[0])
+    rois, levels = roi_rows_and_levels(proposals, scales, canonical_size, box_scale)
+    if debug is not None:
+        debug["rois"], debug["levels"] = rois, levels
+    geom = []
+    for x, scale in zip(features, scales):
+        _hip.require_gpu(x.features)
+        if int(x.features.shape[0]) == 0:
+            geom.append((None, (0, 0, 0, 0), float(scale)))
+            continue
+        ext = _occupied_extent(x)                                       # (x, y, z, batch), cached per grid
+        geom.append((_cellmap(x, ext), tuple(int(v) for v in ext), float(scale)))
+    nb = max([len(proposals)] + [g[1][3] for g in geom])             # scenes: the proposals' or the maps', whichever is more
+    cfg = (tuple(int(v) for v in output_size), int(sampling_ratio), nb)
+    return _PoolRois.apply(rois, levels, geom, cfg, *[x.features for x in features])

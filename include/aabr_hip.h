@@ -37,7 +37,9 @@ const char *aabr_last_error(void);
  * 600 = round 6 (regression targets out of the label kernel, list encode / decode, fused small-map records);
  * 610 = the RPN loss (aabr_rpn_loss_*, aabr_sample_list, aabr_smooth_l1_*); 620 = the ROI box post-processor
  * (aabr_roi_post_*); 630 = aabr_roi_align_rotated_3d_forward_batch (the dense ROI-align forward told the batch size);
- * 640 = the box head's loss (aabr_roi_targets, aabr_roi_box_loss_*). */
+ * 640 = the box head's loss (aabr_roi_targets, aabr_roi_box_loss_*).
+ * The multi-level ROI pooler (aabr_roi_pool_*, AabrRoiLevel) came after 640 WITHOUT a bump: it adds symbols and one new
+ * record only, no existing signature or layout changed, so a binding written for 640 still matches. */
 #define AABR_ABI_VERSION 640
 int aabr_version(void);
 /* Tuning knobs for experiments and tests (no counterpart in the reference; the defaults are what ships): CONV_WIDE,
@@ -845,6 +847,41 @@ int aabr_roi_align_rotated_3d_sparse_backward(const float *grad_output, int chan
                                               const float *rois, int64_t num_rois, float spatial_scale,
                                               int pooled_h, int pooled_w, int pooled_z, int sampling_ratio,
                                               int64_t V, float *d_feats, void *stream);
+
+/* ---- multi-level ROI pooler (csrc/roi_pool.hip): Pooler.forward of the box head (modeling/poolers_3d.py:73-168)
+ * with FPN2MLPFeatureExtractor.convert_metric_to_pixel (roi_box_feature_extractors.py:108-114) in front of it.
+ * Forward = 2 launches (prepare, gather), backward = 1 memset + 1 launch, whatever the level count; no host read.
+ *
+ * aabr_roi_pool_prepare: boxes [N, 7] yx_zb, the nb scenes' rows concatenated (n_host[b] rows each, 1 <= nb <= 16) ->
+ *   rois [N, 8] fp32 = (scene, p1, p0, p2 + p5 / 2, p3, p4, p5, yaw in degrees), p = box[0..5] * box_scale, yaw =
+ *   limit_period(box[6] + pi / 2, 0, pi) (BoxList3D.convert('standard') + the constructor's limit_yaw,
+ *   Pooler.convert_to_roi_format), and levels [N] int32 = LevelMapper_3d: argmin_l |scales[l] - sqrt(max(p3, p4)) /
+ *   canonical_size|, the first minimum, a NaN first (a NaN or negative size: level 0).  The fp32 operations of the torch
+ *   expressions in their order, as CPU torch evaluates them (true divisions).
+ * aabr_roi_pool_forward: output [num_rois, channels, ph, pw, pz]; ROI n is gathered from level levels[n] exactly as
+ *   aabr_roi_align_rotated_3d_sparse_forward would on that level (bit-identical).  A level with V == 0, and a level index
+ *   outside [0, n_levels), give zeros; every output element is written.  A level with V > 0 needs 1 <= nb <= batch_size.
+ * aabr_roi_pool_backward: d_feats_all [total_rows, channels] holds every level's gradient rows, level l at row
+ *   row_offset (row_offset + V <= total_rows); zeroed here, then fp32 atomics on active cells only.                   */
+typedef struct AabrRoiLevel {
+  const float *feats;          /* [V, channels] fp32 feature rows of the level (unused when V == 0)                  */
+  const int32_t *cellmap;      /* [nb, height, width, zsize] int32, aabr_roi_cellmap over the occupied extent        */
+  int32_t height, width, zsize; /* the occupied extent                                                               */
+  int32_t nb;                  /* samples the cell map covers: an ROI of scene >= nb names an empty sample           */
+  int64_t V;                   /* active sites                                                                       */
+  int64_t row_offset;          /* backward: first row of this level in d_feats_all                                   */
+  float spatial_scale;
+  int32_t reserved;
+} AabrRoiLevel;
+int aabr_roi_pool_prepare(const float *boxes, int nb, const int64_t *n_host, float box_scale, int n_levels,
+                          const float *scales_host, float canonical_size, float *rois, int32_t *levels, void *stream);
+int aabr_roi_pool_forward(const AabrRoiLevel *levels_desc_host, int n_levels, int channels, int batch_size,
+                          const float *rois, const int32_t *levels, int64_t num_rois, int pooled_h, int pooled_w,
+                          int pooled_z, int sampling_ratio, float *output, void *stream);
+int aabr_roi_pool_backward(const AabrRoiLevel *levels_desc_host, int n_levels, int channels, int batch_size,
+                           const float *rois, const int32_t *levels, int64_t num_rois, int pooled_h, int pooled_w,
+                           int pooled_z, int sampling_ratio, const float *grad_output, float *d_feats_all,
+                           int64_t total_rows, void *stream);
 
 /* ---- RPN loss (csrc/rpn_loss.hip): RPNLossComputation.__call__ (modeling/rpn/loss_3d.py:201-251), one objectness group.
  * Per example the BalancedPositiveNegativeSampler (modeling/balanced_positive_negative_sampler.py:19-68):
