@@ -202,7 +202,16 @@ _SIGS = {
     "aabr_roi_pool_forward": (C.c_int, [_lvp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "aabr_roi_pool_backward": (C.c_int, [_lvp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i64,
                                          _vp]),
+    "aabr_roi_mlp_tile": (C.c_int, [_i64, _i64]),
+    "aabr_roi_mlp_dw_splits": (C.c_int, [_i64, _i64, _i64]),
+    "aabr_roi_mlp_dw_scratch_floats": (C.c_int64, [_i64, _i64, _i64]),
+    "aabr_roi_mlp_forward": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp]),
+    "aabr_roi_mlp_backward_input": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i64, _i32, _vp, _vp]),
+    "aabr_roi_mlp_backward_weight": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
+                                               _vp]),
+    "aabr_roi_mlp_pack_fc6": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
 }
+MLP_ROWS, MLP_POOLED = 0, 1     # include/aabr_hip.h AABR_MLP_ROWS / AABR_MLP_POOLED
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))
 
 

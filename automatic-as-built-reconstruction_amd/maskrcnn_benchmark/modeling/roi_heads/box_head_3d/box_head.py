@@ -1,0 +1,59 @@
+"""The box head (reference: maskrcnn_benchmark/modeling/roi_heads/box_head_3d/box_head.py:41-257), centroid form
+(forward_centroid_box, :168-248): feature extractor, predictor, loss evaluator and post-processor in the reference's
+order.  `proposals` is one duck-typed list per scene (`.bbox3d` [n, 7] yx_zb, `.size3d`), or an object whose
+`seperate_examples()` returns that.  Not part of this package: the corner-ROI form, the separated-classifier groups, and
+cfg.DEBUG.eval_in_train (its rm_gt_from_proposals_ reads an `is_gt` field the sampled lists here do not carry)."""
+import torch
+
+from .inference import make_roi_box_post_processor
+from .loss import make_roi_box_loss_evaluator
+from .roi_box_feature_extractors import make_roi_box_feature_extractor
+from .roi_box_predictors import make_roi_box_predictor
+
+
+class ROIBoxHead3D(torch.nn.Module):
+    """extractor + predictor + loss evaluator (training) or post-processor (evaluation), the centroid form"""
+
+    def __init__(self, cfg):
+        super(ROIBoxHead3D, self).__init__()
+        if cfg.MODEL.CORNER_ROI:
+            raise ValueError("cfg.MODEL.CORNER_ROI: the corner-ROI form of the box head is not part of this package")
+        if cfg.DEBUG.eval_in_train > 0:
+            raise ValueError("cfg.DEBUG.eval_in_train > 0 is not part of this package")
+        self.feature_extractor = make_roi_box_feature_extractor(cfg)
+        self.predictor = make_roi_box_predictor(cfg)
+        self.post_processor_ = make_roi_box_post_processor(cfg)
+        self.loss_evaluator, self.seperate_classifier = make_roi_box_loss_evaluator(cfg)
+        self.need_seperate = False
+        self.eval_in_train = cfg.DEBUG.eval_in_train
+        self.add_gt_proposals = cfg.MODEL.RPN.ADD_GT_PROPOSALS
+        self.detections_per_img = cfg.MODEL.ROI_HEADS.DETECTIONS_PER_IMG
+        self.corner_roi = cfg.MODEL.CORNER_ROI
+        self.cfg = cfg
+
+    def post_processor(self, log_reg, proposals):
+        return self.post_processor_(log_reg, proposals)
+
+    def forward(self, features, proposals, targets=None):
+        """features: one SparseConvNetTensor per level; proposals: per-scene lists; targets: per-scene ground truth
+        (training).  Returns (x, proposals, losses): training -- the sampled proposals and {"loss_classifier_roi",
+        "loss_box_reg_roi"}; evaluation -- the detections and {}."""
+        if hasattr(proposals, "seperate_examples"):
+            proposals = proposals.seperate_examples()
+        if self.training:
+            # training runs on the balanced sample of the proposals, not on all of them
+            with torch.no_grad():
+                proposals = self.loss_evaluator.subsample(proposals, targets)
+        x = self.feature_extractor(features, proposals)
+        class_logits, box_regression = self.predictor(x)
+        if not self.training:
+            result = self.post_processor((class_logits, box_regression, None), proposals)
+            return x, result, {}
+        loss_classifier, loss_box_reg, _ = self.loss_evaluator(class_logits, box_regression, corners_semantic=None,
+                                                               targets=targets)
+        return x, proposals, {"loss_classifier_roi": loss_classifier, "loss_box_reg_roi": loss_box_reg}
+
+
+def build_roi_box_head(cfg):
+    """the factory the reference's model builder calls"""
+    return ROIBoxHead3D(cfg)

@@ -5,7 +5,10 @@ without its Python loops over scenes and classes.  And the training half (csrc/r
 (proposals -> matched, labelled, encoded, sampled: FastRCNNLossComputation.subsample, box_head_3d/loss.py:163-293) and
 `box_head_loss` (cross-entropy + per-class smooth-L1 with autograd: FastRCNNLossComputation.__call__, loss.py:295-382).
 Between the two, `pool_rois` (csrc/roi_pool.hip): the FPN maps and the sampled proposals -> [N, C, ph, pw, pz] features,
-Pooler.forward (modeling/poolers_3d.py:126-168) without its per-level nonzero / index / indexed write."""
+Pooler.forward (modeling/poolers_3d.py:126-168) without its per-level nonzero / index / indexed write.  And what turns
+the pooled tensor into the other two (csrc/roi_mlp.hip, a dense fp32 MFMA GEMM family): `dense_linear`, `box_head_mlp`
+(FPN2MLPFeatureExtractor after its pooler, roi_box_feature_extractors.py:149-157) and `box_predictions` (FPNPredictor,
+roi_box_predictors.py:105-109)."""
 import ctypes as C
 
 import torch
@@ -371,3 +374,161 @@ def pool_rois(features, proposals, output_size, scales, sampling_ratio, canonica
     nb = max([len(proposals)] + [g[1][3] for g in geom])             # scenes: the proposals' or the maps', whichever is more
     cfg = (tuple(int(v) for v in output_size), int(sampling_ratio), nb)
     return _PoolRois.apply(rois, levels, geom, cfg, *[x.features for x in features])
+
+
+class _Mlp(torch.autograd.Function):
+    """one dense layer act(A W^T + bias) over csrc/roi_mlp.hip.  `pooled` = (hw, pz): A is the pooler's [n, C, ..., pz]
+    tensor read in place (rows n hw + s, columns c pz + z).  `perm_hw` > 0: `weight` is fc6's [N, R hw] in the reference's
+    column order r hw + s while A's columns are s R + r -- the weight is packed once (one launch), both GEMMs that read it
+    run on the packed copy, and the weight gradient is stored through the inverse permutation."""
+
+    @staticmethod
+    def forward(ctx, a, weight, bias, relu, pooled, perm_hw):
+        lib = _hip.load()
+        dev = a.device
+        a, weight = a.contiguous(), weight.contiguous()
+        bias = bias.contiguous() if bias is not None else None
+        N, K = int(weight.shape[0]), int(weight.shape[1])
+        if pooled is None:
+            layout, hw, pz, M = _hip.MLP_ROWS, 0, 0, int(a.shape[0])
+        else:
+            layout, (hw, pz) = _hip.MLP_POOLED, pooled
+            M = int(a.shape[0]) * hw
+        w_used = weight
+        if perm_hw:
+            w_used = torch.empty_like(weight)
+            check(lib.aabr_roi_mlp_pack_fc6(ptr(weight), N, K // perm_hw, perm_hw, ptr(w_used), _hip.stream()))
+        y = torch.empty((M, N), dtype=torch.float32, device=dev)                      # every element is written
+        check(lib.aabr_roi_mlp_forward(ptr(a), layout, hw, pz, ptr(w_used), ptr(bias), int(relu), M, N, K, ptr(y),
+                                       _hip.stream()))
+        ctx.save_for_backward(a, w_used, y if relu else None)
+        ctx.cfg = (layout, hw, pz, M, N, K, int(perm_hw), bias is not None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        lib = _hip.load()
+        a, w_used, y = ctx.saved_tensors
+        layout, hw, pz, M, N, K, perm_hw, has_bias = ctx.cfg
+        dy = dy.contiguous()
+        dev = dy.device
+        d_a = d_w = d_b = None
+        if ctx.needs_input_grad[0]:
+            d_a = torch.empty_like(a)                                                  # every element is written
+            check(lib.aabr_roi_mlp_backward_input(ptr(dy), ptr(y), ptr(w_used), M, N, K, layout, hw, pz, ptr(d_a),
+                                                  _hip.stream()))
+        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
+            d_w = torch.empty((N, K), dtype=torch.float32, device=dev)
+            d_b = torch.empty(N, dtype=torch.float32, device=dev) if has_bias else None
+            floats = int(lib.aabr_roi_mlp_dw_scratch_floats(M, N, K))
+            scr = _hip.workspace("roi_mlp_dw", floats, torch.float32, dev) if floats else None
+            check(lib.aabr_roi_mlp_backward_weight(ptr(dy), ptr(y), ptr(a), layout, hw, pz, M, N, K, perm_hw, ptr(d_w),
+                                                   ptr(d_b), ptr(scr), _hip.stream()))
+        return d_a, d_w, d_b, None, None, None
+
+
+def _mlp_f32(name, **tensors):
+    for k, t in tensors.items():
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError("%s: %s must be float32, got %s (bf16 is not part of this path)" % (name, k, t.dtype))
+
+
+def dense_linear(x, weight, bias=None, relu=False):
+    """act(x W^T + bias): x [M, K] fp32, weight [N, K] (nn.Linear.weight), bias [N] or None, relu: ReLU fused into the
+    write-out (and its mask into both gradients' operand loads).  Autograd to x, weight and bias; the weight and bias
+    gradients are deterministic (no atomics).  K % 4 == 0 and K >= 4, any M >= 0 and N >= 1.  One launch forward; backward
+    one for the input gradient and one (two when the reduction over M is split: aabr_roi_mlp_dw_splits) for the weight
+    and bias gradients."""
+    _mlp_f32("dense_linear", x=x, weight=weight, bias=bias)
+    if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1]:
+        raise ValueError("dense_linear: x [M, K] and weight [N, K], got %s and %s" % (tuple(x.shape), tuple(weight.shape)))
+    if bias is not None and tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError("dense_linear: bias must be [%d]" % weight.shape[0])
+    _hip.require_gpu(x)
+    return _Mlp.apply(x, weight, bias, bool(relu), None, 0)
+
+
+def box_head_mlp(pooled, conv_w, conv_b, bn_w, bn_b, bn_state, fc6_w, fc6_b, fc7_w, fc7_b):
+    """FPN2MLPFeatureExtractor.forward_centroid_box after its pooler (roi_box_feature_extractors.py:152-157):
+      pooled [N, C, ph, pw, pz] -> Conv3d([1, 1, pz]) -> BatchNorm3d -> ReLU -> view(N, -1) -> fc6, ReLU -> fc7, ReLU
+    and returns x4 [N, R].  Parameters in the reference's layouts: conv_w [R, C, 1, 1, pz], fc6_w [R, R ph pw] (columns in
+    the (r, h, w) order of the view), fc7_w [R, R].  The convolution reads the pooled tensor in place and keeps its result
+    as rows [N ph pw, R]; BatchNorm + ReLU is the library's aabr_bn_forward / _backward over those rows (leakiness 0, the
+    statistics in fp64); fc6 reads them as [N, ph pw R] against its weight packed to that column order.
+
+    bn_state: dict with `eps`, `momentum` (torch's: the share of the NEW statistic; the library multiplies the running
+    value, so it receives 1 - momentum), `training`, `track_running_stats`, and `running_mean` / `running_var` (updated
+    in place in training; None without tracking).  Without tracking the batch statistics serve in both modes.
+    6 launches forward (GEMM, BatchNorm 2, pack, GEMM, GEMM; box_predictions adds a seventh and two torch.cat copies),
+    whatever N."""
+    from sparseconvnet.batchNormalization import BatchNormFunction
+    _mlp_f32("box_head_mlp", pooled=pooled, conv_w=conv_w, conv_b=conv_b, bn_w=bn_w, bn_b=bn_b, fc6_w=fc6_w, fc6_b=fc6_b,
+             fc7_w=fc7_w, fc7_b=fc7_b)
+    if pooled.dim() != 5:
+        raise ValueError("pooled must be [N, C, ph, pw, pz], got %s" % (tuple(pooled.shape),))
+    _hip.require_gpu(pooled)
+    n, c, ph, pw, pz = (int(v) for v in pooled.shape)
+    R = int(conv_w.shape[0])
+    if tuple(conv_w.shape) != (R, c, 1, 1, pz):
+        raise ValueError("conv_w must be [R, %d, 1, 1, %d], got %s" % (c, pz, tuple(conv_w.shape)))
+    hw = ph * pw
+    if tuple(fc6_w.shape) != (int(fc6_w.shape[0]), R * hw):
+        raise ValueError("fc6_w must be [*, %d], got %s" % (R * hw, tuple(fc6_w.shape)))
+    if bn_state.get("momentum") is None:
+        raise ValueError("BatchNorm momentum None (cumulative average) is not part of this path")
+    x1 = _Mlp.apply(pooled, conv_w.reshape(R, c * pz), conv_b, False, (hw, pz), 0)            # [N hw, R]
+    track = bool(bn_state["track_running_stats"])
+    train = bool(bn_state["training"]) or not track
+    if track:
+        rm, rv = bn_state["running_mean"], bn_state["running_var"]
+    else:                                                  # the kernel's running-statistics update lands in scratch
+        rm = _hip.workspace("roi_mlp_bn", 2 * R, torch.float32, pooled.device)
+        rm, rv = rm[:R], rm[R:2 * R]
+    empty = pooled.new_empty(0)
+    x2 = BatchNormFunction.apply(x1, empty if bn_w is None else bn_w, empty if bn_b is None else bn_b, rm, rv,
+                                 (float(bn_state["eps"]), 1.0 - float(bn_state["momentum"]), train, 0))
+    x3 = _Mlp.apply(x2.view(n, hw * R), fc6_w, fc6_b, True, None, hw)
+    return _Mlp.apply(x3, fc7_w, fc7_b, True, None, 0)
+
+
+def box_predictions(x, cls_w, cls_b, reg_w, reg_b):
+    """FPNPredictor.forward_centroid_box (roi_box_predictors.py:105-109): (cls_score(x), bbox_pred(x)) as ONE GEMM over
+    the two weights concatenated along N, returned as two column views of its result.  Device work per call: the one
+    GEMM launch, plus torch's own 2 copies (torch.cat of the two weights and of the two biases); backward 2 or 3 library
+    launches (input gradient, weight + bias gradient, its second stage when split) plus torch's 5 small kernels for the
+    two column views (two zero fills, two copies, one add)."""
+    _mlp_f32("box_predictions", x=x, cls_w=cls_w, cls_b=cls_b, reg_w=reg_w, reg_b=reg_b)
+    if x.dim() != 2 or cls_w.dim() != 2 or reg_w.dim() != 2 or cls_w.shape[1] != x.shape[1] or reg_w.shape[1] != x.shape[1]:
+        raise ValueError("box_predictions: x [n, R], cls_w [C, R], reg_w [7 C or 7, R]")
+    if (cls_b is None) != (reg_b is None):
+        raise ValueError("box_predictions: both biases or neither")
+    _hip.require_gpu(x)
+    nc = int(cls_w.shape[0])
+    w = torch.cat([cls_w, reg_w])
+    b = torch.cat([cls_b, reg_b]) if cls_b is not None else None
+    y = _Mlp.apply(x, w, b, False, None, 0)
+    return y[:, :nc], y[:, nc:]
+
+
+class _Cfg(object):
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def box_head_cfg(C=8, resolution=(2, 3, 2), R=12, classes=("background", "wall", "door"), class_specific=True, separate=(),
+                 corner=False, track=False, scales=(0.5, 0.25, 0.125), canonical=10.0, sampling=2, voxel_scale=1.0,
+                 extractor="FPN2MLPFeatureExtractor", predictor="FPNPredictor", eval_in_train=0, detections=20):
+    """a plain attribute tree with the cfg keys the box head's modules read, named as in the reference's
+    config/defaults.py -- for smoke(), the timing tool and the tests, which have no yacs config"""
+    box_head = _Cfg(POOLER_RESOLUTION=tuple(resolution), POOLER_SCALES_SPATIAL=tuple(scales),
+                    POOLER_SAMPLING_RATIO=sampling, CANONICAL_SIZE=canonical, MLP_HEAD_DIM=R, FEATURE_EXTRACTOR=extractor,
+                    PREDICTOR=predictor)
+    heads = _Cfg(FG_IOU_THRESHOLD=0.5, BG_IOU_THRESHOLD=0.5, BBOX_REG_WEIGHTS=(10.0, 10.0, 10.0, 5.0, 5.0, 5.0, 10.0),
+                 BATCH_SIZE_PER_IMAGE=16, POSITIVE_FRACTION=0.25, LABEL_AUG_THICKNESS_Y_TAR_ANC=(0.0, 0.0),
+                 LABEL_AUG_THICKNESS_Z_TAR_ANC=(0.0, 0.0), SCORE_THRESH=0.05, NMS=0.5, NMS_AUG_THICKNESS_Y_Z=(0.0, 0.0),
+                 DETECTIONS_PER_IMG=detections)
+    model = _Cfg(CORNER_ROI=corner, CLASS_SPECIFIC=class_specific, SEPARATE_CLASSES=list(separate), SEPARATE_CLASSES_ID=[],
+                 ROI_BOX_HEAD=box_head, ROI_HEADS=heads, LOSS=_Cfg(YAW_MODE="Diff"), RPN=_Cfg(ADD_GT_PROPOSALS=False))
+    return _Cfg(MODEL=model, SPARSE3D=_Cfg(VOXEL_SCALE=voxel_scale, nPlaneMap=C), SOLVER=_Cfg(TRACK_RUNNING_STATS=track),
+                INPUT=_Cfg(CLASSES=list(classes)), DEBUG=_Cfg(eval_in_train=eval_in_train))

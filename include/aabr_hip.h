@@ -39,7 +39,8 @@ const char *aabr_last_error(void);
  * (aabr_roi_post_*); 630 = aabr_roi_align_rotated_3d_forward_batch (the dense ROI-align forward told the batch size);
  * 640 = the box head's loss (aabr_roi_targets, aabr_roi_box_loss_*).
  * The multi-level ROI pooler (aabr_roi_pool_*, AabrRoiLevel) came after 640 WITHOUT a bump: it adds symbols and one new
- * record only, no existing signature or layout changed, so a binding written for 640 still matches. */
+ * record only, no existing signature or layout changed, so a binding written for 640 still matches.  The box head's
+ * dense layers (aabr_roi_mlp_*) came the same way: symbols only. */
 #define AABR_ABI_VERSION 640
 int aabr_version(void);
 /* Tuning knobs for experiments and tests (no counterpart in the reference; the defaults are what ships): CONV_WIDE,
@@ -1037,6 +1038,58 @@ int aabr_roi_box_loss_backward(const void *class_logits, const void *box_regress
                                int class_specific, const int64_t *labels, const float *regression_targets, float beta,
                                const float *grad_cls_loss, const float *grad_box_loss, void *grad_logits,
                                void *grad_regression, void *stream);
+
+/* ---- the box head's dense layers (csrc/roi_mlp.hip): FPN2MLPFeatureExtractor after its pooler
+ * (roi_box_feature_extractors.py:46-169: Conv3d([1,1,pz]) + BatchNorm3d + ReLU, fc6 + ReLU, fc7 + ReLU) and FPNPredictor
+ * (roi_box_predictors.py:34-109) as a dense fp32 GEMM family on v_mfma_f32_32x32x2_f32 (fp32 storage only, exact fp32:
+ * every result element is an fmaf chain over its reduction).  A layer is Y [M, N] = act(A W^T + bias) with W [N, K]
+ * row-major, the reference's parameter layout (nn.Linear.weight; Conv3d.weight viewed as [R, C pz]).
+ *   shapes: any M >= 0 (M == 0 launches no kernel and succeeds; the weight gradient of M == 0 is a memset to zero), any
+ *   N >= 1, K >= 4 with K % 4 == 0, all below 2^31 - 256; anything else, a null pointer or a negative size: AABR_EINVAL.
+ *   a_layout: AABR_MLP_ROWS = A is row-major [M, K] (hw, pz ignored); AABR_MLP_POOLED = A is the pooler's
+ *   [n, C, hw, pz] tensor read in place: row m = n hw + s, column k = c pz + z, element ((n C + c) hw + s) pz + z
+ *   (M % hw == 0, K % pz == 0) -- no transposed copy of the activation is written in either direction.
+ * aabr_roi_mlp_forward:         Y = A W^T (+ bias if not NULL) (ReLU if relu).                          1 launch.
+ * aabr_roi_mlp_backward_input:  dA [M, K] = (dY . mask) W, mask = (Y > 0) read with dY when Y is not NULL (the forward
+ *   applied ReLU), all ones when Y is NULL; dA is stored in a_layout (pooled: what aabr_roi_pool_backward reads), every
+ *   element exactly once.                                                                                1 launch.
+ * aabr_roi_mlp_backward_weight: dW [N, K] = (dY . mask)^T A and, when db is not NULL, db [N] = column sums of dY . mask
+ *   (added in row order inside the same kernel).  Deterministic, no float atomics: when aabr_roi_mlp_dw_splits(M, N, K)
+ *   > 1 the reduction over M is cut into that many runs of whole 32-row chunks, one workgroup per run and tile, each
+ *   writing its partial to scratch (fp32 [aabr_roi_mlp_dw_scratch_floats(M, N, K)], may be NULL when that is 0), and a
+ *   second launch adds the partials in run order.  perm_hw > 0 (K % perm_hw == 0, R = K / perm_hw): A's column
+ *   k' = s R + r is stored at dW column r perm_hw + s -- fc6's gradient in the reference's layout while the GEMM ran on
+ *   the packed weight.                                                                         1 launch, 2 when split.
+ * aabr_roi_mlp_pack_fc6: Wp [N, hw R] with Wp[o, s R + r] = W[o, r hw + s]: fc6.weight (columns in x.view(N, -1) order
+ *   over the reference's [N, R, h, w] activation) for the activation kept as rows [N hw, R].            1 launch.
+ * Dispatch (host functions, so tests can place shapes on both sides):
+ *   aabr_roi_mlp_tile(rows, cols): edge of the square output tile a workgroup owns, for an output of [rows, cols]:
+ *     128 when there are at least 192 tiles of 128 x 128, else 64 (0 for an empty output).  Forward: (M, N); input
+ *     gradient: (M, K); weight gradient: (N, K).  The reduction runs in chunks of 32.
+ *   aabr_roi_mlp_dw_splits(M, N, K): runs the weight gradient's reduction is cut into: min(512 / tiles, 64,
+ *     ceil(M / 256)), at least 1, then rounded so every run is whole 32-row chunks and none is empty.
+ * BatchNorm3d + ReLU between the convolution and fc6 is aabr_bn_forward / aabr_bn_backward over the [n hw, R] rows
+ * (leakiness 0); the statistics are NOT taken from the GEMM's write-out.
+ * Launch counts of the whole head, whatever the ROI count (roi_glue.box_head_mlp + box_predictions).  Library launches:
+ * forward 7 = conv GEMM 1 + BatchNorm 2 + fc6 pack 1 + fc6 1 + fc7 1 + predictor 1 (both linears as one GEMM); backward
+ * 10 to 14 = per GEMM 1 input gradient + 1 weight gradient (+ 1 when split: 13 at the default sizes, where all but
+ * fc6's are) + BatchNorm's own 2.  On top of these, torch's own small kernels in the Python layer: forward 2 copies
+ * (torch.cat of the predictor's two weights and two biases) and 1 add when the BatchNorm tracks running statistics
+ * (num_batches_tracked); backward 5 for the two column views of the predictor's result (two zero fills, two copies, one
+ * add), besides the gradient accumulation into the parameters that every autograd function has.                     */
+#define AABR_MLP_ROWS 0
+#define AABR_MLP_POOLED 1
+int aabr_roi_mlp_tile(int64_t rows, int64_t cols);
+int aabr_roi_mlp_dw_splits(int64_t M, int64_t N, int64_t K);
+int64_t aabr_roi_mlp_dw_scratch_floats(int64_t M, int64_t N, int64_t K);
+int aabr_roi_mlp_forward(const float *A, int a_layout, int64_t hw, int pz, const float *W, const float *bias, int relu,
+                         int64_t M, int64_t N, int64_t K, float *Y, void *stream);
+int aabr_roi_mlp_backward_input(const float *dY, const float *Y, const float *W, int64_t M, int64_t N, int64_t K,
+                                int a_layout, int64_t hw, int pz, float *dA, void *stream);
+int aabr_roi_mlp_backward_weight(const float *dY, const float *Y, const float *A, int a_layout, int64_t hw, int pz,
+                                 int64_t M, int64_t N, int64_t K, int64_t perm_hw, float *dW, float *db, float *scratch,
+                                 void *stream);
+int aabr_roi_mlp_pack_fc6(const float *W, int64_t N, int64_t R, int64_t hw, float *Wp, void *stream);
 
 #ifdef __cplusplus
 }
