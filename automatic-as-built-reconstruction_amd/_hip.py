@@ -28,7 +28,14 @@ class AabrRoiLevel(C.Structure):
                 ("spatial_scale", C.c_float), ("reserved", C.c_int32)]
 
 
+class AabrRpnMap(C.Structure):
+    """include/aabr_hip.h AabrRpnMap: one feature map of the RPN head"""
+    _fields_ = [("features", C.c_void_p), ("rows", C.c_int64), ("objectness", C.c_void_p),
+                ("box_regression", C.c_void_p), ("d_features", C.c_void_p)]
+
+
 _lvp = C.POINTER(AabrRoiLevel)
+_rmp = C.POINTER(AabrRpnMap)
 _SIGS = {
     "aabr_version": (C.c_int, []),
     "aabr_build_flags": (C.c_int, []),
@@ -210,6 +217,11 @@ _SIGS = {
     "aabr_roi_mlp_backward_weight": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
                                                _vp]),
     "aabr_roi_mlp_pack_fc6": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
+    "aabr_rpn_head_tile_rows": (C.c_int, [_i32]),
+    "aabr_rpn_head_groups": (C.c_int, [_i64]),
+    "aabr_rpn_head_scratch_floats": (C.c_int64, [_i64, _i32, _i32]),
+    "aabr_rpn_head_forward": (C.c_int, [_rmp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aabr_rpn_head_backward": (C.c_int, [_rmp, _i32, _i32, _i32] + [_vp] * 12),
 }
 MLP_ROWS, MLP_POOLED = 0, 1     # include/aabr_hip.h AABR_MLP_ROWS / AABR_MLP_POOLED
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))

@@ -1,0 +1,483 @@
+// rpn_head.hip -- the RPN head (SingleConvRPNHead_Sparse3D, modeling/rpn/rpn_sparse3d.py:81-131) over the rows of every
+// feature map in ONE launch, gfx950, fp32 storage only, on v_mfma_f32_32x32x2_f32 (an exact fmaf chain per element):
+//   t = relu(f W1^T + b1),  obj = t Wc^T + bc  [V, A],  reg = t Wr^T + br  [V, A, 7] (channel a 7 + j: the reference's
+//   permute + reshape 'box_toghter', the [site, yaw] flatten order the rpn_glue consumers read).
+// W1 [C, C], Wc [A, C], Wr [7 A, C] are the Conv2d weights as [out, in].  C in {32, 64, 96, 128}, 1 <= A <= 4.
+//
+// The maps come as a by-value table (RpnMaps, built from the caller's AabrRpnMap records): block b serves the map m with
+// first[m] <= b < first[m + 1] and the kRpnT = 64 consecutive rows (b - first[m]) 64 ... of it.  Nothing is concatenated.
+//
+// Forward, k_rpn_head_fwd<C> (256 threads = 2 x 2 waves; wave (wm, wn) owns rows wm 32 .. + 32 and the 32-column tiles
+// wn, wn + 2 of t): the f tile and W1 go through LDS in reduction chunks of 32 ([32][64 + 2] and [32][C + 2]), bias and
+// ReLU are applied in registers, t is kept in LDS as [C][64 + 2] (and stored to `hidden` only when that is not NULL),
+// and the second product reads it against the 8 A columns of [Wc; Wr] zero-padded to one 32-wide MFMA tile (the two
+// wn = 0 waves); both outputs are written from those accumulators.  58.9 KB of LDS at C = 128.
+//
+// Backward, k_rpn_head_bwd<C>: ONE fused kernel (it fits: 108.5 KB of dynamic LDS at C = 128, one workgroup per CU).
+// Workgroup w of G = aabr_rpn_head_groups(total_tiles) serves tiles w, w + G, ...  Per tile, with D = [d_obj | d_reg]
+// padded to 32 columns (a NULL gradient reads as zeros):
+//   d[Wc; Wr] += D^T t                     (registers, one 32 x 32 tile per wave)
+//   dt = (D [Wc; Wr]) . (t > 0)            -> LDS [64][C + 2]; serves as rows (reduce over the site) and, read transposed,
+//                                             as columns (reduce over the hidden unit): C + 2 = 2 mod 32 keeps both
+//                                             access patterns off each other's banks
+//   dW1 += dt^T f                          (registers, up to 4 tiles per wave)
+//   d_f = dt W1                            (W1 through LDS in chunks of 32 rows; every d_f element stored exactly once)
+//   db1, [dbc; dbr]: column sums of dt and D, added in row order by one thread per column.
+// Each workgroup then writes ONE partial [C C + 32 C + C + 32] to scratch and k_rpn_head_reduce adds the partials in
+// workgroup order: deterministic, no float atomics.
+//
+// Launches: forward 1; backward 2 (main, reduce) -- whatever n_maps.  No weight pack is needed.  All maps empty: no
+// launch; backward then zeroes the six weight gradients with memsets.
+#include "common.h"
+
+namespace aabr {
+
+constexpr int kRpnT = 64;          // rows per tile
+constexpr int kRpnN2 = 32;         // the 8 A output columns, padded to one MFMA tile
+constexpr int kRpnMaxMaps = 8;
+constexpr int kRpnMaxGroups = 256; // one workgroup per CU of an MI355X; a constant, never read from the device
+constexpr int kRpnLD = kRpnT + 2;  // LDS row of a [reduce][64 rows] image
+constexpr int kRpnLD2 = kRpnN2 + 2;
+
+struct RpnMaps {
+  const float *f[kRpnMaxMaps];
+  float *obj[kRpnMaxMaps];         // forward: outputs; backward: d_obj (read only, may be NULL)
+  float *reg[kRpnMaxMaps];
+  float *df[kRpnMaxMaps];          // backward: d_f
+  int64_t rows[kRpnMaxMaps];
+  int64_t hoff[kRpnMaxMaps];       // first row of the map in `hidden`
+  uint32_t first[kRpnMaxMaps + 1]; // first tile of map m; first[n] = total tiles
+  int n;
+};
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+__device__ inline int rpn_map_of(const RpnMaps &g, uint32_t tile) {
+  int m = 0;
+  while (m + 1 < g.n && tile >= g.first[m + 1]) ++m;
+  return m;
+}
+
+// element (n, k) of the packed [Wc; Wr] block, zero beyond its 8 A rows
+__device__ inline float rpn_w2(const float *__restrict__ Wc, const float *__restrict__ Wr, int A, int C, int n, int k) {
+  if (n < A) return Wc[n * C + k];
+  if (n < 8 * A) return Wr[(n - A) * C + k];
+  return 0.f;
+}
+
+// accumulator register r of a 32 x 32 tile: row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31
+__device__ inline int rpn_acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
+
+template <int C>
+__global__ __launch_bounds__(256) void k_rpn_head_fwd(const RpnMaps g, const float *__restrict__ W1,
+                                                      const float *__restrict__ b1, const float *__restrict__ Wc,
+                                                      const float *__restrict__ bc, const float *__restrict__ Wr,
+                                                      const float *__restrict__ br, int A, float *__restrict__ hidden) {
+  constexpr int NT = C / 32, LDB = C + 2;
+  __shared__ float sA[32 * kRpnLD];
+  __shared__ float sB[32 * LDB];
+  __shared__ float sT[C * kRpnLD];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave & 1, wn = wave >> 1;
+  const int l31 = lane & 31, kh = 16 * (lane >> 5), tk = t & 31, tr = t >> 5;
+  const int m = rpn_map_of(g, blockIdx.x);
+  const int64_t rows = g.rows[m], row0 = (int64_t)(blockIdx.x - g.first[m]) * kRpnT;
+  const float *__restrict__ f = g.f[m];
+
+  f32x16 acc[2];
+#pragma unroll
+  for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[jj][r] = 0.f;
+
+  for (int k0 = 0; k0 < C; k0 += 32) {
+    __syncthreads();                                  // the previous chunk's reads are done
+#pragma unroll
+    for (int i = 0; i < kRpnT / 8; ++i) {
+      const int64_t row = row0 + tr + 8 * i;
+      sA[tk * kRpnLD + tr + 8 * i] = row < rows ? f[row * C + k0 + tk] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < C / 8; ++i) sB[tk * LDB + tr + 8 * i] = W1[(tr + 8 * i) * C + k0 + tk];
+    __syncthreads();
+#pragma unroll 4
+    for (int kk = 0; kk < 16; ++kk) {                 // MFMA step kk sums reduce rows kk and kk + 16 of the chunk
+      const float a = sA[(kk + kh) * kRpnLD + wm * 32 + l31];
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) {
+        const int j = wn + 2 * jj;
+        if (j < NT) acc[jj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, sB[(kk + kh) * LDB + j * 32 + l31], acc[jj], 0, 0, 0);
+      }
+    }
+  }
+  // bias and ReLU in registers; t -> LDS [hidden unit][row], and to `hidden` for the backward pass
+#pragma unroll
+  for (int jj = 0; jj < 2; ++jj) {
+    const int j = wn + 2 * jj;
+    if (j >= NT) continue;
+    const int col = j * 32 + l31;
+    const float bias = b1[col];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = wm * 32 + rpn_acc_row(r, lane);
+      float x = acc[jj][r] + bias;
+      x = x > 0.f ? x : 0.f;
+      sT[col * kRpnLD + row] = x;
+      if (hidden != nullptr && row0 + row < rows) hidden[(g.hoff[m] + row0 + row) * C + col] = x;
+    }
+  }
+
+  f32x16 acc2;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
+  for (int k0 = 0; k0 < C; k0 += 32) {
+    __syncthreads();                                  // sT is complete; the previous chunk's reads of sB are done
+#pragma unroll
+    for (int i = 0; i < kRpnN2 / 8; ++i) sB[tk * kRpnLD2 + tr + 8 * i] = rpn_w2(Wc, Wr, A, C, tr + 8 * i, k0 + tk);
+    __syncthreads();
+    if (wn == 0) {
+#pragma unroll 4
+      for (int kk = 0; kk < 16; ++kk)
+        acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(sT[(k0 + kk + kh) * kRpnLD + wm * 32 + l31],
+                                                    sB[(kk + kh) * kRpnLD2 + l31], acc2, 0, 0, 0);
+    }
+  }
+  if (wn == 0 && l31 < 8 * A) {
+    const bool is_obj = l31 < A;
+    const float bias = is_obj ? bc[l31] : br[l31 - A];
+    float *__restrict__ out = is_obj ? g.obj[m] : g.reg[m];
+    const int64_t ld = is_obj ? A : 7 * A;
+    const int col = is_obj ? l31 : l31 - A;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int64_t row = row0 + wm * 32 + rpn_acc_row(r, lane);
+      if (row < rows) out[row * ld + col] = acc2[r] + bias;
+    }
+  }
+}
+
+// floats of one workgroup's partial: dW1 [C][C], d[Wc; Wr] [32][C], db1 [C], [dbc; dbr] [32]
+__host__ __device__ constexpr int64_t rpn_partial_floats(int C) { return (int64_t)C * C + 32 * C + C + 32; }
+
+template <int C>
+__global__ __launch_bounds__(256) void k_rpn_head_bwd(const RpnMaps g, const float *__restrict__ W1,
+                                                      const float *__restrict__ Wc, const float *__restrict__ Wr, int A,
+                                                      const float *__restrict__ hidden, uint32_t total_tiles,
+                                                      float *__restrict__ scratch) {
+  constexpr int NT = C / 32, LDC = C + 2;
+  extern __shared__ float smem[];
+  float *sX = smem;                     // [64][C + 2]: the t tile, then the f tile
+  float *sDT = sX + kRpnT * LDC;        // [64][C + 2]: dt
+  float *sB = sDT + kRpnT * LDC;        // [32][C + 2]: a chunk of W1's rows
+  float *sW2 = sB + 32 * LDC;           // [32][C + 2]: [Wc; Wr], zero-padded, for the whole kernel
+  float *sD = sW2 + 32 * LDC;           // [64][32 + 2]: D = [d_obj | d_reg | 0]
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave & 1, wn = wave >> 1;
+  const int l31 = lane & 31, kh = 16 * (lane >> 5);
+
+  for (int i = t; i < 32 * C; i += 256) {
+    const int n = i / C, c = i - n * C;
+    sW2[n * LDC + c] = rpn_w2(Wc, Wr, A, C, n, c);
+  }
+
+  f32x16 accW1[4], accW2, acc[2];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) accW1[q][r] = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) accW2[r] = 0.f;
+  float dbacc = 0.f;                    // thread c < C: db1[c]; thread C + n, n < 32: [dbc; dbr][n]
+
+  for (uint32_t tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
+    const int m = rpn_map_of(g, tile);
+    const int64_t rows = g.rows[m], row0 = (int64_t)(tile - g.first[m]) * kRpnT;
+    const float *__restrict__ dobj = g.obj[m];
+    const float *__restrict__ dreg = g.reg[m];
+    const float *__restrict__ tm = hidden + (g.hoff[m] + row0) * C;
+    const float *__restrict__ fm = g.f[m] + row0 * C;
+    const int64_t left = rows - row0;   // >= 1
+
+    __syncthreads();                    // the previous tile's reads are done (first tile: sW2 is complete)
+    for (int i = t; i < kRpnT * kRpnN2; i += 256) {
+      const int row = i >> 5, n = i & 31;
+      float v = 0.f;
+      if (row < left) {
+        if (n < A) v = dobj ? dobj[(row0 + row) * A + n] : 0.f;
+        else if (n < 8 * A) v = dreg ? dreg[(row0 + row) * (7 * A) + n - A] : 0.f;
+      }
+      sD[row * kRpnLD2 + n] = v;
+    }
+    for (int i = t; i < kRpnT * C; i += 256) {
+      const int row = i / C, c = i - row * C;
+      sX[row * LDC + c] = row < left ? tm[(int64_t)row * C + c] : 0.f;
+    }
+    __syncthreads();
+
+    // d[Wc; Wr] += D^T t: rows n (32), columns c, reduce over the 64 sites; wave w owns column tile w
+    if (wave < NT) {
+#pragma unroll 4
+      for (int kk = 0; kk < 16; ++kk) {
+#pragma unroll
+        for (int h = 0; h < kRpnT / 32; ++h) {
+          const int r_ = 32 * h + kk + kh;
+          accW2 = __builtin_amdgcn_mfma_f32_32x32x2f32(sD[r_ * kRpnLD2 + l31], sX[r_ * LDC + wave * 32 + l31], accW2, 0, 0, 0);
+        }
+      }
+    }
+    if (t >= C && t < C + kRpnN2) {
+      for (int r_ = 0; r_ < kRpnT; ++r_) dbacc += sD[r_ * kRpnLD2 + t - C];
+    }
+    // dt = (D [Wc; Wr]) . (t > 0): rows = sites (wm), columns = hidden units (tiles wn, wn + 2), reduce over n (32)
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[jj][r] = 0.f;
+#pragma unroll 4
+    for (int kk = 0; kk < 16; ++kk) {
+      const float a = sD[(wm * 32 + l31) * kRpnLD2 + kk + kh];
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) {
+        const int j = wn + 2 * jj;
+        if (j < NT) acc[jj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, sW2[(kk + kh) * LDC + j * 32 + l31], acc[jj], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      const int j = wn + 2 * jj;
+      if (j >= NT) continue;
+      const int col = j * 32 + l31;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = wm * 32 + rpn_acc_row(r, lane);
+        sDT[row * LDC + col] = sX[row * LDC + col] > 0.f ? acc[jj][r] : 0.f;
+      }
+    }
+    __syncthreads();                    // dt is complete; every read of the t tile is done
+
+    for (int i = t; i < kRpnT * C; i += 256) {
+      const int row = i / C, c = i - row * C;
+      sX[row * LDC + c] = row < left ? fm[(int64_t)row * C + c] : 0.f;
+    }
+    if (t < C) {
+      for (int r_ = 0; r_ < kRpnT; ++r_) dbacc += sDT[r_ * LDC + t];
+    }
+    __syncthreads();
+
+    // dW1 += dt^T f: rows c, columns k, reduce over the sites; wave w owns tiles q = w, w + 4, ... of the NT x NT grid
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+      const int q = wave + 4 * qq;
+      if (q >= NT * NT) continue;
+      const int ci = q / NT, kj = q - ci * NT;
+#pragma unroll 4
+      for (int kk = 0; kk < 16; ++kk) {
+#pragma unroll
+        for (int h = 0; h < kRpnT / 32; ++h) {
+          const int r_ = 32 * h + kk + kh;
+          accW1[qq] = __builtin_amdgcn_mfma_f32_32x32x2f32(sDT[r_ * LDC + ci * 32 + l31], sX[r_ * LDC + kj * 32 + l31],
+                                                           accW1[qq], 0, 0, 0);
+        }
+      }
+    }
+
+    // d_f = dt W1: rows = sites, columns k, reduce over the hidden unit c; dt read transposed
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[jj][r] = 0.f;
+    for (int c0 = 0; c0 < C; c0 += 32) {
+      __syncthreads();                  // the previous chunk's reads of sB are done
+      for (int i = t; i < 32 * C; i += 256) {
+        const int cc = i / C, k = i - cc * C;
+        sB[cc * LDC + k] = W1[(c0 + cc) * C + k];
+      }
+      __syncthreads();
+#pragma unroll 4
+      for (int kk = 0; kk < 16; ++kk) {
+        const float a = sDT[(wm * 32 + l31) * LDC + c0 + kk + kh];
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) {
+          const int j = wn + 2 * jj;
+          if (j < NT) acc[jj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, sB[(kk + kh) * LDC + j * 32 + l31], acc[jj], 0, 0, 0);
+        }
+      }
+    }
+    float *__restrict__ df = g.df[m] + row0 * C;
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      const int j = wn + 2 * jj;
+      if (j >= NT) continue;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = wm * 32 + rpn_acc_row(r, lane);
+        if (row < left) df[(int64_t)row * C + j * 32 + l31] = acc[jj][r];
+      }
+    }
+  }
+
+  // this workgroup's partial (a workgroup without a tile writes zeros)
+  float *__restrict__ part = scratch + (int64_t)blockIdx.x * rpn_partial_floats(C);
+#pragma unroll
+  for (int qq = 0; qq < 4; ++qq) {
+    const int q = wave + 4 * qq;
+    if (q >= NT * NT) continue;
+    const int ci = q / NT, kj = q - ci * NT;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) part[(ci * 32 + rpn_acc_row(r, lane)) * C + kj * 32 + l31] = accW1[qq][r];
+  }
+  if (wave < NT) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) part[C * C + rpn_acc_row(r, lane) * C + wave * 32 + l31] = accW2[r];
+  }
+  if (t < C + kRpnN2) part[C * C + 32 * C + t] = dbacc;
+}
+
+// the partials added in workgroup order, stored into the six gradients
+__global__ __launch_bounds__(256) void k_rpn_head_reduce(const float *__restrict__ scratch, int groups, int C, int A,
+                                                         float *__restrict__ dW1, float *__restrict__ db1,
+                                                         float *__restrict__ dWc, float *__restrict__ dbc,
+                                                         float *__restrict__ dWr, float *__restrict__ dbr) {
+  const int64_t per = rpn_partial_floats(C);
+  int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= per) return;
+  float s = scratch[i];
+  for (int p = 1; p < groups; ++p) s += scratch[(int64_t)p * per + i];
+  if (i < (int64_t)C * C) {
+    dW1[i] = s;
+    return;
+  }
+  i -= (int64_t)C * C;
+  if (i < 32 * C) {
+    const int n = (int)(i / C), c = (int)(i - (int64_t)n * C);
+    if (n < A) dWc[n * C + c] = s;
+    else if (n < 8 * A) dWr[(n - A) * C + c] = s;
+    return;
+  }
+  i -= 32 * C;
+  if (i < C) {
+    db1[i] = s;
+    return;
+  }
+  i -= C;
+  if (i < A) dbc[i] = s;
+  else if (i < 8 * A) dbr[i - A] = s;
+}
+
+static bool rpn_c_ok(int C) { return C >= 32 && C <= 128 && C % 32 == 0; }
+
+static size_t rpn_bwd_lds_bytes(int C) { return sizeof(float) * ((size_t)(2 * kRpnT + 64) * (C + 2) + kRpnT * kRpnLD2); }
+
+} // namespace aabr
+
+using namespace aabr;
+
+extern "C" int aabr_rpn_head_tile_rows(int C) { return rpn_c_ok(C) ? kRpnT : 0; }
+
+extern "C" int aabr_rpn_head_groups(int64_t total_tiles) {
+  if (total_tiles < 1) return 0;
+  return total_tiles < kRpnMaxGroups ? (int)total_tiles : kRpnMaxGroups;
+}
+
+extern "C" int64_t aabr_rpn_head_scratch_floats(int64_t total_tiles, int C, int A) {
+  if (total_tiles < 1 || !rpn_c_ok(C) || A < 1 || A > 4) return 0;
+  return (int64_t)aabr_rpn_head_groups(total_tiles) * rpn_partial_floats(C);
+}
+
+// checks the caller's records and builds the kernels' table; *total_tiles = 0 when every map is empty
+static int rpn_head_table(const AabrRpnMap *maps, int n_maps, int C, int A, bool backward, RpnMaps &g, int64_t *total_tiles) {
+  AABR_CHECK_ARG(n_maps >= 1 && n_maps <= kRpnMaxMaps, "n_maps must be 1..8");
+  AABR_CHECK_ARG(rpn_c_ok(C), "C must be 32, 64, 96 or 128");
+  AABR_CHECK_ARG(A >= 1 && A <= 4, "A must be 1..4");
+  AABR_CHECK_ARG(maps, "null pointer");
+  g = RpnMaps{};
+  g.n = n_maps;
+  int64_t tiles = 0, hoff = 0;
+  for (int m = 0; m < n_maps; ++m) {
+    const AabrRpnMap &q = maps[m];
+    AABR_CHECK_ARG(q.rows >= 0, "negative row count");
+    AABR_CHECK_ARG(q.rows <= (1LL << 40) / C, "map too large");
+    if (q.rows > 0) {
+      AABR_CHECK_ARG(q.features, "null features");
+      if (backward) AABR_CHECK_ARG(q.d_features, "null d_features");
+      else AABR_CHECK_ARG(q.objectness && q.box_regression, "null output");
+    }
+    g.f[m] = q.features, g.obj[m] = q.objectness, g.reg[m] = q.box_regression, g.df[m] = q.d_features;
+    g.rows[m] = q.rows, g.hoff[m] = hoff;
+    AABR_CHECK_ARG(tiles < (1LL << 31) - 1, "too many tiles");
+    g.first[m] = (uint32_t)tiles;
+    tiles += ceil_div(q.rows, kRpnT);
+    hoff += q.rows;
+  }
+  AABR_CHECK_ARG(tiles < (1LL << 31) - 1, "too many tiles");
+  for (int m = n_maps; m <= kRpnMaxMaps; ++m) g.first[m] = (uint32_t)tiles;
+  *total_tiles = tiles;
+  return AABR_OK;
+}
+
+extern "C" int aabr_rpn_head_forward(const AabrRpnMap *maps_host, int n_maps, int C, int A, const float *W1,
+                                     const float *b1, const float *Wc, const float *bc, const float *Wr, const float *br,
+                                     float *hidden, void *stream_) {
+  RpnMaps g;
+  int64_t tiles = 0;
+  const int rc = rpn_head_table(maps_host, n_maps, C, A, false, g, &tiles);
+  if (rc != AABR_OK) return rc;
+  AABR_CHECK_ARG(W1 && b1 && Wc && bc && Wr && br, "null pointer");
+  if (tiles == 0) return AABR_OK;
+  hipStream_t st = (hipStream_t)stream_;
+  const dim3 grid((unsigned)tiles), block(256);
+  switch (C) {
+  case 32: hipLaunchKernelGGL(k_rpn_head_fwd<32>, grid, block, 0, st, g, W1, b1, Wc, bc, Wr, br, A, hidden); break;
+  case 64: hipLaunchKernelGGL(k_rpn_head_fwd<64>, grid, block, 0, st, g, W1, b1, Wc, bc, Wr, br, A, hidden); break;
+  case 96: hipLaunchKernelGGL(k_rpn_head_fwd<96>, grid, block, 0, st, g, W1, b1, Wc, bc, Wr, br, A, hidden); break;
+  default: hipLaunchKernelGGL(k_rpn_head_fwd<128>, grid, block, 0, st, g, W1, b1, Wc, bc, Wr, br, A, hidden); break;
+  }
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+template <int C>
+static int rpn_head_bwd_launch(const RpnMaps &g, const float *W1, const float *Wc, const float *Wr, int A,
+                               const float *hidden, int64_t tiles, int groups, float *scratch, hipStream_t st) {
+  static DynLdsOnce attr;
+  const size_t lds = rpn_bwd_lds_bytes(C);
+  AABR_CHECK_HIP(dyn_lds_once(attr, (const void *)(k_rpn_head_bwd<C>), (int)lds));
+  hipLaunchKernelGGL(k_rpn_head_bwd<C>, dim3((unsigned)groups), dim3(256), lds, st, g, W1, Wc, Wr, A, hidden,
+                     (uint32_t)tiles, scratch);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+extern "C" int aabr_rpn_head_backward(const AabrRpnMap *maps_host, int n_maps, int C, int A, const float *W1,
+                                      const float *Wc, const float *Wr, const float *hidden, float *dW1, float *db1,
+                                      float *dWc, float *dbc, float *dWr, float *dbr, float *scratch, void *stream_) {
+  RpnMaps g;
+  int64_t tiles = 0;
+  int rc = rpn_head_table(maps_host, n_maps, C, A, true, g, &tiles);
+  if (rc != AABR_OK) return rc;
+  AABR_CHECK_ARG(W1 && Wc && Wr, "null pointer");
+  AABR_CHECK_ARG(dW1 && db1 && dWc && dbc && dWr && dbr, "null gradient pointer");
+  hipStream_t st = (hipStream_t)stream_;
+  if (tiles == 0) {                                   // empty sums: zeros, no kernel
+    AABR_CHECK_HIP(hipMemsetAsync(dW1, 0, sizeof(float) * C * C, st));
+    AABR_CHECK_HIP(hipMemsetAsync(db1, 0, sizeof(float) * C, st));
+    AABR_CHECK_HIP(hipMemsetAsync(dWc, 0, sizeof(float) * A * C, st));
+    AABR_CHECK_HIP(hipMemsetAsync(dbc, 0, sizeof(float) * A, st));
+    AABR_CHECK_HIP(hipMemsetAsync(dWr, 0, sizeof(float) * 7 * A * C, st));
+    AABR_CHECK_HIP(hipMemsetAsync(dbr, 0, sizeof(float) * 7 * A, st));
+    return AABR_OK;
+  }
+  AABR_CHECK_ARG(hidden, "null hidden");
+  AABR_CHECK_ARG(scratch, "null scratch");
+  const int groups = aabr_rpn_head_groups(tiles);
+  switch (C) {
+  case 32: rc = rpn_head_bwd_launch<32>(g, W1, Wc, Wr, A, hidden, tiles, groups, scratch, st); break;
+  case 64: rc = rpn_head_bwd_launch<64>(g, W1, Wc, Wr, A, hidden, tiles, groups, scratch, st); break;
+  case 96: rc = rpn_head_bwd_launch<96>(g, W1, Wc, Wr, A, hidden, tiles, groups, scratch, st); break;
+  default: rc = rpn_head_bwd_launch<128>(g, W1, Wc, Wr, A, hidden, tiles, groups, scratch, st); break;
+  }
+  if (rc != AABR_OK) return rc;
+  const int64_t per = rpn_partial_floats(C);
+  hipLaunchKernelGGL(k_rpn_head_reduce, dim3((unsigned)ceil_div(per, 256)), dim3(256), 0, st, scratch, groups, C, A, dW1,
+                     db1, dWc, dbc, dWr, dbr);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}

@@ -498,3 +498,134 @@ def rpn_loss(maps, objectness, box_regression, labels, base_anchors, batch_size_
            "labels": [l.contiguous() for l in lab], "targets": tgt}
     obj_loss, box_loss, sel, _ = _RpnLoss.apply(cfg, *objectness, *box_regression)
     return (obj_loss, box_loss, sel) if return_samples else (obj_loss, box_loss)
+
+
+# ---------------------------------------------------------------------------------------------------- the RPN head
+RPN_HEAD_MAX_MAPS, RPN_HEAD_MAX_ANCHORS = 8, 4
+RPN_HEAD_CHANNELS = (32, 64, 96, 128)
+
+
+class _RpnHead(torch.autograd.Function):
+    """SingleConvRPNHead_Sparse3D over every map in one launch (csrc/rpn_head.hip); the hidden activation is written to
+    memory only when some input requires a gradient"""
+
+    @staticmethod
+    def forward(ctx, A, W1, b1, Wc, bc, Wr, br, *feats):
+        lib = _hip.load()
+        dev = W1.device
+        C, n_maps = int(W1.shape[0]), len(feats)
+        params = [p.contiguous() for p in (W1, b1, Wc, bc, Wr, br)]
+        feats = [f.contiguous() for f in feats]
+        rows = [int(f.shape[0]) for f in feats]
+        obj = [torch.empty(v * A, dtype=torch.float32, device=dev) for v in rows]       # every element is written
+        reg = [torch.empty((v * A, 7), dtype=torch.float32, device=dev) for v in rows]
+        need = any(ctx.needs_input_grad)
+        hidden = torch.empty((sum(rows), C), dtype=torch.float32, device=dev) if need else None
+        tab = (_hip.AabrRpnMap * n_maps)()
+        for m in range(n_maps):
+            tab[m].features, tab[m].rows = ptr(feats[m]), rows[m]
+            tab[m].objectness, tab[m].box_regression = ptr(obj[m]), ptr(reg[m])
+        check(lib.aabr_rpn_head_forward(tab, n_maps, C, A, *[ptr(p) for p in params], ptr(hidden), stream()))
+        if need:
+            ctx.save_for_backward(hidden, params[0], params[2], params[4], *feats)
+        ctx.cfg = (A, C, n_maps, rows)
+        return tuple(obj) + tuple(reg)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        lib = _hip.load()
+        A, C, n_maps, rows = ctx.cfg
+        hidden, W1, Wc, Wr = ctx.saved_tensors[:4]
+        feats = ctx.saved_tensors[4:]
+        dev = W1.device
+        g_obj = [g.contiguous() if g is not None else None for g in grads[:n_maps]]
+        g_reg = [g.contiguous() if g is not None else None for g in grads[n_maps:]]
+        d_all = torch.empty((sum(rows), C), dtype=torch.float32, device=dev)           # every element is written
+        d_f = list(torch.split(d_all, rows))
+        sizes = (C * C, C, A * C, A, 7 * A * C, 7 * A)
+        d_p = list(torch.split(torch.empty(sum(sizes), dtype=torch.float32, device=dev), sizes))
+        t_rows = lib.aabr_rpn_head_tile_rows(C)
+        tiles = sum(-(-v // t_rows) for v in rows)
+        floats = int(lib.aabr_rpn_head_scratch_floats(tiles, C, A))
+        scr = _hip.workspace("rpn_head", floats, torch.float32, dev) if floats else None
+        tab = (_hip.AabrRpnMap * n_maps)()
+        for m in range(n_maps):
+            tab[m].features, tab[m].rows, tab[m].d_features = ptr(feats[m]), rows[m], ptr(d_f[m])
+            tab[m].objectness, tab[m].box_regression = ptr(g_obj[m]), ptr(g_reg[m])
+        check(lib.aabr_rpn_head_backward(tab, n_maps, C, A, ptr(W1), ptr(Wc), ptr(Wr), ptr(hidden),
+                                         *[ptr(p) for p in d_p], ptr(scr), stream()))
+        return (None, d_p[0].view(C, C), d_p[1], d_p[2].view(A, C), d_p[3], d_p[4].view(7 * A, C), d_p[5]) + tuple(d_f)
+
+
+def _as_out_in(name, w):
+    """a Conv2d weight [out, in, 1, 1] or a Linear weight [out, in] -> [out, in]"""
+    if w.dim() == 4 and tuple(w.shape[2:]) == (1, 1):
+        return w.reshape(w.shape[0], w.shape[1])
+    if w.dim() != 2:
+        raise ValueError("rpn_head: %s must be [out, in] or [out, in, 1, 1], got %s" % (name, tuple(w.shape)))
+    return w
+
+
+def rpn_head(features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b):
+    """SingleConvRPNHead_Sparse3D.forward (modeling/rpn/rpn_sparse3d.py:109-131) for all maps at once:
+      t = relu(f conv_w^T + conv_b), objectness = t cls_w^T + cls_b, box_regression = t reg_w^T + reg_b
+    features: a list (1..8 maps) of SparseConvNetTensors or of [V_m, C] fp32 tensors; the weights as [out, in] or the
+    reference's Conv2d [out, in, 1, 1]: conv_w [C, C], cls_w [A, C], reg_w [7 A, C] (channel a 7 + j, 'box_toghter').
+    C in {32, 64, 96, 128}, 1 <= A <= 4.  Returns (objectness, box_regression): lists over the maps of [V_m A] and
+    [V_m A, 7] in the [site, yaw] flatten order rpn_proposals, rpn_label_matches and rpn_loss read.
+    Device work: forward 1 library launch whatever the number of maps (nothing concatenated, the hidden activation
+    reaches memory only when a gradient is required); backward 2 (the fused main kernel and the in-order reduction of its
+    per-workgroup partials: deterministic, no atomics).  No host read."""
+    feats = [f.features if hasattr(f, "features") else f for f in features]
+    if not 1 <= len(feats) <= RPN_HEAD_MAX_MAPS:
+        raise ValueError("rpn_head: 1 to %d maps, got %d" % (RPN_HEAD_MAX_MAPS, len(feats)))
+    w1, wc, wr = _as_out_in("conv_w", conv_w), _as_out_in("cls_w", cls_w), _as_out_in("reg_w", reg_w)
+    for k, t in [("conv_w", w1), ("conv_b", conv_b), ("cls_w", wc), ("cls_b", cls_b), ("reg_w", wr), ("reg_b", reg_b)] + \
+            [("features[%d]" % i, f) for i, f in enumerate(feats)]:
+        if t.dtype != torch.float32:
+            raise TypeError("rpn_head: %s must be float32, got %s (bf16 feature storage is not part of this path)"
+                            % (k, t.dtype))
+    C, A = int(w1.shape[1]), int(wc.shape[0])
+    if C not in RPN_HEAD_CHANNELS:
+        raise ValueError("rpn_head: C = %d; supported: a multiple of 32 from 32 to 128" % C)
+    if not 1 <= A <= RPN_HEAD_MAX_ANCHORS:
+        raise ValueError("rpn_head: A = %d anchors per site; supported: 1 to %d" % (A, RPN_HEAD_MAX_ANCHORS))
+    if tuple(w1.shape) != (C, C) or tuple(wc.shape) != (A, C) or tuple(wr.shape) != (7 * A, C):
+        raise ValueError("rpn_head: conv_w [C, C], cls_w [A, C], reg_w [7 A, C]; got %s, %s, %s"
+                         % (tuple(w1.shape), tuple(wc.shape), tuple(wr.shape)))
+    if tuple(conv_b.shape) != (C,) or tuple(cls_b.shape) != (A,) or tuple(reg_b.shape) != (7 * A,):
+        raise ValueError("rpn_head: the biases must be [C], [A] and [7 A]")
+    for i, f in enumerate(feats):
+        if f.dim() != 2 or int(f.shape[1]) != C:
+            raise ValueError("rpn_head: features[%d] must be [V, %d], got %s" % (i, C, tuple(f.shape)))
+    _hip.require_gpu(feats[0])
+    out = _RpnHead.apply(A, w1, conv_b, wc, cls_b, wr, reg_b, *feats)
+    return list(out[:len(feats)]), list(out[len(feats):])
+
+
+class _Cfg(object):
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def clone(self):
+        return self
+
+
+def rpn_cfg(C=32, anchor_sizes=((0.4, 1.5, 1.5), (1.5, 1.5, 1.0)), yaws=(0, -1.57), strides=((8, 8, 8), (16, 16, 16)),
+            voxel_scale=20.0, pre_nms_top_n=(200, 200), post_nms_top_n=(50, 50), nms_thresh=0.5, rpn_only=False,
+            add_gt_proposals=False, separate=(), separate_rpn=True, batch_size_per_image=256, positive_fraction=0.5,
+            classes=("background", "wall", "door")):
+    """a plain attribute tree with the cfg keys the RPN modules read, named as in the reference's config/defaults.py
+    (pre / post_nms_top_n: (train, test)) -- for smoke(), the timing tool and the tests, which have no yacs config"""
+    rpn = _Cfg(ANCHOR_SIZES_3D=[list(s) for s in anchor_sizes], YAWS=tuple(yaws), RATIOS=[[1, 1, 1]] * len(yaws),
+               USE_YAWS=[1] * len(anchor_sizes), ANCHOR_STRIDE=[list(s) for s in strides], USE_FPN=True,
+               FG_IOU_THRESHOLD=0.55, BG_IOU_THRESHOLD=0.2, YAW_THRESHOLD=0.7, BATCH_SIZE_PER_IMAGE=batch_size_per_image,
+               POSITIVE_FRACTION=positive_fraction, NMS_THRESH=nms_thresh, NMS_AUG_THICKNESS_Y_Z=[0.3, 0.3],
+               LABEL_AUG_THICKNESS_Y_TAR_ANC=[0.4, 0], LABEL_AUG_THICKNESS_Z_TAR_ANC=[0.8, 0],
+               FPN_PRE_NMS_TOP_N_TRAIN=pre_nms_top_n[0], FPN_PRE_NMS_TOP_N_TEST=pre_nms_top_n[1],
+               FPN_POST_NMS_TOP_N_TRAIN=post_nms_top_n[0], FPN_POST_NMS_TOP_N_TEST=post_nms_top_n[1],
+               RPN_HEAD="SingleConvRPNHead_Sparse3D", ADD_GT_PROPOSALS=add_gt_proposals)
+    model = _Cfg(RPN=rpn, RPN__ONLY=rpn_only, SEPARATE_CLASSES=list(separate), SEPARATE_RPN=separate_rpn, IOU_CRITERIA=6,
+                 LOSS=_Cfg(YAW_MODE="Diff"))
+    return _Cfg(MODEL=model, SPARSE3D=_Cfg(VOXEL_SCALE=voxel_scale, nPlaneMap=C), INPUT=_Cfg(CLASSES=list(classes)))

@@ -40,7 +40,7 @@ const char *aabr_last_error(void);
  * 640 = the box head's loss (aabr_roi_targets, aabr_roi_box_loss_*).
  * The multi-level ROI pooler (aabr_roi_pool_*, AabrRoiLevel) came after 640 WITHOUT a bump: it adds symbols and one new
  * record only, no existing signature or layout changed, so a binding written for 640 still matches.  The box head's
- * dense layers (aabr_roi_mlp_*) came the same way: symbols only. */
+ * dense layers (aabr_roi_mlp_*) and the RPN head (aabr_rpn_head_*, AabrRpnMap) came the same way: symbols only. */
 #define AABR_ABI_VERSION 640
 int aabr_version(void);
 /* Tuning knobs for experiments and tests (no counterpart in the reference; the defaults are what ships): CONV_WIDE,
@@ -1090,6 +1090,48 @@ int aabr_roi_mlp_backward_weight(const float *dY, const float *Y, const float *A
                                  int64_t M, int64_t N, int64_t K, int64_t perm_hw, float *dW, float *db, float *scratch,
                                  void *stream);
 int aabr_roi_mlp_pack_fc6(const float *W, int64_t N, int64_t R, int64_t hw, float *Wp, void *stream);
+
+/* ---- the RPN head (csrc/rpn_head.hip): SingleConvRPNHead_Sparse3D (modeling/rpn/rpn_sparse3d.py:81-131) over the rows
+ * of every feature map in one launch, fp32 storage only, on v_mfma_f32_32x32x2_f32 (every element an exact fmaf chain):
+ *   t = relu(f W1^T + b1),  obj = t Wc^T + bc,  reg = t Wr^T + br
+ * with f [rows, C] the rows of a map and W1 [C, C], Wc [A, C], Wr [7 A, C] the Conv2d weights viewed as [out, in].
+ * Output channel order is the reference's permute + reshape ('box_toghter'): objectness [rows, A], box_regression
+ * [rows, A, 7] with channel a 7 + j -- the [site, yaw] flatten order aabr_rpn_decode_maps, aabr_rpn_label_generation and
+ * aabr_rpn_loss_forward read.
+ *   shapes: 1 <= n_maps <= 8; C in {32, 64, 96, 128}; 1 <= A <= 4; any rows >= 0 (a map with 0 rows contributes
+ *   nothing and its pointers are not read).  Anything else, a null pointer or a negative size: AABR_EINVAL.
+ * maps_host: a host array of n_maps records (read during the call, passed to the kernels by value; nothing is
+ *   concatenated).  `hidden`: one fp32 [sum of rows, C] allocation, map-major, or NULL.
+ * aabr_rpn_head_forward: a workgroup owns aabr_rpn_head_tile_rows(C) consecutive rows of one map, forms t in LDS and
+ *   both outputs from it; t is stored to `hidden` only when that is not NULL (evaluation: it never reaches memory; the
+ *   outputs are the same bits either way).  1 launch, whatever n_maps; none when every map is empty.
+ * aabr_rpn_head_backward: the records' objectness / box_regression point at d_obj / d_reg (read only; NULL = zeros),
+ *   d_features receives d_f (every element stored exactly once).  dW1 [C, C], db1 [C], dWc [A, C], dbc [A],
+ *   dWr [7 A, C], dbr [7 A] are overwritten.  Deterministic, no float atomics: tile i of the concatenated tile list goes
+ *   to workgroup i mod G, G = aabr_rpn_head_groups(total_tiles); ONE fused kernel forms dt = (d_out [Wc; Wr]) . (t > 0),
+ *   stores d_f = dt W1 and keeps its share of all six sums in registers; each workgroup writes one partial to
+ *   `scratch` (fp32 [aabr_rpn_head_scratch_floats(total_tiles, C, A)]) and a second launch adds the partials in
+ *   workgroup order.  2 launches (main, reduce; no weight pack is needed), whatever n_maps.  Every map empty: no
+ *   launch, the six gradients are set to zero (memsets).
+ * Host functions of the shape only (never of the device), so tests can place shapes on both sides:
+ *   aabr_rpn_head_tile_rows(C): 64 for a supported C, else 0.  total_tiles = sum over maps of ceil(rows / tile_rows).
+ *   aabr_rpn_head_groups(total_tiles): min(total_tiles, 256); 0 for total_tiles < 1.
+ *   aabr_rpn_head_scratch_floats(total_tiles, C, A): groups * (C C + 32 C + C + 32); 0 for an unsupported shape.      */
+typedef struct AabrRpnMap {
+  const float *features;       /* [rows, C] fp32 feature rows of the map                                              */
+  int64_t rows;
+  float *objectness;           /* forward: output [rows, A]; backward: d_obj (read only) or NULL                      */
+  float *box_regression;       /* forward: output [rows, A, 7]; backward: d_reg (read only) or NULL                   */
+  float *d_features;           /* backward: output [rows, C]; unused by forward                                       */
+} AabrRpnMap;
+int aabr_rpn_head_tile_rows(int C);
+int aabr_rpn_head_groups(int64_t total_tiles);
+int64_t aabr_rpn_head_scratch_floats(int64_t total_tiles, int C, int A);
+int aabr_rpn_head_forward(const AabrRpnMap *maps_host, int n_maps, int C, int A, const float *W1, const float *b1,
+                          const float *Wc, const float *bc, const float *Wr, const float *br, float *hidden, void *stream);
+int aabr_rpn_head_backward(const AabrRpnMap *maps_host, int n_maps, int C, int A, const float *W1, const float *Wc,
+                           const float *Wr, const float *hidden, float *dW1, float *db1, float *dWc, float *dbc,
+                           float *dWr, float *dbr, float *scratch, void *stream);
 
 #ifdef __cplusplus
 }
