@@ -24,10 +24,12 @@ enum Knob { AABR_KNOB_LIST(AABR_KNOB_ENUM) K_COUNT };
 #undef AABR_KNOB_ENUM
 int knob(Knob k);            // kKnobUnset when neither the environment nor aabr_set_knob gave a value
 
-#define AABR_CHECK_ARG(cond, msg)                                   \
+// AABR_CHECK_ARG_AS: the same check inside a helper, reported under the name `fn` of the entry point that called it
+#define AABR_CHECK_ARG_AS(fn, cond, msg)                            \
   do {                                                              \
-    if (!(cond)) { aabr::set_error("%s: %s", __func__, msg); return AABR_EINVAL; } \
+    if (!(cond)) { aabr::set_error("%s: %s", fn, msg); return AABR_EINVAL; } \
   } while (0)
+#define AABR_CHECK_ARG(cond, msg) AABR_CHECK_ARG_AS(__func__, cond, msg)
 
 #define AABR_CHECK_LAUNCH()                                                   \
   do {                                                                        \

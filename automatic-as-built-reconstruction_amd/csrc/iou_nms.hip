@@ -11,9 +11,13 @@
 //                 resolved on the diagonal 64x64 bit block by one wave in registers
 //                 (wavefront-level), then the kept rows' words are OR-reduced in parallel.
 // Everything stays on the device; the keep list never round-trips through the host.
+// Also here: the RPN stages over an example's anchor list (decode, padded logits, fused top-k, label generation).  The
+// list's table, its host-side checks, the locate and the anchor of a site live in anchor_list.h; the box decode / encode
+// in nms_shared.h.
 #include "common.h"
 #include "iou_math.h"
 #include "nms_shared.h"
+#include "anchor_list.h"
 
 namespace aabr {
 using namespace aabr_iou;
@@ -64,72 +68,46 @@ __global__ __launch_bounds__(256) void k_scale_by_z(float *__restrict__ iou, int
 // RPN glue: anchors from sparse locations + BoxCoder3D.decode_centroid_box for the selected
 // (top-k) anchors, fused (reference: modeling/rpn/anchor_generator_sparse3d.py:88-104,
 // modeling/box_coder_3d.py:53-80, second/pytorch/core/box_torch_ops.py:118-154 with
-// smooth_dim=True, utils3d/geometric_torch.py:4-10).  Flat anchor index t = site * A + yaw.
+// smooth_dim=True, utils3d/geometric_torch.py:4-10).  Flat anchor index t = site * A + yaw.  The anchor and the decode
+// are anchor_box7 (anchor_list.h) and box_decode7 (nms_shared.h), here over a one-map AnchorGeom.
 struct RpnDecodeParams {
-  float inv_scale_num;      // voxel_scale
-  float stride[3];
-  float weights[7];
+  AnchorGeom g;
+  BoxEncodeW w;
   float clip;               // bbox_xform_clip
 };
+static_assert(sizeof(RpnDecodeParams) + 8 * 8 <= kKernelArgBytes, "k_rpn_decode: the struct and 8 words");
 
-__global__ __launch_bounds__(256) void k_rpn_decode(const int32_t *__restrict__ site_coords, int64_t site0,
+__global__ __launch_bounds__(256) void k_rpn_decode(RpnDecodeParams p, int64_t site0,
                                                     const int64_t *__restrict__ sel, int64_t k,
                                                     const float *__restrict__ regression, int64_t reg0,
                                                     const float *__restrict__ base_anchors, int A,
-                                                    RpnDecodeParams p, float *__restrict__ boxes) {
+                                                    float *__restrict__ boxes) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= k) return;
   const int64_t t = sel[i];
-  const int64_t site = site0 + t / A;
-  const int a = (int)(t % A);
-  const float *ba = base_anchors + 7 * a;
-  float an[7];
-#pragma unroll
-  for (int d = 0; d < 3; ++d)  // (location.float() + 0) / voxel_scale * stride  + base
-    an[d] = (float)site_coords[4 * site + d] / p.inv_scale_num * p.stride[d] + ba[d];
-#pragma unroll
-  for (int d = 3; d < 7; ++d) an[d] = 0.0f + ba[d];
-  const float *r = regression + 7 * (reg0 + t);
-  float e[7];
-#pragma unroll
-  for (int d = 0; d < 7; ++d) e[d] = r[d] / p.weights[d];
-#pragma unroll
-  for (int d = 3; d < 6; ++d) e[d] = e[d] > p.clip ? p.clip : e[d];
-  // second_box_decode: anchors split as (xa, ya, za, wa, la, ha, ra)
-  const float diagonal = sqrtf(an[4] * an[4] + an[3] * an[3]);
-  float o[7];
-  o[0] = e[0] * diagonal + an[0];
-  o[1] = e[1] * diagonal + an[1];
-  o[2] = e[2] * an[5] + an[2];
-  o[3] = (e[3] + 1) * an[3];   // wg = (wt + 1) * wa
-  o[4] = (e[4] + 1) * an[4];   // lg = (lt + 1) * la
-  o[5] = (e[5] + 1) * an[5];
-  float rg = e[6] + an[6];
-  const float period = 3.14159265358979323846f;
-  rg = rg - floorf(rg / period + 0.5f) * period; // limit_period(., 0.5, pi)
-  o[6] = rg;
+  const AnchorLoc L = {0, (int)(t % A), site0 + t / A};
+  float an[7], o[7];
+  anchor_box7(p.g, base_anchors, A, L, an);
+  box_decode7(regression + 7 * (reg0 + t), an, p.w, p.clip, o);
 #pragma unroll
   for (int d = 0; d < 7; ++d) boxes[7 * i + d] = o[d];
 }
 
 // Cross-scale form (the shape RPNPostProcessor actually runs in: cat_scales_obj_reg regroups the scales
 // example-major, rpn_sparse3d.py:19-77, then ONE top-k + decode + NMS per example, rpn/inference_3d.py:95-149).
-// `selected[i]` indexes the example's concatenated anchor list [map][site][yaw]; the segment table maps it
+// `selected[i]` indexes the example's concatenated anchor list [map][site][yaw]; anchor_locate (anchor_list.h) maps it
 // back to (map, site row, yaw) so neither the anchors nor the concatenated regression are ever materialised.
 // Also fused: objectness sigmoid of the selected logits and the boxlist_nms_3d thickness clamps
 // (structures/boxlist_ops_3d.py:42-44) into a second, NMS-only copy of the boxes.
-constexpr int kMaxRpnMaps = 8;
 struct RpnMapsParams {
-  const int32_t *coords[kMaxRpnMaps];   // [V_m,4] site lists
-  const float *logits[kMaxRpnMaps];     // [V_m*A]
-  const float *regression[kMaxRpnMaps]; // [V_m*A,7]
-  int32_t seg_begin[kMaxRpnMaps + 1];   // first local anchor index of map m in this example's list
-  int32_t site_begin[kMaxRpnMaps];      // first site row of this example in map m
-  float stride[kMaxRpnMaps][3];
-  int n_maps, A;
-  float voxel_scale, clip, nms_min_yx, nms_min_z;
-  float weights[7];
+  AnchorSegs s;                            // one example: row 0
+  AnchorGeom g;
+  const float *logits[kAnchorMaxMaps];     // [V_m*A]
+  const float *regression[kAnchorMaxMaps]; // [V_m*A,7]
+  float clip, nms_min_yx, nms_min_z;
+  BoxEncodeW w;
 };
+static_assert(sizeof(RpnMapsParams) + 6 * 8 <= kKernelArgBytes, "k_rpn_decode_maps: the struct and 6 words");
 
 __global__ __launch_bounds__(256) void k_rpn_decode_maps(RpnMapsParams p, const int64_t *__restrict__ sel, int64_t k,
                                                          const float *__restrict__ base_anchors /*[n_maps*A,7]*/,
@@ -137,39 +115,12 @@ __global__ __launch_bounds__(256) void k_rpn_decode_maps(RpnMapsParams p, const 
                                                          float *__restrict__ scores) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= k) return;
-  const int32_t t = (int32_t)sel[i];
-  int m = 0;
-#pragma unroll
-  for (int q = 1; q < kMaxRpnMaps; ++q)
-    if (q < p.n_maps && t >= p.seg_begin[q]) m = q;
-  const int32_t r = t - p.seg_begin[m];
-  const int64_t site = (int64_t)p.site_begin[m] + r / p.A;
-  const int a = r % p.A;
-  const int32_t *sc = p.coords[m] + 4 * site;
-  const float *ba = base_anchors + 7 * ((int64_t)m * p.A + a);
-  float an[7];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) an[d] = (float)sc[d] / p.voxel_scale * p.stride[m][d] + ba[d];
-#pragma unroll
-  for (int d = 3; d < 7; ++d) an[d] = 0.0f + ba[d];
-  const int64_t row = site * p.A + a;
-  const float *rg7 = p.regression[m] + 7 * row;
-  float e[7];
-#pragma unroll
-  for (int d = 0; d < 7; ++d) e[d] = rg7[d] / p.weights[d];
-#pragma unroll
-  for (int d = 3; d < 6; ++d) e[d] = e[d] > p.clip ? p.clip : e[d];
-  const float diagonal = sqrtf(an[4] * an[4] + an[3] * an[3]);
-  float o[7];
-  o[0] = e[0] * diagonal + an[0];
-  o[1] = e[1] * diagonal + an[1];
-  o[2] = e[2] * an[5] + an[2];
-  o[3] = (e[3] + 1) * an[3];
-  o[4] = (e[4] + 1) * an[4];
-  o[5] = (e[5] + 1) * an[5];
-  float rg = e[6] + an[6];
-  const float period = 3.14159265358979323846f;
-  o[6] = rg - floorf(rg / period + 0.5f) * period;
+  const AnchorLoc L = anchor_locate(p.s, 0, sel[i]);
+  const int m = L.m;
+  const int64_t row = L.row * p.s.A + L.a;
+  float an[7], o[7];
+  anchor_box7(p.g, base_anchors, p.s.A, L, an);
+  box_decode7(p.regression[m] + 7 * row, an, p.w, p.clip, o);
 #pragma unroll
   for (int d = 0; d < 7; ++d) boxes[7 * i + d] = o[d];
   if (nms_boxes) {
@@ -292,13 +243,12 @@ extern "C" int aabr_rpn_decode(const int32_t *site_coords, int64_t site_begin, c
   if (k == 0) return AABR_OK;
   AABR_CHECK_ARG(site_coords && selected && regression && base_anchors && boxes, "null pointer");
   RpnDecodeParams p;
-  p.inv_scale_num = voxel_scale;
-  for (int d = 0; d < 3; ++d) p.stride[d] = stride_host[d];
-  for (int d = 0; d < 7; ++d) p.weights[d] = weights_host[d];
+  const void *coords[1] = {site_coords};
+  fill_anchor_geom(p.g, 1, coords, stride_host, voxel_scale);
+  for (int d = 0; d < 7; ++d) p.w.w[d] = weights_host[d];
   p.clip = clip;
-  hipLaunchKernelGGL(k_rpn_decode, dim3((unsigned)ceil_div(k, 256)), dim3(256), 0, (hipStream_t)stream_,
-                     site_coords, site_begin, selected, k, regression, reg_begin, base_anchors, num_anchors, p,
-                     boxes);
+  hipLaunchKernelGGL(k_rpn_decode, dim3((unsigned)ceil_div(k, 256)), dim3(256), 0, (hipStream_t)stream_, p, site_begin,
+                     selected, k, regression, reg_begin, base_anchors, num_anchors, boxes);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }
@@ -310,30 +260,24 @@ extern "C" int aabr_rpn_decode_maps(int n_maps, const void *const *coords_ptrs, 
                                     const float *weights_host, float clip, float nms_min_yx, float nms_min_z,
                                     const int64_t *selected, int64_t k, float *boxes, float *nms_boxes,
                                     float *scores, void *stream_) {
-  AABR_CHECK_ARG(n_maps >= 1 && n_maps <= kMaxRpnMaps && k >= 0 && num_anchors > 0 && voxel_scale > 0,
+  AABR_CHECK_ARG(n_maps >= 1 && n_maps <= kAnchorMaxMaps && k >= 0 && num_anchors > 0 && voxel_scale > 0,
                  "bad arguments");
   AABR_CHECK_ARG(coords_ptrs && logit_ptrs && regression_ptrs && seg_begin_host && site_begin_host &&
                      strides_host && weights_host, "null host table");
   if (k == 0) return AABR_OK;
   AABR_CHECK_ARG(selected && base_anchors && boxes, "null pointer");
   RpnMapsParams p;
-  for (int m = 0; m < kMaxRpnMaps; ++m) {
-    const bool on = m < n_maps;
-    p.coords[m] = on ? (const int32_t *)coords_ptrs[m] : nullptr;
-    p.logits[m] = on ? (const float *)logit_ptrs[m] : nullptr;
-    p.regression[m] = on ? (const float *)regression_ptrs[m] : nullptr;
-    p.site_begin[m] = on ? site_begin_host[m] : 0;
-    for (int d = 0; d < 3; ++d) p.stride[m][d] = on ? strides_host[3 * m + d] : 0.f;
-  }
-  for (int m = 0; m <= kMaxRpnMaps; ++m) p.seg_begin[m] = seg_begin_host[m <= n_maps ? m : n_maps];
-  for (int m = 0; m < n_maps; ++m) {
-    AABR_CHECK_ARG(p.seg_begin[m + 1] >= p.seg_begin[m], "segment table must be non-decreasing");
-    AABR_CHECK_ARG(p.seg_begin[m + 1] == p.seg_begin[m] || (p.coords[m] && p.logits[m] && p.regression[m]),
+  int rc = fill_anchor_segs(p.s, __func__, n_maps, num_anchors, 0, 1, seg_begin_host, site_begin_host, nullptr);
+  if (rc != AABR_OK) return rc;
+  fill_anchor_geom(p.g, n_maps, coords_ptrs, strides_host, voxel_scale);
+  for (int m = 0; m < kAnchorMaxMaps; ++m) {
+    p.logits[m] = m < n_maps ? (const float *)logit_ptrs[m] : nullptr;
+    p.regression[m] = m < n_maps ? (const float *)regression_ptrs[m] : nullptr;
+    AABR_CHECK_ARG(p.s.seg[0][m + 1] == p.s.seg[0][m] || (p.g.coords[m] && p.logits[m] && p.regression[m]),
                    "null map pointer");
   }
-  p.n_maps = n_maps; p.A = num_anchors; p.voxel_scale = voxel_scale; p.clip = clip;
-  p.nms_min_yx = nms_min_yx; p.nms_min_z = nms_min_z;
-  for (int d = 0; d < 7; ++d) p.weights[d] = weights_host[d];
+  p.clip = clip; p.nms_min_yx = nms_min_yx; p.nms_min_z = nms_min_z;
+  for (int d = 0; d < 7; ++d) p.w.w[d] = weights_host[d];
   hipLaunchKernelGGL(k_rpn_decode_maps, dim3((unsigned)ceil_div(k, 256)), dim3(256), 0, (hipStream_t)stream_, p,
                      selected, k, base_anchors, boxes, nms_boxes, scores);
   AABR_CHECK_LAUNCH();
@@ -382,13 +326,17 @@ extern "C" int aabr_nms_sorted(const float *dets4, int64_t n, float thresh, uint
 //   aabr_rpn_proposals_batch: per example the decode of the selected anchors (aabr_rpn_decode_maps) and the rotated
 //                           NMS of the decoded list (aabr_rotate_nms_sorted), looped HERE; the numbers kept stay on
 //                           the device (meta[b][0]) for the caller to read once.
-constexpr int kMaxRpnBatch = 16;
 struct RpnGatherParams {
-  const float *logits[kMaxRpnMaps];
-  int32_t seg_begin[kMaxRpnBatch][kMaxRpnMaps + 1]; // in anchors, per example
-  int32_t src_begin[kMaxRpnBatch][kMaxRpnMaps];     // first anchor of example b in map m's logit vector
-  int n_maps, nb;
+  AnchorSegs s;
+  const float *logits[kAnchorMaxMaps];
 };
+static_assert(sizeof(RpnGatherParams) + 2 * 8 <= kKernelArgBytes, "k_rpn_gather_logits: the struct and 2 words");
+// the j-th logit of example b's list
+__device__ __forceinline__ float rpn_list_logit(const RpnGatherParams &p, int b, int64_t j) {
+  int m;
+  const int64_t i = anchor_flat(p.s, b, j, m);
+  return p.logits[m][i];
+}
 
 // RPN label generation, fused (reference: RPNLossComputation.match_targets_to_anchors, modeling/rpn/loss_3d.py:91-100:
 // `boxlist_iou_3d(target, anchor, aug_thickness, criterion, flag='rpn_label_generation')` over the anchors of ALL maps
@@ -396,7 +344,7 @@ struct RpnGatherParams {
 // make_rpn_loss_evaluator builds it, loss_3d.py:338-344 / modeling/matcher.py:50-196: yaw mask, best ground truth
 // per anchor, the two thresholds, set_low_quality_matches_ and its ignore-nearby pass).
 // One thread per anchor of one example: the anchor is generated from its site (anchor_generator_sparse3d.py:88-104)
-// through the same segment table as k_rpn_decode_maps, the example's ground-truth boxes sit in LDS with the
+// through the same anchor table (anchor_list.h) as k_rpn_decode_maps, the example's ground-truth boxes sit in LDS with the
 // target-side thickness clamps applied (rotate_nms_3d_torch.py:59-66), every pair goes through the same
 // iou_eval_entry as aabr_boxes_iou_3d.  The [G, N] matrix is never stored (only when the caller asks for it):
 // set_low_quality_matches_ needs every ground truth's row maximum before any anchor can be labelled, so the pairs are
@@ -404,30 +352,20 @@ struct RpnGatherParams {
 // order-preserving integer keys: max is order-independent, the result is bit-reproducible), PASS 1 re-evaluates the
 // same pairs with the same instructions and labels the anchors.
 struct RpnLabelParams {
-  const int32_t *coords[kMaxRpnMaps];
-  const float *targets[kMaxRpnBatch];               // [G_b, 7] yx_zb
-  int32_t n_targets[kMaxRpnBatch];
-  int32_t gt_begin[kMaxRpnBatch];                   // first row-maximum key of example b
-  int32_t seg_begin[kMaxRpnBatch][kMaxRpnMaps + 1]; // in anchors, per example
-  int32_t site_begin[kMaxRpnBatch][kMaxRpnMaps];
-  int64_t out_begin[kMaxRpnBatch];                  // first anchor of example b in the concatenated outputs
-  int64_t iou_begin[kMaxRpnBatch];                  // first float of example b's [G_b, N_b] matrix
-  float stride[kMaxRpnMaps][3];
+  AnchorSegs s;
+  AnchorGeom g;
+  const float *targets[kAnchorMaxBatch];            // [G_b, 7] yx_zb
+  int32_t n_targets[kAnchorMaxBatch];
+  int32_t gt_begin[kAnchorMaxBatch];                // first row-maximum key of example b
+  int64_t out_begin[kAnchorMaxBatch];               // first anchor of example b in the concatenated outputs
+  int64_t iou_begin[kAnchorMaxBatch];               // first float of example b's [G_b, N_b] matrix
   float aug[4];                                     // target_Y, target_Z, anchor_Y, anchor_Z
-  int n_maps, A, criterion, only_xy, use_yaw, allow_low;
-  float voxel_scale, fg, bg, yaw_thr;
+  int criterion, only_xy, use_yaw, allow_low;
+  float fg, bg, yaw_thr;
   float w[7];                                       // BoxCoder3D weights of the regression targets
 };
+static_assert(sizeof(RpnLabelParams) + 6 * 8 <= kKernelArgBytes, "k_rpn_label_maps: the struct and 6 pointers");
 constexpr int kLabelTgtChunk = 128;
-
-// order-preserving float -> uint32 key (0 = below every float): the row maxima are reduced with integer atomicMax
-__device__ __forceinline__ uint32_t label_key(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float label_unkey(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
 
 // match-quality entry of (ground truth g, this thread's anchor): the IoU of boxlist_iou_3d and, masked, what the
 // Matcher sees (matcher.py:50-55: `match_quality_matrix * (abs(yaw_diff) < yaw_threshold).float()`; yaw_diff =
@@ -461,26 +399,14 @@ __global__ __launch_bounds__(256) void k_rpn_label_maps(RpnLabelParams p, const 
   __shared__ uint32_t s_key[kLabelTgtChunk];        // PASS 0: this workgroup's row maxima
   __shared__ float s_hi[kLabelTgtChunk][2];         // PASS 1: row maximum, ignore threshold
   const int b = blockIdx.y;
-  const int64_t N = p.seg_begin[b][p.n_maps];
+  const int64_t N = p.s.seg[b][p.s.n_maps];
   if ((int64_t)blockIdx.x * blockDim.x >= N) return;   // grid.x is sized for the largest example
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int G = p.n_targets[b];
   float a5[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, az0 = 0.f, az1 = 0.f;
   float an[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (t < N) {
-    int m = 0;
-#pragma unroll
-    for (int q = 1; q < kMaxRpnMaps; ++q)
-      if (q < p.n_maps && t >= p.seg_begin[b][q]) m = q;
-    const int32_t r = (int32_t)(t - p.seg_begin[b][m]);
-    const int64_t site = (int64_t)p.site_begin[b][m] + r / p.A;
-    const int a = r % p.A;
-    const int32_t *sc = p.coords[m] + 4 * site;
-    const float *ba = base_anchors + 7 * ((int64_t)m * p.A + a);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) an[d] = (float)sc[d] / p.voxel_scale * p.stride[m][d] + ba[d];
-#pragma unroll
-    for (int d = 3; d < 7; ++d) an[d] = 0.0f + ba[d];
+    anchor_box7(p.g, base_anchors, p.s.A, anchor_locate(p.s, b, t), an);
     const float th = an[3] < p.aug[2] ? p.aug[2] : an[3];
     const float h = an[5] < p.aug[3] ? p.aug[3] : an[5];
     a5[0] = an[0]; a5[1] = an[1]; a5[2] = th; a5[3] = an[4]; a5[4] = an[6];
@@ -501,7 +427,7 @@ __global__ __launch_bounds__(256) void k_rpn_label_maps(RpnLabelParams p, const 
       s_tz[threadIdx.x][0] = tb[2]; s_tz[threadIdx.x][1] = tb[2] + h;
       if (PASS == 0) s_key[threadIdx.x] = 0u;
       if (PASS == 1 && p.allow_low) {
-        const float hi = label_unkey(gt_best[p.gt_begin[b] + g0 + threadIdx.x]);
+        const float hi = float_order_unkey(gt_best[p.gt_begin[b] + g0 + threadIdx.x]);
         const float thr = hi - 0.05f;                 // matcher.py:166-167
         s_hi[threadIdx.x][0] = hi;
         s_hi[threadIdx.x][1] = 0.02f > thr ? 0.02f : thr;
@@ -515,7 +441,7 @@ __global__ __launch_bounds__(256) void k_rpn_label_maps(RpnLabelParams p, const 
       float raw;
       const float v = label_pair(p, t5, s_tz[g][0], s_tz[g][1], a5, az0, az1, &raw);
       if (PASS == 0) {
-        uint32_t k = t < N ? label_key(v) : 0u;
+        uint32_t k = t < N ? float_order_key(v) : 0u;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
           const uint32_t q = (uint32_t)__shfl_xor((int)k, o, 64);
@@ -576,32 +502,32 @@ __global__ __launch_bounds__(256) void k_rpn_gather_logits(RpnGatherParams p, in
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= lmax) return;
   float v = -__builtin_inff();
-  if (j < p.seg_begin[b][p.n_maps]) {
-    int m = 0;
-    while (m + 1 < p.n_maps && j >= p.seg_begin[b][m + 1]) ++m;
-    v = p.logits[m][(int64_t)p.src_begin[b][m] + (j - p.seg_begin[b][m])];
-  }
+  if (j < p.s.seg[b][p.s.n_maps]) v = rpn_list_logit(p, b, j);
   out[(int64_t)b * lmax + j] = v;
+}
+
+// the table and the logit pointers of the padded-logit and top-k entries
+static int fill_gather(RpnGatherParams &p, const char *fn, int n_maps, const void *const *logit_ptrs, int nb,
+                       const int32_t *seg_begin_host, const int32_t *site_begin_host, int num_anchors, int64_t *nmax) {
+  int rc = fill_anchor_segs(p.s, fn, n_maps, num_anchors, 0, nb, seg_begin_host, site_begin_host, nmax);
+  if (rc != AABR_OK) return rc;
+  for (int m = 0; m < kAnchorMaxMaps; ++m) {
+    p.logits[m] = m < n_maps ? (const float *)logit_ptrs[m] : nullptr;
+    for (int b = 0; b < nb; ++b) AABR_CHECK_ARG_AS(fn, p.s.seg[b][m + 1] == p.s.seg[b][m] || p.logits[m], "null map pointer");
+  }
+  return AABR_OK;
 }
 
 extern "C" int aabr_rpn_gather_logits(int n_maps, const void *const *logit_ptrs, int nb, const int32_t *seg_begin_host,
                                       const int32_t *site_begin_host, int num_anchors, int64_t lmax, float *out,
                                       void *stream_) {
-  AABR_CHECK_ARG(n_maps >= 1 && n_maps <= kMaxRpnMaps && nb >= 1 && nb <= kMaxRpnBatch && num_anchors > 0 && lmax > 0,
+  AABR_CHECK_ARG(n_maps >= 1 && n_maps <= kAnchorMaxMaps && nb >= 1 && nb <= kAnchorMaxBatch && num_anchors > 0 && lmax > 0,
                  "bad arguments (at most 8 maps, 16 examples)");
   AABR_CHECK_ARG(logit_ptrs && seg_begin_host && site_begin_host && out, "null pointer");
   RpnGatherParams p;
-  p.n_maps = n_maps; p.nb = nb;
-  for (int m = 0; m < kMaxRpnMaps; ++m) p.logits[m] = m < n_maps ? (const float *)logit_ptrs[m] : nullptr;
-  for (int b = 0; b < nb; ++b) {
-    for (int m = 0; m <= n_maps; ++m) p.seg_begin[b][m] = seg_begin_host[b * (n_maps + 1) + m];
-    for (int m = 0; m < n_maps; ++m) {
-      p.src_begin[b][m] = site_begin_host[b * n_maps + m] * num_anchors;
-      AABR_CHECK_ARG(p.seg_begin[b][m + 1] >= p.seg_begin[b][m], "segment table must be non-decreasing");
-      AABR_CHECK_ARG(p.seg_begin[b][m + 1] == p.seg_begin[b][m] || p.logits[m], "null map pointer");
-    }
-    AABR_CHECK_ARG(p.seg_begin[b][n_maps] <= lmax, "lmax smaller than an example's list");
-  }
+  int rc = fill_gather(p, __func__, n_maps, logit_ptrs, nb, seg_begin_host, site_begin_host, num_anchors, nullptr);
+  if (rc != AABR_OK) return rc;
+  for (int b = 0; b < nb; ++b) AABR_CHECK_ARG(p.s.seg[b][n_maps] <= lmax, "lmax smaller than an example's list");
   hipLaunchKernelGGL(k_rpn_gather_logits, dim3((unsigned)ceil_div(lmax, 256), (unsigned)nb), dim3(256), 0,
                      (hipStream_t)stream_, p, lmax, out);
   AABR_CHECK_LAUNCH();
@@ -624,20 +550,12 @@ extern "C" int aabr_rpn_gather_logits(int n_maps, const void *const *logit_ptrs,
 constexpr int kTopkBins = 4096, kTopkCand = 4096;
 struct RpnTopkParams {
   RpnGatherParams g;
-  int32_t k[kMaxRpnBatch];
+  int32_t k[kAnchorMaxBatch];
 };
+static_assert(sizeof(RpnTopkParams) + 4 * 8 <= kKernelArgBytes, "k_rpn_topk_*: the struct and up to 4 words");
 // per example: hist1[4096], hist2[4096], then 8 control words, then the candidates (uint64 x kTopkCand)
 constexpr int kTopkCtl = 8, kTopkWordsPerEx = 2 * kTopkBins + kTopkCtl + 2 * kTopkCand;
 enum { kTkBin1 = 0, kTkAbove1 = 1, kTkCount = 2, kTkOverflow = 3 };
-__device__ inline uint32_t topk_key(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);          // ascending in the float order (-0 < +0: harmless)
-}
-__device__ inline float topk_logit(const RpnGatherParams &p, int b, int64_t j) {
-  int m = 0;
-  while (m + 1 < p.n_maps && j >= p.seg_begin[b][m + 1]) ++m;
-  return p.logits[m][(int64_t)p.src_begin[b][m] + (j - p.seg_begin[b][m])];
-}
 // the bin (from the top) in which the running count reaches `need`: returns it, and the count ABOVE it through `above`
 __device__ inline int topk_find_bin(const int32_t *__restrict__ hist, int need, int &above) {
   __shared__ int s_part[256], s_bin, s_above;
@@ -672,7 +590,7 @@ __global__ __launch_bounds__(256) void k_rpn_topk_hist(RpnTopkParams p, int32_t 
   __shared__ int32_t s_hist[kTopkBins];
   const int b = blockIdx.y;
   int32_t *sc = scratch + (int64_t)b * kTopkWordsPerEx;
-  const int64_t n = p.g.seg_begin[b][p.g.n_maps];
+  const int64_t n = p.g.s.seg[b][p.g.s.n_maps];
   int bin1 = 0;
   if (LEVEL == 2) {
     int above;
@@ -682,7 +600,7 @@ __global__ __launch_bounds__(256) void k_rpn_topk_hist(RpnTopkParams p, int32_t 
   for (int q = threadIdx.x; q < kTopkBins; q += 256) s_hist[q] = 0;
   __syncthreads();
   for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
-    const uint32_t key = topk_key(topk_logit(p.g, b, j));
+    const uint32_t key = float_order_key(rpn_list_logit(p.g, b, j));
     if (LEVEL == 1) atomicAdd(&s_hist[key >> 20], 1);
     else if ((int)(key >> 20) == bin1) atomicAdd(&s_hist[(key >> 8) & 4095u], 1);
   }
@@ -696,13 +614,13 @@ __global__ __launch_bounds__(256) void k_rpn_topk_compact(RpnTopkParams p, int32
   int32_t *sc = scratch + (int64_t)b * kTopkWordsPerEx;
   int32_t *ctl = sc + 2 * kTopkBins;
   unsigned long long *cand = reinterpret_cast<unsigned long long *>(ctl + kTopkCtl);
-  const int64_t n = p.g.seg_begin[b][p.g.n_maps];
+  const int64_t n = p.g.s.seg[b][p.g.s.n_maps];
   const int bin1 = ctl[kTkBin1];
   int above2;
   const int bin2 = topk_find_bin(sc + kTopkBins, p.k[b] - ctl[kTkAbove1], above2);
   const uint32_t thr = ((uint32_t)bin1 << 12) | (uint32_t)bin2;
   for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
-    const uint32_t key = topk_key(topk_logit(p.g, b, j));
+    const uint32_t key = float_order_key(rpn_list_logit(p.g, b, j));
     if ((key >> 8) >= thr) {
       const int pos = atomicAdd(&ctl[kTkCount], 1);
       if (pos < kTopkCand) cand[pos] = ((unsigned long long)(~key) << 32) | (unsigned long long)(uint32_t)j;
@@ -746,28 +664,20 @@ extern "C" int aabr_rpn_topk_maps(int n_maps, const void *const *logit_ptrs, int
                                   const int32_t *site_begin_host, int num_anchors, const int32_t *k_host, int64_t *selected,
                                   int64_t sel_stride, int32_t *info, int32_t *scratch, void *stream_) {
   hipStream_t st = (hipStream_t)stream_;
-  AABR_CHECK_ARG(n_maps >= 1 && n_maps <= kMaxRpnMaps && nb >= 1 && nb <= kMaxRpnBatch && num_anchors > 0,
+  AABR_CHECK_ARG(n_maps >= 1 && n_maps <= kAnchorMaxMaps && nb >= 1 && nb <= kAnchorMaxBatch && num_anchors > 0,
                  "bad arguments (at most 8 maps, 16 examples)");
   AABR_CHECK_ARG(logit_ptrs && seg_begin_host && site_begin_host && k_host && selected && info && scratch, "null pointer");
   AABR_CHECK_ARG(((uintptr_t)scratch & 7) == 0, "scratch must be 8-byte aligned");
   RpnTopkParams p;
-  p.g.n_maps = n_maps; p.g.nb = nb;
   int64_t nmax = 0;
-  for (int m = 0; m < kMaxRpnMaps; ++m) p.g.logits[m] = m < n_maps ? (const float *)logit_ptrs[m] : nullptr;
+  int rc = fill_gather(p.g, __func__, n_maps, logit_ptrs, nb, seg_begin_host, site_begin_host, num_anchors, &nmax);
+  if (rc != AABR_OK) return rc;
   for (int b = 0; b < nb; ++b) {
-    for (int m = 0; m <= n_maps; ++m) p.g.seg_begin[b][m] = seg_begin_host[b * (n_maps + 1) + m];
-    for (int m = 0; m < n_maps; ++m) {
-      p.g.src_begin[b][m] = site_begin_host[b * n_maps + m] * num_anchors;
-      AABR_CHECK_ARG(p.g.seg_begin[b][m + 1] >= p.g.seg_begin[b][m], "segment table must be non-decreasing");
-      AABR_CHECK_ARG(p.g.seg_begin[b][m + 1] == p.g.seg_begin[b][m] || p.g.logits[m], "null map pointer");
-    }
-    const int64_t n = p.g.seg_begin[b][n_maps];
-    AABR_CHECK_ARG(k_host[b] >= 0 && k_host[b] <= n && k_host[b] <= kTopkCand / 2 && k_host[b] <= sel_stride,
-                   "k: 0 .. min(anchors of the example, 2048, sel_stride)");
+    AABR_CHECK_ARG(k_host[b] >= 0 && k_host[b] <= p.g.s.seg[b][n_maps] && k_host[b] <= kTopkCand / 2 &&
+                       k_host[b] <= sel_stride, "k: 0 .. min(anchors of the example, 2048, sel_stride)");
     p.k[b] = k_host[b];
-    nmax = n > nmax ? n : nmax;
   }
-  for (int b = nb; b < kMaxRpnBatch; ++b) p.k[b] = 0;
+  for (int b = nb; b < kAnchorMaxBatch; ++b) p.k[b] = 0;
   AABR_CHECK_HIP(hipMemsetAsync(scratch, 0, (size_t)nb * kTopkWordsPerEx * sizeof(int32_t), st));
   if (nmax == 0) { AABR_CHECK_HIP(hipMemsetAsync(info, 0, (size_t)nb * 2 * sizeof(int32_t), st)); return AABR_OK; }
   int64_t gx = ceil_div(nmax, 256 * 8);
@@ -788,7 +698,7 @@ extern "C" int aabr_rpn_proposals_batch(int n_maps, const void *const *coords_pt
                                         const int64_t *selected, int64_t k, float *boxes, float *nms_boxes,
                                         float *scores, float nms_thresh, int only_xy, int64_t post_max, uint64_t *mask,
                                         int64_t *keep, int32_t *meta, void *stream_) {
-  AABR_CHECK_ARG(nb >= 1 && nb <= kMaxRpnBatch && k >= 0 && seg_begin_host && site_begin_host, "bad arguments");
+  AABR_CHECK_ARG(nb >= 1 && nb <= kAnchorMaxBatch && k >= 0 && seg_begin_host && site_begin_host, "bad arguments");
   AABR_CHECK_ARG(selected && boxes && nms_boxes && scores && mask && keep && meta, "null pointer");
   const int64_t cb = ceil_div(k > 0 ? k : 1, (int64_t)64);
   for (int b = 0; b < nb; ++b) {
@@ -814,46 +724,37 @@ extern "C" int aabr_rpn_label_generation_targets(int n_maps, const void *const *
                                          int allow_low_quality_matches, int64_t *matched_idx, float *matched_val,
                                          float *iou_out, uint32_t *row_max_scratch, const float *weights_host,
                                          float *regression_targets, void *stream_) {
-  AABR_CHECK_ARG(n_maps >= 1 && n_maps <= kMaxRpnMaps && nb >= 0 && nb <= kMaxRpnBatch && num_anchors > 0 &&
+  AABR_CHECK_ARG(n_maps >= 1 && n_maps <= kAnchorMaxMaps && nb >= 0 && nb <= kAnchorMaxBatch && num_anchors > 0 &&
                      voxel_scale > 0, "bad arguments (<= 8 maps, <= 16 examples)");
   AABR_CHECK_ARG(coords_ptrs && seg_begin_host && site_begin_host && strides_host && target_ptrs && n_targets_host &&
                      aug_host, "null host table");
   if (nb == 0) return AABR_OK;
   RpnLabelParams p;
-  for (int m = 0; m < kMaxRpnMaps; ++m) {
-    p.coords[m] = m < n_maps ? (const int32_t *)coords_ptrs[m] : nullptr;
-    for (int d = 0; d < 3; ++d) p.stride[m][d] = m < n_maps ? strides_host[3 * m + d] : 0.f;
-  }
   int64_t out = 0, mat = 0, nmax = 0;
+  int rc = fill_anchor_segs(p.s, __func__, n_maps, num_anchors, 0, nb, seg_begin_host, site_begin_host, &nmax);
+  if (rc != AABR_OK) return rc;
+  fill_anchor_geom(p.g, n_maps, coords_ptrs, strides_host, voxel_scale);
   int32_t gts = 0;
-  for (int b = 0; b < kMaxRpnBatch; ++b) {
+  for (int b = 0; b < kAnchorMaxBatch; ++b) {
     const bool on = b < nb;
-    for (int m = 0; m <= kMaxRpnMaps; ++m)
-      p.seg_begin[b][m] = on ? seg_begin_host[b * (n_maps + 1) + (m <= n_maps ? m : n_maps)] : 0;
-    for (int m = 0; m < kMaxRpnMaps; ++m) p.site_begin[b][m] = on && m < n_maps ? site_begin_host[b * n_maps + m] : 0;
     p.targets[b] = on ? (const float *)target_ptrs[b] : nullptr;
     p.n_targets[b] = on ? n_targets_host[b] : 0;
     p.out_begin[b] = out;
     p.iou_begin[b] = mat;
     p.gt_begin[b] = gts;
-    if (on) gts += p.n_targets[b];
-    if (on) {
-      AABR_CHECK_ARG(p.n_targets[b] >= 0 && (p.n_targets[b] == 0 || p.targets[b]), "null target list");
-      for (int m = 0; m < n_maps; ++m) {
-        AABR_CHECK_ARG(p.seg_begin[b][m + 1] >= p.seg_begin[b][m], "segment table must be non-decreasing");
-        AABR_CHECK_ARG(p.seg_begin[b][m + 1] == p.seg_begin[b][m] || p.coords[m], "null map pointer");
-      }
-      const int64_t n = p.seg_begin[b][n_maps];
-      out += n;
-      mat += n * p.n_targets[b];
-      if (n > nmax) nmax = n;
-    }
+    if (!on) continue;
+    gts += p.n_targets[b];
+    AABR_CHECK_ARG(p.n_targets[b] >= 0 && (p.n_targets[b] == 0 || p.targets[b]), "null target list");
+    for (int m = 0; m < n_maps; ++m)
+      AABR_CHECK_ARG(p.s.seg[b][m + 1] == p.s.seg[b][m] || p.g.coords[m], "null map pointer");
+    const int64_t n = p.s.seg[b][n_maps];
+    out += n;
+    mat += n * p.n_targets[b];
   }
   if (nmax == 0) return AABR_OK;
   AABR_CHECK_ARG(base_anchors && matched_idx && matched_val, "null pointer");
   for (int d = 0; d < 4; ++d) p.aug[d] = aug_host[d];
-  p.n_maps = n_maps; p.A = num_anchors; p.criterion = criterion; p.only_xy = only_xy;
-  p.voxel_scale = voxel_scale; p.fg = fg_iou; p.bg = bg_iou;
+  p.criterion = criterion; p.only_xy = only_xy; p.fg = fg_iou; p.bg = bg_iou;
   // Matcher.yaw_diff_constrain: no mask when the threshold exceeds 1.58 (matcher.py:51-52)
   p.use_yaw = yaw_threshold > 1.58f ? 0 : 1;
   p.yaw_thr = yaw_threshold;

@@ -377,9 +377,9 @@ extern "C" int aabr_roi_targets(const float *proposals, const float *targets, co
   std::vector<const void *> label_ptrs(nb);
   for (int b = 0; b < nb; ++b) label_ptrs[b] = n_host[b] ? (const void *)(labels + p.prop_begin[b]) : nullptr;
   LossParams sp = {};
-  sp.n_maps = 1; sp.A = 1; sp.flat = 1; sp.with_loss = 0; sp.label_mode = 1; sp.k_pos0 = num_pos_max;
+  sp.s.n_maps = 1; sp.s.A = 1; sp.flat = 1; sp.with_loss = 0; sp.label_mode = 1; sp.k_pos0 = num_pos_max;
   sp.B = batch_size_per_image; sp.seed = seed; sp.beta = 1.f;
-  int rc = run_select_chunks(sp, nb, seg.data(), nullptr, label_ptrs.data(), nullptr, nullptr, nullptr, sel, sinfo, scratch,
+  int rc = run_select_chunks(sp, __func__, nb, seg.data(), nullptr, label_ptrs.data(), nullptr, nullptr, nullptr, sel, sinfo, scratch,
                              st);
   if (rc != AABR_OK) return rc;
   hipLaunchKernelGGL(k_roi_compact, dim3((unsigned)nb), dim3(256), 0, st, p, sel, sinfo, proposals, labels,

@@ -6,7 +6,7 @@
 // The reference concatenates the scales example-major (cat_scales_obj_reg), runs two torch.nonzero (host syncs) and two
 // randperm per example and gathers.  Here nothing is concatenated: anchor (b, m, row r, a) is read where the RPN head
 // wrote it, objectness / regression index (site_begin[b][m] + r) * A + a of map m, label / target index
-// seg_begin[b][m] + r * A + a of example b's lists (the tables aabr_rpn_label_generation_targets takes).
+// seg_begin[b][m] + r * A + a of example b's lists (the tables aabr_rpn_label_generation_targets takes; anchor_list.h).
 //
 // Selection rule (restated in include/aabr_hip.h): every anchor gets a 32-bit key, a chain of murmur3's finaliser
 //   h = fmix32(seed ^ 0x9E3779B9); h = fmix32(h ^ v) for v in (example, map, x, y, z, anchor)
@@ -45,11 +45,11 @@ __global__ __launch_bounds__(64) void k_loss_finalize(int nb, const float *__res
 }
 
 // the select of every chunk, then (with the loss) the finalize: 1 memset + 4 launches per chunk + 1
-int run_select(LossParams &p, int nb, const int32_t *seg_begin_host, const int32_t *site_begin_host,
+int run_select(LossParams &p, const char *fn, int nb, const int32_t *seg_begin_host, const int32_t *site_begin_host,
                const void *const *label_ptrs, const void *const *target_ptrs, void *const *pos_masks,
                void *const *neg_masks, int64_t *selected, int32_t *info, float *obj_loss, float *box_loss,
                int32_t *scratch, hipStream_t st) {
-  int rc = run_select_chunks(p, nb, seg_begin_host, site_begin_host, label_ptrs, target_ptrs, pos_masks, neg_masks, selected,
+  int rc = run_select_chunks(p, fn, nb, seg_begin_host, site_begin_host, label_ptrs, target_ptrs, pos_masks, neg_masks, selected,
                              info, scratch, st);
   if (rc != AABR_OK) return rc;
   if (p.with_loss)
@@ -60,8 +60,8 @@ int run_select(LossParams &p, int nb, const int32_t *seg_begin_host, const int32
 }
 
 struct GradPtrs {
-  void *obj[kLossMaxMaps];
-  void *reg[kLossMaxMaps];
+  void *obj[kAnchorMaxMaps];
+  void *reg[kAnchorMaxMaps];
 };
 // gradients at the sampled anchors (the caller has zeroed the gradient buffers)
 __global__ __launch_bounds__(256) void k_loss_backward(LossParams p, const int64_t *__restrict__ sel,
@@ -75,8 +75,8 @@ __global__ __launch_bounds__(256) void k_loss_backward(LossParams p, const int64
   const int64_t s_i = sel[(int64_t)e * p.B + i];
   if (s_i < 0) return;
   const int64_t j = s_i - p.out_begin[b];
-  const Loc L = locate(p, b, j);
-  const int64_t oi = L.row * p.A + L.a;
+  const AnchorLoc L = locate(p, b, j);
+  const int64_t oi = L.row * p.s.A + L.a;
   const float x = ld(p.obj[L.m], oi, p.bf16);
   const float y = i < kp ? 1.f : 0.f;
   const float go = *g_obj / (float)ns;
@@ -138,21 +138,21 @@ extern "C" int aabr_rpn_loss_forward(int n_maps, const void *const *coords_ptrs,
                                      const void *const *label_ptrs, const void *const *target_ptrs, uint32_t seed,
                                      int batch_size_per_image, int num_pos_max, float beta, int64_t *selected,
                                      int32_t *info, float *obj_loss, float *box_loss, int32_t *scratch, void *stream_) {
-  AABR_CHECK_ARG(n_maps >= 1 && n_maps <= kLossMaxMaps && nb >= 1 && num_anchors > 0, "bad arguments (1 .. 8 maps, >= 1 example)");
+  AABR_CHECK_ARG(n_maps >= 1 && n_maps <= kAnchorMaxMaps && nb >= 1 && num_anchors > 0, "bad arguments (1 .. 8 maps, >= 1 example)");
   AABR_CHECK_ARG(batch_size_per_image >= 1 && batch_size_per_image <= kLossMaxB && num_pos_max >= 0 &&
                      num_pos_max <= batch_size_per_image && beta > 0.f,
                  "need 1 <= batch_size_per_image <= 512, 0 <= num_pos_max <= batch_size_per_image, beta > 0");
   AABR_CHECK_ARG(coords_ptrs && obj_ptrs && reg_ptrs && seg_begin_host && site_begin_host && label_ptrs && target_ptrs &&
                      selected && info && obj_loss && box_loss && scratch, "null pointer");
   LossParams p = {};
-  p.n_maps = n_maps; p.A = num_anchors; p.flat = 0; p.with_loss = 1; p.label_mode = 0; p.bf16 = input_bf16 ? 1 : 0;
+  p.s.n_maps = n_maps; p.s.A = num_anchors; p.flat = 0; p.with_loss = 1; p.label_mode = 0; p.bf16 = input_bf16 ? 1 : 0;
   p.k_pos0 = num_pos_max; p.B = batch_size_per_image; p.seed = seed; p.beta = beta;
   for (int m = 0; m < n_maps; ++m) {
     p.obj[m] = obj_ptrs[m];
     p.reg[m] = reg_ptrs[m];
     p.coords[m] = (const int32_t *)coords_ptrs[m];
   }
-  return run_select(p, nb, seg_begin_host, site_begin_host, label_ptrs, target_ptrs, nullptr, nullptr, selected, info,
+  return run_select(p, __func__, nb, seg_begin_host, site_begin_host, label_ptrs, target_ptrs, nullptr, nullptr, selected, info,
                     obj_loss, box_loss, scratch, (hipStream_t)stream_);
 }
 
@@ -163,12 +163,12 @@ extern "C" int aabr_rpn_loss_backward(int n_maps, const void *const *obj_ptrs, c
                                       const int32_t *info, const float *grad_obj_loss, const float *grad_box_loss,
                                       void *const *grad_obj_ptrs, void *const *grad_reg_ptrs, void *stream_) {
   hipStream_t st = (hipStream_t)stream_;
-  AABR_CHECK_ARG(n_maps >= 1 && n_maps <= kLossMaxMaps && nb >= 1 && num_anchors > 0 && batch_size_per_image >= 1 &&
+  AABR_CHECK_ARG(n_maps >= 1 && n_maps <= kAnchorMaxMaps && nb >= 1 && num_anchors > 0 && batch_size_per_image >= 1 &&
                      batch_size_per_image <= kLossMaxB && beta > 0.f, "bad arguments");
   AABR_CHECK_ARG(obj_ptrs && reg_ptrs && seg_begin_host && site_begin_host && target_ptrs && selected && info &&
                      grad_obj_loss && grad_box_loss && grad_obj_ptrs && grad_reg_ptrs, "null pointer");
   LossParams p = {};
-  p.n_maps = n_maps; p.A = num_anchors; p.with_loss = 1; p.bf16 = input_bf16 ? 1 : 0; p.B = batch_size_per_image;
+  p.s.n_maps = n_maps; p.s.A = num_anchors; p.with_loss = 1; p.bf16 = input_bf16 ? 1 : 0; p.B = batch_size_per_image;
   p.beta = beta;
   GradPtrs g = {};
   for (int m = 0; m < n_maps; ++m) {
@@ -183,15 +183,15 @@ extern "C" int aabr_rpn_loss_backward(int n_maps, const void *const *obj_ptrs, c
     out_begin[b] = total;
     total += seg_begin_host[b * (n_maps + 1) + n_maps];
   }
-  for (int b0 = 0; b0 < nb; b0 += kLossMaxBatch) {
-    const int nbc = nb - b0 < kLossMaxBatch ? nb - b0 : kLossMaxBatch;
+  for (int b0 = 0; b0 < nb; b0 += kAnchorMaxBatch) {
+    const int nbc = nb - b0 < kAnchorMaxBatch ? nb - b0 : kAnchorMaxBatch;
     int64_t nmax = 0;
-    int rc = fill_chunk(p, b0, nbc, seg_begin_host, site_begin_host, nullptr, target_ptrs, out_begin.data(), nullptr,
+    int rc = fill_chunk(p, __func__, b0, nbc, seg_begin_host, site_begin_host, nullptr, target_ptrs, out_begin.data(), nullptr,
                         nullptr, false, nmax);
     if (rc != AABR_OK) return rc;
     for (int m = 0; m < n_maps; ++m)
       for (int b = 0; b < nbc; ++b)
-        AABR_CHECK_ARG(p.seg[b][m + 1] == p.seg[b][m] || (g.obj[m] && g.reg[m]), "null gradient pointer");
+        AABR_CHECK_ARG(p.s.seg[b][m + 1] == p.s.seg[b][m] || (g.obj[m] && g.reg[m]), "null gradient pointer");
     hipLaunchKernelGGL(k_loss_backward, dim3((unsigned)ceil_div(batch_size_per_image, 256), (unsigned)nbc), dim3(256), 0, st,
                        p, selected, info, grad_obj_loss, grad_box_loss, g);
   }
@@ -213,9 +213,9 @@ extern "C" int aabr_sample_list(int nb, const void *const *label_ptrs, const int
     seg[2 * b + 1] = (int32_t)n_host[b];
   }
   LossParams p = {};
-  p.n_maps = 1; p.A = 1; p.flat = 1; p.with_loss = 0; p.label_mode = 1; p.k_pos0 = num_pos_max;
+  p.s.n_maps = 1; p.s.A = 1; p.flat = 1; p.with_loss = 0; p.label_mode = 1; p.k_pos0 = num_pos_max;
   p.B = batch_size_per_image; p.seed = seed; p.beta = 1.f;
-  return run_select(p, nb, seg.data(), nullptr, label_ptrs, nullptr, pos_masks, neg_masks, selected, info, nullptr, nullptr,
+  return run_select(p, __func__, nb, seg.data(), nullptr, label_ptrs, nullptr, pos_masks, neg_masks, selected, info, nullptr, nullptr,
                     scratch, (hipStream_t)stream_);
 }
 

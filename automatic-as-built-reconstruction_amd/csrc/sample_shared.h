@@ -3,15 +3,16 @@
 // and the exact select (K1 .. K4 of the scheme rpn_loss.hip describes), with their host-side launcher.  rpn_loss.hip wraps
 // them into aabr_rpn_loss_forward / aabr_sample_list; roi_loss.hip runs the same kernels over the box head's labels.
 // Nothing here is copied: both files compile this code (the kernels sit in an unnamed namespace, one instance per file).
+// The anchor table (LossParams::s), its host-side checks and the locate behind the key are anchor_list.h's.
 #pragma once
 #include "common.h"
+#include "anchor_list.h"
 
 #include <vector>
 
 namespace aabr {
 
 namespace {
-constexpr int kLossMaxMaps = 8, kLossMaxBatch = 16;
 constexpr int kLossBins = 4096, kLossCand = 1024, kLossMaxB = 512;
 constexpr int kLossCtl = 16;
 // scratch: per example hist1[class][4096], hist2[class][4096], ctl[16] (one block, cleared by one memset per call); then
@@ -24,20 +25,21 @@ enum { kCtlK = 0, kCtlBin1 = 2, kCtlBelow1 = 4, kCtlCount = 6, kCtlOverflow = 8,
 constexpr int kInfoWords = 8;
 
 struct LossParams {
-  int32_t n_maps, nb, nb_total, A, flat, with_loss, label_mode, bf16, example0, k_pos0, B;
+  AnchorSegs s;                    // the chunk's examples; flat: one map, A = 1, list index = row
+  int32_t nb_total, flat, with_loss, label_mode, bf16, example0, k_pos0, B;
   uint32_t seed;
   float beta;
-  const void *obj[kLossMaxMaps];
-  const void *reg[kLossMaxMaps];
-  const int32_t *coords[kLossMaxMaps];
-  int32_t seg[kLossMaxBatch][kLossMaxMaps + 1];
-  int32_t site[kLossMaxBatch][kLossMaxMaps];
-  const int64_t *labels[kLossMaxBatch];
-  const float *targets[kLossMaxBatch];
-  int64_t out_begin[kLossMaxBatch];
-  uint8_t *pos_mask[kLossMaxBatch];
-  uint8_t *neg_mask[kLossMaxBatch];
+  const void *obj[kAnchorMaxMaps];
+  const void *reg[kAnchorMaxMaps];
+  const int32_t *coords[kAnchorMaxMaps];
+  const int64_t *labels[kAnchorMaxBatch];
+  const float *targets[kAnchorMaxBatch];
+  int64_t out_begin[kAnchorMaxBatch];
+  uint8_t *pos_mask[kAnchorMaxBatch];
+  uint8_t *neg_mask[kAnchorMaxBatch];
 };
+// the largest set beside it: k_loss_backward (rpn_loss.hip), 4 pointers and GradPtrs, 2 x 8 pointers
+static_assert(sizeof(LossParams) + (4 + 2 * kAnchorMaxMaps) * 8 <= kKernelArgBytes, "k_loss_*: the struct and 20 pointers");
 
 __device__ inline uint32_t fmix32(uint32_t h) {
   h ^= h >> 16;
@@ -53,18 +55,11 @@ __device__ inline int class_of(const LossParams &p, int64_t v) {
   if (p.label_mode == 0) return v >= 0 ? 0 : (v == -1 ? 1 : -1);
   return v >= 1 ? 0 : (v == 0 ? 1 : -1);
 }
-struct Loc {
-  int m, a;
-  int64_t row;
-};
-__device__ inline Loc locate(const LossParams &p, int b, int64_t j) {
+__device__ inline AnchorLoc locate(const LossParams &p, int b, int64_t j) {
   if (p.flat) return {0, 0, j};
-  int m = 0;
-  while (m + 1 < p.n_maps && j >= p.seg[b][m + 1]) ++m;
-  const int64_t q = j - p.seg[b][m];
-  return {m, (int)(q % p.A), p.site[b][m] + q / p.A};
+  return anchor_locate(p.s, b, j);
 }
-__device__ inline uint32_t key_of(const LossParams &p, int b, int64_t j, const Loc &L) {
+__device__ inline uint32_t key_of(const LossParams &p, int b, int64_t j, const AnchorLoc &L) {
   uint32_t h = fmix32(p.seed ^ 0x9E3779B9u);
   h = fmix32(h ^ (uint32_t)(p.example0 + b));
   if (p.flat) return fmix32(h ^ (uint32_t)j);
@@ -80,7 +75,7 @@ __device__ inline bool cand_less(const LossParams &p, int b, unsigned long long 
   if ((x >> 32) != (y >> 32)) return (x >> 32) < (y >> 32);
   const uint32_t jx = (uint32_t)x, jy = (uint32_t)y;
   if (p.flat || jx == jy || jx == 0xffffffffu || jy == 0xffffffffu) return jx < jy;
-  const Loc lx = locate(p, b, jx), ly = locate(p, b, jy);
+  const AnchorLoc lx = locate(p, b, jx), ly = locate(p, b, jy);
   if (lx.m != ly.m) return lx.m < ly.m;
   const int32_t *cx = p.coords[lx.m] + lx.row * 4, *cy = p.coords[ly.m] + ly.row * 4;
   for (int d = 0; d < 3; ++d)
@@ -137,7 +132,7 @@ __global__ __launch_bounds__(256) void k_loss_hist(LossParams p, int32_t *__rest
   const int b = blockIdx.y, t = threadIdx.x;
   int32_t *sc = ex_scratch(scratch, p, b);
   int32_t *ctl = sc + 4 * kLossBins;
-  const int64_t n = p.seg[b][p.n_maps];
+  const int64_t n = p.s.seg[b][p.s.n_maps];
   if (LEVEL == 2) {
     // num_pos = min(P, int(B * f)), num_neg = min(N, B - num_pos) from the level-1 totals, then the level-1 bins
     for (int c = 0; c < 2; ++c) {
@@ -170,7 +165,7 @@ __global__ __launch_bounds__(256) void k_loss_hist(LossParams p, int32_t *__rest
     const int c = class_of(p, p.labels[b][j]);
     if (c < 0) continue;
     if (LEVEL == 2 && s_bin[c] < 0) continue;
-    const Loc L = locate(p, b, j);
+    const AnchorLoc L = locate(p, b, j);
     const uint32_t key = key_of(p, b, j, L);
     if (LEVEL == 1) atomicAdd(&s_hist[c][key >> 20], 1);
     else if ((int)(key >> 20) == s_bin[c]) atomicAdd(&s_hist[c][(key >> 8) & 4095u], 1);
@@ -191,7 +186,7 @@ __global__ __launch_bounds__(256) void k_loss_compact(LossParams p, int32_t *__r
   int32_t *sc = ex_scratch(scratch, p, b);
   int32_t *ctl = sc + 4 * kLossBins;
   unsigned long long *cand = ex_cand(scratch, p, b);
-  const int64_t n = p.seg[b][p.n_maps];
+  const int64_t n = p.s.seg[b][p.s.n_maps];
   for (int c = 0; c < 2; ++c) {
     int sum = 0;
     for (int q = 0; q < 16; ++q) sum += sc[2 * kLossBins + c * kLossBins + 16 * t + q];
@@ -212,7 +207,7 @@ __global__ __launch_bounds__(256) void k_loss_compact(LossParams p, int32_t *__r
   for (int64_t j = (int64_t)blockIdx.x * 256 + t; j < n; j += (int64_t)gridDim.x * 256) {
     const int c = class_of(p, p.labels[b][j]);
     if (c < 0 || s_k[c] == 0) continue;
-    const Loc L = locate(p, b, j);
+    const AnchorLoc L = locate(p, b, j);
     const uint32_t key = key_of(p, b, j, L);
     if ((key >> 8) <= s_thr[c]) {
       const int pos = atomicAdd(&ctl[kCtlCount + c], 1);
@@ -265,8 +260,8 @@ __global__ __launch_bounds__(256) void k_loss_select(LossParams p, int32_t *__re
       out[o + i] = p.out_begin[b] + j;
       if (mask) mask[j] = 1;
       if (loss) {
-        const Loc L = locate(p, b, j);
-        const int64_t oi = L.row * p.A + L.a;
+        const AnchorLoc L = locate(p, b, j);
+        const int64_t oi = L.row * p.s.A + L.a;
         bce += bce_term(ld(p.obj[L.m], oi, p.bf16), c == 0 ? 1.f : 0.f);
         if (c == 0)
           for (int d = 0; d < 7; ++d)
@@ -289,38 +284,28 @@ __global__ __launch_bounds__(256) void k_loss_select(LossParams p, int32_t *__re
   }
 }
 
-// host side: the tables of chunk [b0, b0 + nbc) (<= 16 examples)
-int fill_chunk(LossParams &p, int b0, int nbc, const int32_t *seg_begin_host, const int32_t *site_begin_host,
+// host side: the tables of chunk [b0, b0 + nbc) (<= 16 examples); `fn` names the entry point in an error
+int fill_chunk(LossParams &p, const char *fn, int b0, int nbc, const int32_t *seg_begin_host, const int32_t *site_begin_host,
                const void *const *label_ptrs, const void *const *target_ptrs, const int64_t *out_begin,
                void *const *pos_masks, void *const *neg_masks, bool need_labels, int64_t &nmax) {
-  const int n_maps = p.n_maps;
-  p.nb = nbc;
+  int rc = fill_anchor_segs(p.s, fn, p.s.n_maps, p.s.A, b0, nbc, seg_begin_host, site_begin_host, &nmax);
+  if (rc != AABR_OK) return rc;
   p.example0 = b0;
-  nmax = 0;
-  for (int b = 0; b < kLossMaxBatch; ++b) {
+  for (int b = 0; b < kAnchorMaxBatch; ++b) {
     const bool on = b < nbc;
     const int g = b0 + b;
-    for (int m = 0; m <= kLossMaxMaps; ++m)
-      p.seg[b][m] = on ? seg_begin_host[g * (n_maps + 1) + (m <= n_maps ? m : n_maps)] : 0;
-    for (int m = 0; m < kLossMaxMaps; ++m)
-      p.site[b][m] = on && m < n_maps && site_begin_host ? site_begin_host[g * n_maps + m] : 0;
     p.labels[b] = on && label_ptrs ? (const int64_t *)label_ptrs[g] : nullptr;
     p.targets[b] = on && target_ptrs ? (const float *)target_ptrs[g] : nullptr;
     p.out_begin[b] = on ? out_begin[g] : 0;
     p.pos_mask[b] = on && pos_masks ? (uint8_t *)pos_masks[g] : nullptr;
     p.neg_mask[b] = on && neg_masks ? (uint8_t *)neg_masks[g] : nullptr;
     if (!on) continue;
-    const int64_t n = p.seg[b][n_maps];
-    AABR_CHECK_ARG(p.seg[b][0] == 0, "an example's segment table starts at 0");
-    AABR_CHECK_ARG(n == 0 || !need_labels || p.labels[b], "null label list");
-    AABR_CHECK_ARG(n == 0 || !p.with_loss || p.targets[b], "null regression-target list");
-    for (int m = 0; m < n_maps; ++m) {
-      AABR_CHECK_ARG(p.seg[b][m + 1] >= p.seg[b][m], "segment table must be non-decreasing");
-      AABR_CHECK_ARG(p.flat || p.seg[b][m + 1] == p.seg[b][m] || ((p.coords[m] || !need_labels) && p.obj[m] && p.reg[m]),
-                     "null map pointer");
-      AABR_CHECK_ARG(p.flat || (p.seg[b][m + 1] - p.seg[b][m]) % p.A == 0, "a map's segment is not a multiple of A");
-    }
-    nmax = n > nmax ? n : nmax;
+    const int64_t n = p.s.seg[b][p.s.n_maps];
+    AABR_CHECK_ARG_AS(fn, n == 0 || !need_labels || p.labels[b], "null label list");
+    AABR_CHECK_ARG_AS(fn, n == 0 || !p.with_loss || p.targets[b], "null regression-target list");
+    for (int m = 0; m < p.s.n_maps; ++m)
+      AABR_CHECK_ARG_AS(fn, p.flat || p.s.seg[b][m + 1] == p.s.seg[b][m] ||
+                               ((p.coords[m] || !need_labels) && p.obj[m] && p.reg[m]), "null map pointer");
   }
   return AABR_OK;
 }
@@ -331,27 +316,33 @@ inline float *select_partials(int32_t *scratch, int nb) {
 }
 
 // the select of every chunk: 1 memset + 4 launches per chunk of 16 examples
-int run_select_chunks(LossParams &p, int nb, const int32_t *seg_begin_host, const int32_t *site_begin_host,
+int run_select_chunks(LossParams &p, const char *fn, int nb, const int32_t *seg_begin_host, const int32_t *site_begin_host,
                       const void *const *label_ptrs, const void *const *target_ptrs, void *const *pos_masks,
                       void *const *neg_masks, int64_t *selected, int32_t *info, int32_t *scratch, hipStream_t st) {
-  AABR_CHECK_ARG(((uintptr_t)scratch & 7) == 0, "scratch must be 8-byte aligned");
+  AABR_CHECK_ARG_AS(fn, ((uintptr_t)scratch & 7) == 0, "scratch must be 8-byte aligned");
   std::vector<int64_t> out_begin(nb);
   int64_t total = 0;
   for (int b = 0; b < nb; ++b) {
     out_begin[b] = total;
-    const int64_t n = seg_begin_host[b * (p.n_maps + 1) + p.n_maps];
-    AABR_CHECK_ARG(n >= 0, "negative list length");
+    const int64_t n = seg_begin_host[b * (p.s.n_maps + 1) + p.s.n_maps];
+    AABR_CHECK_ARG_AS(fn, n >= 0, "negative list length");
     total += n;
   }
-  AABR_CHECK_ARG(total < ((int64_t)1 << 31), "more than 2^31 - 1 entries per call");
+  AABR_CHECK_ARG_AS(fn, total < ((int64_t)1 << 31), "more than 2^31 - 1 entries per call");
   p.nb_total = nb;
+  for (int b0 = 0; b0 < nb; b0 += kAnchorMaxBatch) {   // every chunk's table, before anything is enqueued
+    AnchorSegs t;
+    int rc = fill_anchor_segs(t, fn, p.s.n_maps, p.s.A, b0, nb - b0 < kAnchorMaxBatch ? nb - b0 : kAnchorMaxBatch,
+                              seg_begin_host, site_begin_host, nullptr);
+    if (rc != AABR_OK) return rc;
+  }
   AABR_CHECK_HIP(hipMemsetAsync(scratch, 0, (size_t)nb * kLossZeroWords * sizeof(int32_t), st));
   float *partial = select_partials(scratch, nb);
-  for (int b0 = 0; b0 < nb; b0 += kLossMaxBatch) {
-    const int nbc = nb - b0 < kLossMaxBatch ? nb - b0 : kLossMaxBatch;
+  for (int b0 = 0; b0 < nb; b0 += kAnchorMaxBatch) {
+    const int nbc = nb - b0 < kAnchorMaxBatch ? nb - b0 : kAnchorMaxBatch;
     int64_t nmax = 0;
-    int rc = fill_chunk(p, b0, nbc, seg_begin_host, site_begin_host, label_ptrs, target_ptrs, out_begin.data(), pos_masks,
-                        neg_masks, true, nmax);
+    int rc = fill_chunk(p, fn, b0, nbc, seg_begin_host, site_begin_host, label_ptrs, target_ptrs, out_begin.data(),
+                        pos_masks, neg_masks, true, nmax);
     if (rc != AABR_OK) return rc;
     int64_t gx = ceil_div(nmax, 256 * 8);
     gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);

@@ -16,6 +16,7 @@ import torch
 import _hip
 import _nms
 from _hip import check, ptr
+from rpn_glue import _Cfg
 
 PRE_NMS, POST_NMS = 2000, 500      # boxlist_nms_3d(flag='roi_post'): rotate_nms_3d(pre_max_size=2000, post_max_size=500)
 INFO_WORDS = 8
@@ -509,11 +510,6 @@ def box_predictions(x, cls_w, cls_b, reg_w, reg_b):
     b = torch.cat([cls_b, reg_b]) if cls_b is not None else None
     y = _Mlp.apply(x, w, b, False, None, 0)
     return y[:, :nc], y[:, nc:]
-
-
-class _Cfg(object):
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
 
 
 def box_head_cfg(C=8, resolution=(2, 3, 2), R=12, classes=("background", "wall", "door"), class_specific=True, separate=(),

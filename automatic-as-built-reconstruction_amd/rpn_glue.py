@@ -78,6 +78,36 @@ def rpn_proposals_single_map(tensor, objectness, box_regression, base_anchors, v
     return out
 
 
+def _site_counts(grids, nb, dev):
+    """sites per (map, example), counts[m][b]: the per-sample row offsets every grid got with its site-count read
+    (SparseGrid::ctr, Metadata.h:24-33); only a grid built without them costs a read here"""
+    counts = [g.sample_counts(nb) for g in grids]
+    if any(c is None for c in counts):
+        counts = torch.stack([torch.bincount(g.coords[:, 3].long(), minlength=nb)[:nb] if g.V else
+                              torch.zeros(nb, dtype=torch.int64, device=dev) for g in grids]).tolist()
+    return counts
+
+
+def _anchor_tables(counts, A, b0=0, b1=None):
+    """The two host tables of the examples' anchor lists (csrc/anchor_list.h) for examples b0 .. b1 (default: all), from
+    counts[m][b] = sites of example b in map m.  Returns (seg, site, n_anchor): seg flat, n_maps + 1 per example, the
+    first list index of every map and the list's length; site flat, n_maps per example, the example's first site row
+    in every map (absolute: b0 > 0 starts behind the earlier examples); n_anchor[i] = the length of example b0 + i's
+    list.  Plain Python on ints."""
+    n_maps = len(counts)
+    b1 = len(counts[0]) if b1 is None else b1
+    row = [sum(c[:b0]) for c in counts]
+    seg, site, n_anchor = [], [], []
+    for b in range(b0, b1):
+        seg.append(0)
+        for m in range(n_maps):
+            seg.append(seg[-1] + counts[m][b] * A)
+            site.append(row[m])
+            row[m] += counts[m][b]
+        n_anchor.append(seg[-1])
+    return seg, site, n_anchor
+
+
 fused_topk = True      # aabr_rpn_topk_maps instead of torch.cat + torch.topk per example (False: the round-4 path, for A/B)
 topk_stats = {"fallbacks": 0}
 _trace = None     # tools/tools_step_timeline.py: called with a label at the stage's host-side boundaries
@@ -115,27 +145,13 @@ def rpn_proposals(maps, objectness, box_regression, base_anchors, strides, voxel
         nb = int(batch_size)
     else:
         nb = max((int(g.coords[-1, 3].item()) + 1 if g.V else 0) for g in grids[:1])
-    # sites per (map, example): the per-sample row offsets every grid got with its site-count read
-    # (SparseGrid::ctr, Metadata.h:24-33); only a grid built without them costs a read here
-    counts = [g.sample_counts(nb) for g in grids]
-    if any(c is None for c in counts):
-        counts = torch.stack([torch.bincount(g.coords[:, 3].long(), minlength=nb)[:nb] if g.V else
-                              torch.zeros(nb, dtype=torch.int64, device=dev) for g in grids]).tolist()
+    counts = _site_counts(grids, nb, dev)
+    segs, sites, n_anchor = _anchor_tables(counts, A, 0, nb)
     if batched and 1 <= nb <= 16 and n_maps <= 8:
-        segs, sites, site0 = [], [], [0] * n_maps
-        for bi in range(nb):
-            seg = [0]
-            for m in range(n_maps):
-                seg.append(seg[-1] + counts[m][bi] * A)
-            segs.append(seg)
-            sites.append(list(site0))
-            for m in range(n_maps):
-                site0[m] += counts[m][bi]
-        if min(s[-1] for s in segs) >= pre_nms_top_n:
+        if min(n_anchor) >= pre_nms_top_n:
             k = int(pre_nms_top_n)
-            lmax = max(s[-1] for s in segs)
-            seg_h = _hip.i32xn([v for s_ in segs for v in s_])
-            site_h = _hip.i32xn([v for s_ in sites for v in s_])
+            lmax = max(n_anchor)
+            seg_h, site_h = _hip.i32xn(segs), _hip.i32xn(sites)
             padded = torch.empty((nb, lmax), dtype=torch.float32, device=dev)
             check(lib.aabr_rpn_gather_logits(n_maps, _hip.ptrs(obj), nb, seg_h, site_h, A, lmax, ptr(padded), stream()))
             _, sel = padded.topk(k, dim=1, sorted=True)
@@ -166,15 +182,7 @@ def rpn_proposals(maps, objectness, box_regression, base_anchors, strides, voxel
     # fallback for shapes the kernel does not take and for the (reported) case of > 4096 exactly tied logits at the cut
     sel_all = topk_info = None
     if fused_topk and 1 <= nb <= 16 and n_maps <= 8 and pre_nms_top_n <= 2048:
-        segs, sites, s0 = [], [], [0] * n_maps
-        for bi in range(nb):
-            seg = [0]
-            for m in range(n_maps):
-                seg.append(seg[-1] + counts[m][bi] * A)
-            segs += seg
-            sites += s0
-            s0 = [s0[m] + counts[m][bi] for m in range(n_maps)]
-        ks = [min(pre_nms_top_n, segs[bi * (n_maps + 1) + n_maps]) for bi in range(nb)]
+        ks = [min(pre_nms_top_n, n) for n in n_anchor]
         kmax = max(max(ks), 1)
         sel_all = torch.empty((nb, kmax), dtype=torch.int64, device=dev)
         topk_info = torch.empty((nb, 2), dtype=torch.int32, device=dev)
@@ -182,38 +190,48 @@ def rpn_proposals(maps, objectness, box_regression, base_anchors, strides, voxel
         tso = (-tscr.data_ptr() // 4) % 2
         check(lib.aabr_rpn_topk_maps(n_maps, obj_p, nb, _hip.i32xn(segs), _hip.i32xn(sites), A, _hip.i32xn(ks), ptr(sel_all),
                                      kmax, ptr(topk_info), tscr.data_ptr() + 4 * tso, stream()))
-    site0 = [0] * n_maps
-    out, pending = [], []
-    for bi in range(nb):
-        seg = [0]
-        for m in range(n_maps):
-            seg.append(seg[-1] + counts[m][bi] * A)
-        n_anchor = seg[-1]
-        if n_anchor == 0:
-            out.append((torch.zeros(0, 7, device=dev), torch.zeros(0, device=dev)))
-            continue
-        k = min(pre_nms_top_n, n_anchor)
-        if sel_all is not None:
-            sel = sel_all[bi, :k]
-        else:
-            logit_b = torch.cat([obj[m][site0[m] * A:(site0[m] + counts[m][bi]) * A] for m in range(n_maps)])
-            _, sel = logit_b.topk(k, dim=0, sorted=True)
-        boxes = torch.empty((k, 7), dtype=torch.float32, device=dev)
+
+    def rows_of(bi):
+        """example bi's rows of the two tables"""
+        return segs[bi * (n_maps + 1):(bi + 1) * (n_maps + 1)], sites[bi * n_maps:(bi + 1) * n_maps]
+
+    def logits_of(bi):
+        """example bi's logits, concatenated in map order (the torch.topk paths)"""
+        seg, st0 = rows_of(bi)
+        return torch.cat([obj[m][st0[m] * A:st0[m] * A + (seg[m + 1] - seg[m])] for m in range(n_maps)])
+
+    def decode(bi, sel, boxes, scores):
+        """example bi's selected anchors decoded into `boxes` / `scores`; returns the thickness-clamped copy for the NMS"""
+        k = boxes.shape[0]
+        seg, st0 = rows_of(bi)
         nms_boxes = torch.empty((k, 7), dtype=torch.float32, device=dev)
-        scores = torch.empty(k, dtype=torch.float32, device=dev)
-        check(lib.aabr_rpn_decode_maps(n_maps, coords_p, obj_p, reg_p, _hip.i32xn(seg), _hip.i32xn(site0), strides_h,
+        check(lib.aabr_rpn_decode_maps(n_maps, coords_p, obj_p, reg_p, _hip.i32xn(seg), _hip.i32xn(st0), strides_h,
                                        ptr(ba), A, float(voxel_scale), weights_h, float(bbox_xform_clip),
                                        float(nms_aug_thickness[0]), float(nms_aug_thickness[1]), ptr(sel), k,
                                        ptr(boxes), ptr(nms_boxes), ptr(scores), stream()))
+        return nms_boxes
+
+    out, pending = [], []
+    for bi in range(nb):
+        if n_anchor[bi] == 0:
+            out.append((torch.zeros(0, 7, device=dev), torch.zeros(0, device=dev)))
+            continue
+        k = min(pre_nms_top_n, n_anchor[bi])
+        if sel_all is not None:
+            sel = sel_all[bi, :k]
+        else:
+            _, sel = logits_of(bi).topk(k, dim=0, sorted=True)
+        boxes = torch.empty((k, 7), dtype=torch.float32, device=dev)
+        scores = torch.empty(k, dtype=torch.float32, device=dev)
+        nms_boxes = decode(bi, sel, boxes, scores)
         if debug_nms_inputs is not None:
             debug_nms_inputs.append((nms_boxes, scores))
         # every example's launches go out first; the numbers kept are read once, after the last one
         keep, meta = _nms.rotate_nms_sorted(nms_boxes, nms_thresh, post_nms_top_n, _nms.REFERENCE_DEBUG_ONLY_XY,
                                             lazy=True)
-        pending.append((len(out), boxes, scores, keep, meta, bi, list(seg), list(site0)))
+        pending.append((len(out), boxes, scores, keep, meta, bi))
         out.append(None)
-        for m in range(n_maps):
-            site0[m] += counts[m][bi]
+
     def finish():
         if pending:
             if _trace is not None:
@@ -225,18 +243,12 @@ def rpn_proposals(maps, objectness, box_regression, base_anchors, strides, voxel
             kept, over = vals[:len(pending)], vals[len(pending):]
             if _trace is not None:
                 _trace("proposal counts read")
-            for (i, boxes, scores, keep, meta, bi, seg, st0), nk in zip(pending, kept):
+            for (i, boxes, scores, keep, meta, bi), nk in zip(pending, kept):
                 if over and over[bi]:
                     # > 4096 exactly tied logits at the cut: this example again, selected by a full torch.topk
                     topk_stats["fallbacks"] += 1
-                    logit_b = torch.cat([obj[m][st0[m] * A:st0[m] * A + (seg[m + 1] - seg[m])] for m in range(n_maps)])
-                    k_ = boxes.shape[0]
-                    _, sel = logit_b.topk(k_, dim=0, sorted=True)
-                    nms_boxes = torch.empty((k_, 7), dtype=torch.float32, device=dev)
-                    check(lib.aabr_rpn_decode_maps(n_maps, coords_p, obj_p, reg_p, _hip.i32xn(seg), _hip.i32xn(st0), strides_h,
-                                                   ptr(ba), A, float(voxel_scale), weights_h, float(bbox_xform_clip),
-                                                   float(nms_aug_thickness[0]), float(nms_aug_thickness[1]), ptr(sel), k_,
-                                                   ptr(boxes), ptr(nms_boxes), ptr(scores), stream()))
+                    _, sel = logits_of(bi).topk(boxes.shape[0], dim=0, sorted=True)
+                    nms_boxes = decode(bi, sel, boxes, scores)
                     kp = _nms.rotate_nms_sorted(nms_boxes, nms_thresh, post_nms_top_n, _nms.REFERENCE_DEBUG_ONLY_XY)
                     out[i] = (boxes[kp], scores[kp])
                     continue
@@ -285,26 +297,12 @@ def rpn_label_matches(maps, base_anchors, strides, voxel_scale, targets, aug_thi
     ba = _device_anchors(base_anchors, A, dev)
     nb = int(batch_size) if batch_size is not None else len(targets)
     assert aug_thickness["anchor_Y"] == 0 and aug_thickness["target_Y"] >= 0.3     # rotate_nms_3d_torch.py:34-36
-    counts = [g.sample_counts(nb) for g in grids]
-    if any(c is None for c in counts):
-        counts = torch.stack([torch.bincount(g.coords[:, 3].long(), minlength=nb)[:nb] if g.V else
-                              torch.zeros(nb, dtype=torch.int64, device=dev) for g in grids]).tolist()
+    counts = _site_counts(grids, nb, dev)
     out = []
     for b0 in range(0, nb, 16):            # the library takes up to 16 examples per call
         b1 = min(nb, b0 + 16)
-        seg, site, site0 = [], [], [sum(counts[m][:b0]) for m in range(n_maps)]
-        n_anch, tg = [], []
-        for bi in range(b0, b1):
-            s_ = [0]
-            for m in range(n_maps):
-                s_.append(s_[-1] + counts[m][bi] * A)
-            seg += s_
-            site += list(site0)
-            for m in range(n_maps):
-                site0[m] += counts[m][bi]
-            n_anch.append(s_[-1])
-            t = targets[bi].to(device=dev, dtype=torch.float32).contiguous()
-            tg.append(t)
+        seg, site, n_anch = _anchor_tables(counts, A, b0, b1)
+        tg = [targets[bi].to(device=dev, dtype=torch.float32).contiguous() for bi in range(b0, b1)]
         total = sum(n_anch)
         midx = torch.empty(total, dtype=torch.int64, device=dev)
         mval = torch.empty(total, dtype=torch.float32, device=dev)
@@ -471,24 +469,15 @@ def rpn_loss(maps, objectness, box_regression, labels, base_anchors, batch_size_
     grids = [t.metadata.grids[_SCN._key(t.spatial_size)] for t in maps]
     dev = objectness[0].device
     A = int(base_anchors[0].shape[0])
-    counts = [g.sample_counts(nb) for g in grids]
-    if any(c is None for c in counts):
-        counts = torch.stack([torch.bincount(g.coords[:, 3].long(), minlength=nb)[:nb] if g.V else
-                              torch.zeros(nb, dtype=torch.int64, device=dev) for g in grids]).tolist()
+    counts = _site_counts(grids, nb, dev)
     for m in range(n_maps):
         V = sum(counts[m])
         if objectness[m].numel() != V * A or box_regression[m].numel() != V * A * 7:
             raise ValueError("map %d: objectness / box_regression do not hold %d sites x %d anchors" % (m, V, A))
-    seg, site, s0 = [], [], [0] * n_maps
+    seg, site, n_anchor = _anchor_tables(counts, A, 0, nb)
     for bi in range(nb):
-        s_ = [0]
-        for m in range(n_maps):
-            s_.append(s_[-1] + counts[m][bi] * A)
-        if labels[bi][0].numel() != s_[-1] or labels[bi][3].shape[0] != s_[-1]:
+        if labels[bi][0].numel() != n_anchor[bi] or labels[bi][3].shape[0] != n_anchor[bi]:
             raise ValueError("example %d: the labels do not match the maps' anchors" % bi)
-        seg += s_
-        site += s0
-        s0 = [s0[m] + counts[m][bi] for m in range(n_maps)]
     lab = [l[0] if l[0].dtype == torch.int64 else l[0].long() for l in labels]
     tgt = [l[3].float().contiguous() for l in labels]
     cfg = {"n_maps": n_maps, "nb": nb, "A": A, "B": int(batch_size_per_image),

@@ -778,6 +778,8 @@ int aabr_rpn_decode(const int32_t *site_coords, int64_t site_begin, const int64_
  * logits [V_m*A] and regression [V_m*A,7]; seg_begin_host[n_maps+1] = first local anchor index of each map in
  * this example's list; site_begin_host[n_maps] = this example's first site row in each map;
  * strides_host[n_maps*3]; base_anchors device [n_maps*A,7].  selected int64 [k] (descending score).
+ * Every entry that takes these two tables checks them alike (csrc/anchor_list.h): a row starts at 0, is
+ * non-decreasing and every segment is a multiple of num_anchors; otherwise AABR_EINVAL before any launch.
  * Outputs: boxes [k,7], nms_boxes [k,7] (may be NULL), scores [k] (may be NULL).                 */
 int aabr_rpn_decode_maps(int n_maps, const void *const *coords_ptrs, const void *const *logit_ptrs,
                          const void *const *regression_ptrs, const int32_t *seg_begin_host,
