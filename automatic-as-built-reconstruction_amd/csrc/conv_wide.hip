@@ -22,6 +22,7 @@
 //     out[o] = bias + sum_k in[table[k][o]] @ Wl[k]
 // Requires n_in % 32 == 0 (above 128: % 128), n_out % 64 == 0, vol <= 63, rows_in < 2^23, buffers < 2 GiB.
 #include "common.h"
+#include "conv_wide_tiles.h"   // kWS, kMaxVol, kMaxTileRows, wide_words and the launch decision
 #include <stdlib.h>
 
 namespace aabr {
@@ -31,9 +32,7 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 extern thread_local const char *g_last_variant; // conv.hip
 
-constexpr int kWS = 64;    // tile row stride in floats = slab width
 constexpr int kNB = 4;     // 16-column blocks per slab
-constexpr int kMaxVol = 63;  // vol + 1 prefix entries live in the lanes of one VGPR
 
 // ------------------------------------------------------------------ compiled rule book, big-tile form
 //   words: [ntiles][vol+1] block prefix per offset | [ntiles][(T/16)*vol][16] entries   (T rows per tile)
@@ -109,7 +108,6 @@ __device__ inline float bcf_(unsigned int v) { return __builtin_bit_cast(float, 
 // weights cost 8 KiB per wave per OFFSET (registers), and every wave issues the same MFMAs.
 // One barrier per block pair (~2 x 1024 MFMA cycles per wave) with the double-buffered stage (NBUF = 2), two with a
 // single stage buffer (NBUF = 1: 49 KiB of LDS at 128-channel groups => three workgroups per CU instead of two).
-constexpr int kMaxTileRows = 240; // (240 + 1) rows x 256 B + 16 KiB stage = 76 KiB: two workgroups per CU
 
 // NBUF = LDS stage buffers: 2 (one barrier per pair, 2 workgroups per CU) or 1 (two barriers per pair, 3 per CU)
 // BF: bf16 feature storage (extension): rows, stage and weight packs hold bf16, one v_mfma_f32_16x16x32_bf16 per 32
@@ -571,11 +569,6 @@ __global__ __launch_bounds__(256, NBUF == 2 ? 2 : 3) void k_conv_cs(const float 
 } // namespace aabr
 using namespace aabr;
 
-static int64_t wide_words(int64_t V, int vol, int T) {
-  const int64_t nt = (V + T - 1) / T;
-  return nt * (vol + 1) + nt * (int64_t)(T / 16) * vol * 16;
-}
-
 extern "C" int64_t aabr_wide_blocks_words(int64_t V, int vol, int tile_rows) { return wide_words(V, vol, tile_rows); }
 
 extern "C" int aabr_build_wide_blocks(const int32_t *table, int64_t V, int vol, int tile_rows, int32_t *blocks,
@@ -619,51 +612,28 @@ int aabr::launch_wide_blocks_jobs(const StreamJob *jobs, int n, hipStream_t st) 
   return AABR_OK;
 }
 
-// 0: use the 64-row-tile kernels of conv.hip; 128 / 256: rows per tile of the block stream aabr_conv_forward_wide wants
-extern "C" int aabr_conv_wide_tile_rows(int n_in, int n_out, int64_t rows_in, int64_t V_out, int vol) {
-  if (n_in <= 0 || n_out <= 0 || (n_in & 31) || (n_out & 63) || vol <= 0 || vol > kMaxVol) return 0;
-  if (rows_in >= (1ll << 23) || rows_in * n_in * 4 >= (1ll << 31)) return 0;
-  // rows per tile: 128, except when the whole launch fits the chip in ONE round (512 resident workgroups, 2 per
-  // CU): then its time is the longest workgroup, so take the smallest tile (>= 64 rows) that still fits one round
-  // (measured, profiles/r02_conv_wide_ab.txt: 22k rows x 2 slabs, 128 -> 96 rows: 184 -> 133 us; with several rounds
-  // smaller tiles only lower the block fill: 84k rows 385 -> 400 us)
-  // up to 64 input channels (channel groups of 32 / 64: 8 KiB of stage, ~100 registers) 112-row tiles with a single
-  // stage buffer fit FOUR workgroups per CU (36.9 KiB each): 64->64 at 200k rows 204 -> 190 us, at 282k rows 180 -> 171
-  // (round 4, measured with AABR_WIDE_NBUF / AABR_WIDE_ROWS); 128-channel groups stay at 128 rows / three per CU
-  int T = n_in <= 64 ? 112 : 128;
-  {
-    const int64_t slabs = n_out / 64;
-    if (((V_out + T - 1) / T) * slabs <= 512)
-      for (int t = 64; t < T; t += 16)
-        if (((V_out + t - 1) / t) * slabs <= 512) { T = t; break; }
-  }
-  {                                                // tuning experiments only
-    const int v = knob(K_WIDE_ROWS);
-    if (v >= 16 && v <= kMaxTileRows && (v & 15) == 0) T = v;
-  }
-  if (wide_words(V_out, vol, T) * 4 >= (1ll << 31)) return 0;
-  if ((int64_t)vol * n_in * n_out * 4 >= (1ll << 31)) return 0;
-  if (n_in > 128 && (n_in & 127)) return 0; // channel groups of 128: every load of the inner loop unconditional
-  {                                                // tuning experiments / tests only: 0 = never, 1 = whenever supported
-    const int v = knob(K_CONV_WIDE);
-    if (v == 0) return 0;
-    if (v == 1) return T;
-  }
-  // enough workgroups to fill the chip twice over (measured, profiles/r02_conv_wide_ab.txt: wins from ~340
-  // workgroups up, loses below ~180)
-  return (((V_out + T - 1) / T) * (n_out / 64) >= 320) ? T : 0;
+// ---- the dispatch queries: conv_wide_tiles.h decides, with the knobs as they stand --------------------------------------
+static WideKnobs wide_knobs() {
+  return {knob(K_WIDE_ROWS), knob(K_CONV_WIDE), knob(K_CONV_WIDE_BF16), knob(K_WIDE_SPLIT), knob(K_SPLIT_ROWS),
+          knob(K_SPLIT_MIN_ITEMS), knob(K_SPLIT_TARGET), knob(K_WIDE_NBUF), knob(K_SPLIT_NBUF), knob(K_WIDE_NCB),
+          knob(K_WIDE_PRIO)};
 }
 
-extern "C" int aabr_conv_forward_wide_res(const float *in_feats, int n_in, int64_t rows_in, float *out_feats,
-                                          int n_out, int64_t V_out, const int32_t *blocks, int tile_rows, int vol,
-                                          const float *bias, int flags, const float *wpack, const float *residual,
-                                          void *stream_);
-
-extern "C" int aabr_conv_forward_wide(const float *in_feats, int n_in, int64_t rows_in, float *out_feats, int n_out,
-                                      int64_t V_out, const int32_t *blocks, int tile_rows, int vol, const float *bias,
-                                      int flags, const float *wpack, void *stream_) {
-  return aabr_conv_forward_wide_res(in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias,
-                                    flags, wpack, nullptr, stream_);
+// 0: use the 64-row-tile kernels of conv.hip; otherwise rows per tile of the block stream aabr_conv_forward_wide wants
+extern "C" int aabr_conv_wide_tile_rows(int n_in, int n_out, int64_t rows_in, int64_t V_out, int vol) {
+  return wide_tile_rows(kWideF32, n_in, n_out, rows_in, V_out, vol, wide_knobs());
+}
+// 0: use aabr_conv_forward_bf16 (64-row tiles); otherwise rows per tile for aabr_conv_forward_wide_bf16
+extern "C" int aabr_conv_wide_tile_rows_bf16(int n_in, int n_out, int64_t rows_in, int64_t V_out, int vol) {
+  return wide_tile_rows(kWideBf16, n_in, n_out, rows_in, V_out, vol, wide_knobs());
+}
+// (P << 16) | tile_rows when this launch should go to aabr_conv_forward_wide_split, else 0.  Asked after
+// aabr_conv_wide_tile_rows declined (fewer than 320 (tile, slab) items).
+extern "C" int aabr_conv_wide_split(int n_in, int n_out, int64_t rows_in, int64_t V_out, int vol) {
+  return wide_split(kWideF32, n_in, n_out, rows_in, V_out, vol, wide_knobs());
+}
+extern "C" int aabr_conv_wide_split_bf16(int n_in, int n_out, int64_t rows_in, int64_t V_out, int vol) {
+  return wide_split(kWideBf16, n_in, n_out, rows_in, V_out, vol, wide_knobs());
 }
 
 extern "C" int64_t aabr_conv_wide_stats_doubles(int64_t V_out, int tile_rows, int n_out) {
@@ -671,115 +641,8 @@ extern "C" int64_t aabr_conv_wide_stats_doubles(int64_t V_out, int tile_rows, in
   return ((V_out + tile_rows - 1) / tile_rows) * 2 * n_out;
 }
 
-extern "C" int aabr_conv_forward_wide_stats(const float *in_feats, int n_in, int64_t rows_in, float *out_feats,
-                                            int n_out, int64_t V_out, const int32_t *blocks, int tile_rows, int vol,
-                                            const float *bias, int flags, const float *wpack, const float *residual,
-                                            double *stats, void *stream_);
-
-extern "C" int aabr_conv_forward_wide_res(const float *in_feats, int n_in, int64_t rows_in, float *out_feats,
-                                          int n_out, int64_t V_out, const int32_t *blocks, int tile_rows, int vol,
-                                          const float *bias, int flags, const float *wpack, const float *residual,
-                                          void *stream_) {
-  return aabr_conv_forward_wide_stats(in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias,
-                                      flags, wpack, residual, nullptr, stream_);
-}
-
-static int wide_launch_f32(const float *in_feats, int n_in, int64_t rows_in, float *out_feats, int n_out, int64_t V_out,
-                           const int32_t *blocks, int tile_rows, int vol, const float *bias, int flags,
-                           const float *wpack, const float *residual, double *stats, BnBwdStats bn, void *stream_);
-
-extern "C" int aabr_conv_forward_wide_stats(const float *in_feats, int n_in, int64_t rows_in, float *out_feats,
-                                            int n_out, int64_t V_out, const int32_t *blocks, int tile_rows, int vol,
-                                            const float *bias, int flags, const float *wpack, const float *residual,
-                                            double *stats, void *stream_) {
-  return wide_launch_f32(in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags, wpack,
-                         residual, stats, BnBwdStats{}, stream_);
-}
-
-extern "C" int aabr_conv_forward_wide_bwd_stats(const float *in_feats, int n_in, int64_t rows_in, float *out_feats,
-                                                int n_out, int64_t V_out, const int32_t *blocks, int tile_rows, int vol,
-                                                const float *bias, int flags, const float *wpack, const float *residual,
-                                                double *stats, const float *bn_in, const float *save_mean,
-                                                const float *save_invstd, const float *bn_weight, const float *bn_bias,
-                                                float leakiness, void *stream_) {
-  AABR_CHECK_ARG(stats && bn_in && save_mean && save_invstd, "null pointer");
-  AABR_CHECK_ARG(leakiness >= 0.0f, "the activation sign is recomputed from the BatchNorm input: leakiness >= 0");
-  AABR_CHECK_ARG(((uintptr_t)bn_in & 15) == 0, "the BatchNorm input must be 16-byte aligned");
-  BnBwdStats bn{bn_in, save_mean, save_invstd, bn_weight, bn_bias, leakiness};
-  return wide_launch_f32(in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags, wpack,
-                         residual, stats, bn, stream_);
-}
-
-static int wide_launch_f32(const float *in_feats, int n_in, int64_t rows_in, float *out_feats, int n_out, int64_t V_out,
-                           const int32_t *blocks, int tile_rows, int vol, const float *bias, int flags,
-                           const float *wpack, const float *residual, double *stats, BnBwdStats bn, void *stream_) {
-  hipStream_t st = (hipStream_t)stream_;
-  AABR_CHECK_ARG(((uintptr_t)residual & 15) == 0, "residual must be 16-byte aligned");
-  AABR_CHECK_ARG(!stats || (tile_rows >= 64 && ((uintptr_t)stats & 7) == 0), "statistics need tiles of >= 64 rows");
-  AABR_CHECK_ARG(n_in > 0 && n_out > 0 && (n_in & 31) == 0 && (n_out & 63) == 0, "plane counts: n_in % 32, n_out % 64");
-  AABR_CHECK_ARG(vol > 0 && vol <= kMaxVol && V_out >= 0 && rows_in >= 0, "bad sizes");
-  AABR_CHECK_ARG(tile_rows >= 16 && tile_rows <= kMaxTileRows && (tile_rows & 15) == 0, "tile_rows: multiple of 16, <= 240");
-  if (V_out == 0) return AABR_OK;
-  AABR_CHECK_ARG(in_feats && out_feats && blocks && wpack && rows_in > 0, "null pointer / empty input");
-  AABR_CHECK_ARG(rows_in < (1ll << 23), "too many input rows for the wide block format");
-  const int64_t in_bytes = rows_in * n_in * 4, words_bytes = wide_words(V_out, vol, tile_rows) * 4;
-  AABR_CHECK_ARG(in_bytes < (1ll << 31) && words_bytes < (1ll << 31), "buffers must be < 2 GiB");
-  AABR_CHECK_ARG(((uintptr_t)in_feats & 15) == 0 && ((uintptr_t)out_feats & 15) == 0 && ((uintptr_t)wpack & 15) == 0,
-                 "feature / weight pointers must be 16-byte aligned");
-  const int dbg = flags >> 8;
-  const int nkc = n_in / 32;
-  const int64_t wp_bytes = (int64_t)vol * nkc * (n_out / 16) * 2048;
-  AABR_CHECK_ARG(wp_bytes < (1ll << 31), "packed weights must be < 2 GiB");
-  AABR_CHECK_ARG(n_in <= 128 || (n_in & 127) == 0, "n_in above 128 must be a multiple of 128");
-  dim3 grid((unsigned)((V_out + tile_rows - 1) / tile_rows), (unsigned)(n_out / 64));
-  // bit 1: the waves raise their priority for the matrix phase of a step (s_setprio): the wave that holds its operands
-  // gets the pipe, the others issue their gathers -- measured 331 -> 323.5 us on the dominant instance; WIDE_PRIO knob 0: off
-  const int flip = ((flags >> 1) & 1) | (knob(K_WIDE_PRIO) == 0 ? 0 : 2);
-  const int kg = nkc >= 4 ? 4 : nkc;
-  // LDS stage buffers: with 128-channel groups the double-buffered stage (32 KiB) allows two workgroups per CU, a
-  // single buffer three (49 KiB each) at the price of a second barrier per pair: measured +4...+10 % (128->128 at 84k
-  // rows 380 -> 367 us, 256->256 1366 -> 1272 us); narrower groups fit three workgroups with the double buffer
-  int nbuf = (kg == 4 || kg <= 2) ? 1 : 2;   // kg <= 2: single buffer + 112-row tiles = four workgroups per CU (above)
-  {                                                // tuning experiments only
-    const int v = knob(K_WIDE_NBUF);
-    if (v == 1 || v == 2) nbuf = v;
-  }
-#define AABR_LAUNCH_WIDE(KERNEL, NAME, LDS, ...)                                                          \
-  do {                                                                                                    \
-    static DynLdsOnce attr;                                                                               \
-    AABR_CHECK_HIP(dyn_lds_once(attr, (const void *)KERNEL, 80 * 1024));          \
-    g_last_variant = NAME;                                                                                \
-    hipLaunchKernelGGL(KERNEL, grid, dim3(256), (LDS), st, __VA_ARGS__);                                  \
-  } while (0)
-  {
-#define AABR_WIDE_CS_N(KG, D, NB)                                                                         \
-  AABR_LAUNCH_WIDE((k_conv_cs<KG, D, NB>), "k_conv_cs<" #KG "," #D "," #NB ">",                           \
-                   (size_t)((tile_rows + 1) * kWS + NB * 2 * 16 * KG * 32) * sizeof(float), in_feats, n_in, in_bytes,   \
-                   out_feats, n_out, V_out, blocks, words_bytes, vol, flip, wpack, wp_bytes, bias, tile_rows, residual, stats, bn)
-#define AABR_WIDE_CS(KG, D)                                                                               \
-  do {                                                                                                    \
-    if (nbuf == 1) AABR_WIDE_CS_N(KG, D, 1); else AABR_WIDE_CS_N(KG, D, 2);                               \
-  } while (0)
-#ifdef AABR_DEV
-    if (dbg & 7) { // timing experiments (tools/, `make DEV=1`): only the 128-channel-group instance carries the debug variants
-      AABR_CHECK_ARG(kg == 4, "debug variants exist for n_in >= 128 only");
-      nbuf = 2;
-      if (dbg & 4) AABR_WIDE_CS(4, 4);
-      else if ((dbg & 3) == 1) AABR_WIDE_CS(4, 1); else if ((dbg & 3) == 2) AABR_WIDE_CS(4, 2); else AABR_WIDE_CS(4, 3);
-    } else
-#else
-    AABR_CHECK_ARG(!(dbg & 7), "the timing-experiment variants of k_conv_cs exist in a `make DEV=1` build only");
-#endif
-    {
-      if (kg == 1) AABR_WIDE_CS(1, 0); else if (kg == 2) AABR_WIDE_CS(2, 0); else if (kg == 3) AABR_WIDE_CS(3, 0);
-      else AABR_WIDE_CS(4, 0);
-    }
-#undef AABR_WIDE_CS
-#undef AABR_WIDE_CS_N
-  }
-#undef AABR_LAUNCH_WIDE
-  AABR_CHECK_LAUNCH();
-  return AABR_OK;
+extern "C" int64_t aabr_conv_wide_split_scratch_floats(int64_t V_out, int n_out, int parts) {
+  return V_out > 0 && n_out > 0 && parts > 0 ? (int64_t)parts * V_out * n_out : 0;
 }
 
 // ---- offset split for coarse maps ---------------------------------------------------------------------------------------
@@ -791,6 +654,9 @@ static int wide_launch_f32(const float *in_feats, int n_in, int64_t rows_in, flo
 // bf16 rounding.  Scratch: P x V_out x n_out floats.  Measured on the bench's coarse rule books (profiles/r04_conv_split_ab.txt):
 // 128->128 at 5,565 rows 62 -> 53 us, 256->256 at 1,382 rows 83 -> 62 us, at 332 rows 47 -> 28 us; single stage buffer (three
 // workgroups per CU) over the double one: -10 %; below 8 (tile, slab) items the 16-column item kernel stays ahead.
+// bf16 storage (round 4: 50 launches of k_conv_blocks_mfma_bf16 per step, 8 % of the bf16 step's kernel time): the same cut
+// over the filter offsets; the parts are fp32 (the kernel's LDS tile is), the reduce kernel rounds once to bf16 -- the same
+// single rounding per stored value as the unsplit kernels.
 namespace aabr {
 template <bool BF>
 __global__ __launch_bounds__(256) void k_split_reduce(const float *__restrict__ parts, int nparts, int64_t n4, int co4,
@@ -826,146 +692,195 @@ __global__ __launch_bounds__(256) void k_split_reduce(const float *__restrict__ 
 }
 } // namespace aabr
 
-// (P << 16) | tile_rows when this launch should go to aabr_conv_forward_wide_split, else 0.  Asked after
-// aabr_conv_wide_tile_rows declined (fewer than 320 (tile, slab) items).
-extern "C" int aabr_conv_wide_split(int n_in, int n_out, int64_t rows_in, int64_t V_out, int vol) {
-  if (n_in <= 0 || n_out <= 0 || (n_in & 31) || (n_out & 63) || vol <= 1 || vol > kMaxVol || V_out <= 0) return 0;
-  if (rows_in >= (1ll << 23) || rows_in * n_in * 4 >= (1ll << 31)) return 0;
-  if (n_in < 64 || (n_in > 128 && (n_in & 127))) return 0;
-  if (knob(K_WIDE_SPLIT) == 0) return 0;
-  if (((V_out + 63) / 64) * (n_out / 64) >= 320) return 0;
-  int T = V_out >= 1024 ? 96 : 64;     // fp32, round 5: 96-row tiles from ~1 k rows on (5,565 rows 54 -> 49 us, 1,382 rows 57 -> 53; 332 rows 27 vs 29)
-  { const int v = knob(K_SPLIT_ROWS); if (v >= 64 && v <= 128 && (v & 15) == 0) T = v; }   // (A/B)
-  const int64_t items = ((V_out + T - 1) / T) * (n_out / 64);
-  const int min_items = knob(K_SPLIT_MIN_ITEMS) == kKnobUnset ? 8 : knob(K_SPLIT_MIN_ITEMS);   // below: the 16-column item kernel wins
-  if (items < min_items) return 0;
-  const int target = knob(K_SPLIT_TARGET) == kKnobUnset ? 768 : knob(K_SPLIT_TARGET);   // workgroups aimed at (round 5: 512 .. 1536 re-measured; 768 and 1280 best by ~3 %)
-  int P = (int)((target + items - 1) / items);
-  if (P > vol) P = vol;
-  if (P > 32) P = 32;
-  {                                                // tuning experiments only
-    const int v = knob(K_WIDE_SPLIT);
-    if (v >= 2 && v <= 32) P = v < vol ? v : vol;
+// ---- the launch: one table of the compiled instances, one function that carries conv_wide_tiles.h's decision out -------
+typedef decltype(&k_conv_cs<1, 0, 1>) WideFn;   // every instantiation has this type
+struct WideInst {
+  WideKernel k;                    // (split = false: a split launch runs the same instance)
+  const char *name, *split_name;   // what aabr_conv_last_variant reports; split_name == nullptr: no split launch uses it
+  WideFn fn;
+};
+static const WideInst kWide[] = {
+    // fp32 storage: channel groups of 32 .. 128, one or two stage buffers
+    {{1, 0, 1, false, 1, false}, "k_conv_cs<1,0,1>", nullptr, k_conv_cs<1, 0, 1>},
+    {{1, 0, 2, false, 1, false}, "k_conv_cs<1,0,2>", nullptr, k_conv_cs<1, 0, 2>},
+    {{2, 0, 1, false, 1, false}, "k_conv_cs<2,0,1>", "k_conv_cs<2,0,1,split>", k_conv_cs<2, 0, 1>},
+    {{2, 0, 2, false, 1, false}, "k_conv_cs<2,0,2>", "k_conv_cs<2,0,2,split>", k_conv_cs<2, 0, 2>},
+    {{3, 0, 1, false, 1, false}, "k_conv_cs<3,0,1>", "k_conv_cs<3,0,1,split>", k_conv_cs<3, 0, 1>},
+    {{3, 0, 2, false, 1, false}, "k_conv_cs<3,0,2>", "k_conv_cs<3,0,2,split>", k_conv_cs<3, 0, 2>},
+    {{4, 0, 1, false, 1, false}, "k_conv_cs<4,0,1>", "k_conv_cs<4,0,1,split>", k_conv_cs<4, 0, 1>},
+    {{4, 0, 2, false, 1, false}, "k_conv_cs<4,0,2>", "k_conv_cs<4,0,2,split>", k_conv_cs<4, 0, 2>},
+    // bf16 storage: channel groups of 64 .. 256; 128-column slabs up to 128 input channels (two gather register sets:
+    // four measured slower, 100 -> 112 us)
+    {{1, 0, 1, true, 1, false}, "k_conv_cs<1,0,1,bf16>", "k_conv_cs<1,0,1,bf16,split>", k_conv_cs<1, 0, 1, true, 1>},
+    {{1, 0, 2, true, 1, false}, "k_conv_cs<1,0,2,bf16>", nullptr, k_conv_cs<1, 0, 2, true, 1>},
+    {{1, 0, 1, true, 2, false}, "k_conv_cs<1,0,1,bf16,x128>", nullptr, k_conv_cs<1, 0, 1, true, 2>},
+    {{1, 0, 2, true, 2, false}, "k_conv_cs<1,0,2,bf16,x128>", nullptr, k_conv_cs<1, 0, 2, true, 2>},
+    {{2, 0, 1, true, 1, false}, "k_conv_cs<2,0,1,bf16>", "k_conv_cs<2,0,1,bf16,split>", k_conv_cs<2, 0, 1, true, 1>},
+    {{2, 0, 2, true, 1, false}, "k_conv_cs<2,0,2,bf16>", nullptr, k_conv_cs<2, 0, 2, true, 1>},
+    {{2, 0, 1, true, 2, false}, "k_conv_cs<2,0,1,bf16,x128>", nullptr, k_conv_cs<2, 0, 1, true, 2>},
+    {{2, 0, 2, true, 2, false}, "k_conv_cs<2,0,2,bf16,x128>", nullptr, k_conv_cs<2, 0, 2, true, 2>},
+    {{3, 0, 1, true, 1, false}, "k_conv_cs<3,0,1,bf16>", "k_conv_cs<3,0,1,bf16,split>", k_conv_cs<3, 0, 1, true, 1>},
+    {{3, 0, 2, true, 1, false}, "k_conv_cs<3,0,2,bf16>", nullptr, k_conv_cs<3, 0, 2, true, 1>},
+    {{4, 0, 1, true, 1, false}, "k_conv_cs<4,0,1,bf16>", "k_conv_cs<4,0,1,bf16,split>", k_conv_cs<4, 0, 1, true, 1>},
+    {{4, 0, 2, true, 1, false}, "k_conv_cs<4,0,2,bf16>", nullptr, k_conv_cs<4, 0, 2, true, 1>},
+#ifdef AABR_DEV
+    // timing experiments (tools/): the 128-channel instances with debug bits.  The fp32 ones always run with two stage
+    // buffers (wide_launch); their single-buffer rows are compiled but never launched.
+    {{4, 1, 1, false, 1, false}, "k_conv_cs<4,1,1>", nullptr, k_conv_cs<4, 1, 1>},
+    {{4, 1, 2, false, 1, false}, "k_conv_cs<4,1,2>", nullptr, k_conv_cs<4, 1, 2>},
+    {{4, 2, 1, false, 1, false}, "k_conv_cs<4,2,1>", nullptr, k_conv_cs<4, 2, 1>},
+    {{4, 2, 2, false, 1, false}, "k_conv_cs<4,2,2>", nullptr, k_conv_cs<4, 2, 2>},
+    {{4, 3, 1, false, 1, false}, "k_conv_cs<4,3,1>", nullptr, k_conv_cs<4, 3, 1>},
+    {{4, 3, 2, false, 1, false}, "k_conv_cs<4,3,2>", nullptr, k_conv_cs<4, 3, 2>},
+    {{4, 4, 1, false, 1, false}, "k_conv_cs<4,4,1>", nullptr, k_conv_cs<4, 4, 1>},
+    {{4, 4, 2, false, 1, false}, "k_conv_cs<4,4,2>", nullptr, k_conv_cs<4, 4, 2>},
+    {{2, 4, 1, true, 1, false}, "k_conv_cs<2,4,1,bf16>", nullptr, k_conv_cs<2, 4, 1, true, 1>},
+    {{2, 4, 1, true, 2, false}, "k_conv_cs<2,4,1,bf16,x128>", nullptr, k_conv_cs<2, 4, 1, true, 2>},
+#endif
+};
+constexpr int kWideCount = sizeof(kWide) / sizeof(kWide[0]);
+static DynLdsOnce kWideLds[kWideCount];
+
+// One launch as an entry point hands it over.  Feature pointers are typed as the kernel types them (fp32); with bf16
+// storage they point at bf16 rows.  parts != 0: the offset split through `scratch`.
+struct WideArgs {
+  const char *fn;   // the entry point, for its error text
+  int storage;
+  const void *in;
+  int n_in;
+  int64_t rows_in;
+  void *out;
+  int n_out;
+  int64_t V_out;
+  const int32_t *blocks;
+  int tile_rows, vol;
+  const float *bias;
+  int flags;
+  const void *wpack, *residual;
+  double *stats;
+  BnBwdStats bn;
+  bool split;
+  int parts;
+  float *scratch;
+  void *stream;
+};
+
+static int wide_run(const WideArgs &a) {
+  hipStream_t st = (hipStream_t)a.stream;
+  const WideStorageDesc &s = wide_storage(a.storage);
+  const bool bf16 = a.storage == kWideBf16;
+  AABR_CHECK_ARG_AS(a.fn, !a.split || (a.parts != 0 && a.scratch && ((uintptr_t)a.scratch & 15) == 0),
+                    "2 <= parts <= min(32, vol) and a 16-byte aligned scratch of parts x V_out x n_out floats");
+  AABR_CHECK_ARG_AS(a.fn, ((uintptr_t)a.residual & (s.res_align - 1)) == 0,
+                    bf16 ? "residual must be 8-byte aligned" : "residual must be 16-byte aligned");
+  AABR_CHECK_ARG_AS(a.fn, ((uintptr_t)a.stats & 7) == 0, "statistics need tiles of >= 64 rows");
+  WideLaunch t;
+  const char *refused = wide_launch(a.storage, a.split ? a.parts : 0, a.n_in, a.n_out, a.rows_in, a.V_out, a.tile_rows,
+                                    a.vol, a.flags, a.stats != nullptr, wide_knobs(), t);
+  AABR_CHECK_ARG_AS(a.fn, !refused, refused);
+  if (a.V_out == 0) return AABR_OK;
+  AABR_CHECK_ARG_AS(a.fn, a.in && a.out && a.blocks && a.wpack, "null pointer / empty input");
+  AABR_CHECK_ARG_AS(a.fn, (((uintptr_t)a.in | (uintptr_t)a.out | (uintptr_t)a.wpack) & 15) == 0,
+                    "feature / weight pointers must be 16-byte aligned");
+  WideKernel k = t.k;
+  k.split = false;   // a split runs the plain launch's instance: one row serves both, its split_name says whether it may
+  const WideInst *e = nullptr;
+  for (int i = 0; i < kWideCount && !e; ++i)
+    if (kWide[i].k == k) e = &kWide[i];
+  AABR_CHECK_ARG_AS(a.fn, e && (!a.split || e->split_name), "no kernel instance for this launch");
+  AABR_CHECK_HIP(dyn_lds_once(kWideLds[e - kWide], (const void *)e->fn, 80 * 1024));
+  g_last_variant = a.split ? e->split_name : e->name;
+  const dim3 grid((unsigned)t.grid_x, (unsigned)t.grid_y);
+  const float *in = static_cast<const float *>(a.in), *wp = static_cast<const float *>(a.wpack);
+  if (a.split) {   // fp32 partial tiles into the scratch; bias, residual and the storage rounding happen in the reduce
+    hipLaunchKernelGGL(e->fn, grid, dim3(256), (size_t)t.lds_bytes, st, in, a.n_in, t.in_bytes, a.scratch, a.n_out, a.V_out,
+                       a.blocks, t.words_bytes, a.vol, t.wflip, wp, t.wp_bytes, (const float *)nullptr, a.tile_rows,
+                       (const float *)nullptr, (double *)nullptr, BnBwdStats{});
+    const int64_t n4 = a.V_out * a.n_out / 4;
+    const dim3 rgrid((unsigned)((n4 + 255) / 256));
+    const float *res = static_cast<const float *>(a.residual);
+    if (bf16)
+      hipLaunchKernelGGL((k_split_reduce<true>), rgrid, dim3(256), 0, st, a.scratch, a.parts, n4, a.n_out / 4, a.bias, res, a.out);
+    else
+      hipLaunchKernelGGL((k_split_reduce<false>), rgrid, dim3(256), 0, st, a.scratch, a.parts, n4, a.n_out / 4, a.bias, res, a.out);
+  } else {
+    hipLaunchKernelGGL(e->fn, grid, dim3(256), (size_t)t.lds_bytes, st, in, a.n_in, t.in_bytes, static_cast<float *>(a.out),
+                       a.n_out, a.V_out, a.blocks, t.words_bytes, a.vol, t.wflip, wp, t.wp_bytes, a.bias, a.tile_rows,
+                       static_cast<const float *>(a.residual), a.stats, a.bn);
   }
-  if (P < 2) return 0;
-  if (wide_words(V_out, vol, T) * 4 >= (1ll << 31) || (int64_t)vol * n_in * n_out * 4 >= (1ll << 31)) return 0;
-  return (P << 16) | T;
-}
-
-extern "C" int64_t aabr_conv_wide_split_scratch_floats(int64_t V_out, int n_out, int parts) {
-  return V_out > 0 && n_out > 0 && parts > 0 ? (int64_t)parts * V_out * n_out : 0;
-}
-
-extern "C" int aabr_conv_forward_wide_split(const float *in_feats, int n_in, int64_t rows_in, float *out_feats, int n_out,
-                                            int64_t V_out, const int32_t *blocks, int tile_rows, int vol,
-                                            const float *bias, int flags, const float *wpack, const float *residual,
-                                            int parts, float *scratch, void *stream_) {
-  hipStream_t st = (hipStream_t)stream_;
-  AABR_CHECK_ARG(parts >= 2 && parts <= 32 && parts <= vol && scratch && ((uintptr_t)scratch & 15) == 0,
-                 "2 <= parts <= min(32, vol) and a 16-byte aligned scratch of parts x V_out x n_out floats");
-  AABR_CHECK_ARG(((uintptr_t)residual & 15) == 0, "residual must be 16-byte aligned");
-  AABR_CHECK_ARG(n_in > 0 && n_out > 0 && (n_in & 31) == 0 && (n_out & 63) == 0, "plane counts: n_in % 32, n_out % 64");
-  AABR_CHECK_ARG(vol > 0 && vol <= kMaxVol && V_out >= 0 && rows_in >= 0, "bad sizes");
-  AABR_CHECK_ARG(tile_rows >= 16 && tile_rows <= kMaxTileRows && (tile_rows & 15) == 0, "tile_rows: multiple of 16, <= 240");
-  if (V_out == 0) return AABR_OK;
-  AABR_CHECK_ARG(in_feats && out_feats && blocks && wpack && rows_in > 0, "null pointer / empty input");
-  AABR_CHECK_ARG(rows_in < (1ll << 23), "too many input rows for the wide block format");
-  const int64_t in_bytes = rows_in * n_in * 4, words_bytes = wide_words(V_out, vol, tile_rows) * 4;
-  AABR_CHECK_ARG(in_bytes < (1ll << 31) && words_bytes < (1ll << 31), "buffers must be < 2 GiB");
-  AABR_CHECK_ARG(((uintptr_t)in_feats & 15) == 0 && ((uintptr_t)out_feats & 15) == 0 && ((uintptr_t)wpack & 15) == 0,
-                 "feature / weight pointers must be 16-byte aligned");
-  const int nkc = n_in / 32;
-  const int64_t wp_bytes = (int64_t)vol * nkc * (n_out / 16) * 2048;
-  AABR_CHECK_ARG(wp_bytes < (1ll << 31), "packed weights must be < 2 GiB");
-  AABR_CHECK_ARG(n_in <= 128 || (n_in & 127) == 0, "n_in above 128 must be a multiple of 128");
-  dim3 grid((unsigned)((V_out + tile_rows - 1) / tile_rows), (unsigned)((n_out / 64) * parts));
-  const int flip = ((flags >> 1) & 1) | (knob(K_WIDE_PRIO) == 0 ? 0 : 2) | (parts << 8);
-  const int kg = nkc >= 4 ? 4 : nkc;
-  const int nbuf = knob(K_SPLIT_NBUF) == 2 ? 2 : 1;   // single stage buffer: three workgroups per CU (latency-bound launches)
-#define AABR_SPLIT_CS_N(KG, NB)                                                                                        \
-  do {                                                                                                                 \
-    static DynLdsOnce attr;                                                                               \
-    AABR_CHECK_HIP(dyn_lds_once(attr, (const void *)(k_conv_cs<KG, 0, NB>), 80 * 1024));          \
-    g_last_variant = "k_conv_cs<" #KG ",0," #NB ",split>";                                                             \
-    hipLaunchKernelGGL((k_conv_cs<KG, 0, NB>), grid, dim3(256),                                                        \
-                       (size_t)((tile_rows + 1) * kWS + NB * 2 * 16 * KG * 32) * sizeof(float), st, in_feats, n_in,     \
-                       in_bytes, scratch, n_out, V_out, blocks, words_bytes, vol, flip, wpack, wp_bytes,                \
-                       (const float *)nullptr, tile_rows, (const float *)nullptr, (double *)nullptr, BnBwdStats{});     \
-  } while (0)
-#define AABR_SPLIT_CS(KG) do { if (nbuf == 1) AABR_SPLIT_CS_N(KG, 1); else AABR_SPLIT_CS_N(KG, 2); } while (0)
-  if (kg == 2) AABR_SPLIT_CS(2); else if (kg == 3) AABR_SPLIT_CS(3); else AABR_SPLIT_CS(4);
-#undef AABR_SPLIT_CS
-#undef AABR_SPLIT_CS_N
-  const int64_t n4 = V_out * n_out / 4;
-  hipLaunchKernelGGL((k_split_reduce<false>), dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, scratch, parts, n4,
-                     n_out / 4, bias, residual, (void *)out_feats);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }
 
+// ---- fp32 storage -------------------------------------------------------------------------------------------------------
+extern "C" int aabr_conv_forward_wide_stats(const float *in_feats, int n_in, int64_t rows_in, float *out_feats,
+                                            int n_out, int64_t V_out, const int32_t *blocks, int tile_rows, int vol,
+                                            const float *bias, int flags, const float *wpack, const float *residual,
+                                            double *stats, void *stream_) {
+  return wide_run({__func__, kWideF32, in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags,
+                   wpack, residual, stats, BnBwdStats{}, false, 0, nullptr, stream_});
+}
+
+extern "C" int aabr_conv_forward_wide_res(const float *in_feats, int n_in, int64_t rows_in, float *out_feats,
+                                          int n_out, int64_t V_out, const int32_t *blocks, int tile_rows, int vol,
+                                          const float *bias, int flags, const float *wpack, const float *residual,
+                                          void *stream_) {
+  return wide_run({__func__, kWideF32, in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags,
+                   wpack, residual, nullptr, BnBwdStats{}, false, 0, nullptr, stream_});
+}
+
+extern "C" int aabr_conv_forward_wide(const float *in_feats, int n_in, int64_t rows_in, float *out_feats, int n_out,
+                                      int64_t V_out, const int32_t *blocks, int tile_rows, int vol, const float *bias,
+                                      int flags, const float *wpack, void *stream_) {
+  return wide_run({__func__, kWideF32, in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags,
+                   wpack, nullptr, nullptr, BnBwdStats{}, false, 0, nullptr, stream_});
+}
+
+extern "C" int aabr_conv_forward_wide_bwd_stats(const float *in_feats, int n_in, int64_t rows_in, float *out_feats,
+                                                int n_out, int64_t V_out, const int32_t *blocks, int tile_rows, int vol,
+                                                const float *bias, int flags, const float *wpack, const float *residual,
+                                                double *stats, const float *bn_in, const float *save_mean,
+                                                const float *save_invstd, const float *bn_weight, const float *bn_bias,
+                                                float leakiness, void *stream_) {
+  AABR_CHECK_ARG(stats && bn_in && save_mean && save_invstd, "null pointer");
+  AABR_CHECK_ARG(leakiness >= 0.0f, "the activation sign is recomputed from the BatchNorm input: leakiness >= 0");
+  AABR_CHECK_ARG(((uintptr_t)bn_in & 15) == 0, "the BatchNorm input must be 16-byte aligned");
+  return wide_run({__func__, kWideF32, in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags,
+                   wpack, residual, stats, BnBwdStats{bn_in, save_mean, save_invstd, bn_weight, bn_bias, leakiness}, false, 0,
+                   nullptr, stream_});
+}
+
+// n_in >= 64: the split compiles no 32-channel instance, and n_in = 32 is AABR_EINVAL before any launch.  (It used to
+// pass every check and run the 128-channel instance on 32-channel rows; the library's own route never asks for it,
+// aabr_conv_wide_split requires n_in >= 64.)
+extern "C" int aabr_conv_forward_wide_split(const float *in_feats, int n_in, int64_t rows_in, float *out_feats, int n_out,
+                                            int64_t V_out, const int32_t *blocks, int tile_rows, int vol,
+                                            const float *bias, int flags, const float *wpack, const float *residual,
+                                            int parts, float *scratch, void *stream_) {
+  return wide_run({__func__, kWideF32, in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags,
+                   wpack, residual, nullptr, BnBwdStats{}, true, parts, scratch, stream_});
+}
+
 // ---- bf16 feature storage (extension): the same kernel on 128-byte row chunks of 64 bf16 channels ------------------
-// 16-column blocks per wave of the bf16 launch: 2 (128-column slabs) for n_out % 128 == 0 up to 128 input channels
-// (two weight register sets of 16 x NCB x KG registers), else 1; WIDE_NCB knob: 1 forces 64-column slabs
-static int wide_bf16_ncb(int n_in, int n_out) {
-  if (knob(K_WIDE_NCB) == 1) return 1;
-  return ((n_out & 127) == 0 && n_in <= 128) ? 2 : 1;
+// the statistics forms read the STORED activations: bn_in / bn_out are bf16 rows
+static BnBwdStats bf16_bwd_stats(const uint16_t *bn_in, const uint16_t *bn_out, const float *save_mean, float leakiness) {
+  return BnBwdStats{reinterpret_cast<const float *>(bn_in), save_mean, nullptr, nullptr, nullptr, leakiness,
+                    reinterpret_cast<const float *>(bn_out)};
 }
-
-// 0: use aabr_conv_forward_bf16 (64-row tiles); otherwise rows per tile for aabr_conv_forward_wide_bf16
-extern "C" int aabr_conv_wide_tile_rows_bf16(int n_in, int n_out, int64_t rows_in, int64_t V_out, int vol) {
-  if (n_in <= 0 || n_out <= 0 || (n_in & 63) || (n_out & 63) || vol <= 0 || vol > kMaxVol) return 0;
-  if (rows_in >= (1ll << 23) || rows_in * n_in * 2 >= (1ll << 31)) return 0;
-  if (n_in > 256 && (n_in & 255)) return 0; // channel groups of 256: every load of the inner loop unconditional
-  // bf16: two MFMAs per block and 64-channel chunk -- the gather / stage / barrier skeleton sets the pace, so more
-  // resident workgroups pay: 96-row tiles with a single stage buffer (measured on the bench's rule books: convolution
-  // time of a bf16 step 5.25 -> 5.01 ms against 128 rows + two buffers; 64 rows: 5.24)
-  // 128-column slabs when the layer has them: the kernel is bound by the CU's random-row gather rate and a 64-column
-  // slab gathers every row once per slab.  Their fp32 tile is 512 B per row: 64 rows (33 KiB + 8 KiB of stage) keep
-  // three workgroups per CU; 64-column slabs keep the 96-row tiles of round 2.
-  const int ncb = wide_bf16_ncb(n_in, n_out);
-  int T = ncb == 2 ? 64 : 96;
-  {
-    const int64_t slabs = n_out / (64 * ncb);
-    if (((V_out + T - 1) / T) * slabs <= 512)
-      for (int t = 64; t < T; t += 16)
-        if (((V_out + t - 1) / t) * slabs <= 512) { T = t; break; }
-  }
-  {                                                // tuning experiments only
-    const int v = knob(K_WIDE_ROWS);
-    if (v >= 16 && v <= kMaxTileRows && (v & 15) == 0) T = v;
-  }
-  if (wide_words(V_out, vol, T) * 4 >= (1ll << 31)) return 0;
-  if ((int64_t)vol * n_in * n_out * 2 >= (1ll << 31)) return 0;
-  {                                                // tuning experiments / tests only: 0 = never, 1 = whenever supported
-    const int v = knob(K_CONV_WIDE_BF16);
-    if (v == 0) return 0;
-    if (v == 1) return T;
-  }
-  return (((V_out + T - 1) / T) * (n_out / (64 * ncb)) >= 320) ? T : 0;
-}
-
-extern "C" int aabr_conv_forward_wide_bf16_stats(const uint16_t *in_feats, int n_in, int64_t rows_in,
-                                                 uint16_t *out_feats, int n_out, int64_t V_out, const int32_t *blocks,
-                                                 int tile_rows, int vol, const float *bias, int flags,
-                                                 const uint16_t *wpack, double *stats, void *stream_);
-
-extern "C" int aabr_conv_forward_wide_bf16(const uint16_t *in_feats, int n_in, int64_t rows_in, uint16_t *out_feats,
-                                           int n_out, int64_t V_out, const int32_t *blocks, int tile_rows, int vol,
-                                           const float *bias, int flags, const uint16_t *wpack, void *stream_) {
-  return aabr_conv_forward_wide_bf16_stats(in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias,
-                                           flags, wpack, nullptr, stream_);
-}
-
-static int wide_launch_bf16(const uint16_t *in_feats, int n_in, int64_t rows_in, uint16_t *out_feats, int n_out,
-                            int64_t V_out, const int32_t *blocks, int tile_rows, int vol, const float *bias, int flags,
-                            const uint16_t *wpack, const uint16_t *residual, double *stats, BnBwdStats bn, void *stream_);
 
 extern "C" int aabr_conv_forward_wide_bf16_stats(const uint16_t *in_feats, int n_in, int64_t rows_in,
                                                  uint16_t *out_feats, int n_out, int64_t V_out, const int32_t *blocks,
                                                  int tile_rows, int vol, const float *bias, int flags,
                                                  const uint16_t *wpack, double *stats, void *stream_) {
-  return wide_launch_bf16(in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags, wpack,
-                          nullptr, stats, BnBwdStats{}, stream_);
+  return wide_run({__func__, kWideBf16, in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags,
+                   wpack, nullptr, stats, BnBwdStats{}, false, 0, nullptr, stream_});
+}
+
+extern "C" int aabr_conv_forward_wide_bf16(const uint16_t *in_feats, int n_in, int64_t rows_in, uint16_t *out_feats,
+                                           int n_out, int64_t V_out, const int32_t *blocks, int tile_rows, int vol,
+                                           const float *bias, int flags, const uint16_t *wpack, void *stream_) {
+  return wide_run({__func__, kWideBf16, in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags,
+                   wpack, nullptr, nullptr, BnBwdStats{}, false, 0, nullptr, stream_});
 }
 
 // the general bf16-storage form behind the compiled pass: optional residual (out = conv + residual, both rounded as
@@ -977,16 +892,13 @@ extern "C" int aabr_conv_forward_wide_bf16_res(const uint16_t *in_feats, int n_i
                                                const uint16_t *residual, double *stats, const uint16_t *bn_in,
                                                const uint16_t *bn_out, const float *save_mean, float leakiness,
                                                void *stream_) {
-  AABR_CHECK_ARG(((uintptr_t)residual & 7) == 0, "residual must be 8-byte aligned");
-  BnBwdStats bn{};
   if (bn_in) {
     AABR_CHECK_ARG(stats && bn_out && save_mean, "null pointer");
     AABR_CHECK_ARG((((uintptr_t)bn_in | (uintptr_t)bn_out) & 7) == 0, "the BatchNorm's input / output must be 8-byte aligned");
-    bn = BnBwdStats{reinterpret_cast<const float *>(bn_in), save_mean, nullptr, nullptr, nullptr, leakiness,
-                    reinterpret_cast<const float *>(bn_out)};
   }
-  return wide_launch_bf16(in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags, wpack,
-                          residual, stats, bn, stream_);
+  return wide_run({__func__, kWideBf16, in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags,
+                   wpack, residual, stats, bn_in ? bf16_bwd_stats(bn_in, bn_out, save_mean, leakiness) : BnBwdStats{}, false,
+                   0, nullptr, stream_});
 }
 
 extern "C" int aabr_conv_forward_wide_bf16_bwd_stats(const uint16_t *in_feats, int n_in, int64_t rows_in,
@@ -997,136 +909,8 @@ extern "C" int aabr_conv_forward_wide_bf16_bwd_stats(const uint16_t *in_feats, i
                                                      const float *save_mean, float leakiness, void *stream_) {
   AABR_CHECK_ARG(stats && bn_in && bn_out && save_mean, "null pointer");
   AABR_CHECK_ARG((((uintptr_t)bn_in | (uintptr_t)bn_out) & 7) == 0, "the BatchNorm's input / output must be 8-byte aligned");
-  BnBwdStats bn{reinterpret_cast<const float *>(bn_in), save_mean, nullptr, nullptr, nullptr, leakiness,
-                reinterpret_cast<const float *>(bn_out)};
-  return wide_launch_bf16(in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags, wpack,
-                          nullptr, stats, bn, stream_);
-}
-
-static int wide_launch_bf16(const uint16_t *in_feats, int n_in, int64_t rows_in, uint16_t *out_feats, int n_out,
-                            int64_t V_out, const int32_t *blocks, int tile_rows, int vol, const float *bias, int flags,
-                            const uint16_t *wpack, const uint16_t *residual, double *stats, BnBwdStats bn, void *stream_) {
-  hipStream_t st = (hipStream_t)stream_;
-  AABR_CHECK_ARG(!stats || (tile_rows >= 64 && ((uintptr_t)stats & 7) == 0), "statistics need tiles of >= 64 rows");
-  AABR_CHECK_ARG(n_in > 0 && n_out > 0 && (n_in & 63) == 0 && (n_out & 63) == 0, "plane counts: n_in % 64, n_out % 64");
-  AABR_CHECK_ARG(vol > 0 && vol <= kMaxVol && V_out >= 0 && rows_in >= 0, "bad sizes");
-  AABR_CHECK_ARG(tile_rows >= 16 && tile_rows <= kMaxTileRows && (tile_rows & 15) == 0, "tile_rows: multiple of 16, <= 240");
-  if (V_out == 0) return AABR_OK;
-  AABR_CHECK_ARG(in_feats && out_feats && blocks && wpack && rows_in > 0, "null pointer / empty input");
-  AABR_CHECK_ARG(rows_in < (1ll << 23), "too many input rows for the wide block format");
-  const int64_t in_bytes = rows_in * n_in * 2, words_bytes = wide_words(V_out, vol, tile_rows) * 4;
-  AABR_CHECK_ARG(in_bytes < (1ll << 31) && words_bytes < (1ll << 31), "buffers must be < 2 GiB");
-  AABR_CHECK_ARG(((uintptr_t)in_feats & 15) == 0 && ((uintptr_t)out_feats & 15) == 0 && ((uintptr_t)wpack & 15) == 0,
-                 "feature / weight pointers must be 16-byte aligned");
-  const int nkc = n_in / 64; // 128-byte chunks per row
-  const int64_t wp_bytes = (int64_t)vol * (n_in / 32) * (n_out / 16) * 1024;
-  AABR_CHECK_ARG(wp_bytes < (1ll << 31), "packed weights must be < 2 GiB");
-  AABR_CHECK_ARG(n_in <= 256 || (n_in & 255) == 0, "n_in above 256 must be a multiple of 256");
-  const int ncb = wide_bf16_ncb(n_in, n_out);
-  dim3 grid((unsigned)((V_out + tile_rows - 1) / tile_rows), (unsigned)(n_out / (64 * ncb)));
-  const int flip = ((flags >> 1) & 1) | (knob(K_WIDE_PRIO) == 1 ? 2 : 0);   // bf16: priority only on request (measured below)
-  const int kg = nkc >= 4 ? 4 : nkc;
-  int nbuf = 1;
-  {                                                // tuning experiments only
-    const int v = knob(K_WIDE_NBUF);
-    if (v == 1 || v == 2) nbuf = v;
-  }
-  const float *in_f = reinterpret_cast<const float *>(in_feats), *wp_f = reinterpret_cast<const float *>(wpack);
-  float *out_f = reinterpret_cast<float *>(out_feats);
-  const float *res_f = reinterpret_cast<const float *>(residual);
-constexpr int kBfSets = 2;   // gather register sets of the bf16 launches (4: measured slower, 100 -> 112 us)
-#define AABR_WIDE_BF(KG, NB, NCB) AABR_WIDE_BF_S(KG, NB, NCB, ((KG) <= 2 ? kBfSets : 2))
-#define AABR_WIDE_BF_D(KG, NB, NCB, D)                                                                              \
-  do {                                                                                                             \
-    static DynLdsOnce attr;                                                                                        \
-    AABR_CHECK_HIP(dyn_lds_once(attr, (const void *)(k_conv_cs<KG, D, NB, true, NCB, kBfSets>), 80 * 1024));       \
-    hipLaunchKernelGGL((k_conv_cs<KG, D, NB, true, NCB, kBfSets>), grid, dim3(256),                                \
-                       (size_t)((tile_rows + 1) * kWS * NCB + NB * 2 * 16 * KG * 32) * sizeof(float), st, in_f,    \
-                       n_in, in_bytes, out_f, n_out, V_out, blocks, words_bytes, vol, flip, wp_f, wp_bytes, bias,  \
-                       tile_rows, res_f, stats, bn);                                                      \
-  } while (0)
-#define AABR_WIDE_BF_S(KG, NB, NCB, NS) AABR_WIDE_BF_L(KG, NB, NCB, NS)
-#define AABR_WIDE_BF_L(KG, NB, NCB, NS)                                                                            \
-  do {                                                                                                             \
-    static DynLdsOnce attr;                                                                                        \
-    AABR_CHECK_HIP(dyn_lds_once(attr, (const void *)(k_conv_cs<KG, 0, NB, true, NCB, NS>), 80 * 1024));          \
-    g_last_variant = NCB == 2 ? "k_conv_cs<" #KG ",0," #NB ",bf16,x128>" : "k_conv_cs<" #KG ",0," #NB ",bf16>";    \
-    hipLaunchKernelGGL((k_conv_cs<KG, 0, NB, true, NCB, NS>), grid, dim3(256),                   \
-                       (size_t)((tile_rows + 1) * kWS * NCB + NB * 2 * 16 * KG * 32) * sizeof(float), st, in_f,    \
-                       n_in, in_bytes, out_f, n_out, V_out, blocks, words_bytes, vol, flip, wp_f, wp_bytes, bias,  \
-                       tile_rows, res_f, stats, bn);                                              \
-  } while (0)
-#define AABR_WIDE_BF_K(KG)                                                                                         \
-  do {                                                                                                             \
-    if (ncb == 2) { if (nbuf == 1) AABR_WIDE_BF(KG, 1, 2); else AABR_WIDE_BF(KG, 2, 2); }                          \
-    else { if (nbuf == 1) AABR_WIDE_BF(KG, 1, 1); else AABR_WIDE_BF(KG, 2, 1); }                                   \
-  } while (0)
-#define AABR_WIDE_BF_K1(KG) /* more than 128 input channels: 64-column slabs only (wide_bf16_ncb) */                 \
-  do {                                                                                                             \
-    if (nbuf == 1) AABR_WIDE_BF(KG, 1, 1); else AABR_WIDE_BF(KG, 2, 1);                                            \
-  } while (0)
-  AABR_CHECK_ARG(ncb == 1 || kg <= 2, "128-column slabs need n_in <= 128");
-#ifdef AABR_DEV
-  if ((flags >> 8) & 4) {   // timing experiments (tools/tools_cs_phases.py bf16): phase clocks of the 128-channel instance
-    AABR_CHECK_ARG(kg == 2, "the bf16 phase-clock variant exists for n_in = 128 only");
-    if (ncb == 2) AABR_WIDE_BF_D(2, 1, 2, 4);
-    else AABR_WIDE_BF_D(2, 1, 1, 4);
-    AABR_CHECK_LAUNCH();
-    return AABR_OK;
-  }
-#endif
-  if (kg == 1) AABR_WIDE_BF_K(1); else if (kg == 2) AABR_WIDE_BF_K(2); else if (kg == 3) AABR_WIDE_BF_K1(3);
-  else AABR_WIDE_BF_K1(4);
-#undef AABR_WIDE_BF_K1
-#undef AABR_WIDE_BF_K
-#undef AABR_WIDE_BF
-#undef AABR_WIDE_BF_S
-#undef AABR_WIDE_BF_L
-#undef AABR_WIDE_BF_D
-  AABR_CHECK_LAUNCH();
-  return AABR_OK;
-}
-
-
-// ---- offset split, bf16 storage ---------------------------------------------------------------------------------------
-// the coarse scales of a bf16-storage pass (round 4: 50 launches of k_conv_blocks_mfma_bf16 per step, 8 % of the bf16
-// step's kernel time): the same cut over the filter offsets; the parts are fp32 (the kernel's LDS tile is), the reduce
-// kernel rounds once to bf16 -- the same single rounding per stored value as the unsplit kernels.
-extern "C" int aabr_conv_wide_split_bf16(int n_in, int n_out, int64_t rows_in, int64_t V_out, int vol) {
-  if (n_in <= 0 || n_out <= 0 || (n_in & 63) || (n_out & 63) || vol <= 1 || vol > kMaxVol || V_out <= 0) return 0;
-  if (rows_in >= (1ll << 23) || rows_in * n_in * 2 >= (1ll << 31)) return 0;
-  if (n_in > 256 && (n_in & 255)) return 0;
-  if (knob(K_WIDE_SPLIT) == 0 || knob(K_CONV_WIDE_BF16) == 0) return 0;
-  int T = 64;
-  if (((V_out + 63) / 64) * (n_out / 64) >= 320) return 0;
-  { const int v = knob(K_SPLIT_ROWS); if (v >= 64 && v <= 128 && (v & 15) == 0) T = v; }   // (A/B)
-  const int64_t items = ((V_out + T - 1) / T) * (n_out / 64);
-  const int min_items = knob(K_SPLIT_MIN_ITEMS) == kKnobUnset ? 8 : knob(K_SPLIT_MIN_ITEMS);
-  if (items < min_items) return 0;
-  const int target = knob(K_SPLIT_TARGET) == kKnobUnset ? 768 : knob(K_SPLIT_TARGET);   // (bf16: 768 / 1024 / 1280 -> 1156 / 1192 / 1204 us of coarse-scale convolutions per step)
-  int P = (int)((target + items - 1) / items);
-  if (P > vol) P = vol;
-  if (P > 32) P = 32;
-  {
-    const int v = knob(K_WIDE_SPLIT);
-    if (v >= 2 && v <= 32) P = v < vol ? v : vol;
-  }
-  if (P < 2) return 0;
-  if (wide_words(V_out, vol, T) * 4 >= (1ll << 31) || (int64_t)vol * n_in * n_out * 2 >= (1ll << 31)) return 0;
-  return (P << 16) | T;
-}
-
-extern "C" int aabr_conv_forward_wide_split_bf16_res(const uint16_t *in_feats, int n_in, int64_t rows_in,
-                                                     uint16_t *out_feats, int n_out, int64_t V_out, const int32_t *blocks,
-                                                     int tile_rows, int vol, const float *bias, int flags,
-                                                     const uint16_t *wpack, int parts, float *scratch,
-                                                     const uint16_t *residual, void *stream_);
-extern "C" int aabr_conv_forward_wide_split_bf16(const uint16_t *in_feats, int n_in, int64_t rows_in, uint16_t *out_feats,
-                                                 int n_out, int64_t V_out, const int32_t *blocks, int tile_rows, int vol,
-                                                 const float *bias, int flags, const uint16_t *wpack, int parts,
-                                                 float *scratch, void *stream_) {
-  return aabr_conv_forward_wide_split_bf16_res(in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias,
-                                               flags, wpack, parts, scratch, nullptr, stream_);
+  return wide_run({__func__, kWideBf16, in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags,
+                   wpack, nullptr, stats, bf16_bwd_stats(bn_in, bn_out, save_mean, leakiness), false, 0, nullptr, stream_});
 }
 
 extern "C" int aabr_conv_forward_wide_split_bf16_res(const uint16_t *in_feats, int n_in, int64_t rows_in,
@@ -1134,44 +918,14 @@ extern "C" int aabr_conv_forward_wide_split_bf16_res(const uint16_t *in_feats, i
                                                      int tile_rows, int vol, const float *bias, int flags,
                                                      const uint16_t *wpack, int parts, float *scratch,
                                                      const uint16_t *residual, void *stream_) {
-  hipStream_t st = (hipStream_t)stream_;
-  AABR_CHECK_ARG(((uintptr_t)residual & 7) == 0, "residual must be 8-byte aligned");
-  AABR_CHECK_ARG(parts >= 2 && parts <= 32 && parts <= vol && scratch && ((uintptr_t)scratch & 15) == 0,
-                 "2 <= parts <= min(32, vol) and a 16-byte aligned scratch of parts x V_out x n_out floats");
-  AABR_CHECK_ARG(n_in > 0 && n_out > 0 && (n_in & 63) == 0 && (n_out & 63) == 0, "plane counts: n_in % 64, n_out % 64");
-  AABR_CHECK_ARG(vol > 0 && vol <= kMaxVol && V_out >= 0 && rows_in >= 0, "bad sizes");
-  AABR_CHECK_ARG(tile_rows >= 16 && tile_rows <= kMaxTileRows && (tile_rows & 15) == 0, "tile_rows: multiple of 16, <= 240");
-  if (V_out == 0) return AABR_OK;
-  AABR_CHECK_ARG(in_feats && out_feats && blocks && wpack && rows_in > 0, "null pointer / empty input");
-  AABR_CHECK_ARG(rows_in < (1ll << 23), "too many input rows for the wide block format");
-  const int64_t in_bytes = rows_in * n_in * 2, words_bytes = wide_words(V_out, vol, tile_rows) * 4;
-  AABR_CHECK_ARG(in_bytes < (1ll << 31) && words_bytes < (1ll << 31), "buffers must be < 2 GiB");
-  AABR_CHECK_ARG(((uintptr_t)in_feats & 15) == 0 && ((uintptr_t)out_feats & 15) == 0 && ((uintptr_t)wpack & 15) == 0,
-                 "feature / weight pointers must be 16-byte aligned");
-  const int nkc = n_in / 64;
-  const int64_t wp_bytes = (int64_t)vol * (n_in / 32) * (n_out / 16) * 1024;
-  AABR_CHECK_ARG(wp_bytes < (1ll << 31), "packed weights must be < 2 GiB");
-  AABR_CHECK_ARG(n_in <= 256 || (n_in & 255) == 0, "n_in above 256 must be a multiple of 256");
-  dim3 grid((unsigned)((V_out + tile_rows - 1) / tile_rows), (unsigned)((n_out / 64) * parts));
-  const int flip = ((flags >> 1) & 1) | (parts << 8);
-  const int kg = nkc >= 4 ? 4 : nkc;
-  const float *in_f = reinterpret_cast<const float *>(in_feats), *wp_f = reinterpret_cast<const float *>(wpack);
-#define AABR_SPLIT_BF(KG)                                                                                              \
-  do {                                                                                                                 \
-    static DynLdsOnce attr;                                                                                        \
-    AABR_CHECK_HIP(dyn_lds_once(attr, (const void *)(k_conv_cs<KG, 0, 1, true, 1, 2>), 80 * 1024));          \
-    g_last_variant = "k_conv_cs<" #KG ",0,1,bf16,split>";                                                              \
-    hipLaunchKernelGGL((k_conv_cs<KG, 0, 1, true, 1, 2>), grid, dim3(256),                                             \
-                       (size_t)((tile_rows + 1) * kWS + 2 * 16 * KG * 32) * sizeof(float), st, in_f, n_in, in_bytes,    \
-                       scratch, n_out, V_out, blocks, words_bytes, vol, flip, wp_f, wp_bytes, (const float *)nullptr,   \
-                       tile_rows, (const float *)nullptr, (double *)nullptr, BnBwdStats{});                            \
-  } while (0)
-  if (kg == 1) AABR_SPLIT_BF(1); else if (kg == 2) AABR_SPLIT_BF(2); else if (kg == 3) AABR_SPLIT_BF(3); else AABR_SPLIT_BF(4);
-#undef AABR_SPLIT_BF
-  const int64_t n4 = V_out * n_out / 4;
-  hipLaunchKernelGGL((k_split_reduce<true>), dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, scratch, parts, n4,
-                     n_out / 4, bias, reinterpret_cast<const float *>(residual), (void *)out_feats);
-  AABR_CHECK_LAUNCH();
-  return AABR_OK;
+  return wide_run({__func__, kWideBf16, in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags,
+                   wpack, residual, nullptr, BnBwdStats{}, true, parts, scratch, stream_});
 }
 
+extern "C" int aabr_conv_forward_wide_split_bf16(const uint16_t *in_feats, int n_in, int64_t rows_in, uint16_t *out_feats,
+                                                 int n_out, int64_t V_out, const int32_t *blocks, int tile_rows, int vol,
+                                                 const float *bias, int flags, const uint16_t *wpack, int parts,
+                                                 float *scratch, void *stream_) {
+  return wide_run({__func__, kWideBf16, in_feats, n_in, rows_in, out_feats, n_out, V_out, blocks, tile_rows, vol, bias, flags,
+                   wpack, nullptr, nullptr, BnBwdStats{}, true, parts, scratch, stream_});
+}

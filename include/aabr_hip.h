@@ -573,7 +573,8 @@ int aabr_conv_forward_narrow_bf16_bwd_stats(const uint16_t *in_feats, int64_t ro
  *                             p8 save_mean, p9 save_invstd, p10 bn_weight, p11 bn_bias, f32[0] leakiness); bf16
  *                             storage: aabr_conv_forward_wide_bf16_res(..., p5 wpack, p3 residual, p6 stats), with
  *                             i32[5] == 1 also p7 bn_in, p9 bn_out, p8 save_mean, f32[0] leakiness (the backward
- *                             statistics); p3 / p6 NULL: no residual / no statistics, in either storage
+ *                             statistics); p3 / p6 NULL: no residual / no statistics, in either storage -- in bf16
+ *                             storage too p3 is READ as the residual (bf16 rows): it must be NULL when none is wanted
  *        AABR_PLAN_CONV_DW    aabr_conv_backward_weight[_bf16](p0 in, i32[0] n_in, p1 d_out, i32[1] n_out,
  *                             i64[0] V_out, p2 pairs, i32[2] vol, i64[1] max_chunks, p3 dW, p4 d_bias, p5 scratch)
  *        AABR_PLAN_BN_FWD     aabr_bn_forward[_bf16](p0 in, p1 out, i64[0] rows, i32[0] planes, p2 save_mean,
@@ -584,8 +585,9 @@ int aabr_conv_forward_narrow_bf16_bwd_stats(const uint16_t *in_feats, int64_t ro
  *                             p4 save_mean, p5 save_invstd, p6 weight, p10 bias, p7 d_weight, p8 d_bias,
  *                             f32[2] leakiness, p9 scratch) with p11 d_in_add (the gradient sum folded in; NULL: none,
  *                             in either storage) and, i64[1] != 0, the statistics' partial sums (parts =
- *                             (double *)i64[1], i32[1] nparts).  fp32: i64[1] != 0 ? aabr_bn_backward_parts(..., p9,
- *                             p11) : aabr_bn_backward_add(..., p9, p11); bf16: p11 != NULL ?
+ *                             (double *)i64[1], i32[1] nparts).  A bf16 record's p11 is READ and added as a fp32 one's
+ *                             is: it must be NULL when no sum is wanted.  fp32: i64[1] != 0 ?
+ *                             aabr_bn_backward_parts(..., p9, p11) : aabr_bn_backward_add(..., p9, p11); bf16: p11 != NULL ?
  *                             aabr_bn_backward_add_bf16(..., parts or NULL, i32[1], p9, p11) : i64[1] != 0 ?
  *                             aabr_bn_backward_parts_bf16(..., parts, i32[1], p9) : aabr_bn_backward_bf16(..., p9)
  *        AABR_PLAN_ADD        aabr_add(p0 a, p1 b, p2 out, i64[0] n)
@@ -602,7 +604,8 @@ int aabr_conv_forward_narrow_bf16_bwd_stats(const uint16_t *in_feats, int64_t ro
 #define AABR_PLAN_CONV_WIDE_SPLIT 9 /* aabr_conv_forward_wide_split(p0, i32[0], i64[0], p1, i32[1], i64[1], p2 blocks,
                                        i32[4] tile_rows, i32[2] vol, p4 bias, i32[3] flags, p5 wpack, p3 residual,
                                        i32[5] parts, p6 scratch); bf16 storage: aabr_conv_forward_wide_split_bf16_res(
-                                       ..., p3 residual); p3 NULL: no residual, in either storage */
+                                       ..., p3 residual); p3 NULL: no residual, in either storage (a bf16 record's
+                                       p3 is read as bf16 rows: it must be NULL when no residual is wanted) */
 #define AABR_PLAN_CONV_NARROW 10 /* aabr_conv_forward_narrow[_bf16](p0 in, i64[0] rows_in, p1 out, i64[1] V_out, p2 table,
                                    i32[2] vol, p3 W, p4 bias, i32[3] flags); bf16 storage with p6 != NULL: .._bf16_stats(.., p6
                                    stats); i32[5] == 1: .._bf16_bwd_stats(.., p6 stats, p7 bn_in, p9 bn_out, p8 save_mean,

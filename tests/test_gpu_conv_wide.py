@@ -691,3 +691,81 @@ def test_bf16_residual_in_the_write_out_equals_store_then_add(request, nIn, nOut
         check(lib.aabr_bn_backward_add_bf16(ptr(xb), ptr(dx1), ptr(yb), ptr(dy), rows, planes, ptr(mean), ptr(inv), ptr(w_),
                                             ptr(b_), ptr(dw1), ptr(db1), 0.2, None, 0, ptr(ws), ptr(add), stream()))
         assert torch.equal(dx1, dx0 + add) and torch.equal(dw1, dw0) and torch.equal(db1, db0)
+
+
+def _instance_cases():
+    """every release row of conv_wide.hip's instance table (tests/conv_wide_rule.py lists them), and for the rows a split
+    launch runs too, that launch: (kg, nbuf, bf16, ncb, split); the release rows carry no debug bits"""
+    import conv_wide_rule as R
+    cases = [k + (0,) for k in R.compiled_instances()] + [k + (1,) for k in R.split_instances()]
+    assert all(c[1] == 0 for c in cases)
+    return [(c[0],) + c[2:] for c in cases]
+
+
+@pytest.fixture(scope="module")
+def instance_scene():
+    """a random gather table [8][150] into 170 rows with about a quarter of its entries -1, and the oracle's rule book"""
+    rng = np.random.default_rng(640)
+    V, rows, vol = 150, 170, 8
+    table = rng.integers(0, rows, (vol, V)).astype(np.int32)
+    table[rng.random((vol, V)) < 0.25] = -1
+    counts = (table >= 0).sum(1).astype(np.int64)
+    rules = np.zeros((vol, V, 2), np.int32)
+    for k in range(vol):
+        o = np.nonzero(table[k] >= 0)[0]
+        rules[k, :len(o), 0], rules[k, :len(o), 1] = table[k, o], o
+    return table, O.Rules(rules, counts, V)
+
+
+@pytest.mark.parametrize("kg,nbuf,bf,ncb,split", _instance_cases())
+def test_every_instance_of_the_table_runs_under_its_name(request, instance_scene, kg, nbuf, bf, ncb, split):
+    """each k_conv_cs instance through its entry point at the smallest shape that reaches it (n_in = 32 kg resp. 64 kg,
+    64 or 128 columns, 64-row tiles: two full tiles and a partial one), stage buffers and slab width chosen with the
+    WIDE_NBUF / SPLIT_NBUF / WIDE_NCB knobs: aabr_conv_last_variant names the row, the output matches the oracle"""
+    import _hip
+    import conv_wide_rule as R
+    from _hip import ptr, stream, check
+    lib = _hip.load()
+    table, rb = instance_scene
+    V, rows, vol, T, P = 150, 170, 8, 64, 3
+    n_in, n_out = (64 if bf else 32) * kg, 128 if ncb == 2 else 64
+    for k, v in (("SPLIT_NBUF" if split else "WIDE_NBUF", nbuf), ("WIDE_NCB", ncb)):
+        _hip.set_knob(k, v)
+        request.addfinalizer(lambda k=k: _hip.set_knob(k, None))
+    blocks = torch.empty(int(lib.aabr_wide_blocks_words(V, vol, T)), dtype=torch.int32, device=DEV)
+    check(lib.aabr_build_wide_blocks(ptr(_t(table)), V, vol, T, ptr(blocks), stream()))
+    rs = np.random.default_rng(1000 * kg + 100 * nbuf + 10 * bf + ncb)
+    W = (rs.standard_normal((vol, 1, n_in, n_out)) * 0.1).astype(np.float32)
+    f = rs.standard_normal((rows, n_in)).astype(np.float32)
+    Wd, fd = _t(W), _t(f)
+    scratch = torch.empty(int(lib.aabr_conv_wide_split_scratch_floats(V, n_out, P)), device=DEV)
+    if bf:
+        n = int(lib.aabr_conv_wpack_bf16_elems(vol, n_in, n_out))
+        wp, wt = (torch.empty(n, dtype=torch.bfloat16, device=DEV) for _ in range(2))
+        check(lib.aabr_conv_pack_weights2_bf16(ptr(Wd), vol, n_in, n_out, ptr(wp), ptr(wt), stream()))
+        fd = fd.bfloat16()
+        out = torch.empty((V, n_out), dtype=torch.bfloat16, device=DEV)
+        if split:
+            check(lib.aabr_conv_forward_wide_split_bf16(ptr(fd), n_in, rows, ptr(out), n_out, V, ptr(blocks), T, vol, None,
+                                                        0, ptr(wp), P, ptr(scratch), stream()))
+        else:
+            check(lib.aabr_conv_forward_wide_bf16(ptr(fd), n_in, rows, ptr(out), n_out, V, ptr(blocks), T, vol, None, 0,
+                                                  ptr(wp), stream()))
+    else:
+        wp = torch.empty(lib.aabr_conv_wpack_floats(vol, n_in, n_out), device=DEV)
+        check(lib.aabr_conv_pack_weights(ptr(Wd), vol, n_in, n_out, 0, ptr(wp), stream()))
+        out = torch.empty((V, n_out), device=DEV)
+        if split:
+            check(lib.aabr_conv_forward_wide_split(ptr(fd), n_in, rows, ptr(out), n_out, V, ptr(blocks), T, vol, None, 0,
+                                                   ptr(wp), None, P, ptr(scratch), stream()))
+        else:
+            check(lib.aabr_conv_forward_wide(ptr(fd), n_in, rows, ptr(out), n_out, V, ptr(blocks), T, vol, None, 0, ptr(wp),
+                                             stream()))
+    assert _variant() == R.name((kg, 0, nbuf, bf, ncb), bool(split))
+    if bf:      # the oracle on the same bf16-rounded operands (test_wide_bf16_storage_matches_oracle_on_rounded_operands)
+        ref, _ = O.conv_fwd(fd.float().cpu().numpy(), Wd.bfloat16().float().cpu().numpy().reshape(vol, n_in, n_out), rb, V,
+                            None)
+        np.testing.assert_allclose(out.float().cpu().numpy(), ref, rtol=2 ** -7, atol=2 ** -7 * np.abs(ref).max())
+    else:
+        ref, _ = O.conv_fwd(f, W.reshape(vol, n_in, n_out), rb, V, None)
+        np.testing.assert_allclose(out.cpu().numpy(), ref, rtol=1e-4, atol=2e-6 * np.abs(ref).max() * n_in)
