@@ -94,6 +94,9 @@ _SIGS = {
     "aabr_bn_backward_add_bf16": (C.c_int, [_vp] * 4 + [_i64, _i32] + [_vp] * 6 + [_f32, _vp, _i32, _vp, _vp, _vp]),
     "aabr_conv_forward_wide_split": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp,
                                                _i32, _vp, _vp]),
+    "aabr_conv_single_chunk": (C.c_int, [_i32, _i32, _i64, _i64, _i32, _i32, _i32]),
+    "aabr_conv_single_refusal": (C.c_char_p, [_i32, _i32, _i64, _i64, _i32, _i32, _i32]),
+    "aabr_conv_forward_single": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "aabr_conv_wide_tile_rows_bf16": (C.c_int, [_i32, _i32, _i64, _i64, _i32]),
     "aabr_conv_forward_wide_bf16": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp]),
     "aabr_conv_forward_wide_res": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp,

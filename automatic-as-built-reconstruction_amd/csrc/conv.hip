@@ -19,6 +19,7 @@
 //
 // fp32 MFMA == k-ordered fmaf chain (exact fp32); peak 157 TFLOP/s.
 #include "common.h"
+#include "offset_pairs.h"   // op_hdr, op_nb256, dw_chunk_range: the pair list's layout and its chunks
 #include <stdlib.h>
 
 namespace aabr {
@@ -1442,9 +1443,6 @@ __global__ __launch_bounds__(WPB * 64, 2) void k_conv_blocks_mfma_bf16(
 __host__ __device__ inline int dw_chunk(int64_t V, int vol, int n_in, int n_out) {
   return ((int64_t)vol * V <= (1ll << 21) && (int64_t)n_in * n_out <= 64 * 64) ? 256 : 1024;
 }
-__host__ __device__ inline int64_t op_hdr(int vol) { return (int64_t)vol + 2 * (vol + 1); }
-__host__ __device__ inline int64_t op_nb256(int64_t V) { return (V + 255) / 256; }
-
 // one block per offset: exclusive scan of the per-256-row hit counts
 __global__ __launch_bounds__(256) void k_offset_bases(const StreamJobs js) {            // common.h: one launch, many books
   __shared__ int ws[4];
@@ -1523,30 +1521,6 @@ __global__ __launch_bounds__(256) void k_fill_offset_pairs(const StreamJobs js) 
 // reduction dimension.  Pair indices are loaded 64 at a time (coalesced) and handed to the lane
 // groups by shuffles; 16 pairs are gathered per step before their MFMAs issue.  The four waves'
 // accumulators are summed through LDS in wave order (deterministic).  CB x NB blocks of 16.
-__device__ inline bool dw_chunk_range(const int32_t *__restrict__ words, int vol, int chunk_pairs, int direct, int chunk,
-                                      int lane, int &k, int &p0, int &p1) {
-  if (direct) {
-    k = chunk;
-    p0 = 0;
-    p1 = words[k];
-    return true;
-  }
-  const int32_t *cstart = words + vol + (chunk_pairs == 256 ? vol + 1 : 0);
-  if (chunk >= cstart[vol]) return false;                  // workgroup-uniform
-  k = 0;
-  for (int k0 = 0; k0 < vol; k0 += 64) {
-    int kk = k0 + lane;
-    bool mine = kk < vol && cstart[kk] <= chunk && chunk < cstart[kk + 1];
-    unsigned long long m = __ballot(mine);
-    if (m) { k = k0 + (__ffsll((long long)m) - 1); break; }
-  }
-  const int rk = words[k];
-  p0 = (chunk - cstart[k]) * chunk_pairs;
-  p1 = p0 + chunk_pairs;
-  if (p1 > rk) p1 = rk;
-  return true;
-}
-
 __device__ inline float ldf(const float *p, int64_t i) { return p[i]; }
 __device__ inline float ldf(const __bf16 *p, int64_t i) { return (float)p[i]; }
 

@@ -262,6 +262,12 @@ static int plan_dispatch(const AabrPlanOp &o, void *st) {
                                            (const int32_t *)p[2], o.i32[4], o.i32[2], (const float *)p[4], o.i32[3],
                                            (const float *)p[5], (const float *)p[3], o.i32[5], (float *)p[6], st);
     break;
+  case AABR_PLAN_CONV_SINGLE:
+    if (bf) { aabr::set_error("aabr_plan_run: the single-rule convolution is fp32 storage only"); rc = AABR_EINVAL; break; }
+    rc = aabr_conv_forward_single((const float *)p[0], o.i32[0], o.i64[0], (float *)p[1], o.i32[1], o.i64[1],
+                                  (const int32_t *)p[2], o.i32[2], (const float *)p[4], o.i32[3], (const float *)p[5],
+                                  (const float *)p[3], st);
+    break;
   case AABR_PLAN_CONV_NARROW:
     if (bf && o.i32[5] == 1) {
       rc = aabr_conv_forward_narrow_bf16_bwd_stats((const uint16_t *)p[0], o.i64[0], (uint16_t *)p[1], o.i64[1],

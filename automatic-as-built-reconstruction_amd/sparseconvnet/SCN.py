@@ -1251,10 +1251,11 @@ def OutputLayer_updateGradInput(metadata, d_input_features, d_output_features):
 # ------------------------------------------------------------------------------------------------
 # the shared gather-GEMM
 # ------------------------------------------------------------------------------------------------
-def _conv_fwd(inp, out, n_rows_out, gather, weight, bias, flags, pack_t=None):
+def _conv_fwd(inp, out, n_rows_out, gather, weight, bias, flags, pack_t=None, single=False):
     """`pack_t` (extension): a list owned by the autograd node.  The forward call (flags bit0 = 0) packs
     the weights in both orientations with one launch and leaves the input-gradient layout in it; the
-    backward call (bit0 = 1) finds it there and runs without a pack launch of its own."""
+    backward call (bit0 = 1) finds it there and runs without a pack launch of its own.
+    `single`: the caller knows that `gather` gives every output row exactly one rule (`single_route` is asked first)."""
     lib = _hip.load()
     if weight.size(1) != 1:
         return _conv_fwd_groups(inp, out, n_rows_out, gather, weight, bias, flags)
@@ -1272,7 +1273,10 @@ def _conv_fwd(inp, out, n_rows_out, gather, weight, bias, flags, pack_t=None):
     if w.dtype != torch.float32:
         raise TypeError("convolution weights are fp32 master parameters, got %s" % w.dtype)
     bf16 = inp.dtype == torch.bfloat16
-    route = conv_route(n_in, n_out, inp.size(0), n_rows_out, gather.vol, bf16)
+    route = single_route(n_in, n_out, inp.size(0), n_rows_out, gather.vol, bf16) if single else None
+    single = route is not None
+    if not single:
+        route = conv_route(n_in, n_out, inp.size(0), n_rows_out, gather.vol, bf16)
     if route.kind == "narrow":
         # 32 -> 32 planes: all offsets' weights in LDS, 16 output rows per wave in registers, straight from the gather
         # table (csrc/conv_narrow.hip) -- no weight pack, no block stream
@@ -1309,13 +1313,18 @@ def _conv_fwd(inp, out, n_rows_out, gather, weight, bias, flags, pack_t=None):
     if not (flags & 4) and n_rows_out > 0:
         pack_stats["own"] += 1                               # this call packs its weights itself
         # (the route above was asked for a packed weight: ahead of the pack, as the narrow kernel takes none)
-        route = conv_route(n_in, n_out, inp.size(0), n_rows_out, gather.vol, bf16, prepacked=False)
+        if not single:
+            route = conv_route(n_in, n_out, inp.size(0), n_rows_out, gather.vol, bf16, prepacked=False)
     T, P = route.tile_rows, route.parts
-    if route.kind in ("wide", "split") and not (flags & 4):      # (fp32 storage: bf16 comes here packed only)
+    if route.kind in ("wide", "split", "single") and not (flags & 4):      # (fp32 storage: bf16 comes here packed only)
         # the LAUNCH's (n_in, n_out): for a transposed launch these are (w.size(3), w.size(2))
         check(lib.aabr_conv_pack_weights(ptr(w), gather.vol, n_in, n_out, flags & 1, ptr(wpack), stream()))
     blocks = ptr(route.stream(gather))
-    if route.kind == "wide":
+    if route.kind == "single":
+        # one rule per output row: register accumulators over the offset-pair list (csrc/conv_single.hip)
+        check(lib.aabr_conv_forward_single(ptr(inp), n_in, inp.size(0), ptr(out), n_out, n_rows_out, blocks, gather.vol,
+                                           ptr(_opt(bias)), flags & 3, ptr(wpack), None, stream()))
+    elif route.kind == "wide":
         # wide layer: big tiles, weights shared per offset (csrc/conv_wide.hip)
         fn = lib.aabr_conv_forward_wide_bf16 if bf16 else lib.aabr_conv_forward_wide
         check(fn(ptr(inp), n_in, inp.size(0), ptr(out), n_out, n_rows_out, blocks, T, gather.vol, ptr(_opt(bias)),
@@ -1443,13 +1452,16 @@ def wide_split(n_in, n_out, rows_in, rows_out, vol, bf16=False):
 
 class ConvRoute(collections.namedtuple("ConvRoute", "kind tile_rows parts bf16")):
     """What `conv_route` decided for one forward-form launch: `kind` None (no output rows), "narrow", "wide", "split"
-    or "tiles"; `tile_rows` T of "wide" / "split" and `parts` P of "split", else 0; `bf16` the feature storage."""
+    or "tiles"; `tile_rows` T of "wide" / "split" and `parts` P of "split", else 0; `bf16` the feature storage.
+    `single_route` returns kind "single" (k_conv_single over the offset pairs) or None."""
     __slots__ = ()
 
     def stream(self, gather):
         """the structure of `gather` the launch reads, built on first use (a launch without rows: the tile blocks)"""
         if self.kind == "narrow":
             return gather.table
+        if self.kind == "single":
+            return gather.pairs()
         if self.kind in ("wide", "split"):
             return gather.blocks_wide(self.tile_rows)
         return gather.blocks()
@@ -1457,7 +1469,7 @@ class ConvRoute(collections.namedtuple("ConvRoute", "kind tile_rows parts bf16")
     @property
     def takes_residual(self):
         """the launch can add a residual in its write-out (the split's second stage, k_split_reduce, adds it)"""
-        return self.kind in ("wide", "split")
+        return self.kind in ("wide", "split", "single")
 
     def stats_parts(self, rows_out):
         """BatchNorm partial sums the launch's write-out can form over its `rows_out` rows -- one per tile of >= 64
@@ -1483,6 +1495,19 @@ def conv_route(n_in, n_out, rows_in, rows_out, vol, bf16, prepacked=True, residu
         return ConvRoute("wide", T, 0, bf16)
     sp = wide_split(n_in, n_out, rows_in, rows_out, vol, bf16) if (prepacked or not bf16) else None
     return ConvRoute("split", sp[0], sp[1], bf16) if sp else ConvRoute("tiles", 0, 0, bf16)
+
+
+def single_route(n_in, n_out, rows_in, rows_out, vol, bf16, stats=False):
+    """Asked BEFORE `conv_route`, and only by callers that know by construction that every output row of the launch's rule
+    book has exactly one rule (a SubmanifoldConvolution of filter volume 1, forward and input gradient; a Deconvolution with
+    filter == stride, forward): ConvRoute("single") when the launch should go to k_conv_single (csrc/conv_single.hip,
+    decided by csrc/conv_single_tiles.h: fp32 storage, no BatchNorm statistics wanted from the write-out -- `stats` --,
+    n_in <= 128, enough rows, knob CONV_SINGLE), else None.  The route takes a packed weight and a residual."""
+    if rows_out == 0:
+        return None
+    if not _hip.load().aabr_conv_single_chunk(n_in, n_out, rows_in, rows_out, vol, 1 if bf16 else 0, 1 if stats else 0):
+        return None
+    return ConvRoute("single", 0, 0, bf16)
 
 
 def _conv_dw(inp, d_out, gather, d_weight, d_bias):
@@ -1512,12 +1537,15 @@ def _conv_dw(inp, d_out, gather, d_weight, d_bias):
         trace.append(("dw", n_in, n_out, gather, inp.size(0), 0, inp.dtype))
 
 
-def compile_streams(gather, rows_in, n_in, n_out, dtype, weight_grad=False):
+def compile_streams(gather, rows_in, n_in, n_out, dtype, weight_grad=False, single=False):
     """Build, ahead of their first use, the block stream the forward-form launch (n_in -> n_out over `gather`) will
-    read (its `conv_route`, for a prepacked weight) -- and, with `weight_grad`, the offset-pair lists of the dW kernel."""
+    read (its `conv_route`, for a prepacked weight) -- and, with `weight_grad`, the offset-pair lists of the dW kernel.
+    `single`: the book gives every output row one rule (see `single_route`, asked first: such a launch reads the pairs)."""
     if gather is None or gather.rows == 0:
         return
-    conv_route(n_in, n_out, rows_in, gather.rows, gather.vol, dtype == torch.bfloat16).stream(gather)
+    bf16 = dtype == torch.bfloat16
+    route = single_route(n_in, n_out, rows_in, gather.rows, gather.vol, bf16) if single else None
+    (route or conv_route(n_in, n_out, rows_in, gather.rows, gather.vol, bf16)).stream(gather)
     if weight_grad:
         gather.pairs()
 
@@ -1533,7 +1561,7 @@ def SubmanifoldConvolution_updateOutput(spatial_size, filter_size, metadata, inp
                                         weight, bias, pack_t=None):
     inp = _featc(input_features, "input_features")
     tb = metadata.getSubmanifoldRuleBook(spatial_size, filter_size)
-    _conv_fwd(inp, output_features, tb.V_out, tb.out, weight, bias, 0, pack_t)
+    _conv_fwd(inp, output_features, tb.V_out, tb.out, weight, bias, 0, pack_t, single=tb.vol == 1)
     return _macs(tb, weight)
 
 
@@ -1543,7 +1571,7 @@ def SubmanifoldConvolution_backward(spatial_size, filter_size, metadata, input_f
     d_out = _featc(d_output_features, "d_output_features")
     tb = metadata.getSubmanifoldRuleBook(spatial_size, filter_size)
     if need_d_input:  # d_in[u] = sum_k d_out[table[k'][u]] @ W[vol-1-k']^T  (flags: transpose | mirrored offset)
-        _conv_fwd(d_out, d_input_features, tb.V_in, tb.out, weight, None, 1 | 2, pack_t)
+        _conv_fwd(d_out, d_input_features, tb.V_in, tb.out, weight, None, 1 | 2, pack_t, single=tb.vol == 1)
     _conv_dw(inp, d_out, tb.out, d_weight, d_bias)
 
 
@@ -1572,7 +1600,9 @@ def Deconvolution_updateOutput(input_size, output_size, filter_size, filter_stri
                                output_features, weight, bias, pack_t=None):
     inp = _featc(input_features, "input_features")
     tb = metadata.getRuleBook(output_size, input_size, filter_size, filter_stride)
-    _conv_fwd(inp, output_features, tb.V_in, tb.inn, weight, bias, 0, pack_t)
+    # filter == stride: every output site has one parent site at one offset
+    _conv_fwd(inp, output_features, tb.V_in, tb.inn, weight, bias, 0, pack_t,
+              single=_key(filter_size) == _key(filter_stride))
     return _macs(tb, weight)
 
 

@@ -297,15 +297,16 @@ class FPN_Net(torch.nn.Module):
 
         def subm(k, fs, ci, co, dtype):
             tb = md.submanifold[key(sizes[k]) + fs]
-            SCN.compile_streams(tb.out, tb.V_in, ci, co, dtype, weight_grad=True)    # forward + dW
-            SCN.compile_streams(tb.out, tb.V_out, co, ci, dtype)                      # input gradient (mirrored)
+            single = fs == one                                   # 1x1x1: one rule per row (SCN.single_route)
+            SCN.compile_streams(tb.out, tb.V_in, ci, co, dtype, weight_grad=True, single=single)    # forward + dW
+            SCN.compile_streams(tb.out, tb.V_out, co, ci, dtype, single=single)       # input gradient (mirrored)
 
-        def strided(tb, ci, co, dtype, transposed):
+        def strided(tb, ci, co, dtype, transposed, single=False):
             if not transposed:     # Convolution: fine -> coarse
                 SCN.compile_streams(tb.out, tb.V_in, ci, co, dtype, weight_grad=True)
                 SCN.compile_streams(tb.inn, tb.V_out, co, ci, dtype)
             else:                  # Deconvolution over the same book: coarse -> fine
-                SCN.compile_streams(tb.inn, tb.V_out, ci, co, dtype, weight_grad=True)
+                SCN.compile_streams(tb.inn, tb.V_out, ci, co, dtype, weight_grad=True, single=single)
                 SCN.compile_streams(tb.out, tb.V_in, co, ci, dtype)
 
         planes = [self.m_shortcuts[k].nIn for k in range(nscale)]
@@ -321,7 +322,7 @@ class FPN_Net(torch.nn.Module):
                 tb = md.rulebooks[key(sizes[k]) + ks + st]
                 strided(tb, planes[k], planes[k + 1], dt, False)  # down-sampling convolution
                 if live(k):
-                    strided(tb, nM, nM, dt, True)                 # up-sampling deconvolution of the same book
+                    strided(tb, nM, nM, dt, True, single=ks == st)   # up-sampling deconvolution of the same book
             if k < nscale - 1 and live(k):
                 subm(k, three, nM, nM, dt)                        # merged 3x3x3 on the up path
         for i, scale_from_top in enumerate(self.fpn_scales_from_top):

@@ -40,7 +40,7 @@ from .deconvolution import Deconvolution
 
 _OP = struct.Struct("<ii6i4f4q12Q")          # AabrPlanOp (include/aabr_hip.h)
 assert _OP.size == 176
-K_CONV, K_WIDE, K_DW, K_BNF, K_BNB, K_ADD, K_CAST, K_WSPLIT, K_NARROW = 1, 2, 3, 4, 5, 6, 7, 9, 10
+K_CONV, K_WIDE, K_DW, K_BNF, K_BNB, K_ADD, K_CAST, K_WSPLIT, K_NARROW, K_SINGLE = 1, 2, 3, 4, 5, 6, 7, 9, 10, 11
 F_BF16, F_TO_BF16, F_SIDE, F_JOIN = 1, 2, 4, 8
 _ALIGN = 256
 BF16 = torch.bfloat16
@@ -93,6 +93,8 @@ pipeline_records = int(os.environ.get("AABR_PLAN_PIPELINE", "0"))
 # tests: a list here receives every _Pass that runs (its arena holds every activation of the pass --
 # `_Pass.bn_outputs()`); None in production
 debug_passes = None
+# tests: a list here receives ("fwd" | "bwd", [record kinds]) of every launch list a pass builds; None in production
+debug_kinds = None
 # a pass that will not be differentiated packs its activations by liveness (AABR_PLAN_PACK_ARENA=0: one slot each, as
 # the training pass needs them)
 pack_inference_arena = os.environ.get("AABR_PLAN_PACK_ARENA", "1") != "0"
@@ -143,7 +145,26 @@ class _Template(object):
         # that buffer's producer, on the second stream; its first reader joins
         self.emit = self._emission()
         self.fuse = self._fusable_adds() if (fuse_adds and not lateral_side_stream) else {}
+        self.stat_claims = self._stat_claims()
         stats["templates"] += 1
+
+    def _stat_claims(self):
+        """ids of the convolution ops whose write-out a training-mode BatchNorm may ask for its statistics (`_Pass._forward`):
+        the next record on the convolution's stream -- its own fused add aside -- is that BatchNorm, reading what the
+        launch writes"""
+        out = set()
+        for i, (op, xf) in enumerate(self.emit):
+            if op[0] != "conv":
+                continue
+            fz = self.fuse.get(id(op))
+            wrote = (op[2],) if fz is None else (op[2], fz[0][3])
+            for nop, nxf in self.emit[i + 1:]:
+                if (nxf ^ xf) & F_SIDE or (fz is not None and nop is fz[0]):
+                    continue
+                if nop[0] == "bn" and nop[6] and nop[4] == op[6] and nop[1] in wrote:
+                    out.add(id(op))
+                break
+        return out
 
     def _fusable_adds(self):
         """{id(conv op): (add op, other operand)}: a convolution whose only reader is an add with an operand that
@@ -415,7 +436,7 @@ class _Template(object):
                     tmp = gnew(lvl, n_in, dt) if res is not None else None   # used when the launch is not a wide one
                     # the launch reads d_out (n_out planes) and writes d_in (n_in planes)
                     ops.append(("din", gy, gx, lo, lvl, n_out, n_in, book, side_din, din_flags, p_w, pt, flg, res,
-                                tmp))
+                                tmp, _one_rule(m, True)))
                     if res is not None:
                         acc[x] = gx
                     else:
@@ -424,6 +445,16 @@ class _Template(object):
                     ops.append(("dw", x, gy, lo, n_in, n_out, book, side_dw, pslot(m.weight), flg))
         gx0 = total(0) if need_dx else None
         return {"gbufs": gbufs, "ops": ops, "poff": poff, "ptotal": ptotal, "gx0": gx0}
+
+
+def _one_rule(m, din):
+    """True when the rule book of this module's forward (`din` False) or input-gradient launch gives every output row
+    exactly one rule, by construction: what entitles the caller to ask `SCN.single_route`"""
+    if isinstance(m, SubmanifoldConvolution):
+        return m.filter_volume == 1
+    if isinstance(m, Deconvolution) and not din:
+        return SCN._key(m.filter_size) == SCN._key(m.filter_stride)
+    return False
 
 
 def _out_of(op):
@@ -458,7 +489,27 @@ class _Pass(object):
             bk.append((tb.out, tb.inn if tb.inn is not None else tb.out, tb))
         self.books = bk
         self.route = functools.lru_cache(maxsize=None)(SCN.conv_route)   # {launch shape: its ConvRoute} of the pass
+        self.single = functools.lru_cache(maxsize=None)(SCN.single_route)
         self._tmp = []
+
+    def fwd_route(self, op):
+        """(route, fused add or None) of a forward convolution record: `SCN.single_route` first where the module's rule
+        book has one rule per output row, then `SCN.conv_route`; the add behind the convolution rides in the write-out
+        when the route takes a residual"""
+        x, y, lvl, lo, n_in, n_out, book, side = op[1:9]
+        t, V = self.t, self.V
+        fz = t.fuse.get(id(op))
+        g, bfx = self.books[book][side], t.fbufs[x][2] == BF16
+        r = None
+        if _one_rule(op[15], False):
+            r = self.single(n_in, n_out, V[lvl], V[lo], g.vol, bfx, conv_bn_stats and id(op) in t.stat_claims)
+        if r is None and fz is not None:
+            r = self.route(n_in, n_out, V[lvl], V[lo], g.vol, bfx, residual=True)
+        if fz is not None and r.takes_residual:
+            return r, fz
+        if r is None or r.kind != "single":
+            r = self.route(n_in, n_out, V[lvl], V[lo], g.vol, bfx)
+        return r, None
 
     def conv_launch(self, route, pack, buf, off, src, rows_in, n_in, dst, rows_out, n_out, gather, p_w, p_pack, flags,
                     xf=0, res=0):
@@ -473,6 +524,9 @@ class _Pass(object):
         if route.kind == "narrow":        # from the gather table, raw weights
             pack(buf, off, K_NARROW, xf, n_in, n_out, gather.vol, flags & 3, 0, 0, 0.0, 0.0, 0.0, 0.0, rows_in, rows_out,
                  0, 0, src, dst, blocks, p_w, 0, 0, 0, 0, 0, 0, 0, 0)
+        elif route.kind == "single":      # one rule per output row: from the offset pairs, residual in the write-out
+            pack(buf, off, K_SINGLE, xf, n_in, n_out, gather.vol, flags & 3, 0, 0, 0.0, 0.0, 0.0, 0.0, rows_in, rows_out,
+                 0, 0, src, dst, blocks, res, 0, p_pack, 0, 0, 0, 0, 0, 0)
         elif route.kind == "wide":
             pack(buf, off, K_WIDE, xf, n_in, n_out, gather.vol, flags & 3, route.tile_rows, 0, 0.0, 0.0, 0.0, 0.0,
                  rows_in, rows_out, 0, 0, src, dst, blocks, res, 0, p_pack, 0, 0, 0, 0, 0, 0)
@@ -501,10 +555,9 @@ class _Pass(object):
                 return None
             kind = op[0]
             if kind == "conv":
-                x, y, lvl, lo, n_in, n_out, book, side = op[1:9]
-                fz = fuse.get(id(op))
-                if fz is not None and self.route(n_in, n_out, V[lvl], V[lo], books[book][side].vol, fbufs[x][2] == BF16,
-                                                 residual=True).takes_residual:
+                x, y = op[1:3]
+                fz = self.fwd_route(op)[1]
+                if fz is not None:
                     add_op, other = fz
                     skip.add(id(add_op))
                     steps.append(((x, other), add_op[3]))
@@ -604,15 +657,12 @@ class _Pass(object):
             sk = xf & F_SIDE
             if kind == "conv":
                 x, y, lvl, lo, n_in, n_out, book, side, p_w, pf = op[1:11]
-                fz = fuse.get(id(op))
-                g, bfx, off0 = books[book][side], fbufs[x][2] == BF16, off
-                r = self.route(n_in, n_out, V[lvl], V[lo], g.vol, bfx, residual=True) if fz is not None else None
-                if r is not None and r.takes_residual:
+                g, off0, res = books[book][side], off, 0
+                r, fz = self.fwd_route(op)
+                if fz is not None:
                     add_op, other = fz           # out = conv + other, written where the add would have written
                     skip.add(id(add_op))
                     y, res = add_op[3], A[other]
-                else:
-                    r, res = self.route(n_in, n_out, V[lvl], V[lo], g.vol, bfx), 0
                 off, nparts = self.conv_launch(r, pack, buf, off, A[x], V[lvl], n_in, A[y], V[lo], n_out, g, p_w, pf, 0,
                                                xf, res)
                 last[sk] = (y, off0, nparts, n_out) if nparts else None
@@ -645,6 +695,8 @@ class _Pass(object):
                      A[x], A[y], 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
                 off += 176
             last[sk] = None
+        if debug_kinds is not None:
+            debug_kinds.append(("fwd", [struct.unpack_from("<i", buf, o)[0] for o in range(0, off, 176)]))
         if part:
             check(self.lib.aabr_plan_submit(bytes(buf[start:off]), (off - start) // 176, strm, 0))
             check(self.lib.aabr_plan_drain())      # everything issued: the caller's next launches queue behind the pass
@@ -719,6 +771,14 @@ class _Pass(object):
         cut = [(len(bops) * (q + 1)) // nseg for q in range(nseg)] if nseg > 1 else []
         inv = sorted((o, i) for i, o in bw["poff"].items()) if nseg > 1 else []
         done_floats, seg_no, next_inv = 0, 0, 0
+        claimed = bw.get("claimed")
+        if claimed is None:              # input-gradient records whose write-out a BatchNorm backward record may ask for
+            claimed = bw["claimed"] = set()   # its statistics: the next record, weight gradients aside, reads their d_in
+            for i, op in enumerate(bops):
+                if op[0] == "din":
+                    nxt = next((o for o in bops[i + 1:] if o[0] != "dw"), None)
+                    if nxt is not None and nxt[0] == "bn" and nxt[4] == op[2] and nxt[6] == op[6]:
+                        claimed.add(i)
         last_din, bstat = None, None     # the last wide input-gradient record of the main stream / statistics workspace
         part, start, strm = (pipeline_records * 176 if nseg == 1 else 0), 0, stream()
         for op_no, op in enumerate(bops):
@@ -749,10 +809,14 @@ class _Pass(object):
                     if po >= 0:
                         done_floats = max(done_floats, po // 4 + (t.params[self._pinv(bw, po)].numel() + 63) // 64 * 64)
             if kind == "din":
-                _, gy, gx, lo, lvl, n_in, n_out, book, side, flags, p_w, pt, flg, res, tmp = op
+                _, gy, gx, lo, lvl, n_in, n_out, book, side, flags, p_w, pt, flg, res, tmp, one_rule = op
                 g = books[book][side]
                 last_din, bf = None, flg == F_BF16
-                r = self.route(n_in, n_out, V[lo], V[lvl], g.vol, bf, residual=res is not None)
+                r = None
+                if one_rule:     # (statistics: a BatchNorm backward record may claim this launch's write-out)
+                    r = self.single(n_in, n_out, V[lo], V[lvl], g.vol, bf, conv_bn_bwd_stats and op_no in claimed)
+                if r is None:
+                    r = self.route(n_in, n_out, V[lo], V[lvl], g.vol, bf, residual=res is not None)
                 if res is None or r.takes_residual:
                     off0 = off
                     off, nparts = self.conv_launch(r, pack, buf, off, AD[gy[0]][gy[1]], V[lo], n_in, AD[gx[0]][gx[1]],
@@ -809,6 +873,8 @@ class _Pass(object):
                 pack(buf, off, K_CAST, flg, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, V[lvl] * planes, 0, 0, 0,
                      AD[gy[0]][gy[1]], AD[gx[0]][gx[1]], 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
                 off += 176
+        if debug_kinds is not None:      # (with grad_segments > 1: the last piece only)
+            debug_kinds.append(("bwd", [struct.unpack_from("<i", buf, o)[0] for o in range(0, off, 176)]))
         if part:
             check(self.lib.aabr_plan_submit(bytes(buf[start:off]), (off - start) // 176, strm, 0))
             check(self.lib.aabr_plan_drain())

@@ -321,6 +321,25 @@ int aabr_conv_forward_wide_stats(const float *in_feats, int n_in, int64_t rows_i
 int aabr_conv_forward_wide_bf16_stats(const uint16_t *in_feats, int n_in, int64_t rows_in, uint16_t *out_feats,
                                       int n_out, int64_t V_out, const int32_t *blocks, int tile_rows, int vol,
                                       const float *bias, int flags, const uint16_t *wpack, double *stats, void *stream);
+/* Single-rule form (csrc/conv_single.hip, fp32 storage): the same contraction for rule books in which EVERY OUTPUT ROW
+ * HAS EXACTLY ONE RULE -- out[o] = in[i(o)] @ Wl[k(o)] (+ bias, + residual) -- as in the reference's Deconvolution with
+ * filter == stride (SCN/CPU/Deconvolution.cpp:7-77) and its 1x1x1 SubmanifoldConvolution, forward and input gradient.
+ * THE CALLER GUARANTEES that property: the library cannot see it; a row named by several rules would hold one of their
+ * terms, a row named by none is not written.  Reads the offset pairs of aabr_build_offset_pairs (built over the
+ * launch's gather table [vol][V_out]) instead of tile blocks; `wpack` as aabr_conv_forward_wide (the orientation of the
+ * launch: the input-gradient form hands over the transposed pack and the same pairs); flags bit1: mirrored offsets.
+ * n_in % 32 == 0, n_in <= 128, n_out % 64 == 0.  No fp32 output tile, no weight reload per tile: one MFMA chain per
+ * output element in the K order of aabr_conv_forward_wide, then + bias, + residual -- the result equals
+ * aabr_conv_forward_wide_res's bit for bit.
+ *   aabr_conv_single_chunk: pairs per chunk (256 / 1024) when such a launch should take this form, else 0 (bf16 storage,
+ *     statistics wanted in the write-out, an unsupported shape, too few rows, knob CONV_SINGLE = 0);
+ *   aabr_conv_single_refusal: why it returned 0 ("" when it did not).                                              */
+int aabr_conv_single_chunk(int n_in, int n_out, int64_t rows_in, int64_t V_out, int vol, int bf16, int has_stats);
+const char *aabr_conv_single_refusal(int n_in, int n_out, int64_t rows_in, int64_t V_out, int vol, int bf16,
+                                     int has_stats);
+int aabr_conv_forward_single(const float *in_feats, int n_in, int64_t rows_in, float *out_feats, int n_out,
+                             int64_t V_out, const int32_t *pairs, int vol, const float *bias, int flags,
+                             const float *wpack, const float *residual, void *stream);
 /* Input-gradient form of the same launch (flags = transposed | mirrored, as aabr_conv_forward_wide): its output is the
  * d_out of the BatchNormalization(+leaky ReLU) whose result the convolution consumed; the write-out forms THAT
  * BatchNorm's backward statistics (replaces the first loop of BatchNormalization_BackwardPass,
@@ -610,6 +629,9 @@ int aabr_conv_forward_narrow_bf16_bwd_stats(const uint16_t *in_feats, int64_t ro
                                    i32[2] vol, p3 W, p4 bias, i32[3] flags); bf16 storage with p6 != NULL: .._bf16_stats(.., p6
                                    stats); i32[5] == 1: .._bf16_bwd_stats(.., p6 stats, p7 bn_in, p9 bn_out, p8 save_mean,
                                    f32[0] leakiness) */
+#define AABR_PLAN_CONV_SINGLE 11 /* aabr_conv_forward_single(p0 in, i32[0] n_in, i64[0] rows_in, p1 out, i32[1] n_out,
+                                   i64[1] V_out, p2 pairs, i32[2] vol, p4 bias, i32[3] flags, p5 wpack, p3 residual);
+                                   fp32 storage only; the caller guarantees one rule per output row */
 #define AABR_PLAN_BF16 1
 #define AABR_PLAN_TO_BF16 2
 #define AABR_PLAN_JOIN 8 /* the caller's stream waits for the second stream in front of this record */
