@@ -97,6 +97,11 @@ _SIGS = {
     "aabr_conv_single_chunk": (C.c_int, [_i32, _i32, _i64, _i64, _i32, _i32, _i32]),
     "aabr_conv_single_refusal": (C.c_char_p, [_i32, _i32, _i64, _i64, _i32, _i32, _i32]),
     "aabr_conv_forward_single": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "aabr_conv_single_bwd_stats_chunk": (C.c_int, [_i32, _i32, _i64, _i64, _i32, _i32]),
+    "aabr_conv_single_bwd_stats_refusal": (C.c_char_p, [_i32, _i32, _i64, _i64, _i32, _i32]),
+    "aabr_conv_single_bwd_stats_parts": (_i64, [_i64, _i32, _i32]),
+    "aabr_conv_forward_single_bwd_stats": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _vp,
+                                                     _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp]),
     "aabr_conv_wide_tile_rows_bf16": (C.c_int, [_i32, _i32, _i64, _i64, _i32]),
     "aabr_conv_forward_wide_bf16": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp]),
     "aabr_conv_forward_wide_res": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i32, _vp, _i32, _vp, _vp,

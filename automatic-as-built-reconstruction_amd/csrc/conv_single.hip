@@ -20,6 +20,17 @@
 // for such a book (its tile's 0 + x is exact).  Every output row is written by exactly one lane group: no atomics.
 // THE CALLER GUARANTEES the one-rule property; a row named by two pairs would hold whichever was written last, a row
 // named by none is not written.
+//
+//   k_conv_single<KG, true> -- the input-gradient launch of a convolution with filter == stride (every fine row has one
+//   parent), whose output is the d_out of the BatchNorm(+leaky ReLU) in front of that convolution: the write-out also
+//   forms that BatchNorm's BACKWARD statistics, with exactly the terms of k_conv_cs' write-out (conv_wide.hip, `bn.x`):
+//   d = the stored value masked by the sign of the activation recomputed from the BatchNorm's input x, fp64 sums of d and
+//   (x - mean) * d.  The x rows are requested with the residual rows, ahead of the gathers; a lane keeps the eight sums of
+//   its four columns in registers over the chunk's steps (padding pairs add nothing), and after the last step the
+//   workgroup combines them through LDS (the stage is free by then) in lane order into ONE part [2][64 columns] per
+//   (chunk, slab): stats[(chunk * 2 + s) * n_out + column].  A workgroup without pairs writes zeros, so the BatchNorm
+//   backward sums all gridDim.x parts in part order (aabr_bn_backward_parts) and the result does not depend on which
+//   workgroup ran when: no atomics.  `out` is what k_conv_single<KG> writes, bit for bit.
 #include "common.h"
 #include "conv_single_tiles.h"
 #include "offset_pairs.h"
@@ -33,12 +44,21 @@ extern thread_local const char *g_last_variant; // conv.hip
 
 __device__ inline float bcs_(unsigned int v) { return __builtin_bit_cast(float, v); }
 
-template <int KG>
-__global__ __launch_bounds__(256, 2) void k_conv_single(const float *__restrict__ in, int ci, int64_t in_bytes,
+// BS instances: the BatchNorm whose backward statistics the write-out forms (x its input, the saved statistics, its affine
+// coefficients or nullptr) and the parts buffer [gridDim.x][2][co]; all nullptr for the plain instances
+struct SingleBwdStats {
+  double *stats;
+  const float *x, *mean, *invstd, *weight, *bias;
+  float leak;
+};
+
+template <int KG, bool BS = false>
+__global__ __launch_bounds__(256, (BS && KG == 4) ? 3 : 2) void k_conv_single(const float *__restrict__ in, int ci, int64_t in_bytes,
                                                         float *__restrict__ out, int co, int64_t V_out,
                                                         const int32_t *__restrict__ words, int vol, int chunk_pairs,
                                                         int wflip, const float *__restrict__ Wp, int64_t wp_bytes,
-                                                        const float *__restrict__ bias, const float *__restrict__ res) {
+                                                        const float *__restrict__ bias, const float *__restrict__ res,
+                                                        SingleBwdStats bn) {
   constexpr int NW = 4;                    // waves per workgroup
   constexpr int LPR = 8;                   // lanes per gathered pair row: 256 threads, 32 rows
   constexpr int RF = KG * 32;              // floats per staged row
@@ -62,8 +82,13 @@ __global__ __launch_bounds__(256, 2) void k_conv_single(const float *__restrict_
     nb0 = (int)(wi % ny) * NW;
   }
   int k, p0, p1;
-  if (!dw_chunk_range(words, vol, chunk_pairs, 0, chunk, lane, k, p0, p1)) return;   // surplus workgroup
-  if (p0 >= p1) return;                                                              // (workgroup-uniform)
+  bool work = dw_chunk_range(words, vol, chunk_pairs, 0, chunk, lane, k, p0, p1);    // false: surplus workgroup
+  work = work && p0 < p1;                                                            // (workgroup-uniform)
+  if (!work) {
+    if (BS && threadIdx.x < 128)           // its part of the statistics: zeros
+      bn.stats[((int64_t)chunk * 2 + (threadIdx.x >> 6)) * co + nb0 * 16 + (threadIdx.x & 63)] = 0.0;
+    return;
+  }
   const int last = words[k] - 1;           // >= p0: clamps the entry loads of the padded tail and of the steps past the end
   // the offset's (partner row, row) pairs, read word by word (the list is 4-byte aligned)
   const int32_t *__restrict__ pairs = words + op_hdr(vol) + (int64_t)vol * op_nb256(V_out) + 2 * (int64_t)k * V_out;
@@ -108,6 +133,18 @@ __global__ __launch_bounds__(256, 2) void k_conv_single(const float *__restrict_
   const int colo = (nb0 + wave) * 16 + g * 4;        // this lane's four output columns
   f32x4 bv = {0.f, 0.f, 0.f, 0.f};
   if (bias) bv = *reinterpret_cast<const f32x4 *>(bias + colo);
+  // BS: the BatchNorm's forward coefficients of this lane's four columns (k_conv_cs' write-out forms them the same way) and
+  // the lane's sums over the chunk
+  float bmu[4] = {0.f, 0.f, 0.f, 0.f}, bwc[4] = {0.f, 0.f, 0.f, 0.f}, bbc[4] = {0.f, 0.f, 0.f, 0.f};
+  double sd[4] = {0.0, 0.0, 0.0, 0.0}, sxd[4] = {0.0, 0.0, 0.0, 0.0};   // sums of d, of (x - mean) * d
+  if (BS) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      bmu[j] = bn.mean[colo + j];
+      bwc[j] = bn.invstd[colo + j] * (bn.weight ? bn.weight[colo + j] : 1.0f);
+      bbc[j] = -bmu[j] * bwc[j] + (bn.bias ? bn.bias[colo + j] : 0.0f);
+    }
+  }
 
   const int nsteps = (p1 - p0 + kSingleStepPairs - 1) / kSingleStepPairs;
   // Software pipeline over the chunk's steps: entries three steps ahead (registers), gathered rows two steps ahead
@@ -145,6 +182,11 @@ __global__ __launch_bounds__(256, 2) void k_conv_single(const float *__restrict_
     if (res) {                             // (kernel-uniform)
       ra = *reinterpret_cast<const f32x4 *>(res + ia);
       rb = *reinterpret_cast<const f32x4 *>(res + ib);
+    }
+    f32x4 xa = {0.f, 0.f, 0.f, 0.f}, xb = xa;   // BS: the BatchNorm's input at the same (row, columns), requested with them
+    if (BS) {
+      xa = *reinterpret_cast<const f32x4 *>(bn.x + ia);
+      xb = *reinterpret_cast<const f32x4 *>(bn.x + ib);
     }
     // entries before the gather: loads return in order, and the next step's wait for these entries (its gather's
     // addresses) must not cover the rows requested here
@@ -190,6 +232,19 @@ __global__ __launch_bounds__(256, 2) void k_conv_single(const float *__restrict_
     if (res) { accA += ra; accB += rb; }
     if (!pa) *reinterpret_cast<f32x4 *>(out + ia) = accA;
     if (!pb) *reinterpret_cast<f32x4 *>(out + ib) = accB;
+    if (BS) {                              // the terms of k_conv_cs' write-out, from the values just stored
+      auto add = [&](const f32x4 &v, const f32x4 &xv) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float o = xv[j] * bwc[j] + bbc[j];
+          const float d = (o > 0.0f) ? v[j] : v[j] * bn.leak;
+          sd[j] += (double)d;
+          sxd[j] += (double)(xv[j] - bmu[j]) * (double)d;
+        }
+      };
+      if (!pa) add(accA, xa);
+      if (!pb) add(accB, xb);
+    }
     stage_store(g_store, par ^ 1);         // the next step's rows, gathered a step ago
     wg_barrier();
     par ^= 1;
@@ -210,6 +265,26 @@ __global__ __launch_bounds__(256, 2) void k_conv_single(const float *__restrict_
     if (s < nsteps) {
       step(eb, ed, ea, gq1, gq0);
       if (s < nsteps) step(ec, ea, eb, gq0, gq1);
+    }
+  }
+  if (BS) {
+    // The last step's barrier is behind every wave: nobody reads the stage any more, and it holds the sums now, [8][256]
+    // doubles.  Column c of the slab belongs to wave c / 16, lane group (c / 4) % 4, register c % 4; its 16 lanes hold
+    // the chunk's rows: added in lane order by one thread per column and sum.
+    double *red = reinterpret_cast<double *>(St);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      red[j * 256 + threadIdx.x] = sd[j];
+      red[(4 + j) * 256 + threadIdx.x] = sxd[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < 128) {
+      const int which = threadIdx.x >> 6, c = threadIdx.x & 63;
+      const double *col = red + (which * 4 + (c & 3)) * 256 + (c >> 4) * 64 + ((c >> 2) & 3) * 16;
+      double a = 0.0;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) a += col[r];
+      bn.stats[((int64_t)chunk * 2 + which) * co + nb0 * 16 + c] = a;
     }
   }
 }
@@ -233,11 +308,33 @@ extern "C" const char *aabr_conv_single_refusal(int n_in, int n_out, int64_t row
   return m ? m : "";
 }
 
+// the same for the input-gradient launch that owes a BatchNorm its backward statistics (aabr_conv_forward_single_bwd_stats)
+extern "C" int aabr_conv_single_bwd_stats_chunk(int n_in, int n_out, int64_t rows_in, int64_t V_out, int vol, int bf16) {
+  const SingleKnobs kn = single_knobs();
+  if (single_bwd_stats_refusal(bf16 != 0, n_in, n_out, rows_in, V_out, vol, kn, knob(K_SINGLE_BWD_STATS))) return 0;
+  return single_chunk_pairs(kn);
+}
+extern "C" const char *aabr_conv_single_bwd_stats_refusal(int n_in, int n_out, int64_t rows_in, int64_t V_out, int vol,
+                                                          int bf16) {
+  const char *m = single_bwd_stats_refusal(bf16 != 0, n_in, n_out, rows_in, V_out, vol, single_knobs(),
+                                           knob(K_SINGLE_BWD_STATS));
+  return m ? m : "";
+}
+// parts [2][n_out] of fp64 sums that launch writes, for the chunk length the query above returned
+extern "C" int64_t aabr_conv_single_bwd_stats_parts(int64_t V_out, int vol, int chunk_pairs) {
+  if (V_out <= 0 || vol <= 0 || (chunk_pairs != 256 && chunk_pairs != 1024)) return 0;
+  return single_chunk_bound(V_out, vol, chunk_pairs);
+}
+
 // ---- the launch ---------------------------------------------------------------------------------------------------------
-typedef decltype(&k_conv_single<1>) SingleFn;
+typedef decltype(&k_conv_single<1>) SingleFn;      // every instantiation has this type
 struct SingleInst { const char *name; SingleFn fn; };
 static const SingleInst kSingle[4] = {{"k_conv_single<1>", k_conv_single<1>}, {"k_conv_single<2>", k_conv_single<2>},
                                       {"k_conv_single<3>", k_conv_single<3>}, {"k_conv_single<4>", k_conv_single<4>}};
+static const SingleInst kSingleBwdStats[4] = {{"k_conv_single<1,bwd_stats>", k_conv_single<1, true>},
+                                              {"k_conv_single<2,bwd_stats>", k_conv_single<2, true>},
+                                              {"k_conv_single<3,bwd_stats>", k_conv_single<3, true>},
+                                              {"k_conv_single<4,bwd_stats>", k_conv_single<4, true>}};
 
 extern "C" int aabr_conv_forward_single(const float *in_feats, int n_in, int64_t rows_in, float *out_feats, int n_out,
                                         int64_t V_out, const int32_t *pairs, int vol, const float *bias, int flags,
@@ -253,7 +350,36 @@ extern "C" int aabr_conv_forward_single(const float *in_feats, int n_in, int64_t
   g_last_variant = e.name;
   hipLaunchKernelGGL(e.fn, dim3((unsigned)t.grid_x, (unsigned)t.grid_y), dim3(256), (size_t)t.lds_bytes,
                      (hipStream_t)stream_, in_feats, n_in, t.in_bytes, out_feats, n_out, V_out, pairs, vol, t.chunk_pairs,
-                     t.wflip, wpack, t.wp_bytes, bias, residual);
+                     t.wflip, wpack, t.wp_bytes, bias, residual, SingleBwdStats{});
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+// The input-gradient form whose write-out forms the backward statistics of the BatchNorm whose d_out it writes: `stats`
+// takes single_bwd_stats_launch's parts x [2][n_out] doubles; the BatchNorm arguments as aabr_conv_forward_wide_bwd_stats.
+extern "C" int aabr_conv_forward_single_bwd_stats(const float *in_feats, int n_in, int64_t rows_in, float *out_feats,
+                                                  int n_out, int64_t V_out, const int32_t *pairs, int vol,
+                                                  const float *bias, int flags, const float *wpack, const float *residual,
+                                                  double *stats, const float *bn_in, const float *save_mean,
+                                                  const float *save_invstd, const float *bn_weight, const float *bn_bias,
+                                                  float leakiness, void *stream_) {
+  SingleBwdStatsLaunch t;
+  const char *refused = single_bwd_stats_launch(n_in, n_out, rows_in, V_out, vol, flags, single_knobs(), t);
+  AABR_CHECK_ARG(!refused, refused);
+  if (V_out == 0) return AABR_OK;
+  AABR_CHECK_ARG(in_feats && out_feats && pairs && wpack, "null pointer / empty input");
+  AABR_CHECK_ARG(stats && bn_in && save_mean && save_invstd, "null pointer");
+  AABR_CHECK_ARG(leakiness >= 0.0f, "the activation sign is recomputed from the BatchNorm input: leakiness >= 0");
+  AABR_CHECK_ARG((((uintptr_t)in_feats | (uintptr_t)out_feats | (uintptr_t)wpack | (uintptr_t)residual |
+                   (uintptr_t)bias | (uintptr_t)bn_in) & 15) == 0,
+                 "feature / weight / residual / bias / BatchNorm input pointers must be 16-byte aligned");
+  AABR_CHECK_ARG(((uintptr_t)stats & 7) == 0, "the statistics must be 8-byte aligned");
+  const SingleInst &e = kSingleBwdStats[t.l.kg - 1];
+  g_last_variant = e.name;
+  hipLaunchKernelGGL(e.fn, dim3((unsigned)t.l.grid_x, (unsigned)t.l.grid_y), dim3(256), (size_t)t.l.lds_bytes,
+                     (hipStream_t)stream_, in_feats, n_in, t.l.in_bytes, out_feats, n_out, V_out, pairs, vol,
+                     t.l.chunk_pairs, t.l.wflip, wpack, t.l.wp_bytes, bias, residual,
+                     SingleBwdStats{stats, bn_in, save_mean, save_invstd, bn_weight, bn_bias, leakiness});
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }

@@ -2,7 +2,13 @@
 // k_conv_single (conv_single.hip only carries it out), and what that kernel is launched with: shape conditions, the least
 // number of output rows, pairs per chunk, grid, LDS bytes.  Free of HIP headers: tests/conv_single_host_harness.cpp compiles
 // it with g++ and pins the decision.  The one-rule property itself is the CALLER's knowledge (a 1x1x1 submanifold
-// convolution, a deconvolution with filter == stride): nothing here can see it.
+// convolution, a deconvolution with filter == stride, the input gradient of a convolution with filter == stride): nothing
+// here can see it.
+// Two decisions: `single_refusal` / `single_launch` for the plain launch (k_conv_single<KG>), whose `has_stats` means
+// FORWARD statistics -- the following BatchNorm's sums of the stored values, which the kernel does not form -- and, since
+// that flag cannot tell the two apart, is also what a caller without the backward form passes for backward ones; and
+// `single_bwd_stats_refusal` / `single_bwd_stats_launch` for the input-gradient launch whose write-out forms the BACKWARD
+// statistics of the BatchNorm whose d_out it writes (k_conv_single<KG, true>: one fp64 part per chunk).
 #pragma once
 #include <stdint.h>
 #include "conv_tiles.h"   // ceil_div, kKnobUnset
@@ -24,7 +30,8 @@ struct SingleKnobs {
 };
 constexpr bool kSingleDefaultOn = true;   // what an unset CONV_SINGLE means
 
-// The shapes the kernel serves, or the first condition violated.  fp32 storage, no statistics in the write-out.
+// The shapes the kernel serves, or the first condition violated.  fp32 storage; `has_stats`: forward statistics wanted in
+// the write-out (see above; the backward form has its own decision below).
 inline const char *single_unsupported(bool bf16, bool has_stats, int n_in, int n_out, int64_t rows_in, int64_t rows_out,
                                       int vol) {
   if (bf16) return "fp32 storage only (bf16 rows stay on their kernels)";
@@ -86,6 +93,38 @@ inline const char *single_launch(int n_in, int n_out, int64_t rows_in, int64_t r
   t.in_bytes = rows_in * n_in * 4;
   t.wp_bytes = (int64_t)vol * (n_in / 32) * (n_out / 16) * 2048;
   out = t;
+  return nullptr;
+}
+
+// ---- the backward-statistics form -------------------------------------------------------------------------------------
+// knob SINGLE_BWD_STATS (0: off, 1: on, unset: the shipped default); everything else -- CONV_SINGLE, the row threshold,
+// the chunk length -- is the plain route's.  On: with the route the fp32 training step took 12.085 - 12.125 ms against
+// 12.216 - 12.240 without, four runs each, interleaved on one GPU (profiles/conv_single_bwd_stats_bench_lines.txt).
+constexpr bool kSingleBwdStatsDefaultOn = true;
+
+// nullptr = the input-gradient launch that owes a BatchNorm its backward statistics goes to k_conv_single<KG, true>, else
+// why not: every condition of the plain route but the statistics one.
+inline const char *single_bwd_stats_refusal(bool bf16, int n_in, int n_out, int64_t rows_in, int64_t rows_out, int vol,
+                                            const SingleKnobs &kn, int bwd_stats_knob) {
+  if (bwd_stats_knob == 0 || (bwd_stats_knob == kKnobUnset && !kSingleBwdStatsDefaultOn)) return "SINGLE_BWD_STATS is off";
+  return single_refusal(bf16, false, n_in, n_out, rows_in, rows_out, vol, kn);
+}
+
+struct SingleBwdStatsLaunch {
+  SingleLaunch l;         // grid, chunk length, weight orientation as the plain launch; lds_bytes also holds the sums
+  int64_t parts;          // fp64 parts [2][n_out] the launch writes = grid_x: one per chunk, surplus chunks write zeros
+  int64_t stats_doubles;  // parts x 2 x n_out
+};
+constexpr int64_t kSingleReduceBytes = 256 * 8 * 8;   // a workgroup's 256 x 8 fp64 sums, combined through LDS after the last step
+
+inline const char *single_bwd_stats_launch(int n_in, int n_out, int64_t rows_in, int64_t rows_out, int vol, int flags,
+                                           const SingleKnobs &kn, SingleBwdStatsLaunch &out) {
+  out = SingleBwdStatsLaunch{};
+  if (const char *m = single_launch(n_in, n_out, rows_in, rows_out, vol, flags, kn, out.l)) return m;
+  if (rows_out == 0) return nullptr;
+  if (out.l.lds_bytes < kSingleReduceBytes) out.l.lds_bytes = kSingleReduceBytes;
+  out.parts = single_chunk_bound(rows_out, vol, out.l.chunk_pairs);
+  out.stats_doubles = out.parts * 2 * n_out;
   return nullptr;
 }
 

@@ -264,6 +264,14 @@ static int plan_dispatch(const AabrPlanOp &o, void *st) {
     break;
   case AABR_PLAN_CONV_SINGLE:
     if (bf) { aabr::set_error("aabr_plan_run: the single-rule convolution is fp32 storage only"); rc = AABR_EINVAL; break; }
+    if (o.i32[5] == 1) { // the write-out forms the backward statistics of the BatchNorm whose d_out it produces
+      rc = aabr_conv_forward_single_bwd_stats((const float *)p[0], o.i32[0], o.i64[0], (float *)p[1], o.i32[1], o.i64[1],
+                                              (const int32_t *)p[2], o.i32[2], (const float *)p[4], o.i32[3],
+                                              (const float *)p[5], (const float *)p[3], (double *)p[6],
+                                              (const float *)p[7], (const float *)p[8], (const float *)p[9],
+                                              (const float *)p[10], (const float *)p[11], o.f32[0], st);
+      break;
+    }
     rc = aabr_conv_forward_single((const float *)p[0], o.i32[0], o.i64[0], (float *)p[1], o.i32[1], o.i64[1],
                                   (const int32_t *)p[2], o.i32[2], (const float *)p[4], o.i32[3], (const float *)p[5],
                                   (const float *)p[3], st);

@@ -1453,7 +1453,8 @@ def wide_split(n_in, n_out, rows_in, rows_out, vol, bf16=False):
 class ConvRoute(collections.namedtuple("ConvRoute", "kind tile_rows parts bf16")):
     """What `conv_route` decided for one forward-form launch: `kind` None (no output rows), "narrow", "wide", "split"
     or "tiles"; `tile_rows` T of "wide" / "split" and `parts` P of "split", else 0; `bf16` the feature storage.
-    `single_route` returns kind "single" (k_conv_single over the offset pairs) or None."""
+    `single_route` returns kind "single" (k_conv_single over the offset pairs) or None; `single_bwd_stats_route` the same
+    kind with `parts` = the backward-statistics parts its write-out forms."""
     __slots__ = ()
 
     def stream(self, gather):
@@ -1478,6 +1479,8 @@ class ConvRoute(collections.namedtuple("ConvRoute", "kind tile_rows parts bf16")
             return (rows_out + self.tile_rows - 1) // self.tile_rows
         if self.kind == "narrow" and self.bf16:
             return int(_hip.load().aabr_conv_narrow_parts(rows_out))
+        if self.kind == "single":         # `single_bwd_stats_route`: one part per chunk of the pair list; else 0
+            return self.parts
         return 0
 
 
@@ -1510,6 +1513,21 @@ def single_route(n_in, n_out, rows_in, rows_out, vol, bf16, stats=False):
     return ConvRoute("single", 0, 0, bf16)
 
 
+def single_bwd_stats_route(n_in, n_out, rows_in, rows_out, vol, bf16):
+    """Asked before `single_route(..., stats=True)` (which keeps refusing) for an INPUT-GRADIENT launch with one rule per
+    output row whose write-out owes the BatchNorm behind it its backward statistics -- the input gradient of a Convolution
+    with filter == stride: ConvRoute("single") with `parts` = the fp64 parts k_conv_single<KG, true> writes (one per chunk
+    of the pair list, `stats_parts`), when csrc/conv_single_tiles.h's `single_bwd_stats_refusal` lets it through (the
+    conditions of `single_route` but the statistics one, knob SINGLE_BWD_STATS), else None."""
+    if rows_out == 0:
+        return None
+    lib = _hip.load()
+    chunk = lib.aabr_conv_single_bwd_stats_chunk(n_in, n_out, rows_in, rows_out, vol, 1 if bf16 else 0)
+    if not chunk:
+        return None
+    return ConvRoute("single", 0, int(lib.aabr_conv_single_bwd_stats_parts(rows_out, vol, chunk)), bf16)
+
+
 def _conv_dw(inp, d_out, gather, d_weight, d_bias):
     lib = _hip.load()
     if d_weight.dim() == 4 and d_weight.size(1) != 1:     # groups: one launch per group (see _conv_fwd_groups)
@@ -1537,16 +1555,19 @@ def _conv_dw(inp, d_out, gather, d_weight, d_bias):
         trace.append(("dw", n_in, n_out, gather, inp.size(0), 0, inp.dtype))
 
 
-def compile_streams(gather, rows_in, n_in, n_out, dtype, weight_grad=False, single=False):
+def compile_streams(gather, rows_in, n_in, n_out, dtype, weight_grad=False, single=False, single_bwd_stats=False):
     """Build, ahead of their first use, the block stream the forward-form launch (n_in -> n_out over `gather`) will
     read (its `conv_route`, for a prepacked weight) -- and, with `weight_grad`, the offset-pair lists of the dW kernel.
-    `single`: the book gives every output row one rule (see `single_route`, asked first: such a launch reads the pairs)."""
+    `single`: the book gives every output row one rule (see `single_route`, asked first: such a launch reads the pairs).
+    `single_bwd_stats`: an input-gradient launch over such a book that may owe a BatchNorm its backward statistics
+    (`single_bwd_stats_route`): the pairs as well as the stream of its `conv_route`, which it takes when nothing claims them."""
     if gather is None or gather.rows == 0:
         return
     bf16 = dtype == torch.bfloat16
     route = single_route(n_in, n_out, rows_in, gather.rows, gather.vol, bf16) if single else None
     (route or conv_route(n_in, n_out, rows_in, gather.rows, gather.vol, bf16)).stream(gather)
-    if weight_grad:
+    if weight_grad or (single_bwd_stats and
+                       single_bwd_stats_route(n_in, n_out, rows_in, gather.rows, gather.vol, bf16) is not None):
         gather.pairs()
 
 

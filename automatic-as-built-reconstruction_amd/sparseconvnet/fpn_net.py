@@ -302,9 +302,9 @@ class FPN_Net(torch.nn.Module):
             SCN.compile_streams(tb.out, tb.V_out, co, ci, dtype, single=single)       # input gradient (mirrored)
 
         def strided(tb, ci, co, dtype, transposed, single=False):
-            if not transposed:     # Convolution: fine -> coarse
+            if not transposed:     # Convolution: fine -> coarse; filter == stride: its input gradient has one rule per row
                 SCN.compile_streams(tb.out, tb.V_in, ci, co, dtype, weight_grad=True)
-                SCN.compile_streams(tb.inn, tb.V_out, co, ci, dtype)
+                SCN.compile_streams(tb.inn, tb.V_out, co, ci, dtype, single_bwd_stats=single)
             else:                  # Deconvolution over the same book: coarse -> fine
                 SCN.compile_streams(tb.inn, tb.V_out, ci, co, dtype, weight_grad=True, single=single)
                 SCN.compile_streams(tb.out, tb.V_in, co, ci, dtype)
@@ -320,7 +320,7 @@ class FPN_Net(torch.nn.Module):
             if k + 1 < nscale:
                 ks, st = tuple(self.down_kernels[k]), tuple(self.down_strides[k])
                 tb = md.rulebooks[key(sizes[k]) + ks + st]
-                strided(tb, planes[k], planes[k + 1], dt, False)  # down-sampling convolution
+                strided(tb, planes[k], planes[k + 1], dt, False, single=ks == st)  # down-sampling convolution
                 if live(k):
                     strided(tb, nM, nM, dt, True, single=ks == st)   # up-sampling deconvolution of the same book
             if k < nscale - 1 and live(k):

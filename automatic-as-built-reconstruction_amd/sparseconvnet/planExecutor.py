@@ -95,6 +95,7 @@ pipeline_records = int(os.environ.get("AABR_PLAN_PIPELINE", "0"))
 debug_passes = None
 # tests: a list here receives ("fwd" | "bwd", [record kinds]) of every launch list a pass builds; None in production
 debug_kinds = None
+debug_bwd_stats = None   # tests: a list that receives, per backward list, (kind, i32[5]) of every record
 # a pass that will not be differentiated packs its activations by liveness (AABR_PLAN_PACK_ARENA=0: one slot each, as
 # the training pass needs them)
 pack_inference_arena = os.environ.get("AABR_PLAN_PACK_ARENA", "1") != "0"
@@ -448,13 +449,17 @@ class _Template(object):
 
 
 def _one_rule(m, din):
-    """True when the rule book of this module's forward (`din` False) or input-gradient launch gives every output row
-    exactly one rule, by construction: what entitles the caller to ask `SCN.single_route`"""
+    """0 when the rule book of this module's forward (`din` False) or input-gradient launch may give an output row several
+    rules or none; 1 when it gives every output row exactly one, by construction: what entitles the caller to ask
+    `SCN.single_route`; 2 for the input gradient of a Convolution with filter == stride (every fine row has one parent),
+    which entitles it to `SCN.single_bwd_stats_route` ALONE: without statistics to deliver that launch stays where it was"""
     if isinstance(m, SubmanifoldConvolution):
-        return m.filter_volume == 1
+        return int(m.filter_volume == 1)
     if isinstance(m, Deconvolution) and not din:
-        return SCN._key(m.filter_size) == SCN._key(m.filter_stride)
-    return False
+        return int(SCN._key(m.filter_size) == SCN._key(m.filter_stride))
+    if isinstance(m, Convolution) and din:
+        return 2 if SCN._key(m.filter_size) == SCN._key(m.filter_stride) else 0
+    return 0
 
 
 def _out_of(op):
@@ -490,6 +495,7 @@ class _Pass(object):
         self.books = bk
         self.route = functools.lru_cache(maxsize=None)(SCN.conv_route)   # {launch shape: its ConvRoute} of the pass
         self.single = functools.lru_cache(maxsize=None)(SCN.single_route)
+        self.single_bwd_stats = functools.lru_cache(maxsize=None)(SCN.single_bwd_stats_route)
         self._tmp = []
 
     def fwd_route(self, op):
@@ -501,7 +507,7 @@ class _Pass(object):
         fz = t.fuse.get(id(op))
         g, bfx = self.books[book][side], t.fbufs[x][2] == BF16
         r = None
-        if _one_rule(op[15], False):
+        if _one_rule(op[15], False) == 1:
             r = self.single(n_in, n_out, V[lvl], V[lo], g.vol, bfx, conv_bn_stats and id(op) in t.stat_claims)
         if r is None and fz is not None:
             r = self.route(n_in, n_out, V[lvl], V[lo], g.vol, bfx, residual=True)
@@ -813,8 +819,13 @@ class _Pass(object):
                 g = books[book][side]
                 last_din, bf = None, flg == F_BF16
                 r = None
-                if one_rule:     # (statistics: a BatchNorm backward record may claim this launch's write-out)
-                    r = self.single(n_in, n_out, V[lo], V[lvl], g.vol, bf, conv_bn_bwd_stats and op_no in claimed)
+                claim = conv_bn_bwd_stats and op_no in claimed   # a BatchNorm backward record may ask for its statistics
+                if one_rule and claim:   # k_conv_single's backward-statistics form: one part per chunk of the pair list
+                    r = self.single_bwd_stats(n_in, n_out, V[lo], V[lvl], g.vol, bf)
+                    if r is not None:    # (holds from 32,768 rows on: V / 256 + vol <= V / 64 + 1)
+                        assert r.parts <= max(V) // 64 + 1, "the conv_bwd_stats workspace does not hold this launch's parts"
+                if r is None and one_rule == 1:
+                    r = self.single(n_in, n_out, V[lo], V[lvl], g.vol, bf, claim)
                 if r is None:
                     r = self.route(n_in, n_out, V[lo], V[lvl], g.vol, bf, residual=res is not None)
                 if res is None or r.takes_residual:
@@ -875,6 +886,9 @@ class _Pass(object):
                 off += 176
         if debug_kinds is not None:      # (with grad_segments > 1: the last piece only)
             debug_kinds.append(("bwd", [struct.unpack_from("<i", buf, o)[0] for o in range(0, off, 176)]))
+        if debug_bwd_stats is not None:  # i32[5] == 1 on a convolution record: its write-out delivers backward statistics
+            debug_bwd_stats.append([(struct.unpack_from("<i", buf, o)[0], struct.unpack_from("<i", buf, o + 28)[0])
+                                    for o in range(0, off, 176)])
         if part:
             check(self.lib.aabr_plan_submit(bytes(buf[start:off]), (off - start) // 176, strm, 0))
             check(self.lib.aabr_plan_drain())

@@ -340,6 +340,24 @@ const char *aabr_conv_single_refusal(int n_in, int n_out, int64_t rows_in, int64
 int aabr_conv_forward_single(const float *in_feats, int n_in, int64_t rows_in, float *out_feats, int n_out,
                              int64_t V_out, const int32_t *pairs, int vol, const float *bias, int flags,
                              const float *wpack, const float *residual, void *stream);
+/* The single-rule form as an INPUT-GRADIENT launch whose output is the d_out of a BatchNormalization(+leaky ReLU) -- the
+ * input gradient of a Convolution with filter == stride, every fine row having one parent: the write-out also forms that
+ * BatchNorm's backward statistics, term for term those of aabr_conv_forward_wide_bwd_stats below, whose BatchNorm
+ * arguments it takes in the same order; `out_feats` equals aabr_conv_forward_single's bit for bit.  `stats` receives
+ * aabr_conv_single_bwd_stats_parts(V_out, vol, chunk) parts of [2][n_out] fp64 sums, one per chunk of the pair list
+ * (chunks without pairs write zeros), to be summed in part order (aabr_bn_backward_parts); no atomics.  fp32 storage.
+ *   aabr_conv_single_bwd_stats_chunk: pairs per chunk when such a launch should take this form, else 0 (the conditions of
+ *     aabr_conv_single_chunk without the statistics one; knob SINGLE_BWD_STATS = 0).  `has_stats` of the two queries
+ *     above means statistics this plain form does not deliver: they keep refusing it;
+ *   aabr_conv_single_bwd_stats_refusal: why it returned 0 ("" when it did not).                                    */
+int aabr_conv_single_bwd_stats_chunk(int n_in, int n_out, int64_t rows_in, int64_t V_out, int vol, int bf16);
+const char *aabr_conv_single_bwd_stats_refusal(int n_in, int n_out, int64_t rows_in, int64_t V_out, int vol, int bf16);
+int64_t aabr_conv_single_bwd_stats_parts(int64_t V_out, int vol, int chunk_pairs);
+int aabr_conv_forward_single_bwd_stats(const float *in_feats, int n_in, int64_t rows_in, float *out_feats, int n_out,
+                                       int64_t V_out, const int32_t *pairs, int vol, const float *bias, int flags,
+                                       const float *wpack, const float *residual, double *stats, const float *bn_in,
+                                       const float *save_mean, const float *save_invstd, const float *bn_weight,
+                                       const float *bn_bias, float leakiness, void *stream);
 /* Input-gradient form of the same launch (flags = transposed | mirrored, as aabr_conv_forward_wide): its output is the
  * d_out of the BatchNormalization(+leaky ReLU) whose result the convolution consumed; the write-out forms THAT
  * BatchNorm's backward statistics (replaces the first loop of BatchNormalization_BackwardPass,
@@ -587,7 +605,8 @@ int aabr_conv_forward_narrow_bf16_bwd_stats(const uint16_t *in_feats, int64_t ro
  *   kind AABR_PLAN_CONV       aabr_conv_forward[_bf16](p0 in, i32[0] n_in, i64[0] rows_in, p1 out, i32[1] n_out,
  *                             i64[1] V_out, p2 blocks, i32[2] vol, p3 W, p4 bias, i32[3] flags, p5 wpack)
  *        AABR_PLAN_CONV_WIDE  aabr_conv_forward_wide_stats(p0, i32[0], i64[0], p1, i32[1], i64[1], p2 blocks,
- *                             i32[4] tile_rows, i32[2] vol, p4 bias, i32[3] flags, p5 wpack, p3 residual, p6 stats);
+ *                             i32[4] tile_rows, i32[2] vol, p4 bias, i32[3] flags, p5 wpack, p3 residual, p6 stats),
+ *                             the forward statistics of the FOLLOWING BatchNorm (p6 NULL: none; p7 .. p11 must be NULL);
  *                             i32[5] == 1: aabr_conv_forward_wide_bwd_stats(..., p3 residual, p6 stats, p7 bn_in,
  *                             p8 save_mean, p9 save_invstd, p10 bn_weight, p11 bn_bias, f32[0] leakiness); bf16
  *                             storage: aabr_conv_forward_wide_bf16_res(..., p5 wpack, p3 residual, p6 stats), with
@@ -626,12 +645,16 @@ int aabr_conv_forward_narrow_bf16_bwd_stats(const uint16_t *in_feats, int64_t ro
                                        ..., p3 residual); p3 NULL: no residual, in either storage (a bf16 record's
                                        p3 is read as bf16 rows: it must be NULL when no residual is wanted) */
 #define AABR_PLAN_CONV_NARROW 10 /* aabr_conv_forward_narrow[_bf16](p0 in, i64[0] rows_in, p1 out, i64[1] V_out, p2 table,
-                                   i32[2] vol, p3 W, p4 bias, i32[3] flags); bf16 storage with p6 != NULL: .._bf16_stats(.., p6
-                                   stats); i32[5] == 1: .._bf16_bwd_stats(.., p6 stats, p7 bn_in, p9 bn_out, p8 save_mean,
-                                   f32[0] leakiness) */
+                                   i32[2] vol, p3 W (the raw weight: this kernel takes no residual), p4 bias,
+                                   i32[3] flags); bf16 storage with p6 != NULL: .._bf16_stats(.., p6 stats); bf16
+                                   storage with i32[5] == 1: .._bf16_bwd_stats(.., p6 stats, p7 bn_in, p9 bn_out,
+                                   p8 save_mean, f32[0] leakiness); fp32 storage reads neither: p6 .. p11 must be NULL */
 #define AABR_PLAN_CONV_SINGLE 11 /* aabr_conv_forward_single(p0 in, i32[0] n_in, i64[0] rows_in, p1 out, i32[1] n_out,
                                    i64[1] V_out, p2 pairs, i32[2] vol, p4 bias, i32[3] flags, p5 wpack, p3 residual);
-                                   fp32 storage only; the caller guarantees one rule per output row */
+                                   fp32 storage only; the caller guarantees one rule per output row; p3 NULL: no
+                                   residual.  i32[5] == 1: aabr_conv_forward_single_bwd_stats(..., p3 residual,
+                                   p6 stats, p7 bn_in, p8 save_mean, p9 save_invstd, p10 bn_weight, p11 bn_bias,
+                                   f32[0] leakiness); otherwise p6 .. p11 are not read and must be NULL */
 #define AABR_PLAN_BF16 1
 #define AABR_PLAN_TO_BF16 2
 #define AABR_PLAN_JOIN 8 /* the caller's stream waits for the second stream in front of this record */

@@ -3,7 +3,10 @@ L0 .. L8): the route SCN.conv_route gives it today (k_conv_cs, its offset split 
 k_conv_single at both chunk lengths -- the up-sampling deconvolutions (filter 2 / stride 2, 128 -> 128), the 1x1x1 laterals
 forward (planes -> 128) and their input gradients (128 -> planes), each with a residual in the write-out where the route
 takes one.  Device time per call with the host taken out; outputs compared bit for bit where both routes run k_conv_cs'
-arithmetic.  usage: [first_seen|brick]"""
+arithmetic.  With `bwd_stats`: only the statistics-carrying books -- the input gradients of the down-sampling convolutions
+(filter 2 / stride 2), whose write-out forms the backward statistics of the BatchNorm in front: k_conv_cs with backward
+statistics (aabr_conv_forward_wide_bwd_stats) against k_conv_single with them (aabr_conv_forward_single_bwd_stats), outputs
+compared bit for bit, column totals of the statistics to 1e-12.  usage: [first_seen|brick] [bwd_stats]"""
 import importlib
 import os
 import sys
@@ -21,7 +24,7 @@ from sparseconvnet import SCN
 
 dev = torch.device("cuda:0")
 lib = _hip.load()
-order = sys.argv[1] if len(sys.argv) > 1 else "brick"
+order = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] != "bwd_stats" else "brick"
 PLANES = [32, 64, 64, 128, 128, 128, 256, 256, 256]
 l, _ = S.make_batch(4, 80000, 9000, 50)
 md = SCN.Metadata_3(order)
@@ -83,6 +86,61 @@ def run(name, ga, rows_in, n_in, n_out, transposed):
     print(line, flush=True)
 
 
+def run_bwd_stats(name, ga, rows_in, n_in, n_out):
+    vol, V = ga.vol, ga.rows
+    torch.manual_seed(1)
+    x = torch.randn((rows_in, n_in), device=dev)
+    W = torch.randn((vol, n_out, n_in), device=dev)
+    bx, mean, invstd = torch.randn((V, n_out), device=dev), torch.randn(n_out, device=dev), torch.rand(n_out, device=dev) + 0.5
+    bw, bb = torch.randn(n_out, device=dev), torch.randn(n_out, device=dev)
+    wpack = torch.empty(lib.aabr_conv_wpack_floats(vol, n_in, n_out), device=dev)
+    check(lib.aabr_conv_pack_weights(ptr(W), vol, n_in, n_out, 1, ptr(wpack), stream()))
+    route = SCN.conv_route(n_in, n_out, rows_in, V, vol, False, residual=True)
+    line = "%-22s %7d rows %3d->%-3d |" % (name, V, n_in, n_out)
+    if route.kind != "wide" or not route.stats_parts(V):
+        print(line + " no statistics in today's write-out (%s)" % route.kind, flush=True)
+        return
+    blocks, pairs, T = route.stream(ga), ga.pairs(), route.tile_rows
+    SCN.flush_geom()
+    out0, st0 = torch.empty((V, n_out), device=dev), torch.empty((route.stats_parts(V), 2, n_out), dtype=torch.float64, device=dev)
+    bn = (ptr(bx), ptr(mean), ptr(invstd), ptr(bw), ptr(bb), 0.0)
+    old = lambda: check(lib.aabr_conv_forward_wide_bwd_stats(ptr(x), n_in, rows_in, ptr(out0), n_out, V, ptr(blocks), T, vol,
+                                                             None, 3, ptr(wpack), None, ptr(st0), *bn, stream()))
+    old()
+    v0 = lib.aabr_conv_last_variant().decode()
+    t0 = bench.device_time(torch, old)
+    flop = 2.0 * V * n_in * n_out
+    line += " %-16s +stats %7.1f us %5.1f TF |" % (v0, t0 * 1e6, flop / t0 / 1e12)
+    _hip.set_knob("SINGLE_ROWS", 0)
+    _hip.set_knob("SINGLE_BWD_STATS", 1)
+    for chunk in (256, 1024):
+        _hip.set_knob("SINGLE_CHUNK", chunk)
+        why = lib.aabr_conv_single_bwd_stats_refusal(n_in, n_out, rows_in, V, vol, 0).decode()
+        if why:
+            line += " single: " + why
+            break
+        P = lib.aabr_conv_single_bwd_stats_parts(V, vol, chunk)
+        out1 = torch.full((V, n_out), float("nan"), device=dev)
+        st1 = torch.full((P, 2, n_out), float("nan"), dtype=torch.float64, device=dev)
+        new = lambda: check(lib.aabr_conv_forward_single_bwd_stats(ptr(x), n_in, rows_in, ptr(out1), n_out, V, ptr(pairs), vol,
+                                                                   None, 3, ptr(wpack), None, ptr(st1), *bn, stream()))
+        new()
+        a, b = st0.sum(0), st1.sum(0)
+        same = torch.equal(out0, out1) and float((a - b).abs().max()) <= 1e-12 * float(a.abs().max())
+        t1 = bench.device_time(torch, new)
+        line += " single/%d +stats %7.1f us %5.1f TF %s" % (chunk, t1 * 1e6, flop / t1 / 1e12, "" if same else "(DIFFERS)")
+    _hip.set_knob("SINGLE_CHUNK", None)
+    _hip.set_knob("SINGLE_ROWS", None)
+    _hip.set_knob("SINGLE_BWD_STATS", None)
+    print(line, flush=True)
+
+
+if "bwd_stats" in sys.argv[1:]:
+    print("input gradients of the down-sampling convolutions with backward statistics in the write-out, fp32 storage, "
+          "site order %s" % order)
+    for k in range(8):
+        run_bwd_stats("down d_in L%d<-L%d" % (k, k + 1), books[k].inn, books[k].V_out, PLANES[k + 1], PLANES[k])
+    sys.exit(0)
 print("one-rule-per-row launches, fp32 storage, site order %s; residual in the write-out where the route takes one" % order)
 for k in range(8):
     tb = books[k]
