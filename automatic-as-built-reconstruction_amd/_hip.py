@@ -133,6 +133,10 @@ _SIGS = {
     "aabr_conv_pack_weights2": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "aabr_conv_pack_weights2_bf16": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "aabr_plan_run": (C.c_int, [_vp, _i32, _vp]),
+    "aabr_plan_run_tail": (C.c_int, [_vp, _i32, _vp, C.POINTER(C.c_uint64)]),
+    "aabr_plan_tail_join": (C.c_int, [C.c_uint64, _vp]),
+    "aabr_plan_tail_sync": (C.c_int, [C.c_uint64]),
+    "aabr_plan_tail_release": (C.c_int, [C.c_uint64]),
     "aabr_plan_submit": (C.c_int, [_vp, _i32, _vp, _i32]),
     "aabr_plan_drain": (C.c_int, []),
     "aabr_plan_launcher_stats": (None, [_vp, _vp, _vp]),

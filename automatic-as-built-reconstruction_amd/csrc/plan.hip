@@ -12,6 +12,7 @@
 // Also the two elementwise launches such a plan needs that the layer API gets from torch: residual add and the
 // fp32 <-> bf16 storage casts (round-to-nearest-even, as torch's `.to(torch.bfloat16)`).
 #include "common.h"
+#include "plan_tail.h"
 #include <string.h>
 #include <chrono>
 #include <condition_variable>
@@ -199,7 +200,8 @@ static_assert(sizeof(AabrPlanOp) == 176, "AabrPlanOp layout is part of the C ABI
 // of the main chain leave idle.  Same kernels on the same operands: the results do not depend on the interleaving.
 namespace {
 struct SideStream {
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr;            // the second stream in use: `own`, or the process-wide one (PLAN_TAIL = 2)
+  hipStream_t own = nullptr;               // this thread's second stream, created at its first side record
   size_t pending = 0;                      // side launches a held part (plan_run_part(.., hold)) left unjoined
   std::vector<hipEvent_t> events;
   hipEvent_t get(size_t k) {
@@ -212,7 +214,81 @@ struct SideStream {
   }
 };
 thread_local SideStream g_side;
+
+// ---- the deferred-join tail ------------------------------------------------------------------------------------------
+// Records flagged AABR_PLAN_TAIL run, in list order, on a TAIL stream: process-wide, one per device, lowest priority.
+// Each run of consecutive tail records starts once everything recorded before its first record on the caller's stream
+// is done (one fork event per run).  Unlike the second stream they are NOT joined when the call returns: the call
+// hands back a TICKET (aabr_plan_run_tail) -- an event recorded behind the last tail record -- and whoever holds it
+// joins: aabr_plan_tail_join(ticket, stream), from any thread, any number of times, or an AABR_PLAN_TAIL_JOIN record
+// in a later list (the backward list of the pass whose forward list forked the tail: autograd runs it on another
+// thread, which is why nothing here is thread-local).  Meant for launches whose results no later record and no
+// returned buffer reads -- the FPN's unconsumed top-down levels -- so that they fill the CUs the head, the loss and
+// the coarse half of the backward pass leave idle instead of standing in front of them.
+// PLAN_TAIL knob: 0 = tail records run where they stand on the caller's stream (no ticket), 1 = a stream of its own,
+// 2 = the tail shares ONE process-wide second stream with the AABR_PLAN_SIDE records of every thread (the process has
+// a fixed number of hardware queues: a fifth stream shares a queue with one of the other four).
+constexpr int kPlanTailDefault = 2;   // measured on the bench step: 12.12-12.17 ms off, 11.43-11.45 with 2, 19.5 with 1
+struct DevStreams { hipStream_t tail = nullptr, shared = nullptr; };
+std::mutex g_dev_mu;
+std::vector<DevStreams> g_dev_streams;     // by device ordinal; streams are created once and never destroyed
+TailTickets g_tickets;
+
+inline int plan_tail_mode() {
+  const int v = knob(K_PLAN_TAIL);
+  return (v == 0 || v == 1 || v == 2) ? v : kPlanTailDefault;
+}
+
+// the process-wide second stream (shared = true) or the tail's own stream of the current device
+int dev_stream(bool shared, hipStream_t *out) {
+  int dev = 0;
+  AABR_CHECK_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> l(g_dev_mu);
+  if ((int)g_dev_streams.size() <= dev) g_dev_streams.resize(dev + 1);
+  hipStream_t &s = shared ? g_dev_streams[dev].shared : g_dev_streams[dev].tail;
+  if (!s) {
+    int lo = 0, hi = 0;
+    const bool have = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess;
+    const int v = knob(K_PLAN_SIDE_PRIO);  // the shared stream carries the weight gradients: their rule (plan_run_part)
+    if (!shared && have)
+      AABR_CHECK_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, lo));
+    else if (shared && have && (v == 1 || v == 2))
+      AABR_CHECK_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, v == 1 ? lo : hi));
+    else
+      AABR_CHECK_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  }
+  *out = s;
+  return AABR_OK;
+}
 } // namespace
+
+extern "C" int aabr_plan_tail_join(uint64_t ticket, void *stream) {
+  std::lock_guard<std::mutex> l(g_tickets.m);
+  const int s = g_tickets.find(ticket);
+  if (s < 0) return AABR_OK;               // no tail, or released: its owner has joined it
+  AABR_CHECK_HIP(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)g_tickets.slots[s].event, 0));
+  return AABR_OK;
+}
+
+extern "C" int aabr_plan_tail_sync(uint64_t ticket) {
+  hipEvent_t e = nullptr;
+  {
+    std::lock_guard<std::mutex> l(g_tickets.m);
+    const int s = g_tickets.find(ticket);
+    if (s < 0) return AABR_OK;
+    e = (hipEvent_t)g_tickets.slots[s].event;
+  }
+  // outside the lock (the wait can be long).  A release + reuse meanwhile makes this wait for a LATER tail: longer, never
+  // shorter, than asked for.
+  AABR_CHECK_HIP(hipEventSynchronize(e));
+  return AABR_OK;
+}
+
+extern "C" int aabr_plan_tail_release(uint64_t ticket) {
+  std::lock_guard<std::mutex> l(g_tickets.m);
+  g_tickets.release(ticket);               // a second release, or one of 0, does nothing
+  return AABR_OK;
+}
 
 // one record = one entry point of include/aabr_hip.h on stream `st`
 static int plan_dispatch(const AabrPlanOp &o, void *st) {
@@ -371,11 +447,21 @@ static int plan_dispatch(const AabrPlanOp &o, void *st) {
 
 // `hold`: this list is a PART of a pass whose next part follows on the same thread -- the side stream is left unjoined at
 // the end (its launches keep running beside the next part's); the part that ends the pass (hold = 0) joins.
-static int plan_run_part(const AabrPlanOp *ops, int n_ops, void *st_, int hold) {
+// `ticket_out`: where the ticket of this list's tail records goes (0 when it has none, or with PLAN_TAIL = 0); NULL = the
+// entry point has no way to hand one back and tail records are an error.
+static int plan_run_part(const AabrPlanOp *ops, int n_ops, void *st_, int hold, uint64_t *ticket_out) {
   AABR_CHECK_ARG(n_ops >= 0 && (ops || n_ops == 0), "bad plan");
+  if (ticket_out) *ticket_out = 0;
   hipStream_t main_stream = (hipStream_t)st_;
   size_t n_events = 0, n_pending = g_side.pending;   // events used by this call / side launches not yet joined
   g_side.pending = 0;
+  const int tail_mode = plan_tail_mode();
+  // (a held part's launches stay on the stream they went to.)  PLAN_TAIL = 2: the process-wide stream, looked up at the
+  // first side record of the call (flush) -- a list without side or tail records touches no HIP call of this file
+  if (n_pending == 0) g_side.stream = tail_mode == 2 ? nullptr : g_side.own;
+  hipStream_t tail_stream = nullptr;
+  size_t n_tail = 0;                       // tail launches of this call (no ticket yet)
+  bool in_tail_run = false;
   // AABR_PLAN_SIDE records can be handed to the second stream in BATCHES (PLAN_SIDE_BATCH knob): one event on the
   // caller's stream per batch instead of one per record (an event is a marker packet in the queue, ~5 us of it).
   // Measured on the bench step: 13.47 ms with an event per record, 13.60 in batches of 4, 13.68 of 8 -- starting the
@@ -385,6 +471,7 @@ static int plan_run_part(const AabrPlanOp *ops, int n_ops, void *st_, int hold) 
   std::vector<int> deferred;
   auto fail = [&](int rc) {               // the failing entry point has set the error text; never leave the side stream unjoined
     if (n_pending) hipStreamSynchronize(g_side.stream);
+    if (n_tail) hipStreamSynchronize(tail_stream);   // ... nor a tail nobody holds a ticket for
     return rc;
   };
   // the caller's stream waits for everything issued on the second stream so far; every error leaves through fail()
@@ -398,6 +485,10 @@ static int plan_run_part(const AabrPlanOp *ops, int n_ops, void *st_, int hold) 
   };
   auto flush = [&]() -> int {
     if (deferred.empty()) return AABR_OK;
+    if (!g_side.stream && tail_mode == 2) {
+      const int rc = dev_stream(true, &g_side.stream);
+      if (rc != AABR_OK) return rc;
+    }
     if (!g_side.stream) {
       // PLAN_SIDE_PRIO knob (experiment): 1 = lowest queue priority for the second stream (its launches are not on the
       // critical chain), 2 = highest
@@ -407,6 +498,7 @@ static int plan_run_part(const AabrPlanOp *ops, int n_ops, void *st_, int hold) 
         AABR_CHECK_HIP(hipStreamCreateWithPriority(&g_side.stream, hipStreamNonBlocking, v == 1 ? lo : hi));
       else
         AABR_CHECK_HIP(hipStreamCreateWithFlags(&g_side.stream, hipStreamNonBlocking));
+      g_side.own = g_side.stream;
     }
     hipEvent_t e = g_side.get(n_events++);
     AABR_CHECK_ARG(e != nullptr, "event creation failed");
@@ -420,8 +512,45 @@ static int plan_run_part(const AabrPlanOp *ops, int n_ops, void *st_, int hold) 
     deferred.clear();
     return AABR_OK;
   };
+  // the tail stream waits for everything recorded so far on the caller's stream: once per run of tail records
+  auto fork_tail = [&]() -> int {
+    if (!tail_stream) {
+      const int rc = dev_stream(tail_mode == 2, &tail_stream);
+      if (rc != AABR_OK) return rc;
+    }
+    hipEvent_t e = g_side.get(n_events++);
+    AABR_CHECK_ARG(e != nullptr, "event creation failed");
+    AABR_CHECK_HIP(hipEventRecord(e, main_stream));
+    AABR_CHECK_HIP(hipStreamWaitEvent(tail_stream, e, 0));
+    return AABR_OK;
+  };
   for (int j = 0; j < n_ops; ++j) {
     const AabrPlanOp &o = ops[j];
+    if (o.kind == AABR_PLAN_TAIL_JOIN) {   // the caller's stream waits for an earlier list's tail (ticket in i64[0])
+      const int rc = aabr_plan_tail_join((uint64_t)o.i64[0], st_);
+      if (rc != AABR_OK) return fail(rc);
+      in_tail_run = false;
+      continue;
+    }
+    if ((o.flags & AABR_PLAN_TAIL) && tail_mode != 0) {
+      if (!ticket_out) {
+        aabr::set_error("aabr_plan_run: AABR_PLAN_TAIL records need aabr_plan_run_tail (somebody must hold the ticket)");
+        return fail(AABR_EINVAL);
+      }
+      if (o.flags & (AABR_PLAN_SIDE | AABR_PLAN_JOIN)) {
+        aabr::set_error("aabr_plan_run_tail: a tail record cannot also be a side or a join record");
+        return fail(AABR_EINVAL);
+      }
+      int rc = flush();                    // (PLAN_TAIL = 2: side records ahead of it in the list go ahead of it on the stream)
+      if (rc == AABR_OK && !in_tail_run) rc = fork_tail();
+      if (rc != AABR_OK) return fail(rc);
+      in_tail_run = true;
+      ++n_tail;                            // counted first: a record that fails after some of its launches is synchronised too
+      rc = plan_dispatch(o, (void *)tail_stream);
+      if (rc != AABR_OK) return fail(rc);
+      continue;
+    }
+    in_tail_run = false;
     if (o.flags & AABR_PLAN_JOIN) {        // this record reads what the side stream produced
       const int rc = flush();
       if (rc != AABR_OK) return fail(rc);
@@ -450,7 +579,7 @@ static int plan_run_part(const AabrPlanOp *ops, int n_ops, void *st_, int hold) 
       };
       int m = 1;
       while (j + m < n_ops && m < kCastJobsMax && ops[j + m].kind == AABR_PLAN_CAST &&
-             !(ops[j + m].flags & (AABR_PLAN_SIDE | AABR_PLAN_JOIN)) &&
+             !(ops[j + m].flags & (AABR_PLAN_SIDE | AABR_PLAN_JOIN | (tail_mode ? AABR_PLAN_TAIL : 0))) &&
              ((ops[j + m].flags ^ o.flags) & AABR_PLAN_TO_BF16) == 0) {
         const AabrPlanOp &c = ops[j + m];
         bool clash = false;
@@ -477,6 +606,25 @@ static int plan_run_part(const AabrPlanOp *ops, int n_ops, void *st_, int hold) 
     const int rc = flush();
     if (rc != AABR_OK) return fail(rc);
   }
+  if (n_tail) {                            // the ticket: an event behind the last tail record, owned by the caller from here on
+    std::lock_guard<std::mutex> l(g_tickets.m);
+    int dev = 0, slot = -1;
+    hipError_t he = hipGetDevice(&dev);
+    const uint64_t t = he == hipSuccess ? g_tickets.acquire(dev, &slot) : 0;
+    if (t != 0 && g_tickets.slots[slot].event == nullptr) {
+      hipEvent_t e = nullptr;
+      he = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+      if (he == hipSuccess) { g_tickets.slots[slot].event = (void *)e; g_tickets.slots[slot].device = dev; }
+    }
+    if (t != 0 && he == hipSuccess) he = hipEventRecord((hipEvent_t)g_tickets.slots[slot].event, tail_stream);
+    if (t == 0 || he != hipSuccess) {
+      if (t != 0) g_tickets.release(t);
+      aabr::set_error("aabr_plan_run_tail: no ticket for the tail (%s)", t == 0 ? "table full" : hipGetErrorString(he));
+      return fail(AABR_ELAUNCH);
+    }
+    *ticket_out = t;
+    n_tail = 0;                            // joined through the ticket from here on
+  }
   if (hold) {
     g_side.pending = n_pending;
     return AABR_OK;
@@ -493,7 +641,14 @@ extern "C" int aabr_plan_run(const AabrPlanOp *ops, int n_ops, void *st_) {
   // the second stream's join state and event pool are shared with the launcher thread: a pass handed over in parts must
   // have been drained before another list is run directly
   AABR_CHECK_ARG(!launcher_has_work(), "parts submitted with aabr_plan_submit are still queued: call aabr_plan_drain first");
-  return plan_run_part(ops, n_ops, st_, 0);
+  return plan_run_part(ops, n_ops, st_, 0, nullptr);
+}
+
+extern "C" int aabr_plan_run_tail(const AabrPlanOp *ops, int n_ops, void *st_, uint64_t *ticket) {
+  AABR_CHECK_ARG(ticket != nullptr, "the ticket needs a place to go");
+  *ticket = 0;
+  AABR_CHECK_ARG(!launcher_has_work(), "parts submitted with aabr_plan_submit are still queued: call aabr_plan_drain first");
+  return plan_run_part(ops, n_ops, st_, 0, ticket);
 }
 
 // ---- pipelined submission ---------------------------------------------------------------------------------------------
@@ -533,7 +688,7 @@ struct Launcher {
       { std::lock_guard<std::mutex> l(m); skip = rc != AABR_OK; }   // after a failure the rest of the pass is dropped
       if (!skip) {
         if (j.dev != cur_dev) { hipSetDevice(j.dev); cur_dev = j.dev; }
-        r = plan_run_part(j.ops.data(), (int)j.ops.size(), j.st, j.hold);
+        r = plan_run_part(j.ops.data(), (int)j.ops.size(), j.st, j.hold, nullptr);
       } else if (!j.hold && g_side.pending) {                        // ... but its side stream is never left unjoined
         hipStreamSynchronize(g_side.stream);
         g_side.pending = 0;
@@ -562,6 +717,8 @@ namespace aabr { extern thread_local const char *g_last_variant; }   // conv.hip
 
 extern "C" int aabr_plan_submit(const AabrPlanOp *ops, int n_ops, void *st, int hold_side) {
   AABR_CHECK_ARG(n_ops >= 0 && (ops || n_ops == 0), "bad plan");
+  for (int j = 0; j < n_ops; ++j)          // the launcher thread has nobody to hand a ticket to
+    AABR_CHECK_ARG(!(ops[j].flags & AABR_PLAN_TAIL), "AABR_PLAN_TAIL records cannot be submitted in parts: use aabr_plan_run_tail");
   int dev = 0;
   AABR_CHECK_HIP(hipGetDevice(&dev));
   std::call_once(g_launcher_once, [] {

@@ -396,7 +396,25 @@ class FPN_Net(torch.nn.Module):
         plan.refresh()
         return plan
 
+    def join_unconsumed(self):
+        """Extension: a training pass of the compiled graph may still be computing, on the library's tail stream, the
+        top-down stages no returned map depends on (planExecutor `plan_tail`).  The pass's backward joins them, and so does
+        the next forward; a caller that reads running statistics or updates parameters, BatchNorm buffers or
+        `load_state_dict` on its own between the two calls this first: the current stream then waits for them."""
+        if self.compiled_graph:
+            from . import planExecutor
+            planExecutor.join_pending()
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        self.join_unconsumed()          # state_dict() hands out the running statistics the tail may still be writing
+        return super()._save_to_state_dict(destination, prefix, keep_vars)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self.join_unconsumed()          # ... and load_state_dict() overwrites them, and the parameters it reads
+        return super()._load_from_state_dict(*args, **kwargs)
+
     def forward(self, net0):
+        self.join_unconsumed()          # ... they read the packed weights and the parameters of the previous pass
         plan = self._refresh_weight_packs() if self.prepack_weights else None
         try:
             return self._forward(net0)

@@ -20,8 +20,10 @@ Two stages, so that a pass costs little Python:
 What it buys: the ~25 us of interpreter + autograd work per layer and direction leave the critical path.  What it
 does not do: change any number -- `tests/test_gpu_fpn.py` holds it bit-equal to the module path.  Falls back
 (returns None) when a module of the graph carries hooks or is of a type it does not know."""
+import ctypes
 import functools
 import struct
+import threading
 
 import torch
 from torch.autograd import Function
@@ -41,7 +43,8 @@ from .deconvolution import Deconvolution
 _OP = struct.Struct("<ii6i4f4q12Q")          # AabrPlanOp (include/aabr_hip.h)
 assert _OP.size == 176
 K_CONV, K_WIDE, K_DW, K_BNF, K_BNB, K_ADD, K_CAST, K_WSPLIT, K_NARROW, K_SINGLE = 1, 2, 3, 4, 5, 6, 7, 9, 10, 11
-F_BF16, F_TO_BF16, F_SIDE, F_JOIN = 1, 2, 4, 8
+K_TAIL_JOIN = 12
+F_BF16, F_TO_BF16, F_SIDE, F_JOIN, F_TAIL = 1, 2, 4, 8, 16
 _ALIGN = 256
 BF16 = torch.bfloat16
 
@@ -70,6 +73,65 @@ conv_bn_bwd_stats = os.environ.get("AABR_PLAN_CONV_BN_BWD_STATS", "1") != "0"
 # the wave-level reductions (16 x 8 fp64 values per 16-row group) cost the launch more than the BatchNorm's own HBM-bound
 # statistics passes; off by default.
 narrow_stats = os.environ.get("AABR_PLAN_NARROW_STATS", "0") != "0"
+# The forward ops no returned map depends on (`unconsumed_ops`: for the bench network the top-down stages below the last
+# consumed level, which the reference computes all the same) go to the END of a training pass's forward list, flagged
+# AABR_PLAN_TAIL: the library runs them on its tail stream beside the head, the loss and the backward pass instead of
+# in front of them, and the pass holds the ticket (`_Pass.join_tail`; who joins when: DESIGN.md "The deferred-join tail").
+# Same records, same operands, same bits.  0 = today's list; 1 = a tail stream of its own; 2 = the tail shares one
+# process-wide second stream with the weight gradients.  The environment variable is the library's PLAN_TAIL knob as
+# well (one name, read by both sides); `set_plan_tail` switches both inside a process.
+PLAN_TAIL_DEFAULT = 2                    # = kPlanTailDefault of csrc/plan.hip
+plan_tail = int(os.environ.get("AABR_PLAN_TAIL", PLAN_TAIL_DEFAULT))
+
+
+def set_plan_tail(v):
+    """switch the tail (0 / 1 / 2) on both sides of the C ABI; None = the shipped default.  Joins what is in flight."""
+    global plan_tail
+    join_pending()
+    plan_tail = PLAN_TAIL_DEFAULT if v is None else int(v)
+    assert plan_tail in (0, 1, 2)
+    _hip.set_knob("PLAN_TAIL", plan_tail)
+
+
+def unconsumed_ops(fops, outs):
+    """indices of the forward ops from which no returned buffer is reachable: walking the list backwards, an op is
+    needed when a returned buffer or a needed op reads what it writes.  `fops`: the template's op tuples (("add", a, b,
+    out, ..) / (kind, in, out, ..)); `outs`: [(buffer, ..)] of the returned maps.  A rule over the dataflow, not over
+    level numbers."""
+    need = {o[0] for o in outs}
+    dead = set()
+    for i in range(len(fops) - 1, -1, -1):
+        op = fops[i]
+        if _out_of(op) in need:
+            need.update((op[1], op[2]) if op[0] == "add" else (op[1],))
+        else:
+            dead.add(i)
+    return frozenset(dead)
+
+
+def tail_emission(fops, dead):
+    """[(op, record flags)]: the consumed ops in their order, then the unconsumed ones in theirs, flagged for the tail.
+    A stable partition, so two ops of the same class that stood next to each other still do: a convolution and the
+    add that rides in its write-out (the add is the convolution's only reader, so both are in the same class), and a
+    convolution and the BatchNorm that takes its statistics, unless the convolution is consumed and the BatchNorm is
+    not -- the one pair that crosses (`_Template._cross_claims`)."""
+    return [(op, 0) for i, op in enumerate(fops) if i not in dead] + \
+           [(op, F_TAIL) for i, op in enumerate(fops) if i in dead]
+
+
+# passes whose tail nobody has joined yet.  A STRONG reference: the arena, the geometry, the split scratch and the
+# statistics buffers the tail reads and writes cannot go back to the allocator (which reuses blocks in main-stream
+# order) before a join has been enqueued -- "the pass went away without a backward" cannot precede its join.
+_tails = []
+_tails_lock = threading.Lock()
+
+
+def join_pending(device=None):
+    """the current stream of `device` (None: of each pass's own device) waits for every tail still in flight there"""
+    with _tails_lock:
+        take = [p for p in _tails if device is None or p.dev == device]
+    for p in take:
+        p.join_tail()
 
 
 # Data-parallel hook (extension; the reference wraps the model in DistributedDataParallel, whose bucketed all-reduce
@@ -147,6 +209,10 @@ class _Template(object):
         self.emit = self._emission()
         self.fuse = self._fusable_adds() if (fuse_adds and not lateral_side_stream) else {}
         self.stat_claims = self._stat_claims()
+        # the tail form of the list (a training pass with `plan_tail`): consumed records first, then the unconsumed ones
+        self.dead = unconsumed_ops(self.fops, self.outs) if not lateral_side_stream else frozenset()
+        self.emit_tail = tail_emission(self.fops, self.dead) if self.dead else None
+        self.cross = self._cross_claims() if self.dead else {}
         stats["templates"] += 1
 
     def _stat_claims(self):
@@ -164,6 +230,25 @@ class _Template(object):
                     continue
                 if nop[0] == "bn" and nop[6] and nop[4] == op[6] and nop[1] in wrote:
                     out.add(id(op))
+                break
+        return out
+
+    def _cross_claims(self):
+        """{id(BatchNorm op): id(convolution op)} of the statistics claims (`_stat_claims`) that cross from the caller's
+        stream to the tail: a consumed convolution whose write-out forms the statistics of an UNCONSUMED BatchNorm (the
+        first top-down stage below the last returned map normalises that map).  The convolution still forms them, into a
+        buffer of the pair's own, and the BatchNorm record on the tail reads them there: the bits of the one-stream list."""
+        idx = {id(op): i for i, op in enumerate(self.fops)}
+        out = {}
+        for i, (op, xf) in enumerate(self.emit):
+            if id(op) not in self.stat_claims or idx[id(op)] in self.dead:
+                continue
+            fz = self.fuse.get(id(op))
+            for nop, nxf in self.emit[i + 1:]:
+                if (nxf ^ xf) & F_SIDE or (fz is not None and nop is fz[0]):
+                    continue
+                if idx[id(nop)] in self.dead:
+                    out[id(nop)] = id(op)
                 break
         return out
 
@@ -497,6 +582,26 @@ class _Pass(object):
         self.single = functools.lru_cache(maxsize=None)(SCN.single_route)
         self.single_bwd_stats = functools.lru_cache(maxsize=None)(SCN.single_bwd_stats_route)
         self._tmp = []
+        self._tail_tmp = []                # the offset-split scratch of tail records: dropped after the join, not before
+        self._ticket = 0                   # the tail of this pass's forward list (aabr_plan_run_tail), 0 = none / joined
+        self._strm = None
+
+    def join_tail(self):
+        """the stream the pass ran on (and the current one) waits for the pass's tail; the ticket goes back.  From any
+        thread, any number of times."""
+        with _tails_lock:
+            tk, self._ticket = self._ticket, 0
+            if tk:
+                _tails[:] = [p for p in _tails if p is not self]
+        if not tk:
+            return
+        with torch.cuda.device(self.dev):
+            cur = stream()
+            check(self.lib.aabr_plan_tail_join(tk, self._strm))
+            if cur != self._strm:
+                check(self.lib.aabr_plan_tail_join(tk, cur))
+            check(self.lib.aabr_plan_tail_release(tk))
+        self._tail_tmp = []
 
     def fwd_route(self, op):
         """(route, fused add or None) of a forward convolution record: `SCN.single_route` first where the module's rule
@@ -541,7 +646,7 @@ class _Pass(object):
             # be reallocated under records already written (the allocator frees it in stream order once the pass's
             # next list is built)
             tmp = torch.empty(route.parts * rows_out * n_out, dtype=torch.float32, device=self.dev)
-            self._tmp.append(tmp)
+            (self._tail_tmp if xf & F_TAIL else self._tmp).append(tmp)
             pack(buf, off, K_WSPLIT, xf, n_in, n_out, gather.vol, flags & 3, route.tile_rows, route.parts, 0.0, 0.0,
                  0.0, 0.0, rows_in, rows_out, 0, 0, src, dst, blocks, res, 0, p_pack, tmp.data_ptr(), 0, 0, 0, 0, 0)
         else:
@@ -613,17 +718,22 @@ class _Pass(object):
             free = merged
         return offs, top, sum(size(b) for b in range(1, len(fbufs)))
 
-    def forward(self, keep=True):
-        """`keep` False (no autograd): the arena is packed by liveness (`_live_offsets`)"""
+    def forward(self, keep=True, tail=False):
+        """`keep` False (no autograd): the arena is packed by liveness (`_live_offsets`); `tail`: a training pass, whose
+        unconsumed records may go to the tail stream (`plan_tail`)"""
         try:
-            return self._forward(keep)
+            return self._forward(keep, tail)
         except BaseException:
             self.lib.aabr_plan_drain()     # never leave parts of a failed pass in the launcher's queue
             raise
 
-    def _forward(self, keep):
+    def _forward(self, keep, tail=False):
         t, V = self.t, self.V
+        self.join_tail()                   # (a pass object run twice)
         self._tmp = []
+        # the tail: one slot per activation (nothing of the arena is handed on) and one call per list (the launcher
+        # thread has nobody to hand a ticket to)
+        use_tail = bool(tail and keep and plan_tail and t.emit_tail is not None and not pipeline_records)
         packed = None if keep else self._live_offsets()
         if packed is not None:
             offs, total, flat = packed
@@ -637,6 +747,9 @@ class _Pass(object):
         A = self.A = [base + o for o in offs]
         A[0] = self.x.data_ptr()
         bnws = _hip.workspace("bn", t.bn_floats, torch.float32, self.dev).data_ptr() if t.bn_floats else 0
+        # the tail's BatchNorm records run beside the backward list's, which use "bn" on this same stream key
+        bnws_tail = _hip.workspace("bn_tail", t.bn_floats, torch.float32, self.dev).data_ptr() \
+            if (use_tail and t.bn_floats) else 0
         buf = bytearray(len(t.fops) * 176)
         pack, off = _OP.pack_into, 0
         books = self.books
@@ -645,10 +758,12 @@ class _Pass(object):
         # BatchNorm statistics from the producing convolution's write-out: a training-mode BatchNorm that is the NEXT
         # record on its stream after the k_conv_cs launch that wrote its input gets the per-tile partial sums from
         # that launch (record p6 -> BatchNorm p9) and skips its own statistics pass over the matrix
-        last = {0: None, F_SIDE: None}     # per stream: (buffer index written, record offset, parts, planes)
+        last = {0: None, F_SIDE: None, F_TAIL: None}   # per stream: (buffer index written, record offset, parts, planes)
         cstat = {}
+        cross = t.cross if use_tail else {}
+        cross_convs, xlast = set(cross.values()), {}
         part, start, strm = pipeline_records * 176, 0, stream()
-        for op, xf in t.emit:
+        for op, xf in (t.emit_tail if use_tail else t.emit):
             if part and off - start >= part:
                 # records up to `safe` are final (a convolution record stays open while the BatchNorm behind it may
                 # still claim its write-out for the statistics)
@@ -660,7 +775,7 @@ class _Pass(object):
                     check(self.lib.aabr_plan_submit(bytes(buf[start:safe]), (safe - start) // 176, strm, 1))
                     start = safe
             kind = op[0]
-            sk = xf & F_SIDE
+            sk = xf & (F_SIDE | F_TAIL)
             if kind == "conv":
                 x, y, lvl, lo, n_in, n_out, book, side, p_w, pf = op[1:11]
                 g, off0, res = books[book][side], off, 0
@@ -672,21 +787,27 @@ class _Pass(object):
                 off, nparts = self.conv_launch(r, pack, buf, off, A[x], V[lvl], n_in, A[y], V[lo], n_out, g, p_w, pf, 0,
                                                xf, res)
                 last[sk] = (y, off0, nparts, n_out) if nparts else None
+                if id(op) in cross_convs:
+                    xlast[id(op)] = last[sk]
                 continue
             elif kind == "bn":
                 _, x, y, lvl, planes, flg, train, eps, mom, leak, st, p_rm, p_rv, p_w, p_b, m = op
                 if V[lvl]:
                     parts, nparts, lw = 0, 0, last[sk]
+                    wk = sk
+                    if id(op) in cross:  # the convolution ran on the caller's stream: a buffer of this pair's own
+                        lw, wk = xlast.get(cross[id(op)]), "_cross%d" % len(cstat)
                     if conv_bn_stats and train and lw is not None and lw[0] == x and lw[3] == planes:
                         nparts = lw[2]
-                        ws = cstat.get(sk)
+                        ws = cstat.get(wk)
                         if ws is None:   # one buffer per stream: written by the convolution, read by the very next record
-                            ws = cstat[sk] = _hip.workspace("conv_stats%d" % sk, (max(V) // 64 + 1) * 2 * t.max_planes,
+                            ws = cstat[wk] = _hip.workspace("conv_stats%s" % wk, (max(V) // 64 + 1) * 2 * t.max_planes,
                                                             torch.float64, self.dev).data_ptr()
                         parts = ws
                         struct.pack_into("<Q", buf, lw[1] + 128, ws)          # the convolution record's p6
                     pack(buf, off, K_BNF, flg | xf, planes, train, nparts, 0, 0, 0, eps, mom, leak, 0.0, V[lvl], 0, 0, 0,
-                         A[x], A[y], sbase + st * 4, sbase + (st + planes) * 4, p_rm, p_rv, p_w, p_b, bnws, parts, 0, 0)
+                         A[x], A[y], sbase + st * 4, sbase + (st + planes) * 4, p_rm, p_rv, p_w, p_b,
+                         bnws_tail if sk & F_TAIL else bnws, parts, 0, 0)
                     off += 176
             elif kind == "add":
                 if id(op) in skip:
@@ -706,6 +827,14 @@ class _Pass(object):
         if part:
             check(self.lib.aabr_plan_submit(bytes(buf[start:off]), (off - start) // 176, strm, 0))
             check(self.lib.aabr_plan_drain())      # everything issued: the caller's next launches queue behind the pass
+        elif off and use_tail:
+            ticket = ctypes.c_uint64(0)
+            self._strm = strm
+            check(self.lib.aabr_plan_run_tail(bytes(buf[:off]), off // 176, strm, ctypes.byref(ticket)))
+            if ticket.value:
+                with _tails_lock:
+                    self._ticket = ticket.value
+                    _tails.append(self)
         elif off:
             check(self.lib.aabr_plan_run(bytes(buf[:off]), off // 176, strm))
         res = []
@@ -717,6 +846,7 @@ class _Pass(object):
 
     def buffer(self, b):
         """forward buffer `b` of this pass as a tensor view into the arena (tests)"""
+        self.join_tail()                   # an unconsumed stage's buffer is written on the tail stream
         lvl, planes, dt = self.t.fbufs[b]
         n = self.V[lvl] * planes * _es(dt)
         return self.arena[self.offs[b]:self.offs[b] + n].view(dt).view(self.V[lvl], planes)
@@ -768,7 +898,7 @@ class _Pass(object):
         dwmc.reverse()
         dwws = _hip.workspace("dw", dws, torch.float32, self.dev).data_ptr() if dws else 0
         bnws = _hip.workspace("bn", t.bn_floats, torch.float32, self.dev).data_ptr() if t.bn_floats else 0
-        buf = bytearray(len(bops) * 2 * 176)
+        buf = bytearray((len(bops) * 2 + 1) * 176)
         pack, off = _OP.pack_into, 0
         dw_side = F_SIDE if dw_side_stream else 0
         # pieces of the list for the data-parallel hook: cut after every len/S-th record; parameter gradients are laid
@@ -889,11 +1019,21 @@ class _Pass(object):
         if debug_bwd_stats is not None:  # i32[5] == 1 on a convolution record: its write-out delivers backward statistics
             debug_bwd_stats.append([(struct.unpack_from("<i", buf, o)[0], struct.unpack_from("<i", buf, o + 28)[0])
                                     for o in range(0, off, 176)])
+        # The forward list's tail is joined HERE, by the last record of the (last piece of the) backward list: behind it
+        # come the gradient hand-over and the caller's update, which rewrites the BatchNorm parameters and running
+        # statistics the tail's records read and write.
+        tk = self._ticket
+        if tk and not part:
+            pack(buf, off, K_TAIL_JOIN, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, tk, 0, 0, 0,
+                 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+            off += 176
         if part:
             check(self.lib.aabr_plan_submit(bytes(buf[start:off]), (off - start) // 176, strm, 0))
             check(self.lib.aabr_plan_drain())
         elif off:
             check(self.lib.aabr_plan_run(bytes(buf[:off]), off // 176, stream()))
+        if tk:                            # enqueued on this stream by the record; `join_tail` covers the other cases
+            self.join_tail()              # (pipelined backward, another stream than the forward's) and returns the ticket
         if nseg > 1:                      # the last piece's gradients
             pairs = []
             while next_inv < len(inv):
@@ -922,7 +1062,7 @@ class _Pass(object):
 class _GraphFunction(Function):
     @staticmethod
     def forward(ctx, ps, x, *params):
-        res = ps.forward()
+        res = ps.forward(tail=True)
         ctx.ps = ps
         ctx.need_dx = x.requires_grad
         # The backward list reads the transposed weight packs of THIS forward and recomputes the BatchNorm activation

@@ -40,12 +40,15 @@ const char *aabr_last_error(void);
  * 640 = the box head's loss (aabr_roi_targets, aabr_roi_box_loss_*).
  * The multi-level ROI pooler (aabr_roi_pool_*, AabrRoiLevel) came after 640 WITHOUT a bump: it adds symbols and one new
  * record only, no existing signature or layout changed, so a binding written for 640 still matches.  The box head's
- * dense layers (aabr_roi_mlp_*) and the RPN head (aabr_rpn_head_*, AabrRpnMap) came the same way: symbols only. */
+ * dense layers (aabr_roi_mlp_*) and the RPN head (aabr_rpn_head_*, AabrRpnMap) came the same way: symbols only.  So did
+ * the deferred-join tail of a launch plan (AABR_PLAN_TAIL, AABR_PLAN_TAIL_JOIN, aabr_plan_run_tail, aabr_plan_tail_*):
+ * one flag bit and one record kind that no earlier list carries, four new symbols, AabrPlanOp unchanged. */
 #define AABR_ABI_VERSION 640
 int aabr_version(void);
 /* Tuning knobs for experiments and tests (no counterpart in the reference; the defaults are what ships): CONV_WIDE,
  * CONV_WIDE_BF16 (0 = never / 1 = whenever supported), WIDE_ROWS, WIDE_NBUF, CONV_WLDS,
- * CONV_SMALL, CONV_NBW, CONV_WPB, VOXEL_MEAN, GEOM_JOBS (0: aabr_geom_run issues its stream builders book by book).  A knob takes its value from the environment variable AABR_<NAME>,
+ * CONV_SMALL, CONV_NBW, CONV_WPB, VOXEL_MEAN, GEOM_JOBS (0: aabr_geom_run issues its stream builders book by book).  PLAN_TAIL
+ * (0 / 1 / 2: where AABR_PLAN_TAIL records run, see the compiled launch plans below; 2 ships).  A knob takes its value from the environment variable AABR_<NAME>,
  * read ONCE at its first use in the process; aabr_set_knob overrides it (unset != 0: back to "no value").  No entry
  * point reads the environment on its launch path.                                                              */
 int aabr_set_knob(const char *name, int value, int unset);
@@ -660,6 +663,33 @@ int aabr_conv_forward_narrow_bf16_bwd_stats(const uint16_t *in_feats, int64_t ro
 #define AABR_PLAN_JOIN 8 /* the caller's stream waits for the second stream in front of this record */
 #define AABR_PLAN_SIDE 4 /* run this record on the library's second stream: it starts after everything recorded
                             before it, and the caller's stream waits for it before aabr_plan_run returns it */
+/* The deferred-join TAIL (extension): launches whose results nothing later in the list and no returned buffer reads.
+ *   AABR_PLAN_TAIL (flag)  the record runs on the library's tail stream (process-wide, one per device, lowest stream
+ *                          priority), in list order among the tail records.  A run of consecutive tail records starts
+ *                          after everything recorded before its first record on the caller's stream (one event per
+ *                          run).  It is NOT joined when the call returns: only aabr_plan_run_tail accepts such records,
+ *                          and hands back a ticket.  aabr_plan_run and aabr_plan_submit refuse them (AABR_EINVAL).
+ *                          Cannot be combined with AABR_PLAN_SIDE / AABR_PLAN_JOIN.  Runs of AABR_PLAN_CAST records are
+ *                          merged per stream: a tail cast never joins a run of the caller's stream.
+ *   ticket                 an event recorded behind the last tail record of the call; 0 = the list had no tail record
+ *                          (or PLAN_TAIL = 0).  The CALLER owns it, from the moment aabr_plan_run_tail returns AABR_OK
+ *                          until it calls aabr_plan_tail_release; on any other return code no tail is left running
+ *                          (the call has synchronised it) and the ticket is 0.
+ *   who must join before what: the holder makes a stream wait for the ticket -- aabr_plan_tail_join(ticket, stream),
+ *                          or an AABR_PLAN_TAIL_JOIN record (kind; i64[0] = the ticket, every other field 0) in a list
+ *                          run on that stream -- BEFORE anything on that stream overwrites or frees what the tail
+ *                          reads or writes: its operands, scratch buffers, the parameters and running statistics an
+ *                          optimizer step or a later pass rewrites.  aabr_plan_tail_sync(ticket) is the host-side form.
+ *                          All three may be called from any thread, any number of times; for ticket 0 and for a
+ *                          RELEASED ticket they do nothing and return AABR_OK (releasing says "I have joined").
+ *   aabr_plan_tail_release returns the ticket's event to the library's pool; a second release does nothing.  Release
+ *                          only after a join has been enqueued (or a sync has returned): the library does not wait.
+ *   PLAN_TAIL knob         0 = tail records run where they stand in the list on the caller's stream, ticket 0;
+ *                          1 = the tail stream is a stream of its own; 2 = the tail stream IS the second stream, one
+ *                          per process and device, shared with the AABR_PLAN_SIDE records of every thread (a process
+ *                          has a fixed number of hardware queues; with 1 the side stream stays per thread). */
+#define AABR_PLAN_TAIL 16
+#define AABR_PLAN_TAIL_JOIN 12
 typedef struct AabrPlanOp {
   int32_t kind, flags;
   int32_t i32[6];
@@ -668,6 +698,10 @@ typedef struct AabrPlanOp {
   void *p[12];
 } AabrPlanOp; /* 176 bytes, no padding */
 int aabr_plan_run(const AabrPlanOp *ops, int n_ops, void *stream);
+int aabr_plan_run_tail(const AabrPlanOp *ops, int n_ops, void *stream, uint64_t *ticket);
+int aabr_plan_tail_join(uint64_t ticket, void *stream);
+int aabr_plan_tail_sync(uint64_t ticket);
+int aabr_plan_tail_release(uint64_t ticket);
 /* Pipelined form (extension): a pass's list handed over in PARTS.  aabr_plan_submit copies the records, queues them for the
  * library's launcher thread and returns at once -- the caller fills the next part while this one's launches go out
  * (issuing ~450 launches costs the host 1.7 ms per training step, filling their records about as much).  Parts are
