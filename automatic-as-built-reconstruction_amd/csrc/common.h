@@ -11,6 +11,11 @@ namespace aabr {
 
 void set_error(const char *fmt, ...);
 
+// vector types the convolution sources share (MFMA operands and accumulators)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
 // Tuning knobs (experiments and tests only; the defaults are what ships).  Each is read from its environment
 // variable AABR_<NAME> ONCE, at its first use in the process, and can be set explicitly through aabr_set_knob --
 // no entry point calls getenv on its launch path.
@@ -131,7 +136,7 @@ __device__ inline uint32_t grid_insert(GridEnt *g, uint64_t mask, uint64_t key) 
 
 // ---- stream builders over MANY rule books in one launch (round 6) ----------------------------------------------------
 // A pass compiles every gather table into its streaming forms: wide tile blocks (conv_wide.hip), 64-row tile blocks and
-// the offset-major pair list of the weight gradient (conv.hip).  Round 5 issued them book by book -- 4 launches x ~45
+// the offset-major pair list of the weight gradient (built in conv.hip, read by conv_dw.hip).  Round 5 issued them book by book -- 4 launches x ~45
 // books of 2.5-14 us each, a third of a step's launches.  A job list hands up to kStreamJobsMax books to ONE launch:
 // block b of the grid serves job j with first[j] <= b < first[j + 1].  Same per-book code, bit-identical words.
 constexpr int kStreamJobsMax = 48;

@@ -21,8 +21,6 @@
 
 namespace aabr {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8n __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4n __attribute__((ext_vector_type(4)));
 extern thread_local const char *g_last_variant; // conv.hip

@@ -27,8 +27,6 @@
 
 namespace aabr {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 extern thread_local const char *g_last_variant; // conv.hip
 

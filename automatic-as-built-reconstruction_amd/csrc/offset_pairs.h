@@ -1,5 +1,5 @@
 // offset_pairs.h -- layout of the offset-major compacted pair list (built by k_offset_bases / k_fill_offset_pairs in
-// conv.hip) and the chunk-to-workgroup scheme its readers share: the weight-gradient kernels of conv.hip and the
+// conv.hip) and the chunk-to-workgroup scheme its readers share: the weight-gradient kernels of conv_dw.hip and the
 // single-rule convolution of conv_single.hip.
 //   words: [vol] R_k | [vol+1] first 1024-pair chunk of offset k | [vol+1] first 256-pair chunk |
 //          [vol][nb256] block bases | [vol][V][2] pairs (partner row, row), ascending row order per offset

@@ -6,12 +6,13 @@ must be the float64 reference's bits -- in fp32 storage the exact sum, in bf16 s
 input row must reach exactly the outputs a rule connects it to (the rules-only property: padding entries of the tile,
 wide, pair-list and table formats never leak a row).  The C ABI is called directly (reference: SCN/CPU/Convolution.cpp:
 46-185, Deconvolution.cpp:7-77 through the oracle's rule books); every case asserts the kernel instance that ran, and the
-last test checks that the names seen cover the launch tables of csrc/conv.hip and csrc/conv_wide.hip."""
+last test checks that the names seen cover the launch tables of csrc/conv.hip, csrc/conv_dw.hip and csrc/conv_wide.hip."""
 import numpy as np
 import pytest
 import torch
 
 import _hip
+import conv_dw_rule as RD
 import conv_exact as E
 import conv_tiles_rule as R
 import conv_wide_rule as RW
@@ -26,6 +27,7 @@ SEEN = set()                        # kernel instances the cases of this file ra
 LARGEST = {}                        # per family: the largest sum |x||w| / granule the precondition saw
 _cache = {}
 TILE_INSTANCES = [k for k in R.compiled_instances() if R.KINDS[k[0]] != "generic"]
+DW_INSTANCES = RD.compiled_instances()
 
 
 def _p(t):
@@ -710,6 +712,54 @@ def test_weight_gradient_is_exact(request, book, n_in, n_out, chunk, form, bf):
     E.assert_bits(db.cpu().numpy(), E.to_f32_exact(rb_), what="d_bias")
 
 
+# planes per side by blocks of 16 (cb / nb): the smallest that select the instance; the scalar bf16 kernel at counts
+# that are no multiple of 32 (the MFMA form is not taken), none a multiple of 128 (nor is the full-tile path)
+DW_PLANES = {("pairs", 0): {1: 16, 2: 32, 4: 64}, ("pairs", 1): {1: 16, 2: 48, 4: 80}, ("pairs_mfma", 1): {2: 32, 4: 64}}
+
+
+def _dw_exact_operands(bk, n_in, n_out):
+    """integer-valued rows and output gradients of one launch with the reference's dW and d_bias (float64), shared by
+    the storage types and instances that use the shape"""
+    k = ("dw", bk.key, n_in, n_out)
+    if k not in _cache:
+        rng = np.random.default_rng(n_in * 7 + n_out + bk.V_out)
+        x, g = E.rows(rng, bk.rows_in, n_in), E.rows(rng, bk.V_out, n_out)
+        largest = E.require_exact_weight_grad(x, g, bk.rb, bk.in_col)
+        _cache[k] = (x, g, largest) + E.ref_weight_grad(x, g, bk.rb, bk.in_col)
+    return _cache[k]
+
+
+@pytest.mark.parametrize("inst", [RD.name(k) for k in DW_INSTANCES])
+def test_weight_gradient_instance_is_exact(request, inst):
+    """every row of the instance tables of csrc/conv_dw.hip through the C ABI with d_bias: the 64 x 64-block kernels
+    direct (129 sites: V <= 256, the kernel writes dW) and chunked + reduce (1500 sites: V > 1024), the full-tile
+    kernels at 128 -> 128 planes on the 1500-site book (DW_FULL_MIN = 8); the name reported is the row's, dW and d_bias
+    are the reference's bits"""
+    key = next(k for k in DW_INSTANCES if RD.name(k) == inst)
+    kind, bf = RD.KINDS[key[0]], bool(key[1])
+    knobs = {}
+    if kind == "full":
+        knobs = {"DW_FULL_MIN": 8}
+        launches = [("1500", 128, 128, "ranges")]
+    else:
+        planes = DW_PLANES[(kind, key[1])]
+        launches = [(book, planes[key[2]], planes[key[3]], reduce) for book, reduce in (("129", "none"), ("1500", "chunks"))]
+    _knobs(request, **knobs)
+    dt = torch.bfloat16 if bf else torch.float32
+    for book, n_in, n_out, reduce in launches:
+        bk = _dw_book(book)
+        x, g, largest, rW, rb_ = _dw_exact_operands(bk, n_in, n_out)
+        _note("weight gradient", largest)
+        dW, db, cp = _run_dw(bk, _t(E.f32(x), dt), _t(E.f32(g), dt), bf)
+        _ran(expect=inst)
+        mc = (bk.vol * bk.V_out + cp - 1) // cp + bk.vol
+        want = RD.decide(bf, n_in, n_out, bk.V_out, bk.vol, mc, True, tuple(knobs.get(k, RD.UNSET) for k in RD.KNOBS))
+        assert want[:4] == key and RD.REDUCES[want[9]] == reduce and want[4] == cp, (want, key, reduce, cp)
+        what = "%s %s %d->%d V %d" % (inst, reduce, n_in, n_out, bk.V_out)
+        E.assert_bits(dW.cpu().numpy(), E.to_f32_exact(rW), what="dW " + what)
+        E.assert_bits(db.cpu().numpy(), E.to_f32_exact(rb_), what="d_bias " + what)
+
+
 @pytest.mark.parametrize("bf", [False, True])
 @pytest.mark.parametrize("book,n_in,n_out", [("129", 64, 64), ("700", 64, 64), ("1500", 128, 128), ("1500", 64, 128)])
 def test_weight_gradient_rules_only(request, book, n_in, n_out, bf):
@@ -882,14 +932,14 @@ def test_layers_are_exact_under_default_dispatch(dt, n_in, n_out):
 # ---------------------------------------------------------------------------------------------------------- coverage
 def test_zz_the_names_seen_cover_the_launch_tables():
     """reads only what the cases above collected (it runs last in this file): every 64-row-tile instance but the generic
-    one, every k_conv_cs instance and split launch, the narrow forms, the single-rule kernel, both weight-gradient kinds"""
+    one, every k_conv_cs instance and split launch, the narrow forms, the single-rule kernel, every weight-gradient instance"""
     want = {R.name(k) for k in TILE_INSTANCES}
     want |= {RW.name(k) for k in RW.compiled_instances()} | {RW.name(k, True) for k in RW.split_instances()}
     want |= {"k_conv_narrow<bf16>", "k_conv_narrow<bf16,stats>", "k_conv_narrow<bf16,bwd_stats>", "k_conv_single<1>",
-             "k_conv_single<2>", "k_conv_single<3>", "k_conv_single<4>", "k_conv_dw_full_f32", "k_conv_dw_full_bf16"}
+             "k_conv_single<2>", "k_conv_single<3>", "k_conv_single<4>"}
+    want |= {RD.name(k) for k in DW_INSTANCES}
     print("largest sum |x||w| / granule per family:",
           {k: "2^%.2f" % np.log2(v) for k, v in sorted(LARGEST.items()) if v > 0})
     missing = sorted(want - SEEN)
     assert not missing, missing
-    assert any(v.startswith("k_conv_dw_pairs<") for v in SEEN) and any(v.startswith("k_conv_dw_pairs_bf16<") for v in SEEN)
     assert any(v.startswith("k_conv_narrow<") and "bf16" not in v for v in SEEN)
