@@ -18,6 +18,7 @@ ABI_VERSION = 640      # include/aabr_hip.h AABR_ABI_VERSION this binding (_SIGS
 _vp, _i64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 _i32p = C.POINTER(C.c_int32)
 _f32p = C.POINTER(C.c_float)
+_i64p = C.POINTER(C.c_int64)
 
 
 
@@ -234,6 +235,10 @@ _SIGS = {
     "aabr_rpn_head_scratch_floats": (C.c_int64, [_i64, _i32, _i32]),
     "aabr_rpn_head_forward": (C.c_int, [_rmp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aabr_rpn_head_backward": (C.c_int, [_rmp, _i32, _i32, _i32] + [_vp] * 12),
+    "aabr_sgd_chunk_elems": (C.c_int, []),
+    "aabr_sgd_chunk_table": (C.c_int64, [_i64p, _i64p, _i32p, _i64, _i64, _i64p, _i64]),
+    "aabr_sgd_momentum_step": (C.c_int, [_vp, _vp, _i64, _vp, _i64p, _i64, _i64, _vp, _vp, _i32, _f32p, _f32p, _i32, _f32,
+                                         _f32, _vp]),
 }
 MLP_ROWS, MLP_POOLED = 0, 1     # include/aabr_hip.h AABR_MLP_ROWS / AABR_MLP_POOLED
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))

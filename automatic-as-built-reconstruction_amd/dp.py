@@ -28,6 +28,17 @@ class FlatParams(object):
         params = []
         for m in modules:
             params += [p for p in m.parameters() if p.requires_grad]
+        self._adopt(params, grad_dtype)
+
+    @classmethod
+    def from_params(cls, params, grad_dtype=None):
+        """the same object over an explicit list of parameters, in the order given (solver_glue.FusedSGD builds its
+        flat buffer from an optimizer's parameter groups this way)"""
+        self = cls.__new__(cls)
+        self._adopt(list(params), grad_dtype)
+        return self
+
+    def _adopt(self, params, grad_dtype):
         self.params = params
         n = sum(p.numel() for p in params)
         dev, dt = params[0].device, params[0].dtype
@@ -79,9 +90,15 @@ class FlatParams(object):
         self._pending = dist.all_reduce(self.msg if self.msg is not None else self.flat_grad, op=dist.ReduceOp.SUM,
                                         group=group, async_op=True)
 
-    def finish_update(self, lr, world_size):
+    def finish_update(self, lr, world_size, optimizer=None):
         """wait (stream-ordered for nccl) for the pending all-reduce and apply the SGD update with the mean
-        gradient; no-op when nothing is pending"""
+        gradient; no-op when nothing is pending.
+
+        optimizer (a solver_glue.FusedSGD over these parameters): the update is `optimizer.step(...)` instead -- momentum,
+        weight decay and the learning rates of the optimizer's parameter groups; `lr` is then IGNORED.  The summed message
+        is read where the collective left it (the bf16 message in place, no widening copy) and the mean's 1 / world_size
+        goes in as the step's grad_scale.  The bucketed path (`finish_bucketed`) takes no optimizer: its gradients live
+        in per-bucket buffers, not in one buffer of the flat layout."""
         work = getattr(self, "_pending", None)
         if work is None:
             return False
@@ -91,14 +108,27 @@ class FlatParams(object):
         self.wait_ms.append((time.perf_counter() - t0) * 1e3)
         del self.wait_ms[:-512]
         self._pending = None
+        if optimizer is not None:
+            optimizer.step(flat_grad=self.msg if self.msg is not None else self.flat_grad, grad_scale=1.0 / world_size)
+            return True
         if self.msg is not None:
             self.flat_grad.copy_(self.msg)
         self.flat.add_(self.flat_grad, alpha=-lr / world_size)
         return True
 
-    def sgd_step(self, lr, world_size=1):
+    def sgd_step(self, lr, world_size=1, optimizer=None):
         """fused SGD update.  With one rank the gradients are consumed where autograd left them (one
-        multi-tensor launch, no packing); with several ranks the all-reduced flat buffer is used."""
+        multi-tensor launch, no packing); with several ranks the all-reduced flat buffer is used.
+
+        optimizer (a solver_glue.FusedSGD over these parameters): the update is `optimizer.step(...)` on the same
+        gradients -- one library launch with momentum, weight decay and the optimizer's per-group learning rates; `lr`
+        is then IGNORED."""
+        if optimizer is not None:
+            if world_size > 1:
+                optimizer.step(flat_grad=self.flat_grad)      # allreduce_mean left the mean there
+            else:
+                optimizer.step()
+            return
         if world_size > 1:
             self.flat.add_(self.flat_grad, alpha=-lr)
         else:

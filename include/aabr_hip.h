@@ -1217,6 +1217,39 @@ int aabr_rpn_head_backward(const AabrRpnMap *maps_host, int n_maps, int C, int A
                            const float *Wr, const float *hidden, float *dW1, float *db1, float *dWc, float *dbc,
                            float *dWr, float *dbr, float *scratch, void *stream);
 
+/* ---- the optimizer step (csrc/solver.hip, csrc/solver_segs.h): torch.optim.SGD with momentum and weight decay
+ * (dampening 0, no Nesterov form) over all parameters of one flat fp32 buffer in ONE launch.  Per element, fp32, each
+ * operation rounded on its own, in this order:
+ *   g  = widen(grad);  g = g * grad_scale  only when grad_scale != 1
+ *   d  = g + wd * p                        only when wd != 0 (else d = g)
+ *   m' = momentum * m + d                  only when momentum != 0 (else momentum_buf is neither read nor written)
+ *   p' = p - lr * m'
+ * A parameter is a segment (flat offset, numel, group) of `flat`; a group is one (lr, weight_decay) pair, at most 8.
+ * aabr_sgd_chunk_elems(): the most elements of a chunk.  Segments are cut into chunks of at most that many elements;
+ *   every cut inside a segment lies on a multiple of 4 elements of the flat offset; a segment of 0 elements has no chunk.
+ * aabr_sgd_chunk_table: host only.  Cuts the segments (ascending, non-overlapping, inside [0, n)) and writes one record
+ *   of 4 int64 words per chunk -- flat offset, the segment's flat offset, elements, segment index * 8 + group -- to
+ *   table_host [cap_chunks][4]; table_host NULL: counts only.  Returns the number of chunks, or -1 (aabr_last_error).
+ *   The caller uploads the table once and keeps the host copy.
+ * aabr_sgd_momentum_step: min(n_chunks, 2048) workgroups of 256 threads grid-stride over chunk_table (device).  flat and
+ *   momentum_buf: fp32 [n], 16-byte aligned, the same layout.  Exactly one gradient source:
+ *     grad_flat       a device buffer [n] of the flat layout, fp32 or (grad_is_bf16 = 1) bf16, read in place;
+ *     grad_ptr_table  a device table [n_segs] of 64-bit gradient addresses, one contiguous gradient per segment; a
+ *                     segment whose address is 0 is skipped (p and m stay bit for bit).
+ *   A gradient whose address does not allow 4-element loads at a chunk is read element by element; p and m are always
+ *   accessed 16 bytes at a time between a segment's first and last multiple of 4.
+ *   lr, wd: host arrays of n_groups values, passed to the kernel by value (a new learning rate is no device write).
+ *   chunk_table_host: the host copy of the uploaded table; its last record is checked against n and n_segs.
+ *   Refused with AABR_EINVAL before any launch: both gradient sources or neither, n_groups outside 1 .. 8, a null
+ *   pointer, a negative size, a misaligned buffer, a table whose last chunk ends past n.  n_chunks == 0: no launch.   */
+int aabr_sgd_chunk_elems(void);
+int64_t aabr_sgd_chunk_table(const int64_t *seg_off, const int64_t *seg_numel, const int32_t *seg_group, int64_t n_segs,
+                             int64_t n, int64_t *table_host, int64_t cap_chunks);
+int aabr_sgd_momentum_step(float *flat, float *momentum_buf, int64_t n, const int64_t *chunk_table,
+                           const int64_t *chunk_table_host, int64_t n_chunks, int64_t n_segs, const void *grad_flat,
+                           const void *grad_ptr_table, int grad_is_bf16, const float *lr, const float *wd, int n_groups,
+                           float momentum, float grad_scale, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
