@@ -351,6 +351,10 @@ __device__ __forceinline__ float rpn_list_logit(const RpnGatherParams &p, int b,
 // evaluated twice -- PASS 0 reduces the row maxima (wave max -> LDS -> one device atomicMax per row and workgroup, on
 // order-preserving integer keys: max is order-independent, the result is bit-reproducible), PASS 1 re-evaluates the
 // same pairs with the same instructions and labels the anchors.
+// A NaN entry (0 / 0 in the z factor when only_xy is off: two zero heights at one z with no thickness clamp; or a
+// non-finite ground-truth box) behaves as in the reference's torch.max calls: it is the best value of its anchor, the
+// first one by index, matched_val is NaN and -- both threshold comparisons being false -- the anchor is matched to that
+// box; it makes its ground truth's row maximum NaN, with which nothing ties and near which nothing lies.
 struct RpnLabelParams {
   AnchorSegs s;
   AnchorGeom g;
@@ -441,7 +445,8 @@ __global__ __launch_bounds__(256) void k_rpn_label_maps(RpnLabelParams p, const 
       float raw;
       const float v = label_pair(p, t5, s_tz[g][0], s_tz[g][1], a5, az0, az1, &raw);
       if (PASS == 0) {
-        uint32_t k = t < N ? float_order_key(v) : 0u;
+        // a NaN entry makes the row maximum NaN, as in torch.max(dim=1): the topmost key whatever the NaN's sign bit
+        uint32_t k = t < N ? (v != v ? 0xffffffffu : float_order_key(v)) : 0u;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
           const uint32_t q = (uint32_t)__shfl_xor((int)k, o, 64);
@@ -450,7 +455,9 @@ __global__ __launch_bounds__(256) void k_rpn_label_maps(RpnLabelParams p, const 
         if ((threadIdx.x & 63) == 0) atomicMax(&s_key[g], k);
       } else if (t < N) {
         if (iou_out) iou_out[p.iou_begin[b] + (int64_t)(g0 + g) * N + t] = raw;
-        if (v > best) { best = v; best_g = g0 + g; }   // first maximum, like torch.max(dim=0) on the host
+        // torch.max(dim=0) on the host, the order k_roi_match keeps too (roi_loss.hip roi_better): a NaN first, then
+        // the larger value, the lower index among equals
+        if (v != v ? best == best : v > best) { best = v; best_g = g0 + g; }
         if (p.allow_low) {
           tie = tie || (v == s_hi[g][0]);              // matcher.py:126-128 (== : -0 ties with +0, as in torch)
           near = near || (v > s_hi[g][1]);             // :168

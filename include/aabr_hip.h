@@ -804,7 +804,10 @@ int aabr_boxes_iou_3d(const float *targets, int64_t M, const float *anchors, int
  * matched_val = best masked value over the ground truths, matched_idx = its index (first maximum), or -1 below
  * bg_iou / -2 below fg_iou; with allow_low_quality_matches != 0 (the RPN's setting) set_low_quality_matches_
  * follows: an anchor that ties with the row maximum of any ground truth gets its best index back, and an anchor
- * still at -1 with an entry above max(0.02, row maximum - 0.05) of any ground truth becomes -2.  All -1 for an
+ * still at -1 with an entry above max(0.02, row maximum - 0.05) of any ground truth becomes -2.  A NaN entry (0 / 0 in
+ * the z factor with only_xy off, or a non-finite box) behaves as in torch.max: it is its anchor's best value, the first
+ * one by index, matched_val is NaN and the anchor is matched to that box; its ground truth's row maximum is NaN, which
+ * ties with nothing.  All -1 for an
  * example without ground truth.  Outputs are concatenated over the examples in order (sum_b N_b entries); iou_out
  * (optional, may be NULL) receives the UNMASKED [G_b, N_b] IoU matrices back to back.  target_ptrs[b] = device
  * [G_b, 7] yx_zb boxes; aug_host[4] = {target_Y, target_Z, anchor_Y, anchor_Z}; row_max_scratch = device words,
