@@ -131,6 +131,7 @@ _SIGS = {
     "aabr_conv_dw_scratch_floats": (C.c_int64, [_i64, _i32, _i32]),
     "aabr_conv_backward_weight": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
     "aabr_conv_dw_chunk_pairs": (C.c_int, [_i64, _i32, _i32, _i32]),
+    "aabr_conv_dw_vec_operands": (C.c_int, [_i32, _vp, _i32, _vp, _i32, _i64, _i32, _i64]),
     "aabr_conv_pack_weights2": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "aabr_conv_pack_weights2_bf16": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "aabr_plan_run": (C.c_int, [_vp, _i32, _vp]),

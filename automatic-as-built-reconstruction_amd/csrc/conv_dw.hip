@@ -20,12 +20,35 @@ extern thread_local const char *g_last_variant; // conv.hip
 __device__ inline float ldf(const float *p, int64_t i) { return p[i]; }
 __device__ inline float ldf(const __bf16 *p, int64_t i) { return (float)p[i]; }
 
+// Form of the launch (bits 1 and 2 of `form`, bit 0 = direct; dw_vec_operands in conv_dw_tiles.h, fp32 storage only): an
+// operand in the VECTOR form has lane (g, c16) load its CB (NB) consecutive channels CB c16 + a with one dwordx4 / dwordx2
+// instead of one dword per 16-channel block -- a quarter of the load instructions through the vector L1, whole 256-byte
+// row slices per instruction -- and block a then holds the channels {CB i + a}; the sums and their order are the same,
+// the write-out maps the accumulators back (dw_tile_row / dw_tile_col).  Bit 3: a lane's four columns of a row are
+// contiguous and 16-byte aligned in the destination, one 16-byte store.  The form is chosen once per launch, outside the
+// pair loop: one copy of the loop per combination the instance can meet.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+template <int N> __device__ inline void ld_row(float (&d)[N], const float *p) {
+  if constexpr (N == 4) {
+    const f32x4 v = *reinterpret_cast<const f32x4 *>(p);
+    d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
+  } else if constexpr (N == 2) {
+    const f32x2 v = *reinterpret_cast<const f32x2 *>(p);
+    d[0] = v[0]; d[1] = v[1];
+  } else d[0] = p[0];
+}
+template <int N> __device__ inline void ld_row(__bf16 (&)[N], const __bf16 *) {}   // (never called: bf16 keeps the scalar form)
+template <bool V> struct DwForm { static constexpr bool value = V; };
+
 template <int CB, int NB, typename T>
-__global__ __launch_bounds__(256) void k_conv_dw_pairs(const T *__restrict__ in, int ci,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k_conv_dw_pairs(const T *__restrict__ in, int ci,
                                                        const T *__restrict__ d_out, int co, int64_t V,
                                                        const int32_t *__restrict__ words, int vol,
-                                                       int chunk_pairs, float *__restrict__ partial, int direct) {
+                                                       int chunk_pairs, float *__restrict__ partial, int form) {
   __shared__ f32x4 red[CB * NB][64];
+  constexpr bool kF32 = sizeof(T) == 4;
+  const int direct = form & 1;
+  const bool vin = kF32 && CB > 1 && (form & (kDwVecIn << 1)), vout = kF32 && NB > 1 && (form & (kDwVecOut << 1));
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int g = lane >> 4, c16 = lane & 15;
   const int nnb = nnb_of(co);
@@ -56,35 +79,43 @@ __global__ __launch_bounds__(256) void k_conv_dw_pairs(const T *__restrict__ in,
   for (int a = 0; a < CB; ++a) { int c = (cb0 + a) * 16 + c16; ca[a] = c < ci ? c : cA; }
 #pragma unroll
   for (int b = 0; b < NB; ++b) { int n = (nb0 + b) * 16 + c16; na[b] = n < co ? n : nA; }
-  auto gather = [&](T (&av)[4][CB], T (&bv)[4][NB], int2 pr, int q0) {
+  const int cv = cb0 * 16 + CB * c16, nv = nb0 * 16 + NB * c16;   // vector form: the lane's first channel (every tile full)
+  auto run = [&](auto va_, auto vb_) {
+    constexpr bool VA = decltype(va_)::value, VB = decltype(vb_)::value;
+    auto gather = [&](T (&av)[4][CB], T (&bv)[4][NB], int2 pr, int q0) {
 #pragma unroll
-    for (int st = 0; st < 4; ++st) {
-      const int src = q0 + st * 4 + g;
-      int tq = __shfl(pr.x, src), oq = __shfl(pr.y, src);
-      tq = tq < 0 ? 0 : tq; oq = oq < 0 ? 0 : oq;
+      for (int st = 0; st < 4; ++st) {
+        const int src = q0 + st * 4 + g;
+        int tq = __shfl(pr.x, src), oq = __shfl(pr.y, src);
+        tq = tq < 0 ? 0 : tq; oq = oq < 0 ? 0 : oq;
+        if constexpr (VA) ld_row<CB>(av[st], in + (int64_t)tq * ci + cv);
+        else {
 #pragma unroll
-      for (int a = 0; a < CB; ++a) av[st][a] = in[(int64_t)tq * ci + ca[a]];
+          for (int a = 0; a < CB; ++a) av[st][a] = in[(int64_t)tq * ci + ca[a]];
+        }
+        if constexpr (VB) ld_row<NB>(bv[st], d_out + (int64_t)oq * co + nv);
+        else {
 #pragma unroll
-      for (int b = 0; b < NB; ++b) bv[st][b] = d_out[(int64_t)oq * co + na[b]];
-    }
-  };
-  auto mfmas = [&](T (&av)[4][CB], T (&bv)[4][NB], int qbase) {
+          for (int b = 0; b < NB; ++b) bv[st][b] = d_out[(int64_t)oq * co + na[b]];
+        }
+      }
+    };
+    auto mfmas = [&](T (&av)[4][CB], T (&bv)[4][NB], int qbase) {
 #pragma unroll
-    for (int st = 0; st < 4; ++st) {
-      const bool on = qbase + st * 4 + g < p1;
-      float fa[CB], fb[NB];
+      for (int st = 0; st < 4; ++st) {
+        const bool on = qbase + st * 4 + g < p1;
+        float fa[CB], fb[NB];
 #pragma unroll
-      for (int a = 0; a < CB; ++a) fa[a] = (on && (cb0 + a) * 16 + c16 < ci) ? (float)av[st][a] : 0.0f;
+        for (int a = 0; a < CB; ++a) fa[a] = (on && (VA || (cb0 + a) * 16 + c16 < ci)) ? (float)av[st][a] : 0.0f;
 #pragma unroll
-      for (int b = 0; b < NB; ++b) fb[b] = (on && (nb0 + b) * 16 + c16 < co) ? (float)bv[st][b] : 0.0f;
+        for (int b = 0; b < NB; ++b) fb[b] = (on && (VB || (nb0 + b) * 16 + c16 < co)) ? (float)bv[st][b] : 0.0f;
 #pragma unroll
-      for (int a = 0; a < CB; ++a)
+        for (int a = 0; a < CB; ++a)
 #pragma unroll
-        for (int b = 0; b < NB; ++b)
-          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[a], fb[b], acc[a][b], 0, 0, 0);
-    }
-  };
-  if (p0 < p1) {
+          for (int b = 0; b < NB; ++b)
+            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[a], fb[b], acc[a][b], 0, 0, 0);
+      }
+    };
     T avA[4][CB], bvA[4][NB], avB[4][CB], bvB[4][NB];
     const int last = rk - 1;                                 // rk >= 1 here
     auto load_pr = [&](int q64) {
@@ -114,6 +145,20 @@ __global__ __launch_bounds__(256) void k_conv_dw_pairs(const T *__restrict__ in,
       mfmas(avB, bvB, q64 + 48);
       pr = prn;
     }
+  };
+  if (p0 < p1) {                                             // (wave-uniform, and so is the form)
+    if constexpr (kF32 && CB > 1 && NB > 1) {
+      if (vin && vout) run(DwForm<true>{}, DwForm<true>{});
+      else if (vin) run(DwForm<true>{}, DwForm<false>{});
+      else if (vout) run(DwForm<false>{}, DwForm<true>{});
+      else run(DwForm<false>{}, DwForm<false>{});
+    } else if constexpr (kF32 && CB > 1) {
+      if (vin) run(DwForm<true>{}, DwForm<false>{});
+      else run(DwForm<false>{}, DwForm<false>{});
+    } else if constexpr (kF32 && NB > 1) {
+      if (vout) run(DwForm<false>{}, DwForm<true>{});
+      else run(DwForm<false>{}, DwForm<false>{});
+    } else run(DwForm<false>{}, DwForm<false>{});
   }
   // sum the four waves' accumulators in wave order: w0 + w1 + w2 + w3
   for (int w = 0; w < 4; ++w) {
@@ -133,8 +178,24 @@ __global__ __launch_bounds__(256) void k_conv_dw_pairs(const T *__restrict__ in,
     __syncthreads();
   }
   if (wave != 0) return;
-  // D[i = c (row of dW) = g*4 + r][j = n = c16]
+  // D[i = 4 g + r][j = c16] of block (a, b) is row dw_tile_row, column dw_tile_col of the tile
   float *P = partial + (int64_t)(direct ? k : chunk) * ci * co;
+  if constexpr (kF32 && NB == 4) {
+    if (form & 8) {                                          // (vout holds: the lane's columns nv .. nv + 3, all below co)
+#pragma unroll
+      for (int a = 0; a < CB; ++a) {
+        f32x4 t[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) t[b] = red[a * 4 + b][lane];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int c = cb0 * 16 + dw_tile_row(vin, CB, g, r, a);
+          if (c < ci) *reinterpret_cast<f32x4 *>(P + (int64_t)c * co + nv) = (f32x4){t[0][r], t[1][r], t[2][r], t[3][r]};
+        }
+      }
+      return;
+    }
+  }
 #pragma unroll
   for (int a = 0; a < CB; ++a)
 #pragma unroll
@@ -142,7 +203,7 @@ __global__ __launch_bounds__(256) void k_conv_dw_pairs(const T *__restrict__ in,
       f32x4 t = red[a * NB + b][lane];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        int c = (cb0 + a) * 16 + g * 4 + r, n = (nb0 + b) * 16 + c16;
+        int c = cb0 * 16 + dw_tile_row(vin, CB, g, r, a), n = nb0 * 16 + dw_tile_col(vout, NB, c16, b);
         if (c < ci && n < co) P[(int64_t)c * co + n] = t[r];
       }
     }
@@ -680,6 +741,25 @@ static const DwInst<Fn> *dw_inst(const DwInst<Fn> (&tab)[N], const DwKernel &k) 
   return nullptr;
 }
 
+// the `form` argument of k_conv_dw_pairs: bit 0 direct, bits 1-2 the vector-loaded operands (fp32 instances of that
+// kernel only), bit 3 16-byte stores (four column blocks in the vector form, destination aligned)
+static int dw_pairs_form(const DwLaunch &d, int n_in, int n_out, const void *in_feats, const void *d_out, const float *dst) {
+  const int vec = d.k.kind == kDwPairs ? dw_vec_operands(d.k.bf16, n_in, n_out, d.k.cb, d.k.nb, (uintptr_t)in_feats,
+                                                          (uintptr_t)d_out, knob(K_DW_VEC)) : 0;
+  const int st16 = (vec & kDwVecOut) && d.k.nb == 4 && ((uintptr_t)dst & 15) == 0;
+  return d.direct | vec << 1 | st16 << 3;
+}
+
+extern "C" int aabr_conv_dw_vec_operands(int bf16, const void *in_feats, int n_in, const void *d_out, int n_out,
+                                         int64_t V_out, int vol, int64_t max_chunks) {
+  if (n_in <= 0 || n_out <= 0 || vol <= 0 || V_out <= 0 || max_chunks <= 0) return 0;
+  const bool bf = bf16 != 0, aligned16 = ((uintptr_t)in_feats & 15) == 0 && ((uintptr_t)d_out & 15) == 0;
+  const DwLaunch d = conv_dw_launch(bf, n_in, n_out, V_out, vol, max_chunks, aligned16,
+                                    DwKnobs{knob(K_DW_FULL), knob(K_DW_FULL_MIN), knob(K_DW_FULL_WGS)});
+  return d.k.kind == kDwPairs ? dw_vec_operands(bf, n_in, n_out, d.k.cb, d.k.nb, (uintptr_t)in_feats, (uintptr_t)d_out,
+                                                knob(K_DW_VEC)) : 0;
+}
+
 extern "C" int64_t aabr_conv_dw_scratch_floats(int64_t max_chunks, int n_in, int n_out) {
   return max_chunks * n_in * n_out;
 }
@@ -719,7 +799,7 @@ static int conv_backward_weight_t(const T *in_feats, int n_in, const T *d_out, i
     AABR_CHECK_ARG(e, "no kernel instance for this launch");
     g_last_variant = e->name;
     hipLaunchKernelGGL(e->fn, grid, dim3(256), 0, st, in_feats, n_in, d_out, n_out, V_out, pairs, vol, d.chunk_pairs, dst,
-                       d.direct);
+                       dw_pairs_form(d, n_in, n_out, in_feats, d_out, dst));
   }
   const dim3 rgrid((unsigned)ceil_div(cico, 64), (unsigned)vol);
   if (d.reduce == kDwReduceRanges)

@@ -83,6 +83,30 @@ inline void dw_tiling(int ci, int co, int &cb, int &nb, int &tiles) {
   tiles = (int)(ceil_div(ncb, cb) * ceil_div(nnb, nb));
 }
 
+// ---- k_conv_dw_pairs<cb, nb, float>: which operand rows are gathered with one load per lane ------------------------------
+// The MFMA's row index is only a name for a channel.  Scalar form: lane (g, c16) loads channel 16 a + c16 of block a, one
+// dword per block -- a 64-channel row slice is four load instructions of half a cache line per row each.  Vector form:
+// the lane loads the cb CONSECUTIVE channels cb c16 + a, a = 0 .. cb-1, in one instruction (dwordx4 / dwordx2) and register
+// a is block a's operand as before, so block a holds the channels {cb i + a} instead of {16 a + i}.  Every element of dW
+// is still the sum over the same pairs in the same wave, step and k-slot of the same MFMA chain: bit-identical, only the
+// accumulator that holds it differs, and the write-out maps back.  The same for the output gradients with nb.
+// An operand is vector-loaded when every tile is full (planes a multiple of 16 cb: no channel masks) and its pointer is
+// aligned to the load (4 cb bytes); fp32 storage only; cb = 1 is the scalar form by construction.
+enum { kDwVecIn = 1, kDwVecOut = 2 };
+// align_in / align_dout: the pointers' addresses (or their low four bits).  knob_vec: DW_VEC (0: scalar form everywhere)
+inline int dw_vec_operands(bool bf16, int n_in, int n_out, int cb, int nb, uint64_t align_in, uint64_t align_dout,
+                           int knob_vec = kKnobUnset) {
+  if (bf16 || knob_vec == 0) return 0;
+  int m = 0;
+  if (cb > 1 && n_in % (16 * cb) == 0 && align_in % (4 * cb) == 0) m |= kDwVecIn;
+  if (nb > 1 && n_out % (16 * nb) == 0 && align_dout % (4 * nb) == 0) m |= kDwVecOut;
+  return m;
+}
+// Channel (row of dW / column of dW) inside the workgroup's tile of 16 cb x 16 nb that accumulator register r of block
+// (a, b) holds in lane (g, c16): the MFMA's D[i = 4 g + r][j = c16].
+AABR_HD int dw_tile_row(bool vec, int cb, int g, int r, int a) { return vec ? cb * (4 * g + r) + a : 16 * a + 4 * g + r; }
+AABR_HD int dw_tile_col(bool vec, int nb, int c16, int b) { return vec ? nb * c16 + b : 16 * b + c16; }
+
 // aligned16: both feature pointers (input features, output gradients) are 16-byte aligned.  V_out > 0, max_chunks > 0.
 inline DwLaunch conv_dw_launch(bool bf16, int n_in, int n_out, int64_t V_out, int vol, int64_t max_chunks, bool aligned16,
                                const DwKnobs &kn) {

@@ -454,6 +454,11 @@ int aabr_conv_pack_weights_jobs(const void *jobs_dev, int n_jobs, int64_t total_
  * CUDA/Convolution.cu:249-441,526-667).                                                     */
 int64_t aabr_conv_dw_scratch_floats(int64_t max_chunks, int n_in, int n_out);
 int aabr_conv_dw_chunk_pairs(int64_t V_out, int vol, int n_in, int n_out); /* 256 or 1024 */
+/* Which operands' rows a launch with these arguments gathers with one 16- / 8-byte load per lane (fp32 storage, the
+ * 64 x 64-block kernel; csrc/conv_dw_tiles.h dw_vec_operands): bit 0 the input features, bit 1 the output gradients; 0
+ * for every other kernel and under the knob DW_VEC = 0.  The result of the launch does not depend on it.            */
+int aabr_conv_dw_vec_operands(int bf16, const void *in_feats, int n_in, const void *d_out, int n_out, int64_t V_out,
+                              int vol, int64_t max_chunks);
 int aabr_conv_backward_weight(const float *in_feats, int n_in, const float *d_out, int n_out,
                               int64_t V_out, const int32_t *pairs, int vol, int64_t max_chunks,
                               float *dW, float *d_bias, float *scratch, void *stream);
