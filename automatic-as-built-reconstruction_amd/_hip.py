@@ -240,6 +240,11 @@ _SIGS = {
     "aabr_sgd_chunk_table": (C.c_int64, [_i64p, _i64p, _i32p, _i64, _i64, _i64p, _i64]),
     "aabr_sgd_momentum_step": (C.c_int, [_vp, _vp, _i64, _vp, _i64p, _i64, _i64, _vp, _vp, _i32, _f32p, _f32p, _i32, _f32,
                                          _f32, _vp]),
+    "aabr_det_eval_scratch_words": (C.c_int64, [_i64, _i64]),
+    "aabr_det_eval_match": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _f32, _f32p, _i32,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aabr_det_eval_curves": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "aabr_det_eval_scan_chunk": (C.c_int, []),
 }
 MLP_ROWS, MLP_POOLED = 0, 1     # include/aabr_hip.h AABR_MLP_ROWS / AABR_MLP_POOLED
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))

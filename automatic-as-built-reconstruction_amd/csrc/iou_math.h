@@ -268,4 +268,12 @@ AABR_HD float iou_eval_entry(const float *box_n, const float *query_k, int crite
   return same_box(box_n, query_k) ? 1.0f : rotate_iou(query_k, box_n, criterion);
 }
 
+// The order in which the matching loops (roi_loss.hip k_roi_match, det_eval.hip k_eval_match) pick one ground-truth box
+// out of many: is the candidate (ov, og) ahead of (v, g) in "NaN first, then larger value; lower index among equals"?
+// Folding candidates with it in any order gives the first maximum by index, a NaN entry winning, as np.argmax does.
+AABR_HD bool roi_better(float ov, int og, float v, int g) {
+  if (ov != ov) return v == v || og < g;
+  return v == v && (ov > v || (ov == v && og < g));
+}
+
 } // namespace aabr_iou

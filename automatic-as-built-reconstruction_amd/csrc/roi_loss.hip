@@ -53,18 +53,12 @@ struct RoiTargetParams {
 // kRoiLanes adjacent lanes of a wave share one proposal: lane j takes the ground-truth boxes j, j + kRoiLanes, ... of
 // every staged chunk, so the serial chain per lane is ceil(G_b / kRoiLanes) pairs and a workgroup of 256 threads serves
 // 256 / kRoiLanes proposals.  Each lane keeps the first maximum of its own ascending subsequence; the lanes' candidates
-// are then folded with roi_better, which prefers the lower index among equal values, so the result is the first maximum
+// are then folded with roi_better (iou_math.h), which prefers the lower index among equal values, so the result is the first maximum
 // over all G_b whatever the lane count.  A NaN entry (0 / 0 in the z factor when only_xy is off: two zero heights at the
 // same z with no thickness clamp) behaves as in torch.max / np.argmax: it wins, the first one by index, matched_val is
 // NaN and, since both threshold comparisons are false for it, the proposal is matched to that box.
 constexpr int kRoiLanes = 16;
 constexpr int kRoiPropsPerBlock = 256 / kRoiLanes;
-
-// is the candidate (ov, og) ahead of (v, g) in the order "NaN first, then larger value; lower index among equals"?
-__device__ inline bool roi_better(float ov, int og, float v, int g) {
-  if (ov != ov) return v == v || og < g;
-  return v == v && (ov > v || (ov == v && og < g));
-}
 
 __global__ __launch_bounds__(256) void k_roi_match(RoiTargetParams p, const float *__restrict__ proposals,
                                                    const float *__restrict__ targets,

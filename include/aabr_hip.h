@@ -1258,6 +1258,58 @@ int aabr_sgd_momentum_step(float *flat, float *momentum_buf, int64_t n, const in
                            const void *grad_ptr_table, int grad_is_bf16, const float *lr, const float *wd, int n_groups,
                            float momentum, float grad_scale, void *stream);
 
+/* ---- detection evaluation (csrc/det_eval.hip, csrc/det_eval.h): eval_detection_suncg of the reference
+ * (data3d/evaluation/suncg/suncg_eval.py:733-986, use_07_metric=True; the other value is not implemented) for a whole
+ * data set, in two entries with the caller's sort between them.  4 library launches + that sort for a whole evaluation,
+ * whatever the number of scenes, classes and boxes; no host read inside; no float atomics: bit-identical run to run.
+ *
+ * Inputs are scene-major concatenations over n_scenes >= 1 scenes (<= 65535): det_boxes fp32 [n_det, 7] yx_zb,
+ * det_labels int64, det_scores fp32; gt_boxes fp32 [n_gt, 7], gt_labels int64.  det_begin / gt_begin: DEVICE int64
+ * arrays of n_scenes + 1 ascending row offsets (first 0, last n_det / n_gt), which the caller forms from list lengths it
+ * knows on the host; offsets that disagree with the totals are clamped to them.  n_det_max: the largest scene's detection
+ * count (it sizes the grid).  C: classes, background included, 2 <= C <= 32.
+ *
+ * aabr_det_eval_match (3 launches; 1 without ground truth or without detections).  Per detection of scene s, label l:
+ *   IoU with every ground-truth box of the scene whose label is l = boxlist_iou_3d(gt, pred, aug, criterion=-1,
+ *   flag='eval'), the arithmetic of aabr_boxes_iou_3d (aug_host[4] = {target_Y, target_Z, anchor_Y, anchor_Z}, ground
+ *   truth on the target side; only_xy != 0: no z factor, what the reference's DEBUG = 1 forces);
+ *   pred_iou = the maximum, gt_index = the first maximum's index AMONG THE SCENE'S BOXES OF CLASS l (a NaN entry wins,
+ *   the first NaN by index, as np.argmax / np.max: the order of aabr_roi_targets); gt_index = -1 where
+ *   pred_iou < iou_thresh (strict: IoU == iou_thresh matches, a NaN matches); no box of the class in the scene:
+ *   gt_index = -1, pred_iou = 0;
+ *   match = 1 for the first detection in score order among those of the scene that share a gt_index >= 0 and label, 0
+ *   for every other detection.  Score order: descending score (-0.0 == +0.0, NaN scores behind -inf), equal scores by
+ *   ascending detection row.  Implemented as an integer 64-bit minimum over (score key, row), not a sequential loop;
+ *   sort_key int64 [n_det] = (label << 32) | score key, ascending = class-major, descending score.
+ *   A detection label outside [0, C) is skipped (gt_index -1, pred_iou 0, match 0, sort_key of class C: behind every
+ *   class) and a ground-truth label outside [0, C) matches nothing; both are counted in aabr_det_eval_curves' cls.
+ *   iou_out (optional, NULL): fp32 matrices [g_s, n_s] back to back at iou_begin[s] (DEVICE int64 [n_scenes]); only the
+ *   entries of equal label are written.  scratch: aabr_det_eval_scratch_words(n_det, n_gt) int32, 8-byte aligned.
+ * The caller then sorts sort_key ascending with a STABLE sort: sorted_key and `order` (the source row of each position).
+ * aabr_det_eval_curves (1 launch, one workgroup per class, which walks the class's run serially on one CU; a class's
+ * detection count is bounded only by n_det < 2^31 -- addressing, not speed: nothing above a few thousand per class is timed):
+ *   over class l's run of the sorted order, tp = cumsum(match == 1), fp = cumsum(match == 0) as integers,
+ *   rec = tp / n_pos[l], prec = tp / (tp + fp) in float64 (0 / 0 = NaN for a class without ground truth);
+ *   rows fp64 [n_det, 4] = rec, prec, score, pred_iou at every sorted position (rows of skipped labels: not written);
+ *   cls [C][64] 64-bit words per class: doubles 0 = 11-point AP (p / 11 added over t = 0.0 + 0.1 i, i = 0 .. 10),
+ *   1 .. 44 = the 11 rows [t, max nan_to_num(prec) over rec >= t else 0, min score over rec <= t else max score + 0.01,
+ *   max nan_to_num(pred_iou) over rec >= t else 0], 45 .. 46 / 47 .. 48 = prec, rec at k = count(score > 0.5 / 0.7) - 1
+ *   (k = -1: the last position); all NaN for a class without a detection; int64 56 = n_pos, 57 = detections, 58 = tp
+ *   total, 59 = first sorted position; in class 0's row 60 / 61 = ground-truth / detection labels outside [0, C).
+ *   aabr_det_eval_scan_chunk(): detections per pass of the scan (the results do not depend on it).
+ * Refused with AABR_EINVAL before any launch: C outside 2 .. 32, n_scenes outside 1 .. 65535, a negative count, 2^31 or
+ * more rows, n_det_max > n_det, a null pointer, a misaligned scratch.                                                  */
+int64_t aabr_det_eval_scratch_words(int64_t n_det, int64_t n_gt);
+int aabr_det_eval_match(const float *det_boxes, const int64_t *det_labels, const float *det_scores,
+                        const float *gt_boxes, const int64_t *gt_labels, int64_t n_scenes, const int64_t *det_begin,
+                        const int64_t *gt_begin, int64_t n_det, int64_t n_gt, int64_t n_det_max, int C, float iou_thresh,
+                        const float *aug_host, int only_xy, int64_t *gt_index, float *pred_iou, int8_t *match,
+                        int64_t *sort_key, float *iou_out, const int64_t *iou_begin, int32_t *scratch, void *stream);
+int aabr_det_eval_curves(const int64_t *sorted_key, const int64_t *order, const int8_t *match, const float *pred_iou,
+                         const float *det_scores, const int64_t *gt_labels, int64_t n_det, int64_t n_gt, int C,
+                         double *rows, int64_t *cls, void *stream);
+int aabr_det_eval_scan_chunk(void);
+
 #ifdef __cplusplus
 }
 #endif
