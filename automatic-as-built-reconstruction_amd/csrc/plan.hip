@@ -12,6 +12,7 @@
 // Also the two elementwise launches such a plan needs that the layer API gets from torch: residual add and the
 // fp32 <-> bf16 storage casts (round-to-nearest-even, as torch's `.to(torch.bfloat16)`).
 #include "common.h"
+#include "plan_records.h"
 #include "plan_tail.h"
 #include <string.h>
 #include <chrono>
@@ -169,12 +170,12 @@ static int plan_cast_run(const AabrPlanOp *ops, int m, void *st) {
   uint64_t blocks = 0;
   int c = 0;
   for (int j = 0; j < m; ++j) {
-    const AabrPlanOp &o = ops[j];
-    AABR_CHECK_ARG(o.i64[0] >= 0 && (o.i64[0] == 0 || (o.p[0] && o.p[1])), "cast record: bad size / null pointer");
-    if (o.i64[0] == 0) continue;
-    js.in[c] = o.p[0]; js.out[c] = o.p[1]; js.n[c] = o.i64[0];
+    const PlanCast r{ops[j]};
+    AABR_CHECK_ARG(r.n() >= 0 && (r.n() == 0 || (r.in() && r.out())), "cast record: bad size / null pointer");
+    if (r.n() == 0) continue;
+    js.in[c] = r.in(); js.out[c] = r.out(); js.n[c] = r.n();
     js.first[c] = (uint32_t)blocks;
-    blocks += (uint64_t)((o.i64[0] + 1023) / 1024);
+    blocks += (uint64_t)((r.n() + 1023) / 1024);
     ++c;
   }
   AABR_CHECK_ARG(blocks < (1ull << 31), "too many elements");
@@ -189,7 +190,8 @@ static int plan_cast_run(const AabrPlanOp *ops, int m, void *st) {
   return AABR_OK;
 }
 
-// One record = one library call; the field use per kind is listed in include/aabr_hip.h (AabrPlanOp).
+// One record = one library call; the field use per kind is listed in include/aabr_hip.h (AabrPlanOp) and named, slot
+// by slot, in plan_records.h: records are read through its views only.
 static_assert(sizeof(AabrPlanOp) == 176, "AabrPlanOp layout is part of the C ABI");
 
 // Records flagged AABR_PLAN_SIDE run on a second stream of the library's own: they start once everything recorded
@@ -291,158 +293,147 @@ extern "C" int aabr_plan_tail_release(uint64_t ticket) {
 }
 
 // one record = one entry point of include/aabr_hip.h on stream `st`
+namespace {
+// a record's operands in the storage its entry point takes them in: fp32 rows / bf16 rows / index lists / fp64 partial sums
+inline const float *f32(const void *p) { return (const float *)p; }
+inline float *f32(void *p) { return (float *)p; }
+inline const uint16_t *b16(const void *p) { return (const uint16_t *)p; }
+inline uint16_t *b16(void *p) { return (uint16_t *)p; }
+inline const int32_t *idx(const void *p) { return (const int32_t *)p; }
+inline double *f64(void *p) { return (double *)p; }
+} // namespace
+
 static int plan_dispatch(const AabrPlanOp &o, void *st) {
   const bool bf = (o.flags & AABR_PLAN_BF16) != 0;
-  void *const *p = o.p;
-  int rc = AABR_OK;
   switch (o.kind) {
-  case AABR_PLAN_CONV:
-    rc = bf ? aabr_conv_forward_bf16((const uint16_t *)p[0], o.i32[0], o.i64[0], (uint16_t *)p[1], o.i32[1], o.i64[1],
-                                     (const int32_t *)p[2], o.i32[2], (const float *)p[3], (const float *)p[4],
-                                     o.i32[3], (uint16_t *)p[5], st)
-            : aabr_conv_forward((const float *)p[0], o.i32[0], o.i64[0], (float *)p[1], o.i32[1], o.i64[1],
-                                (const int32_t *)p[2], o.i32[2], (const float *)p[3], (const float *)p[4], o.i32[3],
-                                (float *)p[5], st);
-    break;
-  case AABR_PLAN_CONV_WIDE:
-    if (o.i32[5] == 1) { // the write-out forms the BACKWARD statistics of the BatchNorm whose d_out it produces
-      if (bf) {          // p7 the BatchNorm's input, p9 its stored output (the sign), p8 save_mean; p3 = residual or NULL
-        rc = aabr_conv_forward_wide_bf16_res((const uint16_t *)p[0], o.i32[0], o.i64[0], (uint16_t *)p[1], o.i32[1],
-                                             o.i64[1], (const int32_t *)p[2], o.i32[4], o.i32[2], (const float *)p[4],
-                                             o.i32[3], (const uint16_t *)p[5], (const uint16_t *)p[3], (double *)p[6],
-                                             (const uint16_t *)p[7], (const uint16_t *)p[9], (const float *)p[8], o.f32[0],
-                                             st);
-        break;
-      }
-      rc = aabr_conv_forward_wide_bwd_stats((const float *)p[0], o.i32[0], o.i64[0], (float *)p[1], o.i32[1], o.i64[1],
-                                            (const int32_t *)p[2], o.i32[4], o.i32[2], (const float *)p[4], o.i32[3],
-                                            (const float *)p[5], (const float *)p[3], (double *)p[6],
-                                            (const float *)p[7], (const float *)p[8], (const float *)p[9],
-                                            (const float *)p[10], (const float *)p[11], o.f32[0], st);
-      break;
+  case AABR_PLAN_CONV: {
+    const PlanConv r{o};
+    return bf ? aabr_conv_forward_bf16(b16(r.in()), r.n_in(), r.rows_in(), b16(r.out()), r.n_out(), r.V_out(),
+                                       idx(r.gather()), r.vol(), f32(r.weight()), f32(r.bias()), r.conv_flags(),
+                                       b16(r.wpack()), st)
+              : aabr_conv_forward(f32(r.in()), r.n_in(), r.rows_in(), f32(r.out()), r.n_out(), r.V_out(), idx(r.gather()),
+                                  r.vol(), f32(r.weight()), f32(r.bias()), r.conv_flags(), f32(r.wpack()), st);
+  }
+  case AABR_PLAN_CONV_WIDE: {
+    const PlanConv r{o};
+    const bool bs = r.bwd_stats() == 1;   // the write-out forms the BACKWARD statistics of the BatchNorm whose d_out it produces
+    if (bf)
+      return aabr_conv_forward_wide_bf16_res(b16(r.in()), r.n_in(), r.rows_in(), b16(r.out()), r.n_out(), r.V_out(),
+                                             idx(r.gather()), r.tile_rows(), r.vol(), f32(r.bias()), r.conv_flags(),
+                                             b16(r.wpack()), b16(r.residual()), f64(r.stats()),
+                                             bs ? b16(r.bn_in()) : nullptr, bs ? b16(r.bn_out()) : nullptr,
+                                             bs ? f32(r.save_mean()) : nullptr, bs ? r.leak() : 0.0f, st);
+    if (bs)
+      return aabr_conv_forward_wide_bwd_stats(f32(r.in()), r.n_in(), r.rows_in(), f32(r.out()), r.n_out(), r.V_out(),
+                                              idx(r.gather()), r.tile_rows(), r.vol(), f32(r.bias()), r.conv_flags(),
+                                              f32(r.wpack()), f32(r.residual()), f64(r.stats()), f32(r.bn_in()),
+                                              f32(r.save_mean()), f32(r.save_invstd()), f32(r.bn_weight()),
+                                              f32(r.bn_bias()), r.leak(), st);
+    return aabr_conv_forward_wide_stats(f32(r.in()), r.n_in(), r.rows_in(), f32(r.out()), r.n_out(), r.V_out(),
+                                        idx(r.gather()), r.tile_rows(), r.vol(), f32(r.bias()), r.conv_flags(),
+                                        f32(r.wpack()), f32(r.residual()), f64(r.stats()), st);
+  }
+  case AABR_PLAN_CONV_WIDE_SPLIT: {
+    const PlanConv r{o};
+    return bf ? aabr_conv_forward_wide_split_bf16_res(b16(r.in()), r.n_in(), r.rows_in(), b16(r.out()), r.n_out(),
+                                                      r.V_out(), idx(r.gather()), r.tile_rows(), r.vol(), f32(r.bias()),
+                                                      r.conv_flags(), b16(r.wpack()), r.parts(), f32(r.scratch()),
+                                                      b16(r.residual()), st)
+              : aabr_conv_forward_wide_split(f32(r.in()), r.n_in(), r.rows_in(), f32(r.out()), r.n_out(), r.V_out(),
+                                             idx(r.gather()), r.tile_rows(), r.vol(), f32(r.bias()), r.conv_flags(),
+                                             f32(r.wpack()), f32(r.residual()), r.parts(), f32(r.scratch()), st);
+  }
+  case AABR_PLAN_CONV_SINGLE: {
+    const PlanConv r{o};
+    if (bf) { aabr::set_error("aabr_plan_run: the single-rule convolution is fp32 storage only"); return AABR_EINVAL; }
+    if (r.bwd_stats() == 1)   // the write-out forms the backward statistics of the BatchNorm whose d_out it produces
+      return aabr_conv_forward_single_bwd_stats(f32(r.in()), r.n_in(), r.rows_in(), f32(r.out()), r.n_out(), r.V_out(),
+                                                idx(r.gather()), r.vol(), f32(r.bias()), r.conv_flags(), f32(r.wpack()),
+                                                f32(r.residual()), f64(r.stats()), f32(r.bn_in()), f32(r.save_mean()),
+                                                f32(r.save_invstd()), f32(r.bn_weight()), f32(r.bn_bias()), r.leak(), st);
+    return aabr_conv_forward_single(f32(r.in()), r.n_in(), r.rows_in(), f32(r.out()), r.n_out(), r.V_out(),
+                                    idx(r.gather()), r.vol(), f32(r.bias()), r.conv_flags(), f32(r.wpack()),
+                                    f32(r.residual()), st);
+  }
+  case AABR_PLAN_CONV_NARROW: {
+    const PlanConv r{o};
+    if (bf && r.bwd_stats() == 1)
+      return aabr_conv_forward_narrow_bf16_bwd_stats(b16(r.in()), r.rows_in(), b16(r.out()), r.V_out(), idx(r.gather()),
+                                                     r.vol(), f32(r.weight()), f32(r.bias()), r.conv_flags(),
+                                                     f64(r.stats()), b16(r.bn_in()), b16(r.bn_out()), f32(r.save_mean()),
+                                                     r.leak(), st);
+    if (bf && r.stats())
+      return aabr_conv_forward_narrow_bf16_stats(b16(r.in()), r.rows_in(), b16(r.out()), r.V_out(), idx(r.gather()),
+                                                 r.vol(), f32(r.weight()), f32(r.bias()), r.conv_flags(), f64(r.stats()),
+                                                 st);
+    return bf ? aabr_conv_forward_narrow_bf16(b16(r.in()), r.rows_in(), b16(r.out()), r.V_out(), idx(r.gather()), r.vol(),
+                                              f32(r.weight()), f32(r.bias()), r.conv_flags(), st)
+              : aabr_conv_forward_narrow(f32(r.in()), r.rows_in(), f32(r.out()), r.V_out(), idx(r.gather()), r.vol(),
+                                         f32(r.weight()), f32(r.bias()), r.conv_flags(), st);
+  }
+  case AABR_PLAN_CONV_DW: {
+    const PlanConvDw r{o};
+    return bf ? aabr_conv_backward_weight_bf16(b16(r.in()), r.n_in(), b16(r.d_out()), r.n_out(), r.V_out(), idx(r.pairs()),
+                                               r.vol(), r.max_chunks(), f32(r.dW()), f32(r.d_bias()), f32(r.scratch()), st)
+              : aabr_conv_backward_weight(f32(r.in()), r.n_in(), f32(r.d_out()), r.n_out(), r.V_out(), idx(r.pairs()),
+                                          r.vol(), r.max_chunks(), f32(r.dW()), f32(r.d_bias()), f32(r.scratch()), st);
+  }
+  case AABR_PLAN_BN_FWD: {
+    const PlanBnFwd r{o};
+    if (r.parts()) { // the statistics' partial sums came with the producing convolution (nparts of them)
+      AABR_CHECK_ARG(r.train(), "precomputed statistics in training mode only");
+      return bf ? aabr_bn_forward_parts_bf16(b16(r.in()), b16(r.out()), r.rows(), r.planes(), f32(r.save_mean()),
+                                             f32(r.save_invstd()), f32(r.running_mean()), f32(r.running_var()),
+                                             f32(r.weight()), f32(r.bias()), r.eps(), r.momentum(), r.leak(),
+                                             r.parts(), r.nparts(), f32(r.scratch()), st)
+                : aabr_bn_forward_parts(f32(r.in()), f32(r.out()), r.rows(), r.planes(), f32(r.save_mean()),
+                                        f32(r.save_invstd()), f32(r.running_mean()), f32(r.running_var()),
+                                        f32(r.weight()), f32(r.bias()), r.eps(), r.momentum(), r.leak(),
+                                        r.parts(), r.nparts(), f32(r.scratch()), st);
     }
-    rc = bf ? aabr_conv_forward_wide_bf16_res((const uint16_t *)p[0], o.i32[0], o.i64[0], (uint16_t *)p[1], o.i32[1],
-                                              o.i64[1], (const int32_t *)p[2], o.i32[4], o.i32[2], (const float *)p[4],
-                                              o.i32[3], (const uint16_t *)p[5], (const uint16_t *)p[3], (double *)p[6],
-                                              nullptr, nullptr, nullptr, 0.0f, st)
-            : aabr_conv_forward_wide_stats((const float *)p[0], o.i32[0], o.i64[0], (float *)p[1], o.i32[1], o.i64[1],
-                                           (const int32_t *)p[2], o.i32[4], o.i32[2], (const float *)p[4], o.i32[3],
-                                           (const float *)p[5], (const float *)p[3], (double *)p[6], st);
-    break;
-  case AABR_PLAN_CONV_WIDE_SPLIT:
-    rc = bf ? aabr_conv_forward_wide_split_bf16_res((const uint16_t *)p[0], o.i32[0], o.i64[0], (uint16_t *)p[1],
-                                                    o.i32[1], o.i64[1], (const int32_t *)p[2], o.i32[4], o.i32[2],
-                                                    (const float *)p[4], o.i32[3], (const uint16_t *)p[5], o.i32[5],
-                                                    (float *)p[6], (const uint16_t *)p[3], st)
-            : aabr_conv_forward_wide_split((const float *)p[0], o.i32[0], o.i64[0], (float *)p[1], o.i32[1], o.i64[1],
-                                           (const int32_t *)p[2], o.i32[4], o.i32[2], (const float *)p[4], o.i32[3],
-                                           (const float *)p[5], (const float *)p[3], o.i32[5], (float *)p[6], st);
-    break;
-  case AABR_PLAN_CONV_SINGLE:
-    if (bf) { aabr::set_error("aabr_plan_run: the single-rule convolution is fp32 storage only"); rc = AABR_EINVAL; break; }
-    if (o.i32[5] == 1) { // the write-out forms the backward statistics of the BatchNorm whose d_out it produces
-      rc = aabr_conv_forward_single_bwd_stats((const float *)p[0], o.i32[0], o.i64[0], (float *)p[1], o.i32[1], o.i64[1],
-                                              (const int32_t *)p[2], o.i32[2], (const float *)p[4], o.i32[3],
-                                              (const float *)p[5], (const float *)p[3], (double *)p[6],
-                                              (const float *)p[7], (const float *)p[8], (const float *)p[9],
-                                              (const float *)p[10], (const float *)p[11], o.f32[0], st);
-      break;
-    }
-    rc = aabr_conv_forward_single((const float *)p[0], o.i32[0], o.i64[0], (float *)p[1], o.i32[1], o.i64[1],
-                                  (const int32_t *)p[2], o.i32[2], (const float *)p[4], o.i32[3], (const float *)p[5],
-                                  (const float *)p[3], st);
-    break;
-  case AABR_PLAN_CONV_NARROW:
-    if (bf && o.i32[5] == 1) {
-      rc = aabr_conv_forward_narrow_bf16_bwd_stats((const uint16_t *)p[0], o.i64[0], (uint16_t *)p[1], o.i64[1],
-                                                   (const int32_t *)p[2], o.i32[2], (const float *)p[3], (const float *)p[4],
-                                                   o.i32[3], (double *)p[6], (const uint16_t *)p[7], (const uint16_t *)p[9],
-                                                   (const float *)p[8], o.f32[0], st);
-      break;
-    }
-    if (bf && p[6]) {
-      rc = aabr_conv_forward_narrow_bf16_stats((const uint16_t *)p[0], o.i64[0], (uint16_t *)p[1], o.i64[1],
-                                               (const int32_t *)p[2], o.i32[2], (const float *)p[3], (const float *)p[4],
-                                               o.i32[3], (double *)p[6], st);
-      break;
-    }
-    rc = bf ? aabr_conv_forward_narrow_bf16((const uint16_t *)p[0], o.i64[0], (uint16_t *)p[1], o.i64[1],
-                                            (const int32_t *)p[2], o.i32[2], (const float *)p[3], (const float *)p[4],
-                                            o.i32[3], st)
-            : aabr_conv_forward_narrow((const float *)p[0], o.i64[0], (float *)p[1], o.i64[1], (const int32_t *)p[2],
-                                       o.i32[2], (const float *)p[3], (const float *)p[4], o.i32[3], st);
-    break;
-  case AABR_PLAN_CONV_DW:
-    rc = bf ? aabr_conv_backward_weight_bf16((const uint16_t *)p[0], o.i32[0], (const uint16_t *)p[1], o.i32[1],
-                                             o.i64[0], (const int32_t *)p[2], o.i32[2], o.i64[1], (float *)p[3],
-                                             (float *)p[4], (float *)p[5], st)
-            : aabr_conv_backward_weight((const float *)p[0], o.i32[0], (const float *)p[1], o.i32[1], o.i64[0],
-                                        (const int32_t *)p[2], o.i32[2], o.i64[1], (float *)p[3], (float *)p[4],
-                                        (float *)p[5], st);
-    break;
-  case AABR_PLAN_BN_FWD:
-    if (p[9]) { // the statistics' partial sums came with the producing convolution (p9, i32[2] of them)
-      AABR_CHECK_ARG(o.i32[1], "precomputed statistics in training mode only");
-      rc = bf ? aabr_bn_forward_parts_bf16((const uint16_t *)p[0], (uint16_t *)p[1], o.i64[0], o.i32[0], (float *)p[2],
-                                           (float *)p[3], (float *)p[4], (float *)p[5], (const float *)p[6],
-                                           (const float *)p[7], o.f32[0], o.f32[1], o.f32[2], (const double *)p[9],
-                                           o.i32[2], (float *)p[8], st)
-              : aabr_bn_forward_parts((const float *)p[0], (float *)p[1], o.i64[0], o.i32[0], (float *)p[2],
-                                      (float *)p[3], (float *)p[4], (float *)p[5], (const float *)p[6],
-                                      (const float *)p[7], o.f32[0], o.f32[1], o.f32[2], (const double *)p[9], o.i32[2],
-                                      (float *)p[8], st);
-      break;
-    }
-    rc = bf ? aabr_bn_forward_bf16((const uint16_t *)p[0], (uint16_t *)p[1], o.i64[0], o.i32[0], (float *)p[2],
-                                   (float *)p[3], (float *)p[4], (float *)p[5], (const float *)p[6],
-                                   (const float *)p[7], o.f32[0], o.f32[1], o.i32[1], o.f32[2], (float *)p[8], st)
-            : aabr_bn_forward((const float *)p[0], (float *)p[1], o.i64[0], o.i32[0], (float *)p[2], (float *)p[3],
-                              (float *)p[4], (float *)p[5], (const float *)p[6], (const float *)p[7], o.f32[0],
-                              o.f32[1], o.i32[1], o.f32[2], (float *)p[8], st);
-    break;
-  case AABR_PLAN_BN_BWD:
-    if (bf && p[11]) { // bf16 storage with the gradient sum folded in (p11); statistics given (i64[1], i32[1]) or its own
-      rc = aabr_bn_backward_add_bf16((const uint16_t *)p[0], (uint16_t *)p[1], (const uint16_t *)p[2],
-                                     (const uint16_t *)p[3], o.i64[0], o.i32[0], (const float *)p[4], (const float *)p[5],
-                                     (const float *)p[6], (const float *)p[10], (float *)p[7], (float *)p[8], o.f32[2],
-                                     (const double *)(uintptr_t)o.i64[1], o.i32[1], (float *)p[9], (const uint16_t *)p[11],
-                                     st);
-      break;
-    }
-    if (o.i64[1]) { // the statistics' partial sums came with the producing convolution (i64[1] = address, i32[1] of them)
-      if (bf) {
-        rc = aabr_bn_backward_parts_bf16((const uint16_t *)p[0], (uint16_t *)p[1], (const uint16_t *)p[2],
-                                         (const uint16_t *)p[3], o.i64[0], o.i32[0], (const float *)p[4], (const float *)p[5],
-                                         (const float *)p[6], (const float *)p[10], (float *)p[7], (float *)p[8], o.f32[2],
-                                         (const double *)(uintptr_t)o.i64[1], o.i32[1], (float *)p[9], st);
-        break;
-      }
-      rc = aabr_bn_backward_parts((const float *)p[0], (float *)p[1], (const float *)p[2], (const float *)p[3], o.i64[0],
-                                  o.i32[0], (const float *)p[4], (const float *)p[5], (const float *)p[6],
-                                  (const float *)p[10], (float *)p[7], (float *)p[8], o.f32[2],
-                                  (const double *)(uintptr_t)o.i64[1], o.i32[1], (float *)p[9], (const float *)p[11], st);
-      break;
-    }
-    rc = bf ? aabr_bn_backward_bf16((const uint16_t *)p[0], (uint16_t *)p[1], (const uint16_t *)p[2],
-                                    (const uint16_t *)p[3], o.i64[0], o.i32[0], (const float *)p[4],
-                                    (const float *)p[5], (const float *)p[6], (const float *)p[10], (float *)p[7],
-                                    (float *)p[8], o.f32[2], (float *)p[9], st)
-            : aabr_bn_backward_add((const float *)p[0], (float *)p[1], (const float *)p[2], (const float *)p[3],
-                                   o.i64[0], o.i32[0], (const float *)p[4], (const float *)p[5], (const float *)p[6],
-                                   (const float *)p[10], (float *)p[7], (float *)p[8], o.f32[2], (float *)p[9],
-                                   (const float *)p[11], st);
-    break;
-  case AABR_PLAN_ADD:
-    rc = aabr_add(p[0], p[1], p[2], o.i64[0], bf ? 1 : 0, st);
-    break;
-  case AABR_PLAN_CAST:
-    rc = aabr_cast_storage(p[0], p[1], o.i64[0], (o.flags & AABR_PLAN_TO_BF16) ? 1 : 0, st);
-    break;
+    return bf ? aabr_bn_forward_bf16(b16(r.in()), b16(r.out()), r.rows(), r.planes(), f32(r.save_mean()),
+                                     f32(r.save_invstd()), f32(r.running_mean()), f32(r.running_var()), f32(r.weight()),
+                                     f32(r.bias()), r.eps(), r.momentum(), r.train(), r.leak(), f32(r.scratch()), st)
+              : aabr_bn_forward(f32(r.in()), f32(r.out()), r.rows(), r.planes(), f32(r.save_mean()), f32(r.save_invstd()),
+                                f32(r.running_mean()), f32(r.running_var()), f32(r.weight()), f32(r.bias()), r.eps(),
+                                r.momentum(), r.train(), r.leak(), f32(r.scratch()), st);
+  }
+  case AABR_PLAN_BN_BWD: {
+    const PlanBnBwd r{o};
+    if (bf && r.d_in_add())   // bf16 storage with the gradient sum folded in; statistics given (parts, nparts) or its own
+      return aabr_bn_backward_add_bf16(b16(r.in()), b16(r.d_in()), b16(r.out()), b16(r.d_out()), r.rows(), r.planes(),
+                                       f32(r.save_mean()), f32(r.save_invstd()), f32(r.weight()), f32(r.bias()),
+                                       f32(r.d_weight()), f32(r.d_bias()), r.leak(), r.parts(), r.nparts(),
+                                       f32(r.scratch()), b16(r.d_in_add()), st);
+    if (r.parts() && bf)      // the statistics' partial sums came with the producing convolution (nparts of them)
+      return aabr_bn_backward_parts_bf16(b16(r.in()), b16(r.d_in()), b16(r.out()), b16(r.d_out()), r.rows(), r.planes(),
+                                         f32(r.save_mean()), f32(r.save_invstd()), f32(r.weight()), f32(r.bias()),
+                                         f32(r.d_weight()), f32(r.d_bias()), r.leak(), r.parts(), r.nparts(),
+                                         f32(r.scratch()), st);
+    if (r.parts())
+      return aabr_bn_backward_parts(f32(r.in()), f32(r.d_in()), f32(r.out()), f32(r.d_out()), r.rows(), r.planes(),
+                                    f32(r.save_mean()), f32(r.save_invstd()), f32(r.weight()), f32(r.bias()),
+                                    f32(r.d_weight()), f32(r.d_bias()), r.leak(), r.parts(), r.nparts(), f32(r.scratch()),
+                                    f32(r.d_in_add()), st);
+    return bf ? aabr_bn_backward_bf16(b16(r.in()), b16(r.d_in()), b16(r.out()), b16(r.d_out()), r.rows(), r.planes(),
+                                      f32(r.save_mean()), f32(r.save_invstd()), f32(r.weight()), f32(r.bias()),
+                                      f32(r.d_weight()), f32(r.d_bias()), r.leak(), f32(r.scratch()), st)
+              : aabr_bn_backward_add(f32(r.in()), f32(r.d_in()), f32(r.out()), f32(r.d_out()), r.rows(), r.planes(),
+                                     f32(r.save_mean()), f32(r.save_invstd()), f32(r.weight()), f32(r.bias()),
+                                     f32(r.d_weight()), f32(r.d_bias()), r.leak(), f32(r.scratch()), f32(r.d_in_add()), st);
+  }
+  case AABR_PLAN_ADD: {
+    const PlanAdd r{o};
+    return aabr_add(r.a(), r.b(), r.out(), r.n(), bf ? 1 : 0, st);
+  }
+  case AABR_PLAN_CAST: {
+    const PlanCast r{o};
+    return aabr_cast_storage(r.in(), r.out(), r.n(), (o.flags & AABR_PLAN_TO_BF16) ? 1 : 0, st);
+  }
   default:
     aabr::set_error("aabr_plan_run: a record has unknown kind %d", o.kind);
     return AABR_EINVAL;
   }
-  return rc;
 }
 
 // `hold`: this list is a PART of a pass whose next part follows on the same thread -- the side stream is left unjoined at
@@ -527,7 +518,7 @@ static int plan_run_part(const AabrPlanOp *ops, int n_ops, void *st_, int hold, 
   for (int j = 0; j < n_ops; ++j) {
     const AabrPlanOp &o = ops[j];
     if (o.kind == AABR_PLAN_TAIL_JOIN) {   // the caller's stream waits for an earlier list's tail (ticket in i64[0])
-      const int rc = aabr_plan_tail_join((uint64_t)o.i64[0], st_);
+      const int rc = aabr_plan_tail_join((uint64_t)PlanTailJoin{o}.ticket(), st_);
       if (rc != AABR_OK) return fail(rc);
       in_tail_run = false;
       continue;
@@ -581,13 +572,13 @@ static int plan_run_part(const AabrPlanOp *ops, int n_ops, void *st_, int hold, 
       while (j + m < n_ops && m < kCastJobsMax && ops[j + m].kind == AABR_PLAN_CAST &&
              !(ops[j + m].flags & (AABR_PLAN_SIDE | AABR_PLAN_JOIN | (tail_mode ? AABR_PLAN_TAIL : 0))) &&
              ((ops[j + m].flags ^ o.flags) & AABR_PLAN_TO_BF16) == 0) {
-        const AabrPlanOp &c = ops[j + m];
+        const PlanCast c{ops[j + m]};
         bool clash = false;
         for (int q = 0; q < m && !clash; ++q) {
-          const AabrPlanOp &e = ops[j + q];
-          clash = overlaps(c.p[1], (size_t)c.i64[0] * es_out, e.p[0], (size_t)e.i64[0] * es_in) ||
-                  overlaps(c.p[1], (size_t)c.i64[0] * es_out, e.p[1], (size_t)e.i64[0] * es_out) ||
-                  overlaps(c.p[0], (size_t)c.i64[0] * es_in, e.p[1], (size_t)e.i64[0] * es_out);
+          const PlanCast e{ops[j + q]};
+          clash = overlaps(c.out(), (size_t)c.n() * es_out, e.in(), (size_t)e.n() * es_in) ||
+                  overlaps(c.out(), (size_t)c.n() * es_out, e.out(), (size_t)e.n() * es_out) ||
+                  overlaps(c.in(), (size_t)c.n() * es_in, e.out(), (size_t)e.n() * es_out);
         }
         if (clash) break;
         ++m;

@@ -22,7 +22,6 @@ does not do: change any number -- `tests/test_gpu_fpn.py` holds it bit-equal to 
 (returns None) when a module of the graph carries hooks or is of a type it does not know."""
 import ctypes
 import functools
-import struct
 import threading
 
 import torch
@@ -31,6 +30,9 @@ from torch.autograd import Function
 import _hip
 from _hip import stream, check
 from . import SCN
+from . import plan_records as R      # the AabrPlanOp record format: one field table and one writer per layout
+from .plan_records import (K_CONV, K_WIDE, K_DW, K_BNF, K_BNB, K_ADD, K_CAST, K_WSPLIT, K_NARROW, K_SINGLE,  # noqa: F401
+                           K_TAIL_JOIN, F_BF16, F_TO_BF16, F_SIDE, F_JOIN, F_TAIL)
 from .sparseConvNetTensor import SparseConvNetTensor
 from .sequential import Sequential
 from .tables import AddTable, ConcatTable
@@ -40,11 +42,6 @@ from .submanifoldConvolution import SubmanifoldConvolution
 from .convolution import Convolution
 from .deconvolution import Deconvolution
 
-_OP = struct.Struct("<ii6i4f4q12Q")          # AabrPlanOp (include/aabr_hip.h)
-assert _OP.size == 176
-K_CONV, K_WIDE, K_DW, K_BNF, K_BNB, K_ADD, K_CAST, K_WSPLIT, K_NARROW, K_SINGLE = 1, 2, 3, 4, 5, 6, 7, 9, 10, 11
-K_TAIL_JOIN = 12
-F_BF16, F_TO_BF16, F_SIDE, F_JOIN, F_TAIL = 1, 2, 4, 8, 16
 _ALIGN = 256
 BF16 = torch.bfloat16
 
@@ -157,7 +154,7 @@ pipeline_records = int(os.environ.get("AABR_PLAN_PIPELINE", "0"))
 debug_passes = None
 # tests: a list here receives ("fwd" | "bwd", [record kinds]) of every launch list a pass builds; None in production
 debug_kinds = None
-debug_bwd_stats = None   # tests: a list that receives, per backward list, (kind, i32[5]) of every record
+debug_bwd_stats = None   # tests: a list that receives, per backward list, (kind, bwd_stats slot) of every record
 # a pass that will not be differentiated packs its activations by liveness (AABR_PLAN_PACK_ARENA=0: one slot each, as
 # the training pass needs them)
 pack_inference_arena = os.environ.get("AABR_PLAN_PACK_ARENA", "1") != "0"
@@ -622,8 +619,8 @@ class _Pass(object):
             r = self.route(n_in, n_out, V[lvl], V[lo], g.vol, bfx)
         return r, None
 
-    def conv_launch(self, route, pack, buf, off, src, rows_in, n_in, dst, rows_out, n_out, gather, p_w, p_pack, flags,
-                    xf=0, res=0):
+    def conv_launch(self, route, buf, off, src, rows_in, n_in, dst, rows_out, n_out, gather, p_w, p_pack, flags, xf=0,
+                    res=0):
         """the record of the launch SCN._conv_fwd makes for a prepacked weight along `route`; returns the new write
         offset and the BatchNorm partial sums its write-out can form for the record behind it (the narrow kernel's
         with AABR_PLAN_NARROW_STATS only), or 0"""
@@ -631,28 +628,24 @@ class _Pass(object):
         if route.kind is None:
             return off, 0
         xf |= F_BF16 if route.bf16 else 0
-        blocks = route.stream(gather).data_ptr()
+        # the tile kernel: p3 the raw weight next to the pack
+        kind, cflags, p3, wpack, tile_rows, parts, scratch = K_CONV, flags | 4, p_w, p_pack, 0, 0, 0
         if route.kind == "narrow":        # from the gather table, raw weights
-            pack(buf, off, K_NARROW, xf, n_in, n_out, gather.vol, flags & 3, 0, 0, 0.0, 0.0, 0.0, 0.0, rows_in, rows_out,
-                 0, 0, src, dst, blocks, p_w, 0, 0, 0, 0, 0, 0, 0, 0)
+            kind, cflags, wpack = K_NARROW, flags & 3, 0
         elif route.kind == "single":      # one rule per output row: from the offset pairs, residual in the write-out
-            pack(buf, off, K_SINGLE, xf, n_in, n_out, gather.vol, flags & 3, 0, 0, 0.0, 0.0, 0.0, 0.0, rows_in, rows_out,
-                 0, 0, src, dst, blocks, res, 0, p_pack, 0, 0, 0, 0, 0, 0)
-        elif route.kind == "wide":
-            pack(buf, off, K_WIDE, xf, n_in, n_out, gather.vol, flags & 3, route.tile_rows, 0, 0.0, 0.0, 0.0, 0.0,
-                 rows_in, rows_out, 0, 0, src, dst, blocks, res, 0, p_pack, 0, 0, 0, 0, 0, 0)
-        elif route.kind == "split":       # coarse map: the wide kernel cut into parts over the filter offsets
-            # its own scratch per record: the list is launched later in ONE call, so a shared grow-only workspace could
-            # be reallocated under records already written (the allocator frees it in stream order once the pass's
-            # next list is built)
-            tmp = torch.empty(route.parts * rows_out * n_out, dtype=torch.float32, device=self.dev)
-            (self._tail_tmp if xf & F_TAIL else self._tmp).append(tmp)
-            pack(buf, off, K_WSPLIT, xf, n_in, n_out, gather.vol, flags & 3, route.tile_rows, route.parts, 0.0, 0.0,
-                 0.0, 0.0, rows_in, rows_out, 0, 0, src, dst, blocks, res, 0, p_pack, tmp.data_ptr(), 0, 0, 0, 0, 0)
-        else:
-            pack(buf, off, K_CONV, xf, n_in, n_out, gather.vol, flags | 4, 0, 0, 0.0, 0.0, 0.0, 0.0, rows_in, rows_out,
-                 0, 0, src, dst, blocks, p_w, 0, p_pack, 0, 0, 0, 0, 0, 0)
-        return off + 176, route.stats_parts(rows_out) if (narrow_stats or route.kind != "narrow") else 0
+            kind, cflags, p3 = K_SINGLE, flags & 3, res
+        elif route.kind in ("wide", "split"):
+            kind, cflags, p3, tile_rows = K_WIDE, flags & 3, res, route.tile_rows
+            if route.kind == "split":     # coarse map: the wide kernel cut into parts over the filter offsets
+                # its own scratch per record: the list is launched later in ONE call, so a shared grow-only workspace
+                # could be reallocated under records already written (the allocator frees it in stream order once the
+                # pass's next list is built)
+                tmp = torch.empty(route.parts * rows_out * n_out, dtype=torch.float32, device=self.dev)
+                (self._tail_tmp if xf & F_TAIL else self._tmp).append(tmp)
+                kind, parts, scratch = K_WSPLIT, route.parts, tmp.data_ptr()
+        R.CONV.pack_into(buf, off, kind, xf, n_in, n_out, gather.vol, cflags, tile_rows, parts, rows_in, rows_out,
+                         src, dst, route.stream(gather).data_ptr(), p3, 0, wpack, scratch)
+        return off + R.SIZE, route.stats_parts(rows_out) if (narrow_stats or route.kind != "narrow") else 0
 
     def _live_offsets(self):
         """arena offsets for a pass nobody will differentiate (torch.no_grad): a buffer's bytes are handed on once its
@@ -750,8 +743,9 @@ class _Pass(object):
         # the tail's BatchNorm records run beside the backward list's, which use "bn" on this same stream key
         bnws_tail = _hip.workspace("bn_tail", t.bn_floats, torch.float32, self.dev).data_ptr() \
             if (use_tail and t.bn_floats) else 0
-        buf = bytearray(len(t.fops) * 176)
-        pack, off = _OP.pack_into, 0
+        SZ, off = R.SIZE, 0
+        buf = bytearray(len(t.fops) * SZ)
+        stats_patch, stats_at = R.CONV_STATS
         books = self.books
         fbufs = t.fbufs
         fuse, skip = t.fuse, set()
@@ -762,7 +756,7 @@ class _Pass(object):
         cstat = {}
         cross = t.cross if use_tail else {}
         cross_convs, xlast = set(cross.values()), {}
-        part, start, strm = pipeline_records * 176, 0, stream()
+        part, start, strm = pipeline_records * SZ, 0, stream()
         for op, xf in (t.emit_tail if use_tail else t.emit):
             if part and off - start >= part:
                 # records up to `safe` are final (a convolution record stays open while the BatchNorm behind it may
@@ -772,7 +766,7 @@ class _Pass(object):
                     if lw is not None and lw[1] < safe:
                         safe = lw[1]
                 if safe > start:
-                    check(self.lib.aabr_plan_submit(bytes(buf[start:safe]), (safe - start) // 176, strm, 1))
+                    check(self.lib.aabr_plan_submit(bytes(buf[start:safe]), (safe - start) // SZ, strm, 1))
                     start = safe
             kind = op[0]
             sk = xf & (F_SIDE | F_TAIL)
@@ -784,7 +778,7 @@ class _Pass(object):
                     add_op, other = fz           # out = conv + other, written where the add would have written
                     skip.add(id(add_op))
                     y, res = add_op[3], A[other]
-                off, nparts = self.conv_launch(r, pack, buf, off, A[x], V[lvl], n_in, A[y], V[lo], n_out, g, p_w, pf, 0,
+                off, nparts = self.conv_launch(r, buf, off, A[x], V[lvl], n_in, A[y], V[lo], n_out, g, p_w, pf, 0,
                                                xf, res)
                 last[sk] = (y, off0, nparts, n_out) if nparts else None
                 if id(op) in cross_convs:
@@ -804,39 +798,37 @@ class _Pass(object):
                             ws = cstat[wk] = _hip.workspace("conv_stats%s" % wk, (max(V) // 64 + 1) * 2 * t.max_planes,
                                                             torch.float64, self.dev).data_ptr()
                         parts = ws
-                        struct.pack_into("<Q", buf, lw[1] + 128, ws)          # the convolution record's p6
-                    pack(buf, off, K_BNF, flg | xf, planes, train, nparts, 0, 0, 0, eps, mom, leak, 0.0, V[lvl], 0, 0, 0,
-                         A[x], A[y], sbase + st * 4, sbase + (st + planes) * 4, p_rm, p_rv, p_w, p_b,
-                         bnws_tail if sk & F_TAIL else bnws, parts, 0, 0)
-                    off += 176
+                        stats_patch.pack_into(buf, lw[1] + stats_at, ws)      # the convolution record's `stats`
+                    R.BN_FWD.pack_into(buf, off, K_BNF, flg | xf, planes, train, nparts, eps, mom, leak, V[lvl], A[x], A[y],
+                                       sbase + st * 4, sbase + (st + planes) * 4, p_rm, p_rv, p_w, p_b,
+                                       bnws_tail if sk & F_TAIL else bnws, parts)
+                    off += SZ
             elif kind == "add":
                 if id(op) in skip:
                     continue
                 _, a_, b_, y, lvl, planes, flg = op
-                pack(buf, off, K_ADD, flg | xf, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, V[lvl] * planes, 0, 0, 0,
-                     A[a_], A[b_], A[y], 0, 0, 0, 0, 0, 0, 0, 0, 0)
-                off += 176
+                R.ADD.pack_into(buf, off, K_ADD, flg | xf, V[lvl] * planes, A[a_], A[b_], A[y])
+                off += SZ
             else:
                 _, x, y, lvl, planes, flg = op
-                pack(buf, off, K_CAST, flg | xf, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, V[lvl] * planes, 0, 0, 0,
-                     A[x], A[y], 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
-                off += 176
+                R.CAST.pack_into(buf, off, K_CAST, flg | xf, V[lvl] * planes, A[x], A[y])
+                off += SZ
             last[sk] = None
         if debug_kinds is not None:
-            debug_kinds.append(("fwd", [struct.unpack_from("<i", buf, o)[0] for o in range(0, off, 176)]))
+            debug_kinds.append(("fwd", R.kinds(buf, off)))
         if part:
-            check(self.lib.aabr_plan_submit(bytes(buf[start:off]), (off - start) // 176, strm, 0))
+            check(self.lib.aabr_plan_submit(bytes(buf[start:off]), (off - start) // SZ, strm, 0))
             check(self.lib.aabr_plan_drain())      # everything issued: the caller's next launches queue behind the pass
         elif off and use_tail:
             ticket = ctypes.c_uint64(0)
             self._strm = strm
-            check(self.lib.aabr_plan_run_tail(bytes(buf[:off]), off // 176, strm, ctypes.byref(ticket)))
+            check(self.lib.aabr_plan_run_tail(bytes(buf[:off]), off // SZ, strm, ctypes.byref(ticket)))
             if ticket.value:
                 with _tails_lock:
                     self._ticket = ticket.value
                     _tails.append(self)
         elif off:
-            check(self.lib.aabr_plan_run(bytes(buf[:off]), off // 176, strm))
+            check(self.lib.aabr_plan_run(bytes(buf[:off]), off // SZ, strm))
         res = []
         for b, _ in t.outs:
             lvl, planes, dt = fbufs[b]
@@ -898,8 +890,9 @@ class _Pass(object):
         dwmc.reverse()
         dwws = _hip.workspace("dw", dws, torch.float32, self.dev).data_ptr() if dws else 0
         bnws = _hip.workspace("bn", t.bn_floats, torch.float32, self.dev).data_ptr() if t.bn_floats else 0
-        buf = bytearray((len(bops) * 2 + 1) * 176)
-        pack, off = _OP.pack_into, 0
+        SZ, off = R.SIZE, 0
+        buf = bytearray((len(bops) * 2 + 1) * SZ)
+        (flag_patch, flag_at), (bn_patch, bn_at) = R.CONV_BWD_STATS
         dw_side = F_SIDE if dw_side_stream else 0
         # pieces of the list for the data-parallel hook: cut after every len/S-th record; parameter gradients are laid
         # out in the order their records appear (pslot), so the ones a piece completes form one slice of `gparams`
@@ -916,17 +909,17 @@ class _Pass(object):
                     if nxt is not None and nxt[0] == "bn" and nxt[4] == op[2] and nxt[6] == op[6]:
                         claimed.add(i)
         last_din, bstat = None, None     # the last wide input-gradient record of the main stream / statistics workspace
-        part, start, strm = (pipeline_records * 176 if nseg == 1 else 0), 0, stream()
+        part, start, strm = (pipeline_records * SZ if nseg == 1 else 0), 0, stream()
         for op_no, op in enumerate(bops):
             if part and off - start >= part:
                 safe = last_din[1] if last_din is not None else off    # (that record may still get the statistics)
                 if safe > start:
-                    check(self.lib.aabr_plan_submit(bytes(buf[start:safe]), (safe - start) // 176, strm, 1))
+                    check(self.lib.aabr_plan_submit(bytes(buf[start:safe]), (safe - start) // SZ, strm, 1))
                     start = safe
             if nseg > 1 and seg_no < nseg - 1 and op_no == cut[seg_no]:
                 last_din = None          # its record has been handed over
                 if off:
-                    check(self.lib.aabr_plan_run(bytes(buf[:off]), off // 176, stream()))
+                    check(self.lib.aabr_plan_run(bytes(buf[:off]), off // SZ, stream()))
                     off = 0
                 pairs = []
                 while next_inv < len(inv) and inv[next_inv][0] < done_floats:
@@ -960,24 +953,24 @@ class _Pass(object):
                     r = self.route(n_in, n_out, V[lo], V[lvl], g.vol, bf, residual=res is not None)
                 if res is None or r.takes_residual:
                     off0 = off
-                    off, nparts = self.conv_launch(r, pack, buf, off, AD[gy[0]][gy[1]], V[lo], n_in, AD[gx[0]][gx[1]],
+                    off, nparts = self.conv_launch(r, buf, off, AD[gy[0]][gy[1]], V[lo], n_in, AD[gx[0]][gx[1]],
                                                    V[lvl], n_out, g, p_w, pt, flags, 0,
                                                    AD[res[0]][res[1]] if res is not None else 0)
                     if nparts:
                         last_din = (gx, off0, nparts, n_out)
                 else:                    # not a wide launch: d_in into the spare buffer, then the sum
-                    off, _ = self.conv_launch(self.route(n_in, n_out, V[lo], V[lvl], g.vol, bf), pack, buf, off,
+                    off, _ = self.conv_launch(self.route(n_in, n_out, V[lo], V[lvl], g.vol, bf), buf, off,
                                               AD[gy[0]][gy[1]], V[lo], n_in, AD[tmp[0]][tmp[1]], V[lvl], n_out, g, p_w,
                                               pt, flags)
-                    pack(buf, off, K_ADD, flg, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, V[lvl] * n_out, 0, 0, 0,
-                         AD[res[0]][res[1]], AD[tmp[0]][tmp[1]], AD[gx[0]][gx[1]], 0, 0, 0, 0, 0, 0, 0, 0, 0)
-                    off += 176
+                    R.ADD.pack_into(buf, off, K_ADD, flg, V[lvl] * n_out, AD[res[0]][res[1]], AD[tmp[0]][tmp[1]],
+                                    AD[gx[0]][gx[1]])
+                    off += SZ
             elif kind == "dw":
                 _, x, gy, lo, n_in, n_out, book, side, pg, flg = op
                 g = books[book][side]
-                pack(buf, off, K_DW, flg | dw_side, n_in, n_out, g.vol, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, V[lo], dwmc.pop(), 0, 0,
-                     A[x], AD[gy[0]][gy[1]], g.pairs().data_ptr(), pbase + pg, 0, dwws, 0, 0, 0, 0, 0, 0)
-                off += 176
+                R.CONV_DW.pack_into(buf, off, K_DW, flg | dw_side, n_in, n_out, g.vol, V[lo], dwmc.pop(), A[x],
+                                    AD[gy[0]][gy[1]], g.pairs().data_ptr(), pbase + pg, 0, dwws)
+                off += SZ
             elif kind == "bn":
                 _, x, gx, y, gy, lvl, planes, flg, leak, st, p_w, pw, pb, p_b, res = op
                 if V[lvl]:
@@ -986,52 +979,48 @@ class _Pass(object):
                             and (flg == F_BF16 or (not flg and leak >= 0.0))):
                         # the BatchNorm's d_out was written by the wide-kernel input-gradient launch right before it (the
                         # weight-gradient record in between runs on the second stream): that launch's write-out forms the
-                        # backward statistics (record i32[5] = 1, p6 stats, p7.. the BatchNorm's input and coefficients)
+                        # backward statistics (the record's bwd_stats = 1, leak, stats, then the BatchNorm's input and
+                        # coefficients: save_invstd in fp32 storage, the BatchNorm's stored output in bf16)
                         nparts = ld[2]
                         if bstat is None:
                             bstat = _hip.workspace("conv_bwd_stats", (max(V) // 64 + 1) * 2 * t.max_planes,
                                                    torch.float64, self.dev).data_ptr()
                         parts = bstat
-                        struct.pack_into("<i", buf, ld[1] + 8 + 5 * 4, 1)                                   # i32[5]
-                        struct.pack_into("<f", buf, ld[1] + 32, leak)                                       # f32[0]
-                        struct.pack_into("<6Q", buf, ld[1] + 80 + 6 * 8, bstat, A[x], sbase + st * 4,
-                                         A[y] if flg == F_BF16 else sbase + (st + planes) * 4, p_w, p_b)    # p6 .. p11
-                    pack(buf, off, K_BNB, flg, planes, nparts, 0, 0, 0, 0, 0.0, 0.0, leak, 0.0, V[lvl], parts, 0, 0,
-                         A[x], AD[gx[0]][gx[1]], A[y], AD[gy[0]][gy[1]], sbase + st * 4, sbase + (st + planes) * 4,
-                         p_w, pbase + pw if pw >= 0 else 0, pbase + pb if pb >= 0 else 0, bnws, p_b,
-                         AD[res[0]][res[1]] if res is not None else 0)
-                    off += 176
+                        flag_patch.pack_into(buf, ld[1] + flag_at, 1, leak)
+                        bn_patch.pack_into(buf, ld[1] + bn_at, bstat, A[x], sbase + st * 4,
+                                           A[y] if flg == F_BF16 else sbase + (st + planes) * 4, p_w, p_b)
+                    R.BN_BWD.pack_into(buf, off, K_BNB, flg, planes, nparts, leak, V[lvl], parts, A[x], AD[gx[0]][gx[1]],
+                                       A[y], AD[gy[0]][gy[1]], sbase + st * 4, sbase + (st + planes) * 4, p_w,
+                                       pbase + pw if pw >= 0 else 0, pbase + pb if pb >= 0 else 0, bnws, p_b,
+                                       AD[res[0]][res[1]] if res is not None else 0)
+                    off += SZ
                 last_din = None
             elif kind == "add":
                 _, a_, b_, s, lvl, planes, flg = op
-                pack(buf, off, K_ADD, flg, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, V[lvl] * planes, 0, 0, 0,
-                     AD[a_[0]][a_[1]], AD[b_[0]][b_[1]], AD[s[0]][s[1]], 0, 0, 0, 0, 0, 0, 0, 0, 0)
-                off += 176
+                R.ADD.pack_into(buf, off, K_ADD, flg, V[lvl] * planes, AD[a_[0]][a_[1]], AD[b_[0]][b_[1]], AD[s[0]][s[1]])
+                off += SZ
                 last_din = None
             else:
                 last_din = None
                 _, gy, gx, lvl, planes, flg = op
-                pack(buf, off, K_CAST, flg, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, V[lvl] * planes, 0, 0, 0,
-                     AD[gy[0]][gy[1]], AD[gx[0]][gx[1]], 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
-                off += 176
+                R.CAST.pack_into(buf, off, K_CAST, flg, V[lvl] * planes, AD[gy[0]][gy[1]], AD[gx[0]][gx[1]])
+                off += SZ
         if debug_kinds is not None:      # (with grad_segments > 1: the last piece only)
-            debug_kinds.append(("bwd", [struct.unpack_from("<i", buf, o)[0] for o in range(0, off, 176)]))
-        if debug_bwd_stats is not None:  # i32[5] == 1 on a convolution record: its write-out delivers backward statistics
-            debug_bwd_stats.append([(struct.unpack_from("<i", buf, o)[0], struct.unpack_from("<i", buf, o + 28)[0])
-                                    for o in range(0, off, 176)])
+            debug_kinds.append(("bwd", R.kinds(buf, off)))
+        if debug_bwd_stats is not None:  # bwd_stats == 1 on a convolution record: its write-out delivers backward statistics
+            debug_bwd_stats.append([(k, R.conv_bwd_stats(buf, i * SZ)) for i, k in enumerate(R.kinds(buf, off))])
         # The forward list's tail is joined HERE, by the last record of the (last piece of the) backward list: behind it
         # come the gradient hand-over and the caller's update, which rewrites the BatchNorm parameters and running
         # statistics the tail's records read and write.
         tk = self._ticket
         if tk and not part:
-            pack(buf, off, K_TAIL_JOIN, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, tk, 0, 0, 0,
-                 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
-            off += 176
+            R.TAIL_JOIN.pack_into(buf, off, K_TAIL_JOIN, 0, tk)
+            off += SZ
         if part:
-            check(self.lib.aabr_plan_submit(bytes(buf[start:off]), (off - start) // 176, strm, 0))
+            check(self.lib.aabr_plan_submit(bytes(buf[start:off]), (off - start) // SZ, strm, 0))
             check(self.lib.aabr_plan_drain())
         elif off:
-            check(self.lib.aabr_plan_run(bytes(buf[:off]), off // 176, stream()))
+            check(self.lib.aabr_plan_run(bytes(buf[:off]), off // SZ, stream()))
         if tk:                            # enqueued on this stream by the record; `join_tail` covers the other cases
             self.join_tail()              # (pipelined backward, another stream than the forward's) and returns the ticket
         if nseg > 1:                      # the last piece's gradients

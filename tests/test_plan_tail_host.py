@@ -98,6 +98,18 @@ def test_record_constants_match_the_header():
     flags = [val(n) for n in ("AABR_PLAN_BF16", "AABR_PLAN_TO_BF16", "AABR_PLAN_SIDE", "AABR_PLAN_JOIN", "AABR_PLAN_TAIL")]
     assert len(set(flags)) == 5 and all(f & (f - 1) == 0 for f in flags)
     assert pe.plan_tail in (0, 1, 2) and pe.PLAN_TAIL_DEFAULT in (0, 1, 2)
+    # every record kind and flag of the header, by name, in the record module (and through planExecutor's re-export)
+    from sparseconvnet import plan_records
+    names = {"CONV": "K_CONV", "CONV_WIDE": "K_WIDE", "CONV_DW": "K_DW", "BN_FWD": "K_BNF", "BN_BWD": "K_BNB", "ADD": "K_ADD",
+             "CAST": "K_CAST", "CONV_WIDE_SPLIT": "K_WSPLIT", "CONV_NARROW": "K_NARROW", "CONV_SINGLE": "K_SINGLE",
+             "TAIL_JOIN": "K_TAIL_JOIN", "BF16": "F_BF16", "TO_BF16": "F_TO_BF16", "SIDE": "F_SIDE", "JOIN": "F_JOIN",
+             "TAIL": "F_TAIL"}
+    defined = dict(re.findall(r"#define AABR_PLAN_(\w+) (\d+)", hdr))
+    assert sorted(defined) == sorted(names)
+    for n, v in defined.items():
+        assert getattr(plan_records, names[n]) == getattr(pe, names[n]) == int(v), n
+    kinds = [int(v) for n, v in defined.items() if names[n].startswith("K_")]
+    assert sorted(kinds) == sorted(plan_records.LAYOUT) and plan_records.SIZE == 176
 
 
 def test_c_abi_refusals_and_no_op_tickets_without_a_device():

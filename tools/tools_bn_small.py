@@ -1,13 +1,13 @@
 """Dev tool: device time of BatchNorm forward / backward on the coarse scales' small matrices, launched back to back
 through aabr_plan_run (no host pacing)."""
-import importlib, os, struct, sys
+import importlib, os, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 importlib.import_module("automatic-as-built-reconstruction_amd")
 import torch
 import _hip
+from sparseconvnet import plan_records as R
 lib = _hip.load()
-OP = struct.Struct("<ii6i4f4q12Q")
 dev = "cuda:0"
 for rows, planes in ((22250, 128), (5565, 128), (1382, 256), (332, 256), (49, 256)):
     x = torch.randn(rows, planes, device=dev)
@@ -17,12 +17,10 @@ for rows, planes in ((22250, 128), (5565, 128), (1382, 256), (332, 256), (49, 25
     w, b = torch.ones(planes, device=dev), torch.zeros(planes, device=dev)
     dw, db = torch.empty(planes, device=dev), torch.empty(planes, device=dev)
     ws = torch.empty(int(lib.aabr_bn_scratch_floats(planes)), device=dev)
-    f = OP.pack(4, 0, planes, 1, 0, 0, 0, 0, 1e-4, 0.9, 0.0, 0.0, rows, 0, 0, 0, x.data_ptr(), y.data_ptr(),
-                sm.data_ptr(), si.data_ptr(), rm.data_ptr(), rv.data_ptr(), w.data_ptr(), b.data_ptr(), ws.data_ptr(),
-                0, 0, 0)
-    g = OP.pack(5, 0, planes, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, rows, 0, 0, 0, x.data_ptr(), dx.data_ptr(),
-                y.data_ptr(), dy.data_ptr(), sm.data_ptr(), si.data_ptr(), w.data_ptr(), dw.data_ptr(), db.data_ptr(),
-                ws.data_ptr(), b.data_ptr(), 0)
+    f = R.BN_FWD.pack(R.K_BNF, 0, planes, 1, 0, 1e-4, 0.9, 0.0, rows, x.data_ptr(), y.data_ptr(), sm.data_ptr(),
+                      si.data_ptr(), rm.data_ptr(), rv.data_ptr(), w.data_ptr(), b.data_ptr(), ws.data_ptr(), 0)
+    g = R.BN_BWD.pack(R.K_BNB, 0, planes, 0, 0.0, rows, 0, x.data_ptr(), dx.data_ptr(), y.data_ptr(), dy.data_ptr(),
+                      sm.data_ptr(), si.data_ptr(), w.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), b.data_ptr(), 0)
     for name, rec in (("fwd", f), ("bwd", g)):
         n = 50
         plan = rec * n
