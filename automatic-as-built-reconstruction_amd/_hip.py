@@ -35,7 +35,14 @@ class AabrRpnMap(C.Structure):
                 ("box_regression", C.c_void_p), ("d_features", C.c_void_p)]
 
 
+class AabrMlpWindow(C.Structure):
+    """include/aabr_hip.h AabrMlpWindow: a window of the box head's convolution rows as a GEMM operand"""
+    _fields_ = [("n_rois", C.c_int64), ("ph", C.c_int32), ("pw", C.c_int32), ("R", C.c_int32), ("wlen", C.c_int32),
+                ("blocks", C.c_int32), ("w0", C.c_int32 * 2)]
+
+
 _lvp = C.POINTER(AabrRoiLevel)
+_mwp = C.POINTER(AabrMlpWindow)
 _rmp = C.POINTER(AabrRpnMap)
 _SIGS = {
     "aabr_version": (C.c_int, []),
@@ -191,6 +198,10 @@ _SIGS = {
                                                     _f32p, _vp, _vp]),
     "aabr_box_encode": (C.c_int, [_vp, _vp, _i64, _f32p, _vp, _vp]),
     "aabr_box_decode": (C.c_int, [_vp, _vp, _i64, _i32, _f32p, _f32, _vp, _vp]),
+    "aabr_box_to_2corners": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "aabr_box_from_2corners": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "aabr_box_encode_corner": (C.c_int, [_vp, _vp, _i64, _f32p, _vp, _vp]),
+    "aabr_box_decode_corner": (C.c_int, [_vp, _vp, _i64, _i32, _f32p, _f32, _vp, _vp]),
     "aabr_rpn_topk_scratch_words": (C.c_int64, [_i32]),
     "aabr_rpn_topk_maps": (C.c_int, [_i32, _vp, _i32, _i32p, _i32p, _i32, _i32p, _vp, _i64, _vp, _vp, _vp]),
     "aabr_rpn_gather_logits": (C.c_int, [_i32, _vp, _i32, _i32p, _i32p, _i32, _i64, _vp, _vp]),
@@ -212,10 +223,16 @@ _SIGS = {
     "aabr_roi_post_detections": (C.c_int, [_vp, _vp, _vp, _i32, C.POINTER(C.c_int64), _i32, _i32, _f32p, _f32, _f32,
                                            _f32, _f32, _f32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp]),
+    "aabr_roi_post_detections_coder": (C.c_int, [_vp, _vp, _vp, _i32, C.POINTER(C.c_int64), _i32, _i32, _f32p, _i32, _f32,
+                                                 _f32, _f32, _f32, _f32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp, _vp]),
     "aabr_roi_targets_scratch_words": (C.c_int64, [_i32]),
     "aabr_roi_targets": (C.c_int, [_vp, _vp, _vp, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _f32p, _i32, _i32,
                                    _f32, _f32, _f32p, C.c_uint32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp]),
+    "aabr_roi_targets_coder": (C.c_int, [_vp, _vp, _vp, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _f32p, _i32,
+                                         _i32, _f32, _f32, _f32p, _i32, C.c_uint32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aabr_roi_box_loss_scratch_floats": (C.c_int64, []),
     "aabr_roi_box_loss_forward": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
     "aabr_roi_box_loss_backward": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
@@ -231,6 +248,9 @@ _SIGS = {
     "aabr_roi_mlp_backward_weight": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
                                                _vp]),
     "aabr_roi_mlp_pack_fc6": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
+    "aabr_roi_mlp_forward_window": (C.c_int, [_vp, _mwp, _vp, _vp, _i32, _i64, _vp, _vp]),
+    "aabr_roi_mlp_backward_input_window": (C.c_int, [_vp, _vp, _vp, _mwp, _i64, _i32, _i32, _vp, _vp]),
+    "aabr_roi_mlp_backward_weight_window": (C.c_int, [_vp, _vp, _vp, _mwp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "aabr_rpn_head_tile_rows": (C.c_int, [_i32]),
     "aabr_rpn_head_groups": (C.c_int, [_i64]),
     "aabr_rpn_head_scratch_floats": (C.c_int64, [_i64, _i32, _i32]),

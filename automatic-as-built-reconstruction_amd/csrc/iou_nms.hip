@@ -846,3 +846,92 @@ extern "C" int aabr_box_decode(const float *encodings, const float *anchors, int
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }
+
+// ---- the corner form of the box coder on lists (corner_box.h), one thread per box ------------------------------------
+// mode 0: Box3D_Torch.from_yxzb_to_2corners, 1: Box3D_Torch.from_2corners_to_yxzb, both [n, 7] -> [n, 7]
+__global__ __launch_bounds__(256) void k_box_corner_convert(const float *__restrict__ in, int64_t n, int mode,
+                                                            float *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float a[7], o[7];
+#pragma unroll
+  for (int d = 0; d < 7; ++d) a[d] = in[7 * i + d];
+  if (mode == 0) yxzb_to_2corners(a, o);
+  else corners_to_yxzb(a, o);
+#pragma unroll
+  for (int d = 0; d < 7; ++d) out[7 * i + d] = o[d];
+}
+
+static int box_corner_convert(const char *fn, const float *in, int64_t n, int mode, float *out, void *stream_) {
+  AABR_CHECK_ARG_AS(fn, n >= 0, "bad arguments");
+  if (n == 0) return AABR_OK;
+  AABR_CHECK_ARG_AS(fn, in && out, "null pointer");
+  AABR_CHECK_ARG_AS(fn, ceil_div(n, 256) < ((int64_t)1 << 31), "too many boxes");
+  hipLaunchKernelGGL(k_box_corner_convert, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream_, in, n, mode,
+                     out);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+extern "C" int aabr_box_to_2corners(const float *boxes, int64_t n, float *out, void *stream_) {
+  return box_corner_convert("aabr_box_to_2corners", boxes, n, 0, out, stream_);
+}
+
+extern "C" int aabr_box_from_2corners(const float *corners, int64_t n, float *out, void *stream_) {
+  return box_corner_convert("aabr_box_from_2corners", corners, n, 1, out, stream_);
+}
+
+// BoxCoder3D.encode_corner_box on two [n, 7] yx_zb lists (modeling/box_coder_3d.py:82-91)
+__global__ __launch_bounds__(256) void k_box_encode_corner(const float *__restrict__ targets,
+                                                           const float *__restrict__ anchors, int64_t n, BoxEncodeW w,
+                                                           float *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float g[7], a[7], e[7];
+#pragma unroll
+  for (int d = 0; d < 7; ++d) { g[d] = targets[7 * i + d]; a[d] = anchors[7 * i + d]; }
+  box_encode7_corner(g, a, w.w, e);
+#pragma unroll
+  for (int d = 0; d < 7; ++d) out[7 * i + d] = e[d];
+}
+
+extern "C" int aabr_box_encode_corner(const float *targets, const float *anchors, int64_t n, const float *weights_host,
+                                      float *out, void *stream_) {
+  AABR_CHECK_ARG(n >= 0 && weights_host, "bad arguments");
+  if (n == 0) return AABR_OK;
+  AABR_CHECK_ARG(targets && anchors && out, "null pointer");
+  BoxEncodeW w;
+  for (int d = 0; d < 7; ++d) w.w[d] = weights_host[d];
+  hipLaunchKernelGGL(k_box_encode_corner, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream_, targets,
+                     anchors, n, w, out);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+// BoxCoder3D.decode_corner_box on lists (modeling/box_coder_3d.py:93-122): encodings [n, 7 * num_classes] against
+// proposals [n, 7] yx_zb (the proposal of a row serves all its classes) -> yx_zb boxes [n, 7 * num_classes]
+__global__ __launch_bounds__(256) void k_box_decode_corner(const float *__restrict__ enc, const float *__restrict__ anchors,
+                                                           int64_t n, int nc, BoxEncodeW w, float clip,
+                                                           float *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * nc) return;
+  float e[7], a[7], o[7];
+#pragma unroll
+  for (int d = 0; d < 7; ++d) { e[d] = enc[7 * i + d]; a[d] = anchors[7 * (i / nc) + d]; }
+  box_decode7_corner(e, a, w.w, clip, o);
+#pragma unroll
+  for (int d = 0; d < 7; ++d) out[7 * i + d] = o[d];
+}
+
+extern "C" int aabr_box_decode_corner(const float *encodings, const float *anchors, int64_t n, int num_classes,
+                                      const float *weights_host, float clip, float *out, void *stream_) {
+  AABR_CHECK_ARG(n >= 0 && num_classes >= 1 && weights_host, "bad arguments");
+  if (n == 0) return AABR_OK;
+  AABR_CHECK_ARG(encodings && anchors && out, "null pointer");
+  BoxEncodeW w;
+  for (int d = 0; d < 7; ++d) w.w[d] = weights_host[d];
+  hipLaunchKernelGGL(k_box_decode_corner, dim3((unsigned)ceil_div(n * num_classes, 256)), dim3(256), 0,
+                     (hipStream_t)stream_, encodings, anchors, n, num_classes, w, clip, out);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}

@@ -6,6 +6,7 @@
 #pragma once
 #include "common.h"
 #include "iou_math.h"
+#include "corner_box.h"   // the corner form of the coder: box_encode7_corner / box_decode7_corner, host + device
 
 namespace aabr {
 

@@ -60,6 +60,9 @@ struct RoiTargetParams {
 constexpr int kRoiLanes = 16;
 constexpr int kRoiPropsPerBlock = 256 / kRoiLanes;
 
+// kCorner: the regression targets are BoxCoder3D(is_corner_roi=True).encode (box_encode7_corner, corner_box.h) instead of
+// the centroid encode; matching and labels are the same statements in both instances.
+template <bool kCorner>
 __global__ __launch_bounds__(256) void k_roi_match(RoiTargetParams p, const float *__restrict__ proposals,
                                                    const float *__restrict__ targets,
                                                    const int64_t *__restrict__ target_labels,
@@ -143,7 +146,8 @@ __global__ __launch_bounds__(256) void k_roi_match(RoiTargetParams p, const floa
   float g7[7], e[7];
 #pragma unroll
   for (int d = 0; d < 7; ++d) g7[d] = tb[d];
-  box_encode7(g7, an, p.w, e);
+  if (kCorner) box_encode7_corner(g7, an, p.w, e);
+  else box_encode7(g7, an, p.w, e);
 #pragma unroll
   for (int d = 0; d < 7; ++d) reg_targets[7 * o + d] = e[d];
 }
@@ -328,14 +332,16 @@ extern "C" int64_t aabr_roi_targets_scratch_words(int nb) {
   return aabr_rpn_loss_scratch_words(nb) + (int64_t)nb * (2 * kLossMaxB + kInfoWords) + 2;
 }
 
-extern "C" int aabr_roi_targets(const float *proposals, const float *targets, const int64_t *target_labels, int nb,
-                                const int64_t *n_host, const int64_t *g_host, const float *aug_host, int criterion,
-                                int only_xy, float fg_iou, float bg_iou, const float *weights_host, uint32_t seed,
-                                int batch_size_per_image, int num_pos_max, int64_t *matched_idx, float *matched_val,
-                                int64_t *labels, float *regression_targets, float *iou_out, int64_t *samp_rows,
-                                int64_t *samp_labels, float *samp_targets, float *samp_boxes, int32_t *info,
-                                int32_t *scratch, void *stream_) {
+extern "C" int aabr_roi_targets_coder(const float *proposals, const float *targets, const int64_t *target_labels, int nb,
+                                      const int64_t *n_host, const int64_t *g_host, const float *aug_host, int criterion,
+                                      int only_xy, float fg_iou, float bg_iou, const float *weights_host,
+                                      int corner_coder, uint32_t seed, int batch_size_per_image, int num_pos_max,
+                                      int64_t *matched_idx, float *matched_val, int64_t *labels,
+                                      float *regression_targets, float *iou_out, int64_t *samp_rows,
+                                      int64_t *samp_labels, float *samp_targets, float *samp_boxes, int32_t *info,
+                                      int32_t *scratch, void *stream_) {
   hipStream_t st = (hipStream_t)stream_;
+  AABR_CHECK_ARG(corner_coder == 0 || corner_coder == 1, "corner_coder must be 0 (centroid) or 1 (two corners)");
   AABR_CHECK_ARG(nb >= 1 && nb <= kRoiMaxBatch, "nb must be 1 .. 16");
   AABR_CHECK_ARG(batch_size_per_image >= 1 && batch_size_per_image <= kLossMaxB && num_pos_max >= 0 &&
                      num_pos_max <= batch_size_per_image,
@@ -362,9 +368,15 @@ extern "C" int aabr_roi_targets(const float *proposals, const float *targets, co
   for (int d = 0; d < 4; ++d) p.aug[d] = aug_host[d];
   for (int d = 0; d < 7; ++d) p.w[d] = weights_host[d];
   p.fg = fg_iou; p.bg = bg_iou; p.criterion = criterion; p.only_xy = only_xy ? 1 : 0; p.B = batch_size_per_image;
-  if (nmax > 0)
-    hipLaunchKernelGGL(k_roi_match, dim3((unsigned)ceil_div(nmax, kRoiPropsPerBlock), (unsigned)nb), dim3(256), 0, st, p,
-                       proposals, targets, target_labels, matched_idx, matched_val, labels, regression_targets, iou_out);
+  if (nmax > 0) {
+    const dim3 grid((unsigned)ceil_div(nmax, kRoiPropsPerBlock), (unsigned)nb);
+    if (corner_coder)
+      hipLaunchKernelGGL(k_roi_match<true>, grid, dim3(256), 0, st, p, proposals, targets, target_labels, matched_idx,
+                         matched_val, labels, regression_targets, iou_out);
+    else
+      hipLaunchKernelGGL(k_roi_match<false>, grid, dim3(256), 0, st, p, proposals, targets, target_labels, matched_idx,
+                         matched_val, labels, regression_targets, iou_out);
+  }
   // the sampler over the labels just written: the list form of aabr_sample_list, one chunk (nb <= 16)
   int64_t *sel = reinterpret_cast<int64_t *>(scratch + aabr_rpn_loss_scratch_words(nb) + (aabr_rpn_loss_scratch_words(nb) & 1));
   int32_t *sinfo = reinterpret_cast<int32_t *>(sel + (int64_t)nb * kLossMaxB);
@@ -380,6 +392,20 @@ extern "C" int aabr_roi_targets(const float *proposals, const float *targets, co
                      regression_targets, samp_rows, samp_labels, samp_targets, samp_boxes, info);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
+}
+
+// the centroid coder: the signature of before aabr_roi_targets_coder
+extern "C" int aabr_roi_targets(const float *proposals, const float *targets, const int64_t *target_labels, int nb,
+                                const int64_t *n_host, const int64_t *g_host, const float *aug_host, int criterion,
+                                int only_xy, float fg_iou, float bg_iou, const float *weights_host, uint32_t seed,
+                                int batch_size_per_image, int num_pos_max, int64_t *matched_idx, float *matched_val,
+                                int64_t *labels, float *regression_targets, float *iou_out, int64_t *samp_rows,
+                                int64_t *samp_labels, float *samp_targets, float *samp_boxes, int32_t *info,
+                                int32_t *scratch, void *stream_) {
+  return aabr_roi_targets_coder(proposals, targets, target_labels, nb, n_host, g_host, aug_host, criterion, only_xy, fg_iou,
+                                bg_iou, weights_host, 0, seed, batch_size_per_image, num_pos_max, matched_idx, matched_val,
+                                labels, regression_targets, iou_out, samp_rows, samp_labels, samp_targets, samp_boxes, info,
+                                scratch, stream_);
 }
 
 extern "C" int64_t aabr_roi_box_loss_scratch_floats(void) { return 3 * kRoiLossBlocks; }

@@ -18,6 +18,20 @@
 // gradient is stored in the same fragments.  The neighbouring rows' instructions hit the same lines in cache; lanes along
 // a ROI's contiguous (s, z) block for a fixed c would be the coalesced form and is left for when this is timed.
 // A partial tile is zero-filled, so any M >= 1, N >= 1, K work.
+//
+// The corner form of the box head (MODEL.CORNER_ROI) runs fc6 over WINDOWS of the convolution rows X [n ph pw, R]: the
+// feature extractor cuts the pw = 11 axis into cor0 = w 0..2, body = w 2..8 and cor1 = w 8..10
+// (roi_box_feature_extractors.py:122-147) and gives each part its own fc6.  A window [w0, w0 + wlen) of ROI n is ph runs
+// of wlen R contiguous floats, pw R apart, so it is one more outer x reduce operand (kWinM: the rows are the outer index;
+// kWinK: the columns are): row m -> n pw ph R + w0 R, column k = (h wlen + wl) R + r -> h pw R + (wl R + r).  Forward
+// and weight gradient read the windows in place, the input gradient writes them in place (OW); nothing is copied.
+// Rows come in up to two blocks with a w0 each (rows < nsplit: w0a, the rest: w0b and ROI m - nsplit), so the two
+// corner windows, which share their weights, are ONE GEMM with M = 2 n.  Lanes run along k in both layouts: runs of
+// wlen R floats, coalesced.
+// The windows overlap at w = 2 and w = 8, so the input gradient dX receives two contributions there.  Order: the body
+// GEMM goes first and STORES w 2..8; the corner GEMM, next on the same stream, stores w 0, 1, 9, 10 and ADDS into w 2 and
+// w 8 (one thread per element, a plain load-add-store: dX = corner term + body term).  Every element of dX is written
+// once or stored-then-added, there is no zero fill and no atomic, and two runs give the same bits.
 // LDS rows are BT + 2 floats: the reduce-fast store (row = lane & 31) and the MFMA read (lanes 32..63 read row kk + 16,
 // 16 (BT + 2) = 32 mod 64 banks from lanes 0..31) are both conflict-free.
 //
@@ -37,7 +51,25 @@
 namespace aabr {
 
 constexpr int kBK = 32;                      // reduction elements per chunk
-enum { kRed = 0, kOut = 1, kPoolM = 2, kPoolK = 3 };
+enum { kRed = 0, kOut = 1, kPoolM = 2, kPoolK = 3, kWinM = 4, kWinK = 5 };
+
+// a window of the convolution rows [n ph pw, R] as an outer x reduce matrix [blocks n, ph wlen R]
+struct MlpWindow {
+  uint32_t R, wR;          // R, wlen R
+  uint32_t nsplit;         // rows below it use w0a, the rest w0b and ROI m - nsplit
+  uint32_t w0a, w0b;
+  int64_t pwR, nstride;    // pw R, ph pw R
+};
+__device__ inline int64_t mlp_win_row(const MlpWindow &w, uint32_t m, uint32_t &w0) {
+  const bool first = m < w.nsplit;
+  w0 = first ? w.w0a : w.w0b;
+  return (int64_t)(first ? m : m - w.nsplit) * w.nstride + (int64_t)w0 * w.R;
+}
+__device__ inline int64_t mlp_win_col(const MlpWindow &w, uint32_t k, uint32_t &rem) {
+  const uint32_t h = k / w.wR;
+  rem = k - h * w.wR;
+  return (int64_t)h * w.pwR + rem;
+}
 
 struct MlpOperand {
   const float *p;
@@ -45,6 +77,7 @@ struct MlpOperand {
   int64_t ld;              // kRed: outer stride; kOut: reduce stride
   uint32_t hw, pz;         // pooled layouts
   int64_t hwpz, nstride;   // hw * pz, C * hw * pz
+  MlpWindow win;           // window layouts
 };
 
 struct MlpArgs {
@@ -56,6 +89,8 @@ struct MlpArgs {
   int64_t ldo;
   uint32_t o_hw, o_pz;            // o_pz > 0: the output is stored in the pooled layout (rows m, cols k)
   int64_t o_hwpz, o_nstride;
+  MlpWindow o_win;                // OW: the output is stored into windows of the convolution rows (rows m, cols k) ...
+  uint32_t o_acc_w[2];            // ... and ADDED to what is there at these two absolute w positions (~0u: none)
   uint32_t perm_R, perm_hw;       // perm_hw > 0: output column k' = s R + r is stored at column r hw + s
   const float *bias;
   int relu;
@@ -73,6 +108,9 @@ template <int L> __device__ inline int64_t mlp_off_out(const MlpOperand &q, uint
     const uint32_t n = o / q.hw, s = o - n * q.hw;
     return (int64_t)n * q.nstride + (int64_t)s * q.pz;
   }
+  uint32_t x;
+  if (L == kWinM) return mlp_win_row(q.win, o, x);
+  if (L == kWinK) return mlp_win_col(q.win, o, x);
   const uint32_t c = o / q.pz, z = o - c * q.pz;     // outer = k = c pz + z
   return (int64_t)c * q.hwpz + z;
 }
@@ -83,18 +121,22 @@ template <int L> __device__ inline int64_t mlp_off_red(const MlpOperand &q, uint
     const uint32_t c = r / q.pz, z = r - c * q.pz;
     return (int64_t)c * q.hwpz + z;
   }
+  uint32_t x;
+  if (L == kWinM) return mlp_win_col(q.win, r, x);
+  if (L == kWinK) return mlp_win_row(q.win, r, x);
   const uint32_t n = r / q.hw, s = r - n * q.hw;     // reduce = m
   return (int64_t)n * q.nstride + (int64_t)s * q.pz;
 }
 
 // One operand's BT x kBK tile: global -> registers -> LDS image [kBK][BT + 2].  Thread t serves, for i < NI,
-//   reduce-fast layouts (kRed, kPoolM):  reduce t & 31, outer (t >> 5) + 8 i
-//   outer-fast layouts  (kOut, kPoolK):  outer t % BT,  reduce t / BT + (256 / BT) i
+//   reduce-fast layouts (kRed, kPoolM, kWinM):  reduce t & 31, outer (t >> 5) + 8 i
+//   outer-fast layouts  (kOut, kPoolK, kWinK):  outer t % BT,  reduce t / BT + (256 / BT) i
 template <int BT, int L> struct MlpLoader {
   static constexpr int NI = BT * kBK / 256;
-  static constexpr bool kRedFast = (L == kRed || L == kPoolM);
+  static constexpr bool kRedFast = (L == kRed || L == kPoolM || L == kWinM);
+  static constexpr bool kOutTab = (L == kPoolM || L == kWinM);   // one off_out per outer index of the thread
   static constexpr int LDT = BT + 2;
-  int64_t oo[L == kPoolM ? NI : 1];  // off_out of this thread's outer indices, -1 outside the matrix (kRed: of the first)
+  int64_t oo[kOutTab ? NI : 1];  // off_out of this thread's outer indices, -1 outside the matrix (kRed: of the first)
   int64_t ld8;                       // kRed: 8 rows further
   int left;                          // kRed: outer indices from the thread's first to the matrix's end (clamped)
   float v[NI];
@@ -105,7 +147,7 @@ template <int BT, int L> struct MlpLoader {
       const int64_t o = o0 + (t >> 5), n = n_out - o;
       oo[0] = o * q.ld;
       left = n < 0 ? 0 : n > BT ? BT : (int)n;
-    } else if (L == kPoolM) {
+    } else if (kOutTab) {
 #pragma unroll
       for (int i = 0; i < NI; ++i) {
         const int64_t o = o0 + (t >> 5) + 8 * i;
@@ -129,7 +171,7 @@ template <int BT, int L> struct MlpLoader {
 #pragma unroll
       for (int i = 0; i < NI; ++i) {
         if (L == kRed) v[i] = (rv && 8 * i < left) ? fetch(q, oo[0] + i * ld8 + ro) : 0.f;
-        else v[i] = (rv && oo[L == kPoolM ? i : 0] >= 0) ? fetch(q, oo[L == kPoolM ? i : 0] + ro) : 0.f;
+        else v[i] = (rv && oo[kOutTab ? i : 0] >= 0) ? fetch(q, oo[kOutTab ? i : 0] + ro) : 0.f;
       }
     } else {
 #pragma unroll
@@ -150,7 +192,7 @@ template <int BT, int L> struct MlpLoader {
   }
 };
 
-template <int BT, int LA, int LB, bool DW>
+template <int BT, int LA, int LB, bool DW, bool OW = false>
 __global__ __launch_bounds__(256) void k_mlp_gemm(const MlpArgs g) {
   constexpr int LDT = BT + 2, TW = BT / 64;          // TW x TW MFMA tiles of 32 x 32 per wave
   __shared__ float sA[kBK * LDT];
@@ -220,7 +262,11 @@ __global__ __launch_bounds__(256) void k_mlp_gemm(const MlpArgs g) {
     if (col >= g.cols) continue;
     int64_t co = col;
     float bias = 0.f;
-    if (!DW) {
+    uint32_t wrem = 0;
+    if (OW) {
+      co = mlp_win_col(g.o_win, (uint32_t)col, wrem);
+      wrem /= g.o_win.R;                             // the column's w inside the window
+    } else if (!DW) {
       if (g.bias) bias = g.bias[col];
       if (g.o_pz) {
         const uint32_t c = (uint32_t)col / g.o_pz, z = (uint32_t)col - c * g.o_pz;
@@ -238,7 +284,12 @@ __global__ __launch_bounds__(256) void k_mlp_gemm(const MlpArgs g) {
         if (row >= g.rows) continue;
         float x = acc[i][j][r];
         int64_t ro;
-        if (!DW) {
+        if (OW) {
+          uint32_t w0;
+          ro = mlp_win_row(g.o_win, (uint32_t)row, w0);
+          const uint32_t w = w0 + wrem;
+          if (w == g.o_acc_w[0] || w == g.o_acc_w[1]) x += outp[ro + co];
+        } else if (!DW) {
           x += bias;
           if (g.relu) x = x > 0.f ? x : 0.f;
           if (g.o_pz) {
@@ -299,10 +350,10 @@ constexpr int kMlpDwRowsPerSplit = 256, kMlpDwMaxSplits = 64;
 
 static int64_t mlp_tiles(int64_t rows, int64_t cols, int bt) { return ceil_div(rows, bt) * ceil_div(cols, bt); }
 
-template <int LA, int LB, bool DW> static void mlp_launch(int bt, const MlpArgs &g, hipStream_t st) {
+template <int LA, int LB, bool DW, bool OW = false> static void mlp_launch(int bt, const MlpArgs &g, hipStream_t st) {
   const unsigned grid = g.tiles_c * g.tiles_r * g.splits;
-  if (bt == 128) hipLaunchKernelGGL((k_mlp_gemm<128, LA, LB, DW>), dim3(grid), dim3(256), 0, st, g);
-  else hipLaunchKernelGGL((k_mlp_gemm<64, LA, LB, DW>), dim3(grid), dim3(256), 0, st, g);
+  if (bt == 128) hipLaunchKernelGGL((k_mlp_gemm<128, LA, LB, DW, OW>), dim3(grid), dim3(256), 0, st, g);
+  else hipLaunchKernelGGL((k_mlp_gemm<64, LA, LB, DW, OW>), dim3(grid), dim3(256), 0, st, g);
 }
 
 static bool mlp_set_grid(MlpArgs &g, int bt, int64_t splits) {
@@ -315,6 +366,21 @@ static bool mlp_set_grid(MlpArgs &g, int bt, int64_t splits) {
 static void mlp_pooled(MlpOperand &q, int64_t K, int64_t hw, int pz) {
   q.hw = (uint32_t)hw, q.pz = (uint32_t)pz;
   q.hwpz = hw * pz, q.nstride = K * hw;     // C hw pz with C = K / pz
+}
+
+// the window description of the C ABI -> MlpWindow, M and K; false: a shape the kernels do not take
+static bool mlp_window(const AabrMlpWindow *v, MlpWindow &w, int64_t &M, int64_t &K) {
+  if (!v || v->n_rois < 0 || v->ph < 1 || v->pw < 1 || v->R < 1 || v->wlen < 1 || (v->blocks != 1 && v->blocks != 2))
+    return false;
+  for (int b = 0; b < v->blocks; ++b)
+    if (v->w0[b] < 0 || (int64_t)v->w0[b] + v->wlen > v->pw) return false;     // every window inside the pw axis
+  if ((int64_t)v->ph * v->pw * v->R > kMlpMaxDim || v->n_rois > kMlpMaxDim / 2) return false;
+  w.R = (uint32_t)v->R, w.wR = (uint32_t)((int64_t)v->wlen * v->R);
+  w.nsplit = (uint32_t)v->n_rois;
+  w.w0a = (uint32_t)v->w0[0], w.w0b = (uint32_t)v->w0[v->blocks - 1];
+  w.pwR = (int64_t)v->pw * v->R, w.nstride = (int64_t)v->ph * w.pwR;
+  M = v->blocks * v->n_rois, K = (int64_t)v->ph * v->wlen * v->R;
+  return true;
 }
 
 } // namespace aabr
@@ -448,5 +514,92 @@ extern "C" int aabr_roi_mlp_pack_fc6(const float *W, int64_t N, int64_t R, int64
   hipLaunchKernelGGL(k_mlp_pack_fc6, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream_, W, total,
                      R, hw, Wp);
   AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+// ---- fc6 over windows of the convolution rows (the corner form of the box head; layouts kWinM / kWinK / OW above) ----
+
+extern "C" int aabr_roi_mlp_forward_window(const float *X, const AabrMlpWindow *win, const float *W, const float *bias,
+                                           int relu, int64_t N, float *Y, void *stream_) {
+  MlpWindow w;
+  int64_t M, K;
+  AABR_CHECK_ARG(mlp_window(win, w, M, K), "bad window (need ph, pw, R, wlen >= 1, blocks 1 or 2, 0 <= w0, w0 + wlen <= pw)");
+  MLP_CHECK_SHAPE(M, N, K);
+  if (M == 0) return AABR_OK;
+  AABR_CHECK_ARG(X && W && Y, "null pointer");
+  MlpArgs g = {};
+  g.a.p = X, g.a.win = w;
+  g.b.p = W, g.b.ld = K;
+  g.rows = M, g.cols = N, g.red = K, g.red_per_split = ceil_div(K, kBK) * kBK;
+  g.out = Y, g.ldo = N, g.bias = bias, g.relu = relu != 0;
+  const int bt = aabr_roi_mlp_tile(M, N);
+  AABR_CHECK_ARG(mlp_set_grid(g, bt, 1), "too many tiles");
+  mlp_launch<kWinM, kRed, false>(bt, g, (hipStream_t)stream_);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+extern "C" int aabr_roi_mlp_backward_input_window(const float *dY, const float *Y, const float *W,
+                                                  const AabrMlpWindow *win, int64_t N, int acc_w0, int acc_w1, float *dX,
+                                                  void *stream_) {
+  MlpWindow w;
+  int64_t M, K;
+  AABR_CHECK_ARG(mlp_window(win, w, M, K), "bad window (need ph, pw, R, wlen >= 1, blocks 1 or 2, 0 <= w0, w0 + wlen <= pw)");
+  MLP_CHECK_SHAPE(M, N, K);
+  AABR_CHECK_ARG(acc_w0 >= -1 && acc_w1 >= -1 && acc_w0 < win->pw && acc_w1 < win->pw, "acc_w must be -1 or a w position");
+  // the rows of a two-block GEMM are stored by different threads: the blocks may not overlap each other
+  AABR_CHECK_ARG(win->blocks == 1 || win->w0[0] + win->wlen <= win->w0[1] || win->w0[1] + win->wlen <= win->w0[0],
+                 "the two row blocks' windows overlap");
+  if (M == 0) return AABR_OK;
+  AABR_CHECK_ARG(dY && W && dX, "null pointer");
+  MlpArgs g = {};
+  g.a.p = dY, g.a.mask = Y, g.a.ld = N;
+  g.b.p = W, g.b.ld = K;
+  g.rows = M, g.cols = K, g.red = N, g.red_per_split = ceil_div(N, kBK) * kBK;
+  g.out = dX, g.o_win = w;
+  g.o_acc_w[0] = acc_w0 < 0 ? ~0u : (uint32_t)acc_w0, g.o_acc_w[1] = acc_w1 < 0 ? ~0u : (uint32_t)acc_w1;
+  const int bt = aabr_roi_mlp_tile(M, K);
+  AABR_CHECK_ARG(mlp_set_grid(g, bt, 1), "too many tiles");
+  mlp_launch<kRed, kOut, false, true>(bt, g, (hipStream_t)stream_);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+extern "C" int aabr_roi_mlp_backward_weight_window(const float *dY, const float *Y, const float *X,
+                                                   const AabrMlpWindow *win, int64_t N, int64_t perm_hw, float *dW,
+                                                   float *db, float *scratch, void *stream_) {
+  MlpWindow w;
+  int64_t M, K;
+  AABR_CHECK_ARG(mlp_window(win, w, M, K), "bad window (need ph, pw, R, wlen >= 1, blocks 1 or 2, 0 <= w0, w0 + wlen <= pw)");
+  MLP_CHECK_SHAPE(M, N, K);
+  AABR_CHECK_ARG(perm_hw >= 0 && (perm_hw == 0 || K % perm_hw == 0), "perm_hw must be 0 or divide K");
+  AABR_CHECK_ARG(dW, "null pointer");
+  hipStream_t st = (hipStream_t)stream_;
+  if (M == 0) {                                       // an empty sum: zeros, no kernel
+    AABR_CHECK_HIP(hipMemsetAsync(dW, 0, sizeof(float) * N * K, st));
+    if (db) AABR_CHECK_HIP(hipMemsetAsync(db, 0, sizeof(float) * N, st));
+    return AABR_OK;
+  }
+  AABR_CHECK_ARG(dY && X, "null pointer");
+  const int splits = aabr_roi_mlp_dw_splits(M, N, K);
+  AABR_CHECK_ARG(splits == 1 || scratch, "null scratch");
+  MlpArgs g = {};
+  g.a.p = dY, g.a.mask = Y, g.a.ld = N;
+  g.b.p = X, g.b.win = w;
+  g.rows = N, g.cols = K, g.red = M;
+  g.red_per_split = ceil_div(ceil_div(M, splits), kBK) * kBK;
+  g.out = dW, g.ldo = K, g.db = db, g.scratch = scratch;
+  if (perm_hw) g.perm_hw = (uint32_t)perm_hw, g.perm_R = (uint32_t)(K / perm_hw);
+  const int bt = aabr_roi_mlp_tile(N, K);
+  AABR_CHECK_ARG(mlp_set_grid(g, bt, splits), "too many tiles");
+  mlp_launch<kOut, kWinK, true>(bt, g, st);
+  AABR_CHECK_LAUNCH();
+  if (splits > 1) {
+    const int64_t per = N * K + N;
+    AABR_CHECK_ARG(ceil_div(per, 256) < (1LL << 31), "too many elements");
+    hipLaunchKernelGGL(k_mlp_dw_reduce, dim3((unsigned)ceil_div(per, 256)), dim3(256), 0, st, scratch, splits, N, K,
+                       g.perm_R, g.perm_hw, K, dW, db);
+    AABR_CHECK_LAUNCH();
+  }
   return AABR_OK;
 }

@@ -115,6 +115,8 @@ __device__ __forceinline__ uint32_t block_select_kth(int n, int need, F get, int
   return prefix;
 }
 
+// kCorner: the regressions are decoded with BoxCoder3D(is_corner_roi=True).decode (box_decode7_corner, corner_box.h)
+template <bool kCorner>
 __global__ __launch_bounds__(256) void k_roi_post_rows(const float *__restrict__ logits, const float *__restrict__ reg,
                                                        const float *__restrict__ props, int64_t N, RoiPostParams p,
                                                        float *__restrict__ prob, float *__restrict__ boxes) {
@@ -130,9 +132,13 @@ __global__ __launch_bounds__(256) void k_roi_post_rows(const float *__restrict__
   float an[7], o[7];
 #pragma unroll
   for (int d = 0; d < 7; ++d) an[d] = props[7 * i + d];
-  if (p.reg_classes == 1) box_decode7(reg + 7 * i, an, p.w, p.clip, o);
+  const auto decode = [&](const float *e) {
+    if (kCorner) box_decode7_corner(e, an, p.w.w, p.clip, o);
+    else box_decode7(e, an, p.w, p.clip, o);
+  };
+  if (p.reg_classes == 1) decode(reg + 7 * i);
   for (int c = 0; c < C; ++c) {
-    if (p.reg_classes != 1) box_decode7(reg + 7 * (i * C + c), an, p.w, p.clip, o);
+    if (p.reg_classes != 1) decode(reg + 7 * (i * C + c));
 #pragma unroll
     for (int d = 0; d < 7; ++d) boxes[7 * (i * C + c) + d] = o[d];
   }
@@ -358,35 +364,36 @@ extern "C" int64_t aabr_roi_post_scratch_words(int nb, int64_t n_max, int C, int
   return roi_post_layout(nb, n_max, n_max * nb, C, pre_max).words;
 }
 
-extern "C" int aabr_roi_post_detections(const float *class_logits, const float *box_regression, const float *proposals,
-                                        int nb, const int64_t *n_host, int C, int class_specific,
-                                        const float *weights_host, float clip, float score_thresh, float nms_thresh,
-                                        float nms_min_yx, float nms_min_z, int only_xy, int pre_max, int post_max,
-                                        int detections_per_img, float *prob, float *boxes, int64_t *det_rows,
-                                        int64_t *det_labels, float *det_scores, float *det_boxes, int32_t *info,
-                                        int32_t *scratch, void *stream_) {
+static int roi_post_detections(const char *fn, const float *class_logits, const float *box_regression,
+                               const float *proposals, int nb, const int64_t *n_host, int C, int class_specific,
+                               const float *weights_host, int corner_coder, float clip, float score_thresh,
+                               float nms_thresh, float nms_min_yx, float nms_min_z, int only_xy, int pre_max,
+                               int post_max, int detections_per_img, float *prob, float *boxes, int64_t *det_rows,
+                               int64_t *det_labels, float *det_scores, float *det_boxes, int32_t *info,
+                               int32_t *scratch, void *stream_) {
   hipStream_t st = (hipStream_t)stream_;
-  int rc = roi_post_check_shape("aabr_roi_post_detections", nb, C, pre_max);
+  int rc = roi_post_check_shape(fn, nb, C, pre_max);
   if (rc != AABR_OK) return rc;
-  AABR_CHECK_ARG(post_max >= 1 && post_max <= pre_max, "post_max must be 1 .. pre_max");
-  AABR_CHECK_ARG(n_host && weights_host, "null host table");
+  AABR_CHECK_ARG_AS(fn, corner_coder == 0 || corner_coder == 1, "corner_coder must be 0 (centroid) or 1 (two corners)");
+  AABR_CHECK_ARG_AS(fn, post_max >= 1 && post_max <= pre_max, "post_max must be 1 .. pre_max");
+  AABR_CHECK_ARG_AS(fn, n_host && weights_host, "null host table");
   RoiPostParams p;
   int64_t N = 0, n_max = 0;
   for (int b = 0; b <= kRoiMaxBatch; ++b) {
     p.row_begin[b] = (int32_t)N;
     if (b < nb) {
-      AABR_CHECK_ARG(n_host[b] >= 0, "negative scene length");
+      AABR_CHECK_ARG_AS(fn, n_host[b] >= 0, "negative scene length");
       N += n_host[b];
       n_max = n_host[b] > n_max ? n_host[b] : n_max;
-      AABR_CHECK_ARG(N * C * 7 < (int64_t)1 << 31, "too many rows (N * C * 7 must stay below 2^31)");
+      AABR_CHECK_ARG_AS(fn, N * C * 7 < (int64_t)1 << 31, "too many rows (N * C * 7 must stay below 2^31)");
     }
   }
-  AABR_CHECK_ARG(info, "null pointer (info)");
+  AABR_CHECK_ARG_AS(fn, info, "null pointer (info)");
   AABR_CHECK_HIP(hipMemsetAsync(info, 0, (size_t)nb * kRoiInfoWords * sizeof(int32_t), st));
   if (N == 0) return AABR_OK;
-  AABR_CHECK_ARG(class_logits && box_regression && proposals && det_rows && det_labels && det_scores && det_boxes &&
+  AABR_CHECK_ARG_AS(fn, class_logits && box_regression && proposals && det_rows && det_labels && det_scores && det_boxes &&
                      scratch, "null pointer");
-  AABR_CHECK_ARG(((uintptr_t)scratch & 7) == 0, "scratch must be 8-byte aligned");
+  AABR_CHECK_ARG_AS(fn, ((uintptr_t)scratch & 7) == 0, "scratch must be 8-byte aligned");
   const RoiPostLayout L = roi_post_layout(nb, n_max, N, C, pre_max);
   p.nb = nb; p.C = C; p.reg_classes = class_specific ? C : 1;
   p.pre_max = pre_max; p.post_max = post_max; p.D = detections_per_img; p.only_xy = only_xy ? 1 : 0;
@@ -406,8 +413,12 @@ extern "C" int aabr_roi_post_detections(const float *class_logits, const float *
   u.seg_kept = u.seg_cnt + L.S;
   const int64_t cap = (int64_t)(C - 1) * post_max;
   const int64_t longest = n_max < pre_max ? n_max : pre_max;     // no sorted list is longer
-  hipLaunchKernelGGL(k_roi_post_rows, dim3((unsigned)ceil_div(N, (int64_t)256)), dim3(256), 0, st, class_logits,
-                     box_regression, proposals, N, p, u.prob, u.boxes);
+  if (corner_coder)
+    hipLaunchKernelGGL(k_roi_post_rows<true>, dim3((unsigned)ceil_div(N, (int64_t)256)), dim3(256), 0, st, class_logits,
+                       box_regression, proposals, N, p, u.prob, u.boxes);
+  else
+    hipLaunchKernelGGL(k_roi_post_rows<false>, dim3((unsigned)ceil_div(N, (int64_t)256)), dim3(256), 0, st, class_logits,
+                       box_regression, proposals, N, p, u.prob, u.boxes);
   hipLaunchKernelGGL(k_roi_post_select, dim3((unsigned)L.S), dim3(1024), 0, st, p, u);
   hipLaunchKernelGGL(k_roi_post_mask,
                      dim3((unsigned)ceil_div(longest, (int64_t)kNmsRows), (unsigned)ceil_div(longest, (int64_t)64),
@@ -418,4 +429,31 @@ extern "C" int aabr_roi_post_detections(const float *class_logits, const float *
                      det_scores, det_boxes, info);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
+}
+
+extern "C" int aabr_roi_post_detections(const float *class_logits, const float *box_regression, const float *proposals,
+                                        int nb, const int64_t *n_host, int C, int class_specific,
+                                        const float *weights_host, float clip, float score_thresh, float nms_thresh,
+                                        float nms_min_yx, float nms_min_z, int only_xy, int pre_max, int post_max,
+                                        int detections_per_img, float *prob, float *boxes, int64_t *det_rows,
+                                        int64_t *det_labels, float *det_scores, float *det_boxes, int32_t *info,
+                                        int32_t *scratch, void *stream_) {
+  return roi_post_detections("aabr_roi_post_detections", class_logits, box_regression, proposals, nb, n_host, C,
+                             class_specific, weights_host, 0, clip, score_thresh, nms_thresh, nms_min_yx, nms_min_z, only_xy,
+                             pre_max, post_max, detections_per_img, prob, boxes, det_rows, det_labels, det_scores, det_boxes,
+                             info, scratch, stream_);
+}
+
+// the same with the coder's form chosen by the caller: corner_coder 0 = centroid (the entry above), 1 = two corners
+extern "C" int aabr_roi_post_detections_coder(const float *class_logits, const float *box_regression,
+                                              const float *proposals, int nb, const int64_t *n_host, int C,
+                                              int class_specific, const float *weights_host, int corner_coder, float clip,
+                                              float score_thresh, float nms_thresh, float nms_min_yx, float nms_min_z,
+                                              int only_xy, int pre_max, int post_max, int detections_per_img, float *prob,
+                                              float *boxes, int64_t *det_rows, int64_t *det_labels, float *det_scores,
+                                              float *det_boxes, int32_t *info, int32_t *scratch, void *stream_) {
+  return roi_post_detections("aabr_roi_post_detections_coder", class_logits, box_regression, proposals, nb, n_host, C,
+                             class_specific, weights_host, corner_coder, clip, score_thresh, nms_thresh, nms_min_yx,
+                             nms_min_z, only_xy, pre_max, post_max, detections_per_img, prob, boxes, det_rows, det_labels,
+                             det_scores, det_boxes, info, scratch, stream_);
 }

@@ -1,10 +1,13 @@
 """The box head (reference: maskrcnn_benchmark/modeling/roi_heads/box_head_3d/box_head.py:41-257), centroid form
-(forward_centroid_box, :168-248): feature extractor, predictor, loss evaluator and post-processor in the reference's
-order.  `proposals` is one duck-typed list per scene (`.bbox3d` [n, 7] yx_zb, `.size3d`), or an object whose
-`seperate_examples()` returns that.  Not part of this package: the corner-ROI form, the separated-classifier groups, and
+(forward_centroid_box, :168-248) and corner form (cfg.MODEL.CORNER_ROI, forward_corner_box, :78-165): feature extractor,
+predictor, loss evaluator and post-processor in the reference's order.  `proposals` is one duck-typed list per scene
+(`.bbox3d` [n, 7] yx_zb, `.size3d`), or an object whose `seperate_examples()` returns that.  The corner form runs with the
+default loss weights, cfg.MODEL.LOSS.WEIGHTS[4:7] == 0, where the reference drops `corners_semantic` (:121-122); nonzero
+corner-connection loss weights are refused.  Not part of this package: the separated-classifier groups, and
 cfg.DEBUG.eval_in_train (its rm_gt_from_proposals_ reads an `is_gt` field the sampled lists here do not carry)."""
 import torch
 
+import roi_glue
 from .inference import make_roi_box_post_processor
 from .loss import make_roi_box_loss_evaluator
 from .roi_box_feature_extractors import make_roi_box_feature_extractor
@@ -12,12 +15,11 @@ from .roi_box_predictors import make_roi_box_predictor
 
 
 class ROIBoxHead3D(torch.nn.Module):
-    """extractor + predictor + loss evaluator (training) or post-processor (evaluation), the centroid form"""
+    """extractor + predictor + loss evaluator (training) or post-processor (evaluation)"""
 
     def __init__(self, cfg):
         super(ROIBoxHead3D, self).__init__()
-        if cfg.MODEL.CORNER_ROI:
-            raise ValueError("cfg.MODEL.CORNER_ROI: the corner-ROI form of the box head is not part of this package")
+        roi_glue.corner_roi_check(cfg)       # POOLER_RESOLUTION[1] == 11 and LOSS.WEIGHTS[4:7] == 0
         if cfg.DEBUG.eval_in_train > 0:
             raise ValueError("cfg.DEBUG.eval_in_train > 0 is not part of this package")
         self.feature_extractor = make_roi_box_feature_extractor(cfg)
@@ -29,6 +31,7 @@ class ROIBoxHead3D(torch.nn.Module):
         self.add_gt_proposals = cfg.MODEL.RPN.ADD_GT_PROPOSALS
         self.detections_per_img = cfg.MODEL.ROI_HEADS.DETECTIONS_PER_IMG
         self.corner_roi = cfg.MODEL.CORNER_ROI
+        self.no_corner_loss = True           # LOSS.WEIGHTS[4:7] == 0, checked above
         self.cfg = cfg
 
     def post_processor(self, log_reg, proposals):
@@ -37,7 +40,10 @@ class ROIBoxHead3D(torch.nn.Module):
     def forward(self, features, proposals, targets=None):
         """features: one SparseConvNetTensor per level; proposals: per-scene lists; targets: per-scene ground truth
         (training).  Returns (x, proposals, losses): training -- the sampled proposals and {"loss_classifier_roi",
-        "loss_box_reg_roi"}; evaluation -- the detections and {}."""
+        "loss_box_reg_roi"}; evaluation -- the detections and {}.  In the corner form x is the list [x_cor0, x_cor1,
+        x_body] and box_regression holds two-corner encodings."""
+        if self.corner_roi:
+            return self.forward_corner_box(features, proposals, targets)
         if hasattr(proposals, "seperate_examples"):
             proposals = proposals.seperate_examples()
         if self.training:
@@ -52,6 +58,26 @@ class ROIBoxHead3D(torch.nn.Module):
         loss_classifier, loss_box_reg, _ = self.loss_evaluator(class_logits, box_regression, corners_semantic=None,
                                                                targets=targets)
         return x, proposals, {"loss_classifier_roi": loss_classifier, "loss_box_reg_roi": loss_box_reg}
+
+
+    def forward_corner_box(self, features, proposals, targets=None):
+        if hasattr(proposals, "seperate_examples"):
+            proposals = proposals.seperate_examples()
+        if self.training:
+            with torch.no_grad():
+                proposals = self.loss_evaluator.subsample(proposals, targets)
+        x = self.feature_extractor(features, proposals)
+        class_logits, box_regression, corners_semantic = self.predictor(x)
+        if self.no_corner_loss:
+            corners_semantic = None
+        if not self.training:
+            result = self.post_processor((class_logits, box_regression, corners_semantic), proposals)
+            return x, result, {}
+        loss_classifier, loss_box_reg, loss_corner_grouping = self.loss_evaluator(
+            class_logits, box_regression, corners_semantic, targets=targets)
+        roi_loss = {"loss_classifier_roi": loss_classifier, "loss_box_reg_roi": loss_box_reg}
+        roi_loss.update(loss_corner_grouping)
+        return x, proposals, roi_loss
 
 
 def build_roi_box_head(cfg):

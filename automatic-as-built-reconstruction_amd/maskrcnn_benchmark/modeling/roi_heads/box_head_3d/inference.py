@@ -2,7 +2,8 @@
 class logits, box regression and the proposals of a batch -> per scene the final labelled, scored, NMS-filtered boxes.
 The reference loops over scenes and classes in Python; here the whole batch is one call of roi_glue.box_detections
 (csrc/roi_post.hip).  `boxes` is duck-typed (`.bbox3d` [n, 7] yx_zb, `.size3d`, `len()`); the result is a small list
-object with the surface structures/boxlist_ops_3d.py names -- not a port of BoxList3D.  `merge_by_corners`
+object with the surface structures/boxlist_ops_3d.py names -- not a port of BoxList3D.  The coder may be the centroid or
+the corner form (MODEL.CORNER_ROI): the kernel decodes in the form of the BoxCoder3D it is given.  `merge_by_corners`
 (MERGE_BY_CORNER = 0 upstream) is not part of this path."""
 import torch
 from torch import nn
@@ -55,8 +56,7 @@ class PostProcessor(nn.Module):
             # (the reference's default, BoxCoder3D(weights=(10., 10., 5., 5.)), cannot be constructed: the 3-D coder
             # takes is_corner_roi and 7 weights; every caller passes a coder)
             box_coder = BoxCoder3D(is_corner_roi=False, weights=None)
-        if getattr(box_coder, "is_corner_roi", False):
-            raise ValueError("the corner-box coder of the ROI heads is not part of this path")
+        roi_glue.coder_args(box_coder)       # ValueError unless it carries seven weights
         self.box_coder = box_coder
         self.nms_aug_thickness = nms_aug_thickness
         self.class_specific = class_specific
@@ -68,13 +68,13 @@ class PostProcessor(nn.Module):
         dets = roi_glue.box_detections(
             class_logits, box_regression, [b.bbox3d for b in boxes], score_thresh=self.score_thresh, nms=self.nms,
             nms_aug_thickness=self.nms_aug_thickness, detections_per_img=self.detections_per_img,
-            weights=self.box_coder.weights, class_specific=bool(self.class_specific),
-            bbox_xform_clip=self.box_coder.bbox_xform_clip)
+            class_specific=bool(self.class_specific), box_coder=self.box_coder)
         return [DetectionList3D(d["bbox3d"], b.size3d, {"scores": d["scores"], "labels": d["labels"], "rows": d["rows"]})
                 for d, b in zip(dets, boxes)]
 
 
 def make_roi_box_post_processor(cfg):
+    roi_glue.corner_roi_check(cfg)
     box_coder = BoxCoder3D(is_corner_roi=cfg.MODEL.CORNER_ROI, weights=cfg.MODEL.ROI_HEADS.BBOX_REG_WEIGHTS)
     return PostProcessor(cfg.MODEL.ROI_HEADS.SCORE_THRESH, cfg.MODEL.ROI_HEADS.NMS,
                          nms_aug_thickness=cfg.MODEL.ROI_HEADS.NMS_AUG_THICKNESS_Y_Z,

@@ -3,8 +3,10 @@
 call (roi_glue.box_head_targets, csrc/roi_loss.hip), `__call__` computes the cross-entropy and the per-class smooth-L1 loss
 with autograd (roi_glue.box_head_loss).  `proposals` / `targets` are duck-typed (`.bbox3d` [n, 7] yx_zb, `.size3d`,
 `len()`; targets also `get_field("labels")`); the sampled lists are DetectionList3D objects (box_head_3d/inference.py).
-Not part of this path, and refused: the separated-classifier groups (SeperateClassifier.need_seperate), the
-corner-connection losses (`corners_semantic`) and the corner-ROI box coder."""
+The coder may be the centroid or the corner form (MODEL.CORNER_ROI): the target kernel encodes in the form of the
+BoxCoder3D it is given, and in `Diff` mode the losses treat element 6 (yaw difference / thickness) as an ordinary
+difference either way.  Not part of this path, and refused: the separated-classifier groups
+(SeperateClassifier.need_seperate) and the corner-connection losses (`corners_semantic`, MODEL.LOSS.WEIGHTS[4:7])."""
 import torch
 
 import roi_glue
@@ -28,8 +30,7 @@ class FastRCNNLossComputation(object):
         appends the ground truth, callers pass the lists they want matched)."""
         if seperate_classifier is not None and getattr(seperate_classifier, "need_seperate", False):
             raise ValueError("the separated-classifier groups (need_seperate) are not part of this path")
-        if getattr(box_coder, "is_corner_roi", False):
-            raise ValueError("the corner-box coder of the ROI heads is not part of this path")
+        roi_glue.coder_args(box_coder)       # ValueError unless it carries seven weights
         parse_yaw_loss_mode(yaw_loss_mode)   # 'Diff' / 'Diff_<w>'; 'SinDiff' cannot run in the reference's box_loss either
         self.proposal_matcher = proposal_matcher
         self.fg_bg_sampler = fg_bg_sampler
@@ -53,7 +54,7 @@ class FastRCNNLossComputation(object):
             [p.bbox3d for p in proposals], [t.bbox3d for t in targets], [t.get_field("labels") for t in targets],
             fg_iou=self.high_threshold, bg_iou=self.low_threshold, aug_thickness=self.aug_thickness,
             batch_size_per_image=s.batch_size_per_image, positive_fraction=s.positive_fraction,
-            weights=self.box_coder.weights, seed=getattr(s, "seed", None))
+            box_coder=self.box_coder, seed=getattr(s, "seed", None))
         out = [DetectionList3D(d["bbox3d"], p.size3d, {"labels": d["labels"], "regression_targets": d["regression_targets"],
                                                        "rows": d["rows"]}) for d, p in zip(dets, proposals)]
         self._proposals = out
@@ -66,7 +67,8 @@ class FastRCNNLossComputation(object):
         tensor of roi_glue.box_head_loss (1 = some label lay outside [0, C): that row was skipped); reading it is a
         host read, so it is the caller's to do, with the losses."""
         if corners_semantic is not None:
-            raise ValueError("the corner-connection losses (corners_semantic) are not part of this path")
+            raise ValueError("the corner-connection losses (corners_semantic; MODEL.LOSS.WEIGHTS[4:7] != 0) are not part "
+                             "of this path")
         if not hasattr(self, "_proposals"):
             raise RuntimeError("subsample needs to be called before")
         props = self._proposals
@@ -83,7 +85,9 @@ class FastRCNNLossComputation(object):
 
 def make_roi_box_loss_evaluator(cfg):
     """loss.py:577-606.  Returns (loss_evaluator, seperate_classifier); the second is None: cfg.MODEL.SEPARATE_CLASSES_ID
-    must be empty here."""
+    must be empty here.  With MODEL.CORNER_ROI the coder is the corner form and MODEL.LOSS.WEIGHTS[4:7] must be 0
+    (roi_glue.corner_roi_check)."""
+    roi_glue.corner_roi_check(cfg)
     matcher = Matcher(cfg.MODEL.ROI_HEADS.FG_IOU_THRESHOLD, cfg.MODEL.ROI_HEADS.BG_IOU_THRESHOLD,
                       allow_low_quality_matches=False)
     box_coder = BoxCoder3D(is_corner_roi=cfg.MODEL.CORNER_ROI, weights=cfg.MODEL.ROI_HEADS.BBOX_REG_WEIGHTS)

@@ -8,7 +8,10 @@ Between the two, `pool_rois` (csrc/roi_pool.hip): the FPN maps and the sampled p
 Pooler.forward (modeling/poolers_3d.py:126-168) without its per-level nonzero / index / indexed write.  And what turns
 the pooled tensor into the other two (csrc/roi_mlp.hip, a dense fp32 MFMA GEMM family): `dense_linear`, `box_head_mlp`
 (FPN2MLPFeatureExtractor after its pooler, roi_box_feature_extractors.py:149-157) and `box_predictions` (FPNPredictor,
-roi_box_predictors.py:105-109)."""
+roi_box_predictors.py:105-109).  The corner form of the head (MODEL.CORNER_ROI): `box_head_mlp_corner` (fc6 over windows
+of the convolution rows, forward_corner_box, roi_box_feature_extractors.py:122-147) and `box_predictions_corner`
+(roi_box_predictors.py:79-103); `box_head_targets` / `box_detections` take the coder's form from the BoxCoder3D they are
+given."""
 import ctypes as C
 
 import torch
@@ -18,13 +21,42 @@ import _nms
 from _hip import check, ptr
 from rpn_glue import _Cfg
 
+def coder_args(box_coder):
+    """(weights [7 floats], bbox_xform_clip, corner form 0 / 1) of a BoxCoder3D-like object: what the target and the
+    detection kernels need of it.  ValueError for an object that does not carry seven weights."""
+    w = getattr(box_coder, "weights", None)
+    if not torch.is_tensor(w) or w.numel() != 7:
+        raise ValueError("box_coder must be a BoxCoder3D: `weights` holding 7 values, got %r" % (w,))
+    return ([float(v) for v in w.reshape(-1).tolist()], float(getattr(box_coder, "bbox_xform_clip", 10000.0)),
+            int(bool(getattr(box_coder, "is_corner_roi", False))))
+
+
+def corner_roi_check(cfg):
+    """What MODEL.CORNER_ROI = True asks of the rest of a config, checked wherever a module of the corner box head is
+    made (ValueError otherwise; a config that lacks one of the keys is refused the same way):
+      MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION[1] == 11 -- the extractor cuts that axis into the corner windows 0..2 and 8..10
+        and the body window 2..8 (roi_box_feature_extractors.py:93-94,122-127);
+      MODEL.LOSS.WEIGHTS[4:7] == 0 -- the corner-connection losses (`corners_semantic`) are not part of this package:
+        with these weights the reference drops corners_semantic (box_head.py:121-122)."""
+    if not cfg.MODEL.CORNER_ROI:
+        return
+    res = getattr(getattr(cfg.MODEL, "ROI_BOX_HEAD", None), "POOLER_RESOLUTION", None)
+    if res is None or len(res) != 3 or int(res[1]) != 11:
+        raise ValueError("MODEL.CORNER_ROI needs MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION[1] == 11 (corner windows 0..2 and "
+                         "8..10, body window 2..8), got %r" % (res,))
+    lw = getattr(getattr(cfg.MODEL, "LOSS", None), "WEIGHTS", None)
+    if lw is None or len(lw) < 7 or any(float(v) != 0.0 for v in lw[4:7]):
+        raise ValueError("MODEL.CORNER_ROI: the corner-connection losses are not part of this path -- "
+                         "MODEL.LOSS.WEIGHTS[4:7] must be given and be 0, got MODEL.LOSS.WEIGHTS = %r" % (lw,))
+
+
 PRE_NMS, POST_NMS = 2000, 500      # boxlist_nms_3d(flag='roi_post'): rotate_nms_3d(pre_max_size=2000, post_max_size=500)
 INFO_WORDS = 8
 
 
 def box_detections(class_logits, box_regression, proposals, score_thresh=0.05, nms=0.5, nms_aug_thickness=None,
                    detections_per_img=100, weights=None, class_specific=None, defer=False, debug=None,
-                   bbox_xform_clip=10000.0):
+                   bbox_xform_clip=10000.0, box_coder=None):
     """class_logits [N, C] (class 0 = background), box_regression [N, 7 C] or [N, 7], proposals: list over scenes of
     [n_b, 7] yx_zb tensors whose rows, concatenated, are the N rows of the other two.
 
@@ -34,6 +66,8 @@ def box_detections(class_logits, box_regression, proposals, score_thresh=0.05, n
     (kthvalue: ties at the cut all stay).  Equal scores inside a class are ordered by ascending proposal row.
 
     `class_specific`: None = told from the regression's width (7 C: one box per class; 7: one box per row).
+    `box_coder`: a BoxCoder3D; given, its weights, clip and form replace `weights` / `bbox_xform_clip` -- with a corner
+    coder (`is_corner_roi`) box_regression holds two-corner encodings and the decode is BoxCoder3D.decode_corner_box.
     Returns a list over scenes of dicts: bbox3d [m, 7], scores [m], labels [m] int64, rows [m] int64 (the scene's
     proposal row each detection came from).  All launches go out without a host read; the one read (the counts) is at
     the end -- `defer=True` returns the function that does it, as rpn_glue.rpn_proposals does.  `debug` (a dict)
@@ -58,6 +92,9 @@ def box_detections(class_logits, box_regression, proposals, score_thresh=0.05, n
     props = props.to(device=dev, dtype=torch.float32).contiguous()
     aug = (0.0, 0.0) if nms_aug_thickness is None else nms_aug_thickness
     w = (1.0,) * 7 if weights is None else [float(v) for v in torch.as_tensor(weights).reshape(-1).tolist()]
+    corner = 0
+    if box_coder is not None:
+        w, bbox_xform_clip, corner = coder_args(box_coder)
     cap = (nc - 1) * POST_NMS
     words = int(lib.aabr_roi_post_scratch_words(nb, max(n_b) if n_b else 0, nc, PRE_NMS))
     if words < 0:
@@ -74,9 +111,9 @@ def box_detections(class_logits, box_regression, proposals, score_thresh=0.05, n
     det_scores = torch.empty((nb, cap), dtype=torch.float32, device=dev)
     det_boxes = torch.empty((nb, cap, 7), dtype=torch.float32, device=dev)
     info = torch.empty((nb, INFO_WORDS), dtype=torch.int32, device=dev)
-    check(lib.aabr_roi_post_detections(
+    check(lib.aabr_roi_post_detections_coder(
         ptr(logits), ptr(reg), ptr(props), nb, (C.c_int64 * nb)(*n_b), nc, int(bool(class_specific)), _hip.f32xn(w),
-        float(bbox_xform_clip), float(score_thresh), float(nms), float(aug[0]), float(aug[1]),
+        corner, float(bbox_xform_clip), float(score_thresh), float(nms), float(aug[0]), float(aug[1]),
         int(_nms.REFERENCE_DEBUG_ONLY_XY), PRE_NMS, POST_NMS, int(detections_per_img), ptr(prob), ptr(boxes),
         ptr(det_rows), ptr(det_labels), ptr(det_scores), ptr(det_boxes), ptr(info), scratch.data_ptr() + 4 * off,
         _hip.stream()))
@@ -98,7 +135,8 @@ def box_detections(class_logits, box_regression, proposals, score_thresh=0.05, n
 
 
 def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, aug_thickness=None,
-                     batch_size_per_image=500, positive_fraction=0.25, weights=None, seed=None, defer=False, debug=None):
+                     batch_size_per_image=500, positive_fraction=0.25, weights=None, seed=None, defer=False, debug=None,
+                     box_coder=None):
     """proposals / targets: lists over scenes of [n_b, 7] / [G_b, 7] yx_zb device tensors, target_labels: list of int64
     [G_b].  Per scene what FastRCNNLossComputation.subsample does (box_head_3d/loss.py:163-293): IoU of every proposal
     with the scene's ground truth (`boxlist_iou_3d(target, proposal, aug_thickness, criterion=-1)`), Matcher(fg_iou,
@@ -108,6 +146,8 @@ def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, 
     sampled rows in ascending proposal row.  A scene without ground truth has all its proposals background; a scene
     without proposals yields an empty sample (the reference raises there).
 
+    `box_coder`: a BoxCoder3D; given, its weights and form replace `weights` -- with a corner coder (`is_corner_roi`)
+    the regression targets are BoxCoder3D.encode_corner_box; matching, labels and the sample do not depend on it.
     `aug_thickness`: dict with target_Y / target_Z / anchor_Y / anchor_Z (None: no clamps).  `seed=None` draws one from
     torch's default CPU generator (rpn_glue.draw_seed).
     Returns a list over scenes of dicts: rows int64 [m] (scene-local proposal rows), bbox3d [m, 7], labels int64 [m],
@@ -135,6 +175,9 @@ def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, 
     aug = aug_thickness or {}
     aug = [float(aug.get(k, 0.0)) for k in ("target_Y", "target_Z", "anchor_Y", "anchor_Z")]
     w = (1.0,) * 7 if weights is None else [float(v) for v in torch.as_tensor(weights).reshape(-1).tolist()]
+    corner = 0
+    if box_coder is not None:
+        w, _clip, corner = coder_args(box_coder)
     words = int(lib.aabr_roi_targets_scratch_words(nb))
     if words < 0:
         raise _hip.AabrError("box_head_targets: 1 <= scenes <= 16, got %d" % nb)
@@ -151,9 +194,9 @@ def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, 
     s_boxes = torch.empty((nb, B, 7), dtype=torch.float32, device=dev)
     info = torch.empty((nb, INFO_WORDS), dtype=torch.int32, device=dev)
     seed = int(draw_seed() if seed is None else seed) & 0xffffffff
-    check(lib.aabr_roi_targets(
+    check(lib.aabr_roi_targets_coder(
         ptr(props), ptr(tg), ptr(tl), nb, _hip.i64xn(n_b), _hip.i64xn(g_b), _hip.f32x4(aug), -1,
-        int(_nms.REFERENCE_DEBUG_ONLY_XY), float(fg_iou), float(bg_iou), _hip.f32xn(w), seed, B,
+        int(_nms.REFERENCE_DEBUG_ONLY_XY), float(fg_iou), float(bg_iou), _hip.f32xn(w), corner, seed, B,
         int(B * positive_fraction), ptr(midx), ptr(mval), ptr(labels), ptr(regt), ptr(iou), ptr(s_rows), ptr(s_labels),
         ptr(s_targets), ptr(s_boxes), ptr(info), scratch.data_ptr() + 4 * off, _hip.stream()))
     if debug is not None:
@@ -463,9 +506,19 @@ def box_head_mlp(pooled, conv_w, conv_b, bn_w, bn_b, bn_state, fc6_w, fc6_b, fc7
     in place in training; None without tracking).  Without tracking the batch statistics serve in both modes.
     6 launches forward (GEMM, BatchNorm 2, pack, GEMM, GEMM; box_predictions adds a seventh and two torch.cat copies),
     whatever N."""
-    from sparseconvnet.batchNormalization import BatchNormFunction
     _mlp_f32("box_head_mlp", pooled=pooled, conv_w=conv_w, conv_b=conv_b, bn_w=bn_w, bn_b=bn_b, fc6_w=fc6_w, fc6_b=fc6_b,
              fc7_w=fc7_w, fc7_b=fc7_b)
+    n, ph, pw, R = _conv_shape(pooled, conv_w)
+    hw = ph * pw
+    if tuple(fc6_w.shape) != (int(fc6_w.shape[0]), R * hw):
+        raise ValueError("fc6_w must be [*, %d], got %s" % (R * hw, tuple(fc6_w.shape)))
+    x2 = _conv_bn_rows(pooled, conv_w, conv_b, bn_w, bn_b, bn_state)
+    x3 = _Mlp.apply(x2.view(n, hw * R), fc6_w, fc6_b, True, None, hw)
+    return _Mlp.apply(x3, fc7_w, fc7_b, True, None, 0)
+
+
+def _conv_shape(pooled, conv_w):
+    """(N, ph, pw, R) of a pooled tensor and the head's convolution weight, after checking them"""
     if pooled.dim() != 5:
         raise ValueError("pooled must be [N, C, ph, pw, pz], got %s" % (tuple(pooled.shape),))
     _hip.require_gpu(pooled)
@@ -473,9 +526,14 @@ def box_head_mlp(pooled, conv_w, conv_b, bn_w, bn_b, bn_state, fc6_w, fc6_b, fc7
     R = int(conv_w.shape[0])
     if tuple(conv_w.shape) != (R, c, 1, 1, pz):
         raise ValueError("conv_w must be [R, %d, 1, 1, %d], got %s" % (c, pz, tuple(conv_w.shape)))
-    hw = ph * pw
-    if tuple(fc6_w.shape) != (int(fc6_w.shape[0]), R * hw):
-        raise ValueError("fc6_w must be [*, %d], got %s" % (R * hw, tuple(fc6_w.shape)))
+    return n, ph, pw, R
+
+
+def _conv_bn_rows(pooled, conv_w, conv_b, bn_w, bn_b, bn_state):
+    """Conv3d([1, 1, pz]) + BatchNorm3d + ReLU of the head on the pooled tensor, kept as rows [N ph pw, R] (3 launches)"""
+    from sparseconvnet.batchNormalization import BatchNormFunction
+    n, c, ph, pw, pz = (int(v) for v in pooled.shape)
+    R, hw = int(conv_w.shape[0]), ph * pw
     if bn_state.get("momentum") is None:
         raise ValueError("BatchNorm momentum None (cumulative average) is not part of this path")
     x1 = _Mlp.apply(pooled, conv_w.reshape(R, c * pz), conv_b, False, (hw, pz), 0)            # [N hw, R]
@@ -487,10 +545,105 @@ def box_head_mlp(pooled, conv_w, conv_b, bn_w, bn_b, bn_state, fc6_w, fc6_b, fc7
         rm = _hip.workspace("roi_mlp_bn", 2 * R, torch.float32, pooled.device)
         rm, rv = rm[:R], rm[R:2 * R]
     empty = pooled.new_empty(0)
-    x2 = BatchNormFunction.apply(x1, empty if bn_w is None else bn_w, empty if bn_b is None else bn_b, rm, rv,
-                                 (float(bn_state["eps"]), 1.0 - float(bn_state["momentum"]), train, 0))
-    x3 = _Mlp.apply(x2.view(n, hw * R), fc6_w, fc6_b, True, None, hw)
-    return _Mlp.apply(x3, fc7_w, fc7_b, True, None, 0)
+    return BatchNormFunction.apply(x1, empty if bn_w is None else bn_w, empty if bn_b is None else bn_b, rm, rv,
+                                   (float(bn_state["eps"]), 1.0 - float(bn_state["momentum"]), train, 0))
+
+
+CORNER_PW = 11                                   # roi_box_feature_extractors.py:93-94: roi_all_cor_body = [11, 3, 7]
+CORNER_WINDOWS = ((0, 8), 3)                     # cor0 = w 0..2 and cor1 = w 8..10: the two row blocks of one GEMM
+BODY_WINDOW = ((2,), 7)                          # body = w 2..8
+CORNER_OVERLAP = (2, 8)                          # the w positions both a corner and the body window hold
+
+
+def _window(n, ph, pw, R, w0, wlen):
+    win = _hip.AabrMlpWindow()
+    win.n_rois, win.ph, win.pw, win.R, win.wlen, win.blocks = n, ph, pw, R, wlen, len(w0)
+    win.w0[0], win.w0[1] = w0[0], w0[-1]
+    return win
+
+
+class _CornerFc6(torch.autograd.Function):
+    """fc6_cor over both corner windows (one GEMM, M = 2 n) and fc6_body over the body window of the convolution rows
+    x2 [n ph pw, R], each with ReLU: the windows are read in place (csrc/roi_mlp.hip, the window layout), the weights
+    packed once per call to the rows' column order, their gradients stored through the inverse permutation.
+    Backward: the input gradient is written by the body GEMM (w 2..8, stores) and then, on the same stream, by the
+    corner GEMM (w 0, 1, 9, 10 stores; w 2 and 8 added to the body's value): every element written, no zero fill, no
+    atomics."""
+
+    @staticmethod
+    def forward(ctx, x2, cor_w, cor_b, body_w, body_b, geom):
+        lib = _hip.load()
+        n, ph, pw, R = geom
+        x2 = x2.contiguous()
+        dev = x2.device
+        parts = []
+        for (w0, wlen), w, b in ((CORNER_WINDOWS, cor_w, cor_b), (BODY_WINDOW, body_w, body_b)):
+            w = w.contiguous()
+            N = int(w.shape[0])
+            wp = torch.empty_like(w)
+            check(lib.aabr_roi_mlp_pack_fc6(ptr(w), N, R, ph * wlen, ptr(wp), _hip.stream()))
+            y = torch.empty((len(w0) * n, N), dtype=torch.float32, device=dev)       # every element is written
+            win = _window(n, ph, pw, R, w0, wlen)
+            check(lib.aabr_roi_mlp_forward_window(ptr(x2), win, ptr(wp), ptr(b.contiguous() if b is not None else None),
+                                                  1, N, ptr(y), _hip.stream()))
+            parts.append((wp, y))
+        ctx.save_for_backward(x2, parts[0][0], parts[0][1], parts[1][0], parts[1][1])
+        ctx.cfg = (geom, cor_b is not None, body_b is not None)
+        return parts[0][1], parts[1][1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy_cor, dy_body):
+        lib = _hip.load()
+        x2, wp_cor, y_cor, wp_body, y_body = ctx.saved_tensors
+        (n, ph, pw, R), has_cb, has_bb = ctx.cfg
+        dev = x2.device
+        st = _hip.stream()
+        body = (BODY_WINDOW, wp_body, y_body, dy_body.contiguous(), has_bb, (-1, -1))
+        cor = (CORNER_WINDOWS, wp_cor, y_cor, dy_cor.contiguous(), has_cb, CORNER_OVERLAP)
+        d_x = None
+        if ctx.needs_input_grad[0]:
+            d_x = torch.empty_like(x2)                                               # body then corner write all of it
+            for (w0, wlen), wp, y, dy, _hb, acc in (body, cor):                     # this order: see the class docstring
+                win = _window(n, ph, pw, R, w0, wlen)
+                check(lib.aabr_roi_mlp_backward_input_window(ptr(dy), ptr(y), ptr(wp), win, int(wp.shape[0]), acc[0],
+                                                             acc[1], ptr(d_x), st))
+        grads = {}
+        for name, ((w0, wlen), wp, y, dy, has_b, _acc) in (("cor", cor), ("body", body)):
+            N, K, M = int(wp.shape[0]), int(wp.shape[1]), len(w0) * n
+            d_w = torch.empty((N, K), dtype=torch.float32, device=dev)
+            d_b = torch.empty(N, dtype=torch.float32, device=dev) if has_b else None
+            floats = int(lib.aabr_roi_mlp_dw_scratch_floats(M, N, K))
+            scr = _hip.workspace("roi_mlp_dw", floats, torch.float32, dev) if floats else None
+            win = _window(n, ph, pw, R, w0, wlen)
+            check(lib.aabr_roi_mlp_backward_weight_window(ptr(dy), ptr(y), ptr(x2), win, N, ph * wlen, ptr(d_w), ptr(d_b),
+                                                          ptr(scr), st))
+            grads[name] = (d_w, d_b)
+        return d_x, grads["cor"][0], grads["cor"][1], grads["body"][0], grads["body"][1], None
+
+
+def box_head_mlp_corner(pooled, conv_w, conv_b, bn_w, bn_b, bn_state, fc6_cor_w, fc6_cor_b, fc6_body_w, fc6_body_b,
+                        fc7_cor_w, fc7_cor_b, fc7_body_w, fc7_body_b):
+    """FPN2MLPFeatureExtractor.forward_corner_box after its pooler (roi_box_feature_extractors.py:122-147):
+      pooled [N, C, ph, 11, pz] -> Conv3d([1, 1, pz]) -> BatchNorm3d -> ReLU -> the three windows of the 11-wide axis
+      (cor0 = w 0..2, body = w 2..8, cor1 = w 8..10) -> fc6_cor / fc7_cor on both corners, fc6_body / fc7_body on the body
+    and returns (x_cor [2 N, R'], x_body [N, R']): rows 0 .. N-1 of x_cor are corner 0, rows N .. 2N-1 corner 1.
+    Parameters in the reference's layouts: fc6_cor_w [R', R ph 3], fc6_body_w [R', R ph 7] (columns in the (r, h, w) order
+    of `.contiguous().view(N, -1)`).  Convolution and BatchNorm as box_head_mlp; the windows are never made contiguous.
+    9 launches forward (GEMM, BatchNorm 2, pack 2, fc6 2, fc7 2), whatever N; N = 1 is the unsqueezed case (the
+    reference's squeeze() drops the ROI axis there)."""
+    _mlp_f32("box_head_mlp_corner", pooled=pooled, conv_w=conv_w, conv_b=conv_b, bn_w=bn_w, bn_b=bn_b,
+             fc6_cor_w=fc6_cor_w, fc6_cor_b=fc6_cor_b, fc6_body_w=fc6_body_w, fc6_body_b=fc6_body_b, fc7_cor_w=fc7_cor_w,
+             fc7_cor_b=fc7_cor_b, fc7_body_w=fc7_body_w, fc7_body_b=fc7_body_b)
+    n, ph, pw, R = _conv_shape(pooled, conv_w)
+    if pw != CORNER_PW:
+        raise ValueError("the corner windows need pw == %d, got pooled %s" % (CORNER_PW, tuple(pooled.shape)))
+    for name, w, wlen in (("fc6_cor_w", fc6_cor_w, CORNER_WINDOWS[1]), ("fc6_body_w", fc6_body_w, BODY_WINDOW[1])):
+        if w.dim() != 2 or int(w.shape[1]) != R * ph * wlen:
+            raise ValueError("%s must be [*, %d], got %s" % (name, R * ph * wlen, tuple(w.shape)))
+    x2 = _conv_bn_rows(pooled, conv_w, conv_b, bn_w, bn_b, bn_state)
+    y_cor, y_body = _CornerFc6.apply(x2, fc6_cor_w, fc6_cor_b, fc6_body_w, fc6_body_b, (n, ph, pw, R))
+    return (_Mlp.apply(y_cor, fc7_cor_w, fc7_cor_b, True, None, 0), _Mlp.apply(y_body, fc7_body_w, fc7_body_b, True, None, 0))
 
 
 def box_predictions(x, cls_w, cls_b, reg_w, reg_b):
@@ -512,9 +665,38 @@ def box_predictions(x, cls_w, cls_b, reg_w, reg_b):
     return y[:, :nc], y[:, nc:]
 
 
+def box_predictions_corner(x_cor, x_body, cls_w, cls_b, body_w, body_b, cor_w, cor_b, sem_w, sem_b, class_specific):
+    """FPNPredictor.forward_corner_box (roi_box_predictors.py:79-103) as two GEMMs: x_body [n, R] against cls_score_body
+    and bbox_pred_body concatenated along N, x_cor [2 n, R] (corner 0 rows, then corner 1 rows) against bbox_pred_cor
+    and bbox_corner_semantic concatenated.  Returns (scores [n, C], bbox_regression_corners, corner_semantics [n, 16]):
+    the regression is [cor0 xy, cor1 xy, body z0 z1 thickness] per class, [n, 7 C] when class specific, else [n, 7];
+    the semantics are corner 0's 8 then corner 1's 8.  score_pred_cor is not computed: the reference drops its result."""
+    _mlp_f32("box_predictions_corner", x_cor=x_cor, x_body=x_body, cls_w=cls_w, cls_b=cls_b, body_w=body_w, body_b=body_b,
+             cor_w=cor_w, cor_b=cor_b, sem_w=sem_w, sem_b=sem_b)
+    if x_cor.dim() != 2 or x_body.dim() != 2 or x_cor.shape[0] != 2 * x_body.shape[0] or x_cor.shape[1] != x_body.shape[1]:
+        raise ValueError("box_predictions_corner: x_cor [2 n, R] and x_body [n, R], got %s and %s"
+                         % (tuple(x_cor.shape), tuple(x_body.shape)))
+    _hip.require_gpu(x_body)
+    n, nc = int(x_body.shape[0]), int(cls_w.shape[0])
+    k = nc if class_specific else 1
+    if tuple(body_w.shape)[0] != 3 * k or tuple(cor_w.shape)[0] != 2 * k:
+        raise ValueError("box_predictions_corner: bbox_pred_body [%d, R] and bbox_pred_cor [%d, R]" % (3 * k, 2 * k))
+    yb = _Mlp.apply(x_body, torch.cat([cls_w, body_w]), torch.cat([cls_b, body_b]), False, None, 0)
+    yc = _Mlp.apply(x_cor, torch.cat([cor_w, sem_w]), torch.cat([cor_b, sem_b]), False, None, 0)
+    scores, bbox_body = yb[:, :nc], yb[:, nc:]
+    bbox_cor0, bbox_cor1 = yc[:n, :2 * k], yc[n:, :2 * k]
+    if class_specific:
+        reg = torch.cat([bbox_cor0.reshape(n, nc, 2), bbox_cor1.reshape(n, nc, 2), bbox_body.reshape(n, nc, 3)],
+                        2).view(n, -1)
+    else:
+        reg = torch.cat([bbox_cor0, bbox_cor1, bbox_body], 1)
+    return scores, reg, torch.cat([yc[:n, 2 * k:], yc[n:, 2 * k:]], 1)
+
+
 def box_head_cfg(C=8, resolution=(2, 3, 2), R=12, classes=("background", "wall", "door"), class_specific=True, separate=(),
                  corner=False, track=False, scales=(0.5, 0.25, 0.125), canonical=10.0, sampling=2, voxel_scale=1.0,
-                 extractor="FPN2MLPFeatureExtractor", predictor="FPNPredictor", eval_in_train=0, detections=20):
+                 extractor="FPN2MLPFeatureExtractor", predictor="FPNPredictor", eval_in_train=0, detections=20,
+                 loss_weights=(1.0, 1.0, 1.0, 1.0, 0.0, 0.0, 0.0)):
     """a plain attribute tree with the cfg keys the box head's modules read, named as in the reference's
     config/defaults.py -- for smoke(), the timing tool and the tests, which have no yacs config"""
     box_head = _Cfg(POOLER_RESOLUTION=tuple(resolution), POOLER_SCALES_SPATIAL=tuple(scales),
@@ -525,6 +707,7 @@ def box_head_cfg(C=8, resolution=(2, 3, 2), R=12, classes=("background", "wall",
                  LABEL_AUG_THICKNESS_Z_TAR_ANC=(0.0, 0.0), SCORE_THRESH=0.05, NMS=0.5, NMS_AUG_THICKNESS_Y_Z=(0.0, 0.0),
                  DETECTIONS_PER_IMG=detections)
     model = _Cfg(CORNER_ROI=corner, CLASS_SPECIFIC=class_specific, SEPARATE_CLASSES=list(separate), SEPARATE_CLASSES_ID=[],
-                 ROI_BOX_HEAD=box_head, ROI_HEADS=heads, LOSS=_Cfg(YAW_MODE="Diff"), RPN=_Cfg(ADD_GT_PROPOSALS=False))
+                 ROI_BOX_HEAD=box_head, ROI_HEADS=heads, LOSS=_Cfg(YAW_MODE="Diff", WEIGHTS=tuple(loss_weights)),
+                 RPN=_Cfg(ADD_GT_PROPOSALS=False))
     return _Cfg(MODEL=model, SPARSE3D=_Cfg(VOXEL_SCALE=voxel_scale, nPlaneMap=C), SOLVER=_Cfg(TRACK_RUNNING_STATS=track),
                 INPUT=_Cfg(CLASSES=list(classes)), DEBUG=_Cfg(eval_in_train=eval_in_train))

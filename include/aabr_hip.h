@@ -42,7 +42,11 @@ const char *aabr_last_error(void);
  * record only, no existing signature or layout changed, so a binding written for 640 still matches.  The box head's
  * dense layers (aabr_roi_mlp_*) and the RPN head (aabr_rpn_head_*, AabrRpnMap) came the same way: symbols only.  So did
  * the deferred-join tail of a launch plan (AABR_PLAN_TAIL, AABR_PLAN_TAIL_JOIN, aabr_plan_run_tail, aabr_plan_tail_*):
- * one flag bit and one record kind that no earlier list carries, four new symbols, AabrPlanOp unchanged. */
+ * one flag bit and one record kind that no earlier list carries, four new symbols, AabrPlanOp unchanged.  The corner
+ * form of the box coder (aabr_box_to_2corners, aabr_box_from_2corners, aabr_box_encode_corner, aabr_box_decode_corner,
+ * aabr_roi_targets_coder, aabr_roi_post_detections_coder) likewise: six new symbols, the older entry points being the
+ * centroid case of the same code; and fc6 over windows of the convolution rows (aabr_roi_mlp_*_window, AabrMlpWindow):
+ * three new symbols and one new record. */
 #define AABR_ABI_VERSION 640
 int aabr_version(void);
 /* Tuning knobs for experiments and tests (no counterpart in the reference; the defaults are what ships): CONV_WIDE,
@@ -846,6 +850,27 @@ int aabr_box_encode(const float *targets, const float *anchors, int64_t n, const
  * (one anchor per row, shared by its classes), yaw through limit_period(., 0.5, pi): out [n, 7*num_classes].         */
 int aabr_box_decode(const float *encodings, const float *anchors, int64_t n, int num_classes,
                     const float *weights_host, float clip, float *out, void *stream);
+/* The corner form of the coder (MODEL.CORNER_ROI; csrc/corner_box.h holds the per-box functions, host + device), on lists,
+ * one thread per box and no host read (the reference converts in a Python loop over boxes on the host).
+ * Two-corner boxes are [x0, y0, x1, y1, z0, z1, thickness]: the end points of the bottom centre line along the length.
+ *   aabr_box_to_2corners   Box3D_Torch.from_yxzb_to_2corners (utils3d/bbox3d_ops_torch.py:115-135): yx_zb [n,7] -> two
+ *                          corners [n,7]; rotation in fp64 rounded once to fp32 as numpy does it, yaw + pi/2 == 0 takes
+ *                          the unrotated branch, corner 0 is the end whose offset from the centroid has a component
+ *                          sum > 0 (strict: a tie swaps).
+ *   aabr_box_from_2corners Box3D_Torch.from_2corners_to_yxzb (:29-55,93-112): two corners [n,7] -> yx_zb [n,7] in the
+ *                          fp32 operations of the torch expressions (asin in fp64, narrowed); yaw in [-pi/2, pi/2).
+ *   aabr_box_encode_corner BoxCoder3D(True, w).encode (modeling/box_coder_3d.py:82-91) of yx_zb targets against yx_zb
+ *                          anchors, both [n,7]: second_corner_box_encode with smooth_dim between their two-corner forms,
+ *                          times weights_host[7].  A zero-length or zero-height anchor gives the IEEE inf / NaN.
+ *   aabr_box_decode_corner BoxCoder3D(True, w).decode (:93-122): encodings [n, 7*num_classes] / weights, elements 3..5
+ *                          clamped at `clip`, second_corner_box_decode with smooth_dim against the proposals' two corners
+ *                          (anchors [n,7] yx_zb, one per row, shared by its classes), back to yx_zb [n, 7*num_classes]. */
+int aabr_box_to_2corners(const float *boxes, int64_t n, float *out, void *stream);
+int aabr_box_from_2corners(const float *corners, int64_t n, float *out, void *stream);
+int aabr_box_encode_corner(const float *targets, const float *anchors, int64_t n, const float *weights_host, float *out,
+                           void *stream);
+int aabr_box_decode_corner(const float *encodings, const float *anchors, int64_t n, int num_classes,
+                           const float *weights_host, float clip, float *out, void *stream);
 /* RPN glue: anchors of the selected flat indices t = site*A + yaw, generated from
  * the sparse site coordinates (modeling/rpn/anchor_generator_sparse3d.py:88-104:
  * centroid = loc / voxel_scale * stride, + base anchor), fused with BoxCoder3D.decode_centroid_box
@@ -1067,6 +1092,16 @@ int aabr_roi_post_detections(const float *class_logits, const float *box_regress
                              int pre_max, int post_max, int detections_per_img, float *prob, float *boxes,
                              int64_t *det_rows, int64_t *det_labels, float *det_scores, float *det_boxes, int32_t *info,
                              int32_t *scratch, void *stream);
+/* The same with the coder's form as an argument: corner_coder = 0 is aabr_roi_post_detections itself; 1 decodes with
+ * BoxCoder3D(is_corner_roi=True).decode, the arithmetic of aabr_box_decode_corner (box_regression then holds two-corner
+ * encodings, proposals stay yx_zb and so do the decoded boxes).  Softmax, NMS, the per-scene cut and the five launches
+ * are the same code. */
+int aabr_roi_post_detections_coder(const float *class_logits, const float *box_regression, const float *proposals, int nb,
+                                   const int64_t *n_host, int C, int class_specific, const float *weights_host,
+                                   int corner_coder, float clip, float score_thresh, float nms_thresh, float nms_min_yx,
+                                   float nms_min_z, int only_xy, int pre_max, int post_max, int detections_per_img,
+                                   float *prob, float *boxes, int64_t *det_rows, int64_t *det_labels, float *det_scores,
+                                   float *det_boxes, int32_t *info, int32_t *scratch, void *stream);
 
 /* ---- Box-head loss (csrc/roi_loss.hip): FastRCNNLossComputation of the box head
  * (modeling/roi_heads/box_head_3d/loss.py:137-382, the non-separated path) in two stages, `subsample` and `__call__`.
@@ -1108,6 +1143,17 @@ int aabr_roi_targets(const float *proposals, const float *targets, const int64_t
                      int num_pos_max, int64_t *matched_idx, float *matched_val, int64_t *labels,
                      float *regression_targets, float *iou_out, int64_t *samp_rows, int64_t *samp_labels,
                      float *samp_targets, float *samp_boxes, int32_t *info, int32_t *scratch, void *stream);
+/* The same with the coder's form as an argument: corner_coder = 0 is aabr_roi_targets itself; 1 makes the regression
+ * targets BoxCoder3D(is_corner_roi=True).encode(target[max(matched_idx, 0)], proposal), bit-equal to
+ * aabr_box_encode_corner on the same rows.  Matching, labels, the sampler, the compaction and the launch count (1 memset
+ * + 6 kernels) do not depend on it. */
+int aabr_roi_targets_coder(const float *proposals, const float *targets, const int64_t *target_labels, int nb,
+                           const int64_t *n_host, const int64_t *g_host, const float *aug_host, int criterion,
+                           int only_xy, float fg_iou, float bg_iou, const float *weights_host, int corner_coder,
+                           uint32_t seed, int batch_size_per_image, int num_pos_max, int64_t *matched_idx,
+                           float *matched_val, int64_t *labels, float *regression_targets, float *iou_out,
+                           int64_t *samp_rows, int64_t *samp_labels, float *samp_targets, float *samp_boxes,
+                           int32_t *info, int32_t *scratch, void *stream);
 /* Stage 2 (loss.py:295-382): class_logits [n, C], box_regression [n, 7 C] (class_specific != 0) or [n, 7], both fp32
  * (input_bf16 = 0) or bf16 (1), arithmetic fp32; labels int64 [n]; regression_targets fp32 [n, 7]; beta > 0 (the
  * reference: 1 / 5).
@@ -1182,6 +1228,37 @@ int aabr_roi_mlp_backward_weight(const float *dY, const float *Y, const float *A
                                  int64_t M, int64_t N, int64_t K, int64_t perm_hw, float *dW, float *db, float *scratch,
                                  void *stream);
 int aabr_roi_mlp_pack_fc6(const float *W, int64_t N, int64_t R, int64_t hw, float *Wp, void *stream);
+/* fc6 over WINDOWS of the convolution rows: the corner form of the box head (MODEL.CORNER_ROI,
+ * roi_box_feature_extractors.py:122-147).  X is the convolution + BatchNorm result kept as rows [n_rois ph pw, R]; the
+ * extractor cuts the pw (= 11) axis into cor0 = w 0..2, body = w 2..8, cor1 = w 8..10 and runs an fc6 on each part made
+ * contiguous.  Here a window [w0, w0 + wlen) is a third operand layout of the same GEMM template, read and written in
+ * place: row m of the operand is ROI n's window, column k = (h wlen + wl) R + r is X[(n ph + h) pw + w0 + wl][r], so
+ * K = ph wlen R and the packed weight is aabr_roi_mlp_pack_fc6 with hw = ph wlen.  `blocks` = 2 stacks two windows that
+ * share a weight into one GEMM with M = 2 n_rois: rows 0 .. n_rois - 1 use w0[0], rows n_rois .. 2 n_rois - 1 use w0[1]
+ * on ROI m - n_rois (the two corners: w0 = {0, 8}).  Limits: ph, pw, R, wlen >= 1, 0 <= w0, w0 + wlen <= pw, K % 4 == 0,
+ * ph pw R and M below 2^31 - 256; otherwise AABR_EINVAL.  Tile and split decisions are those of the dense entry points
+ * at the same (M, N, K).
+ * aabr_roi_mlp_forward_window:         Y [M, N] = act(Xwin W^T + bias).                                 1 launch.
+ * aabr_roi_mlp_backward_weight_window: dW, db and scratch as aabr_roi_mlp_backward_weight.     1 launch, 2 when split.
+ * aabr_roi_mlp_backward_input_window:  (dY . mask) W stored into the windows of dX in place.  acc_w0 / acc_w1: absolute
+ *   w positions (or -1) at which the value is ADDED to what dX holds instead of stored -- the windows of the head overlap
+ *   at w = 2 and w = 8.  The order that makes dX complete without a zero fill and without atomics: the body GEMM
+ *   (w0 = 2, wlen = 7, acc -1, -1) first, then on the same stream the corner GEMM (w0 = {0, 8}, wlen = 3, acc 2, 8), which
+ *   stores w 0, 1, 9, 10 and adds into w 2 and 8; each element is touched by one thread per launch, so two runs give the
+ *   same bits.  The windows of a two-block call may not overlap each other.                              1 launch. */
+typedef struct AabrMlpWindow {
+  int64_t n_rois;
+  int32_t ph, pw, R;           /* the convolution rows are [n_rois ph pw, R]                                          */
+  int32_t wlen;                /* window length along the pw axis                                                     */
+  int32_t blocks;              /* 1 or 2 row blocks of n_rois rows each                                               */
+  int32_t w0[2];               /* first w of each block's window (w0[1] ignored when blocks == 1)                     */
+} AabrMlpWindow;
+int aabr_roi_mlp_forward_window(const float *X, const AabrMlpWindow *win, const float *W, const float *bias, int relu,
+                                int64_t N, float *Y, void *stream);
+int aabr_roi_mlp_backward_input_window(const float *dY, const float *Y, const float *W, const AabrMlpWindow *win,
+                                       int64_t N, int acc_w0, int acc_w1, float *dX, void *stream);
+int aabr_roi_mlp_backward_weight_window(const float *dY, const float *Y, const float *X, const AabrMlpWindow *win,
+                                        int64_t N, int64_t perm_hw, float *dW, float *db, float *scratch, void *stream);
 
 /* ---- the RPN head (csrc/rpn_head.hip): SingleConvRPNHead_Sparse3D (modeling/rpn/rpn_sparse3d.py:81-131) over the rows
  * of every feature map in one launch, fp32 storage only, on v_mfma_f32_32x32x2_f32 (every element an exact fmaf chain):
