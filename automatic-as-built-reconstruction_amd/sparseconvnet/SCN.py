@@ -1716,3 +1716,118 @@ def SparseToDense_updateGradInput(spatial_size, metadata, input_features, d_inpu
     check(_hip.load().aabr_sparse_to_dense_backward(ptr(g.coords), g.V, ptr(d_input_features),
                                                     input_features.size(1), _hip.i32x3(_key(spatial_size)),
                                                     ptr(d_out), stream()))
+
+
+# ------------------------------------------------------------------------------------------------
+# MaxPooling / AveragePooling / UnPooling (pybind.cpp:33-53,171-180; SCN/CPU/MaxPooling.cpp, AveragePooling.cpp,
+# UnPooling.cpp): csrc/pool.hip -- every pass is ONE gather launch over one table of the strided rule book, which is cached
+# under the key of a Convolution of that size and stride (a pooling layer and a strided convolution onto the same level
+# share grid and tables).
+# ------------------------------------------------------------------------------------------------
+POOL_MAX0, POOL_SUM = 0, 1     # csrc/pool.hip modes
+
+
+def _pool_drop(features, nFeaturesToDrop, what):
+    drop = int(nFeaturesToDrop)
+    if features.dim() != 2 or not 0 <= drop < features.size(1):
+        raise ValueError("%s: nFeaturesToDrop = %d of a feature matrix of shape %s" % (what, drop, tuple(features.shape)))
+    return drop
+
+
+def _pool_gather(src, col0, planes, gather, mode, div, dst, dst_col0, dst_width):
+    """dst[gather.rows, dst_width] <- the reduction of src[:, col0:col0 + planes] over `gather` (one launch; none for an
+    empty destination)"""
+    _same_dtype(src, dst, "pooling")
+    dst.resize_(gather.rows, dst_width)
+    if gather.rows == 0:
+        return
+    flush_geom()
+    check(_hip.load().aabr_pool_gather(ptr(src), int(src.dtype == torch.bfloat16), src.size(1), col0, planes,
+                                       ptr(gather.table), gather.vol, gather.rows, mode, float(div), ptr(dst), dst_width,
+                                       dst_col0, dst_width, stream()))
+
+
+def MaxPooling_updateOutput(inputSize, outputSize, poolSize, poolStride, metadata, input_features, output_features,
+                            nFeaturesToDrop):
+    inp = _featc(input_features, "input_features")
+    drop = _pool_drop(inp, nFeaturesToDrop, "MaxPooling")
+    tb = metadata.getRuleBook(inputSize, outputSize, poolSize, poolStride)
+    _pool_gather(inp, drop, inp.size(1) - drop, tb.out, POOL_MAX0, 0.0, output_features, 0, inp.size(1) - drop)
+
+
+def MaxPooling_updateGradInput(inputSize, outputSize, poolSize, poolStride, metadata, input_features, d_input_features,
+                               output_features, d_output_features, nFeaturesToDrop):
+    """every input that equals its window's output receives the window's gradient; the comparison is on the columns the
+    forward pass read (the reference's CPU kernel compares unshifted columns when nFeaturesToDrop > 0: not reproduced)"""
+    inp = _featc(input_features, "input_features")
+    out = _featc(output_features, "output_features")
+    d_out = _featc(d_output_features, "d_output_features")
+    drop = _pool_drop(inp, nFeaturesToDrop, "MaxPooling")
+    planes = inp.size(1) - drop
+    _same_dtype(inp, out, "MaxPooling backward")
+    _same_dtype(inp, d_out, "MaxPooling backward")
+    _same_dtype(inp, d_input_features, "MaxPooling backward")
+    tb = metadata.getRuleBook(inputSize, outputSize, poolSize, poolStride)
+    if tuple(out.shape) != (tb.V_out, planes) or tuple(d_out.shape) != (tb.V_out, planes) or inp.size(0) != tb.V_in:
+        raise ValueError("MaxPooling backward: shapes %s / %s / %s do not fit the rule book (%d -> %d rows, %d planes)"
+                         % (tuple(inp.shape), tuple(out.shape), tuple(d_out.shape), tb.V_in, tb.V_out, planes))
+    d_input_features.resize_(tb.V_in, inp.size(1))
+    if tb.V_in == 0:
+        return
+    flush_geom()
+    check(_hip.load().aabr_pool_max_backward(ptr(inp), ptr(out), ptr(d_out), int(inp.dtype == torch.bfloat16), inp.size(1),
+                                             drop, planes, ptr(tb.inn.table), tb.vol, tb.V_in, ptr(d_input_features),
+                                             stream()))
+
+
+def AveragePooling_updateOutput(inputSize, outputSize, poolSize, poolStride, metadata, input_features, output_features,
+                                nFeaturesToDrop):
+    inp = _featc(input_features, "input_features")
+    drop = _pool_drop(inp, nFeaturesToDrop, "AveragePooling")
+    tb = metadata.getRuleBook(inputSize, outputSize, poolSize, poolStride)
+    _pool_gather(inp, drop, inp.size(1) - drop, tb.out, POOL_SUM, tb.vol, output_features, 0, inp.size(1) - drop)
+
+
+def AveragePooling_updateGradInput(inputSize, outputSize, poolSize, poolStride, metadata, input_features,
+                                   d_input_features, d_output_features, nFeaturesToDrop):
+    d_out = _featc(d_output_features, "d_output_features")
+    drop = _pool_drop(input_features, nFeaturesToDrop, "AveragePooling")
+    planes = input_features.size(1) - drop
+    tb = metadata.getRuleBook(inputSize, outputSize, poolSize, poolStride)
+    if tuple(d_out.shape) != (tb.V_out, planes) or input_features.size(0) != tb.V_in:
+        raise ValueError("AveragePooling backward: shapes %s / %s do not fit the rule book (%d -> %d rows, %d planes)"
+                         % (tuple(input_features.shape), tuple(d_out.shape), tb.V_in, tb.V_out, planes))
+    _pool_gather(d_out, 0, planes, tb.inn, POOL_SUM, tb.vol, d_input_features, drop, input_features.size(1))
+
+
+def _unpool_book(outputSize, inputSize, poolSize, poolStride, metadata):
+    """the book (fine, coarse, size, stride) an UnPooling from the coarse level `inputSize` reads; the fine level must exist"""
+    if getattr(metadata, "_inb", None) is not None:
+        metadata._materialise_input(torch.device("cuda", torch.cuda.current_device()))
+    if _key(outputSize) not in metadata.grids:
+        raise RuntimeError("UnPooling: the metadata holds no level of spatial size %s to unpool onto (UnPooling returns to "
+                           "a level that a pooling or a strided convolution has come from)" % (list(_key(outputSize)),))
+    return metadata.getRuleBook(outputSize, inputSize, poolSize, poolStride)
+
+
+def UnPooling_updateOutput(inputSize, outputSize, poolSize, poolStride, metadata, input_features, output_features,
+                           nFeaturesToDrop):
+    inp = _featc(input_features, "input_features")
+    drop = _pool_drop(inp, nFeaturesToDrop, "UnPooling")
+    tb = _unpool_book(outputSize, inputSize, poolSize, poolStride, metadata)
+    if inp.size(0) != tb.V_out:
+        raise ValueError("UnPooling: %d feature rows on a level of %d sites" % (inp.size(0), tb.V_out))
+    _pool_gather(inp, drop, inp.size(1) - drop, tb.inn, POOL_SUM, 0.0, output_features, 0, inp.size(1) - drop)
+
+
+def UnPooling_updateGradInput(inputSize, outputSize, poolSize, poolStride, metadata, d_input_features, d_output_features,
+                              nFeaturesToDrop):
+    """`d_input_features` arrives with the input's shape (unPooling.py sizes it); every element of it is written"""
+    d_out = _featc(d_output_features, "d_output_features")
+    drop = _pool_drop(d_input_features, nFeaturesToDrop, "UnPooling")
+    planes = d_input_features.size(1) - drop
+    tb = _unpool_book(outputSize, inputSize, poolSize, poolStride, metadata)
+    if tuple(d_out.shape) != (tb.V_in, planes) or d_input_features.size(0) != tb.V_out:
+        raise ValueError("UnPooling backward: shapes %s / %s do not fit the rule book (%d <- %d rows, %d planes)"
+                         % (tuple(d_input_features.shape), tuple(d_out.shape), tb.V_out, tb.V_in, planes))
+    _pool_gather(d_out, 0, planes, tb.out, POOL_SUM, 0.0, d_input_features, drop, d_input_features.size(1))

@@ -1387,6 +1387,34 @@ int aabr_det_eval_curves(const int64_t *sorted_key, const int64_t *order, const 
                          double *rows, int64_t *cls, void *stream);
 int aabr_det_eval_scan_chunk(void);
 
+/* ---- sparse pooling (csrc/pool.hip): MaxPooling, AveragePooling and UnPooling of the reference (SCN/CPU/MaxPooling.cpp,
+ * AveragePooling.cpp, UnPooling.cpp), forward and backward, each pass ONE gather launch over one table of a strided rule
+ * book (table int32 [vol][rows]: the source row per destination row and filter offset, -1 where absent).  No atomics, no
+ * memset, no host read: every destination element is written once, bit-identical run to run.
+ *
+ * aabr_pool_gather:  dst[r, dst_col0 + c] = reduce over o = 0 .. vol-1 ascending, for table[o][r] >= 0, of
+ *   x = src[table[o][r] * src_stride + col0 + c], c in [0, planes):
+ *   mode 0 (MAX0)  acc = +0.0f; if (acc < x) acc = x      -> max(0, inputs), a NaN input is ignored
+ *   mode 1 (SUM)   acc = +0.0f; acc += x / div            (div > 0: one correctly rounded fp32 division per term);
+ *                  div == 0: acc += x                      (no division at all)
+ *   The columns of dst rows outside [dst_col0, dst_col0 + planes) up to dst_width are written 0.
+ *   MaxPooling / AveragePooling forward: the book's `out` table (div = vol for the average); AveragePooling backward: its
+ *   `inn` table, div = vol; UnPooling forward: `inn` of the book (fine, coarse, size, stride), div = 0; its backward: `out`.
+ * aabr_pool_max_backward (over the book's `inn` table, rows_in input rows):
+ *   dx[r, col0 + c] = sum over o ascending, for orow = table_in[o][r] >= 0, of
+ *                     (y[orow, c] == x[r, col0 + c]) ? dy[orow, c] : 0     (+0.0 == -0.0; a NaN never matches)
+ *   x and dx [rows_in, x_stride] with x_stride == col0 + planes, y and dy [*, planes]; dx[:, 0 .. col0) = 0.
+ * bf16 != 0: every feature pointer holds bf16 (widened to fp32, the same fp32 operations, one round-to-nearest-even at
+ * the store; the comparison is on the stored values); else fp32.  16-byte accesses when planes, column offsets and row
+ * strides are multiples of 4 (fp32) / 8 (bf16) and the bases are 16-byte aligned, one element per lane otherwise.
+ * Zero destination rows: AABR_OK without a launch.  Refused with AABR_EINVAL before any launch: planes <= 0, vol <= 0, an
+ * unknown mode, div < 0, a negative row count, columns outside their row, a null pointer with rows > 0.                 */
+int aabr_pool_gather(const void *src, int bf16, int64_t src_stride, int col0, int planes, const int32_t *table, int vol,
+                     int64_t rows_dst, int mode, float div, void *dst, int64_t dst_stride, int dst_col0, int dst_width,
+                     void *stream);
+int aabr_pool_max_backward(const void *x, const void *y, const void *dy, int bf16, int64_t x_stride, int col0, int planes,
+                           const int32_t *table_in, int vol, int64_t rows_in, void *dx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
