@@ -236,6 +236,18 @@ _SIGS = {
     "aabr_roi_box_loss_scratch_floats": (C.c_int64, []),
     "aabr_roi_box_loss_forward": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
     "aabr_roi_box_loss_backward": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "aabr_roi_gt_group_keys": (C.c_int, [_vp, _i32, _i64p, _i32, _i32, _i32p, _i32p, _vp, _vp]),
+    "aabr_roi_targets_grouped": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i64p, _i64p, _f32p, _i32, _i32, _f32, _f32,
+                                           _f32p, _i32, C.c_uint32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _vp]),
+    "aabr_roi_box_loss_grouped_scratch_floats": (C.c_int64, []),
+    "aabr_roi_box_loss_grouped_forward": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _i32p, _i32p, _vp, _vp, _vp, _f32,
+                                                    _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aabr_roi_box_loss_grouped_backward": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _i32p, _i32p, _vp, _vp, _vp, _f32,
+                                                     _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aabr_roi_post_detections_grouped": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64p, _i32, _i32, _i32p, _i32p, _f32p, _i32,
+                                                   _f32, _f32, _f32, _f32, _f32, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
+                                                   _vp, _vp, _vp, _vp, _vp, _vp]),
     "aabr_roi_pool_prepare": (C.c_int, [_vp, _i32, C.POINTER(C.c_int64), _f32, _i32, _f32p, _f32, _vp, _vp, _vp]),
     "aabr_roi_pool_forward": (C.c_int, [_lvp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "aabr_roi_pool_backward": (C.c_int, [_lvp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i64,

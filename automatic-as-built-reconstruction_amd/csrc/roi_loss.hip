@@ -23,10 +23,16 @@
 // row order, a fixed tree per workgroup, the workgroups' sums added in order by one thread: bit-identical run to run.
 // The backward writes every element of both gradients (zeros included), so the caller fills nothing.
 // A label outside [0, C) is never used as an index: the row is skipped and a flag word is raised.
+//
+// With separated-classifier groups (sep_groups.h; the reference's seperate_classifier.py loops over the groups around the
+// code above) both stages have a grouped form of the same launch counts: stage 1 runs over (scene, group) segments with
+// the scene's ground truth filtered by group on the device (k_roi_gt_keys, the caller's stable sort, k_roi_match<.., true>);
+// stage 2 keeps one accumulator set per group (k_roi_sep_loss_*).
 #include "common.h"
 #include "iou_math.h"
 #include "nms_shared.h"
 #include "sample_shared.h"
+#include "sep_groups.h"
 
 namespace aabr {
 
@@ -62,22 +68,48 @@ constexpr int kRoiPropsPerBlock = 256 / kRoiLanes;
 
 // kCorner: the regression targets are BoxCoder3D(is_corner_roi=True).encode (box_encode7_corner, corner_box.h) instead of
 // the centroid encode; matching and labels are the same statements in both instances.
-template <bool kCorner>
+// kGrouped (aabr_roi_targets_grouped): a "scene" is a segment s = scene * groups + group, p.gt_begin[s] is its SCENE's
+// first ground-truth row, and the segment's ground truth is a run of the batch's ground truth sorted by group key
+// (k_roi_gt_keys): sorted positions lo .. lo + G of gt.keys, found here by two binary searches -- the host never
+// learns a group's count.  Sorted position k stands for the ground-truth row gt.perm[k] of the batch and carries its
+// group-local label in the key's low bits; matched_idx reports the row in the scene's own list.
+struct RoiGroupedGt {
+  const int64_t *keys, *perm;        // [total], ascending keys; null when not grouped
+  int64_t total;
+};
+template <bool kCorner, bool kGrouped>
 __global__ __launch_bounds__(256) void k_roi_match(RoiTargetParams p, const float *__restrict__ proposals,
                                                    const float *__restrict__ targets,
-                                                   const int64_t *__restrict__ target_labels,
+                                                   const int64_t *__restrict__ target_labels, RoiGroupedGt gt,
                                                    int64_t *__restrict__ matched_idx, float *__restrict__ matched_val,
                                                    int64_t *__restrict__ labels, float *__restrict__ reg_targets,
                                                    float *__restrict__ iou_out) {
   __shared__ float s_t5[kRoiTgtChunk][5];
   __shared__ float s_tz[kRoiTgtChunk][2];
+  __shared__ int64_t s_rng[2];
   const int b = blockIdx.y;
   const int64_t N = p.n[b];
   if ((int64_t)blockIdx.x * kRoiPropsPerBlock >= N) return;   // grid.x is sized for the largest scene (workgroup-uniform)
   const int lane = threadIdx.x % kRoiLanes;
   const int64_t t = (int64_t)blockIdx.x * kRoiPropsPerBlock + threadIdx.x / kRoiLanes;
-  const int G = p.g[b];
-  const float *tg = targets + 7 * p.gt_begin[b];
+  int64_t lo = 0;                                      // kGrouped: the segment's first sorted position
+  int G = p.g[b];
+  if (kGrouped) {
+    if (threadIdx.x < 2) {                             // lower_bound of the segment's first key and of the next one's
+      const int64_t want = (int64_t)(b + (int)threadIdx.x) * kSepMaxCols;
+      int64_t l = 0, h = gt.total;
+      while (l < h) {
+        const int64_t m = (l + h) >> 1;
+        if (gt.keys[m] < want) l = m + 1; else h = m;
+      }
+      s_rng[threadIdx.x] = l;
+    }
+    __syncthreads();
+    lo = s_rng[0];
+    G = (int)(s_rng[1] - s_rng[0]);
+  }
+  const float *tg = kGrouped ? targets : targets + 7 * p.gt_begin[b];
+  const auto gt_row = [&](int64_t k) -> int64_t { return kGrouped ? gt.perm[lo + k] : k; };   // row of `tg`
   float an[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   float a5[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, az0 = 0.f, az1 = 0.f;
   if (t < N) {
@@ -96,7 +128,7 @@ __global__ __launch_bounds__(256) void k_roi_match(RoiTargetParams p, const floa
     const int gn = G - g0 < kRoiTgtChunk ? G - g0 : kRoiTgtChunk;
     __syncthreads();
     if ((int)threadIdx.x < gn) {
-      const float *tb = tg + 7 * (int64_t)(g0 + threadIdx.x);
+      const float *tb = tg + 7 * gt_row(g0 + threadIdx.x);
       const float th = tb[3] < p.aug[0] ? p.aug[0] : tb[3];
       const float h = tb[5] < p.aug[1] ? p.aug[1] : tb[5];
       s_t5[threadIdx.x][0] = tb[0]; s_t5[threadIdx.x][1] = tb[1]; s_t5[threadIdx.x][2] = th;
@@ -139,10 +171,11 @@ __global__ __launch_bounds__(256) void k_roi_match(RoiTargetParams p, const floa
     return;
   }
   const int64_t mi = best < p.bg ? -1 : (best < p.fg ? -2 : best_g);   // BELOW_LOW_THRESHOLD / BETWEEN_THRESHOLDS
-  matched_idx[o] = mi;
+  matched_idx[o] = kGrouped && mi >= 0 ? gt_row(mi) - p.gt_begin[b] : mi;
   matched_val[o] = best;
-  labels[o] = mi >= 0 ? target_labels[p.gt_begin[b] + mi] : (mi == -1 ? 0 : -1);
-  const float *tb = tg + 7 * (mi < 0 ? 0 : mi);        // target[matched_idxs.clamp(min=0)]: the un-thickened boxes
+  if (kGrouped) labels[o] = mi >= 0 ? (gt.keys[lo + mi] & (kSepMaxCols - 1)) : (mi == -1 ? 0 : -1);
+  else labels[o] = mi >= 0 ? target_labels[p.gt_begin[b] + mi] : (mi == -1 ? 0 : -1);
+  const float *tb = tg + 7 * gt_row(mi < 0 ? 0 : mi);  // target[matched_idxs.clamp(min=0)]: the un-thickened boxes
   float g7[7], e[7];
 #pragma unroll
   for (int d = 0; d < 7; ++d) g7[d] = tb[d];
@@ -320,6 +353,140 @@ __global__ __launch_bounds__(256) void k_roi_loss_backward(const void *__restric
   }
 }
 
+// ---- stage 2 with separated-classifier groups (SeperateClassifier.roi_cross_entropy_seperated / roi_box_loss_seperated):
+// row i belongs to group sep_id[i]; its cross-entropy runs over that group's columns of the C_tot logits in group-local
+// order with the target column cols[g][label], its box term (class-agnostic regression [n, 7]) counts when label > 0, and
+// both sums of a group are divided by the group's row count n_g, counted here.  Same launches and the same fixed
+// summation order as the plain form, with one accumulator set per group.  A row whose sep_id is outside [0, G) is in no
+// group; a row whose label is outside [0, class_nums[g]) counts in n_g (as such a row counts in n above) and adds nothing.
+// Neither is used as an index; both raise the flag.
+constexpr int kSepPartWords = 3 * kSepMaxGroups + 1;   // per workgroup: cls [8], box [8], rows [8] (int32 bits), flag
+
+__device__ inline RoiRow sep_row_softmax(const void *logits, int64_t i, const SepGroups &q, int g, int bf16) {
+  const int cn = q.class_nums[g];
+  const int64_t o = i * q.C_tot;
+  RoiRow r;
+  r.m = ld(logits, o + q.cols[g][0], bf16);
+  for (int k = 1; k < cn; ++k) r.m = fmaxf(r.m, ld(logits, o + q.cols[g][k], bf16));
+  r.s = 0.f;
+  for (int k = 0; k < cn; ++k) r.s += expf(ld(logits, o + q.cols[g][k], bf16) - r.m);
+  return r;
+}
+
+__global__ __launch_bounds__(256) void k_roi_sep_loss_partial(const void *__restrict__ logits, const void *__restrict__ reg,
+                                                              int bf16, int64_t n, SepGroups q,
+                                                              const int32_t *__restrict__ sep_id,
+                                                              const int64_t *__restrict__ labels,
+                                                              const float *__restrict__ targets, float beta,
+                                                              float *__restrict__ partial) {
+  __shared__ float s_red[2][256];
+  __shared__ int s_cnt[256];
+  __shared__ int s_bad;
+  const int t = threadIdx.x;
+  if (t == 0) s_bad = 0;
+  float cls[kSepMaxGroups], box[kSepMaxGroups];
+  int cnt[kSepMaxGroups];
+#pragma unroll
+  for (int g = 0; g < kSepMaxGroups; ++g) { cls[g] = 0.f; box[g] = 0.f; cnt[g] = 0; }
+  bool bad = false;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n; i += (int64_t)gridDim.x * 256) {
+    const int sid = sep_id[i];
+    if (sid < 0 || sid >= q.G) { bad = true; continue; }
+    const int64_t l = labels[i];
+    float c = 0.f, b = 0.f;
+    if (l < 0 || l >= q.class_nums[sid]) {
+      bad = true;
+    } else {
+      const RoiRow r = sep_row_softmax(logits, i, q, sid, bf16);
+      c = (r.m + logf(r.s)) - ld(logits, i * q.C_tot + q.cols[sid][l], bf16);
+      if (l > 0)
+        for (int d = 0; d < 7; ++d) b += smooth_l1_term(fabsf(ld(reg, i * 7 + d, bf16) - targets[i * 7 + d]), beta);
+    }
+#pragma unroll
+    for (int g = 0; g < kSepMaxGroups; ++g)            // (a register per group: no dynamically indexed array)
+      if (g == sid) { cls[g] += c; box[g] += b; cnt[g] += 1; }
+  }
+  __syncthreads();
+  if (bad) s_bad = 1;                                  // (every writer stores the same value)
+  float *out = partial + (int64_t)kSepPartWords * blockIdx.x;
+#pragma unroll
+  for (int g = 0; g < kSepMaxGroups; ++g) {
+    if (g >= q.G) break;                               // workgroup-uniform
+    __syncthreads();
+    s_red[0][t] = cls[g];
+    s_red[1][t] = box[g];
+    s_cnt[t] = cnt[g];
+    for (int w = 128; w > 0; w >>= 1) {
+      __syncthreads();
+      if (t < w) { s_red[0][t] += s_red[0][t + w]; s_red[1][t] += s_red[1][t + w]; s_cnt[t] += s_cnt[t + w]; }
+    }
+    if (t == 0) {
+      out[g] = s_red[0][0];
+      out[kSepMaxGroups + g] = s_red[1][0];
+      out[2 * kSepMaxGroups + g] = __int_as_float(s_cnt[0]);
+    }
+  }
+  __syncthreads();
+  if (t == 0) out[3 * kSepMaxGroups] = s_bad ? 1.f : 0.f;
+}
+
+// thread g: group g's sums in workgroup order, / n_g (0 / 0 = NaN for a group without rows); rows[g] = n_g for the backward
+__global__ __launch_bounds__(64) void k_roi_sep_loss_finalize(int nblocks, int G, const float *__restrict__ partial,
+                                                              float *__restrict__ cls_loss, float *__restrict__ box_loss,
+                                                              int32_t *__restrict__ rows, int32_t *__restrict__ flag) {
+  const int g = threadIdx.x;
+  if (g >= G) return;
+  float cls = 0.f, box = 0.f;
+  int cnt = 0, bad = 0;
+  for (int i = 0; i < nblocks; ++i) {
+    const float *in = partial + (int64_t)kSepPartWords * i;
+    cls += in[g];
+    box += in[kSepMaxGroups + g];
+    cnt += __float_as_int(in[2 * kSepMaxGroups + g]);
+    bad |= in[3 * kSepMaxGroups] != 0.f;
+  }
+  cls_loss[g] = cls / (float)cnt;
+  box_loss[g] = box / (float)cnt;
+  rows[g] = cnt;
+  if (g == 0) *flag = bad;
+}
+
+// one thread per row writes the row's C_tot logit gradients and its 7 regression gradients: zeros in every column outside
+// the row's group, and in the whole row when its sep_id or label is out of range
+__global__ __launch_bounds__(256) void k_roi_sep_loss_backward(const void *__restrict__ logits, const void *__restrict__ reg,
+                                                               int bf16, int64_t n, SepGroups q,
+                                                               const int32_t *__restrict__ sep_id,
+                                                               const int64_t *__restrict__ labels,
+                                                               const float *__restrict__ targets, float beta,
+                                                               const int32_t *__restrict__ rows,
+                                                               const float *__restrict__ g_cls, const float *__restrict__ g_box,
+                                                               void *__restrict__ grad_logits, void *__restrict__ grad_reg) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int C = q.C_tot;
+  const int sid = sep_id[i];
+  const int64_t l = labels[i];
+  const bool ok = sid >= 0 && sid < q.G && l >= 0 && l < q.class_nums[sid];
+  for (int k = 0; k < C; ++k) st(grad_logits, i * C + k, 0.f, bf16);
+  float gb = 0.f;
+  if (ok) {                                            // the group's own columns, over the zeros just written
+    const float ng = (float)rows[sid];
+    const RoiRow r = sep_row_softmax(logits, i, q, sid, bf16);
+    const float gc = g_cls[sid] / ng;
+    gb = g_box[sid] / ng;
+    for (int k = 0; k < q.class_nums[sid]; ++k) {
+      const int64_t o = i * C + q.cols[sid][k];
+      const float pk = expf(ld(logits, o, bf16) - r.m) / r.s;
+      st(grad_logits, o, (pk - (k == l ? 1.f : 0.f)) * gc, bf16);
+    }
+  }
+  for (int d = 0; d < 7; ++d) {
+    float v = 0.f;
+    if (ok && l > 0) v = smooth_l1_grad(ld(reg, i * 7 + d, bf16) - targets[i * 7 + d], beta) * gb;
+    st(grad_reg, i * 7 + d, v, bf16);
+  }
+}
+
 }  // namespace
 
 }  // namespace aabr
@@ -332,50 +499,60 @@ extern "C" int64_t aabr_roi_targets_scratch_words(int nb) {
   return aabr_rpn_loss_scratch_words(nb) + (int64_t)nb * (2 * kLossMaxB + kInfoWords) + 2;
 }
 
-extern "C" int aabr_roi_targets_coder(const float *proposals, const float *targets, const int64_t *target_labels, int nb,
-                                      const int64_t *n_host, const int64_t *g_host, const float *aug_host, int criterion,
-                                      int only_xy, float fg_iou, float bg_iou, const float *weights_host,
-                                      int corner_coder, uint32_t seed, int batch_size_per_image, int num_pos_max,
-                                      int64_t *matched_idx, float *matched_val, int64_t *labels,
-                                      float *regression_targets, float *iou_out, int64_t *samp_rows,
-                                      int64_t *samp_labels, float *samp_targets, float *samp_boxes, int32_t *info,
-                                      int32_t *scratch, void *stream_) {
-  hipStream_t st = (hipStream_t)stream_;
-  AABR_CHECK_ARG(corner_coder == 0 || corner_coder == 1, "corner_coder must be 0 (centroid) or 1 (two corners)");
-  AABR_CHECK_ARG(nb >= 1 && nb <= kRoiMaxBatch, "nb must be 1 .. 16");
-  AABR_CHECK_ARG(batch_size_per_image >= 1 && batch_size_per_image <= kLossMaxB && num_pos_max >= 0 &&
-                     num_pos_max <= batch_size_per_image,
-                 "need 1 <= batch_size_per_image <= 512, 0 <= num_pos_max <= batch_size_per_image");
-  AABR_CHECK_ARG(bg_iou <= fg_iou, "need bg_iou <= fg_iou");
-  AABR_CHECK_ARG(n_host && g_host && aug_host && weights_host && samp_rows && samp_labels && samp_targets && samp_boxes &&
-                     info && scratch, "null pointer");
-  AABR_CHECK_ARG(((uintptr_t)scratch & 7) == 0, "scratch must be 8-byte aligned");
+// The body of every aabr_roi_targets* entry point, reported under the caller's name `fn`.  groups == 0: nb scenes, g_host
+// their ground-truth counts.  groups >= 2 (aabr_roi_targets_grouped): nb = scenes x groups segments (scene-major), n_host
+// the segments' proposal counts, g_host the SCENES' ground-truth counts, gt_keys / gt_perm the batch's ground truth
+// sorted by group key (RoiGroupedGt); target_labels is not read.
+static int roi_targets_run(const char *fn, const float *proposals, const float *targets, const int64_t *target_labels,
+                           int nb, int groups, const int64_t *n_host, const int64_t *g_host, const int64_t *gt_keys,
+                           const int64_t *gt_perm, const float *aug_host, int criterion, int only_xy, float fg_iou,
+                           float bg_iou, const float *weights_host, int corner_coder, uint32_t seed,
+                           int batch_size_per_image, int num_pos_max, int64_t *matched_idx, float *matched_val,
+                           int64_t *labels, float *regression_targets, float *iou_out, int64_t *samp_rows,
+                           int64_t *samp_labels, float *samp_targets, float *samp_boxes, int32_t *info, int32_t *scratch,
+                           hipStream_t st) {
+  AABR_CHECK_ARG_AS(fn, corner_coder == 0 || corner_coder == 1, "corner_coder must be 0 (centroid) or 1 (two corners)");
+  AABR_CHECK_ARG_AS(fn, nb >= 1 && nb <= kRoiMaxBatch, groups ? "scenes x groups must be 1 .. 16" : "nb must be 1 .. 16");
+  AABR_CHECK_ARG_AS(fn, batch_size_per_image >= 1 && batch_size_per_image <= kLossMaxB && num_pos_max >= 0 &&
+                            num_pos_max <= batch_size_per_image,
+                    "need 1 <= batch_size_per_image <= 512, 0 <= num_pos_max <= batch_size_per_image");
+  AABR_CHECK_ARG_AS(fn, bg_iou <= fg_iou, "need bg_iou <= fg_iou");
+  AABR_CHECK_ARG_AS(fn, n_host && g_host && aug_host && weights_host && samp_rows && samp_labels && samp_targets &&
+                            samp_boxes && info && scratch, "null pointer");
+  AABR_CHECK_ARG_AS(fn, ((uintptr_t)scratch & 7) == 0, "scratch must be 8-byte aligned");
   RoiTargetParams p = {};
   int64_t N = 0, G = 0, M = 0, nmax = 0;
   std::vector<int32_t> seg(2 * (size_t)nb);
   for (int b = 0; b < nb; ++b) {
-    AABR_CHECK_ARG(n_host[b] >= 0 && g_host[b] >= 0 && n_host[b] < ((int64_t)1 << 31) && g_host[b] < ((int64_t)1 << 31),
-                   "row count out of range");
-    p.prop_begin[b] = N; p.gt_begin[b] = G; p.iou_begin[b] = M;
-    p.n[b] = (int32_t)n_host[b]; p.g[b] = (int32_t)g_host[b];
+    const bool scene_start = !groups || b % groups == 0;            // g_host has one entry per scene
+    const int64_t gb = g_host[groups ? b / groups : b];
+    AABR_CHECK_ARG_AS(fn, n_host[b] >= 0 && gb >= 0 && n_host[b] < ((int64_t)1 << 31) && gb < ((int64_t)1 << 31),
+                      "row count out of range");
+    p.prop_begin[b] = N; p.iou_begin[b] = M;
+    p.gt_begin[b] = scene_start ? G : p.gt_begin[b - 1];
+    p.n[b] = (int32_t)n_host[b]; p.g[b] = groups ? 0 : (int32_t)gb;   // (a segment's count is found on the device)
     seg[2 * b] = 0; seg[2 * b + 1] = (int32_t)n_host[b];
-    N += n_host[b]; G += g_host[b]; M += n_host[b] * g_host[b];
+    N += n_host[b]; M += n_host[b] * gb;
+    if (scene_start) G += gb;
     nmax = n_host[b] > nmax ? n_host[b] : nmax;
   }
-  AABR_CHECK_ARG(N < ((int64_t)1 << 31), "more than 2^31 - 1 proposals per call");
-  AABR_CHECK_ARG(N == 0 || (proposals && matched_idx && matched_val && labels && regression_targets), "null pointer");
-  AABR_CHECK_ARG(G == 0 || (targets && target_labels), "null pointer");
+  AABR_CHECK_ARG_AS(fn, N < ((int64_t)1 << 31), "more than 2^31 - 1 proposals per call");
+  AABR_CHECK_ARG_AS(fn, G < ((int64_t)1 << 31), "more than 2^31 - 1 ground-truth boxes per call");
+  AABR_CHECK_ARG_AS(fn, N == 0 || (proposals && matched_idx && matched_val && labels && regression_targets), "null pointer");
+  AABR_CHECK_ARG_AS(fn, G == 0 || (targets && (groups ? gt_keys && gt_perm : target_labels != nullptr)), "null pointer");
+  AABR_CHECK_ARG_AS(fn, !groups || !iou_out, "the grouped form does not store the IoU matrices");
   for (int d = 0; d < 4; ++d) p.aug[d] = aug_host[d];
   for (int d = 0; d < 7; ++d) p.w[d] = weights_host[d];
   p.fg = fg_iou; p.bg = bg_iou; p.criterion = criterion; p.only_xy = only_xy ? 1 : 0; p.B = batch_size_per_image;
   if (nmax > 0) {
     const dim3 grid((unsigned)ceil_div(nmax, kRoiPropsPerBlock), (unsigned)nb);
-    if (corner_coder)
-      hipLaunchKernelGGL(k_roi_match<true>, grid, dim3(256), 0, st, p, proposals, targets, target_labels, matched_idx,
-                         matched_val, labels, regression_targets, iou_out);
-    else
-      hipLaunchKernelGGL(k_roi_match<false>, grid, dim3(256), 0, st, p, proposals, targets, target_labels, matched_idx,
-                         matched_val, labels, regression_targets, iou_out);
+    const RoiGroupedGt gt = {gt_keys, gt_perm, G};
+    const auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, p, proposals, targets, target_labels, gt, matched_idx, matched_val,
+                         labels, regression_targets, iou_out);
+    };
+    if (groups) corner_coder ? launch(k_roi_match<true, true>) : launch(k_roi_match<false, true>);
+    else corner_coder ? launch(k_roi_match<true, false>) : launch(k_roi_match<false, false>);
   }
   // the sampler over the labels just written: the list form of aabr_sample_list, one chunk (nb <= 16)
   int64_t *sel = reinterpret_cast<int64_t *>(scratch + aabr_rpn_loss_scratch_words(nb) + (aabr_rpn_loss_scratch_words(nb) & 1));
@@ -385,13 +562,92 @@ extern "C" int aabr_roi_targets_coder(const float *proposals, const float *targe
   LossParams sp = {};
   sp.s.n_maps = 1; sp.s.A = 1; sp.flat = 1; sp.with_loss = 0; sp.label_mode = 1; sp.k_pos0 = num_pos_max;
   sp.B = batch_size_per_image; sp.seed = seed; sp.beta = 1.f;
-  int rc = run_select_chunks(sp, __func__, nb, seg.data(), nullptr, label_ptrs.data(), nullptr, nullptr, nullptr, sel, sinfo, scratch,
+  int rc = run_select_chunks(sp, fn, nb, seg.data(), nullptr, label_ptrs.data(), nullptr, nullptr, nullptr, sel, sinfo, scratch,
                              st);
   if (rc != AABR_OK) return rc;
   hipLaunchKernelGGL(k_roi_compact, dim3((unsigned)nb), dim3(256), 0, st, p, sel, sinfo, proposals, labels,
                      regression_targets, samp_rows, samp_labels, samp_targets, samp_boxes, info);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
+}
+
+extern "C" int aabr_roi_targets_coder(const float *proposals, const float *targets, const int64_t *target_labels, int nb,
+                                      const int64_t *n_host, const int64_t *g_host, const float *aug_host, int criterion,
+                                      int only_xy, float fg_iou, float bg_iou, const float *weights_host,
+                                      int corner_coder, uint32_t seed, int batch_size_per_image, int num_pos_max,
+                                      int64_t *matched_idx, float *matched_val, int64_t *labels,
+                                      float *regression_targets, float *iou_out, int64_t *samp_rows,
+                                      int64_t *samp_labels, float *samp_targets, float *samp_boxes, int32_t *info,
+                                      int32_t *scratch, void *stream_) {
+  return roi_targets_run(__func__, proposals, targets, target_labels, nb, 0, n_host, g_host, nullptr, nullptr, aug_host,
+                         criterion, only_xy, fg_iou, bg_iou, weights_host, corner_coder, seed, batch_size_per_image,
+                         num_pos_max, matched_idx, matched_val, labels, regression_targets, iou_out, samp_rows, samp_labels,
+                         samp_targets, samp_boxes, info, scratch, (hipStream_t)stream_);
+}
+
+// ---- the separated-classifier groups: stage 1 ---------------------------------------------------------------------------
+// key of ground-truth row i of scene b: (b groups + g) kSepMaxCols + i_local when its label is column cols[g][i_local] of
+// group g, nb groups kSepMaxCols (behind every segment) when no group owns the label.  A stable ascending sort of the keys
+// puts every segment's ground truth in one run, ordered (group-local label, row): the order the reference's
+// _seperating_ids gives a group's targets.
+namespace {
+struct RoiKeyParams {
+  int64_t gt_begin[kRoiMaxBatch + 1];
+  int nb;
+};
+__global__ __launch_bounds__(256) void k_roi_gt_keys(RoiKeyParams p, SepGroups q, const int64_t *__restrict__ target_labels,
+                                                     int64_t *__restrict__ keys) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.gt_begin[p.nb]) return;
+  int b = 0;
+  while (b + 1 < p.nb && i >= p.gt_begin[b + 1]) ++b;
+  const int64_t l = target_labels[i];
+  int64_t key = (int64_t)p.nb * q.G * kSepMaxCols;
+  for (int g = 0; g < q.G; ++g)
+    for (int k = 0; k < q.class_nums[g]; ++k)
+      if (q.cols[g][k] == l) key = ((int64_t)b * q.G + g) * kSepMaxCols + k;
+  keys[i] = key;
+}
+}  // namespace
+
+extern "C" int aabr_roi_gt_group_keys(const int64_t *target_labels, int nb, const int64_t *g_host, int G, int C_tot,
+                                      const int32_t *class_nums_host, const int32_t *cols_host, int64_t *keys,
+                                      void *stream_) {
+  SepGroups q;
+  int rc = fill_sep_groups(q, __func__, G, C_tot, class_nums_host, cols_host);
+  if (rc != AABR_OK) return rc;
+  AABR_CHECK_ARG(nb >= 1 && (int64_t)nb * G <= kRoiMaxBatch, "scenes x groups must be 1 .. 16");
+  AABR_CHECK_ARG(g_host, "null pointer");
+  RoiKeyParams p = {};
+  p.nb = nb;
+  for (int b = 0; b < nb; ++b) {
+    AABR_CHECK_ARG(g_host[b] >= 0 && g_host[b] < ((int64_t)1 << 31), "row count out of range");
+    p.gt_begin[b + 1] = p.gt_begin[b] + g_host[b];
+  }
+  const int64_t total = p.gt_begin[nb];
+  AABR_CHECK_ARG(total < ((int64_t)1 << 31), "more than 2^31 - 1 ground-truth boxes per call");
+  if (total == 0) return AABR_OK;
+  AABR_CHECK_ARG(target_labels && keys, "null pointer");
+  hipLaunchKernelGGL(k_roi_gt_keys, dim3((unsigned)ceil_div(total, (int64_t)256)), dim3(256), 0, (hipStream_t)stream_, p, q,
+                     target_labels, keys);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+extern "C" int aabr_roi_targets_grouped(const float *proposals, const float *targets, const int64_t *gt_keys,
+                                        const int64_t *gt_perm, int nb, int G, const int64_t *n_host,
+                                        const int64_t *g_host, const float *aug_host, int criterion, int only_xy,
+                                        float fg_iou, float bg_iou, const float *weights_host, int corner_coder,
+                                        uint32_t seed, int batch_size_per_image, int num_pos_max, int64_t *matched_idx,
+                                        float *matched_val, int64_t *labels, float *regression_targets,
+                                        int64_t *samp_rows, int64_t *samp_labels, float *samp_targets, float *samp_boxes,
+                                        int32_t *info, int32_t *scratch, void *stream_) {
+  AABR_CHECK_ARG(G >= 2 && G <= kSepMaxGroups, "the group count must be 2 .. 8");
+  AABR_CHECK_ARG(nb >= 1 && (int64_t)nb * G <= kRoiMaxBatch, "scenes x groups must be 1 .. 16");
+  return roi_targets_run(__func__, proposals, targets, nullptr, nb * G, G, n_host, g_host, gt_keys, gt_perm, aug_host,
+                         criterion, only_xy, fg_iou, bg_iou, weights_host, corner_coder, seed, batch_size_per_image,
+                         num_pos_max, matched_idx, matched_val, labels, regression_targets, nullptr, samp_rows, samp_labels,
+                         samp_targets, samp_boxes, info, scratch, (hipStream_t)stream_);
 }
 
 // the centroid coder: the signature of before aabr_roi_targets_coder
@@ -446,6 +702,54 @@ extern "C" int aabr_roi_box_loss_backward(const void *class_logits, const void *
   hipLaunchKernelGGL(k_roi_loss_backward, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream_,
                      class_logits, box_regression, input_bf16 ? 1 : 0, n, C, class_specific ? 1 : 0, labels,
                      regression_targets, beta, grad_cls_loss, grad_box_loss, grad_logits, grad_regression);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+// ---- the separated-classifier groups: stage 2 ---------------------------------------------------------------------------
+extern "C" int64_t aabr_roi_box_loss_grouped_scratch_floats(void) { return (int64_t)kSepPartWords * kRoiLossBlocks; }
+
+extern "C" int aabr_roi_box_loss_grouped_forward(const void *class_logits, const void *box_regression, int input_bf16,
+                                                 int64_t n, int G, int C_tot, const int32_t *class_nums_host,
+                                                 const int32_t *cols_host, const int32_t *sep_id, const int64_t *labels,
+                                                 const float *regression_targets, float beta, float *cls_loss,
+                                                 float *box_loss, int32_t *group_rows, int32_t *flag, float *scratch,
+                                                 void *stream_) {
+  hipStream_t st = (hipStream_t)stream_;
+  SepGroups q;
+  int rc = fill_sep_groups(q, __func__, G, C_tot, class_nums_host, cols_host);
+  if (rc != AABR_OK) return rc;
+  AABR_CHECK_ARG(n >= 0 && beta > 0.f, "need n >= 0, beta > 0");
+  AABR_CHECK_ARG(n * 7 * (int64_t)C_tot < ((int64_t)1 << 31), "n * 7 C_tot must stay below 2^31");
+  AABR_CHECK_ARG(cls_loss && box_loss && group_rows && flag && scratch, "null pointer");
+  AABR_CHECK_ARG(n == 0 || (class_logits && box_regression && sep_id && labels && regression_targets), "null pointer");
+  const int nblk = roi_loss_blocks(n);
+  hipLaunchKernelGGL(k_roi_sep_loss_partial, dim3((unsigned)nblk), dim3(256), 0, st, class_logits, box_regression,
+                     input_bf16 ? 1 : 0, n, q, sep_id, labels, regression_targets, beta, scratch);
+  hipLaunchKernelGGL(k_roi_sep_loss_finalize, dim3(1), dim3(64), 0, st, nblk, G, scratch, cls_loss, box_loss, group_rows,
+                     flag);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+extern "C" int aabr_roi_box_loss_grouped_backward(const void *class_logits, const void *box_regression, int input_bf16,
+                                                  int64_t n, int G, int C_tot, const int32_t *class_nums_host,
+                                                  const int32_t *cols_host, const int32_t *sep_id, const int64_t *labels,
+                                                  const float *regression_targets, float beta, const int32_t *group_rows,
+                                                  const float *grad_cls_loss, const float *grad_box_loss,
+                                                  void *grad_logits, void *grad_regression, void *stream_) {
+  SepGroups q;
+  int rc = fill_sep_groups(q, __func__, G, C_tot, class_nums_host, cols_host);
+  if (rc != AABR_OK) return rc;
+  AABR_CHECK_ARG(n >= 0 && beta > 0.f, "need n >= 0, beta > 0");
+  AABR_CHECK_ARG(n * 7 * (int64_t)C_tot < ((int64_t)1 << 31), "n * 7 C_tot must stay below 2^31");
+  AABR_CHECK_ARG(group_rows && grad_cls_loss && grad_box_loss, "null pointer");
+  if (n == 0) return AABR_OK;
+  AABR_CHECK_ARG(class_logits && box_regression && sep_id && labels && regression_targets && grad_logits && grad_regression,
+                 "null pointer");
+  hipLaunchKernelGGL(k_roi_sep_loss_backward, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream_,
+                     class_logits, box_regression, input_bf16 ? 1 : 0, n, q, sep_id, labels, regression_targets, beta,
+                     group_rows, grad_cls_loss, grad_box_loss, grad_logits, grad_regression);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }

@@ -34,8 +34,12 @@
 //   k_roi_post_scene   one workgroup per scene: the D-th largest score by radix select, ordered compaction, info.
 // Limits (validated): 2 <= C <= 32, 1 <= nb <= 16, 1 <= post_max <= pre_max <= 2048, N * C * 7 < 2^31.
 // A scene with n_b = 0, a segment without a candidate and N = 0 are legal and give empty lists.
+// With separated-classifier groups (sep_groups.h, aabr_roi_post_detections_grouped) the same five launches: the row
+// kernel's softmax runs over the row's group columns (k_roi_post_rows_sep), a segment is a foreground column of a group,
+// candidates are tested for group membership, and the detections_per_img cut is taken per (scene, group).
 #include "common.h"
 #include "nms_shared.h"
+#include "sep_groups.h"
 
 namespace aabr {
 
@@ -144,20 +148,65 @@ __global__ __launch_bounds__(256) void k_roi_post_rows(const float *__restrict__
   }
 }
 
-__global__ __launch_bounds__(1024) void k_roi_post_select(RoiPostParams p, RoiPostBufs u) {
+// The separated-classifier form (SeperateClassifier.post_processor): row i belongs to group sep_id[i]; its softmax runs
+// over that group's columns only, summed in group-local order, and every other column of prob is an exact 0.  The
+// regression is class agnostic: boxes is [N, 7].  A sep_id outside [0, G) is never used as an index: the row's prob is
+// all 0, it is no group's candidate, and word 5 of its scene's info block is raised.
+template <bool kCorner>
+__global__ __launch_bounds__(256) void k_roi_post_rows_sep(const float *__restrict__ logits, const float *__restrict__ reg,
+                                                           const float *__restrict__ props,
+                                                           const int32_t *__restrict__ sep_id, int64_t N, RoiPostParams p,
+                                                           SepGroups sg, float *__restrict__ prob,
+                                                           float *__restrict__ boxes, int32_t *__restrict__ info) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const int C = p.C;
+  const float *x = logits + i * C;
+  for (int c = 0; c < C; ++c) prob[i * C + c] = 0.0f;
+  const int g = sep_id[i];
+  if (g >= 0 && g < sg.G) {
+    const int cn = sg.class_nums[g];
+    float m = x[sg.cols[g][0]];
+    for (int k = 1; k < cn; ++k) m = fmaxf(m, x[sg.cols[g][k]]);
+    float s = expf(x[sg.cols[g][0]] - m);
+    for (int k = 1; k < cn; ++k) s += expf(x[sg.cols[g][k]] - m);   // group-local order: cn - 1 additions
+    for (int k = 0; k < cn; ++k) prob[i * C + sg.cols[g][k]] = expf(x[sg.cols[g][k]] - m) / s;
+  } else {
+    int b = 0;
+    while (b + 1 < p.nb && i >= p.row_begin[b + 1]) ++b;
+    atomicOr(&info[b * kRoiInfoWords + 5], 1);
+  }
+  float an[7], o[7];
+#pragma unroll
+  for (int d = 0; d < 7; ++d) an[d] = props[7 * i + d];
+  if (kCorner) box_decode7_corner(reg + 7 * i, an, p.w.w, p.clip, o);
+  else box_decode7(reg + 7 * i, an, p.w, p.clip, o);
+#pragma unroll
+  for (int d = 0; d < 7; ++d) boxes[7 * i + d] = o[d];
+}
+
+// kSep: the segments of a scene are the foreground columns of all groups (sg.fg_col, in (group, group-local) order); the
+// candidates of column j are the rows OF ITS GROUP above the threshold -- membership is tested, a foreign row's zero
+// probability is not relied on (score_thresh may be negative) -- and the boxes are one per row.
+template <bool kSep>
+__global__ __launch_bounds__(1024) void k_roi_post_select(RoiPostParams p, RoiPostBufs u, SepGroups sg,
+                                                          const int32_t *__restrict__ sep_id) {
   __shared__ unsigned long long s_key[kRoiMaxPre];
   __shared__ int s_hist[256], s_wave[16], s_ctl[4];
   const int tid = threadIdx.x;
-  const int s = blockIdx.x, b = s / (p.C - 1), j = 1 + s % (p.C - 1);
+  const int nseg = kSep ? sg.nf : p.C - 1;
+  const int s = blockIdx.x, b = s / nseg, j = kSep ? sg.fg_col[s % nseg] : 1 + s % nseg;
+  const int grp = kSep ? sg.fg_group[s % nseg] : 0;
   const int r0 = p.row_begin[b], n = p.row_begin[b + 1] - r0;
   const float *col = u.prob + (int64_t)r0 * p.C + j;
   const int C = p.C;
   const float thr = p.score_thresh;
+  const auto is_cand = [&](int r, float v) { return v > thr && (!kSep || sep_id[r0 + r] == grp); };
   if (tid == 0) { s_ctl[2] = 0; s_ctl[3] = 0; }
   __syncthreads();
   {
     int c = 0;
-    for (int r = tid; r < n; r += 1024) c += col[(int64_t)r * C] > thr ? 1 : 0;
+    for (int r = tid; r < n; r += 1024) c += is_cand(r, col[(int64_t)r * C]) ? 1 : 0;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
     if ((tid & 63) == 0 && c) atomicAdd(&s_ctl[2], c);
@@ -173,7 +222,7 @@ __global__ __launch_bounds__(1024) void k_roi_post_select(RoiPostParams p, RoiPo
                          [&](int r, uint32_t &key) {
                            const float v = col[(int64_t)r * C];
                            key = __float_as_uint(v);     // probabilities are >= +0: the bit order is the value order
-                           return v > thr;
+                           return is_cand(r, v);
                          },
                          s_hist, s_ctl, need_eq);
   // collect: every candidate above the cut score and the first need_eq rows AT it (ascending row: ordered by a scan);
@@ -182,7 +231,7 @@ __global__ __launch_bounds__(1024) void k_roi_post_select(RoiPostParams p, RoiPo
   for (int base = 0; base < n; base += 1024) {
     const int r = base + tid;
     const float v = r < n ? col[(int64_t)r * C] : 0.0f;
-    const bool cand = r < n && v > thr;
+    const bool cand = r < n && is_cand(r, v);
     const uint32_t bits = __float_as_uint(v);
     bool take = cand;
     if (cut) {
@@ -220,7 +269,7 @@ __global__ __launch_bounds__(1024) void k_roi_post_select(RoiPostParams p, RoiPo
     const int64_t q = (int64_t)s * p.P + k;
     u.sel_row[q] = r;
     u.sel_score[q] = __uint_as_float(~(uint32_t)(key >> 32));
-    const float *src = u.boxes + 7 * ((int64_t)(r0 + r) * C + j);
+    const float *src = u.boxes + 7 * (kSep ? (int64_t)(r0 + r) : (int64_t)(r0 + r) * C + j);
     float o[7];
 #pragma unroll
     for (int d = 0; d < 7; ++d) o[d] = src[d];
@@ -253,13 +302,18 @@ __global__ __launch_bounds__(256) void k_roi_post_scan(RoiPostParams p, RoiPostB
                  u.keep + (int64_t)s * p.keep_stride, u.seg_kept + s, remv);
 }
 
-__global__ __launch_bounds__(1024) void k_roi_post_scene(RoiPostParams p, RoiPostBufs u, int64_t cap,
+// kSep: the scene's list is the groups in ascending order, each group's columns in group-local order; the
+// detections_per_img cut is taken PER GROUP (each group went through a post-processor pass of its own in the reference),
+// and the label is the column index, which is the original label.
+template <bool kSep>
+__global__ __launch_bounds__(1024) void k_roi_post_scene(RoiPostParams p, RoiPostBufs u, SepGroups sg, int64_t cap,
                                                          int64_t *__restrict__ det_rows,
                                                          int64_t *__restrict__ det_labels,
                                                          float *__restrict__ det_scores, float *__restrict__ det_boxes,
                                                          int32_t *__restrict__ info) {
-  __shared__ int s_off[kRoiMaxClasses], s_hist[256], s_wave[16], s_ctl[4];
-  const int tid = threadIdx.x, b = blockIdx.x, nc = p.C - 1;
+  __shared__ int s_off[kRoiMaxClasses + 1], s_hist[256], s_wave[16], s_ctl[4];
+  __shared__ uint32_t s_cut[kSepMaxGroups];
+  const int tid = threadIdx.x, b = blockIdx.x, nc = kSep ? sg.nf : p.C - 1;
   const int s0 = b * nc;
   if (tid == 0) {
     int run = 0;
@@ -269,42 +323,61 @@ __global__ __launch_bounds__(1024) void k_roi_post_scene(RoiPostParams p, RoiPos
   __syncthreads();
   const int M = s_off[nc];
   // entry e of the scene's concatenated list (classes ascending, survivors in order) -> its sorted-list slot
-  auto slot_of = [&](int e, int &label) {
+  auto slot_of = [&](int e, int &label, int &grp) {
     int j = 0;
     while (j + 1 < nc && e >= s_off[j + 1]) ++j;
-    label = j + 1;
+    label = kSep ? sg.fg_col[j] : j + 1;
+    grp = kSep ? sg.fg_group[j] : 0;
     return (int64_t)(s0 + j) * p.P + u.keep[(int64_t)(s0 + j) * p.keep_stride + (e - s_off[j])];
   };
   uint32_t T = 0;                                      // keep score >= T; +0 keeps everything
-  if (p.D > 0 && M > p.D) {
+  if (!kSep && p.D > 0 && M > p.D) {
     int need_eq;
     T = block_select_kth(M, p.D,
                          [&](int e, uint32_t &key) {
-                           int label;
-                           key = __float_as_uint(u.sel_score[slot_of(e, label)]);
+                           int label, grp;
+                           key = __float_as_uint(u.sel_score[slot_of(e, label, grp)]);
                            return true;
                          },
                          s_hist, s_ctl, need_eq);
   }
+  if (kSep) {
+    for (int g = 0; g < sg.G; ++g) {                    // workgroup-uniform: group g's entries are e0 .. e1 of the list
+      const int e0 = s_off[sg.fg_begin[g]], e1 = s_off[sg.fg_begin[g + 1]];
+      uint32_t Tg = 0;
+      if (p.D > 0 && e1 - e0 > p.D) {
+        int need_eq;
+        Tg = block_select_kth(e1 - e0, p.D,
+                              [&](int e, uint32_t &key) {
+                                int label, grp;
+                                key = __float_as_uint(u.sel_score[slot_of(e0 + e, label, grp)]);
+                                return true;
+                              },
+                              s_hist, s_ctl, need_eq);
+      }
+      if (tid == 0) s_cut[g] = Tg;
+    }
+    __syncthreads();
+  }
   int out = 0;
   for (int base = 0; base < M; base += 1024) {
     const int e = base + tid;
-    int label = 0;
-    int64_t q = 0;
+    int label = 0, grp = 0;
+    int64_t k = 0;
     bool take = false;
     if (e < M) {
-      q = slot_of(e, label);
-      take = __float_as_uint(u.sel_score[q]) >= T;
+      k = slot_of(e, label, grp);
+      take = __float_as_uint(u.sel_score[k]) >= (kSep ? s_cut[grp] : T);
     }
     int total;
     const int64_t pos = (int64_t)b * cap + out + block_excl_scan(take ? 1 : 0, s_wave, total);
     out += total;
     if (take) {
-      const int r = u.sel_row[q];
+      const int r = u.sel_row[k];
       det_rows[pos] = r;
       det_labels[pos] = label;
-      det_scores[pos] = u.sel_score[q];
-      const float *src = u.boxes + 7 * ((int64_t)(p.row_begin[b] + r) * p.C + label);
+      det_scores[pos] = u.sel_score[k];
+      const float *src = u.boxes + 7 * (kSep ? (int64_t)(p.row_begin[b] + r) : (int64_t)(p.row_begin[b] + r) * p.C + label);
 #pragma unroll
       for (int d = 0; d < 7; ++d) det_boxes[7 * pos + d] = src[d];
     }
@@ -318,7 +391,8 @@ __global__ __launch_bounds__(1024) void k_roi_post_scene(RoiPostParams p, RoiPos
       most = k > most ? k : most;
     }
     int32_t *w = info + (int64_t)b * kRoiInfoWords;
-    w[0] = out; w[1] = M; w[2] = cand; w[3] = big; w[4] = most; w[5] = 0; w[6] = 0; w[7] = 0;
+    w[0] = out; w[1] = M; w[2] = cand; w[3] = big; w[4] = most; w[6] = 0; w[7] = 0;
+    if (!kSep) w[5] = 0;                               // (kSep: k_roi_post_rows_sep's flag for a sep_id out of range)
   }
 }
 
@@ -364,7 +438,10 @@ extern "C" int64_t aabr_roi_post_scratch_words(int nb, int64_t n_max, int C, int
   return roi_post_layout(nb, n_max, n_max * nb, C, pre_max).words;
 }
 
-static int roi_post_detections(const char *fn, const float *class_logits, const float *box_regression,
+// `groups`: null, or the separated-classifier groups (aabr_roi_post_detections_grouped): C = C_tot, class-agnostic
+// regression, `sep_id` int32 [N], boxes [N, 7], nf = C_tot - G segments per scene
+static int roi_post_detections(const char *fn, const SepGroups *groups, const int32_t *sep_id, const float *class_logits,
+                               const float *box_regression,
                                const float *proposals, int nb, const int64_t *n_host, int C, int class_specific,
                                const float *weights_host, int corner_coder, float clip, float score_thresh,
                                float nms_thresh, float nms_min_yx, float nms_min_z, int only_xy, int pre_max,
@@ -394,7 +471,10 @@ static int roi_post_detections(const char *fn, const float *class_logits, const 
   AABR_CHECK_ARG_AS(fn, class_logits && box_regression && proposals && det_rows && det_labels && det_scores && det_boxes &&
                      scratch, "null pointer");
   AABR_CHECK_ARG_AS(fn, ((uintptr_t)scratch & 7) == 0, "scratch must be 8-byte aligned");
-  const RoiPostLayout L = roi_post_layout(nb, n_max, N, C, pre_max);
+  AABR_CHECK_ARG_AS(fn, !groups || sep_id, "null pointer (sep_id)");
+  const RoiPostLayout L = roi_post_layout(nb, n_max, N, C, pre_max);   // (groups: sized for C_tot - 1 >= nf segments)
+  const SepGroups q = groups ? *groups : SepGroups();
+  const int64_t S = groups ? (int64_t)nb * q.nf : L.S;
   p.nb = nb; p.C = C; p.reg_classes = class_specific ? C : 1;
   p.pre_max = pre_max; p.post_max = post_max; p.D = detections_per_img; p.only_xy = only_xy ? 1 : 0;
   p.P = (int)L.P; p.cbmax = (int)L.cbmax; p.keep_stride = (int)L.keep_stride;
@@ -411,22 +491,38 @@ static int roi_post_detections(const char *fn, const float *class_logits, const 
   u.seg_m = scratch + L.o_seg;
   u.seg_cnt = u.seg_m + L.S;
   u.seg_kept = u.seg_cnt + L.S;
-  const int64_t cap = (int64_t)(C - 1) * post_max;
+  const int64_t cap = (int64_t)(groups ? q.nf : C - 1) * post_max;
   const int64_t longest = n_max < pre_max ? n_max : pre_max;     // no sorted list is longer
-  if (corner_coder)
-    hipLaunchKernelGGL(k_roi_post_rows<true>, dim3((unsigned)ceil_div(N, (int64_t)256)), dim3(256), 0, st, class_logits,
-                       box_regression, proposals, N, p, u.prob, u.boxes);
-  else
-    hipLaunchKernelGGL(k_roi_post_rows<false>, dim3((unsigned)ceil_div(N, (int64_t)256)), dim3(256), 0, st, class_logits,
-                       box_regression, proposals, N, p, u.prob, u.boxes);
-  hipLaunchKernelGGL(k_roi_post_select, dim3((unsigned)L.S), dim3(1024), 0, st, p, u);
+  const dim3 row_grid((unsigned)ceil_div(N, (int64_t)256));
+  if (groups) {
+    if (S == 0) return AABR_OK;                        // no group has a foreground column: nothing can be detected
+    if (corner_coder)
+      hipLaunchKernelGGL(k_roi_post_rows_sep<true>, row_grid, dim3(256), 0, st, class_logits, box_regression, proposals,
+                         sep_id, N, p, q, u.prob, u.boxes, info);
+    else
+      hipLaunchKernelGGL(k_roi_post_rows_sep<false>, row_grid, dim3(256), 0, st, class_logits, box_regression, proposals,
+                         sep_id, N, p, q, u.prob, u.boxes, info);
+    hipLaunchKernelGGL(k_roi_post_select<true>, dim3((unsigned)S), dim3(1024), 0, st, p, u, q, sep_id);
+  } else {
+    if (corner_coder)
+      hipLaunchKernelGGL(k_roi_post_rows<true>, row_grid, dim3(256), 0, st, class_logits, box_regression, proposals, N, p,
+                         u.prob, u.boxes);
+    else
+      hipLaunchKernelGGL(k_roi_post_rows<false>, row_grid, dim3(256), 0, st, class_logits, box_regression, proposals, N, p,
+                         u.prob, u.boxes);
+    hipLaunchKernelGGL(k_roi_post_select<false>, dim3((unsigned)S), dim3(1024), 0, st, p, u, q, sep_id);
+  }
   hipLaunchKernelGGL(k_roi_post_mask,
                      dim3((unsigned)ceil_div(longest, (int64_t)kNmsRows), (unsigned)ceil_div(longest, (int64_t)64),
-                          (unsigned)L.S),
+                          (unsigned)S),
                      dim3(256), 0, st, p, u);
-  hipLaunchKernelGGL(k_roi_post_scan, dim3((unsigned)L.S), dim3(256), 0, st, p, u);
-  hipLaunchKernelGGL(k_roi_post_scene, dim3((unsigned)nb), dim3(1024), 0, st, p, u, cap, det_rows, det_labels,
-                     det_scores, det_boxes, info);
+  hipLaunchKernelGGL(k_roi_post_scan, dim3((unsigned)S), dim3(256), 0, st, p, u);
+  if (groups)
+    hipLaunchKernelGGL(k_roi_post_scene<true>, dim3((unsigned)nb), dim3(1024), 0, st, p, u, q, cap, det_rows, det_labels,
+                       det_scores, det_boxes, info);
+  else
+    hipLaunchKernelGGL(k_roi_post_scene<false>, dim3((unsigned)nb), dim3(1024), 0, st, p, u, q, cap, det_rows, det_labels,
+                       det_scores, det_boxes, info);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }
@@ -438,7 +534,7 @@ extern "C" int aabr_roi_post_detections(const float *class_logits, const float *
                                         int detections_per_img, float *prob, float *boxes, int64_t *det_rows,
                                         int64_t *det_labels, float *det_scores, float *det_boxes, int32_t *info,
                                         int32_t *scratch, void *stream_) {
-  return roi_post_detections("aabr_roi_post_detections", class_logits, box_regression, proposals, nb, n_host, C,
+  return roi_post_detections("aabr_roi_post_detections", nullptr, nullptr, class_logits, box_regression, proposals, nb, n_host, C,
                              class_specific, weights_host, 0, clip, score_thresh, nms_thresh, nms_min_yx, nms_min_z, only_xy,
                              pre_max, post_max, detections_per_img, prob, boxes, det_rows, det_labels, det_scores, det_boxes,
                              info, scratch, stream_);
@@ -452,8 +548,27 @@ extern "C" int aabr_roi_post_detections_coder(const float *class_logits, const f
                                               int only_xy, int pre_max, int post_max, int detections_per_img, float *prob,
                                               float *boxes, int64_t *det_rows, int64_t *det_labels, float *det_scores,
                                               float *det_boxes, int32_t *info, int32_t *scratch, void *stream_) {
-  return roi_post_detections("aabr_roi_post_detections_coder", class_logits, box_regression, proposals, nb, n_host, C,
+  return roi_post_detections("aabr_roi_post_detections_coder", nullptr, nullptr, class_logits, box_regression, proposals, nb, n_host, C,
                              class_specific, weights_host, corner_coder, clip, score_thresh, nms_thresh, nms_min_yx,
                              nms_min_z, only_xy, pre_max, post_max, detections_per_img, prob, boxes, det_rows, det_labels,
                              det_scores, det_boxes, info, scratch, stream_);
+}
+
+// the separated-classifier form: C_tot columns shared by G groups, class-agnostic regression [N, 7], sep_id int32 [N]
+extern "C" int aabr_roi_post_detections_grouped(const float *class_logits, const float *box_regression,
+                                                const float *proposals, const int32_t *sep_id, int nb,
+                                                const int64_t *n_host, int G, int C_tot, const int32_t *class_nums_host,
+                                                const int32_t *cols_host, const float *weights_host, int corner_coder,
+                                                float clip, float score_thresh, float nms_thresh, float nms_min_yx,
+                                                float nms_min_z, int only_xy, int pre_max, int post_max,
+                                                int detections_per_img, float *prob, float *boxes, int64_t *det_rows,
+                                                int64_t *det_labels, float *det_scores, float *det_boxes, int32_t *info,
+                                                int32_t *scratch, void *stream_) {
+  SepGroups q;
+  int rc = fill_sep_groups(q, __func__, G, C_tot, class_nums_host, cols_host);
+  if (rc != AABR_OK) return rc;
+  return roi_post_detections(__func__, &q, sep_id, class_logits, box_regression, proposals, nb, n_host, C_tot, 0,
+                             weights_host, corner_coder, clip, score_thresh, nms_thresh, nms_min_yx, nms_min_z, only_xy,
+                             pre_max, post_max, detections_per_img, prob, boxes, det_rows, det_labels, det_scores,
+                             det_boxes, info, scratch, stream_);
 }

@@ -3,8 +3,10 @@
 predictor, loss evaluator and post-processor in the reference's order.  `proposals` is one duck-typed list per scene
 (`.bbox3d` [n, 7] yx_zb, `.size3d`), or an object whose `seperate_examples()` returns that.  The corner form runs with the
 default loss weights, cfg.MODEL.LOSS.WEIGHTS[4:7] == 0, where the reference drops `corners_semantic` (:121-122); nonzero
-corner-connection loss weights are refused.  Not part of this package: the separated-classifier groups, and
-cfg.DEBUG.eval_in_train (its rm_gt_from_proposals_ reads an `is_gt` field the sampled lists here do not carry)."""
+corner-connection loss weights are refused.  With separated-classifier groups (MODEL.SEPARATE_CLASSES /
+SEPARATE_CLASSES_ID, class-agnostic regression) the proposals carry `sep_id`, the loss evaluator and the post-processor go
+through the SeperateClassifier (modeling/seperate_classifier.py) and the losses come out per group, as
+`loss_classifier_roi_{g}` / `loss_box_reg_roi_{g}` (:149-157).  Not part of this package: cfg.DEBUG.eval_in_train (its rm_gt_from_proposals_ reads an `is_gt` field the sampled lists here do not carry)."""
 import torch
 
 import roi_glue
@@ -26,7 +28,7 @@ class ROIBoxHead3D(torch.nn.Module):
         self.predictor = make_roi_box_predictor(cfg)
         self.post_processor_ = make_roi_box_post_processor(cfg)
         self.loss_evaluator, self.seperate_classifier = make_roi_box_loss_evaluator(cfg)
-        self.need_seperate = False
+        self.need_seperate = self.seperate_classifier is not None and self.seperate_classifier.need_seperate
         self.eval_in_train = cfg.DEBUG.eval_in_train
         self.add_gt_proposals = cfg.MODEL.RPN.ADD_GT_PROPOSALS
         self.detections_per_img = cfg.MODEL.ROI_HEADS.DETECTIONS_PER_IMG
@@ -35,12 +37,27 @@ class ROIBoxHead3D(torch.nn.Module):
         self.cfg = cfg
 
     def post_processor(self, log_reg, proposals):
-        return self.post_processor_(log_reg, proposals)
+        if not self.need_seperate:
+            return self.post_processor_(log_reg, proposals)
+        class_logits, box_regression, corners_semantic = log_reg
+        return self.seperate_classifier.post_processor(class_logits, box_regression, corners_semantic=corners_semantic,
+                                                       proposals=proposals, post_processor_fn=self.post_processor_)
+
+    def _roi_losses(self, loss_classifier, loss_box_reg):
+        """the loss dict of a training pass: one pair, or one pair per separated group (box_head.py:149-157)"""
+        if not self.need_seperate:
+            return {"loss_classifier_roi": loss_classifier, "loss_box_reg_roi": loss_box_reg}
+        roi_loss = {}
+        for gi in range(len(loss_classifier)):
+            roi_loss["loss_classifier_roi_%d" % gi] = loss_classifier[gi]
+            roi_loss["loss_box_reg_roi_%d" % gi] = loss_box_reg[gi]
+        return roi_loss
 
     def forward(self, features, proposals, targets=None):
         """features: one SparseConvNetTensor per level; proposals: per-scene lists; targets: per-scene ground truth
         (training).  Returns (x, proposals, losses): training -- the sampled proposals and {"loss_classifier_roi",
-        "loss_box_reg_roi"}; evaluation -- the detections and {}.  In the corner form x is the list [x_cor0, x_cor1,
+        "loss_box_reg_roi"} (with groups: one pair of keys per group, suffixed _0 .. _{G-1}); evaluation -- the detections
+        and {}.  In the corner form x is the list [x_cor0, x_cor1,
         x_body] and box_regression holds two-corner encodings."""
         if self.corner_roi:
             return self.forward_corner_box(features, proposals, targets)
@@ -57,7 +74,7 @@ class ROIBoxHead3D(torch.nn.Module):
             return x, result, {}
         loss_classifier, loss_box_reg, _ = self.loss_evaluator(class_logits, box_regression, corners_semantic=None,
                                                                targets=targets)
-        return x, proposals, {"loss_classifier_roi": loss_classifier, "loss_box_reg_roi": loss_box_reg}
+        return x, proposals, self._roi_losses(loss_classifier, loss_box_reg)
 
 
     def forward_corner_box(self, features, proposals, targets=None):
@@ -75,7 +92,7 @@ class ROIBoxHead3D(torch.nn.Module):
             return x, result, {}
         loss_classifier, loss_box_reg, loss_corner_grouping = self.loss_evaluator(
             class_logits, box_regression, corners_semantic, targets=targets)
-        roi_loss = {"loss_classifier_roi": loss_classifier, "loss_box_reg_roi": loss_box_reg}
+        roi_loss = self._roi_losses(loss_classifier, loss_box_reg)
         roi_loss.update(loss_corner_grouping)
         return x, proposals, roi_loss
 

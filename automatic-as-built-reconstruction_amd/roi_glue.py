@@ -296,6 +296,282 @@ def box_head_loss(class_logits, box_regression, labels, regression_targets, clas
     return (cls_loss, box_loss, flag) if return_flag else (cls_loss, box_loss)
 
 
+# ---- the separated-classifier groups (MODEL.SEPARATE_CLASSES; csrc/sep_groups.h) -------------------------------------------
+SEP_MAX_GROUPS, SEP_MAX_COLS, SEP_MAX_SEGMENTS = 8, 32, 16
+
+
+def sep_group_tables(groups):
+    """`groups`: a SeperateClassifier (maskrcnn_benchmark/modeling/seperate_classifier.py) or its `grouped_classes`, a
+    list over groups of column lists in group-local order, each group's background column first.  Returns
+    (grouped_classes as lists of int, C_tot, class_nums int32 host array, cols int32 host array): the two host tables
+    every grouped entry point of the library takes.  ValueError outside the library's limits (2 .. 8 groups, C_tot <= 32,
+    every column below C_tot and in one group only) -- raised here, before the GPU is needed."""
+    gc = getattr(groups, "grouped_classes", groups)
+    gc = [[int(c) for c in g] for g in gc]
+    if not 2 <= len(gc) <= SEP_MAX_GROUPS:
+        raise ValueError("separated classifier: 2 .. %d groups, got %d" % (SEP_MAX_GROUPS, len(gc)))
+    flat = [c for g in gc for c in g]
+    c_tot = getattr(groups, "seperated_num_classes_total", None)
+    c_tot = int(c_tot) if c_tot is not None else (max(flat) + 1 if flat else 0)
+    if not 2 <= c_tot <= SEP_MAX_COLS:
+        raise ValueError("separated classifier: 2 <= C_tot <= %d, got %d" % (SEP_MAX_COLS, c_tot))
+    if any(len(g) < 1 for g in gc) or any(not 0 <= c < c_tot for c in flat) or len(set(flat)) != len(flat):
+        raise ValueError("separated classifier: every group needs its background column, every column must lie in "
+                         "[0, %d) and in one group only, got %r" % (c_tot, gc))
+    return gc, c_tot, _hip.i32xn([len(g) for g in gc]), _hip.i32xn(flat)
+
+
+def box_head_targets_grouped(proposals, sep_sizes, targets, target_labels, groups, fg_iou=0.5, bg_iou=0.5,
+                             aug_thickness=None, batch_size_per_image=500, positive_fraction=0.25, weights=None, seed=None,
+                             defer=False, debug=None, box_coder=None):
+    """box_head_targets with separated-classifier groups (SeperateClassifier.seperate_subsample,
+    seperate_classifier.py:134-161) as ONE pass instead of one per group.  proposals: list over scenes of [n_b, 7], the
+    rows of a scene GROUP-MAJOR (all of group 0, then group 1, ...); sep_sizes: per scene the G host-known group sizes
+    (their sum is n_b); targets / target_labels: each scene's whole ground truth with its ORIGINAL labels.
+
+    Segment s = scene G + group is treated as box_head_targets treats a scene: its proposals meet only the scene's ground
+    truth whose label lies in the group (none: all background, zero targets), the label is the GROUP-LOCAL id, and the
+    sampler draws `batch_size_per_image` with the positive share per segment, its hash key over (seed, s, segment-local
+    row).  The ground truth is filtered and ordered on the device: one launch writes a key per box
+    (aabr_roi_gt_group_keys), ONE stable torch.sort of the keys orders every segment's boxes by (group-local label, row)
+    -- the order in which the reference concatenates a group's targets, which decides ties -- and the target kernel finds
+    each segment's run by binary search.  No host read of any per-group ground-truth count.  Library launches: 1 + 1 memset
+    + 6, whatever the scenes and G; scenes x G <= 16.
+
+    Returns a list over scenes of dicts: rows int64 [m] (scene-local proposal rows), bbox3d [m, 7], labels int64 [m]
+    (group-local), regression_targets [m, 7], sep_id int32 [m] -- the groups' samples one after the other, each in
+    ascending row.  `defer` / `debug` as box_head_targets; `debug` receives `matched_idx` (rows of the scene's own
+    ground-truth list), `matched_val`, `labels`, `regression_targets`, the padded `samp_*` [scenes G, B, ...], `gt_keys`,
+    `gt_perm`, `seed` and `info` [scenes G][8] after the read.  The IoU matrices are not stored in this form."""
+    from rpn_glue import draw_seed
+    gc, _c_tot, class_nums, cols = sep_group_tables(groups)
+    G = len(gc)
+    nb = len(proposals)
+    if not (nb == len(targets) == len(target_labels) == len(sep_sizes)):
+        raise ValueError("proposals, sep_sizes, targets and target_labels differ in length")
+    if nb == 0:
+        return (lambda: []) if defer else []
+    S = nb * G
+    if S > SEP_MAX_SEGMENTS:
+        raise _hip.AabrError("box_head_targets_grouped: scenes x groups <= %d, got %d x %d" % (SEP_MAX_SEGMENTS, nb, G))
+    n_s = [int(v) for sz in sep_sizes for v in sz]
+    if any(len(sz) != G for sz in sep_sizes) or any(v < 0 for v in n_s):
+        raise ValueError("sep_sizes needs %d non-negative sizes per scene" % G)
+    n_b = [int(p.shape[0]) for p in proposals]
+    if any(sum(n_s[b * G:(b + 1) * G]) != n_b[b] for b in range(nb)):
+        raise ValueError("sep_sizes do not add up to the scenes' proposal counts")
+    lib = _hip.load()
+    _hip.require_gpu(proposals[0])
+    dev = proposals[0].device
+    g_b = [int(t.shape[0]) for t in targets]
+    if any(int(l.numel()) != g for l, g in zip(target_labels, g_b)):
+        raise ValueError("target_labels do not match the targets")
+    props = torch.cat([p.reshape(-1, 7) for p in proposals]).to(device=dev, dtype=torch.float32).contiguous()
+    tg = torch.cat([t.reshape(-1, 7) for t in targets]).to(device=dev, dtype=torch.float32).contiguous()
+    tl = torch.cat([l.reshape(-1) for l in target_labels]).to(device=dev, dtype=torch.int64).contiguous()
+    N, B = sum(n_b), int(batch_size_per_image)
+    aug = aug_thickness or {}
+    aug = [float(aug.get(k, 0.0)) for k in ("target_Y", "target_Z", "anchor_Y", "anchor_Z")]
+    w = (1.0,) * 7 if weights is None else [float(v) for v in torch.as_tensor(weights).reshape(-1).tolist()]
+    corner = 0
+    if box_coder is not None:
+        w, _clip, corner = coder_args(box_coder)
+    keys = torch.empty(sum(g_b), dtype=torch.int64, device=dev)
+    check(lib.aabr_roi_gt_group_keys(ptr(tl), nb, _hip.i64xn(g_b), G, _c_tot, class_nums, cols, ptr(keys), _hip.stream()))
+    keys, perm = torch.sort(keys, stable=True)                            # the one sort: (segment, group-local label, row)
+    words = int(lib.aabr_roi_targets_scratch_words(S))
+    scratch = _hip.workspace("roi_targets", words + 2, torch.int32, dev)
+    off = (-scratch.data_ptr() // 4) % 2                                  # 8-byte alignment of the first word
+    midx = torch.empty(N, dtype=torch.int64, device=dev)
+    mval = torch.empty(N, dtype=torch.float32, device=dev)
+    labels = torch.empty(N, dtype=torch.int64, device=dev)
+    regt = torch.empty((N, 7), dtype=torch.float32, device=dev)
+    s_rows = torch.empty((S, B), dtype=torch.int64, device=dev)
+    s_labels = torch.empty((S, B), dtype=torch.int64, device=dev)
+    s_targets = torch.empty((S, B, 7), dtype=torch.float32, device=dev)
+    s_boxes = torch.empty((S, B, 7), dtype=torch.float32, device=dev)
+    info = torch.empty((S, INFO_WORDS), dtype=torch.int32, device=dev)
+    seed = int(draw_seed() if seed is None else seed) & 0xffffffff
+    check(lib.aabr_roi_targets_grouped(
+        ptr(props), ptr(tg), ptr(keys), ptr(perm), nb, G, _hip.i64xn(n_s), _hip.i64xn(g_b), _hip.f32x4(aug), -1,
+        int(_nms.REFERENCE_DEBUG_ONLY_XY), float(fg_iou), float(bg_iou), _hip.f32xn(w), corner, seed, B,
+        int(B * positive_fraction), ptr(midx), ptr(mval), ptr(labels), ptr(regt), ptr(s_rows), ptr(s_labels),
+        ptr(s_targets), ptr(s_boxes), ptr(info), scratch.data_ptr() + 4 * off, _hip.stream()))
+    if debug is not None:
+        debug.update(matched_idx=midx, matched_val=mval, labels=labels, regression_targets=regt, samp_rows=s_rows,
+                     samp_labels=s_labels, samp_targets=s_targets, samp_boxes=s_boxes, seed=seed, gt_keys=keys,
+                     gt_perm=perm)
+
+    def finish():
+        counts = _hip.read_back(info)                                     # the one read of the stage
+        if debug is not None:
+            debug["info"] = counts
+        out = []
+        for b in range(nb):
+            ms = [counts[b * G + g][0] for g in range(G)]
+            first = [sum(n_s[b * G:b * G + g]) for g in range(G)]         # the segment's first row inside its scene
+            seg = range(b * G, (b + 1) * G)
+            out.append({"rows": torch.cat([s_rows[s, :m] + o for s, m, o in zip(seg, ms, first)]),
+                        "bbox3d": torch.cat([s_boxes[s, :m] for s, m in zip(seg, ms)]),
+                        "labels": torch.cat([s_labels[s, :m] for s, m in zip(seg, ms)]),
+                        "regression_targets": torch.cat([s_targets[s, :m] for s, m in zip(seg, ms)]),
+                        "sep_id": torch.cat([torch.full((m,), g, dtype=torch.int32, device=dev)
+                                             for g, m in enumerate(ms)]),
+                        "sep_counts": ms})
+        return out
+
+    return finish if defer else finish()
+
+
+class _BoxHeadLossGrouped(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, reg, sep_id, labels, targets, tables, beta):
+        lib = _hip.load()
+        dev = logits.device
+        G, c_tot, class_nums, cols = tables
+        n = int(logits.shape[0])
+        logits_c, reg_c = logits.contiguous(), reg.contiguous()
+        cls_loss = torch.empty(G, dtype=torch.float32, device=dev)
+        box_loss = torch.empty(G, dtype=torch.float32, device=dev)
+        rows = torch.empty(G, dtype=torch.int32, device=dev)
+        flag = torch.empty((), dtype=torch.int32, device=dev)
+        scr = _hip.workspace("roi_box_loss_grouped", int(lib.aabr_roi_box_loss_grouped_scratch_floats()), torch.float32, dev)
+        check(lib.aabr_roi_box_loss_grouped_forward(
+            ptr(logits_c), ptr(reg_c), int(logits.dtype == torch.bfloat16), n, G, c_tot, class_nums, cols, ptr(sep_id),
+            ptr(labels), ptr(targets), beta, ptr(cls_loss), ptr(box_loss), ptr(rows), ptr(flag), ptr(scr), _hip.stream()))
+        ctx.save_for_backward(logits_c, reg_c, sep_id, labels, targets, rows)
+        ctx.cfg = (n, tables, beta)
+        ctx.mark_non_differentiable(flag)
+        return cls_loss, box_loss, flag
+
+    @staticmethod
+    def backward(ctx, g_cls, g_box, _g_flag):
+        lib = _hip.load()
+        logits, reg, sep_id, labels, targets, rows = ctx.saved_tensors
+        n, (G, c_tot, class_nums, cols), beta = ctx.cfg
+        dev = logits.device
+        g_cls = (g_cls if g_cls is not None else torch.zeros(G, device=dev)).float().contiguous()
+        g_box = (g_box if g_box is not None else torch.zeros(G, device=dev)).float().contiguous()
+        d_logits, d_reg = torch.empty_like(logits), torch.empty_like(reg)       # the kernel writes every element
+        check(lib.aabr_roi_box_loss_grouped_backward(
+            ptr(logits), ptr(reg), int(logits.dtype == torch.bfloat16), n, G, c_tot, class_nums, cols, ptr(sep_id),
+            ptr(labels), ptr(targets), beta, ptr(rows), ptr(g_cls), ptr(g_box), ptr(d_logits), ptr(d_reg), _hip.stream()))
+        return d_logits, d_reg, None, None, None, None, None
+
+
+def box_head_loss_grouped(class_logits, box_regression, sep_id, labels, regression_targets, groups, yaw_loss_mode="Diff",
+                          return_flag=False):
+    """box_head_loss with separated-classifier groups (SeperateClassifier.roi_cross_entropy_seperated and
+    roi_box_loss_seperated, seperate_classifier.py:163-204) as one call: class_logits [n, C_tot], box_regression [n, 7]
+    (class agnostic; fp32 or bf16 alike), sep_id [n] (each row's group), labels int64 [n] (GROUP-LOCAL, 0 = the group's
+    background), regression_targets fp32 [n, 7].  For every group g over its n_g rows:
+      cls_loss[g] = F.cross_entropy(class_logits[rows_g][:, grouped_classes[g]], labels[rows_g])
+      box_loss[g] = smooth_l1_loss(box_regression[pos_g], regression_targets[pos_g], beta=1/5, sum) / n_g
+    n_g is counted on the device; a group without rows gives NaN for that group only.  Returns (cls_loss [G], box_loss [G]),
+    fp32 device tensors with autograd to both inputs -- the gradient of a column outside a row's group is an exact 0; no
+    host read; 2 launches forward, 1 backward; bit-identical run to run.  A sep_id outside [0, G) or a label outside the
+    group's range adds nothing, gets zero gradients and raises the flag (`return_flag=True` appends it)."""
+    from rpn_glue import parse_yaw_loss_mode
+    parse_yaw_loss_mode(yaw_loss_mode)
+    gc, c_tot, class_nums, cols = sep_group_tables(groups)
+    if class_logits.dim() != 2 or box_regression.dim() != 2:
+        raise ValueError("class_logits and box_regression must be 2-D")
+    n = int(class_logits.shape[0])
+    if int(class_logits.shape[1]) != c_tot:
+        raise ValueError("class_logits must be [n, %d] (C_tot of the groups), got %s" % (c_tot, tuple(class_logits.shape)))
+    if class_logits.dtype not in (torch.float32, torch.bfloat16) or box_regression.dtype != class_logits.dtype:
+        raise TypeError("class_logits and box_regression must both be float32, or both bfloat16")
+    if tuple(box_regression.shape) != (n, 7):
+        raise ValueError("box_regression must be [%d, 7] (class agnostic with groups), got %s"
+                         % (n, tuple(box_regression.shape)))
+    if labels.numel() != n or regression_targets.numel() != 7 * n or sep_id.numel() != n:
+        raise ValueError("sep_id / labels / regression_targets do not have %d rows" % n)
+    _hip.require_gpu(class_logits)
+    dev = class_logits.device
+    sid = sep_id.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    lab = labels.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    tgt = regression_targets.reshape(-1, 7).to(device=dev, dtype=torch.float32).contiguous()
+    cls_loss, box_loss, flag = _BoxHeadLossGrouped.apply(class_logits, box_regression, sid, lab, tgt,
+                                                         (len(gc), c_tot, class_nums, cols), BOX_LOSS_BETA)
+    return (cls_loss, box_loss, flag) if return_flag else (cls_loss, box_loss)
+
+
+def box_detections_grouped(class_logits, box_regression, proposals, sep_id, groups, score_thresh=0.05, nms=0.5,
+                           nms_aug_thickness=None, detections_per_img=100, weights=None, defer=False, debug=None,
+                           bbox_xform_clip=10000.0, box_coder=None):
+    """box_detections with separated-classifier groups (SeperateClassifier.post_processor, seperate_classifier.py:342-364)
+    as one call: class_logits [N, C_tot], box_regression [N, 7] (class agnostic), proposals: list over scenes of [n_b, 7],
+    sep_id [N] (each row's group; the rows of a scene may come in any order -- no per-group sizes are needed).
+
+    Per row the softmax over its group's columns only; per scene and foreground column the rows of that column's group
+    above `score_thresh` through the NMS of box_detections; per scene the groups in ascending order, each group's
+    columns in group-local order (ascending original label), the `detections_per_img` cut per (scene, group) with ties at
+    the cut staying.  `labels` are original labels (the column index; never a background column).  5 launches, one read
+    of the counts at the end (`defer` as box_detections).  `debug` receives `prob` [N, C_tot] (exact zeros outside the
+    row's group), `boxes` [N, 7] and `info` (word 5 of a scene: some sep_id was outside [0, G))."""
+    gc, c_tot, class_nums, cols = sep_group_tables(groups)
+    G = len(gc)
+    lib = _hip.load()
+    _hip.require_gpu(class_logits)
+    dev = class_logits.device
+    logits = class_logits.to(torch.float32).contiguous()
+    reg = box_regression.to(device=dev, dtype=torch.float32).contiguous()
+    N = int(logits.shape[0])
+    if int(logits.shape[1]) != c_tot:
+        raise ValueError("class_logits must be [N, %d] (C_tot of the groups), got %s" % (c_tot, tuple(logits.shape)))
+    if tuple(reg.shape) != (N, 7):
+        raise ValueError("box_regression must be [%d, 7] (class agnostic with groups), got %s" % (N, tuple(reg.shape)))
+    n_b = [int(p.shape[0]) for p in proposals]
+    nb = len(n_b)
+    if nb == 0 and N == 0:
+        return (lambda: []) if defer else []
+    if sum(n_b) != N or sep_id.numel() != N:
+        raise ValueError("the proposals have %d rows, sep_id %d, class_logits %d" % (sum(n_b), sep_id.numel(), N))
+    props = torch.cat([p.reshape(-1, 7) for p in proposals]).to(device=dev, dtype=torch.float32).contiguous()
+    sid = sep_id.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    aug = (0.0, 0.0) if nms_aug_thickness is None else nms_aug_thickness
+    w = (1.0,) * 7 if weights is None else [float(v) for v in torch.as_tensor(weights).reshape(-1).tolist()]
+    corner = 0
+    if box_coder is not None:
+        w, bbox_xform_clip, corner = coder_args(box_coder)
+    cap = (c_tot - G) * POST_NMS
+    words = int(lib.aabr_roi_post_scratch_words(nb, max(n_b) if n_b else 0, c_tot, PRE_NMS))
+    if words < 0:
+        raise _hip.AabrError("box_detections_grouped: unsupported shape (1 <= scenes <= 16): C_tot=%d nb=%d" % (c_tot, nb))
+    scratch = _hip.workspace("roi_post", words + 2, torch.int32, dev)
+    off = (-scratch.data_ptr() // 4) % 2                                  # 8-byte alignment of the first word
+    prob = boxes = None
+    if debug is not None:
+        prob = torch.empty((N, c_tot), dtype=torch.float32, device=dev)
+        boxes = torch.empty((N, 7), dtype=torch.float32, device=dev)
+    det_rows = torch.empty((nb, cap), dtype=torch.int64, device=dev)
+    det_labels = torch.empty((nb, cap), dtype=torch.int64, device=dev)
+    det_scores = torch.empty((nb, cap), dtype=torch.float32, device=dev)
+    det_boxes = torch.empty((nb, cap, 7), dtype=torch.float32, device=dev)
+    info = torch.empty((nb, INFO_WORDS), dtype=torch.int32, device=dev)
+    check(lib.aabr_roi_post_detections_grouped(
+        ptr(logits), ptr(reg), ptr(props), ptr(sid), nb, _hip.i64xn(n_b), G, c_tot, class_nums, cols, _hip.f32xn(w),
+        corner, float(bbox_xform_clip), float(score_thresh), float(nms), float(aug[0]), float(aug[1]),
+        int(_nms.REFERENCE_DEBUG_ONLY_XY), PRE_NMS, POST_NMS, int(detections_per_img), ptr(prob), ptr(boxes),
+        ptr(det_rows), ptr(det_labels), ptr(det_scores), ptr(det_boxes), ptr(info), scratch.data_ptr() + 4 * off,
+        _hip.stream()))
+    if debug is not None:
+        debug["prob"], debug["boxes"] = prob, boxes
+
+    def finish():
+        counts = _hip.read_back(info)                                     # the one read of the stage
+        if debug is not None:
+            debug["info"] = counts
+        out = []
+        for b in range(nb):
+            m = counts[b][0]
+            out.append({"bbox3d": det_boxes[b, :m], "scores": det_scores[b, :m], "labels": det_labels[b, :m],
+                        "rows": det_rows[b, :m]})
+        return out
+
+    return finish if defer else finish()
+
+
 POOL_MAX_LEVELS = 8          # csrc/roi_pool.hip kPoolMaxLevels: the level table travels in the kernel arguments
 
 
@@ -696,9 +972,12 @@ def box_predictions_corner(x_cor, x_body, cls_w, cls_b, body_w, body_b, cor_w, c
 def box_head_cfg(C=8, resolution=(2, 3, 2), R=12, classes=("background", "wall", "door"), class_specific=True, separate=(),
                  corner=False, track=False, scales=(0.5, 0.25, 0.125), canonical=10.0, sampling=2, voxel_scale=1.0,
                  extractor="FPN2MLPFeatureExtractor", predictor="FPNPredictor", eval_in_train=0, detections=20,
-                 loss_weights=(1.0, 1.0, 1.0, 1.0, 0.0, 0.0, 0.0)):
+                 loss_weights=(1.0, 1.0, 1.0, 1.0, 0.0, 0.0, 0.0), separate_ids=()):
     """a plain attribute tree with the cfg keys the box head's modules read, named as in the reference's
-    config/defaults.py -- for smoke(), the timing tool and the tests, which have no yacs config"""
+    config/defaults.py -- for smoke(), the timing tool and the tests, which have no yacs config.  `separate` are the
+    separated groups' class names (MODEL.SEPARATE_CLASSES: the predictor adds one column per entry), `separate_ids` the
+    same groups as lists of class ids (MODEL.SEPARATE_CLASSES_ID: the loss evaluator builds its SeperateClassifier from
+    them)"""
     box_head = _Cfg(POOLER_RESOLUTION=tuple(resolution), POOLER_SCALES_SPATIAL=tuple(scales),
                     POOLER_SAMPLING_RATIO=sampling, CANONICAL_SIZE=canonical, MLP_HEAD_DIM=R, FEATURE_EXTRACTOR=extractor,
                     PREDICTOR=predictor)
@@ -706,7 +985,8 @@ def box_head_cfg(C=8, resolution=(2, 3, 2), R=12, classes=("background", "wall",
                  BATCH_SIZE_PER_IMAGE=16, POSITIVE_FRACTION=0.25, LABEL_AUG_THICKNESS_Y_TAR_ANC=(0.0, 0.0),
                  LABEL_AUG_THICKNESS_Z_TAR_ANC=(0.0, 0.0), SCORE_THRESH=0.05, NMS=0.5, NMS_AUG_THICKNESS_Y_Z=(0.0, 0.0),
                  DETECTIONS_PER_IMG=detections)
-    model = _Cfg(CORNER_ROI=corner, CLASS_SPECIFIC=class_specific, SEPARATE_CLASSES=list(separate), SEPARATE_CLASSES_ID=[],
+    model = _Cfg(CORNER_ROI=corner, CLASS_SPECIFIC=class_specific, SEPARATE_CLASSES=list(separate),
+                 SEPARATE_CLASSES_ID=[list(g) for g in separate_ids],
                  ROI_BOX_HEAD=box_head, ROI_HEADS=heads, LOSS=_Cfg(YAW_MODE="Diff", WEIGHTS=tuple(loss_weights)),
                  RPN=_Cfg(ADD_GT_PROPOSALS=False))
     return _Cfg(MODEL=model, SPARSE3D=_Cfg(VOXEL_SCALE=voxel_scale, nPlaneMap=C), SOLVER=_Cfg(TRACK_RUNNING_STATS=track),

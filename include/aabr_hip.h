@@ -1177,6 +1177,79 @@ int aabr_roi_box_loss_backward(const void *class_logits, const void *box_regress
                                const float *grad_cls_loss, const float *grad_box_loss, void *grad_logits,
                                void *grad_regression, void *stream);
 
+/* ---- the box head with separated-classifier groups (MODEL.SEPARATE_CLASSES; the reference's
+ * modeling/seperate_classifier.py, which loops over the groups around its single-group code).  Added after 640 without a
+ * bump: symbols only.  G groups share the C_tot = num_input_classes + G - 1 columns of class_logits.  The description is
+ * two host tables -- class_nums int32 [G] and cols int32 [sum of class_nums], the groups' column lists one after the
+ * other, each in group-local order with the group's background column first -- and travels to the kernels by value: no
+ * device table.  Every non-background column index is that class's original label.  Validated before any HIP call
+ * (AABR_EINVAL): 2 <= G <= 8, 2 <= C_tot <= 32, every group 1 .. C_tot columns, every column index in [0, C_tot) and in
+ * at most one group; besides the limits of the plain entry points.  Box regression is class agnostic ([n, 7]).
+ *
+ * Stage 1 (SeperateClassifier.seperate_subsample): a proposal takes part only in its own group's ground truth.  The
+ * proposals are concatenated scene-major and group-major inside a scene; segment s = scene G + group has n_host[s] rows
+ * (host-known) and is to aabr_roi_targets_grouped what a scene is to aabr_roi_targets_coder: IoU with the ground truth of
+ * its scene whose label lies in its group, the Matcher, the label as the GROUP-LOCAL id (0 background, -1 ignored), the
+ * coder's encode, the balanced sampler per segment (hash key over (seed, s, segment-local row)) and the ascending
+ * compaction; samp_* and info are [nb G][...].  A segment without ground truth of its group: all background, zero
+ * targets.  The host never learns how many boxes of a scene fall into a group:
+ *   aabr_roi_gt_group_keys (1 launch): target_labels int64 (the batch's ground truth, scene-major, g_host[b] rows for
+ *     scene b, ORIGINAL labels) -> keys int64: (b G + g) 32 + i when the label is column cols[g][i], nb G 32 (behind
+ *     every segment) when no group owns it;
+ *   the caller sorts the keys ascending and STABLY and passes the sorted keys and the permutation (gt_perm[k] = the
+ *     batch row at sorted position k): a segment's ground truth is then one run in the order (group-local label, row),
+ *     the order in which the reference concatenates a group's targets, so the first maximum of a tie is the lower
+ *     group-local label and then the lower row;
+ *   aabr_roi_targets_grouped (1 memset + 6 launches whatever nb and G) finds each segment's run by binary search on the
+ *     device and reads targets [sum g_host, 7] through gt_perm.  matched_idx is the row in the scene's own list.
+ * nb G <= 16 segments.  scratch: aabr_roi_targets_scratch_words(nb G).  The IoU matrices are not stored.               */
+int aabr_roi_gt_group_keys(const int64_t *target_labels, int nb, const int64_t *g_host, int G, int C_tot,
+                           const int32_t *class_nums_host, const int32_t *cols_host, int64_t *keys, void *stream);
+int aabr_roi_targets_grouped(const float *proposals, const float *targets, const int64_t *gt_keys, const int64_t *gt_perm,
+                             int nb, int G, const int64_t *n_host, const int64_t *g_host, const float *aug_host,
+                             int criterion, int only_xy, float fg_iou, float bg_iou, const float *weights_host,
+                             int corner_coder, uint32_t seed, int batch_size_per_image, int num_pos_max,
+                             int64_t *matched_idx, float *matched_val, int64_t *labels, float *regression_targets,
+                             int64_t *samp_rows, int64_t *samp_labels, float *samp_targets, float *samp_boxes,
+                             int32_t *info, int32_t *scratch, void *stream);
+/* Stage 2 (roi_cross_entropy_seperated, roi_box_loss_seperated): class_logits [n, C_tot], box_regression [n, 7] (fp32 or
+ * bf16), per row sep_id int32 (its group), labels int64 (group-local) and regression_targets fp32 [n, 7]:
+ *   cls_loss[g] = sum over the rows of group g of (logsumexp over the group's columns - x[cols[g][label]]) / n_g
+ *   box_loss[g] = sum over the group's rows with label > 0 and 7 columns of smoothL1(|pred - target|) / n_g
+ * n_g, the group's row count, is counted on the device and left in group_rows int32 [G] for the backward; n_g = 0 gives
+ * NaN for that group only.  Sums in a fixed order (per thread in row order, a fixed tree per workgroup, then workgroup
+ * order), no float atomics.  A sep_id outside [0, G) (the row is in no group) or a label outside [0, class_nums[g]) (the
+ * row counts in n_g) is never used as an index: the row adds nothing, gets zero gradients, *flag becomes 1.  Launches: 2.
+ * scratch: aabr_roi_box_loss_grouped_scratch_floats() fp32.  Backward (1 launch): g_cls / g_box are device fp32 [G];
+ * EVERY element of grad_logits [n, C_tot] and grad_regression [n, 7] is written, exact zeros outside the row's group. */
+int64_t aabr_roi_box_loss_grouped_scratch_floats(void);
+int aabr_roi_box_loss_grouped_forward(const void *class_logits, const void *box_regression, int input_bf16, int64_t n,
+                                      int G, int C_tot, const int32_t *class_nums_host, const int32_t *cols_host,
+                                      const int32_t *sep_id, const int64_t *labels, const float *regression_targets,
+                                      float beta, float *cls_loss, float *box_loss, int32_t *group_rows, int32_t *flag,
+                                      float *scratch, void *stream);
+int aabr_roi_box_loss_grouped_backward(const void *class_logits, const void *box_regression, int input_bf16, int64_t n,
+                                       int G, int C_tot, const int32_t *class_nums_host, const int32_t *cols_host,
+                                       const int32_t *sep_id, const int64_t *labels, const float *regression_targets,
+                                       float beta, const int32_t *group_rows, const float *grad_cls_loss,
+                                       const float *grad_box_loss, void *grad_logits, void *grad_regression,
+                                       void *stream);
+/* Detections (SeperateClassifier.post_processor): aabr_roi_post_detections_coder with groups.  sep_id int32 [N], rows in
+ * any order inside a scene.  Per row the softmax over its group's columns (group-local order), every other column of
+ * prob an exact 0; boxes [N, 7].  Per (scene, foreground column c): the rows OF c's GROUP with prob > score_thresh
+ * (membership is tested; a zero is not relied on), then the same NMS.  Per scene the groups ascending, each group's
+ * columns in group-local order, the detections_per_img cut PER (scene, group) with ties at the cut staying; the label is
+ * the column index (the original label); capacity (C_tot - G) post_max rows per scene.  A sep_id outside [0, G): the
+ * row is no candidate and info[b][5] becomes 1.  5 launches; scratch: aabr_roi_post_scratch_words(nb, n_max, C_tot,
+ * pre_max).                                                                                                          */
+int aabr_roi_post_detections_grouped(const float *class_logits, const float *box_regression, const float *proposals,
+                                     const int32_t *sep_id, int nb, const int64_t *n_host, int G, int C_tot,
+                                     const int32_t *class_nums_host, const int32_t *cols_host, const float *weights_host,
+                                     int corner_coder, float clip, float score_thresh, float nms_thresh, float nms_min_yx,
+                                     float nms_min_z, int only_xy, int pre_max, int post_max, int detections_per_img,
+                                     float *prob, float *boxes, int64_t *det_rows, int64_t *det_labels, float *det_scores,
+                                     float *det_boxes, int32_t *info, int32_t *scratch, void *stream);
+
 /* ---- the box head's dense layers (csrc/roi_mlp.hip): FPN2MLPFeatureExtractor after its pooler
  * (roi_box_feature_extractors.py:46-169: Conv3d([1,1,pz]) + BatchNorm3d + ReLU, fc6 + ReLU, fc7 + ReLU) and FPNPredictor
  * (roi_box_predictors.py:34-109) as a dense fp32 GEMM family on v_mfma_f32_32x32x2_f32 (fp32 storage only, exact fp32:
