@@ -214,6 +214,11 @@ _SIGS = {
                                         _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aabr_rpn_loss_backward": (C.c_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32p, _i32p, _vp, _i32, _f32, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _vp]),
+    "aabr_rpn_loss_grouped_scratch_words": (C.c_int64, [_i32, _i32]),
+    "aabr_rpn_loss_grouped_forward": (C.c_int, [_i32, _vp, _vp, _vp, _i64p, _i32, _i32, _i32, _i32, _i32p, _i32p, _vp, _vp,
+                                                C.c_uint32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aabr_rpn_loss_grouped_backward": (C.c_int, [_i32, _vp, _vp, _i64p, _i32, _i32, _i32, _i32, _i32p, _i32p, _vp, _i32,
+                                                 _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aabr_sample_list": (C.c_int, [_i32, _vp, C.POINTER(C.c_int64), C.c_uint32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                    _vp]),
     "aabr_smooth_l1_scratch_floats": (C.c_int64, []),
@@ -268,6 +273,9 @@ _SIGS = {
     "aabr_rpn_head_scratch_floats": (C.c_int64, [_i64, _i32, _i32]),
     "aabr_rpn_head_forward": (C.c_int, [_rmp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aabr_rpn_head_backward": (C.c_int, [_rmp, _i32, _i32, _i32] + [_vp] * 12),
+    "aabr_rpn_head_grouped_scratch_floats": (C.c_int64, [_i64, _i32, _i32, _i32]),
+    "aabr_rpn_head_grouped_forward": (C.c_int, [_rmp, _i32, _i32, _i32, _i32] + [_vp] * 8),
+    "aabr_rpn_head_grouped_backward": (C.c_int, [_rmp, _i32, _i32, _i32, _i32] + [_vp] * 12),
     "aabr_sgd_chunk_elems": (C.c_int, []),
     "aabr_sgd_chunk_table": (C.c_int64, [_i64p, _i64p, _i32p, _i64, _i64, _i64p, _i64]),
     "aabr_sgd_momentum_step": (C.c_int, [_vp, _vp, _i64, _vp, _i64p, _i64, _i64, _vp, _vp, _i32, _f32p, _f32p, _i32, _f32,

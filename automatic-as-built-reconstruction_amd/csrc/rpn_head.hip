@@ -28,6 +28,16 @@
 //
 // Launches: forward 1; backward 2 (main, reduce) -- whatever n_maps.  No weight pack is needed.  All maps empty: no
 // launch; backward then zeroes the six weight gradients with memsets.
+//
+// Separated-classifier groups (aabr_rpn_head_grouped_*; G = len(SEPARATE_CLASSES) + 1 RPN branches, 2 <= G <= 8,
+// A G <= 16): Wc [A G, C] and Wr [7 A G, C] in the reference's row order (a G + g, a 7 G + 7 g + k), outputs GROUP-MAJOR
+// ([G][V, A], [G][V, A, 7]) so a group's slice is a plain-layout tensor.  k_rpn_head_grouped_fwd<C>: the same first
+// product (rpn_hidden_tile), the second over up to four 32-column tiles of [Wc; Wr], wave (wm, wn) owning tiles wn,
+// wn + 2, in the plain kernel's order over the hidden units -- the same bits as the plain kernel on the matching rows;
+// the permutation is the write-out's.  58.9 KB of LDS at C = 128, as the plain kernel.  k_rpn_head_grouped_bwd<C>: D is
+// [64][NP], NP = 32 ceil(8 A G / 32), loaded in packed order from the group-major gradients; d[Wc; Wr] is up to 16 tiles
+// (4 per wave); [Wc; Wr] is staged 32 rows at a time in the W1 chunk buffer and dt accumulates over the tiles in
+// registers.  LDS per workgroup at C = 128, A G = 16: 116 992 B = 114.3 KiB (of 160 KiB); same 2 launches.
 #include "common.h"
 
 namespace aabr {
@@ -38,6 +48,8 @@ constexpr int kRpnMaxMaps = 8;
 constexpr int kRpnMaxGroups = 256; // one workgroup per CU of an MI355X; a constant, never read from the device
 constexpr int kRpnLD = kRpnT + 2;  // LDS row of a [reduce][64 rows] image
 constexpr int kRpnLD2 = kRpnN2 + 2;
+constexpr int kRpnMaxN2 = 128;     // with groups: 8 A G <= 128 output columns, up to four MFMA tiles
+constexpr int kRpnLDG = kRpnMaxN2 + 2;
 
 struct RpnMaps {
   const float *f[kRpnMaxMaps];
@@ -68,19 +80,16 @@ __device__ inline float rpn_w2(const float *__restrict__ Wc, const float *__rest
 // accumulator register r of a 32 x 32 tile: row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31
 __device__ inline int rpn_acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
+// the first product of a forward tile: t = relu(f W1^T + b1) for the 64 rows from row0 of map m -> sT [hidden unit][row],
+// and to `hidden` when that is not NULL.  sA [32][64 + 2], sB >= [32][C + 2].  Ends WITHOUT a barrier.
 template <int C>
-__global__ __launch_bounds__(256) void k_rpn_head_fwd(const RpnMaps g, const float *__restrict__ W1,
-                                                      const float *__restrict__ b1, const float *__restrict__ Wc,
-                                                      const float *__restrict__ bc, const float *__restrict__ Wr,
-                                                      const float *__restrict__ br, int A, float *__restrict__ hidden) {
+__device__ __forceinline__ void rpn_hidden_tile(const RpnMaps &g, int m, int64_t row0, const float *__restrict__ W1,
+                                                const float *__restrict__ b1, float *__restrict__ hidden, float *sA,
+                                                float *sB, float *sT) {
   constexpr int NT = C / 32, LDB = C + 2;
-  __shared__ float sA[32 * kRpnLD];
-  __shared__ float sB[32 * LDB];
-  __shared__ float sT[C * kRpnLD];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave & 1, wn = wave >> 1;
   const int l31 = lane & 31, kh = 16 * (lane >> 5), tk = t & 31, tr = t >> 5;
-  const int m = rpn_map_of(g, blockIdx.x);
-  const int64_t rows = g.rows[m], row0 = (int64_t)(blockIdx.x - g.first[m]) * kRpnT;
+  const int64_t rows = g.rows[m];
   const float *__restrict__ f = g.f[m];
 
   f32x16 acc[2];
@@ -125,6 +134,22 @@ __global__ __launch_bounds__(256) void k_rpn_head_fwd(const RpnMaps g, const flo
       if (hidden != nullptr && row0 + row < rows) hidden[(g.hoff[m] + row0 + row) * C + col] = x;
     }
   }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void k_rpn_head_fwd(const RpnMaps g, const float *__restrict__ W1,
+                                                      const float *__restrict__ b1, const float *__restrict__ Wc,
+                                                      const float *__restrict__ bc, const float *__restrict__ Wr,
+                                                      const float *__restrict__ br, int A, float *__restrict__ hidden) {
+  constexpr int LDB = C + 2;
+  __shared__ float sA[32 * kRpnLD];
+  __shared__ float sB[32 * LDB];
+  __shared__ float sT[C * kRpnLD];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave & 1, wn = wave >> 1;
+  const int l31 = lane & 31, kh = 16 * (lane >> 5), tk = t & 31, tr = t >> 5;
+  const int m = rpn_map_of(g, blockIdx.x);
+  const int64_t rows = g.rows[m], row0 = (int64_t)(blockIdx.x - g.first[m]) * kRpnT;
+  rpn_hidden_tile<C>(g, m, row0, W1, b1, hidden, sA, sB, sT);
 
   f32x16 acc2;
 #pragma unroll
@@ -155,8 +180,79 @@ __global__ __launch_bounds__(256) void k_rpn_head_fwd(const RpnMaps g, const flo
   }
 }
 
-// floats of one workgroup's partial: dW1 [C][C], d[Wc; Wr] [32][C], db1 [C], [dbc; dbr] [32]
-__host__ __device__ constexpr int64_t rpn_partial_floats(int C) { return (int64_t)C * C + 32 * C + C + 32; }
+// ---- the separated-classifier groups.  Packed column n of [Wc; Wr] is row n of Wc (n < A G) or row n - A G of Wr: the
+// reference's channel order, a G + g and a 7 G + 7 g + k.  Its value belongs to group g and sits at `off` of a row of
+// that group's slice ([rows, A] or [rows, 7 A]); the slices of a map lie group-major behind one pointer.
+__device__ inline void rpn_group_col(int n, int A, int G, bool &is_obj, int &g, int &off) {
+  is_obj = n < A * G;
+  if (is_obj) {
+    off = n / G, g = n - off * G;
+    return;
+  }
+  const int r = n - A * G, a = r / (7 * G), rem = r - a * 7 * G;
+  g = rem / 7;
+  off = a * 7 + rem - g * 7;
+}
+
+// Forward with groups: the first product is rpn_hidden_tile, as in k_rpn_head_fwd; the second runs over the NT2 =
+// ceil(8 A G / 32) <= 4 column tiles, wave (wm, wn) owning tiles wn and wn + 2, in k_rpn_head_fwd's order over the hidden
+// units, so an element is the same fmaf chain as the plain kernel's on the matching weight row.
+template <int C>
+__global__ __launch_bounds__(256) void k_rpn_head_grouped_fwd(const RpnMaps g, const float *__restrict__ W1,
+                                                              const float *__restrict__ b1, const float *__restrict__ Wc,
+                                                              const float *__restrict__ bc, const float *__restrict__ Wr,
+                                                              const float *__restrict__ br, int A, int G,
+                                                              float *__restrict__ hidden) {
+  __shared__ float sA[32 * kRpnLD];
+  __shared__ float sB[32 * kRpnLDG];
+  __shared__ float sT[C * kRpnLD];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave & 1, wn = wave >> 1;
+  const int l31 = lane & 31, kh = 16 * (lane >> 5), tk = t & 31, tr = t >> 5;
+  const int m = rpn_map_of(g, blockIdx.x);
+  const int64_t rows = g.rows[m], row0 = (int64_t)(blockIdx.x - g.first[m]) * kRpnT;
+  const int AG = A * G, NT2 = (8 * AG + 31) / 32;
+  rpn_hidden_tile<C>(g, m, row0, W1, b1, hidden, sA, sB, sT);
+
+  f32x16 acc2[2];
+#pragma unroll
+  for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc2[jj][r] = 0.f;
+  for (int k0 = 0; k0 < C; k0 += 32) {
+    __syncthreads();                                  // sT is complete; the previous chunk's reads of sB are done
+    for (int i = 0; i < 4 * NT2; ++i) sB[tk * kRpnLDG + tr + 8 * i] = rpn_w2(Wc, Wr, AG, C, tr + 8 * i, k0 + tk);
+    __syncthreads();
+#pragma unroll 4
+    for (int kk = 0; kk < 16; ++kk) {
+      const float a = sT[(k0 + kk + kh) * kRpnLD + wm * 32 + l31];
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) {
+        const int j = wn + 2 * jj;
+        if (j < NT2) acc2[jj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, sB[(kk + kh) * kRpnLDG + j * 32 + l31], acc2[jj], 0, 0, 0);
+      }
+    }
+  }
+#pragma unroll
+  for (int jj = 0; jj < 2; ++jj) {
+    const int col = (wn + 2 * jj) * 32 + l31;
+    if (col >= 8 * AG) continue;
+    bool is_obj;
+    int grp, off;
+    rpn_group_col(col, A, G, is_obj, grp, off);
+    const float bias = is_obj ? bc[col] : br[col - AG];
+    const int64_t ld = is_obj ? A : 7 * A;
+    float *__restrict__ out = (is_obj ? g.obj[m] : g.reg[m]) + grp * rows * ld + off;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int64_t row = row0 + wm * 32 + rpn_acc_row(r, lane);
+      if (row < rows) out[row * ld] = acc2[jj][r] + bias;
+    }
+  }
+}
+
+// floats of one workgroup's partial: dW1 [C][C], d[Wc; Wr] [np][C], db1 [C], [dbc; dbr] [np]; np = the packed columns
+// padded to MFMA tiles: 32 without groups
+__host__ __device__ constexpr int64_t rpn_partial_floats(int C, int np = kRpnN2) { return (int64_t)C * C + np * C + C + np; }
 
 template <int C>
 __global__ __launch_bounds__(256) void k_rpn_head_bwd(const RpnMaps g, const float *__restrict__ W1,
@@ -331,12 +427,214 @@ __global__ __launch_bounds__(256) void k_rpn_head_bwd(const RpnMaps g, const flo
   if (t < C + kRpnN2) part[C * C + 32 * C + t] = dbacc;
 }
 
+// Backward with groups: k_rpn_head_bwd's phases with D = [d_obj | d_reg] in packed-column order, NP = 32 NT2 wide, read
+// from the group-major gradients through a column table (sCol: group, offset in the slice's row).  d[Wc; Wr] is NT2 x NT
+// tiles, wave w owning tiles w, w + 4, ... as for dW1.  [Wc; Wr] is NOT held in LDS: dt accumulates in registers over
+// the NT2 tiles, each tile's 32 rows of [Wc; Wr] staged in sB (free until the d_f phase).  LDS: sX, sDT [64][C + 2],
+// sB [32][C + 2], sD [64][NP + 2]; 113.8 KiB at C = 128, A G = 16.
+template <int C>
+__global__ __launch_bounds__(256) void k_rpn_head_grouped_bwd(const RpnMaps g, const float *__restrict__ W1,
+                                                              const float *__restrict__ Wc, const float *__restrict__ Wr,
+                                                              int A, int G, const float *__restrict__ hidden,
+                                                              uint32_t total_tiles, float *__restrict__ scratch) {
+  constexpr int NT = C / 32, LDC = C + 2;
+  extern __shared__ float smem[];
+  __shared__ int sCol[kRpnMaxN2];       // group << 8 | offset; -1 beyond the 8 A G columns
+  const int AG = A * G, NT2 = (8 * AG + 31) / 32, NP = 32 * NT2, LDD = NP + 2;
+  float *sX = smem;                     // [64][C + 2]: the t tile, then the f tile
+  float *sDT = sX + kRpnT * LDC;        // [64][C + 2]: dt
+  float *sB = sDT + kRpnT * LDC;        // [32][C + 2]: 32 rows of [Wc; Wr], then a chunk of W1's rows
+  float *sD = sB + 32 * LDC;            // [64][NP + 2]: D
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave & 1, wn = wave >> 1;
+  const int l31 = lane & 31, kh = 16 * (lane >> 5);
+
+  if (t < kRpnMaxN2) {
+    int v = -1;
+    if (t < 8 * AG) {
+      bool is_obj;
+      int grp, off;
+      rpn_group_col(t, A, G, is_obj, grp, off);
+      v = grp << 8 | off;
+    }
+    sCol[t] = v;
+  }
+
+  f32x16 accW1[4], accW2[4], acc[2];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) accW1[q][r] = 0.f, accW2[q][r] = 0.f;
+  float dbacc = 0.f;                    // thread c < C: db1[c]; thread C + n, n < NP: [dbc; dbr][n]
+
+  for (uint32_t tile = blockIdx.x; tile < total_tiles; tile += gridDim.x) {
+    const int m = rpn_map_of(g, tile);
+    const int64_t rows = g.rows[m], row0 = (int64_t)(tile - g.first[m]) * kRpnT;
+    const float *__restrict__ dobj = g.obj[m];
+    const float *__restrict__ dreg = g.reg[m];
+    const float *__restrict__ tm = hidden + (g.hoff[m] + row0) * C;
+    const float *__restrict__ fm = g.f[m] + row0 * C;
+    const int64_t left = rows - row0;   // >= 1
+
+    __syncthreads();                    // the previous tile's reads are done (first tile: sCol is complete)
+    for (int i = t; i < kRpnT * NP; i += 256) {
+      const int row = i / NP, n = i - row * NP;
+      const int cv = sCol[n];
+      float v = 0.f;
+      if (row < left && cv >= 0) {
+        const int64_t grp = cv >> 8, off = cv & 255;
+        if (n < AG) v = dobj ? dobj[(grp * rows + row0 + row) * A + off] : 0.f;
+        else v = dreg ? dreg[(grp * rows + row0 + row) * (7 * A) + off] : 0.f;
+      }
+      sD[row * LDD + n] = v;
+    }
+    for (int i = t; i < kRpnT * C; i += 256) {
+      const int row = i / C, c = i - row * C;
+      sX[row * LDC + c] = row < left ? tm[(int64_t)row * C + c] : 0.f;
+    }
+    __syncthreads();
+
+    // d[Wc; Wr] += D^T t: rows n (NP), columns c, reduce over the 64 sites; wave w owns tiles w, w + 4, ... of NT2 x NT
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+      const int q = wave + 4 * qq;
+      if (q >= NT2 * NT) continue;
+      const int ni = q / NT, cj = q - ni * NT;
+#pragma unroll 4
+      for (int kk = 0; kk < 16; ++kk) {
+#pragma unroll
+        for (int h = 0; h < kRpnT / 32; ++h) {
+          const int r_ = 32 * h + kk + kh;
+          accW2[qq] = __builtin_amdgcn_mfma_f32_32x32x2f32(sD[r_ * LDD + ni * 32 + l31], sX[r_ * LDC + cj * 32 + l31],
+                                                           accW2[qq], 0, 0, 0);
+        }
+      }
+    }
+    if (t >= C && t < C + NP) {
+      for (int r_ = 0; r_ < kRpnT; ++r_) dbacc += sD[r_ * LDD + t - C];
+    }
+    // dt = (D [Wc; Wr]) . (t > 0): rows = sites (wm), columns = hidden units (tiles wn, wn + 2), reduce over n, a
+    // 32-row tile of [Wc; Wr] at a time
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[jj][r] = 0.f;
+    for (int nt = 0; nt < NT2; ++nt) {
+      if (nt > 0) __syncthreads();      // the previous tile's reads of sB are done
+      for (int i = t; i < 32 * C; i += 256) {
+        const int n = i / C, c = i - n * C;
+        sB[n * LDC + c] = rpn_w2(Wc, Wr, AG, C, nt * 32 + n, c);
+      }
+      __syncthreads();
+#pragma unroll 4
+      for (int kk = 0; kk < 16; ++kk) {
+        const float a = sD[(wm * 32 + l31) * LDD + nt * 32 + kk + kh];
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) {
+          const int j = wn + 2 * jj;
+          if (j < NT) acc[jj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, sB[(kk + kh) * LDC + j * 32 + l31], acc[jj], 0, 0, 0);
+        }
+      }
+    }
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      const int j = wn + 2 * jj;
+      if (j >= NT) continue;
+      const int col = j * 32 + l31;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = wm * 32 + rpn_acc_row(r, lane);
+        sDT[row * LDC + col] = sX[row * LDC + col] > 0.f ? acc[jj][r] : 0.f;
+      }
+    }
+    __syncthreads();                    // dt is complete; every read of the t tile and of sB is done
+
+    for (int i = t; i < kRpnT * C; i += 256) {
+      const int row = i / C, c = i - row * C;
+      sX[row * LDC + c] = row < left ? fm[(int64_t)row * C + c] : 0.f;
+    }
+    if (t < C) {
+      for (int r_ = 0; r_ < kRpnT; ++r_) dbacc += sDT[r_ * LDC + t];
+    }
+    __syncthreads();
+
+    // dW1 += dt^T f
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+      const int q = wave + 4 * qq;
+      if (q >= NT * NT) continue;
+      const int ci = q / NT, kj = q - ci * NT;
+#pragma unroll 4
+      for (int kk = 0; kk < 16; ++kk) {
+#pragma unroll
+        for (int h = 0; h < kRpnT / 32; ++h) {
+          const int r_ = 32 * h + kk + kh;
+          accW1[qq] = __builtin_amdgcn_mfma_f32_32x32x2f32(sDT[r_ * LDC + ci * 32 + l31], sX[r_ * LDC + kj * 32 + l31],
+                                                           accW1[qq], 0, 0, 0);
+        }
+      }
+    }
+
+    // d_f = dt W1
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[jj][r] = 0.f;
+    for (int c0 = 0; c0 < C; c0 += 32) {
+      __syncthreads();                  // the previous chunk's reads of sB are done
+      for (int i = t; i < 32 * C; i += 256) {
+        const int cc = i / C, k = i - cc * C;
+        sB[cc * LDC + k] = W1[(c0 + cc) * C + k];
+      }
+      __syncthreads();
+#pragma unroll 4
+      for (int kk = 0; kk < 16; ++kk) {
+        const float a = sDT[(wm * 32 + l31) * LDC + c0 + kk + kh];
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) {
+          const int j = wn + 2 * jj;
+          if (j < NT) acc[jj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, sB[(kk + kh) * LDC + j * 32 + l31], acc[jj], 0, 0, 0);
+        }
+      }
+    }
+    float *__restrict__ df = g.df[m] + row0 * C;
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      const int j = wn + 2 * jj;
+      if (j >= NT) continue;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = wm * 32 + rpn_acc_row(r, lane);
+        if (row < left) df[(int64_t)row * C + j * 32 + l31] = acc[jj][r];
+      }
+    }
+  }
+
+  // this workgroup's partial (a workgroup without a tile writes zeros): dW1, d[Wc; Wr] [NP][C], db1, [dbc; dbr] [NP]
+  float *__restrict__ part = scratch + (int64_t)blockIdx.x * rpn_partial_floats(C, NP);
+#pragma unroll
+  for (int qq = 0; qq < 4; ++qq) {
+    const int q = wave + 4 * qq;
+    if (q < NT * NT) {
+      const int ci = q / NT, kj = q - ci * NT;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) part[(ci * 32 + rpn_acc_row(r, lane)) * C + kj * 32 + l31] = accW1[qq][r];
+    }
+    if (q < NT2 * NT) {
+      const int ni = q / NT, cj = q - ni * NT;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) part[C * C + (ni * 32 + rpn_acc_row(r, lane)) * C + cj * 32 + l31] = accW2[qq][r];
+    }
+  }
+  if (t < C + NP) part[C * C + NP * C + t] = dbacc;
+}
+
 // the partials added in workgroup order, stored into the six gradients
+// (np = padded packed columns, A = rows of Wc: the anchors, times the groups when there are any)
 __global__ __launch_bounds__(256) void k_rpn_head_reduce(const float *__restrict__ scratch, int groups, int C, int A,
-                                                         float *__restrict__ dW1, float *__restrict__ db1,
+                                                         int np, float *__restrict__ dW1, float *__restrict__ db1,
                                                          float *__restrict__ dWc, float *__restrict__ dbc,
                                                          float *__restrict__ dWr, float *__restrict__ dbr) {
-  const int64_t per = rpn_partial_floats(C);
+  const int64_t per = rpn_partial_floats(C, np);
   int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= per) return;
   float s = scratch[i];
@@ -346,13 +644,13 @@ __global__ __launch_bounds__(256) void k_rpn_head_reduce(const float *__restrict
     return;
   }
   i -= (int64_t)C * C;
-  if (i < 32 * C) {
+  if (i < np * C) {
     const int n = (int)(i / C), c = (int)(i - (int64_t)n * C);
     if (n < A) dWc[n * C + c] = s;
     else if (n < 8 * A) dWr[(n - A) * C + c] = s;
     return;
   }
-  i -= 32 * C;
+  i -= np * C;
   if (i < C) {
     db1[i] = s;
     return;
@@ -476,8 +774,100 @@ extern "C" int aabr_rpn_head_backward(const AabrRpnMap *maps_host, int n_maps, i
   }
   if (rc != AABR_OK) return rc;
   const int64_t per = rpn_partial_floats(C);
-  hipLaunchKernelGGL(k_rpn_head_reduce, dim3((unsigned)ceil_div(per, 256)), dim3(256), 0, st, scratch, groups, C, A, dW1,
-                     db1, dWc, dbc, dWr, dbr);
+  hipLaunchKernelGGL(k_rpn_head_reduce, dim3((unsigned)ceil_div(per, 256)), dim3(256), 0, st, scratch, groups, C, A, kRpnN2,
+                     dW1, db1, dWc, dbc, dWr, dbr);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+// ---------------------------------------------------------------------------------------- separated-classifier groups
+static bool rpn_groups_ok(int A, int G) { return A >= 1 && A <= 4 && G >= 2 && G <= 8 && A * G <= 16; }
+
+static int rpn_group_np(int A, int G) { return 32 * ((8 * A * G + 31) / 32); }
+
+static size_t rpn_grouped_bwd_lds_bytes(int C, int np) {
+  return sizeof(float) * ((size_t)(2 * kRpnT + 32) * (C + 2) + (size_t)kRpnT * (np + 2));
+}
+
+extern "C" int64_t aabr_rpn_head_grouped_scratch_floats(int64_t total_tiles, int C, int A, int G) {
+  if (total_tiles < 1 || !rpn_c_ok(C) || !rpn_groups_ok(A, G)) return 0;
+  return (int64_t)aabr_rpn_head_groups(total_tiles) * rpn_partial_floats(C, rpn_group_np(A, G));
+}
+
+#define AABR_RPN_CHECK_GROUPS(A, G)                                                                                     \
+  AABR_CHECK_ARG((A) >= 1 && (A) <= 4, "A must be 1..4");                                                               \
+  AABR_CHECK_ARG(rpn_groups_ok(A, G), "groups: 2 <= G <= 8 and A G <= 16")
+
+extern "C" int aabr_rpn_head_grouped_forward(const AabrRpnMap *maps_host, int n_maps, int C, int A, int G, const float *W1,
+                                             const float *b1, const float *Wc, const float *bc, const float *Wr,
+                                             const float *br, float *hidden, void *stream_) {
+  AABR_RPN_CHECK_GROUPS(A, G);
+  RpnMaps g;
+  int64_t tiles = 0;
+  const int rc = rpn_head_table(maps_host, n_maps, C, A, false, g, &tiles);
+  if (rc != AABR_OK) return rc;
+  AABR_CHECK_ARG(W1 && b1 && Wc && bc && Wr && br, "null pointer");
+  if (tiles == 0) return AABR_OK;
+  hipStream_t st = (hipStream_t)stream_;
+  const dim3 grid((unsigned)tiles), block(256);
+  switch (C) {
+  case 32: hipLaunchKernelGGL(k_rpn_head_grouped_fwd<32>, grid, block, 0, st, g, W1, b1, Wc, bc, Wr, br, A, G, hidden); break;
+  case 64: hipLaunchKernelGGL(k_rpn_head_grouped_fwd<64>, grid, block, 0, st, g, W1, b1, Wc, bc, Wr, br, A, G, hidden); break;
+  case 96: hipLaunchKernelGGL(k_rpn_head_grouped_fwd<96>, grid, block, 0, st, g, W1, b1, Wc, bc, Wr, br, A, G, hidden); break;
+  default: hipLaunchKernelGGL(k_rpn_head_grouped_fwd<128>, grid, block, 0, st, g, W1, b1, Wc, bc, Wr, br, A, G, hidden); break;
+  }
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+template <int C>
+static int rpn_head_grouped_bwd_launch(const RpnMaps &g, const float *W1, const float *Wc, const float *Wr, int A, int G,
+                                       const float *hidden, int64_t tiles, int groups, float *scratch, hipStream_t st) {
+  static DynLdsOnce attr;               // once, for the widest D: the launch asks for what its A G needs
+  AABR_CHECK_HIP(dyn_lds_once(attr, (const void *)(k_rpn_head_grouped_bwd<C>), (int)rpn_grouped_bwd_lds_bytes(C, kRpnMaxN2)));
+  hipLaunchKernelGGL(k_rpn_head_grouped_bwd<C>, dim3((unsigned)groups), dim3(256),
+                     rpn_grouped_bwd_lds_bytes(C, rpn_group_np(A, G)), st, g, W1, Wc, Wr, A, G, hidden, (uint32_t)tiles,
+                     scratch);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+extern "C" int aabr_rpn_head_grouped_backward(const AabrRpnMap *maps_host, int n_maps, int C, int A, int G, const float *W1,
+                                              const float *Wc, const float *Wr, const float *hidden, float *dW1,
+                                              float *db1, float *dWc, float *dbc, float *dWr, float *dbr, float *scratch,
+                                              void *stream_) {
+  AABR_RPN_CHECK_GROUPS(A, G);
+  RpnMaps g;
+  int64_t tiles = 0;
+  int rc = rpn_head_table(maps_host, n_maps, C, A, true, g, &tiles);
+  if (rc != AABR_OK) return rc;
+  AABR_CHECK_ARG(W1 && Wc && Wr, "null pointer");
+  AABR_CHECK_ARG(dW1 && db1 && dWc && dbc && dWr && dbr, "null gradient pointer");
+  hipStream_t st = (hipStream_t)stream_;
+  const int AG = A * G;
+  if (tiles == 0) {                                   // empty sums: zeros, no kernel
+    AABR_CHECK_HIP(hipMemsetAsync(dW1, 0, sizeof(float) * C * C, st));
+    AABR_CHECK_HIP(hipMemsetAsync(db1, 0, sizeof(float) * C, st));
+    AABR_CHECK_HIP(hipMemsetAsync(dWc, 0, sizeof(float) * AG * C, st));
+    AABR_CHECK_HIP(hipMemsetAsync(dbc, 0, sizeof(float) * AG, st));
+    AABR_CHECK_HIP(hipMemsetAsync(dWr, 0, sizeof(float) * 7 * AG * C, st));
+    AABR_CHECK_HIP(hipMemsetAsync(dbr, 0, sizeof(float) * 7 * AG, st));
+    return AABR_OK;
+  }
+  AABR_CHECK_ARG(hidden, "null hidden");
+  AABR_CHECK_ARG(scratch, "null scratch");
+  const int groups = aabr_rpn_head_groups(tiles);
+  switch (C) {
+  case 32: rc = rpn_head_grouped_bwd_launch<32>(g, W1, Wc, Wr, A, G, hidden, tiles, groups, scratch, st); break;
+  case 64: rc = rpn_head_grouped_bwd_launch<64>(g, W1, Wc, Wr, A, G, hidden, tiles, groups, scratch, st); break;
+  case 96: rc = rpn_head_grouped_bwd_launch<96>(g, W1, Wc, Wr, A, G, hidden, tiles, groups, scratch, st); break;
+  default: rc = rpn_head_grouped_bwd_launch<128>(g, W1, Wc, Wr, A, G, hidden, tiles, groups, scratch, st); break;
+  }
+  if (rc != AABR_OK) return rc;
+  const int np = rpn_group_np(A, G);
+  const int64_t per = rpn_partial_floats(C, np);
+  hipLaunchKernelGGL(k_rpn_head_reduce, dim3((unsigned)ceil_div(per, 256)), dim3(256), 0, st, scratch, groups, C, AG, np,
+                     dW1, db1, dWc, dbc, dWr, dbr);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }

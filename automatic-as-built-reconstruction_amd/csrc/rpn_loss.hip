@@ -21,6 +21,12 @@
 //      the selected list and the per-example sums of the loss terms of those <= B anchors;
 // then K5 adds the per-example sums in example order and divides by N_s.  No float atomics: bit-identical run to run.
 // K1 .. K4 and the loss terms live in sample_shared.h: the box head (roi_loss.hip) samples with the same code.
+//
+// Separated-classifier groups (aabr_rpn_loss_grouped_*): segment e = scene * G + group is an example of the same
+// kernels.  Its anchor tables are its scene's, its head values sit group * V_m * A behind the plain index in the
+// group-major allocations of the grouped RPN head (LossParams::G, group[], rows[]), its labels and targets are its own,
+// and the key hashes the scene: a group's selection, sums and gradients are the plain call's on that group.  The
+// finalize adds each group's sums in scene order; the losses and the upstream gradients are [G].
 #include "common.h"
 #include "sample_shared.h"
 
@@ -44,6 +50,24 @@ __global__ __launch_bounds__(64) void k_loss_finalize(int nb, const float *__res
   for (int e = 0; e < nb; ++e) info[e * kInfoWords + 7] = ns;
 }
 
+// with groups: thread g adds the sums of group g's segments (scene * G + g) in scene order, / the group's N_s
+__global__ __launch_bounds__(64) void k_loss_finalize_grouped(int nb, int G, const float *__restrict__ partial,
+                                                              int32_t *__restrict__ info, float *__restrict__ obj_loss,
+                                                              float *__restrict__ box_loss) {
+  const int g = threadIdx.x;
+  if (g >= G) return;
+  float bce = 0.f, box = 0.f;
+  int ns = 0;
+  for (int e = g; e < nb * G; e += G) {
+    bce += partial[2 * e];
+    box += partial[2 * e + 1];
+    ns += info[e * kInfoWords] + info[e * kInfoWords + 1];
+  }
+  obj_loss[g] = bce / (float)ns;
+  box_loss[g] = box / (float)ns;
+  for (int e = g; e < nb * G; e += G) info[e * kInfoWords + 7] = ns;
+}
+
 // the select of every chunk, then (with the loss) the finalize: 1 memset + 4 launches per chunk + 1
 int run_select(LossParams &p, const char *fn, int nb, const int32_t *seg_begin_host, const int32_t *site_begin_host,
                const void *const *label_ptrs, const void *const *target_ptrs, void *const *pos_masks,
@@ -52,12 +76,17 @@ int run_select(LossParams &p, const char *fn, int nb, const int32_t *seg_begin_h
   int rc = run_select_chunks(p, fn, nb, seg_begin_host, site_begin_host, label_ptrs, target_ptrs, pos_masks, neg_masks, selected,
                              info, scratch, st);
   if (rc != AABR_OK) return rc;
-  if (p.with_loss)
+  if (p.with_loss && p.G)
+    hipLaunchKernelGGL(k_loss_finalize_grouped, dim3(1), dim3(64), 0, st, nb / p.G, p.G, select_partials(scratch, nb), info,
+                       obj_loss, box_loss);
+  else if (p.with_loss)
     hipLaunchKernelGGL(k_loss_finalize, dim3(1), dim3(64), 0, st, nb, select_partials(scratch, nb), info, obj_loss,
                        box_loss);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }
+
+constexpr int kLossMaxGroups = 16;
 
 struct GradPtrs {
   void *obj[kAnchorMaxMaps];
@@ -76,13 +105,13 @@ __global__ __launch_bounds__(256) void k_loss_backward(LossParams p, const int64
   if (s_i < 0) return;
   const int64_t j = s_i - p.out_begin[b];
   const AnchorLoc L = locate(p, b, j);
-  const int64_t oi = L.row * p.s.A + L.a;
+  const int64_t oi = head_index(p, b, L);
   const float x = ld(p.obj[L.m], oi, p.bf16);
   const float y = i < kp ? 1.f : 0.f;
-  const float go = *g_obj / (float)ns;
+  const float go = g_obj[p.group[b]] / (float)ns;
   st(grads.obj[L.m], oi, (1.f / (1.f + expf(-x)) - y) * go, p.bf16);
   if (i < kp) {
-    const float gb = *g_box / (float)ns;
+    const float gb = g_box[p.group[b]] / (float)ns;
     for (int d = 0; d < 7; ++d) {
       const float diff = ld(p.reg[L.m], oi * 7 + d, p.bf16) - p.targets[b][j * 7 + d];
       st(grads.reg[L.m], oi * 7 + d, smooth_l1_grad(diff, p.beta) * gb, p.bf16);
@@ -120,6 +149,60 @@ __global__ __launch_bounds__(256) void k_smooth_l1_backward(const void *__restri
   const float gs = *g / divisor;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
     st(grad, i, smooth_l1_grad(ld(input, i, bf16) - target[i], beta) * gs, bf16);
+}
+
+// the gradient launch of every chunk: 1 per chunk of 16 examples
+int run_backward(LossParams &p, const GradPtrs &g, const char *fn, int nb, const int32_t *seg_begin_host,
+                 const int32_t *site_begin_host, const void *const *target_ptrs, const int64_t *selected,
+                 const int32_t *info, const float *grad_obj_loss, const float *grad_box_loss, hipStream_t st) {
+  const int n_maps = p.s.n_maps;
+  std::vector<int64_t> out_begin(nb);
+  int64_t total = 0;
+  for (int b = 0; b < nb; ++b)
+    out_begin[b] = select_out_begin(p.G, b, seg_begin_host[b * (n_maps + 1) + n_maps], total);
+  for (int b0 = 0; b0 < nb; b0 += kAnchorMaxBatch) {
+    const int nbc = nb - b0 < kAnchorMaxBatch ? nb - b0 : kAnchorMaxBatch;
+    int64_t nmax = 0;
+    int rc = fill_chunk(p, fn, b0, nbc, seg_begin_host, site_begin_host, nullptr, target_ptrs, out_begin.data(), nullptr,
+                        nullptr, false, nmax);
+    if (rc != AABR_OK) return rc;
+    for (int m = 0; m < n_maps; ++m)
+      for (int b = 0; b < nbc; ++b)
+        AABR_CHECK_ARG_AS(fn, p.s.seg[b][m + 1] == p.s.seg[b][m] || (g.obj[m] && g.reg[m]), "null gradient pointer");
+    hipLaunchKernelGGL(k_loss_backward, dim3((unsigned)ceil_div(p.B, 256), (unsigned)nbc), dim3(256), 0, st, p, selected,
+                       info, grad_obj_loss, grad_box_loss, g);
+  }
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+// a scene's rows of the two host tables repeated for its G segments; checks the groups' arguments
+int expand_group_tables(const char *fn, int n_maps, int nb, int G, const int32_t *seg_begin_host,
+                        const int32_t *site_begin_host, const int64_t *rows_host, LossParams &p, std::vector<int32_t> &seg,
+                        std::vector<int32_t> &site) {
+  AABR_CHECK_ARG_AS(fn, n_maps >= 1 && n_maps <= kAnchorMaxMaps && nb >= 1, "bad arguments (1 .. 8 maps, >= 1 scene)");
+  AABR_CHECK_ARG_AS(fn, G >= 2 && G <= kLossMaxGroups, "groups: 2 <= G <= 16");
+  AABR_CHECK_ARG_AS(fn, (int64_t)nb * G < ((int64_t)1 << 24), "too many segments");
+  AABR_CHECK_ARG_AS(fn, seg_begin_host && site_begin_host && rows_host, "null pointer");
+  p.G = G;
+  for (int m = 0; m < n_maps; ++m) {
+    AABR_CHECK_ARG_AS(fn, rows_host[m] >= 0, "negative row count");
+    p.rows[m] = rows_host[m];
+  }
+  seg.resize((size_t)nb * G * (n_maps + 1));
+  site.resize((size_t)nb * G * n_maps);
+  for (int b = 0; b < nb; ++b)
+    for (int g = 0; g < G; ++g) {
+      const size_t e = (size_t)b * G + g;
+      for (int m = 0; m <= n_maps; ++m) seg[e * (n_maps + 1) + m] = seg_begin_host[(size_t)b * (n_maps + 1) + m];
+      for (int m = 0; m < n_maps; ++m) {
+        site[e * n_maps + m] = site_begin_host[(size_t)b * n_maps + m];
+        const int64_t sites = (seg[e * (n_maps + 1) + m + 1] - seg[e * (n_maps + 1) + m]) / (p.s.A > 0 ? p.s.A : 1);
+        AABR_CHECK_ARG_AS(fn, site[e * n_maps + m] >= 0 && site[e * n_maps + m] + sites <= rows_host[m],
+                         "a scene's sites reach past the map's rows");
+      }
+    }
+  return AABR_OK;
 }
 
 }  // namespace
@@ -177,26 +260,68 @@ extern "C" int aabr_rpn_loss_backward(int n_maps, const void *const *obj_ptrs, c
     g.obj[m] = grad_obj_ptrs[m];
     g.reg[m] = grad_reg_ptrs[m];
   }
-  std::vector<int64_t> out_begin(nb);
-  int64_t total = 0;
-  for (int b = 0; b < nb; ++b) {
-    out_begin[b] = total;
-    total += seg_begin_host[b * (n_maps + 1) + n_maps];
+  return run_backward(p, g, __func__, nb, seg_begin_host, site_begin_host, target_ptrs, selected, info, grad_obj_loss,
+                      grad_box_loss, st);
+}
+
+extern "C" int64_t aabr_rpn_loss_grouped_scratch_words(int nb, int G) {
+  return nb > 0 && G >= 2 && G <= kLossMaxGroups ? aabr_rpn_loss_scratch_words(nb * G) : 0;
+}
+
+extern "C" int aabr_rpn_loss_grouped_forward(int n_maps, const void *const *coords_ptrs, const void *const *obj_ptrs,
+                                             const void *const *reg_ptrs, const int64_t *rows_host, int input_bf16,
+                                             int num_anchors, int nb, int G, const int32_t *seg_begin_host,
+                                             const int32_t *site_begin_host, const void *const *label_ptrs,
+                                             const void *const *target_ptrs, uint32_t seed, int batch_size_per_image,
+                                             int num_pos_max, float beta, int64_t *selected, int32_t *info,
+                                             float *obj_loss, float *box_loss, int32_t *scratch, void *stream_) {
+  AABR_CHECK_ARG(num_anchors > 0, "bad arguments (at least one anchor per site)");
+  AABR_CHECK_ARG(batch_size_per_image >= 1 && batch_size_per_image <= kLossMaxB && num_pos_max >= 0 &&
+                     num_pos_max <= batch_size_per_image && beta > 0.f,
+                 "need 1 <= batch_size_per_image <= 512, 0 <= num_pos_max <= batch_size_per_image, beta > 0");
+  AABR_CHECK_ARG(coords_ptrs && obj_ptrs && reg_ptrs && label_ptrs && target_ptrs && selected && info && obj_loss &&
+                     box_loss && scratch, "null pointer");
+  LossParams p = {};
+  p.s.n_maps = n_maps; p.s.A = num_anchors; p.flat = 0; p.with_loss = 1; p.label_mode = 0; p.bf16 = input_bf16 ? 1 : 0;
+  p.k_pos0 = num_pos_max; p.B = batch_size_per_image; p.seed = seed; p.beta = beta;
+  std::vector<int32_t> seg, site;
+  const int rc = expand_group_tables(__func__, n_maps, nb, G, seg_begin_host, site_begin_host, rows_host, p, seg, site);
+  if (rc != AABR_OK) return rc;
+  for (int m = 0; m < n_maps; ++m) {
+    p.obj[m] = obj_ptrs[m];
+    p.reg[m] = reg_ptrs[m];
+    p.coords[m] = (const int32_t *)coords_ptrs[m];
   }
-  for (int b0 = 0; b0 < nb; b0 += kAnchorMaxBatch) {
-    const int nbc = nb - b0 < kAnchorMaxBatch ? nb - b0 : kAnchorMaxBatch;
-    int64_t nmax = 0;
-    int rc = fill_chunk(p, __func__, b0, nbc, seg_begin_host, site_begin_host, nullptr, target_ptrs, out_begin.data(), nullptr,
-                        nullptr, false, nmax);
-    if (rc != AABR_OK) return rc;
-    for (int m = 0; m < n_maps; ++m)
-      for (int b = 0; b < nbc; ++b)
-        AABR_CHECK_ARG(p.s.seg[b][m + 1] == p.s.seg[b][m] || (g.obj[m] && g.reg[m]), "null gradient pointer");
-    hipLaunchKernelGGL(k_loss_backward, dim3((unsigned)ceil_div(batch_size_per_image, 256), (unsigned)nbc), dim3(256), 0, st,
-                       p, selected, info, grad_obj_loss, grad_box_loss, g);
+  return run_select(p, __func__, nb * G, seg.data(), site.data(), label_ptrs, target_ptrs, nullptr, nullptr, selected, info,
+                    obj_loss, box_loss, scratch, (hipStream_t)stream_);
+}
+
+extern "C" int aabr_rpn_loss_grouped_backward(int n_maps, const void *const *obj_ptrs, const void *const *reg_ptrs,
+                                              const int64_t *rows_host, int input_bf16, int num_anchors, int nb, int G,
+                                              const int32_t *seg_begin_host, const int32_t *site_begin_host,
+                                              const void *const *target_ptrs, int batch_size_per_image, float beta,
+                                              const int64_t *selected, const int32_t *info, const float *grad_obj_loss,
+                                              const float *grad_box_loss, void *const *grad_obj_ptrs,
+                                              void *const *grad_reg_ptrs, void *stream_) {
+  AABR_CHECK_ARG(num_anchors > 0 && batch_size_per_image >= 1 && batch_size_per_image <= kLossMaxB && beta > 0.f,
+                 "bad arguments");
+  AABR_CHECK_ARG(obj_ptrs && reg_ptrs && target_ptrs && selected && info && grad_obj_loss && grad_box_loss &&
+                     grad_obj_ptrs && grad_reg_ptrs, "null pointer");
+  LossParams p = {};
+  p.s.n_maps = n_maps; p.s.A = num_anchors; p.with_loss = 1; p.bf16 = input_bf16 ? 1 : 0; p.B = batch_size_per_image;
+  p.beta = beta;
+  std::vector<int32_t> seg, site;
+  const int rc = expand_group_tables(__func__, n_maps, nb, G, seg_begin_host, site_begin_host, rows_host, p, seg, site);
+  if (rc != AABR_OK) return rc;
+  GradPtrs g = {};
+  for (int m = 0; m < n_maps; ++m) {
+    p.obj[m] = obj_ptrs[m];
+    p.reg[m] = reg_ptrs[m];
+    g.obj[m] = grad_obj_ptrs[m];
+    g.reg[m] = grad_reg_ptrs[m];
   }
-  AABR_CHECK_LAUNCH();
-  return AABR_OK;
+  return run_backward(p, g, __func__, nb * G, seg.data(), site.data(), target_ptrs, selected, info, grad_obj_loss,
+                      grad_box_loss, (hipStream_t)stream_);
 }
 
 extern "C" int aabr_sample_list(int nb, const void *const *label_ptrs, const int64_t *n_host, uint32_t seed,

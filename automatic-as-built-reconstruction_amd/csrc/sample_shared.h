@@ -37,6 +37,11 @@ struct LossParams {
   int64_t out_begin[kAnchorMaxBatch];
   uint8_t *pos_mask[kAnchorMaxBatch];
   uint8_t *neg_mask[kAnchorMaxBatch];
+  // separated-classifier groups (aabr_rpn_loss_grouped_*; G = 0: none).  Example e = scene * G + group is a SEGMENT: its
+  // tables are its scene's, its head values sit group[b] * rows[m] * A behind the plain index in map m's group-major
+  // allocation, and the sampler's key hashes the scene, so a segment selects what the plain call selects for its scene
+  int32_t G, group[kAnchorMaxBatch];
+  int64_t rows[kAnchorMaxMaps];
 };
 // the largest set beside it: k_loss_backward (rpn_loss.hip), 4 pointers and GradPtrs, 2 x 8 pointers
 static_assert(sizeof(LossParams) + (4 + 2 * kAnchorMaxMaps) * 8 <= kKernelArgBytes, "k_loss_*: the struct and 20 pointers");
@@ -61,7 +66,7 @@ __device__ inline AnchorLoc locate(const LossParams &p, int b, int64_t j) {
 }
 __device__ inline uint32_t key_of(const LossParams &p, int b, int64_t j, const AnchorLoc &L) {
   uint32_t h = fmix32(p.seed ^ 0x9E3779B9u);
-  h = fmix32(h ^ (uint32_t)(p.example0 + b));
+  h = fmix32(h ^ (uint32_t)(p.G ? (p.example0 + b) / p.G : p.example0 + b));
   if (p.flat) return fmix32(h ^ (uint32_t)j);
   const int32_t *c = p.coords[L.m] + L.row * 4;
   h = fmix32(h ^ (uint32_t)L.m);
@@ -83,6 +88,11 @@ __device__ inline bool cand_less(const LossParams &p, int b, unsigned long long 
   return lx.a < ly.a;
 }
 
+// index of anchor L of example b in map L.m's objectness vector (times 7: its regression row)
+__device__ inline int64_t head_index(const LossParams &p, int b, const AnchorLoc &L) {
+  const int64_t oi = L.row * p.s.A + L.a;
+  return p.G ? oi + p.group[b] * p.rows[L.m] * p.s.A : oi;
+}
 __device__ inline float ld(const void *base, int64_t i, int bf16) {
   return bf16 ? (float)reinterpret_cast<const __bf16 *>(base)[i] : reinterpret_cast<const float *>(base)[i];
 }
@@ -261,7 +271,7 @@ __global__ __launch_bounds__(256) void k_loss_select(LossParams p, int32_t *__re
       if (mask) mask[j] = 1;
       if (loss) {
         const AnchorLoc L = locate(p, b, j);
-        const int64_t oi = L.row * p.s.A + L.a;
+        const int64_t oi = head_index(p, b, L);
         bce += bce_term(ld(p.obj[L.m], oi, p.bf16), c == 0 ? 1.f : 0.f);
         if (c == 0)
           for (int d = 0; d < 7; ++d)
@@ -299,6 +309,7 @@ int fill_chunk(LossParams &p, const char *fn, int b0, int nbc, const int32_t *se
     p.out_begin[b] = on ? out_begin[g] : 0;
     p.pos_mask[b] = on && pos_masks ? (uint8_t *)pos_masks[g] : nullptr;
     p.neg_mask[b] = on && neg_masks ? (uint8_t *)neg_masks[g] : nullptr;
+    p.group[b] = on && p.G ? g % p.G : 0;
     if (!on) continue;
     const int64_t n = p.s.seg[b][p.s.n_maps];
     AABR_CHECK_ARG_AS(fn, n == 0 || !need_labels || p.labels[b], "null label list");
@@ -308,6 +319,15 @@ int fill_chunk(LossParams &p, const char *fn, int b0, int nbc, const int32_t *se
                                ((p.coords[m] || !need_labels) && p.obj[m] && p.reg[m]), "null map pointer");
   }
   return AABR_OK;
+}
+
+// where example b's list (length n) begins in the concatenation the selected indices refer to; `total` runs over the
+// examples in order.  With groups the concatenation is the GROUP's own, scene-major (what a plain call on that group's
+// labels sees): the segments of a scene share its list length and begin at the same index.
+inline int64_t select_out_begin(int G, int b, int64_t n, int64_t &total) {
+  const int64_t begin = total;
+  if (G == 0 || (b + 1) % G == 0) total += n;
+  return begin;
 }
 
 // the per-example loss sums of k_loss_select (float [nb][2]) behind the sampler's words
@@ -323,10 +343,9 @@ int run_select_chunks(LossParams &p, const char *fn, int nb, const int32_t *seg_
   std::vector<int64_t> out_begin(nb);
   int64_t total = 0;
   for (int b = 0; b < nb; ++b) {
-    out_begin[b] = total;
     const int64_t n = seg_begin_host[b * (p.s.n_maps + 1) + p.s.n_maps];
     AABR_CHECK_ARG_AS(fn, n >= 0, "negative list length");
-    total += n;
+    out_begin[b] = select_out_begin(p.G, b, n, total);
   }
   AABR_CHECK_ARG_AS(fn, total < ((int64_t)1 << 31), "more than 2^31 - 1 entries per call");
   p.nb_total = nb;

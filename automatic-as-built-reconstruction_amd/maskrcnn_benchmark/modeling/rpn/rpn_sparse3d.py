@@ -2,14 +2,19 @@
 :81-131, RPNModule :134-303) composed from the device paths of rpn_glue: rpn_head (csrc/rpn_head.hip: one launch per
 forward for all maps, two per backward), rpn_proposals, rpn_label_matches and rpn_loss.  Containers are duck-typed: a
 scene's proposals are a DetectionList3D (`.bbox3d` [n, 7] yx_zb, `.size3d`, field `objectness`), which ROIBoxHead3D
-consumes; targets are objects with `.bbox3d` or plain [G, 7] tensors.  Not part of this package: the separated-classifier
-RPN groups (SEPARATE_RPN with SEPARATE_CLASSES) and the SHOW_* debug paths."""
+consumes; targets are objects with `.bbox3d` or plain [G, 7] tensors.  With MODEL.SEPARATE_CLASSES and SEPARATE_RPN (and
+SEPARATE_CLASSES_ID, the class ids of each entry) the head has G = len(SEPARATE_CLASSES) + 1 branches (rpn_head_grouped,
+the reference's parameter shapes) and RPNModule runs every stage per group as single grouped calls through its
+SeperateClassifier: `boxes` is then a list over groups of lists over scenes, the losses are `loss_objectness_{g}` /
+`loss_rpn_box_reg_{g}`, and the targets must carry the field `labels`.  Not part of this package: the SHOW_* debug
+paths."""
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 import rpn_glue
 from maskrcnn_benchmark.modeling.roi_heads.box_head_3d.inference import DetectionList3D
+from maskrcnn_benchmark.modeling.seperate_classifier import SeperateClassifier
 from .anchor_generator_sparse3d import make_anchor_generator
 
 
@@ -37,19 +42,31 @@ class RPNHead(nn.Module):
         super(RPNHead, self).__init__()
         self.num_anchors_per_location = num_anchors_per_location
         self.seperate_rpn = int(len(cfg.MODEL.SEPARATE_CLASSES) * cfg.MODEL.SEPARATE_RPN) + 1
-        if self.seperate_rpn != 1:
-            raise ValueError("cfg.MODEL.SEPARATE_RPN with SEPARATE_CLASSES: the separated RPN groups are not part of this "
-                             "package")
+        G = self.seperate_rpn
+        if G != 1:
+            group_class_ids(cfg)
+            if not rpn_glue.rpn_head_group_limits_ok(in_channels, num_anchors_per_location, G):
+                raise ValueError("RPNHead with separated RPN groups: C = %d, A = %d, G = %d; supported: %s"
+                                 % (in_channels, num_anchors_per_location, G, rpn_glue.RPN_HEAD_GROUP_LIMITS))
         self.conv = nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
-        self.cls_logits = nn.Conv2d(in_channels, num_anchors_per_location, kernel_size=1, stride=1)
-        self.bbox_pred = nn.Conv2d(in_channels, num_anchors_per_location * 7, kernel_size=1, stride=1)
+        self.cls_logits = nn.Conv2d(in_channels, num_anchors_per_location * G, kernel_size=1, stride=1)
+        self.bbox_pred = nn.Conv2d(in_channels, num_anchors_per_location * 7 * G, kernel_size=1, stride=1)
         for l in (self.conv, self.cls_logits, self.bbox_pred):
             torch.nn.init.normal_(l.weight, std=0.01)
             torch.nn.init.constant_(l.bias, 0)
 
     def forward_flat(self, x):
-        """(objectness[m] [n A], box_regression[m] [n A, 7]): the [site, yaw] order the rpn_glue consumers read"""
+        """(objectness[m] [n A], box_regression[m] [n A, 7]): the [site, yaw] order the rpn_glue consumers read.  With G > 1
+        groups: [G, n A] and [G, n A, 7], group-major, each group's slice in that order"""
         rows = [_rows(f) for f in x]
+        A, G = self.num_anchors_per_location, self.seperate_rpn
+        if G != 1:
+            if self.fused:
+                return rpn_glue.rpn_head_grouped(rows, self.conv.weight, self.conv.bias, self.cls_logits.weight,
+                                                 self.cls_logits.bias, self.bbox_pred.weight, self.bbox_pred.bias, G)
+            logits, bbox = self._forward_reference(rows)
+            return ([l.reshape(-1, A, G).permute(2, 0, 1).reshape(G, -1) for l in logits],
+                    [b.reshape(-1, A, G, 7).permute(2, 0, 1, 3).reshape(G, -1, 7) for b in bbox])
         if self.fused:
             return rpn_glue.rpn_head(rows, self.conv.weight, self.conv.bias, self.cls_logits.weight, self.cls_logits.bias,
                                      self.bbox_pred.weight, self.bbox_pred.bias)
@@ -65,12 +82,48 @@ class RPNHead(nn.Module):
             reg.append(self.bbox_pred(t).permute(0, 2, 1, 3).reshape(-1, 7))    # [1, n, 7 A, 1] -> (site, yaw) rows
         return obj, reg
 
+    def _forward_reference(self, rows):
+        """the reference's forward with groups (rpn_sparse3d.py:114-131) on torch's layers: (logits[m] [1, n, A, G],
+        bbox_reg[m] [1, n, A, 7 G])"""
+        A, G = self.num_anchors_per_location, self.seperate_rpn
+        logits, bbox = [], []
+        for f in rows:
+            if f.shape[0] == 0:         # torch's convolution refuses an empty map
+                t = F.relu(F.linear(f, self.conv.weight.flatten(1), self.conv.bias))
+                logits.append(F.linear(t, self.cls_logits.weight.flatten(1), self.cls_logits.bias).reshape(1, 0, A, G))
+                bbox.append(F.linear(t, self.bbox_pred.weight.flatten(1), self.bbox_pred.bias).reshape(1, 0, A, 7 * G))
+                continue
+            t = F.relu(self.conv(f.t().unsqueeze(0).unsqueeze(3)))
+            lo = self.cls_logits(t).permute(0, 2, 1, 3)
+            logits.append(lo.reshape(1, lo.shape[1], A, G))
+            rg = self.bbox_pred(t).permute(0, 2, 1, 3)
+            bbox.append(rg.reshape(1, rg.shape[1], A, 7 * G))
+        return logits, bbox
+
     def forward(self, x):
         """x: a list over maps of [1, C, n, 1] tensors (the reference), [n, C] rows or SparseConvNetTensors (no
-        transpose).  Returns (logits[m] [1, n, A, 1], bbox_reg[m] [1, n, A, 7])"""
+        transpose).  Returns (logits[m] [1, n, A, 1], bbox_reg[m] [1, n, A, 7]); with G > 1 groups the reference's
+        [1, n, A, G] and [1, n, A, 7 G] (fused: a permuted view of the group-major result)"""
+        A, G = self.num_anchors_per_location, self.seperate_rpn
+        if G != 1:
+            if not self.fused:
+                return self._forward_reference([_rows(f) for f in x])
+            obj, reg = self.forward_flat(x)
+            return ([o.view(G, -1, A).permute(1, 2, 0).unsqueeze(0) for o in obj],
+                    [r.view(G, -1, A, 7).permute(1, 2, 0, 3).reshape(1, -1, A, 7 * G) for r in reg])
         obj, reg = self.forward_flat(x)
-        A = self.num_anchors_per_location
         return [o.view(1, o.numel() // A, A, 1) for o in obj], [r.view(1, r.shape[0] // A, A, 7) for r in reg]
+
+
+def group_class_ids(cfg):
+    """cfg.MODEL.SEPARATE_CLASSES_ID of a configuration with separated RPN groups: one list of class ids per entry of
+    SEPARATE_CLASSES"""
+    names = cfg.MODEL.SEPARATE_CLASSES
+    ids = getattr(cfg.MODEL, "SEPARATE_CLASSES_ID", None)
+    if ids is None or len(ids) != len(names):
+        raise ValueError("cfg.MODEL.SEPARATE_RPN with SEPARATE_CLASSES %r needs cfg.MODEL.SEPARATE_CLASSES_ID, one list of "
+                         "class ids per entry, got %r" % (list(names), ids))
+    return [list(g) for g in ids]
 
 
 def _boxes_of(t):
@@ -81,7 +134,7 @@ class RPNModule(torch.nn.Module):
     """head -> proposals (and, in training, labels -> losses), all on the device.  forward returns (boxes, losses):
     boxes = one DetectionList3D per scene with the field `objectness` (None in training with RPN__ONLY: the reference
     returns its undecoded anchors there, which this path never materialises); losses = {"loss_objectness",
-    "loss_rpn_box_reg"} in training, {} in evaluation."""
+    "loss_rpn_box_reg"} in training, {} in evaluation.  With separated-classifier groups: see _forward_grouped."""
 
     def __init__(self, cfg):
         super(RPNModule, self).__init__()
@@ -90,6 +143,10 @@ class RPNModule(torch.nn.Module):
         if rpn.RPN_HEAD != "SingleConvRPNHead_Sparse3D":
             raise ValueError("cfg.MODEL.RPN.RPN_HEAD %r: only SingleConvRPNHead_Sparse3D is part of this package" % (rpn.RPN_HEAD,))
         self.anchor_generator = make_anchor_generator(cfg)
+        G = int(len(cfg.MODEL.SEPARATE_CLASSES) * cfg.MODEL.SEPARATE_RPN) + 1
+        ids = group_class_ids(cfg) if G != 1 else []
+        self.seperate_classifier = SeperateClassifier(ids, len(cfg.INPUT.CLASSES) if G != 1 else 0,
+                                                      getattr(cfg.MODEL, "CLASS_SPECIFIC", False), "RPN")
         self.head = RPNHead(cfg, cfg.SPARSE3D.nPlaneMap, self.anchor_generator.num_anchors_per_location())
         self.add_gt_proposals = rpn.ADD_GT_PROPOSALS
         self.rpn_only = cfg.MODEL.RPN__ONLY
@@ -107,8 +164,34 @@ class RPNModule(torch.nn.Module):
                                           gen.strides, gen.voxel_scale, pre, post, rpn.NMS_THRESH,
                                           tuple(rpn.NMS_AUG_THICKNESS_Y_Z), batch_size=nb)
 
+    def _forward_grouped(self, maps, targets):
+        """forward with separated-classifier groups: `boxes` is a list over groups of lists over scenes (what
+        SeperateClassifier.cat_boxlist_3d_seperated accepts), the losses are keyed per group"""
+        sc = self.seperate_classifier
+        obj, reg = self.head.forward_flat(maps)
+        nb = len(targets) if targets is not None else None
+        if not self.training:
+            boxes = sc.seperate_rpn_selector(self, maps, obj, reg, None, False, train=False, batch_size=nb)
+            if self.rpn_only:                                   # the final output: high-to-low confidence
+                boxes = [[b[b.get_field("objectness").sort(descending=True)[1]] for b in scenes] for scenes in boxes]
+            return boxes, {}
+        if targets is None:
+            raise ValueError("RPNModule: training needs targets")
+        tg = sc.seperate_rpn_assin(list(targets))
+        boxes = None
+        if not self.rpn_only:
+            boxes = sc.seperate_rpn_selector(self, maps, obj, reg, tg, self.add_gt_proposals, train=True, batch_size=nb)
+        lo, lb = sc.seperate_rpn_loss_evaluator(self, maps, obj, reg, tg)
+        losses = {}
+        for g in range(sc.group_num):
+            losses["loss_objectness_%d" % g] = lo[g]
+            losses["loss_rpn_box_reg_%d" % g] = lb[g]
+        return boxes, losses
+
     def forward(self, inputs_sparse, features_sparse, targets=None):
         maps = list(features_sparse)
+        if self.seperate_classifier.need_seperate:
+            return self._forward_grouped(maps, targets)
         obj, reg = self.head.forward_flat(maps)
         gt = [_boxes_of(t) for t in targets] if targets is not None else None
         nb = len(gt) if gt is not None else None

@@ -16,9 +16,11 @@ group sizes; its rows are then group-major) -- `cat_boxlist_3d_seperated` and `s
 method reads the device.  Without it, `seperate_subsample` and `seperate_proposals` order the batch by one stable sort
 and read the per-group counts of the whole batch in ONE read.  The losses and `post_processor` never need the sizes.
 
-Not part of this change: the RPN half (`seperate_rpn_*`: MODEL.SEPARATE_RPN, G objectness / regression groups per anchor,
-per-group label generation and proposals) raises NotImplementedError, and `group_id_include_wall`, which only the
-corner-connection losses read, is left out."""
+The RPN half (MODEL.SEPARATE_RPN: G objectness / regression groups per anchor) works on the instance RPNModule builds,
+whose flag is 'RPN' -- the reference builds one instance per role: `seperate_targets`, `seperate_rpn_assin`,
+`seperate_rpn_selector` and `seperate_rpn_loss_evaluator` are each ONE grouped call of rpn_glue (rpn_group_targets,
+rpn_proposals_grouped, rpn_label_matches_grouped + rpn_loss_grouped).  On an instance of any other flag they raise
+NotImplementedError.  `group_id_include_wall`, which only the corner-connection losses read, is left out."""
 import torch
 
 import _hip
@@ -69,11 +71,106 @@ class SeperateClassifier(object):
                 self.sep_labels_to_org_labels[g][i] = c
         self._lut = {}
 
-    # ---- the RPN half: a later change ------------------------------------------------------------------------------------
+    # ---- the RPN half: only on the instance RPNModule builds (flag 'RPN'; the reference builds one instance per role) -----
     def _rpn(self, *_a, **_k):
         raise NotImplementedError("the RPN half of the separated classifier (MODEL.SEPARATE_RPN: per-group objectness, "
                                   "label generation and proposals) is a later change; only the box head runs with groups")
-    seperate_rpn_assin = seperate_rpn_selector = seperate_rpn_loss_evaluator = _rpn
+
+    def _rpn_role(fn):
+        def method(self, *a, **k):
+            if getattr(self, "flag", None) != "RPN":
+                self._rpn()
+            return fn(self, *a, **k)
+        method.__name__, method.__doc__ = fn.__name__, fn.__doc__
+        return method
+
+    @_rpn_role
+    def seperate_targets(self, targets):
+        """a batch's ground truth by group, one call (rpn_glue.rpn_group_targets; ONE host read, none when the labels are
+        host tensors): targets = per scene an object with `.bbox3d` [n, 7] and the field `labels` (ORIGINAL ids).
+        Returns (boxes[b][g] [n, 7], local_labels[b][g], rows[b][g], counts[b][g]), each group's boxes in the order
+        (group-local label, row) in which the reference concatenates them; a label no group owns is dropped.  A value
+        this method returned is passed through, so a step splits its targets once."""
+        import rpn_glue
+        if isinstance(targets, tuple) and len(targets) == 4:
+            return targets
+        if any(not (hasattr(t, "bbox3d") and hasattr(t, "get_field")) for t in targets):
+            raise ValueError("the separated RPN groups need targets that carry their classes (`.bbox3d` and the field "
+                             "`labels`); plain box tensors cannot be split by group")
+        return rpn_glue.rpn_group_targets([t.bbox3d for t in targets], [t.get_field("labels") for t in targets], self)
+
+    @_rpn_role
+    def seperate_targets_and_update_labels(self, targets):
+        """-> list over groups of lists over scenes of the group's targets, `labels` GROUP-LOCAL"""
+        from maskrcnn_benchmark.modeling.roi_heads.box_head_3d.inference import DetectionList3D
+        boxes, local, _rows, _counts = self.seperate_targets(targets)
+        size = [getattr(t, "size3d", None) for t in targets] if not isinstance(targets, tuple) else [None] * len(boxes)
+        return [[DetectionList3D(boxes[b][g], size[b], {"labels": local[b][g]}) for b in range(len(boxes))]
+                for g in range(self.group_num)]
+
+    @_rpn_role
+    def seperate_rpn_assin(self, targets):
+        """splits the step's targets once; the value goes to seperate_rpn_selector / seperate_rpn_loss_evaluator"""
+        self.targets_groups = self.seperate_targets(targets)
+        return self.targets_groups
+
+    @_rpn_role
+    def seperate_rpn_selector(self, rpn, maps, objectness, box_regression, targets, add_gt_proposals, train=True,
+                              batch_size=None):
+        """RPNPostProcessor with groups, one stage (rpn_glue.rpn_proposals_grouped; ONE host read): `rpn` = this package's
+        RPNModule, whose anchors and thresholds apply; objectness / box_regression group-major (RPNHead.forward_flat).
+        With `add_gt_proposals` (training) a group gets ITS OWN ground truth with objectness 1.  Returns a list over groups
+        of lists over scenes of DetectionList3D with the field `objectness`: what cat_boxlist_3d_seperated accepts."""
+        import rpn_glue
+        from maskrcnn_benchmark.modeling.roi_heads.box_head_3d.inference import DetectionList3D
+        from maskrcnn_benchmark.modeling.rpn.rpn_sparse3d import RPNModule
+        rpn = _owner(rpn, RPNModule, "rpn")
+        c, gen = rpn.cfg.MODEL.RPN, rpn.anchor_generator
+        pre = c.FPN_PRE_NMS_TOP_N_TRAIN if train else c.FPN_PRE_NMS_TOP_N_TEST
+        post = c.FPN_POST_NMS_TOP_N_TRAIN if train else c.FPN_POST_NMS_TOP_N_TEST
+        tg = self.seperate_targets(targets) if add_gt_proposals and train else None
+        if batch_size is None and tg is not None:
+            batch_size = len(tg[0])
+        with torch.no_grad():
+            props = rpn_glue.rpn_proposals_grouped(maps, [o.detach() for o in objectness],
+                                                   [r.detach() for r in box_regression], self.group_num, gen.cell_anchors,
+                                                   gen.strides, gen.voxel_scale, pre, post, c.NMS_THRESH,
+                                                   tuple(c.NMS_AUG_THICKNESS_Y_Z), batch_size=batch_size)
+            out = []
+            for g, scenes in enumerate(props):
+                row = []
+                for b, (box, score) in enumerate(scenes):
+                    if tg is not None:
+                        gt = tg[0][b][g].to(box.dtype)
+                        box = torch.cat([box, gt])
+                        score = torch.cat([score, torch.ones(gt.shape[0], dtype=score.dtype, device=score.device)])
+                    row.append(DetectionList3D(box, None, {"objectness": score}))
+                out.append(row)
+        return out
+
+    @_rpn_role
+    def seperate_rpn_loss_evaluator(self, rpn, maps, objectness, box_regression, targets):
+        """RPNLossComputation with groups: the labels of every (scene, group) segment in one library call per 16
+        segments (rpn_glue.rpn_label_matches_grouped), both losses of every group in one grouped call
+        (rpn_glue.rpn_loss_grouped).  `rpn` = this package's RPNModule, whose anchors, thresholds and seed apply.
+        Returns (list of G objectness losses, list of G box losses), 0-dim each."""
+        import rpn_glue
+        from maskrcnn_benchmark.modeling.rpn.rpn_sparse3d import RPNModule
+        rpn = _owner(rpn, RPNModule, "rpn")
+        c, gen, G = rpn.cfg.MODEL.RPN, rpn.anchor_generator, self.group_num
+        boxes = self.seperate_targets(targets)[0]
+        nb = len(boxes)
+        flat = [boxes[b][g] for b in range(nb) for g in range(G)]
+        labels = rpn_glue.rpn_label_matches_grouped(maps, gen.cell_anchors, gen.strides, gen.voxel_scale, flat, G,
+                                                    rpn.label_aug, rpn.cfg.MODEL.IOU_CRITERIA, c.FG_IOU_THRESHOLD,
+                                                    c.BG_IOU_THRESHOLD, batch_size=nb, yaw_threshold=c.YAW_THRESHOLD,
+                                                    regression_targets=True)
+        lo, lb = rpn_glue.rpn_loss_grouped(maps, objectness, box_regression, labels, gen.cell_anchors, G,
+                                           c.BATCH_SIZE_PER_IMAGE, c.POSITIVE_FRACTION, rpn.cfg.MODEL.LOSS.YAW_MODE,
+                                           seed=rpn.seed)
+        return list(lo.unbind(0)), list(lb.unbind(0))
+
+    del _rpn_role
 
     # ---- utilities ---------------------------------------------------------------------------------------------------
     def update_labels_to_seperated_id(self, labels_seperated_org):

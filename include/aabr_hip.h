@@ -46,7 +46,8 @@ const char *aabr_last_error(void);
  * form of the box coder (aabr_box_to_2corners, aabr_box_from_2corners, aabr_box_encode_corner, aabr_box_decode_corner,
  * aabr_roi_targets_coder, aabr_roi_post_detections_coder) likewise: six new symbols, the older entry points being the
  * centroid case of the same code; and fc6 over windows of the convolution rows (aabr_roi_mlp_*_window, AabrMlpWindow):
- * three new symbols and one new record. */
+ * three new symbols and one new record.  The RPN with separated-classifier groups (aabr_rpn_head_grouped_*,
+ * aabr_rpn_loss_grouped_*): six new symbols; the plain entry points run the same kernels and give the same bits. */
 #define AABR_ABI_VERSION 640
 int aabr_version(void);
 /* Tuning knobs for experiments and tests (no counterpart in the reference; the defaults are what ships): CONV_WIDE,
@@ -1047,6 +1048,35 @@ int aabr_rpn_loss_backward(int n_maps, const void *const *obj_ptrs, const void *
                            const int64_t *selected, const int32_t *info, const float *grad_obj_loss,
                            const float *grad_box_loss, void *const *grad_obj_ptrs, void *const *grad_reg_ptrs,
                            void *stream);
+/* The loss with separated-classifier groups (the reference's loop over the groups, seperate_classifier.py:68-109, as ONE
+ * call): segment e = b G + g (scene b, group g) is to these calls what an example is to aabr_rpn_loss_forward.
+ *   seg_begin_host / site_begin_host stay per SCENE ([nb][...]), shared by a scene's G segments.
+ *   obj_ptrs[m] / reg_ptrs[m] point at the GROUP-MAJOR allocations aabr_rpn_head_grouped_forward writes ([G][V_m, A] and
+ *   [G][V_m, A, 7]), rows_host[m] = V_m: a head value of segment e sits g V_m A behind the plain index.
+ *   label_ptrs[e] / target_ptrs[e] are per segment (the labels of the scene's anchors against group g's ground truth).
+ *   The key hashes the SCENE index b, not e: one grouped call selects exactly what G plain calls (one per group, over the
+ *   nb scenes) with the same seed select, and gives the same bits.
+ * Outputs: selected [nb G][B], indices into the concatenation of the label lists of the segment's GROUP, scene-major (what
+ *   the plain call on that group returns); info [nb G][8], word 7 = N_s of the segment's group over the batch;
+ *   obj_loss [G], box_loss [G]: each group's sums in scene order / its N_s (NaN for an empty group sample, zero
+ *   gradients).  Any nb G, chunked by 16 segments; 2 <= G <= 16.
+ * Launches: forward 1 memset + 4 per chunk + 1; backward 1 per chunk, upstream gradients grad_obj_loss [G],
+ * grad_box_loss [G], the gradient allocations group-major like the inputs and zeroed by the caller.
+ * scratch: aabr_rpn_loss_grouped_scratch_words(nb, G) int32, 8-byte aligned (0 for an unsupported shape).              */
+int64_t aabr_rpn_loss_grouped_scratch_words(int nb, int G);
+int aabr_rpn_loss_grouped_forward(int n_maps, const void *const *coords_ptrs, const void *const *obj_ptrs,
+                                  const void *const *reg_ptrs, const int64_t *rows_host, int input_bf16, int num_anchors,
+                                  int nb, int G, const int32_t *seg_begin_host, const int32_t *site_begin_host,
+                                  const void *const *label_ptrs, const void *const *target_ptrs, uint32_t seed,
+                                  int batch_size_per_image, int num_pos_max, float beta, int64_t *selected,
+                                  int32_t *info, float *obj_loss, float *box_loss, int32_t *scratch, void *stream);
+int aabr_rpn_loss_grouped_backward(int n_maps, const void *const *obj_ptrs, const void *const *reg_ptrs,
+                                   const int64_t *rows_host, int input_bf16, int num_anchors, int nb, int G,
+                                   const int32_t *seg_begin_host, const int32_t *site_begin_host,
+                                   const void *const *target_ptrs, int batch_size_per_image, float beta,
+                                   const int64_t *selected, const int32_t *info, const float *grad_obj_loss,
+                                   const float *grad_box_loss, void *const *grad_obj_ptrs, void *const *grad_reg_ptrs,
+                                   void *stream);
 /* List form of the sampler (BalancedPositiveNegativeSampler.__call__): label_ptrs[b] int64 [n_host[b]] with >= 1 positive,
  * 0 negative, anything else ignored.  Same kernels and rule with key h = fmix32(seed ^ 0x9E3779B9), h = fmix32(h ^ v) for
  * v in (example, index), ties by index.  selected / info as above (indices into the concatenated lists; info[7] = 0);
@@ -1374,6 +1404,26 @@ int aabr_rpn_head_forward(const AabrRpnMap *maps_host, int n_maps, int C, int A,
 int aabr_rpn_head_backward(const AabrRpnMap *maps_host, int n_maps, int C, int A, const float *W1, const float *Wc,
                            const float *Wr, const float *hidden, float *dW1, float *db1, float *dWc, float *dbc,
                            float *dWr, float *dbr, float *scratch, void *stream);
+/* The head with separated-classifier groups (MODEL.SEPARATE_CLASSES with SEPARATE_RPN, rpn_sparse3d.py:95-131), G =
+ * len(SEPARATE_CLASSES) + 1 RPN branches on one hidden layer.  The weights come in the reference's layout, so its
+ * state_dict loads unchanged: Wc [A G, C] with row a G + g, Wr [7 A G, C] with row a 7 G + 7 g + k; bc [A G], br [7 A G].
+ * The outputs are written GROUP-MAJOR: a record's objectness points at [G][rows, A] and box_regression at
+ * [G][rows, A, 7] (d_obj / d_reg of the backward call likewise), so group g's slice is a contiguous tensor in the plain
+ * [site, yaw] layout above; the permutation is done in the forward write-out and in the backward's load of d_out, no
+ * tensor is permuted or copied.  hidden and d_features as in the plain calls.
+ *   shapes: as above, and 2 <= G <= 8, A G <= 16 (up to 128 output columns, four MFMA tiles); else AABR_EINVAL.
+ * The reduction order over the hidden units is aabr_rpn_head_forward's: `hidden`, and group g's objectness and
+ * box_regression, are bit for bit what aabr_rpn_head_forward gives with rows a G + g of Wc and a 7 G + 7 g + k of Wr.
+ * Launches as in the plain calls: forward 1; backward 2, partials in `scratch`
+ * (fp32 [aabr_rpn_head_grouped_scratch_floats(total_tiles, C, A, G)] = groups * (C C + NP C + C + NP), NP = 8 A G rounded
+ * up to a multiple of 32; 0 for an unsupported shape) added in workgroup order; every map empty: no launch, memsets. */
+int64_t aabr_rpn_head_grouped_scratch_floats(int64_t total_tiles, int C, int A, int G);
+int aabr_rpn_head_grouped_forward(const AabrRpnMap *maps_host, int n_maps, int C, int A, int G, const float *W1,
+                                  const float *b1, const float *Wc, const float *bc, const float *Wr, const float *br,
+                                  float *hidden, void *stream);
+int aabr_rpn_head_grouped_backward(const AabrRpnMap *maps_host, int n_maps, int C, int A, int G, const float *W1,
+                                   const float *Wc, const float *Wr, const float *hidden, float *dW1, float *db1,
+                                   float *dWc, float *dbc, float *dWr, float *dbr, float *scratch, void *stream);
 
 /* ---- the optimizer step (csrc/solver.hip, csrc/solver_segs.h): torch.optim.SGD with momentum and weight decay
  * (dampening 0, no Nesterov form) over all parameters of one flat fp32 buffer in ONE launch.  Per element, fp32, each
