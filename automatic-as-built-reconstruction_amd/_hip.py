@@ -44,6 +44,7 @@ class AabrMlpWindow(C.Structure):
 _lvp = C.POINTER(AabrRoiLevel)
 _mwp = C.POINTER(AabrMlpWindow)
 _rmp = C.POINTER(AabrRpnMap)
+_ppv = C.POINTER(C.c_void_p)      # host array of device pointers (ptrs())
 _SIGS = {
     "aabr_version": (C.c_int, []),
     "aabr_build_flags": (C.c_int, []),
@@ -245,6 +246,11 @@ _SIGS = {
     "aabr_roi_targets_grouped": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i64p, _i64p, _f32p, _i32, _i32, _f32, _f32,
                                            _f32p, _i32, C.c_uint32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp, _vp]),
+    "aabr_corner_loss_tile": (C.c_int, []),
+    "aabr_corner_loss_scratch_words": (C.c_int64, [_i32]),
+    "aabr_corner_tables": (C.c_int, [_vp, _i32, _i64p, _i64p, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aabr_corner_loss_forward": (C.c_int, [_vp, _i64, _i32, _i64p, _i64p, _ppv, _ppv, _ppv, _vp, _vp, _vp, _vp]),
+    "aabr_corner_loss_backward": (C.c_int, [_vp, _i64, _i32, _i64p, _i64p, _ppv, _ppv, _ppv, _vp, _vp, _vp, _vp, _vp]),
     "aabr_roi_box_loss_grouped_scratch_floats": (C.c_int64, []),
     "aabr_roi_box_loss_grouped_forward": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _i32p, _i32p, _vp, _vp, _vp, _f32,
                                                     _vp, _vp, _vp, _vp, _vp, _vp]),

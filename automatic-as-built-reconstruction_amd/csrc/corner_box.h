@@ -84,6 +84,22 @@ AABR_HD void yxzb_to_2corners(const float b[7], float c[7]) {
   c[6] = b[3];
 }
 
+// The two top corners (x0, y0, z1), (x1, y1, z1) of a two-corner box, each moved towards the pair's midpoint by half the
+// thickness (bounding_box_3d.py:270-291, get_2top_corners_offseted), in the fp32 operations of the torch expressions:
+// centroid = (p0 + p1) / 2, offset = centroid - p, offset / |offset| * thickness * 0.5 from left to right, p + offset.
+// o = [corner 0 xyz, corner 1 xyz].  A zero-length box divides by zero and gives the IEEE result.
+AABR_HD void corners_top_offseted(const float c[7], float o[6]) {
+  const float p[2][3] = {{c[0], c[1], c[5]}, {c[2], c[3], c[5]}};
+  float cen[3];
+  for (int d = 0; d < 3; ++d) cen[d] = (p[0][d] + p[1][d]) / 2.0f;
+  for (int k = 0; k < 2; ++k) {
+    float off[3];
+    for (int d = 0; d < 3; ++d) off[d] = cen[d] - p[k][d];
+    const float nrm = sqrtf(off[0] * off[0] + off[1] * off[1] + off[2] * off[2]);
+    for (int d = 0; d < 3; ++d) o[3 * k + d] = p[k][d] + off[d] / nrm * c[6] * 0.5f;
+  }
+}
+
 // One two-corner box back to yx_zb, in the fp32 operations of the torch expressions:
 //   corner_box_to_standard: centroid = (p0 + p1) / 2, length = |p1 - p0|, height = z1 - z0, yaw = angle_with_x(p1 - p0);
 //   angle_with_x against (1, 0): the cross term is the normalised y component and the cosine the normalised x component

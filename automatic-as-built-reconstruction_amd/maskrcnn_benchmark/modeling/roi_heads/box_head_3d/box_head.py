@@ -3,7 +3,9 @@
 predictor, loss evaluator and post-processor in the reference's order.  `proposals` is one duck-typed list per scene
 (`.bbox3d` [n, 7] yx_zb, `.size3d`), or an object whose `seperate_examples()` returns that.  The corner form runs with the
 default loss weights, cfg.MODEL.LOSS.WEIGHTS[4:7] == 0, where the reference drops `corners_semantic` (:121-122); nonzero
-corner-connection loss weights are refused.  With separated-classifier groups (MODEL.SEPARATE_CLASSES /
+corner-connection loss weights need cfg.MODEL.LOSS.CORNER_CONNECTION = True, which passes `corners_semantic` to the loss
+evaluator and adds `geometric_pull_loss`, `semantic_pull_loss`, `semantic_push_loss` to the loss dict (without the key
+they are refused).  With separated-classifier groups (MODEL.SEPARATE_CLASSES /
 SEPARATE_CLASSES_ID, class-agnostic regression) the proposals carry `sep_id`, the loss evaluator and the post-processor go
 through the SeperateClassifier (modeling/seperate_classifier.py) and the losses come out per group, as
 `loss_classifier_roi_{g}` / `loss_box_reg_roi_{g}` (:149-157).  Not part of this package: cfg.DEBUG.eval_in_train (its rm_gt_from_proposals_ reads an `is_gt` field the sampled lists here do not carry)."""
@@ -21,7 +23,7 @@ class ROIBoxHead3D(torch.nn.Module):
 
     def __init__(self, cfg):
         super(ROIBoxHead3D, self).__init__()
-        roi_glue.corner_roi_check(cfg)       # POOLER_RESOLUTION[1] == 11 and LOSS.WEIGHTS[4:7] == 0
+        roi_glue.corner_roi_check(cfg)       # POOLER_RESOLUTION[1] == 11; LOSS.WEIGHTS[4:7] == 0 or LOSS.CORNER_CONNECTION
         if cfg.DEBUG.eval_in_train > 0:
             raise ValueError("cfg.DEBUG.eval_in_train > 0 is not part of this package")
         self.feature_extractor = make_roi_box_feature_extractor(cfg)
@@ -33,7 +35,8 @@ class ROIBoxHead3D(torch.nn.Module):
         self.add_gt_proposals = cfg.MODEL.RPN.ADD_GT_PROPOSALS
         self.detections_per_img = cfg.MODEL.ROI_HEADS.DETECTIONS_PER_IMG
         self.corner_roi = cfg.MODEL.CORNER_ROI
-        self.no_corner_loss = True           # LOSS.WEIGHTS[4:7] == 0, checked above
+        # box_head.py:57-58: the reference drops corners_semantic when the three weights sum to 0
+        self.no_corner_loss = not (roi_glue.corner_loss_on(cfg) and sum(cfg.MODEL.LOSS.WEIGHTS[4:7]) != 0)
         self.cfg = cfg
 
     def post_processor(self, log_reg, proposals):

@@ -31,13 +31,29 @@ def coder_args(box_coder):
             int(bool(getattr(box_coder, "is_corner_roi", False))))
 
 
+def corner_loss_on(cfg):
+    """MODEL.LOSS.CORNER_CONNECTION: the switch of the corner-connection losses (absent = off)"""
+    return bool(getattr(getattr(cfg.MODEL, "LOSS", None), "CORNER_CONNECTION", False))
+
+
 def corner_roi_check(cfg):
     """What MODEL.CORNER_ROI = True asks of the rest of a config, checked wherever a module of the corner box head is
     made (ValueError otherwise; a config that lacks one of the keys is refused the same way):
       MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION[1] == 11 -- the extractor cuts that axis into the corner windows 0..2 and 8..10
         and the body window 2..8 (roi_box_feature_extractors.py:93-94,122-127);
-      MODEL.LOSS.WEIGHTS[4:7] == 0 -- the corner-connection losses (`corners_semantic`) are not part of this package:
-        with these weights the reference drops corners_semantic (box_head.py:121-122)."""
+      MODEL.LOSS.WEIGHTS[4:7] == 0 -- with these weights the reference drops corners_semantic (box_head.py:121-122) --
+        unless MODEL.LOSS.CORNER_CONNECTION = True switches the corner-connection losses on (`corner_connection_loss`;
+        a reference `*_corsem.yaml` needs that one additional line).
+    The switch itself is refused without MODEL.CORNER_ROI (there are no corners_semantic) and together with
+    separated-classifier groups (MODEL.SEPARATE_CLASSES_ID: in the reference's grouped corner loss each group's subsample
+    overwrites the state of the one before, so there is no behaviour to match)."""
+    on = corner_loss_on(cfg)
+    if on and not cfg.MODEL.CORNER_ROI:
+        raise ValueError("MODEL.LOSS.CORNER_CONNECTION needs MODEL.CORNER_ROI = True: the centroid box head has no "
+                         "corners_semantic")
+    if on and len(getattr(cfg.MODEL, "SEPARATE_CLASSES_ID", None) or ()) > 0:
+        raise ValueError("MODEL.LOSS.CORNER_CONNECTION together with separated-classifier groups "
+                         "(MODEL.SEPARATE_CLASSES_ID) is not part of this package")
     if not cfg.MODEL.CORNER_ROI:
         return
     res = getattr(getattr(cfg.MODEL, "ROI_BOX_HEAD", None), "POOLER_RESOLUTION", None)
@@ -45,9 +61,10 @@ def corner_roi_check(cfg):
         raise ValueError("MODEL.CORNER_ROI needs MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION[1] == 11 (corner windows 0..2 and "
                          "8..10, body window 2..8), got %r" % (res,))
     lw = getattr(getattr(cfg.MODEL, "LOSS", None), "WEIGHTS", None)
-    if lw is None or len(lw) < 7 or any(float(v) != 0.0 for v in lw[4:7]):
+    if lw is None or len(lw) < 7 or (not on and any(float(v) != 0.0 for v in lw[4:7])):
         raise ValueError("MODEL.CORNER_ROI: the corner-connection losses are not part of this path -- "
-                         "MODEL.LOSS.WEIGHTS[4:7] must be given and be 0, got MODEL.LOSS.WEIGHTS = %r" % (lw,))
+                         "MODEL.LOSS.WEIGHTS[4:7] must be given and be 0, got MODEL.LOSS.WEIGHTS = %r"
+                         "%s" % (lw, "" if on else " (MODEL.LOSS.CORNER_CONNECTION = True switches them on)"))
 
 
 PRE_NMS, POST_NMS = 2000, 500      # boxlist_nms_3d(flag='roi_post'): rotate_nms_3d(pre_max_size=2000, post_max_size=500)
@@ -136,7 +153,7 @@ def box_detections(class_logits, box_regression, proposals, score_thresh=0.05, n
 
 def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, aug_thickness=None,
                      batch_size_per_image=500, positive_fraction=0.25, weights=None, seed=None, defer=False, debug=None,
-                     box_coder=None):
+                     box_coder=None, corner_groups=False):
     """proposals / targets: lists over scenes of [n_b, 7] / [G_b, 7] yx_zb device tensors, target_labels: list of int64
     [G_b].  Per scene what FastRCNNLossComputation.subsample does (box_head_3d/loss.py:163-293): IoU of every proposal
     with the scene's ground truth (`boxlist_iou_3d(target, proposal, aug_thickness, criterion=-1)`), Matcher(fg_iou,
@@ -154,7 +171,13 @@ def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, 
     regression_targets fp32 [m, 7].  One library call (1 memset + 6 launches whatever the batch), no host read until the
     counts are read at the end -- `defer=True` returns the function that does it, as box_detections does.  `debug` (a
     dict) receives the per-proposal arrays `matched_idx`, `matched_val`, `labels`, `regression_targets` (scene-major
-    concatenations), `iou` (list of [G_b, n_b] matrices), `info` (after the read) and the padded `samp_*` arrays."""
+    concatenations), `iou` (list of [G_b, n_b] matrices), `info` (after the read) and the padded `samp_*` arrays.
+
+    `corner_groups=True` (the label side of `corner_connection_loss`, csrc/corner_loss.hip: 3 more launches whatever the
+    batch, the same one host read): each scene's dict also carries, over its p positives -- the sampled rows with a
+    matched target, ordered by (matched target, row) --, `pos_pos` int64 [p] (positions in the scene's sample),
+    `connect_ids` int32 [2 p, 8] and `corner_xyz` fp32 [2 p, 3]; `debug` also receives `tg_xyz`, `tg_connect` and
+    `corner_info`.  The sample is the same with and without the flag."""
     from rpn_glue import draw_seed
     lib = _hip.load()
     nb = len(proposals)
@@ -192,13 +215,26 @@ def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, 
     s_labels = torch.empty((nb, B), dtype=torch.int64, device=dev)
     s_targets = torch.empty((nb, B, 7), dtype=torch.float32, device=dev)
     s_boxes = torch.empty((nb, B, 7), dtype=torch.float32, device=dev)
-    info = torch.empty((nb, INFO_WORDS), dtype=torch.int32, device=dev)
+    infos = torch.empty((2 if corner_groups else 1, nb, INFO_WORDS), dtype=torch.int32, device=dev)
+    info = infos[0]
     seed = int(draw_seed() if seed is None else seed) & 0xffffffff
     check(lib.aabr_roi_targets_coder(
         ptr(props), ptr(tg), ptr(tl), nb, _hip.i64xn(n_b), _hip.i64xn(g_b), _hip.f32x4(aug), -1,
         int(_nms.REFERENCE_DEBUG_ONLY_XY), float(fg_iou), float(bg_iou), _hip.f32xn(w), corner, seed, B,
         int(B * positive_fraction), ptr(midx), ptr(mval), ptr(labels), ptr(regt), ptr(iou), ptr(s_rows), ptr(s_labels),
         ptr(s_targets), ptr(s_boxes), ptr(info), scratch.data_ptr() + 4 * off, _hip.stream()))
+    if corner_groups:
+        G = sum(g_b)
+        tg_xyz = torch.empty((2 * G, 3), dtype=torch.float32, device=dev)
+        tg_connect = torch.empty((2 * G, 3), dtype=torch.int32, device=dev)
+        c_pos = torch.empty((nb, B), dtype=torch.int64, device=dev)
+        c_ids = torch.empty((nb, 2 * B, 8), dtype=torch.int32, device=dev)
+        c_xyz = torch.empty((nb, 2 * B, 3), dtype=torch.float32, device=dev)
+        check(lib.aabr_corner_tables(ptr(tg), nb, _hip.i64xn(n_b), _hip.i64xn(g_b), ptr(midx), ptr(s_rows), ptr(s_boxes), B,
+                                     ptr(tg_xyz), ptr(tg_connect), ptr(c_pos), ptr(c_ids), ptr(c_xyz), ptr(infos[1]),
+                                     _hip.stream()))
+        if debug is not None:
+            debug.update(tg_xyz=tg_xyz, tg_connect=tg_connect)
     if debug is not None:
         debug.update(matched_idx=midx, matched_val=mval, labels=labels, regression_targets=regt, samp_rows=s_rows,
                      samp_labels=s_labels, samp_targets=s_targets, samp_boxes=s_boxes, seed=seed)
@@ -209,17 +245,102 @@ def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, 
         debug["iou"] = mats
 
     def finish():
-        counts = _hip.read_back(info)                                     # the one read of the stage
+        both = _hip.read_back(infos)                                      # the one read of the stage
+        counts = both[0]
         if debug is not None:
             debug["info"] = counts
+            if corner_groups:
+                debug["corner_info"] = both[1]
         out = []
         for b in range(nb):
             m = counts[b][0]
             out.append({"rows": s_rows[b, :m], "bbox3d": s_boxes[b, :m], "labels": s_labels[b, :m],
                         "regression_targets": s_targets[b, :m]})
+            if corner_groups:
+                p = both[1][b][0]
+                out[b].update(pos_pos=c_pos[b, :p], connect_ids=c_ids[b, :2 * p], corner_xyz=c_xyz[b, :2 * p])
         return out
 
     return finish if defer else finish()
+
+
+CORNER_LOSS_KEYS = ("geometric_pull_loss", "semantic_pull_loss", "semantic_push_loss")    # loss.py:496-498
+
+
+class _CornerLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sem, seg_rows, pos_pos, connect_ids, corner_xyz):
+        lib = _hip.load()
+        dev = sem.device
+        sem_c = sem.contiguous()
+        nb, n = len(seg_rows), int(sem.shape[0])
+        tabs = ([t.contiguous() for t in pos_pos], [t.contiguous() for t in connect_ids],
+                [t.contiguous() for t in corner_xyz])
+        args = (n, nb, _hip.i64xn(seg_rows), _hip.i64xn([int(t.shape[0]) for t in pos_pos]), _hip.ptrs(tabs[0]),
+                _hip.ptrs(tabs[1]), _hip.ptrs(tabs[2]))
+        losses = torch.empty(3, dtype=torch.float32, device=dev)
+        counts = torch.empty((nb, 4), dtype=torch.int32, device=dev)
+        scr = _hip.workspace("corner_loss", int(lib.aabr_corner_loss_scratch_words(nb)), torch.int32, dev)
+        check(lib.aabr_corner_loss_forward(ptr(sem_c), *args, ptr(losses), ptr(counts), ptr(scr), _hip.stream()))
+        ctx.save_for_backward(sem_c, counts, *(tabs[0] + tabs[1] + tabs[2]))
+        ctx.args = args
+        geo, pull, push = losses.unbind(0)
+        ctx.mark_non_differentiable(geo, counts)              # the geometric loss depends on the proposals only
+        return geo, pull, push, counts
+
+    @staticmethod
+    def backward(ctx, _g_geo, g_pull, g_push, _g_counts):
+        lib = _hip.load()
+        sem, counts = ctx.saved_tensors[:2]
+        dev = sem.device
+        g_pull = (g_pull if g_pull is not None else torch.zeros((), device=dev)).float().contiguous()
+        g_push = (g_push if g_push is not None else torch.zeros((), device=dev)).float().contiguous()
+        d_sem = torch.empty_like(sem)                                           # the kernel writes every element
+        check(lib.aabr_corner_loss_backward(ptr(sem), *ctx.args, ptr(counts), ptr(g_pull), ptr(g_push), ptr(d_sem),
+                                            _hip.stream()))
+        return d_sem, None, None, None, None
+
+
+def corner_connection_loss(corners_semantic, seg_rows, pos_pos, connect_ids, corner_xyz, return_counts=False):
+    """FastRCNNLossComputation.corner_connection_loss (box_head_3d/loss.py:384-499) over the concatenated samples of a
+    batch.  corners_semantic fp32 [n, 16] (corner 0's 8 values, then corner 1's; any other dtype raises TypeError: the
+    predictor's output is fp32); the scenes are segments of its rows: seg_rows[b] = rows of scene b's sample, and pos_pos /
+    connect_ids / corner_xyz are the per-scene lists `box_head_targets(corner_groups=True)` returns (int64 [p_b], int32
+    [2 p_b, 8], fp32 [2 p_b, 3]).  The segments may differ in length; a scene without positives adds 0 to each loss and
+    still counts in the batch divisor.  Returns {"geometric_pull_loss", "semantic_pull_loss", "semantic_push_loss"}: 0-dim
+    fp32 device tensors, the semantic two with autograd to corners_semantic (the geometric one depends on the proposals
+    only).  Forward 2 launches, backward 1, whatever the batch; no host read; bit-identical run to run.
+    `return_counts=True` appends the int32 [nb, 4] device tensor of the per-scene counts (geometric entries below the
+    threshold, connected pairs, push pairs, corners)."""
+    lib = _hip.load()
+    if not torch.is_tensor(corners_semantic) or corners_semantic.dtype != torch.float32:
+        raise TypeError("corner_connection_loss: corners_semantic must be a float32 tensor, got %s"
+                        % (getattr(corners_semantic, "dtype", type(corners_semantic)),))
+    if corners_semantic.dim() != 2 or corners_semantic.shape[1] != 16:
+        raise ValueError("corner_connection_loss: corners_semantic must be [n, 16], got %s" % (tuple(corners_semantic.shape),))
+    seg_rows = [int(m) for m in seg_rows]
+    nb = len(seg_rows)
+    if not (nb == len(pos_pos) == len(connect_ids) == len(corner_xyz)):
+        raise ValueError("corner_connection_loss: seg_rows, pos_pos, connect_ids and corner_xyz differ in length")
+    if int(lib.aabr_corner_loss_scratch_words(nb)) < 0:
+        raise _hip.AabrError("corner_connection_loss: 1 <= scenes <= 16, got %d" % nb)
+    if sum(seg_rows) != int(corners_semantic.shape[0]):
+        raise ValueError("corner_connection_loss: the scenes have %d sampled rows, corners_semantic %d"
+                         % (sum(seg_rows), int(corners_semantic.shape[0])))
+    for b in range(nb):
+        p = int(pos_pos[b].shape[0])
+        if (pos_pos[b].dtype != torch.int64 or connect_ids[b].dtype != torch.int32 or corner_xyz[b].dtype != torch.float32
+                or tuple(connect_ids[b].shape) != (2 * p, 8) or tuple(corner_xyz[b].shape) != (2 * p, 3)):
+            raise ValueError("corner_connection_loss: scene %d needs pos_pos int64 [p], connect_ids int32 [2 p, 8] and "
+                             "corner_xyz float32 [2 p, 3]" % b)
+        if p > seg_rows[b] or p > 512:
+            raise ValueError("corner_connection_loss: scene %d has %d positives (at most its %d sampled rows and 512)"
+                             % (b, p, seg_rows[b]))
+    _hip.require_gpu(corners_semantic)
+    geo, pull, push, counts = _CornerLoss.apply(corners_semantic, seg_rows, list(pos_pos), list(connect_ids),
+                                                list(corner_xyz))
+    out = dict(zip(CORNER_LOSS_KEYS, (geo, pull, push)))
+    return (out, counts) if return_counts else out
 
 
 class _BoxHeadLoss(torch.autograd.Function):
@@ -972,12 +1093,12 @@ def box_predictions_corner(x_cor, x_body, cls_w, cls_b, body_w, body_b, cor_w, c
 def box_head_cfg(C=8, resolution=(2, 3, 2), R=12, classes=("background", "wall", "door"), class_specific=True, separate=(),
                  corner=False, track=False, scales=(0.5, 0.25, 0.125), canonical=10.0, sampling=2, voxel_scale=1.0,
                  extractor="FPN2MLPFeatureExtractor", predictor="FPNPredictor", eval_in_train=0, detections=20,
-                 loss_weights=(1.0, 1.0, 1.0, 1.0, 0.0, 0.0, 0.0), separate_ids=()):
+                 loss_weights=(1.0, 1.0, 1.0, 1.0, 0.0, 0.0, 0.0), separate_ids=(), corner_loss=False):
     """a plain attribute tree with the cfg keys the box head's modules read, named as in the reference's
     config/defaults.py -- for smoke(), the timing tool and the tests, which have no yacs config.  `separate` are the
     separated groups' class names (MODEL.SEPARATE_CLASSES: the predictor adds one column per entry), `separate_ids` the
     same groups as lists of class ids (MODEL.SEPARATE_CLASSES_ID: the loss evaluator builds its SeperateClassifier from
-    them)"""
+    them); `corner_loss` sets MODEL.LOSS.CORNER_CONNECTION, the switch of the corner-connection losses (corner_roi_check)"""
     box_head = _Cfg(POOLER_RESOLUTION=tuple(resolution), POOLER_SCALES_SPATIAL=tuple(scales),
                     POOLER_SAMPLING_RATIO=sampling, CANONICAL_SIZE=canonical, MLP_HEAD_DIM=R, FEATURE_EXTRACTOR=extractor,
                     PREDICTOR=predictor)
@@ -987,7 +1108,7 @@ def box_head_cfg(C=8, resolution=(2, 3, 2), R=12, classes=("background", "wall",
                  DETECTIONS_PER_IMG=detections)
     model = _Cfg(CORNER_ROI=corner, CLASS_SPECIFIC=class_specific, SEPARATE_CLASSES=list(separate),
                  SEPARATE_CLASSES_ID=[list(g) for g in separate_ids],
-                 ROI_BOX_HEAD=box_head, ROI_HEADS=heads, LOSS=_Cfg(YAW_MODE="Diff", WEIGHTS=tuple(loss_weights)),
+                 ROI_BOX_HEAD=box_head, ROI_HEADS=heads, LOSS=_Cfg(YAW_MODE="Diff", WEIGHTS=tuple(loss_weights), CORNER_CONNECTION=bool(corner_loss)),
                  RPN=_Cfg(ADD_GT_PROPOSALS=False))
     return _Cfg(MODEL=model, SPARSE3D=_Cfg(VOXEL_SCALE=voxel_scale, nPlaneMap=C), SOLVER=_Cfg(TRACK_RUNNING_STATS=track),
                 INPUT=_Cfg(CLASSES=list(classes)), DEBUG=_Cfg(eval_in_train=eval_in_train))

@@ -1264,6 +1264,57 @@ int aabr_roi_box_loss_grouped_backward(const void *class_logits, const void *box
                                        float beta, const int32_t *group_rows, const float *grad_cls_loss,
                                        const float *grad_box_loss, void *grad_logits, void *grad_regression,
                                        void *stream);
+/* ---- the corner-connection losses of the corner-ROI box head (csrc/corner_loss.hip; the reference's `*_corsem.yaml`
+ * configurations: geometric_pull_loss, semantic_pull_loss, semantic_push_loss, MODEL.LOSS.WEIGHTS[4:7]).  Added after 640
+ * without a bump: symbols only.
+ *
+ * Label side, aabr_corner_tables (3 launches whatever nb; no host read), run behind aabr_roi_targets_coder on its outputs.
+ * targets [sum g_host, 7] yx_zb, matched_idx int64 [sum n_host] (>= 0: the scene-local ground-truth row), samp_rows int64
+ * [nb][B] (ascending scene-local proposal rows, -1 behind the sample), samp_boxes fp32 [nb][B][7], B =
+ * batch_size_per_image <= 512, nb <= 16.  Outputs, every element written:
+ *   tg_xyz fp32 [2 G, 3]      the two top corners of every ground-truth box, moved towards their midpoint by half the
+ *                             thickness (bounding_box_3d.py:270-291) -- corner 2 g + c of the batch's box g;
+ *   tg_connect int32 [2 G, 3] per ground-truth corner the first three OTHER corners of its scene, in ascending scene-local
+ *                             corner index, closer than 0.1; -1 where there are fewer (bounding_box_3d.py:451-477);
+ *   pos_pos int64 [nb][B]     the scene's positives -- sampled rows with matched_idx >= 0 -- ordered by (matched target,
+ *                             position in the sample): the position of the k-th; -1 behind the p_b positives;
+ *   connect_ids int32 [nb][2 B][8]  per proposal corner 2 k + c: over its own ground-truth corner and that corner's up to
+ *                             three connected ones, the corners 2 k' + c' of the first four positives k' of each one's box
+ *                             (c' = that ground-truth corner's parity) -- 16 slots, sorted descending, cut to 8, -1 where
+ *                             there are fewer (box_head_3d/loss.py:22-99); rows behind 2 p_b are -1;
+ *   corner_xyz fp32 [nb][2 B][3]    the proposal corners' coordinates, as tg_xyz of the sampled boxes; zeros behind 2 p_b;
+ *   info int32 [nb][8]        [0] = p_b, [1] = g_host[b], the rest 0.
+ *
+ * Loss (box_head_3d/loss.py:384-499).  corners_semantic fp32 [n, 16] over the concatenated samples: scene b owns m_host[b]
+ * rows (their sum is n), p_host[b] <= 512 of them positives, described by the device arrays pos_pos_ptrs[b] (int64
+ * [p_b]), ids_ptrs[b] (int32 [2 p_b, 8]) and xyz_ptrs[b] (fp32 [2 p_b, 3]) -- host arrays of nb device pointers, e.g. rows
+ * of the padded outputs above.  Corner 2 k + c of scene b has the semantic vector corners_semantic[row of the k-th
+ * positive][8 c .. 8 c + 7].  Per scene, with N = 2 p_b corners, C_i = {i} + the entries of i's table row:
+ *   geometric pull = sum over table entries e of i with |xyz_e - xyz_i| < 0.2 of that distance / max(their count - N, 1)
+ *   semantic pull  = sum over i and a in C_i of |sem_a - sem_i| / max(sum |C_i| - N, 1)
+ *   semantic push  = sum over i and a not in C_i with |xyz_a - xyz_i| < 0.5 of max(1 - |sem_a - sem_i|, 0) /
+ *                    max(their count, 1)
+ * and each loss is the sum over the scenes / nb; a scene without positives adds 0.  losses fp32 [3] = geometric pull,
+ * semantic pull, semantic push; counts int32 [nb][4] = the three counts in that order and N, kept for the backward.  fp32
+ * sums in a fixed order (per tile of aabr_corner_loss_tile() corners, per thread, a fixed tree per workgroup, workgroup
+ * order, scene order), integer counts, no float atomics: bit-identical run to run.  Table entries outside [0, N) and
+ * positions outside [0, m_b) are never used as an index.  Launches: 2.  scratch: aabr_corner_loss_scratch_words(nb) int32.
+ * Backward (1 launch): grad_pull_loss / grad_push_loss are device fp32 scalars (the geometric loss depends on the
+ * proposals only: no gradient); EVERY element of grad_corners_semantic [n, 16] is written, exact zeros in the rows that
+ * are no positive; the gradient of a distance that is exactly 0 is 0.                                               */
+int aabr_corner_loss_tile(void);
+int64_t aabr_corner_loss_scratch_words(int nb);
+int aabr_corner_tables(const float *targets, int nb, const int64_t *n_host, const int64_t *g_host,
+                       const int64_t *matched_idx, const int64_t *samp_rows, const float *samp_boxes,
+                       int batch_size_per_image, float *tg_xyz, int32_t *tg_connect, int64_t *pos_pos,
+                       int32_t *connect_ids, float *corner_xyz, int32_t *info, void *stream);
+int aabr_corner_loss_forward(const float *corners_semantic, int64_t n, int nb, const int64_t *m_host,
+                             const int64_t *p_host, const void *const *pos_pos_ptrs, const void *const *ids_ptrs,
+                             const void *const *xyz_ptrs, float *losses, int32_t *counts, int32_t *scratch, void *stream);
+int aabr_corner_loss_backward(const float *corners_semantic, int64_t n, int nb, const int64_t *m_host,
+                              const int64_t *p_host, const void *const *pos_pos_ptrs, const void *const *ids_ptrs,
+                              const void *const *xyz_ptrs, const int32_t *counts, const float *grad_pull_loss,
+                              const float *grad_push_loss, float *grad_corners_semantic, void *stream);
 /* Detections (SeperateClassifier.post_processor): aabr_roi_post_detections_coder with groups.  sep_id int32 [N], rows in
  * any order inside a scene.  Per row the softmax over its group's columns (group-local order), every other column of
  * prob an exact 0; boxes [N, 7].  Per (scene, foreground column c): the rows OF c's GROUP with prob > score_thresh
