@@ -61,6 +61,7 @@ _SIGS = {
     "aabr_input_layer_rule_table": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "aabr_submanifold_table": (C.c_int, [_vp, _i64, _vp, _i64, _i32p, _vp, _vp, _vp]),
     "aabr_convolution_sites": (C.c_int, [_vp, _i64, _i32p, _i32p, _i32p, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "aabr_full_convolution_sites": (C.c_int, [_vp, _i64, _i32p, _i32p, _i32p, _vp, _i64, _vp, _vp, _vp, _vp]),
     "aabr_convolution_tables": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32p, _i32p,
                                           _i32p, _vp, _vp, _vp, _vp]),
     "aabr_convolution_tables2": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32p, _i32p,
@@ -69,6 +70,8 @@ _SIGS = {
     "aabr_brick_scratch_words": (C.c_int64, [_i64, _i64]),
     "aabr_brick_build": (C.c_int, [_vp, _i64, _vp, _i32p, _i32p, _i32p, _i32p, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp,
                                    _i32, _vp]),
+    "aabr_brick_full_build": (C.c_int, [_vp, _i64, _vp, _i32p, _i32p, _i32p, _i32p, _vp, _vp, _i64, _vp, _vp, _i64, _vp,
+                                        _vp, _i32, _vp]),
     "aabr_brick_renumber": (C.c_int, [_vp, _i64, _i32p, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
                                       _vp, _vp]),
     "aabr_points_prepare": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -54,7 +54,10 @@ __device__ inline bool wave_or64(unsigned long long *arr, int64_t idx, unsigned 
 //   ROUND 1: the item's output voxel marks its brick in the directory word of its super-brick;
 //   ROUND 2 (the directory prefix is known): the voxel sets its cell bit in its brick's mask and leaves the brick's
 //            coordinates (no old value is read back: every sender stores the same coordinates).
-template <int ROUND>
+// FULL: the DILATING build of a FullConvolution's level (FullConvolutionRules.h:19-31): items = (input site u, l-th filter
+// offset), the voxel is u * stride + offset_l (geom.h full_region_lth; g.maxout = the filter volume), and one outside the
+// level's spatial size is an error instead of a clipped window.
+template <int ROUND, bool FULL>
 __global__ __launch_bounds__(256) void k_brick_mark(const int32_t *__restrict__ in_coords, int64_t vin_bound,
                                                     const int32_t *__restrict__ vin_dev, ConvGeom g, BrickDims d,
                                                     uint4 *dir, uint4 *bricks, int64_t nb_cap, int4 *__restrict__ bcoord,
@@ -70,7 +73,8 @@ __global__ __launch_bounds__(256) void k_brick_mark(const int32_t *__restrict__ 
 #pragma unroll 1
   for (int l = 0; l < g.maxout; ++l) {
     int j[3] = {0, 0, 0};
-    bool ok = live && output_region_lth(g, p, l, j);
+    bool ok = live && (FULL ? full_region_lth(g, p, l, j) : output_region_lth(g, p, l, j));
+    if (FULL && live && !ok) err = true;
     int64_t w = -1;
     if (ok) {
       w = brick_dir_index(d, ic.w, j[0], j[1], j[2]);
@@ -364,26 +368,35 @@ extern "C" int64_t aabr_brick_scratch_words(int64_t dir_words_, int64_t nb_cap) 
   return 2 * (c0 + c1) + 4;       // int32 words: two status arrays of 8-byte words + two tickets (+ pad)
 }
 
-extern "C" int aabr_brick_build(const int32_t *in_coords, int64_t vin_bound, const int32_t *vin_count_dev,
-                                const int32_t *size_host, const int32_t *stride_host, const int32_t *out_spatial_host,
-                                const int32_t *dims_host, void *dir, void *bricks, int64_t nb_cap, int32_t *bcoord,
-                                int32_t *out_coords, int64_t v_cap, int32_t *meta, int32_t *scratch, int flags,
-                                void *stream_) {
+// the two level builds: FULL = false the level a strided convolution shrinks to (aabr_brick_build), FULL = true the level a
+// FullConvolution grows to (aabr_brick_full_build); `fn` = the entry point's name for the argument messages
+template <bool FULL>
+static int brick_build(const char *fn, const int32_t *in_coords, int64_t vin_bound, const int32_t *vin_count_dev,
+                       const int32_t *size_host, const int32_t *stride_host, const int32_t *out_spatial_host,
+                       const int32_t *dims_host, void *dir, void *bricks, int64_t nb_cap, int32_t *bcoord,
+                       int32_t *out_coords, int64_t v_cap, int32_t *meta, int32_t *scratch, int flags, void *stream_) {
+#define AABR_BB_ARG(cond, msg) AABR_CHECK_ARG_AS(fn, cond, msg)
   hipStream_t st = (hipStream_t)stream_;
-  AABR_CHECK_ARG((flags & ~1) == 0, "flags: bit 0 = the caller has cleared dir / bricks / meta / scratch");
-  AABR_CHECK_ARG(vin_bound >= 0 && vin_bound < (int64_t)0x7fffffff && size_host && stride_host && out_spatial_host,
-                 "bad arguments");
+  AABR_BB_ARG((flags & ~1) == 0, "flags: bit 0 = the caller has cleared dir / bricks / meta / scratch");
+  AABR_BB_ARG(vin_bound >= 0 && vin_bound < (int64_t)0x7fffffff && size_host && stride_host && out_spatial_host,
+              "bad arguments");
   ConvGeom g;
-  AABR_CHECK_ARG(make_geom(size_host, stride_host, out_spatial_host, g, true) == 0, "bad filter geometry");
+  if (FULL) {
+    AABR_BB_ARG(make_full_geom(size_host, stride_host, out_spatial_host, g) == 0, "bad filter geometry");
+    AABR_BB_ARG(vin_bound * g.maxout < (int64_t)0x7fffffff,
+                "too many candidate sites (V_in * filter volume must stay below 2^31)");
+  } else {
+    AABR_BB_ARG(make_geom(size_host, stride_host, out_spatial_host, g, true) == 0, "bad filter geometry");
+  }
   BrickDims d;
-  AABR_CHECK_ARG(make_dims(dims_host, d) == 0, "dims: super-bricks per axis in [1, 4096], samples in [1, 65535]");
+  AABR_BB_ARG(make_dims(dims_host, d) == 0, "dims: super-bricks per axis in [1, 4096], samples in [1, 65535]");
   const int64_t nw = dir_words(d);
-  AABR_CHECK_ARG(nw < (int64_t)1 << 31 && nb_cap >= 1 && nb_cap < (int64_t)1 << 31 && v_cap >= 1, "level too large");
-  AABR_CHECK_ARG(dir && bricks && bcoord && out_coords && meta && scratch && (vin_bound == 0 || in_coords),
-                 "null pointer");
-  AABR_CHECK_ARG(((uintptr_t)dir & 15) == 0 && ((uintptr_t)bricks & 15) == 0 && ((uintptr_t)bcoord & 15) == 0 &&
-                     ((uintptr_t)out_coords & 15) == 0 && ((uintptr_t)scratch & 7) == 0,
-                 "directory / bricks / coordinates 16-byte, scratch 8-byte aligned");
+  AABR_BB_ARG(nw < (int64_t)1 << 31 && nb_cap >= 1 && nb_cap < (int64_t)1 << 31 && v_cap >= 1, "level too large");
+  AABR_BB_ARG(dir && bricks && bcoord && out_coords && meta && scratch && (vin_bound == 0 || in_coords), "null pointer");
+  AABR_BB_ARG(((uintptr_t)dir & 15) == 0 && ((uintptr_t)bricks & 15) == 0 && ((uintptr_t)bcoord & 15) == 0 &&
+                  ((uintptr_t)out_coords & 15) == 0 && ((uintptr_t)scratch & 7) == 0,
+              "directory / bricks / coordinates 16-byte, scratch 8-byte aligned");
+#undef AABR_BB_ARG
   const int64_t c0 = ceil_div(nw, (int64_t)kBsChunk), c1 = ceil_div(nb_cap, (int64_t)kBsChunk);
   unsigned long long *status0 = reinterpret_cast<unsigned long long *>(scratch);
   unsigned long long *status1 = status0 + c0;
@@ -399,17 +412,35 @@ extern "C" int aabr_brick_build(const int32_t *in_coords, int64_t vin_bound, con
     AABR_CHECK_HIP(hipMemsetAsync(scratch, 0, (size_t)(2 * (c0 + c1) + 4) * sizeof(int32_t), st));
   }
   if (vin_bound > 0)
-    hipLaunchKernelGGL(k_brick_mark<1>, grid1(vin_bound, 256), dim3(256), 0, st, in_coords, vin_bound, vin_count_dev, g,
+    hipLaunchKernelGGL((k_brick_mark<1, FULL>), grid1(vin_bound, 256), dim3(256), 0, st, in_coords, vin_bound, vin_count_dev, g,
                        d, (uint4 *)dir, (uint4 *)bricks, nb_cap, (int4 *)bcoord, meta);
   hipLaunchKernelGGL(k_brick_scan<0>, dim3((unsigned)c0), dim3(kBsThreads), 0, st, (uint4 *)dir, nw, status0, tickets,
                      meta, nb_cap, d, (int4 *)bcoord, (int32_t *)nullptr, (int64_t)0);
   if (vin_bound > 0)
-    hipLaunchKernelGGL(k_brick_mark<2>, grid1(vin_bound, 256), dim3(256), 0, st, in_coords, vin_bound, vin_count_dev, g,
+    hipLaunchKernelGGL((k_brick_mark<2, FULL>), grid1(vin_bound, 256), dim3(256), 0, st, in_coords, vin_bound, vin_count_dev, g,
                        d, (uint4 *)dir, (uint4 *)bricks, nb_cap, (int4 *)bcoord, meta);
   hipLaunchKernelGGL(k_brick_scan<1>, dim3((unsigned)c1), dim3(kBsThreads), 0, st, (uint4 *)bricks, nb_cap, status1,
                      tickets + 1, meta, v_cap, d, (int4 *)bcoord, out_coords, v_cap);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
+}
+
+extern "C" int aabr_brick_build(const int32_t *in_coords, int64_t vin_bound, const int32_t *vin_count_dev,
+                                const int32_t *size_host, const int32_t *stride_host, const int32_t *out_spatial_host,
+                                const int32_t *dims_host, void *dir, void *bricks, int64_t nb_cap, int32_t *bcoord,
+                                int32_t *out_coords, int64_t v_cap, int32_t *meta, int32_t *scratch, int flags,
+                                void *stream_) {
+  return brick_build<false>(__func__, in_coords, vin_bound, vin_count_dev, size_host, stride_host, out_spatial_host,
+                            dims_host, dir, bricks, nb_cap, bcoord, out_coords, v_cap, meta, scratch, flags, stream_);
+}
+
+extern "C" int aabr_brick_full_build(const int32_t *in_coords, int64_t vin_bound, const int32_t *vin_count_dev,
+                                     const int32_t *size_host, const int32_t *stride_host,
+                                     const int32_t *out_spatial_host, const int32_t *dims_host, void *dir, void *bricks,
+                                     int64_t nb_cap, int32_t *bcoord, int32_t *out_coords, int64_t v_cap, int32_t *meta,
+                                     int32_t *scratch, int flags, void *stream_) {
+  return brick_build<true>(__func__, in_coords, vin_bound, vin_count_dev, size_host, stride_host, out_spatial_host,
+                           dims_host, dir, bricks, nb_cap, bcoord, out_coords, v_cap, meta, scratch, flags, stream_);
 }
 
 extern "C" int aabr_brick_renumber(const int32_t *old_coords, int64_t V, const int32_t *dims_host, const void *dir,

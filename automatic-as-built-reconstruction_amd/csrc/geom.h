@@ -46,6 +46,38 @@ static inline int make_geom(const int32_t *size, const int32_t *stride, const in
   return 0;
 }
 
+// ---- FullConvolution: the level that GROWS (FullConvolutionRules.h:11-33) ----------------------------------------------
+// l-th point (offset order, z fastest) of the region input point p writes to: p * stride + offset_l -- the reference walks
+// InputRegionCalculator (RectangularRegions.h:95-105) there, "swapped v.s. a normal Convolution".  False when the point
+// lies outside [0, out_sp) (64-bit arithmetic: 65534 * 65536 does not fit an int).  g.maxout = the filter volume here.
+__device__ inline bool full_region_lth(const ConvGeom &g, const int p[3], int l, int j[3]) {
+  int off[3];
+  off[2] = l % g.size[2]; l /= g.size[2];
+  off[1] = l % g.size[1]; l /= g.size[1];
+  off[0] = l;
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int64_t v = (int64_t)p[i] * g.stride[i] + off[i];
+    ok = ok && p[i] >= 0 && v < (int64_t)g.out_sp[i];
+    j[i] = (int)v;
+  }
+  return ok;
+}
+// per-axis limits of make_geom(sites_only); out_sp = the NEW level's spatial size, within the 16-bit key range; maxout =
+// candidates per input site = the filter volume (< 2^31)
+static inline int make_full_geom(const int32_t *size, const int32_t *stride, const int32_t *out_sp, ConvGeom &g) {
+  if (make_geom(size, stride, out_sp, g, true) != 0) return -1;
+  int64_t vol = 1;
+  for (int i = 0; i < 3; ++i) {
+    if (out_sp[i] > kMaxCoord + 1) return -1;
+    vol *= size[i];
+  }
+  if (vol >= (int64_t)0x7fffffff) return -1;
+  g.maxout = (int)vol;
+  return 0;
+}
+
 // counts[k * gridDim.x + blockIdx.x] = number of hits in this block (plain store: 27 hot
 // addresses hammered by one atomic per wave cost more than the whole table build)
 __device__ inline void block_count_store(int hit, int32_t *__restrict__ counts, int k) {

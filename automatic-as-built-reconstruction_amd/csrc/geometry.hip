@@ -97,7 +97,8 @@ __global__ __launch_bounds__(1024) void k_scan_blockprefix(const int32_t *__rest
   }
 }
 
-// MODE 0: input layer (items = points); MODE 1: strided-conv output sites (items = encounters)
+// MODE 0: input layer (items = points); MODE 1: strided-conv output sites (items = encounters); MODE 2: the sites a
+// FullConvolution reaches (items = input site x filter offset, full_region_lth)
 template <int MODE>
 __global__ __launch_bounds__(kScanThreads) void k_assign_sites(
     const int32_t *__restrict__ slot, GridEnt *__restrict__ minidx,
@@ -154,7 +155,8 @@ __global__ __launch_bounds__(kScanThreads) void k_assign_sites(
         int l = (int)(e % g.maxout);
         int4 ic = *reinterpret_cast<const int4 *>(in_coords + 4 * u);
         int p[3] = {ic.x, ic.y, ic.z}, jj[3];
-        output_region_lth(g, p, l, jj);
+        if (MODE == 1) output_region_lth(g, p, l, jj);
+        else full_region_lth(g, p, l, jj);
         *reinterpret_cast<int4 *>(site_coords + 4 * (int64_t)ra) = make_int4(jj[0], jj[1], jj[2], ic.w);
       }
       ra += 1; rb += c[j];
@@ -196,6 +198,30 @@ __global__ __launch_bounds__(256) void k_conv_insert_sites(const int32_t *__rest
     } else {
       slot[e] = -1;
     }
+  }
+}
+
+// FullConvolution (FullConvolutionRules.h:19-31): encounter e = u * vol + l is the l-th filter offset of input row u; its
+// site p * stride + offset_l is inserted and remembers the smallest e that reached it -- first-seen order over input rows
+// ascending, then offsets z fastest.  One thread per encounter: every insert is an independent random probe.  A site
+// outside the new level's spatial size is reported through meta[2] and left out.
+__global__ __launch_bounds__(256) void k_full_insert_sites(const int32_t *__restrict__ in_coords, int64_t E, ConvGeom g,
+                                                           GridEnt *keys, uint64_t mask, int32_t *__restrict__ slot,
+                                                           int32_t *meta) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  const int64_t u = e / g.maxout;
+  const int l = (int)(e % g.maxout);
+  const int4 ic = *reinterpret_cast<const int4 *>(in_coords + 4 * u);
+  const int p[3] = {ic.x, ic.y, ic.z};
+  int j[3];
+  if (full_region_lth(g, p, l, j)) {
+    const uint32_t h = grid_insert(keys, mask, pack_key(ic.w, j[0], j[1], j[2]));
+    atomicMin(&keys[h].first, (uint32_t)e);
+    slot[e] = (int32_t)h;
+  } else {
+    slot[e] = -1;
+    meta[2] = 1;
   }
 }
 
@@ -341,6 +367,44 @@ extern "C" int aabr_convolution_sites(const int32_t *in_coords, int64_t V_in, co
                      (const uint32_t *)nullptr, E, prefix,
                      inline_prefix ? (const int32_t *)blocksums : (const int32_t *)nullptr, out_site_coords, (int32_t *)nullptr, meta,
                      (const int64_t *)nullptr, 0, in_coords, g);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+extern "C" int aabr_full_convolution_sites(const int32_t *in_coords, int64_t V_in, const int32_t *size_host,
+                                           const int32_t *stride_host, const int32_t *out_spatial_host,
+                                           uint64_t *out_keys, int64_t out_cap, int32_t *scratch,
+                                           int32_t *out_site_coords, int32_t *meta, void *stream_) {
+  hipStream_t st = (hipStream_t)stream_;
+  AABR_CHECK_ARG(V_in >= 0 && V_in < (int64_t)0x7fffffff && size_host && stride_host && out_spatial_host, "bad arguments");
+  ConvGeom g;
+  AABR_CHECK_ARG(make_full_geom(size_host, stride_host, out_spatial_host, g) == 0, "bad filter geometry");
+  const int64_t E = V_in * g.maxout;      // candidates: every input site x every filter offset (< 2^62)
+  AABR_CHECK_ARG(E < (int64_t)0x7fffffff, "too many candidate sites (V_in * filter volume must stay below 2^31)");
+  AABR_CHECK_ARG(is_pow2(out_cap) && 2 * out_cap >= 3 * E && out_cap >= 64,
+                 "out_cap must be a power of two >= max(64, 1.5*V_in*filter volume)");
+  AABR_CHECK_ARG(out_keys && out_site_coords && meta && ((uintptr_t)out_keys & 15) == 0 && (V_in == 0 || (in_coords && scratch)),
+                 "null / misaligned pointer");
+  GridEnt *grid = reinterpret_cast<GridEnt *>(out_keys);
+  AABR_CHECK_HIP(hipMemsetAsync(grid, 0xFF, out_cap * sizeof(GridEnt), st));   // key = empty, first = max, val = -1
+  AABR_CHECK_HIP(hipMemsetAsync(meta, 0, AABR_META_WORDS * sizeof(int32_t), st));
+  if (V_in == 0) return AABR_OK;          // an empty level: meta[0] = 0, no launch
+  const int64_t nblk = ceil_div(E, kScanTile);
+  int32_t *slot = scratch;
+  int32_t *blocksums = slot + E;
+  int32_t *prefix = blocksums + 2 * nblk;
+  hipLaunchKernelGGL(k_full_insert_sites, grid1(E, 256), dim3(256), 0, st, in_coords, E, g, grid, (uint64_t)(out_cap - 1),
+                     slot, meta);
+  hipLaunchKernelGGL(k_scan_blocksums, dim3((unsigned)nblk), dim3(kScanThreads), 0, st, slot, grid,
+                     (const uint32_t *)nullptr, E, blocksums);
+  const bool inline_prefix = nblk <= kInlinePrefixBlocks;
+  if (!inline_prefix)
+    hipLaunchKernelGGL(k_scan_blockprefix, dim3(1), dim3(1024), 0, st, blocksums, nblk, prefix, meta,
+                       (int32_t *)nullptr);
+  hipLaunchKernelGGL(k_assign_sites<2>, dim3((unsigned)nblk), dim3(kScanThreads), 0, st, slot, grid,
+                     (const uint32_t *)nullptr, E, prefix,
+                     inline_prefix ? (const int32_t *)blocksums : (const int32_t *)nullptr, out_site_coords,
+                     (int32_t *)nullptr, meta, (const int64_t *)nullptr, 0, in_coords, g);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }

@@ -339,6 +339,7 @@ def derived_cap(E):
     return _hip.next_pow2(max(64, E + (E + 1) // 2))
 
 
+kMaxSpatial = 65535  # largest spatial size per axis (coordinates <= 65534: csrc/common.h kMaxCoord)
 MAX_SAMPLES = 61     # per-sample offsets that ride along with a grid's site-count read (64-word rows)
 BRICK_MAX_DIR_WORDS = 1 << 25   # 512 MiB of directory for the input level; above it a scene keeps its hash grids
 brick_stats = {"built": 0, "declined": 0}
@@ -500,6 +501,8 @@ class Metadata_3(object):
         self.grids = {}
         self.submanifold = {}
         self.rulebooks = {}
+        self.fullConvolutionRuleBook = None   # the one rule book of the FullConvolution that created this object
+        self._borrowed = set()                # spatial sizes whose level belongs to another Metadata (getFullConvolutionRuleBook)
         self.input = None  # dict(point_site, first_pt, cnt_extra, head, nxt, last_pt, meta, n, V, mode, spatial)
         self.device = None
         self._pregrids = set()
@@ -555,7 +558,8 @@ class Metadata_3(object):
         ts += list(self._brick_keep)
         if self.input is not None:
             ts += [self.input["point_site"]]
-        for tb in list(self.submanifold.values()) + list(self.rulebooks.values()):
+        full = [self.fullConvolutionRuleBook] if self.fullConvolutionRuleBook is not None else []
+        for tb in list(self.submanifold.values()) + list(self.rulebooks.values()) + full:
             for ga in (tb.out, tb.inn):
                 if ga is None:
                     continue
@@ -909,8 +913,8 @@ class Metadata_3(object):
             if r[64 + 2]:
                 raise _hip.AabrError("brick grid %d: a site outside the directory's extent or a capacity overflow "
                                      "(meta %s)" % (i, r[64:64 + 4]))
-        g0 = self.grids[self.input["spatial"]]
-        if rows[0][64] != g0.V:
+        g0 = self.grids[self.input["spatial"]] if self.input is not None else None
+        if g0 is not None and rows[0][64] != g0.V:    # (no input layer: the object a FullConvolution created, row 0 = its level)
             raise _hip.AabrError("brick grid of the input level holds %d sites, the voxel scatter counted %d"
                                  % (rows[0][64], g0.V))
         return rows
@@ -1061,6 +1065,12 @@ class Metadata_3(object):
             fs, st, osz = _key(filter_size), _key(filter_stride), _key(out_spatial)
             dev = gi.coords.device
             vol = fs[0] * fs[1] * fs[2]
+            if osz in self._borrowed and osz != _key(in_spatial):
+                # the input level a FullConvolution shared with this object: a convolution onto that spatial size reaches
+                # other sites than the level holds, and builds its own (the reference clears and rebuilds it too,
+                # ConvolutionRules.h:43-44)
+                self._borrowed.discard(osz)
+                del self.grids[osz]
             have = self.grids.get(osz)
             if gi.brick is not None and gi.V > 0 and osz not in self.__dict__.get("_pregrids", ()) and \
                     not (have is not None and have.brick is not None):
@@ -1128,6 +1138,118 @@ class Metadata_3(object):
             tb = _Table(_Gather(t_out, counts, vol, V_out), _Gather(t_in, counts_in, vol, gi.V), vol, V_out, gi.V)
             self.rulebooks[k] = tb
         return tb
+
+    def getFullConvolutionRuleBook(self, in_spatial, out_spatial, filter_size, filter_stride, new_metadata):
+        """Metadata::getFullConvolutionRuleBook (Metadata.cpp:511-531): the rule book of a FullConvolution from THIS
+        object's level `in_spatial` onto a NEW level -- one site at p * stride + q for every input site p and filter offset
+        q -- that is created in `new_metadata`, built once per `new_metadata`.  `new_metadata` is cleared, takes this
+        object's site order and the input level (the `_Grid` object itself: it is never written) and keeps the book as its
+        `fullConvolutionRuleBook`.  This object is only read.  The book is that of a Convolution from the new level down
+        to the input level: `out` [vol, V_in] is complete by construction, `inn` [vol, V_new] is what the forward pass
+        gathers through (as Deconvolution_updateOutput reads `tb.inn`).  First-seen order: aabr_full_convolution_sites +
+        aabr_convolution_tables2 and one host read of the site count; brick order: aabr_brick_full_build +
+        aabr_brick_convolution_tables, no hash builder."""
+        tb = new_metadata.fullConvolutionRuleBook
+        if tb is not None:
+            return tb
+        lib = _hip.load()
+        if getattr(self, "_inb", None) is not None:
+            self._materialise_input(torch.device("cuda", torch.cuda.current_device()))
+        isz, osz, fs, st = _key(in_spatial), _key(out_spatial), _key(filter_size), _key(filter_stride)
+        assert len(fs) == 3 and len(st) == 3, "dimension 3 only"
+        if osz != tuple((i - 1) * s_ + f for i, f, s_ in zip(isz, fs, st)):
+            raise ValueError("FullConvolution: output spatial size %s is not (input %s - 1) * stride %s + filter %s"
+                             % (osz, isz, st, fs))
+        gi = self.grids[isz]
+        dev = gi.coords.device
+        vol = fs[0] * fs[1] * fs[2]
+        E = gi.V * vol
+        if E >= 0x7fffffff:
+            raise _hip.AabrError("FullConvolution: %d input sites x filter volume %d reaches 2^31 candidate sites" % (gi.V, vol))
+        flush_geom()                     # the calls below launch (and read) right away
+        new_metadata.clear()
+        new_metadata.site_order = self.site_order
+        new_metadata.device = dev
+        new_metadata.input_spatial = isz
+        new_metadata.grids[isz] = gi     # (size 1 / stride 1: the new level below takes this key over, with the same rows)
+        new_metadata._borrowed = {isz}   # not a level of its own making: getRuleBook does not build onto it
+        big = (kMaxSpatial,) * 3         # the tables clip nothing: every site of the new level has its parent
+        empty = lambda rows: torch.empty((vol, rows), dtype=torch.int32, device=dev)
+        if gi.V == 0:
+            new_metadata.grids[osz] = _Grid(gi.coords[:0], None, None, 0, 0) if gi.keys is None else \
+                self._full_hash_level(gi, fs, st, osz, 0)
+            z = lambda: torch.empty(0, dtype=torch.int32, device=dev)
+            tb = _Table(_Gather(empty(0), z(), vol, 0), _Gather(empty(0), z(), vol, 0), vol, 0, 0)
+            new_metadata.fullConvolutionRuleBook = tb
+            return tb
+        if gi.brick is not None:
+            bs = gi.brick
+            rows = new_metadata._brick_rows = torch.zeros((_BK_MAX_LEVELS, _BK_ROW), dtype=torch.int32, device=dev)
+            new_metadata._brick_rows_clean = True
+            new_metadata._brick_nrows = 1
+            ext = [(e - 1) * s_ + f for e, f, s_ in zip(bs.ext, fs, st)]
+            # bricks: bounded by the candidates, not by parent bricks * vol (a dilated 4^3 brick with size == stride == 2 touches
+            # up to 27 bricks); _Brick clips both bounds to what the directory's extent can hold
+            bk = _Brick(ext, bs.dims[3], E, E, dev, rows[0, 64:64 + _hip.META_WORDS], alloc=False)
+            lw = 4 * (bk.nw + bk.nb_cap)
+            sw = (int(lib.aabr_brick_scratch_words(bk.nw, bk.nb_cap)) + 3) // 4 * 4
+            arena = torch.zeros(lw + sw, dtype=torch.int32, device=dev)       # ONE fill: directory, bricks, scan scratch
+            bk.level = arena[:lw]
+            check(lib.aabr_brick_full_build(ptr(gi.coords), gi.V, None, _hip.i32x3(fs), _hip.i32x3(st), _hip.i32x3(osz),
+                                            bk.dims_c(), bk.dir_ptr(), bk.bricks_ptr(), bk.nb_cap, bk.bcoord.data_ptr(),
+                                            bk.coords_full.data_ptr(), bk.v_cap, bk.meta.data_ptr(),
+                                            arena[lw:].data_ptr(), 1, stream()))
+            bm = _hip.read_back(bk.meta)         # host sync: the site count sizes the output feature tensor
+            if bm[2]:
+                raise _hip.AabrError("FullConvolution: a site outside the output spatial size %s, or a brick level "
+                                     "overflow (meta %s)" % (osz, bm[:4]))
+            V_new = bm[0]
+            new_metadata._brick_keep = [rows, arena]
+            go = _Grid(bk.coords_full[:V_new], None, None, 0, V_new, None, bk)
+        else:
+            go = self._full_hash_level(gi, fs, st, osz, E)
+            V_new = go.V
+        new_metadata.grids[osz] = go
+        new_metadata._borrowed.discard(osz)
+        t_out, t_in = empty(gi.V), empty(V_new)
+        counts = torch.empty(vol * ((gi.V + 255) // 256), dtype=torch.int32, device=dev)
+        counts_in = torch.empty(vol * ((V_new + 255) // 256), dtype=torch.int32, device=dev)
+        # a Convolution's tables with the NEW level as the input side and this level as the output side
+        if gi.brick is not None:
+            check(lib.aabr_brick_convolution_tables(ptr(go.coords), V_new, go.brick.dims_c(), go.brick.dir_ptr(),
+                                                    go.brick.bricks_ptr(), ptr(gi.coords), gi.V, gi.brick.dims_c(),
+                                                    gi.brick.dir_ptr(), gi.brick.bricks_ptr(), _hip.i32x3(fs),
+                                                    _hip.i32x3(st), _hip.i32x3(big), ptr(t_out), ptr(t_in), ptr(counts),
+                                                    ptr(counts_in), stream()))
+        else:
+            check(lib.aabr_convolution_tables2(ptr(go.coords), V_new, ptr(go.keys), go.cap, ptr(gi.coords), gi.V,
+                                               ptr(gi.keys), gi.cap, _hip.i32x3(fs), _hip.i32x3(st), _hip.i32x3(big),
+                                               ptr(t_out), ptr(t_in), ptr(counts), ptr(counts_in), stream()))
+        tb = _Table(_Gather(t_out, counts, vol, gi.V), _Gather(t_in, counts_in, vol, V_new), vol, gi.V, V_new)
+        new_metadata.fullConvolutionRuleBook = tb
+        return tb
+
+    @staticmethod
+    def _full_hash_level(gi, fs, st, osz, E):
+        """the hash grid of the level a FullConvolution grows to, numbered first-seen (aabr_full_convolution_sites); the
+        one host read of its site count (none for an empty input level)"""
+        lib = _hip.load()
+        dev = gi.coords.device
+        cap = derived_cap(E)
+        nblk = (max(E, 1) + 255) // 256
+        keys = torch.empty(2 * cap, dtype=torch.int64, device=dev)   # cap 16-byte entries {key, first, val}
+        scratch = torch.empty(E + 4 * nblk + 16, dtype=torch.int32, device=dev)
+        out_coords = torch.empty((max(E, 1), 4), dtype=torch.int32, device=dev)
+        meta = torch.empty(_hip.META_WORDS, dtype=torch.int32, device=dev)
+        check(lib.aabr_full_convolution_sites(ptr(gi.coords), gi.V, _hip.i32x3(fs), _hip.i32x3(st), _hip.i32x3(osz),
+                                              ptr(keys), cap, ptr(scratch), ptr(out_coords), ptr(meta), stream()))
+        V_new = 0
+        if E > 0:
+            m = meta.tolist()            # host sync: sizes the output feature tensor
+            if m[2]:
+                raise _hip.AabrError("FullConvolution: an input site reaches outside the output spatial size %s" % (osz,))
+            V_new = m[0]
+        return _Grid(out_coords[:V_new], keys, None, cap, V_new)
 
     # ---- reference-format views (tests / API parity) ------------------------------------------
     def max_active(self):
@@ -1632,6 +1754,39 @@ def Deconvolution_backward(input_size, output_size, filter_size, filter_stride, 
     inp = _featc(input_features, "input_features")
     d_out = _featc(d_output_features, "d_output_features")
     tb = metadata.getRuleBook(output_size, input_size, filter_size, filter_stride)
+    if need_d_input:
+        _conv_fwd(d_out, d_input_features, tb.V_out, tb.out, weight, None, 1, pack_t)
+    _conv_dw(inp, d_out, tb.inn, d_weight, d_bias)
+
+
+# FullConvolution / TransposeConvolution (pybind.cpp:90-101; CPU/Convolution.cpp:255-329): the arithmetic of a
+# Deconvolution -- out[p * stride + q] += in[p] @ W[q] -- onto a level that `mIn.getFullConvolutionRuleBook` creates in
+# `mOut`; every convolution kernel runs unchanged on that book's tables.
+def FullConvolution_updateOutput(input_size, output_size, filter_size, filter_stride, mIn, mOut, input_features,
+                                 output_features, weight, bias, pack_t=None):
+    inp = _featc(input_features, "input_features")
+    tb = mIn.getFullConvolutionRuleBook(input_size, output_size, filter_size, filter_stride, mOut)
+    if tb.V_in == 0:                                    # no input site, no output site
+        output_features.resize_(0, weight.size(1) * weight.size(3))
+        return 0.0
+    # filter == stride: the regions are disjoint, every new site has one parent site at one offset
+    _conv_fwd(inp, output_features, tb.V_in, tb.inn, weight, bias, 0, pack_t,
+              single=_key(filter_size) == _key(filter_stride))
+    return _macs(tb, weight)
+
+
+def FullConvolution_backward(input_size, output_size, filter_size, filter_stride, mIn, mOut, input_features,
+                             d_input_features, d_output_features, weight, d_weight, d_bias, pack_t=None,
+                             need_d_input=True):
+    inp = _featc(input_features, "input_features")
+    d_out = _featc(d_output_features, "d_output_features")
+    tb = mIn.getFullConvolutionRuleBook(input_size, output_size, filter_size, filter_stride, mOut)
+    if tb.V_in == 0:
+        d_input_features.resize_(0, weight.size(1) * weight.size(2))
+        d_weight.zero_()
+        if d_bias is not None and d_bias.numel():
+            d_bias.zero_()
+        return
     if need_d_input:
         _conv_fwd(d_out, d_input_features, tb.V_out, tb.out, weight, None, 1, pack_t)
     _conv_dw(inp, d_out, tb.inn, d_weight, d_bias)

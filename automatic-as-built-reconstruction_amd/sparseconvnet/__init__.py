@@ -10,6 +10,7 @@ from .averagePooling import AveragePooling  # noqa: E402
 from .batchNormalization import BatchNormalization, BatchNormReLU, BatchNormLeakyReLU  # noqa: E402
 from .convolution import Convolution  # noqa: E402
 from .deconvolution import Deconvolution  # noqa: E402
+from .fullConvolution import FullConvolution, TransposeConvolution  # noqa: E402
 from .identity import Identity  # noqa: E402
 from .ioLayers import InputLayer, OutputLayer  # noqa: E402
 from .maxPooling import MaxPooling  # noqa: E402

@@ -1,5 +1,6 @@
-"""Shared machinery of the three sparse convolution layers (extension of this package's own making: the reference writes
-each layer out in full -- submanifoldConvolution.py:14-113, convolution.py:14-90, deconvolution.py:13-87 -- with its own
+"""Shared machinery of the sparse convolution layers -- SubmanifoldConvolution, Convolution, Deconvolution and
+FullConvolution (extension of this package's own making: the reference writes each layer out in full --
+submanifoldConvolution.py:14-113, convolution.py:14-90, deconvolution.py:13-87, fullConvolution.py:14-158 -- with its own
 autograd Function).  One Module base + ONE autograd Function, parameterised by a `_Kind` record that says how a layer maps
 spatial sizes and which pair of `SCN` entry points serves it.  What stays the reference's, because checkpoints, model code
 and `print(model)` depend on it: class names, constructor arguments, the attributes `dimension / groups / nIn / nOut /
@@ -39,6 +40,12 @@ KINDS = {
                     lambda g, md, x, y, w, b, pk: SCN.Deconvolution_updateOutput(g[0], g[1], g[2], g[3], md, x, y, w, b, pack_t=pk),
                     lambda g, md, x, dx, dy, w, dw, db, pk, need: SCN.Deconvolution_backward(
                         g[0], g[1], g[2], g[3], md, x, dx, dy, w, dw, db, pack_t=pk, need_d_input=need)),
+    # the transpose that GROWS the grid: `md` is the pair (input Metadata, the new Metadata the layer created)
+    "full": _Kind("FullConvolution", True, lambda sz, f, s: (sz - 1) * s + f, lambda sz, f, s: (sz - f) // s + 1,
+                  lambda g, md, x, y, w, b, pk: SCN.FullConvolution_updateOutput(g[0], g[1], g[2], g[3], md[0], md[1], x, y,
+                                                                                 w, b, pack_t=pk),
+                  lambda g, md, x, dx, dy, w, dw, db, pk, need: SCN.FullConvolution_backward(
+                      g[0], g[1], g[2], g[3], md[0], md[1], x, dx, dy, w, dw, db, pack_t=pk, need_d_input=need)),
 }
 
 
@@ -49,7 +56,7 @@ def _dims(t):
 
 
 class SparseConvModule(Module):
-    kind = None        # key of KINDS, set by the three public classes
+    kind = None        # key of KINDS, set by the public classes
 
     def _setup(self, dimension, nIn, nOut, filter_size, filter_stride, bias, groups):
         Module.__init__(self)

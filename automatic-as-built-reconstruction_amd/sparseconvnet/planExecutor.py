@@ -41,6 +41,7 @@ from .batchNormalization import BatchNormalization
 from .submanifoldConvolution import SubmanifoldConvolution
 from .convolution import Convolution
 from .deconvolution import Deconvolution
+from .fullConvolution import FullConvolution
 
 _ALIGN = 256
 BF16 = torch.bfloat16
@@ -353,6 +354,8 @@ class _Template(object):
             return self.conv(m, x)
         if isinstance(m, Deconvolution):
             return self.deconv(m, x)
+        if isinstance(m, FullConvolution):       # creates a Metadata of its own: its level is not part of a static plan
+            raise Unsupported("FullConvolution (it creates a new Metadata; run the network layer by layer)")
         raise Unsupported(type(m).__name__)
 
     def add(self, xs):

@@ -195,6 +195,17 @@ int aabr_brick_build(const int32_t *in_coords, int64_t vin_bound, const int32_t 
                      const int32_t *stride_host, const int32_t *out_spatial_host, const int32_t *dims_host, void *dir,
                      void *bricks, int64_t nb_cap, int32_t *bcoord, int32_t *out_coords, int64_t v_cap, int32_t *meta,
                      int32_t *scratch, int flags, void *stream);
+/* aabr_brick_full_build: the DILATING level build -- the level a FullConvolution / TransposeConvolution writes to, brick-major:
+ * one site at u * stride + q for every input site u and every filter offset q in [0, size) (the serial host loop of
+ * FullConvolution_InputSgToRulesAndOutputSg over a hash map, FullConvolutionRules.h:11-33, with InputRegionCalculator,
+ * RectangularRegions.h:95-105).  Arguments, outputs, scratch and flags as aabr_brick_build; out_spatial = the NEW level's
+ * spatial size (in - 1) * stride + size (<= 65535 per axis), a candidate outside it sets meta[2]; per-axis limits of
+ * aabr_brick_build; vin_bound * prod(size) must stay below 2^31.  Each parent site marks its prod(size) cells, then the same
+ * scans and expansion: no hash table, integer atomics only (the bit-setting OR), rows a function of the site set alone.   */
+int aabr_brick_full_build(const int32_t *in_coords, int64_t vin_bound, const int32_t *vin_count_dev,
+                          const int32_t *size_host, const int32_t *stride_host, const int32_t *out_spatial_host,
+                          const int32_t *dims_host, void *dir, void *bricks, int64_t nb_cap, int32_t *bcoord,
+                          int32_t *out_coords, int64_t v_cap, int32_t *meta, int32_t *scratch, int flags, void *stream);
 /* Input level: the voxel scatter numbers its sites in first-seen order (IOLayersRules.h:86-91); old_coords [V] are those
  * sites, (dir, bricks) the brick level built from them.  new_of_old[r] / old_of_new[i] = the permutation; first_pt /
  * cnt_extra / head re-indexed by the new rows; point_site2[p] = new row of point p's site.                           */
@@ -245,6 +256,20 @@ int aabr_convolution_sites(const int32_t *in_coords, int64_t V_in, const int32_t
                            uint64_t *out_keys, int64_t out_cap,
                            int32_t *scratch, int32_t *out_site_coords, int32_t *meta,
                            void *stream);
+/* FullConvolution / TransposeConvolution geometry -- replaces Metadata<3>::getFullConvolutionRuleBook ->
+ * FullConvolution_InputSgToRulesAndOutputSg (Metadata.cpp:511-531, FullConvolutionRules.h:11-33, RectangularRegions.h:95-105):
+ * the level that GROWS.  Creates the grid that holds one site at u * stride + q for every input site u and every filter
+ * offset q in [0, size); sites are numbered in first-seen order over input rows ascending, then offsets with z fastest
+ * (what an insertion-ordered map gives the reference's loop; samples stay contiguous and in batch order); V_out in meta[0].
+ * Arguments as aabr_convolution_sites with E = V_in * prod(size) candidates (E < 2^31): out_cap a power of two >= 1.5 E,
+ * scratch int32 [E + 4*ceil(E/256) + 16], out_site_coords int32 [E,4]; out_spatial = the new level's spatial size
+ * (in - 1) * stride + size, <= 65535 per axis -- a candidate outside it is left out and sets meta[2].  Per-axis limits of
+ * aabr_convolution_sites.  V_in = 0: the grid is cleared, meta[0] = 0, no launch.  The rule tables of the layer are
+ * aabr_convolution_tables2 with the new level as the convolution's INPUT side and the layer's input level as its output
+ * side: table_out is complete by construction, table_in is what the forward pass gathers through.                       */
+int aabr_full_convolution_sites(const int32_t *in_coords, int64_t V_in, const int32_t *size_host,
+                                const int32_t *stride_host, const int32_t *out_spatial_host, uint64_t *out_keys,
+                                int64_t out_cap, int32_t *scratch, int32_t *out_site_coords, int32_t *meta, void *stream);
 /* counts (optional): int32 [vol * ceil(V_out/256)] per-block rule counts, as above.
  * table_out[k*V_out + o] = input row at offset k of output o's window (or -1);
  * table_in [k*V_in  + u] = output row whose window holds input u at offset k (or -1).       */
