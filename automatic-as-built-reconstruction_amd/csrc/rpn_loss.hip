@@ -34,26 +34,11 @@ namespace aabr {
 
 namespace {
 
-// the batch's sums in example order, / N_s (0 / 0 = NaN for an empty sample, like the reference's mean of nothing)
-__global__ __launch_bounds__(64) void k_loss_finalize(int nb, const float *__restrict__ partial, int32_t *__restrict__ info,
-                                                      float *__restrict__ obj_loss, float *__restrict__ box_loss) {
-  if (threadIdx.x != 0) return;
-  float bce = 0.f, box = 0.f;
-  int ns = 0;
-  for (int e = 0; e < nb; ++e) {
-    bce += partial[2 * e];
-    box += partial[2 * e + 1];
-    ns += info[e * kInfoWords] + info[e * kInfoWords + 1];
-  }
-  *obj_loss = bce / (float)ns;
-  *box_loss = box / (float)ns;
-  for (int e = 0; e < nb; ++e) info[e * kInfoWords + 7] = ns;
-}
-
-// with groups: thread g adds the sums of group g's segments (scene * G + g) in scene order, / the group's N_s
-__global__ __launch_bounds__(64) void k_loss_finalize_grouped(int nb, int G, const float *__restrict__ partial,
-                                                              int32_t *__restrict__ info, float *__restrict__ obj_loss,
-                                                              float *__restrict__ box_loss) {
+// the sums in example order, / N_s (0 / 0 = NaN for an empty sample, like the reference's mean of nothing): thread g
+// adds group g's segments (scene * G + g) in scene order; G = 1 without groups, every example one segment
+__global__ __launch_bounds__(64) void k_loss_finalize(int nb, int G, const float *__restrict__ partial,
+                                                      int32_t *__restrict__ info, float *__restrict__ obj_loss,
+                                                      float *__restrict__ box_loss) {
   const int g = threadIdx.x;
   if (g >= G) return;
   float bce = 0.f, box = 0.f;
@@ -76,12 +61,11 @@ int run_select(LossParams &p, const char *fn, int nb, const int32_t *seg_begin_h
   int rc = run_select_chunks(p, fn, nb, seg_begin_host, site_begin_host, label_ptrs, target_ptrs, pos_masks, neg_masks, selected,
                              info, scratch, st);
   if (rc != AABR_OK) return rc;
-  if (p.with_loss && p.G)
-    hipLaunchKernelGGL(k_loss_finalize_grouped, dim3(1), dim3(64), 0, st, nb / p.G, p.G, select_partials(scratch, nb), info,
-                       obj_loss, box_loss);
-  else if (p.with_loss)
-    hipLaunchKernelGGL(k_loss_finalize, dim3(1), dim3(64), 0, st, nb, select_partials(scratch, nb), info, obj_loss,
+  if (p.with_loss) {
+    const int G = p.G > 1 ? p.G : 1;
+    hipLaunchKernelGGL(k_loss_finalize, dim3(1), dim3(64), 0, st, nb / G, G, select_partials(scratch, nb), info, obj_loss,
                        box_loss);
+  }
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }
@@ -177,7 +161,7 @@ int run_backward(LossParams &p, const GradPtrs &g, const char *fn, int nb, const
 }
 
 // a scene's rows of the two host tables repeated for its G segments; checks the groups' arguments
-int expand_group_tables(const char *fn, int n_maps, int nb, int G, const int32_t *seg_begin_host,
+int expand_group_tables(const char *fn, int n_maps, int A, int nb, int G, const int32_t *seg_begin_host,
                         const int32_t *site_begin_host, const int64_t *rows_host, LossParams &p, std::vector<int32_t> &seg,
                         std::vector<int32_t> &site) {
   AABR_CHECK_ARG_AS(fn, n_maps >= 1 && n_maps <= kAnchorMaxMaps && nb >= 1, "bad arguments (1 .. 8 maps, >= 1 scene)");
@@ -197,12 +181,27 @@ int expand_group_tables(const char *fn, int n_maps, int nb, int G, const int32_t
       for (int m = 0; m <= n_maps; ++m) seg[e * (n_maps + 1) + m] = seg_begin_host[(size_t)b * (n_maps + 1) + m];
       for (int m = 0; m < n_maps; ++m) {
         site[e * n_maps + m] = site_begin_host[(size_t)b * n_maps + m];
-        const int64_t sites = (seg[e * (n_maps + 1) + m + 1] - seg[e * (n_maps + 1) + m]) / (p.s.A > 0 ? p.s.A : 1);
+        const int64_t sites = (seg[e * (n_maps + 1) + m + 1] - seg[e * (n_maps + 1) + m]) / (A > 0 ? A : 1);
         AABR_CHECK_ARG_AS(fn, site[e * n_maps + m] >= 0 && site[e * n_maps + m] + sites <= rows_host[m],
                          "a scene's sites reach past the map's rows");
       }
     }
   return AABR_OK;
+}
+
+// the fields and per-map pointers the four loss entries share (n_maps has been checked).  A forward entry passes the
+// coords and no gradient table; a backward entry the gradient table, no coords, and 0 for the sampler's k_pos0 and seed
+void fill_loss_params(LossParams &p, GradPtrs *g, int n_maps, const void *const *coords_ptrs, const void *const *obj_ptrs,
+                      const void *const *reg_ptrs, void *const *grad_obj_ptrs, void *const *grad_reg_ptrs, int input_bf16,
+                      int num_anchors, int batch_size_per_image, int num_pos_max, uint32_t seed, float beta) {
+  p.s.n_maps = n_maps; p.s.A = num_anchors; p.with_loss = 1; p.bf16 = input_bf16 ? 1 : 0; p.B = batch_size_per_image;
+  p.k_pos0 = num_pos_max; p.seed = seed; p.beta = beta;
+  for (int m = 0; m < n_maps; ++m) {
+    p.obj[m] = obj_ptrs[m];
+    p.reg[m] = reg_ptrs[m];
+    if (coords_ptrs) p.coords[m] = (const int32_t *)coords_ptrs[m];
+    if (g) g->obj[m] = grad_obj_ptrs[m], g->reg[m] = grad_reg_ptrs[m];
+  }
 }
 
 }  // namespace
@@ -228,13 +227,8 @@ extern "C" int aabr_rpn_loss_forward(int n_maps, const void *const *coords_ptrs,
   AABR_CHECK_ARG(coords_ptrs && obj_ptrs && reg_ptrs && seg_begin_host && site_begin_host && label_ptrs && target_ptrs &&
                      selected && info && obj_loss && box_loss && scratch, "null pointer");
   LossParams p = {};
-  p.s.n_maps = n_maps; p.s.A = num_anchors; p.flat = 0; p.with_loss = 1; p.label_mode = 0; p.bf16 = input_bf16 ? 1 : 0;
-  p.k_pos0 = num_pos_max; p.B = batch_size_per_image; p.seed = seed; p.beta = beta;
-  for (int m = 0; m < n_maps; ++m) {
-    p.obj[m] = obj_ptrs[m];
-    p.reg[m] = reg_ptrs[m];
-    p.coords[m] = (const int32_t *)coords_ptrs[m];
-  }
+  fill_loss_params(p, nullptr, n_maps, coords_ptrs, obj_ptrs, reg_ptrs, nullptr, nullptr, input_bf16, num_anchors,
+                   batch_size_per_image, num_pos_max, seed, beta);
   return run_select(p, __func__, nb, seg_begin_host, site_begin_host, label_ptrs, target_ptrs, nullptr, nullptr, selected, info,
                     obj_loss, box_loss, scratch, (hipStream_t)stream_);
 }
@@ -251,15 +245,9 @@ extern "C" int aabr_rpn_loss_backward(int n_maps, const void *const *obj_ptrs, c
   AABR_CHECK_ARG(obj_ptrs && reg_ptrs && seg_begin_host && site_begin_host && target_ptrs && selected && info &&
                      grad_obj_loss && grad_box_loss && grad_obj_ptrs && grad_reg_ptrs, "null pointer");
   LossParams p = {};
-  p.s.n_maps = n_maps; p.s.A = num_anchors; p.with_loss = 1; p.bf16 = input_bf16 ? 1 : 0; p.B = batch_size_per_image;
-  p.beta = beta;
   GradPtrs g = {};
-  for (int m = 0; m < n_maps; ++m) {
-    p.obj[m] = obj_ptrs[m];
-    p.reg[m] = reg_ptrs[m];
-    g.obj[m] = grad_obj_ptrs[m];
-    g.reg[m] = grad_reg_ptrs[m];
-  }
+  fill_loss_params(p, &g, n_maps, nullptr, obj_ptrs, reg_ptrs, grad_obj_ptrs, grad_reg_ptrs, input_bf16, num_anchors,
+                   batch_size_per_image, 0, 0, beta);
   return run_backward(p, g, __func__, nb, seg_begin_host, site_begin_host, target_ptrs, selected, info, grad_obj_loss,
                       grad_box_loss, st);
 }
@@ -282,16 +270,12 @@ extern "C" int aabr_rpn_loss_grouped_forward(int n_maps, const void *const *coor
   AABR_CHECK_ARG(coords_ptrs && obj_ptrs && reg_ptrs && label_ptrs && target_ptrs && selected && info && obj_loss &&
                      box_loss && scratch, "null pointer");
   LossParams p = {};
-  p.s.n_maps = n_maps; p.s.A = num_anchors; p.flat = 0; p.with_loss = 1; p.label_mode = 0; p.bf16 = input_bf16 ? 1 : 0;
-  p.k_pos0 = num_pos_max; p.B = batch_size_per_image; p.seed = seed; p.beta = beta;
   std::vector<int32_t> seg, site;
-  const int rc = expand_group_tables(__func__, n_maps, nb, G, seg_begin_host, site_begin_host, rows_host, p, seg, site);
+  const int rc = expand_group_tables(__func__, n_maps, num_anchors, nb, G, seg_begin_host, site_begin_host, rows_host, p, seg,
+                                     site);
   if (rc != AABR_OK) return rc;
-  for (int m = 0; m < n_maps; ++m) {
-    p.obj[m] = obj_ptrs[m];
-    p.reg[m] = reg_ptrs[m];
-    p.coords[m] = (const int32_t *)coords_ptrs[m];
-  }
+  fill_loss_params(p, nullptr, n_maps, coords_ptrs, obj_ptrs, reg_ptrs, nullptr, nullptr, input_bf16, num_anchors,
+                   batch_size_per_image, num_pos_max, seed, beta);
   return run_select(p, __func__, nb * G, seg.data(), site.data(), label_ptrs, target_ptrs, nullptr, nullptr, selected, info,
                     obj_loss, box_loss, scratch, (hipStream_t)stream_);
 }
@@ -308,18 +292,13 @@ extern "C" int aabr_rpn_loss_grouped_backward(int n_maps, const void *const *obj
   AABR_CHECK_ARG(obj_ptrs && reg_ptrs && target_ptrs && selected && info && grad_obj_loss && grad_box_loss &&
                      grad_obj_ptrs && grad_reg_ptrs, "null pointer");
   LossParams p = {};
-  p.s.n_maps = n_maps; p.s.A = num_anchors; p.with_loss = 1; p.bf16 = input_bf16 ? 1 : 0; p.B = batch_size_per_image;
-  p.beta = beta;
-  std::vector<int32_t> seg, site;
-  const int rc = expand_group_tables(__func__, n_maps, nb, G, seg_begin_host, site_begin_host, rows_host, p, seg, site);
-  if (rc != AABR_OK) return rc;
   GradPtrs g = {};
-  for (int m = 0; m < n_maps; ++m) {
-    p.obj[m] = obj_ptrs[m];
-    p.reg[m] = reg_ptrs[m];
-    g.obj[m] = grad_obj_ptrs[m];
-    g.reg[m] = grad_reg_ptrs[m];
-  }
+  std::vector<int32_t> seg, site;
+  const int rc = expand_group_tables(__func__, n_maps, num_anchors, nb, G, seg_begin_host, site_begin_host, rows_host, p, seg,
+                                     site);
+  if (rc != AABR_OK) return rc;
+  fill_loss_params(p, &g, n_maps, nullptr, obj_ptrs, reg_ptrs, grad_obj_ptrs, grad_reg_ptrs, input_bf16, num_anchors,
+                   batch_size_per_image, 0, 0, beta);
   return run_backward(p, g, __func__, nb * G, seg.data(), site.data(), target_ptrs, selected, info, grad_obj_loss,
                       grad_box_loss, (hipStream_t)stream_);
 }

@@ -19,7 +19,7 @@ import torch
 import _hip
 import _nms
 from _hip import check, ptr
-from rpn_glue import _Cfg
+from rpn_glue import _Cfg, draw_seed, parse_yaw_loss_mode
 
 def coder_args(box_coder):
     """(weights [7 floats], bbox_xform_clip, corner form 0 / 1) of a BoxCoder3D-like object: what the target and the
@@ -107,30 +107,41 @@ def box_detections(class_logits, box_regression, proposals, score_thresh=0.05, n
         raise ValueError("the proposals have %d rows, class_logits %d" % (sum(n_b), N))
     props = (torch.cat([p.reshape(-1, 7) for p in proposals]) if nb else logits.new_zeros((0, 7)))
     props = props.to(device=dev, dtype=torch.float32).contiguous()
+    head = (ptr(logits), ptr(reg), ptr(props), nb, (C.c_int64 * nb)(*n_b), nc, int(bool(class_specific)))
+    return _detections("box_detections", "(2 <= classes <= 32, 1 <= scenes <= 16): C=%d nb=%d",
+                       lib.aabr_roi_post_detections_coder, head, dev, n_b, nc, (nc - 1) * POST_NMS, (N, nc, 7),
+                       score_thresh, nms, nms_aug_thickness, detections_per_img, weights, bbox_xform_clip, box_coder, defer,
+                       debug)
+
+
+def _detections(fn, limits, entry, head, dev, n_b, nc, cap, boxes_shape, score_thresh, nms, nms_aug_thickness,
+                detections_per_img, weights, bbox_xform_clip, box_coder, defer, debug):
+    """what box_detections and box_detections_grouped (`fn`, for the message) share: the coder's arguments, the scratch
+    for `nc` columns, the outputs with `cap` rows per scene, the debug buffers (`boxes_shape`: of the decoded boxes), the
+    library call `entry(*head, <the common tail>)` and the finish()"""
+    lib = _hip.load()
+    nb, N = len(n_b), sum(n_b)
     aug = (0.0, 0.0) if nms_aug_thickness is None else nms_aug_thickness
     w = (1.0,) * 7 if weights is None else [float(v) for v in torch.as_tensor(weights).reshape(-1).tolist()]
     corner = 0
     if box_coder is not None:
         w, bbox_xform_clip, corner = coder_args(box_coder)
-    cap = (nc - 1) * POST_NMS
     words = int(lib.aabr_roi_post_scratch_words(nb, max(n_b) if n_b else 0, nc, PRE_NMS))
     if words < 0:
-        raise _hip.AabrError("box_detections: unsupported shape (2 <= classes <= 32, 1 <= scenes <= 16): C=%d nb=%d"
-                             % (nc, nb))
+        raise _hip.AabrError("%s: unsupported shape %s" % (fn, limits % (nc, nb)))
     scratch = _hip.workspace("roi_post", words + 2, torch.int32, dev)
     off = (-scratch.data_ptr() // 4) % 2                                  # 8-byte alignment of the first word
     prob = boxes = None
     if debug is not None:
         prob = torch.empty((N, nc), dtype=torch.float32, device=dev)
-        boxes = torch.empty((N, nc, 7), dtype=torch.float32, device=dev)
+        boxes = torch.empty(boxes_shape, dtype=torch.float32, device=dev)
     det_rows = torch.empty((nb, cap), dtype=torch.int64, device=dev)
     det_labels = torch.empty((nb, cap), dtype=torch.int64, device=dev)
     det_scores = torch.empty((nb, cap), dtype=torch.float32, device=dev)
     det_boxes = torch.empty((nb, cap, 7), dtype=torch.float32, device=dev)
     info = torch.empty((nb, INFO_WORDS), dtype=torch.int32, device=dev)
-    check(lib.aabr_roi_post_detections_coder(
-        ptr(logits), ptr(reg), ptr(props), nb, (C.c_int64 * nb)(*n_b), nc, int(bool(class_specific)), _hip.f32xn(w),
-        corner, float(bbox_xform_clip), float(score_thresh), float(nms), float(aug[0]), float(aug[1]),
+    check(entry(
+        *head, _hip.f32xn(w), corner, float(bbox_xform_clip), float(score_thresh), float(nms), float(aug[0]), float(aug[1]),
         int(_nms.REFERENCE_DEBUG_ONLY_XY), PRE_NMS, POST_NMS, int(detections_per_img), ptr(prob), ptr(boxes),
         ptr(det_rows), ptr(det_labels), ptr(det_scores), ptr(det_boxes), ptr(info), scratch.data_ptr() + 4 * off,
         _hip.stream()))
@@ -149,6 +160,41 @@ def box_detections(class_logits, box_regression, proposals, score_thresh=0.05, n
         return out
 
     return finish if defer else finish()
+
+
+def _targets_inputs(proposals, targets, target_labels, aug_thickness, weights, box_coder, seed):
+    """the prologue box_head_targets and box_head_targets_grouped share (at least one scene): the scenes' rows
+    concatenated and cast, the clamp list, the coder's arguments and the seed ->
+    (dev, n_b, g_b, props, tg, tl, aug, w, corner, seed)"""
+    _hip.require_gpu(proposals[0])
+    dev = proposals[0].device
+    n_b = [int(p.shape[0]) for p in proposals]
+    g_b = [int(t.shape[0]) for t in targets]
+    if any(int(l.numel()) != g for l, g in zip(target_labels, g_b)):
+        raise ValueError("target_labels do not match the targets")
+    props = torch.cat([p.reshape(-1, 7) for p in proposals]).to(device=dev, dtype=torch.float32).contiguous()
+    tg = torch.cat([t.reshape(-1, 7) for t in targets]).to(device=dev, dtype=torch.float32).contiguous()
+    tl = torch.cat([l.reshape(-1) for l in target_labels]).to(device=dev, dtype=torch.int64).contiguous()
+    aug = aug_thickness or {}
+    aug = [float(aug.get(k, 0.0)) for k in ("target_Y", "target_Z", "anchor_Y", "anchor_Z")]
+    w = (1.0,) * 7 if weights is None else [float(v) for v in torch.as_tensor(weights).reshape(-1).tolist()]
+    corner = 0
+    if box_coder is not None:
+        w, _clip, corner = coder_args(box_coder)
+    return dev, n_b, g_b, props, tg, tl, aug, w, corner, int(draw_seed() if seed is None else seed) & 0xffffffff
+
+
+def _targets_buffers(N, S, B, words, dev):
+    """the per-proposal arrays over N rows and the padded samples of S segments, keyed as `debug` receives them (and in
+    the order the library takes them), and the address of the aligned scratch of `words` words"""
+    scratch = _hip.workspace("roi_targets", words + 2, torch.int32, dev)
+    off = (-scratch.data_ptr() // 4) % 2                                  # 8-byte alignment of the first word
+    i64, f32 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float32, device=dev)
+    bufs = {"matched_idx": torch.empty(N, **i64), "matched_val": torch.empty(N, **f32),
+            "labels": torch.empty(N, **i64), "regression_targets": torch.empty((N, 7), **f32),
+            "samp_rows": torch.empty((S, B), **i64), "samp_labels": torch.empty((S, B), **i64),
+            "samp_targets": torch.empty((S, B, 7), **f32), "samp_boxes": torch.empty((S, B, 7), **f32)}
+    return bufs, scratch.data_ptr() + 4 * off
 
 
 def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, aug_thickness=None,
@@ -178,51 +224,28 @@ def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, 
     matched target, ordered by (matched target, row) --, `pos_pos` int64 [p] (positions in the scene's sample),
     `connect_ids` int32 [2 p, 8] and `corner_xyz` fp32 [2 p, 3]; `debug` also receives `tg_xyz`, `tg_connect` and
     `corner_info`.  The sample is the same with and without the flag."""
-    from rpn_glue import draw_seed
     lib = _hip.load()
     nb = len(proposals)
     if not (nb == len(targets) == len(target_labels)):
         raise ValueError("proposals, targets and target_labels differ in length")
     if nb == 0:
         return (lambda: []) if defer else []
-    _hip.require_gpu(proposals[0])
-    dev = proposals[0].device
-    n_b = [int(p.shape[0]) for p in proposals]
-    g_b = [int(t.shape[0]) for t in targets]
-    if any(int(l.numel()) != g for l, g in zip(target_labels, g_b)):
-        raise ValueError("target_labels do not match the targets")
-    props = torch.cat([p.reshape(-1, 7) for p in proposals]).to(device=dev, dtype=torch.float32).contiguous()
-    tg = torch.cat([t.reshape(-1, 7) for t in targets]).to(device=dev, dtype=torch.float32).contiguous()
-    tl = torch.cat([l.reshape(-1) for l in target_labels]).to(device=dev, dtype=torch.int64).contiguous()
-    N, B = sum(n_b), int(batch_size_per_image)
-    aug = aug_thickness or {}
-    aug = [float(aug.get(k, 0.0)) for k in ("target_Y", "target_Z", "anchor_Y", "anchor_Z")]
-    w = (1.0,) * 7 if weights is None else [float(v) for v in torch.as_tensor(weights).reshape(-1).tolist()]
-    corner = 0
-    if box_coder is not None:
-        w, _clip, corner = coder_args(box_coder)
+    dev, n_b, g_b, props, tg, tl, aug, w, corner, seed = _targets_inputs(proposals, targets, target_labels, aug_thickness,
+                                                                         weights, box_coder, seed)
+    B = int(batch_size_per_image)
     words = int(lib.aabr_roi_targets_scratch_words(nb))
     if words < 0:
         raise _hip.AabrError("box_head_targets: 1 <= scenes <= 16, got %d" % nb)
-    scratch = _hip.workspace("roi_targets", words + 2, torch.int32, dev)
-    off = (-scratch.data_ptr() // 4) % 2                                  # 8-byte alignment of the first word
-    midx = torch.empty(N, dtype=torch.int64, device=dev)
-    mval = torch.empty(N, dtype=torch.float32, device=dev)
-    labels = torch.empty(N, dtype=torch.int64, device=dev)
-    regt = torch.empty((N, 7), dtype=torch.float32, device=dev)
+    bufs, scratch = _targets_buffers(sum(n_b), nb, B, words, dev)
+    midx, mval, labels, regt, s_rows, s_labels, s_targets, s_boxes = bufs.values()
     iou = torch.empty(sum(n * g for n, g in zip(n_b, g_b)), dtype=torch.float32, device=dev) if debug is not None else None
-    s_rows = torch.empty((nb, B), dtype=torch.int64, device=dev)
-    s_labels = torch.empty((nb, B), dtype=torch.int64, device=dev)
-    s_targets = torch.empty((nb, B, 7), dtype=torch.float32, device=dev)
-    s_boxes = torch.empty((nb, B, 7), dtype=torch.float32, device=dev)
     infos = torch.empty((2 if corner_groups else 1, nb, INFO_WORDS), dtype=torch.int32, device=dev)
     info = infos[0]
-    seed = int(draw_seed() if seed is None else seed) & 0xffffffff
     check(lib.aabr_roi_targets_coder(
         ptr(props), ptr(tg), ptr(tl), nb, _hip.i64xn(n_b), _hip.i64xn(g_b), _hip.f32x4(aug), -1,
         int(_nms.REFERENCE_DEBUG_ONLY_XY), float(fg_iou), float(bg_iou), _hip.f32xn(w), corner, seed, B,
         int(B * positive_fraction), ptr(midx), ptr(mval), ptr(labels), ptr(regt), ptr(iou), ptr(s_rows), ptr(s_labels),
-        ptr(s_targets), ptr(s_boxes), ptr(info), scratch.data_ptr() + 4 * off, _hip.stream()))
+        ptr(s_targets), ptr(s_boxes), ptr(info), scratch, _hip.stream()))
     if corner_groups:
         G = sum(g_b)
         tg_xyz = torch.empty((2 * G, 3), dtype=torch.float32, device=dev)
@@ -236,8 +259,7 @@ def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, 
         if debug is not None:
             debug.update(tg_xyz=tg_xyz, tg_connect=tg_connect)
     if debug is not None:
-        debug.update(matched_idx=midx, matched_val=mval, labels=labels, regression_targets=regt, samp_rows=s_rows,
-                     samp_labels=s_labels, samp_targets=s_targets, samp_boxes=s_boxes, seed=seed)
+        debug.update(bufs, seed=seed)
         mats, o = [], 0
         for n, g in zip(n_b, g_b):
             mats.append(iou[o:o + n * g].view(g, n))
@@ -394,7 +416,6 @@ def box_head_loss(class_logits, box_regression, labels, regression_targets, clas
     label outside [0, C) adds nothing, gets zero gradients and raises the flag: `return_flag=True` appends the 0-dim
     int32 device tensor (1 = some label was out of range) for the caller to read with the losses
     (FastRCNNLossComputation.__call__ keeps it as `last_flag`)."""
-    from rpn_glue import parse_yaw_loss_mode
     parse_yaw_loss_mode(yaw_loss_mode)
     _hip.require_gpu(class_logits)
     if class_logits.dim() != 2 or box_regression.dim() != 2:
@@ -464,7 +485,6 @@ def box_head_targets_grouped(proposals, sep_sizes, targets, target_labels, group
     ascending row.  `defer` / `debug` as box_head_targets; `debug` receives `matched_idx` (rows of the scene's own
     ground-truth list), `matched_val`, `labels`, `regression_targets`, the padded `samp_*` [scenes G, B, ...], `gt_keys`,
     `gt_perm`, `seed` and `info` [scenes G][8] after the read.  The IoU matrices are not stored in this form."""
-    from rpn_glue import draw_seed
     gc, _c_tot, class_nums, cols = sep_group_tables(groups)
     G = len(gc)
     nb = len(proposals)
@@ -482,46 +502,22 @@ def box_head_targets_grouped(proposals, sep_sizes, targets, target_labels, group
     if any(sum(n_s[b * G:(b + 1) * G]) != n_b[b] for b in range(nb)):
         raise ValueError("sep_sizes do not add up to the scenes' proposal counts")
     lib = _hip.load()
-    _hip.require_gpu(proposals[0])
-    dev = proposals[0].device
-    g_b = [int(t.shape[0]) for t in targets]
-    if any(int(l.numel()) != g for l, g in zip(target_labels, g_b)):
-        raise ValueError("target_labels do not match the targets")
-    props = torch.cat([p.reshape(-1, 7) for p in proposals]).to(device=dev, dtype=torch.float32).contiguous()
-    tg = torch.cat([t.reshape(-1, 7) for t in targets]).to(device=dev, dtype=torch.float32).contiguous()
-    tl = torch.cat([l.reshape(-1) for l in target_labels]).to(device=dev, dtype=torch.int64).contiguous()
-    N, B = sum(n_b), int(batch_size_per_image)
-    aug = aug_thickness or {}
-    aug = [float(aug.get(k, 0.0)) for k in ("target_Y", "target_Z", "anchor_Y", "anchor_Z")]
-    w = (1.0,) * 7 if weights is None else [float(v) for v in torch.as_tensor(weights).reshape(-1).tolist()]
-    corner = 0
-    if box_coder is not None:
-        w, _clip, corner = coder_args(box_coder)
+    dev, n_b, g_b, props, tg, tl, aug, w, corner, seed = _targets_inputs(proposals, targets, target_labels, aug_thickness,
+                                                                         weights, box_coder, seed)
+    B = int(batch_size_per_image)
     keys = torch.empty(sum(g_b), dtype=torch.int64, device=dev)
     check(lib.aabr_roi_gt_group_keys(ptr(tl), nb, _hip.i64xn(g_b), G, _c_tot, class_nums, cols, ptr(keys), _hip.stream()))
     keys, perm = torch.sort(keys, stable=True)                            # the one sort: (segment, group-local label, row)
-    words = int(lib.aabr_roi_targets_scratch_words(S))
-    scratch = _hip.workspace("roi_targets", words + 2, torch.int32, dev)
-    off = (-scratch.data_ptr() // 4) % 2                                  # 8-byte alignment of the first word
-    midx = torch.empty(N, dtype=torch.int64, device=dev)
-    mval = torch.empty(N, dtype=torch.float32, device=dev)
-    labels = torch.empty(N, dtype=torch.int64, device=dev)
-    regt = torch.empty((N, 7), dtype=torch.float32, device=dev)
-    s_rows = torch.empty((S, B), dtype=torch.int64, device=dev)
-    s_labels = torch.empty((S, B), dtype=torch.int64, device=dev)
-    s_targets = torch.empty((S, B, 7), dtype=torch.float32, device=dev)
-    s_boxes = torch.empty((S, B, 7), dtype=torch.float32, device=dev)
+    bufs, scratch = _targets_buffers(sum(n_b), S, B, int(lib.aabr_roi_targets_scratch_words(S)), dev)
+    midx, mval, labels, regt, s_rows, s_labels, s_targets, s_boxes = bufs.values()
     info = torch.empty((S, INFO_WORDS), dtype=torch.int32, device=dev)
-    seed = int(draw_seed() if seed is None else seed) & 0xffffffff
     check(lib.aabr_roi_targets_grouped(
         ptr(props), ptr(tg), ptr(keys), ptr(perm), nb, G, _hip.i64xn(n_s), _hip.i64xn(g_b), _hip.f32x4(aug), -1,
         int(_nms.REFERENCE_DEBUG_ONLY_XY), float(fg_iou), float(bg_iou), _hip.f32xn(w), corner, seed, B,
         int(B * positive_fraction), ptr(midx), ptr(mval), ptr(labels), ptr(regt), ptr(s_rows), ptr(s_labels),
-        ptr(s_targets), ptr(s_boxes), ptr(info), scratch.data_ptr() + 4 * off, _hip.stream()))
+        ptr(s_targets), ptr(s_boxes), ptr(info), scratch, _hip.stream()))
     if debug is not None:
-        debug.update(matched_idx=midx, matched_val=mval, labels=labels, regression_targets=regt, samp_rows=s_rows,
-                     samp_labels=s_labels, samp_targets=s_targets, samp_boxes=s_boxes, seed=seed, gt_keys=keys,
-                     gt_perm=perm)
+        debug.update(bufs, seed=seed, gt_keys=keys, gt_perm=perm)
 
     def finish():
         counts = _hip.read_back(info)                                     # the one read of the stage
@@ -592,7 +588,6 @@ def box_head_loss_grouped(class_logits, box_regression, sep_id, labels, regressi
     fp32 device tensors with autograd to both inputs -- the gradient of a column outside a row's group is an exact 0; no
     host read; 2 launches forward, 1 backward; bit-identical run to run.  A sep_id outside [0, G) or a label outside the
     group's range adds nothing, gets zero gradients and raises the flag (`return_flag=True` appends it)."""
-    from rpn_glue import parse_yaw_loss_mode
     parse_yaw_loss_mode(yaw_loss_mode)
     gc, c_tot, class_nums, cols = sep_group_tables(groups)
     if class_logits.dim() != 2 or box_regression.dim() != 2:
@@ -650,47 +645,11 @@ def box_detections_grouped(class_logits, box_regression, proposals, sep_id, grou
         raise ValueError("the proposals have %d rows, sep_id %d, class_logits %d" % (sum(n_b), sep_id.numel(), N))
     props = torch.cat([p.reshape(-1, 7) for p in proposals]).to(device=dev, dtype=torch.float32).contiguous()
     sid = sep_id.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
-    aug = (0.0, 0.0) if nms_aug_thickness is None else nms_aug_thickness
-    w = (1.0,) * 7 if weights is None else [float(v) for v in torch.as_tensor(weights).reshape(-1).tolist()]
-    corner = 0
-    if box_coder is not None:
-        w, bbox_xform_clip, corner = coder_args(box_coder)
-    cap = (c_tot - G) * POST_NMS
-    words = int(lib.aabr_roi_post_scratch_words(nb, max(n_b) if n_b else 0, c_tot, PRE_NMS))
-    if words < 0:
-        raise _hip.AabrError("box_detections_grouped: unsupported shape (1 <= scenes <= 16): C_tot=%d nb=%d" % (c_tot, nb))
-    scratch = _hip.workspace("roi_post", words + 2, torch.int32, dev)
-    off = (-scratch.data_ptr() // 4) % 2                                  # 8-byte alignment of the first word
-    prob = boxes = None
-    if debug is not None:
-        prob = torch.empty((N, c_tot), dtype=torch.float32, device=dev)
-        boxes = torch.empty((N, 7), dtype=torch.float32, device=dev)
-    det_rows = torch.empty((nb, cap), dtype=torch.int64, device=dev)
-    det_labels = torch.empty((nb, cap), dtype=torch.int64, device=dev)
-    det_scores = torch.empty((nb, cap), dtype=torch.float32, device=dev)
-    det_boxes = torch.empty((nb, cap, 7), dtype=torch.float32, device=dev)
-    info = torch.empty((nb, INFO_WORDS), dtype=torch.int32, device=dev)
-    check(lib.aabr_roi_post_detections_grouped(
-        ptr(logits), ptr(reg), ptr(props), ptr(sid), nb, _hip.i64xn(n_b), G, c_tot, class_nums, cols, _hip.f32xn(w),
-        corner, float(bbox_xform_clip), float(score_thresh), float(nms), float(aug[0]), float(aug[1]),
-        int(_nms.REFERENCE_DEBUG_ONLY_XY), PRE_NMS, POST_NMS, int(detections_per_img), ptr(prob), ptr(boxes),
-        ptr(det_rows), ptr(det_labels), ptr(det_scores), ptr(det_boxes), ptr(info), scratch.data_ptr() + 4 * off,
-        _hip.stream()))
-    if debug is not None:
-        debug["prob"], debug["boxes"] = prob, boxes
-
-    def finish():
-        counts = _hip.read_back(info)                                     # the one read of the stage
-        if debug is not None:
-            debug["info"] = counts
-        out = []
-        for b in range(nb):
-            m = counts[b][0]
-            out.append({"bbox3d": det_boxes[b, :m], "scores": det_scores[b, :m], "labels": det_labels[b, :m],
-                        "rows": det_rows[b, :m]})
-        return out
-
-    return finish if defer else finish()
+    head = (ptr(logits), ptr(reg), ptr(props), ptr(sid), nb, _hip.i64xn(n_b), G, c_tot, class_nums, cols)
+    return _detections("box_detections_grouped", "(1 <= scenes <= 16): C_tot=%d nb=%d",
+                       lib.aabr_roi_post_detections_grouped, head, dev, n_b, c_tot, (c_tot - G) * POST_NMS, (N, 7),
+                       score_thresh, nms, nms_aug_thickness, detections_per_img, weights, bbox_xform_clip, box_coder, defer,
+                       debug)
 
 
 POOL_MAX_LEVELS = 8          # csrc/roi_pool.hip kPoolMaxLevels: the level table travels in the kernel arguments

@@ -563,26 +563,32 @@ _BF16_OR_F32 = (torch.float32, torch.bfloat16)
 
 
 class _RpnLoss(torch.autograd.Function):
+    """aabr_rpn_loss_*: one segment per example, losses 0-dim; with cfg["G"] (aabr_rpn_loss_grouped_*) one segment per
+    (scene, group), the inputs group-major, losses [G]"""
+
     @staticmethod
     def forward(ctx, cfg, *tensors):
         lib = _hip.load()
-        n_maps = cfg["n_maps"]
+        n_maps, G = cfg["n_maps"], cfg["G"]
         obj, reg = tensors[:n_maps], tensors[n_maps:]
         dev = obj[0].device
         bf16 = int(obj[0].dtype == torch.bfloat16)
         nb, B = cfg["nb"], cfg["B"]
-        obj_c = [o.reshape(-1).contiguous() for o in obj]
-        reg_c = [r.reshape(-1, 7).contiguous() for r in reg]
-        sel = torch.empty((nb, B), dtype=torch.int64, device=dev)
-        info = torch.empty((nb, 8), dtype=torch.int32, device=dev)
-        obj_loss = torch.empty((), dtype=torch.float32, device=dev)
-        box_loss = torch.empty((), dtype=torch.float32, device=dev)
-        scr = _hip.workspace("rpn_loss", int(lib.aabr_rpn_loss_scratch_words(nb)) + 2, torch.int32, dev)
+        lead, ns = ((), nb) if G is None else ((G,), nb * G)
+        obj_c = [o.reshape(lead + (-1,)).contiguous() for o in obj]
+        reg_c = [r.reshape(lead + (-1, 7)).contiguous() for r in reg]
+        sel = torch.empty((ns, B), dtype=torch.int64, device=dev)
+        info = torch.empty((ns, 8), dtype=torch.int32, device=dev)
+        obj_loss = torch.empty(lead, dtype=torch.float32, device=dev)
+        box_loss = torch.empty(lead, dtype=torch.float32, device=dev)
+        words = lib.aabr_rpn_loss_scratch_words(nb) if G is None else lib.aabr_rpn_loss_grouped_scratch_words(nb, G)
+        scr = _hip.workspace("rpn_loss", int(words) + 2, torch.int32, dev)
         so = (-scr.data_ptr() // 4) % 2
-        check(lib.aabr_rpn_loss_forward(
-            n_maps, _hip.ptrs(cfg["coords"]), _hip.ptrs(obj_c), _hip.ptrs(reg_c), bf16, cfg["A"], nb, cfg["seg"],
-            cfg["site"], _hip.ptrs(cfg["labels"]), _hip.ptrs(cfg["targets"]), cfg["seed"], B, cfg["num_pos"], cfg["beta"],
-            ptr(sel), ptr(info), ptr(obj_loss), ptr(box_loss), scr.data_ptr() + 4 * so, stream()))
+        forward = lib.aabr_rpn_loss_forward if G is None else lib.aabr_rpn_loss_grouped_forward
+        check(forward(
+            n_maps, _hip.ptrs(cfg["coords"]), _hip.ptrs(obj_c), _hip.ptrs(reg_c), *cfg["rows"], bf16, cfg["A"], nb, *lead,
+            cfg["seg"], cfg["site"], _hip.ptrs(cfg["labels"]), _hip.ptrs(cfg["targets"]), cfg["seed"], B, cfg["num_pos"],
+            cfg["beta"], ptr(sel), ptr(info), ptr(obj_loss), ptr(box_loss), scr.data_ptr() + 4 * so, stream()))
         ctx.cfg = cfg
         ctx.save_for_backward(sel, info, *obj_c, *reg_c)
         ctx.shapes = [t.shape for t in tensors]
@@ -593,20 +599,58 @@ class _RpnLoss(torch.autograd.Function):
     def backward(ctx, g_obj, g_box, _g_sel, _g_info):
         lib = _hip.load()
         cfg = ctx.cfg
-        n_maps = cfg["n_maps"]
+        n_maps, G = cfg["n_maps"], cfg["G"]
         saved = ctx.saved_tensors
         sel, info, obj_c, reg_c = saved[0], saved[1], saved[2:2 + n_maps], saved[2 + n_maps:]
         dev, dt = obj_c[0].device, obj_c[0].dtype
-        g_obj = (g_obj if g_obj is not None else torch.zeros((), device=dev)).float().contiguous()
-        g_box = (g_box if g_box is not None else torch.zeros((), device=dev)).float().contiguous()
+        lead = () if G is None else (G,)
+        g_obj = (g_obj if g_obj is not None else torch.zeros(lead, device=dev)).float().contiguous()
+        g_box = (g_box if g_box is not None else torch.zeros(lead, device=dev)).float().contiguous()
         sizes = [o.numel() for o in obj_c] + [r.numel() for r in reg_c]
         flat = torch.zeros(sum(sizes), dtype=dt, device=dev)       # one fill for every gradient
         grads = list(torch.split(flat, sizes))
-        check(lib.aabr_rpn_loss_backward(
-            n_maps, _hip.ptrs(obj_c), _hip.ptrs(reg_c), int(dt == torch.bfloat16), cfg["A"], cfg["nb"], cfg["seg"],
-            cfg["site"], _hip.ptrs(cfg["targets"]), cfg["B"], cfg["beta"], ptr(sel), ptr(info), ptr(g_obj), ptr(g_box),
-            _hip.ptrs(grads[:n_maps]), _hip.ptrs(grads[n_maps:]), stream()))
+        backward = lib.aabr_rpn_loss_backward if G is None else lib.aabr_rpn_loss_grouped_backward
+        check(backward(
+            n_maps, _hip.ptrs(obj_c), _hip.ptrs(reg_c), *cfg["rows"], int(dt == torch.bfloat16), cfg["A"], cfg["nb"], *lead,
+            cfg["seg"], cfg["site"], _hip.ptrs(cfg["targets"]), cfg["B"], cfg["beta"], ptr(sel), ptr(info), ptr(g_obj),
+            ptr(g_box), _hip.ptrs(grads[:n_maps]), _hip.ptrs(grads[n_maps:]), stream()))
         return (None,) + tuple(g.view(s) for g, s in zip(grads, ctx.shapes))
+
+
+def _rpn_loss_cfg(maps, objectness, box_regression, labels, base_anchors, G, batch_size_per_image, positive_fraction,
+                  yaw_loss_mode, seed):
+    """the checks and tables rpn_loss (G None: a segment is an example) and rpn_loss_grouped (a segment is (scene,
+    group), len(labels) a multiple of G) share -> _RpnLoss's cfg"""
+    parse_yaw_loss_mode(yaw_loss_mode)
+    n_maps, ng = len(maps), G or 1
+    if not (n_maps == len(objectness) == len(box_regression) == len(base_anchors)):
+        raise ValueError("maps, objectness, box_regression and base_anchors differ in length")
+    nb = len(labels) // ng
+    if any(len(l) < 4 or l[3] is None for l in labels):
+        raise ValueError("labels need the regression targets: rpn_label_matches%s(..., regression_targets=True)"
+                         % ("" if G is None else "_grouped"))
+    dt = objectness[0].dtype
+    if dt not in _BF16_OR_F32 or any(t.dtype != dt for t in list(objectness) + list(box_regression)):
+        raise TypeError("objectness and box_regression must all be float32, or all bfloat16")
+    grids = [t.metadata.grids[_SCN._key(t.spatial_size)] for t in maps]
+    A = int(base_anchors[0].shape[0])
+    counts = _site_counts(grids, nb, objectness[0].device)
+    V = [sum(c) for c in counts]
+    for m in range(n_maps):
+        if objectness[m].numel() != ng * V[m] * A or box_regression[m].numel() != ng * V[m] * A * 7:
+            raise ValueError("map %d: objectness / box_regression do not hold %s%d sites x %d anchors"
+                             % (m, "" if G is None else "%d groups x " % G, V[m], A))
+    seg, site, n_anchor = _anchor_tables(counts, A, 0, nb)
+    for e in range(nb * ng):
+        if labels[e][0].numel() != n_anchor[e // ng] or labels[e][3].shape[0] != n_anchor[e // ng]:
+            raise ValueError("%s %d: the labels do not match the maps' anchors" % ("example" if G is None else "segment", e))
+    lab = [l[0] if l[0].dtype == torch.int64 else l[0].long() for l in labels]
+    return {"n_maps": n_maps, "nb": nb, "G": G, "A": A, "B": int(batch_size_per_image),
+            "num_pos": int(batch_size_per_image * positive_fraction), "beta": 1.0 / 9,
+            "seed": int(draw_seed() if seed is None else seed) & 0xffffffff,
+            "rows": () if G is None else (_hip.i64xn(V),),                 # the grouped entries' rows_host argument
+            "coords": [g.coords for g in grids], "seg": _hip.i32xn(seg), "site": _hip.i32xn(site),
+            "labels": [l.contiguous() for l in lab], "targets": [l[3].float().contiguous() for l in labels]}
 
 
 def rpn_loss(maps, objectness, box_regression, labels, base_anchors, batch_size_per_image=256, positive_fraction=0.5,
@@ -628,89 +672,13 @@ def rpn_loss(maps, objectness, box_regression, labels, base_anchors, batch_size_
     `return_samples` also the int64 [nb, batch_size_per_image] selected indices into the concatenated label lists
     (example-major), positives then negatives, -1 padded; with `return_info` then the int32 [nb, 8] info words of
     aabr_rpn_loss_forward (num_pos, num_neg, P, N, candidates, overflow, N_s)."""
-    parse_yaw_loss_mode(yaw_loss_mode)
-    n_maps = len(maps)
-    if not (n_maps == len(objectness) == len(box_regression) == len(base_anchors)):
-        raise ValueError("maps, objectness, box_regression and base_anchors differ in length")
-    nb = len(labels)
-    if nb == 0:
+    if len(labels) == 0:
         raise ValueError("no examples")
-    if any(len(l) < 4 or l[3] is None for l in labels):
-        raise ValueError("labels need the regression targets: rpn_label_matches(..., regression_targets=True)")
-    dt = objectness[0].dtype
-    if dt not in _BF16_OR_F32 or any(t.dtype != dt for t in list(objectness) + list(box_regression)):
-        raise TypeError("objectness and box_regression must all be float32, or all bfloat16")
-    grids = [t.metadata.grids[_SCN._key(t.spatial_size)] for t in maps]
-    dev = objectness[0].device
-    A = int(base_anchors[0].shape[0])
-    counts = _site_counts(grids, nb, dev)
-    for m in range(n_maps):
-        V = sum(counts[m])
-        if objectness[m].numel() != V * A or box_regression[m].numel() != V * A * 7:
-            raise ValueError("map %d: objectness / box_regression do not hold %d sites x %d anchors" % (m, V, A))
-    seg, site, n_anchor = _anchor_tables(counts, A, 0, nb)
-    for bi in range(nb):
-        if labels[bi][0].numel() != n_anchor[bi] or labels[bi][3].shape[0] != n_anchor[bi]:
-            raise ValueError("example %d: the labels do not match the maps' anchors" % bi)
-    lab = [l[0] if l[0].dtype == torch.int64 else l[0].long() for l in labels]
-    tgt = [l[3].float().contiguous() for l in labels]
-    cfg = {"n_maps": n_maps, "nb": nb, "A": A, "B": int(batch_size_per_image),
-           "num_pos": int(batch_size_per_image * positive_fraction), "beta": 1.0 / 9,
-           "seed": int(draw_seed() if seed is None else seed) & 0xffffffff,
-           "coords": [g.coords for g in grids], "seg": _hip.i32xn(seg), "site": _hip.i32xn(site),
-           "labels": [l.contiguous() for l in lab], "targets": tgt}
+    cfg = _rpn_loss_cfg(maps, objectness, box_regression, labels, base_anchors, None, batch_size_per_image,
+                        positive_fraction, yaw_loss_mode, seed)
     obj_loss, box_loss, sel, info = _RpnLoss.apply(cfg, *objectness, *box_regression)
     out = (obj_loss, box_loss) + ((sel,) if return_samples else ()) + ((info,) if return_info else ())
     return out
-
-
-class _RpnLossGrouped(torch.autograd.Function):
-    """_RpnLoss over (scene, group) segments (aabr_rpn_loss_grouped_*): inputs group-major, losses [G]"""
-
-    @staticmethod
-    def forward(ctx, cfg, *tensors):
-        lib = _hip.load()
-        n_maps, G = cfg["n_maps"], cfg["G"]
-        obj, reg = tensors[:n_maps], tensors[n_maps:]
-        dev = obj[0].device
-        bf16 = int(obj[0].dtype == torch.bfloat16)
-        nb, B = cfg["nb"], cfg["B"]
-        obj_c = [o.reshape(G, -1).contiguous() for o in obj]
-        reg_c = [r.reshape(G, -1, 7).contiguous() for r in reg]
-        sel = torch.empty((nb * G, B), dtype=torch.int64, device=dev)
-        info = torch.empty((nb * G, 8), dtype=torch.int32, device=dev)
-        obj_loss = torch.empty(G, dtype=torch.float32, device=dev)
-        box_loss = torch.empty(G, dtype=torch.float32, device=dev)
-        scr = _hip.workspace("rpn_loss", int(lib.aabr_rpn_loss_grouped_scratch_words(nb, G)) + 2, torch.int32, dev)
-        so = (-scr.data_ptr() // 4) % 2
-        check(lib.aabr_rpn_loss_grouped_forward(
-            n_maps, _hip.ptrs(cfg["coords"]), _hip.ptrs(obj_c), _hip.ptrs(reg_c), cfg["rows"], bf16, cfg["A"], nb, G,
-            cfg["seg"], cfg["site"], _hip.ptrs(cfg["labels"]), _hip.ptrs(cfg["targets"]), cfg["seed"], B, cfg["num_pos"],
-            cfg["beta"], ptr(sel), ptr(info), ptr(obj_loss), ptr(box_loss), scr.data_ptr() + 4 * so, stream()))
-        ctx.cfg = cfg
-        ctx.save_for_backward(sel, info, *obj_c, *reg_c)
-        ctx.shapes = [t.shape for t in tensors]
-        ctx.mark_non_differentiable(sel, info)
-        return obj_loss, box_loss, sel, info
-
-    @staticmethod
-    def backward(ctx, g_obj, g_box, _g_sel, _g_info):
-        lib = _hip.load()
-        cfg = ctx.cfg
-        n_maps, G = cfg["n_maps"], cfg["G"]
-        saved = ctx.saved_tensors
-        sel, info, obj_c, reg_c = saved[0], saved[1], saved[2:2 + n_maps], saved[2 + n_maps:]
-        dev, dt = obj_c[0].device, obj_c[0].dtype
-        g_obj = (g_obj if g_obj is not None else torch.zeros(G, device=dev)).float().contiguous()
-        g_box = (g_box if g_box is not None else torch.zeros(G, device=dev)).float().contiguous()
-        sizes = [o.numel() for o in obj_c] + [r.numel() for r in reg_c]
-        flat = torch.zeros(sum(sizes), dtype=dt, device=dev)       # one fill for every gradient
-        grads = list(torch.split(flat, sizes))
-        check(lib.aabr_rpn_loss_grouped_backward(
-            n_maps, _hip.ptrs(obj_c), _hip.ptrs(reg_c), cfg["rows"], int(dt == torch.bfloat16), cfg["A"], cfg["nb"], G,
-            cfg["seg"], cfg["site"], _hip.ptrs(cfg["targets"]), cfg["B"], cfg["beta"], ptr(sel), ptr(info), ptr(g_obj),
-            ptr(g_box), _hip.ptrs(grads[:n_maps]), _hip.ptrs(grads[n_maps:]), stream()))
-        return (None,) + tuple(g.view(s) for g, s in zip(grads, ctx.shapes))
 
 
 def rpn_loss_grouped(maps, objectness, box_regression, labels, base_anchors, G, batch_size_per_image=256,
@@ -726,40 +694,13 @@ def rpn_loss_grouped(maps, objectness, box_regression, labels, base_anchors, G, 
     Returns (objectness_losses [G], box_losses [G]) with autograd to objectness / box_regression; with `return_samples`
     also the int64 [nb G, batch_size_per_image] selected indices (into group g's scene-major label lists) and the int32
     [nb G, 8] info words."""
-    parse_yaw_loss_mode(yaw_loss_mode)
-    n_maps, G = len(maps), int(G)
-    if not (n_maps == len(objectness) == len(box_regression) == len(base_anchors)):
-        raise ValueError("maps, objectness, box_regression and base_anchors differ in length")
+    G = int(G)
     if G < 2 or len(labels) == 0 or len(labels) % G:
         raise ValueError("rpn_loss_grouped: G >= 2 and one label tuple per (scene, group), got G = %d, %d tuples"
                          % (G, len(labels)))
-    nb = len(labels) // G
-    if any(len(l) < 4 or l[3] is None for l in labels):
-        raise ValueError("labels need the regression targets: rpn_label_matches_grouped(..., regression_targets=True)")
-    dt = objectness[0].dtype
-    if dt not in _BF16_OR_F32 or any(t.dtype != dt for t in list(objectness) + list(box_regression)):
-        raise TypeError("objectness and box_regression must all be float32, or all bfloat16")
-    grids = [t.metadata.grids[_SCN._key(t.spatial_size)] for t in maps]
-    dev = objectness[0].device
-    A = int(base_anchors[0].shape[0])
-    counts = _site_counts(grids, nb, dev)
-    V = [sum(c) for c in counts]
-    for m in range(n_maps):
-        if objectness[m].numel() != G * V[m] * A or box_regression[m].numel() != G * V[m] * A * 7:
-            raise ValueError("map %d: objectness / box_regression do not hold %d groups x %d sites x %d anchors"
-                             % (m, G, V[m], A))
-    seg, site, n_anchor = _anchor_tables(counts, A, 0, nb)
-    for e in range(nb * G):
-        if labels[e][0].numel() != n_anchor[e // G] or labels[e][3].shape[0] != n_anchor[e // G]:
-            raise ValueError("segment %d: the labels do not match the maps' anchors" % e)
-    lab = [l[0] if l[0].dtype == torch.int64 else l[0].long() for l in labels]
-    tgt = [l[3].float().contiguous() for l in labels]
-    cfg = {"n_maps": n_maps, "nb": nb, "G": G, "A": A, "B": int(batch_size_per_image),
-           "num_pos": int(batch_size_per_image * positive_fraction), "beta": 1.0 / 9,
-           "seed": int(draw_seed() if seed is None else seed) & 0xffffffff, "rows": _hip.i64xn(V),
-           "coords": [g.coords for g in grids], "seg": _hip.i32xn(seg), "site": _hip.i32xn(site),
-           "labels": [l.contiguous() for l in lab], "targets": tgt}
-    obj_loss, box_loss, sel, info = _RpnLossGrouped.apply(cfg, *objectness, *box_regression)
+    cfg = _rpn_loss_cfg(maps, objectness, box_regression, labels, base_anchors, G, batch_size_per_image,
+                        positive_fraction, yaw_loss_mode, seed)
+    obj_loss, box_loss, sel, info = _RpnLoss.apply(cfg, *objectness, *box_regression)
     return (obj_loss, box_loss, sel, info) if return_samples else (obj_loss, box_loss)
 
 
@@ -770,116 +711,9 @@ RPN_HEAD_CHANNELS = (32, 64, 96, 128)
 
 class _RpnHead(torch.autograd.Function):
     """SingleConvRPNHead_Sparse3D over every map in one launch (csrc/rpn_head.hip); the hidden activation is written to
-    memory only when some input requires a gradient"""
-
-    @staticmethod
-    def forward(ctx, A, W1, b1, Wc, bc, Wr, br, *feats):
-        lib = _hip.load()
-        dev = W1.device
-        C, n_maps = int(W1.shape[0]), len(feats)
-        params = [p.contiguous() for p in (W1, b1, Wc, bc, Wr, br)]
-        feats = [f.contiguous() for f in feats]
-        rows = [int(f.shape[0]) for f in feats]
-        obj = [torch.empty(v * A, dtype=torch.float32, device=dev) for v in rows]       # every element is written
-        reg = [torch.empty((v * A, 7), dtype=torch.float32, device=dev) for v in rows]
-        need = any(ctx.needs_input_grad)
-        hidden = torch.empty((sum(rows), C), dtype=torch.float32, device=dev) if need else None
-        tab = (_hip.AabrRpnMap * n_maps)()
-        for m in range(n_maps):
-            tab[m].features, tab[m].rows = ptr(feats[m]), rows[m]
-            tab[m].objectness, tab[m].box_regression = ptr(obj[m]), ptr(reg[m])
-        check(lib.aabr_rpn_head_forward(tab, n_maps, C, A, *[ptr(p) for p in params], ptr(hidden), stream()))
-        if need:
-            ctx.save_for_backward(hidden, params[0], params[2], params[4], *feats)
-        ctx.cfg = (A, C, n_maps, rows)
-        return tuple(obj) + tuple(reg)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, *grads):
-        lib = _hip.load()
-        A, C, n_maps, rows = ctx.cfg
-        hidden, W1, Wc, Wr = ctx.saved_tensors[:4]
-        feats = ctx.saved_tensors[4:]
-        dev = W1.device
-        g_obj = [g.contiguous() if g is not None else None for g in grads[:n_maps]]
-        g_reg = [g.contiguous() if g is not None else None for g in grads[n_maps:]]
-        d_all = torch.empty((sum(rows), C), dtype=torch.float32, device=dev)           # every element is written
-        d_f = list(torch.split(d_all, rows))
-        sizes = (C * C, C, A * C, A, 7 * A * C, 7 * A)
-        d_p = list(torch.split(torch.empty(sum(sizes), dtype=torch.float32, device=dev), sizes))
-        t_rows = lib.aabr_rpn_head_tile_rows(C)
-        tiles = sum(-(-v // t_rows) for v in rows)
-        floats = int(lib.aabr_rpn_head_scratch_floats(tiles, C, A))
-        scr = _hip.workspace("rpn_head", floats, torch.float32, dev) if floats else None
-        tab = (_hip.AabrRpnMap * n_maps)()
-        for m in range(n_maps):
-            tab[m].features, tab[m].rows, tab[m].d_features = ptr(feats[m]), rows[m], ptr(d_f[m])
-            tab[m].objectness, tab[m].box_regression = ptr(g_obj[m]), ptr(g_reg[m])
-        check(lib.aabr_rpn_head_backward(tab, n_maps, C, A, ptr(W1), ptr(Wc), ptr(Wr), ptr(hidden),
-                                         *[ptr(p) for p in d_p], ptr(scr), stream()))
-        return (None, d_p[0].view(C, C), d_p[1], d_p[2].view(A, C), d_p[3], d_p[4].view(7 * A, C), d_p[5]) + tuple(d_f)
-
-
-def _as_out_in(name, w):
-    """a Conv2d weight [out, in, 1, 1] or a Linear weight [out, in] -> [out, in]"""
-    if w.dim() == 4 and tuple(w.shape[2:]) == (1, 1):
-        return w.reshape(w.shape[0], w.shape[1])
-    if w.dim() != 2:
-        raise ValueError("rpn_head: %s must be [out, in] or [out, in, 1, 1], got %s" % (name, tuple(w.shape)))
-    return w
-
-
-def rpn_head(features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b):
-    """SingleConvRPNHead_Sparse3D.forward (modeling/rpn/rpn_sparse3d.py:109-131) for all maps at once:
-      t = relu(f conv_w^T + conv_b), objectness = t cls_w^T + cls_b, box_regression = t reg_w^T + reg_b
-    features: a list (1..8 maps) of SparseConvNetTensors or of [V_m, C] fp32 tensors; the weights as [out, in] or the
-    reference's Conv2d [out, in, 1, 1]: conv_w [C, C], cls_w [A, C], reg_w [7 A, C] (channel a 7 + j, 'box_toghter').
-    C in {32, 64, 96, 128}, 1 <= A <= 4.  Returns (objectness, box_regression): lists over the maps of [V_m A] and
-    [V_m A, 7] in the [site, yaw] flatten order rpn_proposals, rpn_label_matches and rpn_loss read.
-    Device work: forward 1 library launch whatever the number of maps (nothing concatenated, the hidden activation
-    reaches memory only when a gradient is required); backward 2 (the fused main kernel and the in-order reduction of its
-    per-workgroup partials: deterministic, no atomics).  No host read."""
-    feats = [f.features if hasattr(f, "features") else f for f in features]
-    if not 1 <= len(feats) <= RPN_HEAD_MAX_MAPS:
-        raise ValueError("rpn_head: 1 to %d maps, got %d" % (RPN_HEAD_MAX_MAPS, len(feats)))
-    w1, wc, wr = _as_out_in("conv_w", conv_w), _as_out_in("cls_w", cls_w), _as_out_in("reg_w", reg_w)
-    for k, t in [("conv_w", w1), ("conv_b", conv_b), ("cls_w", wc), ("cls_b", cls_b), ("reg_w", wr), ("reg_b", reg_b)] + \
-            [("features[%d]" % i, f) for i, f in enumerate(feats)]:
-        if t.dtype != torch.float32:
-            raise TypeError("rpn_head: %s must be float32, got %s (bf16 feature storage is not part of this path)"
-                            % (k, t.dtype))
-    C, A = int(w1.shape[1]), int(wc.shape[0])
-    if C not in RPN_HEAD_CHANNELS:
-        raise ValueError("rpn_head: C = %d; supported: a multiple of 32 from 32 to 128" % C)
-    if not 1 <= A <= RPN_HEAD_MAX_ANCHORS:
-        raise ValueError("rpn_head: A = %d anchors per site; supported: 1 to %d" % (A, RPN_HEAD_MAX_ANCHORS))
-    if tuple(w1.shape) != (C, C) or tuple(wc.shape) != (A, C) or tuple(wr.shape) != (7 * A, C):
-        raise ValueError("rpn_head: conv_w [C, C], cls_w [A, C], reg_w [7 A, C]; got %s, %s, %s"
-                         % (tuple(w1.shape), tuple(wc.shape), tuple(wr.shape)))
-    if tuple(conv_b.shape) != (C,) or tuple(cls_b.shape) != (A,) or tuple(reg_b.shape) != (7 * A,):
-        raise ValueError("rpn_head: the biases must be [C], [A] and [7 A]")
-    for i, f in enumerate(feats):
-        if f.dim() != 2 or int(f.shape[1]) != C:
-            raise ValueError("rpn_head: features[%d] must be [V, %d], got %s" % (i, C, tuple(f.shape)))
-    _hip.require_gpu(feats[0])
-    out = _RpnHead.apply(A, w1, conv_b, wc, cls_b, wr, reg_b, *feats)
-    return list(out[:len(feats)]), list(out[len(feats):])
-
-
-RPN_HEAD_MAX_GROUPS, RPN_HEAD_MAX_COLUMNS = 8, 16
-RPN_HEAD_GROUP_LIMITS = ("C in %s, 1 <= A <= %d anchors per site, 2 <= G <= %d groups, A G <= %d"
-                         % (RPN_HEAD_CHANNELS, RPN_HEAD_MAX_ANCHORS, RPN_HEAD_MAX_GROUPS, RPN_HEAD_MAX_COLUMNS))
-
-
-def rpn_head_group_limits_ok(C, A, G):
-    return (C in RPN_HEAD_CHANNELS and 1 <= A <= RPN_HEAD_MAX_ANCHORS and 2 <= G <= RPN_HEAD_MAX_GROUPS
-            and A * G <= RPN_HEAD_MAX_COLUMNS)
-
-
-class _RpnHeadGrouped(torch.autograd.Function):
-    """_RpnHead with G separated-classifier groups (aabr_rpn_head_grouped_*): Wc [A G, C], Wr [7 A G, C] in the
-    reference's layout, the outputs group-major [G, V A] and [G, V A, 7]"""
+    memory only when some input requires a gradient.  G None: aabr_rpn_head_*, outputs [V A] and [V A, 7]; with G
+    separated-classifier groups: aabr_rpn_head_grouped_*, Wc [A G, C], Wr [7 A G, C] in the reference's layout, the
+    outputs group-major [G, V A] and [G, V A, 7]"""
 
     @staticmethod
     def forward(ctx, A, G, W1, b1, Wc, bc, Wr, br, *feats):
@@ -889,15 +723,17 @@ class _RpnHeadGrouped(torch.autograd.Function):
         params = [p.contiguous() for p in (W1, b1, Wc, bc, Wr, br)]
         feats = [f.contiguous() for f in feats]
         rows = [int(f.shape[0]) for f in feats]
-        obj = [torch.empty((G, v * A), dtype=torch.float32, device=dev) for v in rows]  # every element is written
-        reg = [torch.empty((G, v * A, 7), dtype=torch.float32, device=dev) for v in rows]
+        lead = () if G is None else (G,)
+        obj = [torch.empty(lead + (v * A,), dtype=torch.float32, device=dev) for v in rows]     # every element is written
+        reg = [torch.empty(lead + (v * A, 7), dtype=torch.float32, device=dev) for v in rows]
         need = any(ctx.needs_input_grad)
         hidden = torch.empty((sum(rows), C), dtype=torch.float32, device=dev) if need else None
         tab = (_hip.AabrRpnMap * n_maps)()
         for m in range(n_maps):
             tab[m].features, tab[m].rows = ptr(feats[m]), rows[m]
             tab[m].objectness, tab[m].box_regression = ptr(obj[m]), ptr(reg[m])
-        check(lib.aabr_rpn_head_grouped_forward(tab, n_maps, C, A, G, *[ptr(p) for p in params], ptr(hidden), stream()))
+        forward = lib.aabr_rpn_head_forward if G is None else lib.aabr_rpn_head_grouped_forward
+        check(forward(tab, n_maps, C, A, *lead, *[ptr(p) for p in params], ptr(hidden), stream()))
         if need:
             ctx.save_for_backward(hidden, params[0], params[2], params[4], *feats)
         ctx.cfg = (A, G, C, n_maps, rows)
@@ -915,20 +751,94 @@ class _RpnHeadGrouped(torch.autograd.Function):
         g_reg = [g.contiguous() if g is not None else None for g in grads[n_maps:]]
         d_all = torch.empty((sum(rows), C), dtype=torch.float32, device=dev)           # every element is written
         d_f = list(torch.split(d_all, rows))
-        AG = A * G
+        AG = A * (G or 1)
         sizes = (C * C, C, AG * C, AG, 7 * AG * C, 7 * AG)
         d_p = list(torch.split(torch.empty(sum(sizes), dtype=torch.float32, device=dev), sizes))
         t_rows = lib.aabr_rpn_head_tile_rows(C)
         tiles = sum(-(-v // t_rows) for v in rows)
-        floats = int(lib.aabr_rpn_head_grouped_scratch_floats(tiles, C, A, G))
-        scr = _hip.workspace("rpn_head_grouped", floats, torch.float32, dev) if floats else None
+        lead = () if G is None else (G,)
+        if G is None:
+            floats, backward, key = lib.aabr_rpn_head_scratch_floats, lib.aabr_rpn_head_backward, "rpn_head"
+        else:
+            floats, backward = lib.aabr_rpn_head_grouped_scratch_floats, lib.aabr_rpn_head_grouped_backward
+            key = "rpn_head_grouped"
+        floats = int(floats(tiles, C, A, *lead))
+        scr = _hip.workspace(key, floats, torch.float32, dev) if floats else None
         tab = (_hip.AabrRpnMap * n_maps)()
         for m in range(n_maps):
             tab[m].features, tab[m].rows, tab[m].d_features = ptr(feats[m]), rows[m], ptr(d_f[m])
             tab[m].objectness, tab[m].box_regression = ptr(g_obj[m]), ptr(g_reg[m])
-        check(lib.aabr_rpn_head_grouped_backward(tab, n_maps, C, A, G, ptr(W1), ptr(Wc), ptr(Wr), ptr(hidden),
-                                                 *[ptr(p) for p in d_p], ptr(scr), stream()))
+        check(backward(tab, n_maps, C, A, *lead, ptr(W1), ptr(Wc), ptr(Wr), ptr(hidden), *[ptr(p) for p in d_p],
+                       ptr(scr), stream()))
         return (None, None, d_p[0].view(C, C), d_p[1], d_p[2].view(AG, C), d_p[3], d_p[4].view(7 * AG, C), d_p[5]) + tuple(d_f)
+
+
+def _as_out_in(name, w):
+    """a Conv2d weight [out, in, 1, 1] or a Linear weight [out, in] -> [out, in]"""
+    if w.dim() == 4 and tuple(w.shape[2:]) == (1, 1):
+        return w.reshape(w.shape[0], w.shape[1])
+    if w.dim() != 2:
+        raise ValueError("rpn_head: %s must be [out, in] or [out, in, 1, 1], got %s" % (name, tuple(w.shape)))
+    return w
+
+
+RPN_HEAD_MAX_GROUPS, RPN_HEAD_MAX_COLUMNS = 8, 16
+RPN_HEAD_GROUP_LIMITS = ("C in %s, 1 <= A <= %d anchors per site, 2 <= G <= %d groups, A G <= %d"
+                         % (RPN_HEAD_CHANNELS, RPN_HEAD_MAX_ANCHORS, RPN_HEAD_MAX_GROUPS, RPN_HEAD_MAX_COLUMNS))
+
+
+def rpn_head_group_limits_ok(C, A, G):
+    return (C in RPN_HEAD_CHANNELS and 1 <= A <= RPN_HEAD_MAX_ANCHORS and 2 <= G <= RPN_HEAD_MAX_GROUPS
+            and A * G <= RPN_HEAD_MAX_COLUMNS)
+
+
+def _rpn_head(fn, G, features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b):
+    """the checks and the launch of rpn_head (G None) and rpn_head_grouped; `fn`: the caller's name, for the messages"""
+    feats = [f.features if hasattr(f, "features") else f for f in features]
+    if not 1 <= len(feats) <= RPN_HEAD_MAX_MAPS:
+        raise ValueError("%s: 1 to %d maps, got %d" % (fn, RPN_HEAD_MAX_MAPS, len(feats)))
+    w1, wc, wr = _as_out_in("conv_w", conv_w), _as_out_in("cls_w", cls_w), _as_out_in("reg_w", reg_w)
+    for k, t in [("conv_w", w1), ("conv_b", conv_b), ("cls_w", wc), ("cls_b", cls_b), ("reg_w", wr), ("reg_b", reg_b)] + \
+            [("features[%d]" % i, f) for i, f in enumerate(feats)]:
+        if t.dtype != torch.float32:
+            raise TypeError("%s: %s must be float32, got %s (bf16 feature storage is not part of this path)"
+                            % (fn, k, t.dtype))
+    C, AG = int(w1.shape[1]), int(wc.shape[0])          # AG: the rows of cls_w, A without groups
+    if G is None:
+        A = AG
+        if C not in RPN_HEAD_CHANNELS:
+            raise ValueError("%s: C = %d; supported: a multiple of 32 from 32 to 128" % (fn, C))
+        if not 1 <= A <= RPN_HEAD_MAX_ANCHORS:
+            raise ValueError("%s: A = %d anchors per site; supported: 1 to %d" % (fn, A, RPN_HEAD_MAX_ANCHORS))
+    else:
+        A = AG // G if G > 0 and AG % G == 0 else 0
+        if not rpn_head_group_limits_ok(C, A, G):
+            raise ValueError("%s: C = %d, cls_w with %d rows, G = %d; supported: %s" % (fn, C, AG, G, RPN_HEAD_GROUP_LIMITS))
+    n = "A" if G is None else "A G"
+    if tuple(w1.shape) != (C, C) or tuple(wc.shape) != (AG, C) or tuple(wr.shape) != (7 * AG, C):
+        raise ValueError("%s: conv_w [C, C], cls_w [%s, C], reg_w [7 %s, C]; got %s, %s, %s"
+                         % (fn, n, n, tuple(w1.shape), tuple(wc.shape), tuple(wr.shape)))
+    if tuple(conv_b.shape) != (C,) or tuple(cls_b.shape) != (AG,) or tuple(reg_b.shape) != (7 * AG,):
+        raise ValueError("%s: the biases must be [C], [%s] and [7 %s]" % (fn, n, n))
+    for i, f in enumerate(feats):
+        if f.dim() != 2 or int(f.shape[1]) != C:
+            raise ValueError("%s: features[%d] must be [V, %d], got %s" % (fn, i, C, tuple(f.shape)))
+    _hip.require_gpu(feats[0])
+    out = _RpnHead.apply(A, G, w1, conv_b, wc, cls_b, wr, reg_b, *feats)
+    return list(out[:len(feats)]), list(out[len(feats):])
+
+
+def rpn_head(features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b):
+    """SingleConvRPNHead_Sparse3D.forward (modeling/rpn/rpn_sparse3d.py:109-131) for all maps at once:
+      t = relu(f conv_w^T + conv_b), objectness = t cls_w^T + cls_b, box_regression = t reg_w^T + reg_b
+    features: a list (1..8 maps) of SparseConvNetTensors or of [V_m, C] fp32 tensors; the weights as [out, in] or the
+    reference's Conv2d [out, in, 1, 1]: conv_w [C, C], cls_w [A, C], reg_w [7 A, C] (channel a 7 + j, 'box_toghter').
+    C in {32, 64, 96, 128}, 1 <= A <= 4.  Returns (objectness, box_regression): lists over the maps of [V_m A] and
+    [V_m A, 7] in the [site, yaw] flatten order rpn_proposals, rpn_label_matches and rpn_loss read.
+    Device work: forward 1 library launch whatever the number of maps (nothing concatenated, the hidden activation
+    reaches memory only when a gradient is required); backward 2 (the fused main kernel and the in-order reduction of its
+    per-workgroup partials: deterministic, no atomics).  No host read."""
+    return _rpn_head("rpn_head", None, features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b)
 
 
 def rpn_head_grouped(features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b, G):
@@ -939,32 +849,7 @@ def rpn_head_grouped(features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b, G):
     Returns (objectness, box_regression): lists over the maps of [G, V_m A] and [G, V_m A, 7]: group g's slice is a
     contiguous tensor in the [site, yaw] order of rpn_head, and holds the bits rpn_head gives on that group's weight rows.
     Device work as rpn_head: forward 1 library launch, backward 2; nothing is permuted or copied.  No host read."""
-    feats = [f.features if hasattr(f, "features") else f for f in features]
-    if not 1 <= len(feats) <= RPN_HEAD_MAX_MAPS:
-        raise ValueError("rpn_head_grouped: 1 to %d maps, got %d" % (RPN_HEAD_MAX_MAPS, len(feats)))
-    w1, wc, wr = _as_out_in("conv_w", conv_w), _as_out_in("cls_w", cls_w), _as_out_in("reg_w", reg_w)
-    for k, t in [("conv_w", w1), ("conv_b", conv_b), ("cls_w", wc), ("cls_b", cls_b), ("reg_w", wr), ("reg_b", reg_b)] + \
-            [("features[%d]" % i, f) for i, f in enumerate(feats)]:
-        if t.dtype != torch.float32:
-            raise TypeError("rpn_head_grouped: %s must be float32, got %s (bf16 feature storage is not part of this path)"
-                            % (k, t.dtype))
-    G = int(G)
-    C, AG = int(w1.shape[1]), int(wc.shape[0])
-    A = AG // G if G > 0 and AG % G == 0 else 0
-    if not rpn_head_group_limits_ok(C, A, G):
-        raise ValueError("rpn_head_grouped: C = %d, cls_w with %d rows, G = %d; supported: %s"
-                         % (C, AG, G, RPN_HEAD_GROUP_LIMITS))
-    if tuple(w1.shape) != (C, C) or tuple(wc.shape) != (AG, C) or tuple(wr.shape) != (7 * AG, C):
-        raise ValueError("rpn_head_grouped: conv_w [C, C], cls_w [A G, C], reg_w [7 A G, C]; got %s, %s, %s"
-                         % (tuple(w1.shape), tuple(wc.shape), tuple(wr.shape)))
-    if tuple(conv_b.shape) != (C,) or tuple(cls_b.shape) != (AG,) or tuple(reg_b.shape) != (7 * AG,):
-        raise ValueError("rpn_head_grouped: the biases must be [C], [A G] and [7 A G]")
-    for i, f in enumerate(feats):
-        if f.dim() != 2 or int(f.shape[1]) != C:
-            raise ValueError("rpn_head_grouped: features[%d] must be [V, %d], got %s" % (i, C, tuple(f.shape)))
-    _hip.require_gpu(feats[0])
-    out = _RpnHeadGrouped.apply(A, G, w1, conv_b, wc, cls_b, wr, reg_b, *feats)
-    return list(out[:len(feats)]), list(out[len(feats):])
+    return _rpn_head("rpn_head_grouped", int(G), features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b)
 
 
 class _Cfg(object):

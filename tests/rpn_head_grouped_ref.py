@@ -86,13 +86,13 @@ def make_case(C, A, G, rows, seed):
 
 
 def entry_cases(T):
-    """(C, A, G, rows per map, seed): both ends of C; a padded single tile, a group's columns across a tile edge, two full
+    """(C, A, G, rows per map, seed): every C; a padded single tile, a group's columns across a tile edge, two full
     tiles, the reference's 3g6c, the limit; a map that crosses a tile edge by one row, an empty map, a one-row map"""
-    return [(C, A, G, (T + 1, 0, 1), 3) for C in (32, 128) for A, G in GROUPS]
+    return [(C, A, G, (T + 1, 0, 1), 3) for C in (32, 64, 96, 128) for A, G in GROUPS]
 
 
 def hidden_cases(T):
-    return [(C, A, G, (2 * T, T - 1, 3), 4) for C in (32, 128) for A, G in GROUPS]
+    return [(C, A, G, (2 * T, T - 1, 3), 4) for C in (32, 64, 96, 128) for A, G in GROUPS]
 
 
 def determinism_cases(T, gmax):

@@ -113,10 +113,10 @@ def make_case(C, A, rows, seed):
 
 
 def entry_cases(T):
-    """(C, A, rows per map, seed) of the entry-point test: both ends of C, the padded-column case 8 A = 8, a map that
+    """(C, A, rows per map, seed) of the entry-point test: every C, the padded-column case 8 A = 8, a map that
     crosses a tile edge by one row, an empty map, a one-row map"""
-    return [(C, A, (T + 1, 0, 1), 3) for C in (32, 128) for A in (1, 2, 4)]
+    return [(C, A, (T + 1, 0, 1), 3) for C in (32, 64, 96, 128) for A in (1, 2, 4)]
 
 
 def hidden_cases(T):
-    return [(C, A, (2 * T, T - 1, 3), 4) for C in (32, 128) for A in (1, 2, 4)]
+    return [(C, A, (2 * T, T - 1, 3), 4) for C in (32, 64, 96, 128) for A in (1, 2, 4)]
