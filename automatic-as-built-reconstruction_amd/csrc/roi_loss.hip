@@ -27,7 +27,7 @@
 // With separated-classifier groups (sep_groups.h; the reference's seperate_classifier.py loops over the groups around the
 // code above) both stages have a grouped form of the same launch counts: stage 1 runs over (scene, group) segments with
 // the scene's ground truth filtered by group on the device (k_roi_gt_keys, the caller's stable sort, k_roi_match<.., true>);
-// stage 2 keeps one accumulator set per group (k_roi_sep_loss_*).
+// stage 2 is the same three kernels with one accumulator set per group (k_roi_loss_*<true>).
 #include "common.h"
 #include "iou_math.h"
 #include "nms_shared.h"
@@ -250,240 +250,173 @@ __global__ __launch_bounds__(256) void k_roi_compact(RoiTargetParams p, const in
 }
 
 // ---- stage 2 -------------------------------------------------------------------------------------------------------
-// the softmax statistics of row i of the sampled batch
-struct RoiRow {
-  float m, s;         // maximum logit, sum of expf(x - m) in class order
+// One partial, one finalize and one backward kernel, each instantiated for the plain loss and for the loss with
+// separated-classifier groups (SeperateClassifier.roi_cross_entropy_seperated / roi_box_loss_seperated).  What differs
+// between the two travels in RoiLossForm<kGrouped>; the statements are the same.
+//   plain    one accumulator set; the row's columns are all C in order (no table: C has no upper limit); the regression
+//            is [n, 7 C] (class specific: the row's seven columns are those of its label) or [n, 7]; divisor n -- a row
+//            whose label is outside [0, C) counts in it.
+//   grouped  row i belongs to group sep_id[i]; its cross-entropy runs over that group's columns of the C_tot logits in
+//            group-local order with the target column cols[g][label]; the regression is [n, 7]; one accumulator set per
+//            group (a register per group, no dynamically indexed array) and the divisor is the group's row count n_g,
+//            counted here: a row whose label is outside [0, class_nums[g]) counts in n_g, a row whose sep_id is outside
+//            [0, G) is in no group.
+// Neither out-of-range value is used as an index; both raise the flag, add nothing and get exact zero gradients.
+// A workgroup's partial sums: cls [kSets], box [kSets], grouped only rows [kSets] (int32 bits), then the flag.
+template <bool kGrouped> struct RoiLossForm;
+template <> struct RoiLossForm<false> {
+  static constexpr bool kIsGrouped = false;
+  static constexpr int kSets = 1, kPartWords = 3;
+  int C, class_specific;
+  __device__ int groups() const { return 1; }
+  __device__ int width() const { return C; }                       // row stride of the logits
+  __device__ bool specific() const { return class_specific != 0; }
+  __device__ bool group_of(int64_t, int &g) const { g = 0; return true; }
+  __device__ RowCols<false> cols(int) const { return {C}; }
 };
-__device__ inline RoiRow roi_row_softmax(const void *logits, int64_t i, int C, int bf16) {
-  RoiRow r;
-  r.m = ld(logits, i * C, bf16);
-  for (int k = 1; k < C; ++k) r.m = fmaxf(r.m, ld(logits, i * C + k, bf16));
-  r.s = 0.f;
-  for (int k = 0; k < C; ++k) r.s += expf(ld(logits, i * C + k, bf16) - r.m);
-  return r;
-}
+template <> struct RoiLossForm<true> {
+  static constexpr bool kIsGrouped = true;
+  static constexpr int kSets = kSepMaxGroups, kPartWords = 3 * kSepMaxGroups + 1;
+  SepGroups q;
+  const int32_t *sep_id;
+  __device__ int groups() const { return q.G; }
+  __device__ int width() const { return q.C_tot; }
+  __device__ bool specific() const { return false; }
+  __device__ bool group_of(int64_t i, int &g) const { g = sep_id[i]; return g >= 0 && g < q.G; }
+  __device__ RowCols<true> cols(int g) const { return RowCols<true>(q, g); }
+};
 
+// Per-thread sums in row order (the seven smooth-L1 terms of a row first, then the row), a fixed tree per workgroup
+template <bool kGrouped>
 __global__ __launch_bounds__(256) void k_roi_loss_partial(const void *__restrict__ logits, const void *__restrict__ reg,
-                                                          int bf16, int64_t n, int C, int class_specific,
+                                                          int bf16, int64_t n, RoiLossForm<kGrouped> f,
                                                           const int64_t *__restrict__ labels,
                                                           const float *__restrict__ targets, float beta,
                                                           float *__restrict__ partial) {
+  constexpr int kSets = RoiLossForm<kGrouped>::kSets, kWords = RoiLossForm<kGrouped>::kPartWords;
   __shared__ float s_red[2][256];
+  __shared__ int s_cnt[kGrouped ? 256 : 1];            // (the row counts: grouped only, unused and absent when plain)
   __shared__ int s_bad;
-  const int t = threadIdx.x;
+  const int t = threadIdx.x, C = f.width();
   if (t == 0) s_bad = 0;
-  __syncthreads();
-  float cls = 0.f, box = 0.f;
-  bool bad = false;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n; i += (int64_t)gridDim.x * 256) {
-    const int64_t l = labels[i];
-    if (l < 0 || l >= C) { bad = true; continue; }
-    const RoiRow r = roi_row_softmax(logits, i, C, bf16);
-    cls += (r.m + logf(r.s)) - ld(logits, i * C + l, bf16);
-    if (l > 0) {
-      const int64_t c0 = class_specific ? i * 7 * C + 7 * l : i * 7;
-      float row = 0.f;
-      for (int d = 0; d < 7; ++d) row += smooth_l1_term(fabsf(ld(reg, c0 + d, bf16) - targets[i * 7 + d]), beta);
-      box += row;
-    }
-  }
-  if (bad) s_bad = 1;                                  // (every writer stores the same value)
-  s_red[0][t] = cls;
-  s_red[1][t] = box;
-  for (int w = 128; w > 0; w >>= 1) {
-    __syncthreads();
-    if (t < w) { s_red[0][t] += s_red[0][t + w]; s_red[1][t] += s_red[1][t + w]; }
-  }
-  __syncthreads();
-  if (t == 0) {
-    partial[3 * blockIdx.x] = s_red[0][0];
-    partial[3 * blockIdx.x + 1] = s_red[1][0];
-    partial[3 * blockIdx.x + 2] = s_bad ? 1.f : 0.f;
-  }
-}
-
-// the workgroups' sums in workgroup order, / n (0 / 0 = NaN for an empty sample, like aabr_rpn_loss_forward)
-__global__ __launch_bounds__(64) void k_roi_loss_finalize(int nblocks, const float *__restrict__ partial, int64_t n,
-                                                          float *__restrict__ cls_loss, float *__restrict__ box_loss,
-                                                          int32_t *__restrict__ flag) {
-  if (threadIdx.x != 0) return;
-  float cls = 0.f, box = 0.f;
-  int bad = 0;
-  for (int i = 0; i < nblocks; ++i) {
-    cls += partial[3 * i];
-    box += partial[3 * i + 1];
-    bad |= partial[3 * i + 2] != 0.f;
-  }
-  *cls_loss = cls / (float)n;
-  *box_loss = box / (float)n;
-  *flag = bad;
-}
-
-// one thread per row writes the row's C logit gradients and its 7 C (or 7) regression gradients, zeros included
-__global__ __launch_bounds__(256) void k_roi_loss_backward(const void *__restrict__ logits, const void *__restrict__ reg,
-                                                           int bf16, int64_t n, int C, int class_specific,
-                                                           const int64_t *__restrict__ labels,
-                                                           const float *__restrict__ targets, float beta,
-                                                           const float *__restrict__ g_cls, const float *__restrict__ g_box,
-                                                           void *__restrict__ grad_logits, void *__restrict__ grad_reg) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int64_t l = labels[i];
-  const bool ok = l >= 0 && l < C;
-  const int W = class_specific ? 7 * C : 7;
-  if (ok) {
-    const RoiRow r = roi_row_softmax(logits, i, C, bf16);
-    const float gc = *g_cls / (float)n;
-    for (int k = 0; k < C; ++k) {
-      const float pk = expf(ld(logits, i * C + k, bf16) - r.m) / r.s;
-      st(grad_logits, i * C + k, (pk - (k == l ? 1.f : 0.f)) * gc, bf16);
-    }
-  } else {
-    for (int k = 0; k < C; ++k) st(grad_logits, i * C + k, 0.f, bf16);
-  }
-  const int c0 = ok && l > 0 ? (class_specific ? 7 * (int)l : 0) : -7;   // first column of the row's own box, or none
-  const float gb = *g_box / (float)n;
-  for (int c = 0; c < W; ++c) {
-    float v = 0.f;
-    if (c >= c0 && c < c0 + 7 && c0 >= 0) {
-      const float diff = ld(reg, i * W + c, bf16) - targets[i * 7 + (c - c0)];
-      v = smooth_l1_grad(diff, beta) * gb;
-    }
-    st(grad_reg, i * W + c, v, bf16);
-  }
-}
-
-// ---- stage 2 with separated-classifier groups (SeperateClassifier.roi_cross_entropy_seperated / roi_box_loss_seperated):
-// row i belongs to group sep_id[i]; its cross-entropy runs over that group's columns of the C_tot logits in group-local
-// order with the target column cols[g][label], its box term (class-agnostic regression [n, 7]) counts when label > 0, and
-// both sums of a group are divided by the group's row count n_g, counted here.  Same launches and the same fixed
-// summation order as the plain form, with one accumulator set per group.  A row whose sep_id is outside [0, G) is in no
-// group; a row whose label is outside [0, class_nums[g]) counts in n_g (as such a row counts in n above) and adds nothing.
-// Neither is used as an index; both raise the flag.
-constexpr int kSepPartWords = 3 * kSepMaxGroups + 1;   // per workgroup: cls [8], box [8], rows [8] (int32 bits), flag
-
-__device__ inline RoiRow sep_row_softmax(const void *logits, int64_t i, const SepGroups &q, int g, int bf16) {
-  const int cn = q.class_nums[g];
-  const int64_t o = i * q.C_tot;
-  RoiRow r;
-  r.m = ld(logits, o + q.cols[g][0], bf16);
-  for (int k = 1; k < cn; ++k) r.m = fmaxf(r.m, ld(logits, o + q.cols[g][k], bf16));
-  r.s = 0.f;
-  for (int k = 0; k < cn; ++k) r.s += expf(ld(logits, o + q.cols[g][k], bf16) - r.m);
-  return r;
-}
-
-__global__ __launch_bounds__(256) void k_roi_sep_loss_partial(const void *__restrict__ logits, const void *__restrict__ reg,
-                                                              int bf16, int64_t n, SepGroups q,
-                                                              const int32_t *__restrict__ sep_id,
-                                                              const int64_t *__restrict__ labels,
-                                                              const float *__restrict__ targets, float beta,
-                                                              float *__restrict__ partial) {
-  __shared__ float s_red[2][256];
-  __shared__ int s_cnt[256];
-  __shared__ int s_bad;
-  const int t = threadIdx.x;
-  if (t == 0) s_bad = 0;
-  float cls[kSepMaxGroups], box[kSepMaxGroups];
-  int cnt[kSepMaxGroups];
+  float cls[kSets], box[kSets];
+  int cnt[kSets];
 #pragma unroll
-  for (int g = 0; g < kSepMaxGroups; ++g) { cls[g] = 0.f; box[g] = 0.f; cnt[g] = 0; }
+  for (int g = 0; g < kSets; ++g) { cls[g] = 0.f; box[g] = 0.f; cnt[g] = 0; }
   bool bad = false;
   for (int64_t i = (int64_t)blockIdx.x * 256 + t; i < n; i += (int64_t)gridDim.x * 256) {
-    const int sid = sep_id[i];
-    if (sid < 0 || sid >= q.G) { bad = true; continue; }
+    int sid;
+    if (!f.group_of(i, sid)) { bad = true; continue; }
+    const auto cols = f.cols(sid);
     const int64_t l = labels[i];
     float c = 0.f, b = 0.f;
-    if (l < 0 || l >= q.class_nums[sid]) {
+    if (l < 0 || l >= cols.cn) {
       bad = true;
     } else {
-      const RoiRow r = sep_row_softmax(logits, i, q, sid, bf16);
-      c = (r.m + logf(r.s)) - ld(logits, i * q.C_tot + q.cols[sid][l], bf16);
-      if (l > 0)
-        for (int d = 0; d < 7; ++d) b += smooth_l1_term(fabsf(ld(reg, i * 7 + d, bf16) - targets[i * 7 + d]), beta);
+      const auto x = [&](int k) { return ld(logits, i * C + k, bf16); };
+      const RowSoftmax r = row_softmax(cols, x);
+      c = (r.m + logf(r.s)) - x(cols.col((int)l));
+      if (l > 0) {
+        const int64_t c0 = f.specific() ? i * 7 * C + 7 * l : i * 7;
+        for (int d = 0; d < 7; ++d) b += smooth_l1_term(fabsf(ld(reg, c0 + d, bf16) - targets[i * 7 + d]), beta);
+      }
     }
 #pragma unroll
-    for (int g = 0; g < kSepMaxGroups; ++g)            // (a register per group: no dynamically indexed array)
+    for (int g = 0; g < kSets; ++g)                    // (a register per group: no dynamically indexed array)
       if (g == sid) { cls[g] += c; box[g] += b; cnt[g] += 1; }
   }
   __syncthreads();
   if (bad) s_bad = 1;                                  // (every writer stores the same value)
-  float *out = partial + (int64_t)kSepPartWords * blockIdx.x;
+  float *out = partial + (int64_t)kWords * blockIdx.x;
 #pragma unroll
-  for (int g = 0; g < kSepMaxGroups; ++g) {
-    if (g >= q.G) break;                               // workgroup-uniform
+  for (int g = 0; g < kSets; ++g) {
+    if (g >= f.groups()) break;                        // workgroup-uniform
     __syncthreads();
     s_red[0][t] = cls[g];
     s_red[1][t] = box[g];
-    s_cnt[t] = cnt[g];
+    if constexpr (kGrouped) s_cnt[t] = cnt[g];
     for (int w = 128; w > 0; w >>= 1) {
       __syncthreads();
-      if (t < w) { s_red[0][t] += s_red[0][t + w]; s_red[1][t] += s_red[1][t + w]; s_cnt[t] += s_cnt[t + w]; }
+      if (t < w) {
+        s_red[0][t] += s_red[0][t + w];
+        s_red[1][t] += s_red[1][t + w];
+        if constexpr (kGrouped) s_cnt[t] += s_cnt[t + w];
+      }
     }
     if (t == 0) {
       out[g] = s_red[0][0];
-      out[kSepMaxGroups + g] = s_red[1][0];
-      out[2 * kSepMaxGroups + g] = __int_as_float(s_cnt[0]);
+      out[kSets + g] = s_red[1][0];
+      if constexpr (kGrouped) out[2 * kSets + g] = __int_as_float(s_cnt[0]);
     }
   }
   __syncthreads();
-  if (t == 0) out[3 * kSepMaxGroups] = s_bad ? 1.f : 0.f;
+  if (t == 0) out[kWords - 1] = s_bad ? 1.f : 0.f;
 }
 
-// thread g: group g's sums in workgroup order, / n_g (0 / 0 = NaN for a group without rows); rows[g] = n_g for the backward
-__global__ __launch_bounds__(64) void k_roi_sep_loss_finalize(int nblocks, int G, const float *__restrict__ partial,
-                                                              float *__restrict__ cls_loss, float *__restrict__ box_loss,
-                                                              int32_t *__restrict__ rows, int32_t *__restrict__ flag) {
+// thread g: set g's sums in workgroup order, / its divisor (0 / 0 = NaN for an empty sample or a group without rows, like
+// aabr_rpn_loss_forward); grouped: rows[g] = n_g for the backward
+template <bool kGrouped>
+__global__ __launch_bounds__(64) void k_roi_loss_finalize(int nblocks, int G, const float *__restrict__ partial, int64_t n,
+                                                          float *__restrict__ cls_loss, float *__restrict__ box_loss,
+                                                          int32_t *__restrict__ rows, int32_t *__restrict__ flag) {
+  constexpr int kSets = RoiLossForm<kGrouped>::kSets, kWords = RoiLossForm<kGrouped>::kPartWords;
   const int g = threadIdx.x;
   if (g >= G) return;
   float cls = 0.f, box = 0.f;
   int cnt = 0, bad = 0;
   for (int i = 0; i < nblocks; ++i) {
-    const float *in = partial + (int64_t)kSepPartWords * i;
+    const float *in = partial + (int64_t)kWords * i;
     cls += in[g];
-    box += in[kSepMaxGroups + g];
-    cnt += __float_as_int(in[2 * kSepMaxGroups + g]);
-    bad |= in[3 * kSepMaxGroups] != 0.f;
+    box += in[kSets + g];
+    if (kGrouped) cnt += __float_as_int(in[2 * kSets + g]);
+    bad |= in[kWords - 1] != 0.f;
   }
-  cls_loss[g] = cls / (float)cnt;
-  box_loss[g] = box / (float)cnt;
-  rows[g] = cnt;
+  const float div = kGrouped ? (float)cnt : (float)n;
+  cls_loss[g] = cls / div;
+  box_loss[g] = box / div;
+  if (kGrouped) rows[g] = cnt;
   if (g == 0) *flag = bad;
 }
 
-// one thread per row writes the row's C_tot logit gradients and its 7 regression gradients: zeros in every column outside
-// the row's group, and in the whole row when its sep_id or label is out of range
-__global__ __launch_bounds__(256) void k_roi_sep_loss_backward(const void *__restrict__ logits, const void *__restrict__ reg,
-                                                               int bf16, int64_t n, SepGroups q,
-                                                               const int32_t *__restrict__ sep_id,
-                                                               const int64_t *__restrict__ labels,
-                                                               const float *__restrict__ targets, float beta,
-                                                               const int32_t *__restrict__ rows,
-                                                               const float *__restrict__ g_cls, const float *__restrict__ g_box,
-                                                               void *__restrict__ grad_logits, void *__restrict__ grad_reg) {
+// one thread per row writes the row's logit gradients and its regression gradients, zeros included.  Plain: each of the
+// C + 7 C (or 7) elements is stored once.  Grouped: zeros over the C_tot columns, then the group's own columns over them.
+template <bool kGrouped>
+__global__ __launch_bounds__(256) void k_roi_loss_backward(const void *__restrict__ logits, const void *__restrict__ reg,
+                                                           int bf16, int64_t n, RoiLossForm<kGrouped> f,
+                                                           const int64_t *__restrict__ labels,
+                                                           const float *__restrict__ targets, float beta,
+                                                           const int32_t *__restrict__ rows,
+                                                           const float *__restrict__ g_cls, const float *__restrict__ g_box,
+                                                           void *__restrict__ grad_logits, void *__restrict__ grad_reg) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const int C = q.C_tot;
-  const int sid = sep_id[i];
+  const int C = f.width();
   const int64_t l = labels[i];
-  const bool ok = sid >= 0 && sid < q.G && l >= 0 && l < q.class_nums[sid];
-  for (int k = 0; k < C; ++k) st(grad_logits, i * C + k, 0.f, bf16);
+  int sid;
+  const bool ok = f.group_of(i, sid) && l >= 0 && l < f.cols(sid).cn;
+  if (kGrouped)
+    for (int k = 0; k < C; ++k) st(grad_logits, i * C + k, 0.f, bf16);
   float gb = 0.f;
-  if (ok) {                                            // the group's own columns, over the zeros just written
-    const float ng = (float)rows[sid];
-    const RoiRow r = sep_row_softmax(logits, i, q, sid, bf16);
-    const float gc = g_cls[sid] / ng;
-    gb = g_box[sid] / ng;
-    for (int k = 0; k < q.class_nums[sid]; ++k) {
-      const int64_t o = i * C + q.cols[sid][k];
-      const float pk = expf(ld(logits, o, bf16) - r.m) / r.s;
-      st(grad_logits, o, (pk - (k == l ? 1.f : 0.f)) * gc, bf16);
+  if (ok) {
+    const auto cols = f.cols(sid);
+    const float div = kGrouped ? (float)rows[sid] : (float)n;
+    const auto x = [&](int k) { return ld(logits, i * C + k, bf16); };
+    const RowSoftmax r = row_softmax(cols, x);
+    const float gc = g_cls[sid] / div;
+    gb = g_box[sid] / div;
+    for (int k = 0; k < cols.cn; ++k) {
+      const int c = cols.col(k);
+      st(grad_logits, i * C + c, (r.prob(x(c)) - (k == l ? 1.f : 0.f)) * gc, bf16);
     }
+  } else if (!kGrouped) {
+    for (int k = 0; k < C; ++k) st(grad_logits, i * C + k, 0.f, bf16);
   }
-  for (int d = 0; d < 7; ++d) {
+  const int W = f.specific() ? 7 * C : 7;
+  const int c0 = ok && l > 0 ? (f.specific() ? 7 * (int)l : 0) : -7;   // first column of the row's own box, or none
+  for (int c = 0; c < W; ++c) {
     float v = 0.f;
-    if (ok && l > 0) v = smooth_l1_grad(ld(reg, i * 7 + d, bf16) - targets[i * 7 + d], beta) * gb;
-    st(grad_reg, i * 7 + d, v, bf16);
+    if (c >= c0 && c < c0 + 7 && c0 >= 0) v = smooth_l1_grad(ld(reg, i * W + c, bf16) - targets[i * 7 + (c - c0)], beta) * gb;
+    st(grad_reg, i * W + c, v, bf16);
   }
 }
 
@@ -664,28 +597,73 @@ extern "C" int aabr_roi_targets(const float *proposals, const float *targets, co
                                 scratch, stream_);
 }
 
-extern "C" int64_t aabr_roi_box_loss_scratch_floats(void) { return 3 * kRoiLossBlocks; }
+// ---- stage 2: the four entry points, one runner per direction ------------------------------------------------------------
+extern "C" int64_t aabr_roi_box_loss_scratch_floats(void) { return RoiLossForm<false>::kPartWords * kRoiLossBlocks; }
+extern "C" int64_t aabr_roi_box_loss_grouped_scratch_floats(void) {
+  return (int64_t)RoiLossForm<true>::kPartWords * kRoiLossBlocks;
+}
 
 static int roi_loss_blocks(int64_t n) {
   int64_t nblk = ceil_div(n, 256);
   return (int)(nblk < 1 ? 1 : (nblk > kRoiLossBlocks ? kRoiLossBlocks : nblk));
 }
 
+// The body of both forward entry points, reported under the caller's name `fn`.  `groups` null: the plain loss over C
+// columns.  Else the grouped one: C = C_tot, class-agnostic regression, `sep_id` int32 [n], group_rows int32 [G].
+static int roi_loss_forward_run(const char *fn, const SepGroups *groups, const int32_t *sep_id, const void *class_logits,
+                                const void *box_regression, int input_bf16, int64_t n, int C, int class_specific,
+                                const int64_t *labels, const float *regression_targets, float beta, float *cls_loss,
+                                float *box_loss, int32_t *group_rows, int32_t *flag, float *scratch, hipStream_t st) {
+  AABR_CHECK_ARG_AS(fn, n >= 0 && C >= 1 && beta > 0.f, groups ? "need n >= 0, beta > 0" : "need n >= 0, C >= 1, beta > 0");
+  AABR_CHECK_ARG_AS(fn, n * 7 * (int64_t)C < ((int64_t)1 << 31),
+                    groups ? "n * 7 C_tot must stay below 2^31" : "n * 7 C must stay below 2^31");
+  AABR_CHECK_ARG_AS(fn, cls_loss && box_loss && (!groups || group_rows) && flag && scratch, "null pointer");
+  AABR_CHECK_ARG_AS(fn, n == 0 || (class_logits && box_regression && (!groups || sep_id) && labels && regression_targets),
+                    "null pointer");
+  const int nblk = roi_loss_blocks(n);
+  const auto launch = [&](auto f, int G) {
+    constexpr bool kGrouped = decltype(f)::kIsGrouped;
+    hipLaunchKernelGGL(k_roi_loss_partial<kGrouped>, dim3((unsigned)nblk), dim3(256), 0, st, class_logits, box_regression,
+                       input_bf16 ? 1 : 0, n, f, labels, regression_targets, beta, scratch);
+    hipLaunchKernelGGL(k_roi_loss_finalize<kGrouped>, dim3(1), dim3(64), 0, st, nblk, G, scratch, n, cls_loss, box_loss,
+                       group_rows, flag);
+  };
+  if (groups) launch(RoiLossForm<true>{*groups, sep_id}, groups->G);
+  else launch(RoiLossForm<false>{C, class_specific ? 1 : 0}, 1);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+static int roi_loss_backward_run(const char *fn, const SepGroups *groups, const int32_t *sep_id, const void *class_logits,
+                                 const void *box_regression, int input_bf16, int64_t n, int C, int class_specific,
+                                 const int64_t *labels, const float *regression_targets, float beta,
+                                 const int32_t *group_rows, const float *grad_cls_loss, const float *grad_box_loss,
+                                 void *grad_logits, void *grad_regression, hipStream_t st) {
+  AABR_CHECK_ARG_AS(fn, n >= 0 && C >= 1 && beta > 0.f, groups ? "need n >= 0, beta > 0" : "need n >= 0, C >= 1, beta > 0");
+  AABR_CHECK_ARG_AS(fn, n * 7 * (int64_t)C < ((int64_t)1 << 31),
+                    groups ? "n * 7 C_tot must stay below 2^31" : "n * 7 C must stay below 2^31");
+  AABR_CHECK_ARG_AS(fn, (!groups || group_rows) && grad_cls_loss && grad_box_loss, "null pointer");
+  if (n == 0) return AABR_OK;
+  AABR_CHECK_ARG_AS(fn, class_logits && box_regression && (!groups || sep_id) && labels && regression_targets &&
+                            grad_logits && grad_regression, "null pointer");
+  const auto launch = [&](auto f) {
+    hipLaunchKernelGGL(k_roi_loss_backward<decltype(f)::kIsGrouped>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st,
+                       class_logits, box_regression, input_bf16 ? 1 : 0, n, f, labels, regression_targets, beta, group_rows,
+                       grad_cls_loss, grad_box_loss, grad_logits, grad_regression);
+  };
+  if (groups) launch(RoiLossForm<true>{*groups, sep_id});
+  else launch(RoiLossForm<false>{C, class_specific ? 1 : 0});
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
 extern "C" int aabr_roi_box_loss_forward(const void *class_logits, const void *box_regression, int input_bf16, int64_t n,
                                          int C, int class_specific, const int64_t *labels,
                                          const float *regression_targets, float beta, float *cls_loss, float *box_loss,
                                          int32_t *flag, float *scratch, void *stream_) {
-  hipStream_t st = (hipStream_t)stream_;
-  AABR_CHECK_ARG(n >= 0 && C >= 1 && beta > 0.f, "need n >= 0, C >= 1, beta > 0");
-  AABR_CHECK_ARG(n * 7 * (int64_t)C < ((int64_t)1 << 31), "n * 7 C must stay below 2^31");
-  AABR_CHECK_ARG(cls_loss && box_loss && flag && scratch, "null pointer");
-  AABR_CHECK_ARG(n == 0 || (class_logits && box_regression && labels && regression_targets), "null pointer");
-  const int nblk = roi_loss_blocks(n);
-  hipLaunchKernelGGL(k_roi_loss_partial, dim3((unsigned)nblk), dim3(256), 0, st, class_logits, box_regression,
-                     input_bf16 ? 1 : 0, n, C, class_specific ? 1 : 0, labels, regression_targets, beta, scratch);
-  hipLaunchKernelGGL(k_roi_loss_finalize, dim3(1), dim3(64), 0, st, nblk, scratch, n, cls_loss, box_loss, flag);
-  AABR_CHECK_LAUNCH();
-  return AABR_OK;
+  return roi_loss_forward_run(__func__, nullptr, nullptr, class_logits, box_regression, input_bf16, n, C, class_specific,
+                              labels, regression_targets, beta, cls_loss, box_loss, nullptr, flag, scratch,
+                              (hipStream_t)stream_);
 }
 
 extern "C" int aabr_roi_box_loss_backward(const void *class_logits, const void *box_regression, int input_bf16, int64_t n,
@@ -693,21 +671,10 @@ extern "C" int aabr_roi_box_loss_backward(const void *class_logits, const void *
                                           const float *regression_targets, float beta, const float *grad_cls_loss,
                                           const float *grad_box_loss, void *grad_logits, void *grad_regression,
                                           void *stream_) {
-  AABR_CHECK_ARG(n >= 0 && C >= 1 && beta > 0.f, "need n >= 0, C >= 1, beta > 0");
-  AABR_CHECK_ARG(n * 7 * (int64_t)C < ((int64_t)1 << 31), "n * 7 C must stay below 2^31");
-  AABR_CHECK_ARG(grad_cls_loss && grad_box_loss, "null pointer");
-  if (n == 0) return AABR_OK;
-  AABR_CHECK_ARG(class_logits && box_regression && labels && regression_targets && grad_logits && grad_regression,
-                 "null pointer");
-  hipLaunchKernelGGL(k_roi_loss_backward, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream_,
-                     class_logits, box_regression, input_bf16 ? 1 : 0, n, C, class_specific ? 1 : 0, labels,
-                     regression_targets, beta, grad_cls_loss, grad_box_loss, grad_logits, grad_regression);
-  AABR_CHECK_LAUNCH();
-  return AABR_OK;
+  return roi_loss_backward_run(__func__, nullptr, nullptr, class_logits, box_regression, input_bf16, n, C, class_specific,
+                               labels, regression_targets, beta, nullptr, grad_cls_loss, grad_box_loss, grad_logits,
+                               grad_regression, (hipStream_t)stream_);
 }
-
-// ---- the separated-classifier groups: stage 2 ---------------------------------------------------------------------------
-extern "C" int64_t aabr_roi_box_loss_grouped_scratch_floats(void) { return (int64_t)kSepPartWords * kRoiLossBlocks; }
 
 extern "C" int aabr_roi_box_loss_grouped_forward(const void *class_logits, const void *box_regression, int input_bf16,
                                                  int64_t n, int G, int C_tot, const int32_t *class_nums_host,
@@ -715,21 +682,11 @@ extern "C" int aabr_roi_box_loss_grouped_forward(const void *class_logits, const
                                                  const float *regression_targets, float beta, float *cls_loss,
                                                  float *box_loss, int32_t *group_rows, int32_t *flag, float *scratch,
                                                  void *stream_) {
-  hipStream_t st = (hipStream_t)stream_;
   SepGroups q;
   int rc = fill_sep_groups(q, __func__, G, C_tot, class_nums_host, cols_host);
   if (rc != AABR_OK) return rc;
-  AABR_CHECK_ARG(n >= 0 && beta > 0.f, "need n >= 0, beta > 0");
-  AABR_CHECK_ARG(n * 7 * (int64_t)C_tot < ((int64_t)1 << 31), "n * 7 C_tot must stay below 2^31");
-  AABR_CHECK_ARG(cls_loss && box_loss && group_rows && flag && scratch, "null pointer");
-  AABR_CHECK_ARG(n == 0 || (class_logits && box_regression && sep_id && labels && regression_targets), "null pointer");
-  const int nblk = roi_loss_blocks(n);
-  hipLaunchKernelGGL(k_roi_sep_loss_partial, dim3((unsigned)nblk), dim3(256), 0, st, class_logits, box_regression,
-                     input_bf16 ? 1 : 0, n, q, sep_id, labels, regression_targets, beta, scratch);
-  hipLaunchKernelGGL(k_roi_sep_loss_finalize, dim3(1), dim3(64), 0, st, nblk, G, scratch, cls_loss, box_loss, group_rows,
-                     flag);
-  AABR_CHECK_LAUNCH();
-  return AABR_OK;
+  return roi_loss_forward_run(__func__, &q, sep_id, class_logits, box_regression, input_bf16, n, C_tot, 0, labels,
+                              regression_targets, beta, cls_loss, box_loss, group_rows, flag, scratch, (hipStream_t)stream_);
 }
 
 extern "C" int aabr_roi_box_loss_grouped_backward(const void *class_logits, const void *box_regression, int input_bf16,
@@ -741,15 +698,7 @@ extern "C" int aabr_roi_box_loss_grouped_backward(const void *class_logits, cons
   SepGroups q;
   int rc = fill_sep_groups(q, __func__, G, C_tot, class_nums_host, cols_host);
   if (rc != AABR_OK) return rc;
-  AABR_CHECK_ARG(n >= 0 && beta > 0.f, "need n >= 0, beta > 0");
-  AABR_CHECK_ARG(n * 7 * (int64_t)C_tot < ((int64_t)1 << 31), "n * 7 C_tot must stay below 2^31");
-  AABR_CHECK_ARG(group_rows && grad_cls_loss && grad_box_loss, "null pointer");
-  if (n == 0) return AABR_OK;
-  AABR_CHECK_ARG(class_logits && box_regression && sep_id && labels && regression_targets && grad_logits && grad_regression,
-                 "null pointer");
-  hipLaunchKernelGGL(k_roi_sep_loss_backward, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream_,
-                     class_logits, box_regression, input_bf16 ? 1 : 0, n, q, sep_id, labels, regression_targets, beta,
-                     group_rows, grad_cls_loss, grad_box_loss, grad_logits, grad_regression);
-  AABR_CHECK_LAUNCH();
-  return AABR_OK;
+  return roi_loss_backward_run(__func__, &q, sep_id, class_logits, box_regression, input_bf16, n, C_tot, 0, labels,
+                               regression_targets, beta, group_rows, grad_cls_loss, grad_box_loss, grad_logits,
+                               grad_regression, (hipStream_t)stream_);
 }

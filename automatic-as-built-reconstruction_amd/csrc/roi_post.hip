@@ -35,7 +35,7 @@
 // Limits (validated): 2 <= C <= 32, 1 <= nb <= 16, 1 <= post_max <= pre_max <= 2048, N * C * 7 < 2^31.
 // A scene with n_b = 0, a segment without a candidate and N = 0 are legal and give empty lists.
 // With separated-classifier groups (sep_groups.h, aabr_roi_post_detections_grouped) the same five launches: the row
-// kernel's softmax runs over the row's group columns (k_roi_post_rows_sep), a segment is a foreground column of a group,
+// kernel's softmax runs over the row's group columns (k_roi_post_rows<.., true>), a segment is a foreground column of a group,
 // candidates are tested for group membership, and the detections_per_img cut is taken per (scene, group).
 #include "common.h"
 #include "nms_shared.h"
@@ -119,20 +119,40 @@ __device__ __forceinline__ uint32_t block_select_kth(int n, int need, F get, int
   return prefix;
 }
 
-// kCorner: the regressions are decoded with BoxCoder3D(is_corner_roi=True).decode (box_decode7_corner, corner_box.h)
-template <bool kCorner>
+// One thread per row: the row's softmax (row_softmax, sep_groups.h) and its decodes.
+// kCorner: the regressions are decoded with BoxCoder3D(is_corner_roi=True).decode (box_decode7_corner, corner_box.h).
+// kSep false: prob [N, C] over all columns; one decode per row when reg_classes == 1, else one per class; boxes [N, C, 7].
+// kSep (SeperateClassifier.post_processor): row i belongs to group sep_id[i]; its softmax runs over that group's columns
+// only, summed in group-local order, and every other column of prob is an exact 0.  The regression is class agnostic:
+// one decode, boxes [N, 7].  A sep_id outside [0, G) is never used as an index: the row's prob is all 0, it is no group's
+// candidate, and word 5 of its scene's info block is raised.
+template <bool kCorner, bool kSep>
 __global__ __launch_bounds__(256) void k_roi_post_rows(const float *__restrict__ logits, const float *__restrict__ reg,
-                                                       const float *__restrict__ props, int64_t N, RoiPostParams p,
-                                                       float *__restrict__ prob, float *__restrict__ boxes) {
+                                                       const float *__restrict__ props,
+                                                       const int32_t *__restrict__ sep_id, int64_t N, RoiPostParams p,
+                                                       SepGroups sg, float *__restrict__ prob, float *__restrict__ boxes,
+                                                       int32_t *__restrict__ info) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   const int C = p.C;
   const float *x = logits + i * C;
-  float m = x[0];
-  for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
-  float s = expf(x[0] - m);
-  for (int c = 1; c < C; ++c) s += expf(x[c] - m);     // class order: C - 1 additions
-  for (int c = 0; c < C; ++c) prob[i * C + c] = expf(x[c] - m) / s;
+  const auto softmax_over = [&](const auto &cols) {
+    const RowSoftmax r = row_softmax(cols, [&](int c) { return x[c]; });
+    for (int k = 0; k < cols.cn; ++k) prob[i * C + cols.col(k)] = r.prob(x[cols.col(k)]);
+  };
+  if (kSep) {
+    for (int c = 0; c < C; ++c) prob[i * C + c] = 0.0f;
+    const int g = sep_id[i];
+    if (g >= 0 && g < sg.G) {
+      softmax_over(RowCols<true>(sg, g));
+    } else {
+      int b = 0;
+      while (b + 1 < p.nb && i >= p.row_begin[b + 1]) ++b;
+      atomicOr(&info[b * kRoiInfoWords + 5], 1);
+    }
+  } else {
+    softmax_over(RowCols<false>{C});
+  }
   float an[7], o[7];
 #pragma unroll
   for (int d = 0; d < 7; ++d) an[d] = props[7 * i + d];
@@ -140,49 +160,14 @@ __global__ __launch_bounds__(256) void k_roi_post_rows(const float *__restrict__
     if (kCorner) box_decode7_corner(e, an, p.w.w, p.clip, o);
     else box_decode7(e, an, p.w, p.clip, o);
   };
-  if (p.reg_classes == 1) decode(reg + 7 * i);
-  for (int c = 0; c < C; ++c) {
-    if (p.reg_classes != 1) decode(reg + 7 * (i * C + c));
+  const bool per_class = !kSep && p.reg_classes != 1;
+  const int nbox = kSep ? 1 : C;                       // boxes stored per row
+  if (!per_class) decode(reg + 7 * i);
+  for (int c = 0; c < nbox; ++c) {
+    if (per_class) decode(reg + 7 * (i * C + c));
 #pragma unroll
-    for (int d = 0; d < 7; ++d) boxes[7 * (i * C + c) + d] = o[d];
+    for (int d = 0; d < 7; ++d) boxes[7 * (i * nbox + c) + d] = o[d];
   }
-}
-
-// The separated-classifier form (SeperateClassifier.post_processor): row i belongs to group sep_id[i]; its softmax runs
-// over that group's columns only, summed in group-local order, and every other column of prob is an exact 0.  The
-// regression is class agnostic: boxes is [N, 7].  A sep_id outside [0, G) is never used as an index: the row's prob is
-// all 0, it is no group's candidate, and word 5 of its scene's info block is raised.
-template <bool kCorner>
-__global__ __launch_bounds__(256) void k_roi_post_rows_sep(const float *__restrict__ logits, const float *__restrict__ reg,
-                                                           const float *__restrict__ props,
-                                                           const int32_t *__restrict__ sep_id, int64_t N, RoiPostParams p,
-                                                           SepGroups sg, float *__restrict__ prob,
-                                                           float *__restrict__ boxes, int32_t *__restrict__ info) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  const int C = p.C;
-  const float *x = logits + i * C;
-  for (int c = 0; c < C; ++c) prob[i * C + c] = 0.0f;
-  const int g = sep_id[i];
-  if (g >= 0 && g < sg.G) {
-    const int cn = sg.class_nums[g];
-    float m = x[sg.cols[g][0]];
-    for (int k = 1; k < cn; ++k) m = fmaxf(m, x[sg.cols[g][k]]);
-    float s = expf(x[sg.cols[g][0]] - m);
-    for (int k = 1; k < cn; ++k) s += expf(x[sg.cols[g][k]] - m);   // group-local order: cn - 1 additions
-    for (int k = 0; k < cn; ++k) prob[i * C + sg.cols[g][k]] = expf(x[sg.cols[g][k]] - m) / s;
-  } else {
-    int b = 0;
-    while (b + 1 < p.nb && i >= p.row_begin[b + 1]) ++b;
-    atomicOr(&info[b * kRoiInfoWords + 5], 1);
-  }
-  float an[7], o[7];
-#pragma unroll
-  for (int d = 0; d < 7; ++d) an[d] = props[7 * i + d];
-  if (kCorner) box_decode7_corner(reg + 7 * i, an, p.w.w, p.clip, o);
-  else box_decode7(reg + 7 * i, an, p.w, p.clip, o);
-#pragma unroll
-  for (int d = 0; d < 7; ++d) boxes[7 * i + d] = o[d];
 }
 
 // kSep: the segments of a scene are the foreground columns of all groups (sg.fg_col, in (group, group-local) order); the
@@ -392,7 +377,7 @@ __global__ __launch_bounds__(1024) void k_roi_post_scene(RoiPostParams p, RoiPos
     }
     int32_t *w = info + (int64_t)b * kRoiInfoWords;
     w[0] = out; w[1] = M; w[2] = cand; w[3] = big; w[4] = most; w[6] = 0; w[7] = 0;
-    if (!kSep) w[5] = 0;                               // (kSep: k_roi_post_rows_sep's flag for a sep_id out of range)
+    if (!kSep) w[5] = 0;                               // (kSep: k_roi_post_rows's flag for a sep_id out of range)
   }
 }
 
@@ -494,35 +479,24 @@ static int roi_post_detections(const char *fn, const SepGroups *groups, const in
   const int64_t cap = (int64_t)(groups ? q.nf : C - 1) * post_max;
   const int64_t longest = n_max < pre_max ? n_max : pre_max;     // no sorted list is longer
   const dim3 row_grid((unsigned)ceil_div(N, (int64_t)256));
-  if (groups) {
-    if (S == 0) return AABR_OK;                        // no group has a foreground column: nothing can be detected
-    if (corner_coder)
-      hipLaunchKernelGGL(k_roi_post_rows_sep<true>, row_grid, dim3(256), 0, st, class_logits, box_regression, proposals,
-                         sep_id, N, p, q, u.prob, u.boxes, info);
-    else
-      hipLaunchKernelGGL(k_roi_post_rows_sep<false>, row_grid, dim3(256), 0, st, class_logits, box_regression, proposals,
-                         sep_id, N, p, q, u.prob, u.boxes, info);
-    hipLaunchKernelGGL(k_roi_post_select<true>, dim3((unsigned)S), dim3(1024), 0, st, p, u, q, sep_id);
-  } else {
-    if (corner_coder)
-      hipLaunchKernelGGL(k_roi_post_rows<true>, row_grid, dim3(256), 0, st, class_logits, box_regression, proposals, N, p,
-                         u.prob, u.boxes);
-    else
-      hipLaunchKernelGGL(k_roi_post_rows<false>, row_grid, dim3(256), 0, st, class_logits, box_regression, proposals, N, p,
-                         u.prob, u.boxes);
-    hipLaunchKernelGGL(k_roi_post_select<false>, dim3((unsigned)S), dim3(1024), 0, st, p, u, q, sep_id);
-  }
-  hipLaunchKernelGGL(k_roi_post_mask,
-                     dim3((unsigned)ceil_div(longest, (int64_t)kNmsRows), (unsigned)ceil_div(longest, (int64_t)64),
-                          (unsigned)S),
-                     dim3(256), 0, st, p, u);
-  hipLaunchKernelGGL(k_roi_post_scan, dim3((unsigned)S), dim3(256), 0, st, p, u);
-  if (groups)
-    hipLaunchKernelGGL(k_roi_post_scene<true>, dim3((unsigned)nb), dim3(1024), 0, st, p, u, q, cap, det_rows, det_labels,
+  if (groups && S == 0) return AABR_OK;                // no group has a foreground column: nothing can be detected
+  const auto launch = [&](auto corner, auto sep) {     // the five launches of one (coder, groups) form
+    constexpr bool kCorner = decltype(corner)::value, kSep = decltype(sep)::value;
+    hipLaunchKernelGGL((k_roi_post_rows<kCorner, kSep>), row_grid, dim3(256), 0, st, class_logits, box_regression,
+                       proposals, sep_id, N, p, q, u.prob, u.boxes, info);
+    hipLaunchKernelGGL(k_roi_post_select<kSep>, dim3((unsigned)S), dim3(1024), 0, st, p, u, q, sep_id);
+    hipLaunchKernelGGL(k_roi_post_mask,
+                       dim3((unsigned)ceil_div(longest, (int64_t)kNmsRows), (unsigned)ceil_div(longest, (int64_t)64),
+                            (unsigned)S),
+                       dim3(256), 0, st, p, u);
+    hipLaunchKernelGGL(k_roi_post_scan, dim3((unsigned)S), dim3(256), 0, st, p, u);
+    hipLaunchKernelGGL(k_roi_post_scene<kSep>, dim3((unsigned)nb), dim3(1024), 0, st, p, u, q, cap, det_rows, det_labels,
                        det_scores, det_boxes, info);
-  else
-    hipLaunchKernelGGL(k_roi_post_scene<false>, dim3((unsigned)nb), dim3(1024), 0, st, p, u, q, cap, det_rows, det_labels,
-                       det_scores, det_boxes, info);
+  };
+  const std::true_type yes;
+  const std::false_type no;
+  if (groups) corner_coder ? launch(yes, yes) : launch(no, yes);
+  else corner_coder ? launch(yes, no) : launch(no, no);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }

@@ -20,6 +20,37 @@ struct SepGroups {
   uint8_t fg_begin[kSepMaxGroups + 1];         // group g's foreground columns are fg_begin[g] .. fg_begin[g + 1]
 };
 
+// The columns one row's softmax runs over.  Plain (RowCols<false>): all cn = C columns, column k is k -- no table, so C
+// has no upper limit here.  Grouped (RowCols<true>): group g's cn = class_nums[g] columns, column k is cols[g][k].
+template <bool kGrouped> struct RowCols;
+template <> struct RowCols<false> {
+  int cn;
+  __device__ int col(int k) const { return k; }
+};
+template <> struct RowCols<true> {
+  const SepGroups &q;
+  int g, cn;
+  __device__ RowCols(const SepGroups &q_, int g_) : q(q_), g(g_), cn(q_.class_nums[g_]) {}
+  __device__ int col(int k) const { return q.cols[g][k]; }
+};
+
+// The softmax statistics of one row, the one statement of them for the loss kernels (roi_loss.hip: x reads fp32 or bf16)
+// and the post-processor (roi_post.hip: fp32): x(c) is the row's logit in column c; the maximum over the view's columns
+// in order, then the sum of expf(x - m) in the same order.
+struct RowSoftmax {
+  float m, s;
+  __device__ float prob(float x) const { return expf(x - m) / s; }
+};
+template <class Cols, class Load>
+__device__ inline RowSoftmax row_softmax(const Cols &c, Load x) {
+  RowSoftmax r;
+  r.m = x(c.col(0));
+  for (int k = 1; k < c.cn; ++k) r.m = fmaxf(r.m, x(c.col(k)));
+  r.s = 0.f;
+  for (int k = 0; k < c.cn; ++k) r.s += expf(x(c.col(k)) - r.m);
+  return r;
+}
+
 // class_nums_host int32 [G], cols_host int32 [sum of class_nums]: the groups' column lists one after the other
 inline int fill_sep_groups(SepGroups &q, const char *fn, int G, int C_tot, const int32_t *class_nums_host,
                            const int32_t *cols_host) {

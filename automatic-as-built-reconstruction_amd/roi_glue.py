@@ -12,8 +12,6 @@ roi_box_predictors.py:105-109).  The corner form of the head (MODEL.CORNER_ROI):
 of the convolution rows, forward_corner_box, roi_box_feature_extractors.py:122-147) and `box_predictions_corner`
 (roi_box_predictors.py:79-103); `box_head_targets` / `box_detections` take the coder's form from the BoxCoder3D they are
 given."""
-import ctypes as C
-
 import torch
 
 import _hip
@@ -89,38 +87,52 @@ def box_detections(class_logits, box_regression, proposals, score_thresh=0.05, n
     proposal row each detection came from).  All launches go out without a host read; the one read (the counts) is at
     the end -- `defer=True` returns the function that does it, as rpn_glue.rpn_proposals does.  `debug` (a dict)
     receives `prob` [N, C] and `boxes` [N, C, 7]."""
+    return _detections(class_logits, box_regression, proposals, None, None, class_specific, score_thresh, nms,
+                       nms_aug_thickness, detections_per_img, weights, bbox_xform_clip, box_coder, defer, debug)
+
+
+def _detections(class_logits, box_regression, proposals, sep_id, tables, class_specific, score_thresh, nms,
+                nms_aug_thickness, detections_per_img, weights, bbox_xform_clip, box_coder, defer, debug):
+    """box_detections (`tables` None) and box_detections_grouped (`tables` = (G, C_tot, class_nums, cols) of
+    sep_group_tables, `sep_id` [N]; class-agnostic regression) as one path: casts and shape checks, the proposals
+    concatenated, the empty case, the coder's arguments, scratch, outputs and debug buffers, the one library call and the
+    finish()"""
     lib = _hip.load()
     _hip.require_gpu(class_logits)
     dev = class_logits.device
     logits = class_logits.to(torch.float32).contiguous()
     reg = box_regression.to(device=dev, dtype=torch.float32).contiguous()
     N, nc = int(logits.shape[0]), int(logits.shape[1])
-    if class_specific is None:
-        class_specific = reg.shape[1] == 7 * nc and nc != 1
-    if reg.shape[0] != N or reg.shape[1] != (7 * nc if class_specific else 7):
-        raise ValueError("box_regression must be [N, %d], got %s" % (7 * nc if class_specific else 7, tuple(reg.shape)))
+    if tables is not None:
+        if nc != tables[1]:
+            raise ValueError("class_logits must be [N, %d] (C_tot of the groups), got %s" % (tables[1], tuple(logits.shape)))
+        if tuple(reg.shape) != (N, 7):
+            raise ValueError("box_regression must be [%d, 7] (class agnostic with groups), got %s" % (N, tuple(reg.shape)))
+    else:
+        if class_specific is None:
+            class_specific = reg.shape[1] == 7 * nc and nc != 1
+        if reg.shape[0] != N or reg.shape[1] != (7 * nc if class_specific else 7):
+            raise ValueError("box_regression must be [N, %d], got %s" % (7 * nc if class_specific else 7, tuple(reg.shape)))
     n_b = [int(p.shape[0]) for p in proposals]
     nb = len(n_b)
     if nb == 0 and N == 0:
         return (lambda: []) if defer else []
+    if tables is not None and (sum(n_b) != N or sep_id.numel() != N):
+        raise ValueError("the proposals have %d rows, sep_id %d, class_logits %d" % (sum(n_b), sep_id.numel(), N))
     if sum(n_b) != N:
         raise ValueError("the proposals have %d rows, class_logits %d" % (sum(n_b), N))
-    props = (torch.cat([p.reshape(-1, 7) for p in proposals]) if nb else logits.new_zeros((0, 7)))
-    props = props.to(device=dev, dtype=torch.float32).contiguous()
-    head = (ptr(logits), ptr(reg), ptr(props), nb, (C.c_int64 * nb)(*n_b), nc, int(bool(class_specific)))
-    return _detections("box_detections", "(2 <= classes <= 32, 1 <= scenes <= 16): C=%d nb=%d",
-                       lib.aabr_roi_post_detections_coder, head, dev, n_b, nc, (nc - 1) * POST_NMS, (N, nc, 7),
-                       score_thresh, nms, nms_aug_thickness, detections_per_img, weights, bbox_xform_clip, box_coder, defer,
-                       debug)
-
-
-def _detections(fn, limits, entry, head, dev, n_b, nc, cap, boxes_shape, score_thresh, nms, nms_aug_thickness,
-                detections_per_img, weights, bbox_xform_clip, box_coder, defer, debug):
-    """what box_detections and box_detections_grouped (`fn`, for the message) share: the coder's arguments, the scratch
-    for `nc` columns, the outputs with `cap` rows per scene, the debug buffers (`boxes_shape`: of the decoded boxes), the
-    library call `entry(*head, <the common tail>)` and the finish()"""
-    lib = _hip.load()
-    nb, N = len(n_b), sum(n_b)
+    props = torch.cat([p.reshape(-1, 7) for p in proposals]).to(device=dev, dtype=torch.float32).contiguous()
+    if tables is not None:
+        sid = sep_id.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+        fn, limits = "box_detections_grouped", "(1 <= scenes <= 16): C_tot=%d nb=%d"
+        entry = lib.aabr_roi_post_detections_grouped
+        head = (ptr(logits), ptr(reg), ptr(props), ptr(sid), nb, _hip.i64xn(n_b)) + tuple(tables)
+        cap, boxes_shape = (nc - tables[0]) * POST_NMS, (N, 7)
+    else:
+        fn, limits = "box_detections", "(2 <= classes <= 32, 1 <= scenes <= 16): C=%d nb=%d"
+        entry = lib.aabr_roi_post_detections_coder
+        head = (ptr(logits), ptr(reg), ptr(props), nb, _hip.i64xn(n_b), nc, int(bool(class_specific)))
+        cap, boxes_shape = (nc - 1) * POST_NMS, (N, nc, 7)
     aug = (0.0, 0.0) if nms_aug_thickness is None else nms_aug_thickness
     w = (1.0,) * 7 if weights is None else [float(v) for v in torch.as_tensor(weights).reshape(-1).tolist()]
     corner = 0
@@ -184,9 +196,11 @@ def _targets_inputs(proposals, targets, target_labels, aug_thickness, weights, b
     return dev, n_b, g_b, props, tg, tl, aug, w, corner, int(draw_seed() if seed is None else seed) & 0xffffffff
 
 
-def _targets_buffers(N, S, B, words, dev):
-    """the per-proposal arrays over N rows and the padded samples of S segments, keyed as `debug` receives them (and in
-    the order the library takes them), and the address of the aligned scratch of `words` words"""
+def _targets_run(entry, head, iou, N, S, B, words, dev, aug, fg_iou, bg_iou, w, corner, seed, positive_fraction, info):
+    """the library call of box_head_targets and box_head_targets_grouped, `entry(*head, <what both take alike>)`: the
+    per-proposal arrays over N rows and the padded samples of S segments, keyed as `debug` receives them (and in the order
+    the library takes them), the aligned scratch of `words` words, `iou` = the arguments between the two sets (the plain
+    entry's matrix, nothing for the grouped one) -> the arrays"""
     scratch = _hip.workspace("roi_targets", words + 2, torch.int32, dev)
     off = (-scratch.data_ptr() // 4) % 2                                  # 8-byte alignment of the first word
     i64, f32 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float32, device=dev)
@@ -194,7 +208,23 @@ def _targets_buffers(N, S, B, words, dev):
             "labels": torch.empty(N, **i64), "regression_targets": torch.empty((N, 7), **f32),
             "samp_rows": torch.empty((S, B), **i64), "samp_labels": torch.empty((S, B), **i64),
             "samp_targets": torch.empty((S, B, 7), **f32), "samp_boxes": torch.empty((S, B, 7), **f32)}
-    return bufs, scratch.data_ptr() + 4 * off
+    per_row, samples = list(bufs.values())[:4], list(bufs.values())[4:]
+    check(entry(*head, _hip.f32x4(aug), -1, int(_nms.REFERENCE_DEBUG_ONLY_XY), float(fg_iou), float(bg_iou), _hip.f32xn(w),
+                corner, seed, B, int(B * positive_fraction), *[ptr(t) for t in per_row], *iou, *[ptr(t) for t in samples],
+                ptr(info), scratch.data_ptr() + 4 * off, _hip.stream()))
+    return bufs
+
+
+def _targets_finish(infos, debug, defer, scenes):
+    """the one host read of a target stage: `infos` int32 [k, S, 8] (block 0: the samples' counts, `debug`'s `info`);
+    scenes(<the blocks read>) -> the list over scenes.  `defer`: the function that does it is returned instead."""
+    def finish():
+        read = _hip.read_back(infos)                                      # the one read of the stage
+        if debug is not None:
+            debug["info"] = read[0]
+        return scenes(read)
+
+    return finish if defer else finish()
 
 
 def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, aug_thickness=None,
@@ -236,16 +266,13 @@ def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, 
     words = int(lib.aabr_roi_targets_scratch_words(nb))
     if words < 0:
         raise _hip.AabrError("box_head_targets: 1 <= scenes <= 16, got %d" % nb)
-    bufs, scratch = _targets_buffers(sum(n_b), nb, B, words, dev)
-    midx, mval, labels, regt, s_rows, s_labels, s_targets, s_boxes = bufs.values()
     iou = torch.empty(sum(n * g for n, g in zip(n_b, g_b)), dtype=torch.float32, device=dev) if debug is not None else None
     infos = torch.empty((2 if corner_groups else 1, nb, INFO_WORDS), dtype=torch.int32, device=dev)
-    info = infos[0]
-    check(lib.aabr_roi_targets_coder(
-        ptr(props), ptr(tg), ptr(tl), nb, _hip.i64xn(n_b), _hip.i64xn(g_b), _hip.f32x4(aug), -1,
-        int(_nms.REFERENCE_DEBUG_ONLY_XY), float(fg_iou), float(bg_iou), _hip.f32xn(w), corner, seed, B,
-        int(B * positive_fraction), ptr(midx), ptr(mval), ptr(labels), ptr(regt), ptr(iou), ptr(s_rows), ptr(s_labels),
-        ptr(s_targets), ptr(s_boxes), ptr(info), scratch, _hip.stream()))
+    bufs = _targets_run(lib.aabr_roi_targets_coder, (ptr(props), ptr(tg), ptr(tl), nb, _hip.i64xn(n_b), _hip.i64xn(g_b)),
+                        (ptr(iou),), sum(n_b), nb, B, words, dev, aug, fg_iou, bg_iou, w, corner, seed, positive_fraction,
+                        infos[0])
+    midx, s_rows, s_labels, s_targets, s_boxes = (bufs[k] for k in ("matched_idx", "samp_rows", "samp_labels",
+                                                                    "samp_targets", "samp_boxes"))
     if corner_groups:
         G = sum(g_b)
         tg_xyz = torch.empty((2 * G, 3), dtype=torch.float32, device=dev)
@@ -266,16 +293,12 @@ def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, 
             o += n * g
         debug["iou"] = mats
 
-    def finish():
-        both = _hip.read_back(infos)                                      # the one read of the stage
-        counts = both[0]
-        if debug is not None:
-            debug["info"] = counts
-            if corner_groups:
-                debug["corner_info"] = both[1]
+    def scenes(both):
+        if debug is not None and corner_groups:
+            debug["corner_info"] = both[1]
         out = []
         for b in range(nb):
-            m = counts[b][0]
+            m = both[0][b][0]
             out.append({"rows": s_rows[b, :m], "bbox3d": s_boxes[b, :m], "labels": s_labels[b, :m],
                         "regression_targets": s_targets[b, :m]})
             if corner_groups:
@@ -283,7 +306,7 @@ def box_head_targets(proposals, targets, target_labels, fg_iou=0.5, bg_iou=0.5, 
                 out[b].update(pos_pos=c_pos[b, :p], connect_ids=c_ids[b, :2 * p], corner_xyz=c_xyz[b, :2 * p])
         return out
 
-    return finish if defer else finish()
+    return _targets_finish(infos, debug, defer, scenes)
 
 
 CORNER_LOSS_KEYS = ("geometric_pull_loss", "semantic_pull_loss", "semantic_push_loss")    # loss.py:496-498
@@ -366,40 +389,84 @@ def corner_connection_loss(corners_semantic, seg_rows, pos_pos, connect_ids, cor
 
 
 class _BoxHeadLoss(torch.autograd.Function):
+    """`tables` None: the plain entry points, 0-dim losses (`sep_id` None).  Else (G, C_tot, class_nums, cols) of
+    sep_group_tables: the grouped entry points, losses [G], `sep_id` int32 [n], class-agnostic regression."""
+
     @staticmethod
-    def forward(ctx, logits, reg, labels, targets, class_specific, beta):
+    def forward(ctx, logits, reg, sep_id, labels, targets, tables, class_specific, beta):
         lib = _hip.load()
         dev = logits.device
-        n, nc = int(logits.shape[0]), int(logits.shape[1])
+        grouped = tables is not None
         logits_c, reg_c = logits.contiguous(), reg.contiguous()
-        cls_loss = torch.empty((), dtype=torch.float32, device=dev)
-        box_loss = torch.empty((), dtype=torch.float32, device=dev)
+        shape = (tables[0],) if grouped else ()
+        cls_loss = torch.empty(shape, dtype=torch.float32, device=dev)
+        box_loss = torch.empty(shape, dtype=torch.float32, device=dev)
+        rows = torch.empty(shape, dtype=torch.int32, device=dev) if grouped else None      # n_g, for the backward
         flag = torch.empty((), dtype=torch.int32, device=dev)
-        scr = _hip.workspace("roi_box_loss", int(lib.aabr_roi_box_loss_scratch_floats()), torch.float32, dev)
-        check(lib.aabr_roi_box_loss_forward(ptr(logits_c), ptr(reg_c), int(logits.dtype == torch.bfloat16), n, nc,
-                                            int(class_specific), ptr(labels), ptr(targets), beta, ptr(cls_loss),
-                                            ptr(box_loss), ptr(flag), ptr(scr), _hip.stream()))
-        ctx.save_for_backward(logits_c, reg_c, labels, targets)
-        ctx.cfg = (n, nc, int(class_specific), beta)
+        if grouped:
+            entry, words = lib.aabr_roi_box_loss_grouped_forward, lib.aabr_roi_box_loss_grouped_scratch_floats()
+        else:
+            entry, words = lib.aabr_roi_box_loss_forward, lib.aabr_roi_box_loss_scratch_floats()
+        scr = _hip.workspace("roi_box_loss_grouped" if grouped else "roi_box_loss", int(words), torch.float32, dev)
+        # what the four entry points take between box_regression and labels; `rows` is an argument of the grouped two only
+        ctx.form = (int(logits.dtype == torch.bfloat16), int(logits.shape[0])) + (
+            tuple(tables) + (ptr(sep_id),) if grouped else (int(logits.shape[1]), int(class_specific)))
+        check(entry(ptr(logits_c), ptr(reg_c), *ctx.form, ptr(labels), ptr(targets), beta, ptr(cls_loss), ptr(box_loss),
+                    *([ptr(rows)] if grouped else []), ptr(flag), ptr(scr), _hip.stream()))
+        ctx.save_for_backward(logits_c, reg_c, labels, targets, sep_id, rows)
+        ctx.beta, ctx.shape = beta, shape
         ctx.mark_non_differentiable(flag)
         return cls_loss, box_loss, flag
 
     @staticmethod
     def backward(ctx, g_cls, g_box, _g_flag):
         lib = _hip.load()
-        logits, reg, labels, targets = ctx.saved_tensors
-        n, nc, class_specific, beta = ctx.cfg
-        dev = logits.device
-        g_cls = (g_cls if g_cls is not None else torch.zeros((), device=dev)).float().contiguous()
-        g_box = (g_box if g_box is not None else torch.zeros((), device=dev)).float().contiguous()
+        logits, reg, labels, targets, _sep_id, rows = ctx.saved_tensors   # (sep_id is kept alive: ctx.form holds its address)
+        dev, grouped = logits.device, rows is not None
+        g_cls = (g_cls if g_cls is not None else torch.zeros(ctx.shape, device=dev)).float().contiguous()
+        g_box = (g_box if g_box is not None else torch.zeros(ctx.shape, device=dev)).float().contiguous()
         d_logits, d_reg = torch.empty_like(logits), torch.empty_like(reg)       # the kernel writes every element
-        check(lib.aabr_roi_box_loss_backward(ptr(logits), ptr(reg), int(logits.dtype == torch.bfloat16), n, nc,
-                                             class_specific, ptr(labels), ptr(targets), beta, ptr(g_cls), ptr(g_box),
-                                             ptr(d_logits), ptr(d_reg), _hip.stream()))
-        return d_logits, d_reg, None, None, None, None
+        entry = lib.aabr_roi_box_loss_grouped_backward if grouped else lib.aabr_roi_box_loss_backward
+        check(entry(ptr(logits), ptr(reg), *ctx.form, ptr(labels), ptr(targets), ctx.beta, *([ptr(rows)] if grouped else []),
+                    ptr(g_cls), ptr(g_box), ptr(d_logits), ptr(d_reg), _hip.stream()))
+        return d_logits, d_reg, None, None, None, None, None, None
 
 
 BOX_LOSS_BETA = 1.0 / 5      # box_head_3d/loss.py:374
+
+
+def _box_head_loss(class_logits, box_regression, sep_id, labels, regression_targets, tables, class_specific, return_flag):
+    """the checks, the casts and the call of box_head_loss (`tables` None) and box_head_loss_grouped (`tables` of
+    sep_group_tables and `sep_id`; class-agnostic regression)"""
+    if class_logits.dim() != 2 or box_regression.dim() != 2:
+        raise ValueError("class_logits and box_regression must be 2-D")
+    n, nc = int(class_logits.shape[0]), int(class_logits.shape[1])
+    if tables is not None and nc != tables[1]:
+        raise ValueError("class_logits must be [n, %d] (C_tot of the groups), got %s" % (tables[1], tuple(class_logits.shape)))
+    if class_logits.dtype not in (torch.float32, torch.bfloat16) or box_regression.dtype != class_logits.dtype:
+        raise TypeError("class_logits and box_regression must both be float32, or both bfloat16")
+    if tables is not None:
+        if tuple(box_regression.shape) != (n, 7):
+            raise ValueError("box_regression must be [%d, 7] (class agnostic with groups), got %s"
+                             % (n, tuple(box_regression.shape)))
+        if labels.numel() != n or regression_targets.numel() != 7 * n or sep_id.numel() != n:
+            raise ValueError("sep_id / labels / regression_targets do not have %d rows" % n)
+    else:
+        if class_specific is None:
+            class_specific = box_regression.shape[1] == 7 * nc and nc != 1
+        width = 7 * nc if class_specific else 7
+        if box_regression.shape[0] != n or box_regression.shape[1] != width:
+            raise ValueError("box_regression must be [%d, %d], got %s" % (n, width, tuple(box_regression.shape)))
+        if labels.numel() != n or regression_targets.numel() != 7 * n:
+            raise ValueError("labels / regression_targets do not have %d rows" % n)
+    _hip.require_gpu(class_logits)
+    dev = class_logits.device
+    sid = None if tables is None else sep_id.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    lab = labels.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    tgt = regression_targets.reshape(-1, 7).to(device=dev, dtype=torch.float32).contiguous()
+    cls_loss, box_loss, flag = _BoxHeadLoss.apply(class_logits, box_regression, sid, lab, tgt, tables, bool(class_specific),
+                                                  BOX_LOSS_BETA)
+    return (cls_loss, box_loss, flag) if return_flag else (cls_loss, box_loss)
 
 
 def box_head_loss(class_logits, box_regression, labels, regression_targets, class_specific=None, yaw_loss_mode="Diff",
@@ -418,24 +485,7 @@ def box_head_loss(class_logits, box_regression, labels, regression_targets, clas
     (FastRCNNLossComputation.__call__ keeps it as `last_flag`)."""
     parse_yaw_loss_mode(yaw_loss_mode)
     _hip.require_gpu(class_logits)
-    if class_logits.dim() != 2 or box_regression.dim() != 2:
-        raise ValueError("class_logits and box_regression must be 2-D")
-    n, nc = int(class_logits.shape[0]), int(class_logits.shape[1])
-    if class_logits.dtype not in (torch.float32, torch.bfloat16) or box_regression.dtype != class_logits.dtype:
-        raise TypeError("class_logits and box_regression must both be float32, or both bfloat16")
-    if class_specific is None:
-        class_specific = box_regression.shape[1] == 7 * nc and nc != 1
-    width = 7 * nc if class_specific else 7
-    if box_regression.shape[0] != n or box_regression.shape[1] != width:
-        raise ValueError("box_regression must be [%d, %d], got %s" % (n, width, tuple(box_regression.shape)))
-    if labels.numel() != n or regression_targets.numel() != 7 * n:
-        raise ValueError("labels / regression_targets do not have %d rows" % n)
-    dev = class_logits.device
-    lab = labels.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
-    tgt = regression_targets.reshape(-1, 7).to(device=dev, dtype=torch.float32).contiguous()
-    cls_loss, box_loss, flag = _BoxHeadLoss.apply(class_logits, box_regression, lab, tgt, bool(class_specific),
-                                                  BOX_LOSS_BETA)
-    return (cls_loss, box_loss, flag) if return_flag else (cls_loss, box_loss)
+    return _box_head_loss(class_logits, box_regression, None, labels, regression_targets, None, class_specific, return_flag)
 
 
 # ---- the separated-classifier groups (MODEL.SEPARATE_CLASSES; csrc/sep_groups.h) -------------------------------------------
@@ -508,24 +558,19 @@ def box_head_targets_grouped(proposals, sep_sizes, targets, target_labels, group
     keys = torch.empty(sum(g_b), dtype=torch.int64, device=dev)
     check(lib.aabr_roi_gt_group_keys(ptr(tl), nb, _hip.i64xn(g_b), G, _c_tot, class_nums, cols, ptr(keys), _hip.stream()))
     keys, perm = torch.sort(keys, stable=True)                            # the one sort: (segment, group-local label, row)
-    bufs, scratch = _targets_buffers(sum(n_b), S, B, int(lib.aabr_roi_targets_scratch_words(S)), dev)
-    midx, mval, labels, regt, s_rows, s_labels, s_targets, s_boxes = bufs.values()
-    info = torch.empty((S, INFO_WORDS), dtype=torch.int32, device=dev)
-    check(lib.aabr_roi_targets_grouped(
-        ptr(props), ptr(tg), ptr(keys), ptr(perm), nb, G, _hip.i64xn(n_s), _hip.i64xn(g_b), _hip.f32x4(aug), -1,
-        int(_nms.REFERENCE_DEBUG_ONLY_XY), float(fg_iou), float(bg_iou), _hip.f32xn(w), corner, seed, B,
-        int(B * positive_fraction), ptr(midx), ptr(mval), ptr(labels), ptr(regt), ptr(s_rows), ptr(s_labels),
-        ptr(s_targets), ptr(s_boxes), ptr(info), scratch, _hip.stream()))
+    infos = torch.empty((1, S, INFO_WORDS), dtype=torch.int32, device=dev)
+    bufs = _targets_run(lib.aabr_roi_targets_grouped,
+                        (ptr(props), ptr(tg), ptr(keys), ptr(perm), nb, G, _hip.i64xn(n_s), _hip.i64xn(g_b)), (), sum(n_b), S,
+                        B, int(lib.aabr_roi_targets_scratch_words(S)), dev, aug, fg_iou, bg_iou, w, corner, seed,
+                        positive_fraction, infos[0])
+    s_rows, s_labels, s_targets, s_boxes = (bufs[k] for k in ("samp_rows", "samp_labels", "samp_targets", "samp_boxes"))
     if debug is not None:
         debug.update(bufs, seed=seed, gt_keys=keys, gt_perm=perm)
 
-    def finish():
-        counts = _hip.read_back(info)                                     # the one read of the stage
-        if debug is not None:
-            debug["info"] = counts
+    def scenes(read):
         out = []
         for b in range(nb):
-            ms = [counts[b * G + g][0] for g in range(G)]
+            ms = [read[0][b * G + g][0] for g in range(G)]
             first = [sum(n_s[b * G:b * G + g]) for g in range(G)]         # the segment's first row inside its scene
             seg = range(b * G, (b + 1) * G)
             out.append({"rows": torch.cat([s_rows[s, :m] + o for s, m, o in zip(seg, ms, first)]),
@@ -537,43 +582,7 @@ def box_head_targets_grouped(proposals, sep_sizes, targets, target_labels, group
                         "sep_counts": ms})
         return out
 
-    return finish if defer else finish()
-
-
-class _BoxHeadLossGrouped(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, reg, sep_id, labels, targets, tables, beta):
-        lib = _hip.load()
-        dev = logits.device
-        G, c_tot, class_nums, cols = tables
-        n = int(logits.shape[0])
-        logits_c, reg_c = logits.contiguous(), reg.contiguous()
-        cls_loss = torch.empty(G, dtype=torch.float32, device=dev)
-        box_loss = torch.empty(G, dtype=torch.float32, device=dev)
-        rows = torch.empty(G, dtype=torch.int32, device=dev)
-        flag = torch.empty((), dtype=torch.int32, device=dev)
-        scr = _hip.workspace("roi_box_loss_grouped", int(lib.aabr_roi_box_loss_grouped_scratch_floats()), torch.float32, dev)
-        check(lib.aabr_roi_box_loss_grouped_forward(
-            ptr(logits_c), ptr(reg_c), int(logits.dtype == torch.bfloat16), n, G, c_tot, class_nums, cols, ptr(sep_id),
-            ptr(labels), ptr(targets), beta, ptr(cls_loss), ptr(box_loss), ptr(rows), ptr(flag), ptr(scr), _hip.stream()))
-        ctx.save_for_backward(logits_c, reg_c, sep_id, labels, targets, rows)
-        ctx.cfg = (n, tables, beta)
-        ctx.mark_non_differentiable(flag)
-        return cls_loss, box_loss, flag
-
-    @staticmethod
-    def backward(ctx, g_cls, g_box, _g_flag):
-        lib = _hip.load()
-        logits, reg, sep_id, labels, targets, rows = ctx.saved_tensors
-        n, (G, c_tot, class_nums, cols), beta = ctx.cfg
-        dev = logits.device
-        g_cls = (g_cls if g_cls is not None else torch.zeros(G, device=dev)).float().contiguous()
-        g_box = (g_box if g_box is not None else torch.zeros(G, device=dev)).float().contiguous()
-        d_logits, d_reg = torch.empty_like(logits), torch.empty_like(reg)       # the kernel writes every element
-        check(lib.aabr_roi_box_loss_grouped_backward(
-            ptr(logits), ptr(reg), int(logits.dtype == torch.bfloat16), n, G, c_tot, class_nums, cols, ptr(sep_id),
-            ptr(labels), ptr(targets), beta, ptr(rows), ptr(g_cls), ptr(g_box), ptr(d_logits), ptr(d_reg), _hip.stream()))
-        return d_logits, d_reg, None, None, None, None, None
+    return _targets_finish(infos, debug, defer, scenes)
 
 
 def box_head_loss_grouped(class_logits, box_regression, sep_id, labels, regression_targets, groups, yaw_loss_mode="Diff",
@@ -590,26 +599,8 @@ def box_head_loss_grouped(class_logits, box_regression, sep_id, labels, regressi
     group's range adds nothing, gets zero gradients and raises the flag (`return_flag=True` appends it)."""
     parse_yaw_loss_mode(yaw_loss_mode)
     gc, c_tot, class_nums, cols = sep_group_tables(groups)
-    if class_logits.dim() != 2 or box_regression.dim() != 2:
-        raise ValueError("class_logits and box_regression must be 2-D")
-    n = int(class_logits.shape[0])
-    if int(class_logits.shape[1]) != c_tot:
-        raise ValueError("class_logits must be [n, %d] (C_tot of the groups), got %s" % (c_tot, tuple(class_logits.shape)))
-    if class_logits.dtype not in (torch.float32, torch.bfloat16) or box_regression.dtype != class_logits.dtype:
-        raise TypeError("class_logits and box_regression must both be float32, or both bfloat16")
-    if tuple(box_regression.shape) != (n, 7):
-        raise ValueError("box_regression must be [%d, 7] (class agnostic with groups), got %s"
-                         % (n, tuple(box_regression.shape)))
-    if labels.numel() != n or regression_targets.numel() != 7 * n or sep_id.numel() != n:
-        raise ValueError("sep_id / labels / regression_targets do not have %d rows" % n)
-    _hip.require_gpu(class_logits)
-    dev = class_logits.device
-    sid = sep_id.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
-    lab = labels.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
-    tgt = regression_targets.reshape(-1, 7).to(device=dev, dtype=torch.float32).contiguous()
-    cls_loss, box_loss, flag = _BoxHeadLossGrouped.apply(class_logits, box_regression, sid, lab, tgt,
-                                                         (len(gc), c_tot, class_nums, cols), BOX_LOSS_BETA)
-    return (cls_loss, box_loss, flag) if return_flag else (cls_loss, box_loss)
+    return _box_head_loss(class_logits, box_regression, sep_id, labels, regression_targets,
+                          (len(gc), c_tot, class_nums, cols), False, return_flag)
 
 
 def box_detections_grouped(class_logits, box_regression, proposals, sep_id, groups, score_thresh=0.05, nms=0.5,
@@ -626,28 +617,7 @@ def box_detections_grouped(class_logits, box_regression, proposals, sep_id, grou
     of the counts at the end (`defer` as box_detections).  `debug` receives `prob` [N, C_tot] (exact zeros outside the
     row's group), `boxes` [N, 7] and `info` (word 5 of a scene: some sep_id was outside [0, G))."""
     gc, c_tot, class_nums, cols = sep_group_tables(groups)
-    G = len(gc)
-    lib = _hip.load()
-    _hip.require_gpu(class_logits)
-    dev = class_logits.device
-    logits = class_logits.to(torch.float32).contiguous()
-    reg = box_regression.to(device=dev, dtype=torch.float32).contiguous()
-    N = int(logits.shape[0])
-    if int(logits.shape[1]) != c_tot:
-        raise ValueError("class_logits must be [N, %d] (C_tot of the groups), got %s" % (c_tot, tuple(logits.shape)))
-    if tuple(reg.shape) != (N, 7):
-        raise ValueError("box_regression must be [%d, 7] (class agnostic with groups), got %s" % (N, tuple(reg.shape)))
-    n_b = [int(p.shape[0]) for p in proposals]
-    nb = len(n_b)
-    if nb == 0 and N == 0:
-        return (lambda: []) if defer else []
-    if sum(n_b) != N or sep_id.numel() != N:
-        raise ValueError("the proposals have %d rows, sep_id %d, class_logits %d" % (sum(n_b), sep_id.numel(), N))
-    props = torch.cat([p.reshape(-1, 7) for p in proposals]).to(device=dev, dtype=torch.float32).contiguous()
-    sid = sep_id.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
-    head = (ptr(logits), ptr(reg), ptr(props), ptr(sid), nb, _hip.i64xn(n_b), G, c_tot, class_nums, cols)
-    return _detections("box_detections_grouped", "(1 <= scenes <= 16): C_tot=%d nb=%d",
-                       lib.aabr_roi_post_detections_grouped, head, dev, n_b, c_tot, (c_tot - G) * POST_NMS, (N, 7),
+    return _detections(class_logits, box_regression, proposals, sep_id, (len(gc), c_tot, class_nums, cols), False,
                        score_thresh, nms, nms_aug_thickness, detections_per_img, weights, bbox_xform_clip, box_coder, defer,
                        debug)
 

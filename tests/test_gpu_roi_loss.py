@@ -271,8 +271,23 @@ def _sample_for_loss(c, seed=3):
 @pytest.mark.parametrize("class_specific", [True, False])
 @pytest.mark.parametrize("c", [2, 4, 7])
 def test_losses_and_gradients_within_derived_bounds(c, class_specific, dtype):
+    _check_losses_and_gradients(*_sample_for_loss(c), c, class_specific, dtype)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("class_specific", [True, False])
+def test_losses_and_gradients_c33_two_workgroups(class_specific, dtype):
+    """C = 33: one column more than the separated-classifier group tables can hold (csrc/sep_groups.h) -- the plain loss
+    has no such limit.  257 rows are two workgroups, the second with a single row (the workgroup-order sum and the tail
+    guard); the labels i % 33 meet every class and the background."""
+    n, c = 257, 33
+    labels = (torch.arange(n) % c).to(DEV)
+    tgt = (torch.randn(n, 7, generator=torch.Generator().manual_seed(33)) * 0.3).to(DEV)
+    _check_losses_and_gradients(labels, tgt, c, class_specific, dtype)
+
+
+def _check_losses_and_gradients(labels, tgt, c, class_specific, dtype):
     import roi_glue
-    labels, tgt = _sample_for_loss(c)
     n = labels.numel()
     g = torch.Generator().manual_seed(c * 4 + class_specific)
     logits = (torch.randn(n, c, generator=g) * 2).to(DEV, dtype).requires_grad_()
