@@ -510,6 +510,10 @@ __global__ __launch_bounds__(256) void k_rpn_gather_logits(RpnGatherParams p, in
   if (j >= lmax) return;
   float v = -__builtin_inff();
   if (j < p.s.seg[b][p.s.n_maps]) v = rpn_list_logit(p, b, j);
+  // the matrix exists for torch.topk, which on the device selects a NaN whatever its sign bit but sorts one with the
+  // sign bit set LAST among the selected: every NaN leaves here as the quiet NaN with the sign bit clear, which it puts
+  // first -- the place the fused top-k (topk_order_key below) gives a NaN
+  if (v != v) v = __uint_as_float(0x7fc00000u);
   out[(int64_t)b * lmax + j] = v;
 }
 
@@ -552,9 +556,21 @@ extern "C" int aabr_rpn_gather_logits(int n_maps, const void *const *logit_ptrs,
 //      list (<= 4096: k plus the ties of one 24-bit prefix; more = overflow, reported, the caller falls back);
 //   K4 one workgroup per example sorts the candidates (bitonic, in LDS) by (logit descending, index ascending) and
 //      writes the first k indices.
-// Same selection as torch.topk(sorted=True) except between EXACTLY equal logits, where torch leaves the order (and the
-// choice at the cut) open and this picks the lower index -- deterministic.
+// The order is torch.topk's value order made total by the index: a NaN (either sign bit, any payload) ranks above +inf,
+// then descending value with -0 equal to +0, and between logits that compare equal (all NaN count as equal) the lower
+// list index first.  So: the same selection as torch.topk(sorted=True) except between equal logits, where torch leaves
+// the order (and the choice at the cut) open and this picks the lower index -- deterministic.  All three passes that
+// rank a logit take its key from topk_order_key below, nothing else.
 constexpr int kTopkBins = 4096, kTopkCand = 4096;
+// float_order_key (anchor_list.h) made canonical for that order: any NaN -> 0xffffffff, the topmost key (the bare key
+// puts a NaN with the sign bit set below -inf), and -0 -> the key of +0 (the bare key puts -0 one below +0, which
+// would rank a +0 before a -0 of lower index).  Decided on the bits, so it does not depend on the denormal mode.
+__device__ __forceinline__ uint32_t topk_order_key(float v) {
+  const uint32_t u = __float_as_uint(v);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+  if ((u & 0x7fffffffu) == 0u) return 0x80000000u;
+  return float_order_key(v);
+}
 struct RpnTopkParams {
   RpnGatherParams g;
   int32_t k[kAnchorMaxBatch];
@@ -607,7 +623,7 @@ __global__ __launch_bounds__(256) void k_rpn_topk_hist(RpnTopkParams p, int32_t 
   for (int q = threadIdx.x; q < kTopkBins; q += 256) s_hist[q] = 0;
   __syncthreads();
   for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
-    const uint32_t key = float_order_key(rpn_list_logit(p.g, b, j));
+    const uint32_t key = topk_order_key(rpn_list_logit(p.g, b, j));
     if (LEVEL == 1) atomicAdd(&s_hist[key >> 20], 1);
     else if ((int)(key >> 20) == bin1) atomicAdd(&s_hist[(key >> 8) & 4095u], 1);
   }
@@ -627,7 +643,7 @@ __global__ __launch_bounds__(256) void k_rpn_topk_compact(RpnTopkParams p, int32
   const int bin2 = topk_find_bin(sc + kTopkBins, p.k[b] - ctl[kTkAbove1], above2);
   const uint32_t thr = ((uint32_t)bin1 << 12) | (uint32_t)bin2;
   for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
-    const uint32_t key = float_order_key(rpn_list_logit(p.g, b, j));
+    const uint32_t key = topk_order_key(rpn_list_logit(p.g, b, j));
     if ((key >> 8) >= thr) {
       const int pos = atomicAdd(&ctl[kTkCount], 1);
       if (pos < kTopkCand) cand[pos] = ((unsigned long long)(~key) << 32) | (unsigned long long)(uint32_t)j;

@@ -168,6 +168,8 @@ def rpn_proposals(maps, objectness, box_regression, base_anchors, strides, voxel
                 float(bbox_xform_clip), float(nms_aug_thickness[0]), float(nms_aug_thickness[1]), ptr(sel), k,
                 ptr(boxes), ptr(nms_boxes), ptr(scores), float(nms_thresh), int(_nms.REFERENCE_DEBUG_ONLY_XY),
                 int(post_nms_top_n), ptr(mask), ptr(keep), ptr(meta), stream()))
+            if debug_nms_inputs is not None:
+                debug_nms_inputs.extend((nms_boxes[bi], scores[bi]) for bi in range(nb))
             kept = _hip.read_back(meta[:, 0])       # the one read of the stage
             out = []
             for bi in range(nb):
@@ -222,9 +224,13 @@ def _proposals_of_segments(lib, dev, coords, topk_obj, segments, ba, A, strides,
             over_words.append(topk_info[:, 1])
 
     def logits_of(bi):
-        """segment bi's logits, concatenated in map order (the torch.topk paths)"""
+        """segment bi's logits, concatenated in map order (the torch.topk paths).  torch.topk on the device selects a NaN
+        whatever its sign bit but sorts one with the sign bit set last among the selected: every NaN goes in as
+        float('nan') (sign bit clear), which it puts first -- where the fused top-k puts a NaN (csrc/iou_nms.hip
+        topk_order_key; aabr_rpn_gather_logits does the same for the batched form)"""
         seg, st0, _, obj, _reg = segments[bi]
-        return torch.cat([obj[m][st0[m] * A:st0[m] * A + (seg[m + 1] - seg[m])] for m in range(n_maps)])
+        cat = torch.cat([obj[m][st0[m] * A:st0[m] * A + (seg[m + 1] - seg[m])] for m in range(n_maps)])
+        return torch.where(cat != cat, torch.full_like(cat, float("nan")), cat)
 
     def decode(bi, sel, boxes, scores):
         """segment bi's selected anchors decoded into `boxes` / `scores`; returns the thickness-clamped copy for the NMS"""

@@ -560,16 +560,21 @@ int aabr_bn_backward_add_bf16(const uint16_t *in, uint16_t *d_in, const uint16_t
  * The reference's RPNPostProcessor loops over the examples in Python (rpn/inference_3d.py:95-149).
  * aabr_rpn_gather_logits: out[b][j] = j-th logit of example b's cross-scale anchor list (maps in order; tables
  *   [nb][n_maps+1] / [nb][n_maps] on the host as for aabr_rpn_decode_maps), -inf from its end to lmax -- one
- *   top-k over dim 1 then selects for every example.
+ *   top-k over dim 1 then selects for every example.  A NaN logit is written as the quiet NaN with the sign bit
+ *   clear (0x7fc00000), which torch.topk on the device puts first like aabr_rpn_topk_maps does; one with the sign bit
+ *   set it would select but sort last.
  * aabr_rpn_proposals_batch: per example aabr_rpn_decode_maps on selected[b] followed by aabr_rotate_nms_sorted of
  *   the decoded list; boxes / nms_boxes [nb,k,7], scores [nb,k], mask [nb][k*ceil(k/64)], keep [nb,k],
  *   meta [nb][AABR_META_WORDS] (meta[b][0] = number kept, left on the device).  At most 8 maps, 16 examples.  */
 /* aabr_rpn_topk_maps (round 5): the per-example `objectness.topk(pre_nms_top_n, sorted=True)` of RPNPostProcessor
  *   (rpn/inference_3d.py:107-112) for ALL examples of a step in four launches, on the logits (sigmoid is monotone), with
  *   nothing concatenated: selected[b][0..k_host[b]) = indices into example b's cross-scale anchor list (tables as for
- *   aabr_rpn_gather_logits) in descending logit order, equal logits by ascending index.  info[2b] = candidates gathered,
+ *   aabr_rpn_gather_logits) in torch.topk's value order, equal logits by ascending index: a NaN (either sign bit) ranks
+ *   above +inf, then descending value with -0 equal to +0; logits that compare equal, and NaN among themselves, come
+ *   out by ascending index, in the list and at the cut.  info[2b] = candidates gathered,
  *   info[2b+1] != 0: more than 4096 logits share the 24-bit prefix at the cut (exact ties en masse) -- selected[b] is then
- *   not valid and the caller falls back to a full sort.  k <= 2048.  scratch: aabr_rpn_topk_scratch_words(nb) int32.  */
+ *   not valid (every entry still lies inside the list) and the caller falls back to a full sort.  k <= 2048.
+ *   scratch: aabr_rpn_topk_scratch_words(nb) int32.  */
 int64_t aabr_rpn_topk_scratch_words(int nb);
 int aabr_rpn_topk_maps(int n_maps, const void *const *logit_ptrs, int nb, const int32_t *seg_begin_host,
                        const int32_t *site_begin_host, int num_anchors, const int32_t *k_host, int64_t *selected,
