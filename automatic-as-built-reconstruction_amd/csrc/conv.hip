@@ -19,6 +19,7 @@
 //
 // fp32 MFMA == k-ordered fmaf chain (exact fp32); peak 157 TFLOP/s.
 #include "common.h"
+#include "conv_tile_frame.h" // the frame the k_conv_blocks_mfma* kernels share: context, pair loads, gathers, epilogue
 #include "offset_pairs.h"   // op_hdr, op_nb256: the pair list's layout
 #include <stdlib.h>
 
@@ -176,9 +177,7 @@ __global__ __launch_bounds__(256) void k_pack_weights_jobs(const PackJob *__rest
 // and the input-gradient passes) then streams these blocks with no ballots and no table reads.
 //   words:  [ntiles] nblk | [ntiles][MAXB] offset k of each block | [ntiles][MAXB][16] entries
 //   entry = (partner_row << 6) | local_row; padding entries repeat the block's first pair with
-//   bit 31 set (gather is valid, result is discarded);  MAXB = 4 * vol.
-__host__ __device__ inline int64_t tb_ntiles(int64_t V) { return (V + 63) / 64; }
-__host__ __device__ inline int tb_maxb(int vol) { return 4 * vol; }
+//   bit 31 set (gather is valid, result is discarded);  MAXB = 4 * vol  (tb_ntiles, tb_maxb: conv_tile_frame.h).
 
 __global__ __launch_bounds__(256) void k_build_tile_blocks(const StreamJobs js) {      // common.h: one launch, many books
   const int job = stream_job_of(js, blockIdx.x);
@@ -287,52 +286,29 @@ __device__ inline void conv_step_mfma(const ConvStep &st, const float *__restric
   }
 }
 
-// lane holds D^T[out col = j*16 + g*4 + r][pair c16]: 4 consecutive columns of the pair's row
-template <int NBW, int WS>
-__device__ inline void conv_block_accumulate(float *Ct, int e, int g, const f32x4 (&acc)[NBW]) {
-  if (e >= 0) {
-    const int orow = e & 63;
-#pragma unroll
-    for (int j = 0; j < NBW; ++j) {
-      float4 *dst = reinterpret_cast<float4 *>(Ct + orow * WS + j * 16 + g * 4);
-      float4 cur = *dst;
-      cur.x += acc[j][0]; cur.y += acc[j][1]; cur.z += acc[j][2]; cur.w += acc[j][3];
-      *dst = cur;
-    }
-  }
-}
-
 // One workgroup owns a tile of 64 output rows x (NBW*16) output columns.  Its WPB waves take
 // the tile's blocks round-robin, two blocks per step, and software-pipeline three stages in
 // registers: block entries two pairs ahead, weights + gathered rows one step ahead, MFMAs now.
 // Each wave accumulates into a private LDS tile; the tiles are summed in wave order at the end,
 // so the result is bit-reproducible.  ALIGNED: ci % 32 == 0 (float4 gathers, no bounds checks).
-struct PairEnt { int eA, eB, kA, kB; };
-
+// Flat 64-bit addressing (buffers of 2 GiB and more): of the shared frame it takes the descriptor-free TileLanes.
 template <int NBW, int WPB, bool ALIGNED>
 __global__ __launch_bounds__(WPB * 64, (NBW <= 2 ? 3 : 2)) void k_conv_blocks_mfma(const float *__restrict__ in, int ci,
                                                               float *__restrict__ out, int co,
                                                               int64_t V_out, const int32_t *__restrict__ words,
                                                               int vol, int wflip, const float *__restrict__ Wp,
                                                               const float *__restrict__ bias) {
-  constexpr int WS = NBW * 16;              // C-tile row stride (floats)
-  constexpr int TILE = 64 * WS;             // floats per wave
   extern __shared__ __align__(16) float smem[];
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int g = lane >> 4, c16 = lane & 15;
-  float *Ct = smem + (size_t)wave * TILE;
+  const TileLanes<NBW> c = tile_lanes<NBW>(smem, nkc_of(ci), co);
+  const int wave = c.wave, lane = c.lane, g = c.g, c16 = c.c16, nkc = c.nkc, nnb = c.nnb, nb0 = c.nb0;
   const int maxb = tb_maxb(vol);
-
-  const int nkc = nkc_of(ci), nnb = nnb_of(co);
-  const int nb0 = blockIdx.y * NBW;                       // first global n-block of the slab
   const int64_t tile = blockIdx.x, row0 = tile * 64;
   const int64_t ntiles = tb_ntiles(V_out);
   const int nblk = words[tile];
   const int32_t *blk_k = words + ntiles + tile * maxb;
   const int32_t *ent = words + ntiles + ntiles * maxb + tile * maxb * 16;
   const int64_t wk_stride = (int64_t)nkc * nnb * 512;
-
-  for (int i = lane; i < TILE; i += 64) Ct[i] = 0.0f;
+  zero_tile(c);
   const int dbg = wflip >> 8; // timing experiments only (tools_conv_bench.py): 1 = no MFMAs, 2 = no gathers
   wflip &= 1;
 
@@ -380,42 +356,11 @@ __global__ __launch_bounds__(WPB * 64, (NBW <= 2 ? 3 : 2)) void k_conv_blocks_mf
       if (!(dbg & 1)) conv_step_mfma<NBW>(cur, WkA, WkB, kc, nnb, nb0, lane, accA, accB);
       cur = nxt;
     }
-    conv_block_accumulate<NBW, WS>(Ct, p0.eA, g, accA);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // A and B may hit the same row
-    conv_block_accumulate<NBW, WS>(Ct, p0.eB, g, accB);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    accumulate_pair<NBW>(c.Ct, p0.eA, p0.eB, g, accA, accB);
     p0 = p1; p1 = p2; p2 = load_pair(pr + 3);
   }
   __syncthreads();
-  // combine the per-wave tiles in wave order (+ bias, CPU/Convolution.cpp:59-62) and write once
-  const int nrows = (int)((V_out - row0) < 64 ? (V_out - row0) : 64);
-  const int wcols = (co - nb0 * 16) < NBW * 16 ? (co - nb0 * 16) : NBW * 16;
-  if ((co & 3) == 0) {
-    const int q = wcols >> 2; // float4 per row
-    for (int i = threadIdx.x; i < nrows * q; i += WPB * 64) {
-      int r = i / q, cq = i % q;
-      float4 v = *reinterpret_cast<const float4 *>(smem + r * WS + cq * 4);
-#pragma unroll
-      for (int w = 1; w < WPB; ++w) {
-        float4 u = *reinterpret_cast<const float4 *>(smem + (size_t)w * TILE + r * WS + cq * 4);
-        v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-      }
-      if (bias) {
-        const float *bb = bias + nb0 * 16 + cq * 4;
-        v.x += bb[0]; v.y += bb[1]; v.z += bb[2]; v.w += bb[3];
-      }
-      *reinterpret_cast<float4 *>(out + (row0 + r) * co + nb0 * 16 + cq * 4) = v;
-    }
-  } else {
-    for (int i = threadIdx.x; i < nrows * wcols; i += WPB * 64) {
-      int r = i / wcols, cc = i % wcols;
-      float v = smem[r * WS + cc];
-#pragma unroll
-      for (int w = 1; w < WPB; ++w) v += smem[(size_t)w * TILE + r * WS + cc];
-      if (bias) v += bias[nb0 * 16 + cc];
-      out[(row0 + r) * co + nb0 * 16 + cc] = v;
-    }
-  }
+  tile_epilogue<NBW, WPB, WPB * 64, true>(smem, threadIdx.x, out, co, V_out, row0, nb0, bias);
 }
 
 // Lean variant for ci % 32 == 0 and tensors < 2 GiB: every load goes through a buffer descriptor
@@ -424,11 +369,6 @@ __global__ __launch_bounds__(WPB * 64, (NBW <= 2 ? 3 : 2)) void k_conv_blocks_mf
 // takes a literal zero accumulator.  fp32 MFMA shares the vector datapath with the VALU on gfx950
 // (ablation: kernel time = MFMA time + everything-else time), so every VALU instruction removed
 // from the loop is time given back to the matrix pipe.
-
-struct GStep { u32x4 a0, a1, b0, b1; };
-
-__device__ inline float bcf(unsigned int v) { return __builtin_bit_cast(float, v); }
-
 template <int NBW, bool ADJ>
 __device__ inline void conv_step_mfma_buf(const GStep &q, __amdgpu_buffer_rsrc_t rw, unsigned lane32,
                                           unsigned soA, unsigned soB, int nvalid, f32x4 (&accA)[NBW],
@@ -457,22 +397,7 @@ __device__ inline void conv_step_mfma_buf(const GStep &q, __amdgpu_buffer_rsrc_t
   for (int j = 0; j < NBW; ++j) {
     if (j < nvalid) {
       f32x4 ca = accA[j], cb = accB[j];
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w0[j][0]), bcf(q.a0[0]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(u0[j][0]), bcf(q.b0[0]), cb, 0, 0, 0);
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w0[j][1]), bcf(q.a0[1]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(u0[j][1]), bcf(q.b0[1]), cb, 0, 0, 0);
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w0[j][2]), bcf(q.a0[2]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(u0[j][2]), bcf(q.b0[2]), cb, 0, 0, 0);
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w0[j][3]), bcf(q.a0[3]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(u0[j][3]), bcf(q.b0[3]), cb, 0, 0, 0);
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w1[j][0]), bcf(q.a1[0]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(u1[j][0]), bcf(q.b1[0]), cb, 0, 0, 0);
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w1[j][1]), bcf(q.a1[1]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(u1[j][1]), bcf(q.b1[1]), cb, 0, 0, 0);
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w1[j][2]), bcf(q.a1[2]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(u1[j][2]), bcf(q.b1[2]), cb, 0, 0, 0);
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w1[j][3]), bcf(q.a1[3]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(u1[j][3]), bcf(q.b1[3]), cb, 0, 0, 0);
+      AABR_MFMA16(ca, cb, w0[j], w1[j], u0[j], u1[j], q.a0, q.a1, q.b0, q.b1);
       accA[j] = ca; accB[j] = cb;
     }
   }
@@ -483,73 +408,18 @@ __global__ __launch_bounds__(WPB * 64, (NBW <= 2 ? 3 : 2)) void k_conv_blocks_mf
     const float *__restrict__ in, int ci, int64_t in_bytes, float *__restrict__ out, int co, int64_t V_out,
     const int32_t *__restrict__ words, int64_t words_bytes, int vol, int wflip, const float *__restrict__ Wp,
     int64_t wp_bytes, const float *__restrict__ bias) {
-  constexpr int WS = NBW * 16;              // C-tile row stride (floats)
-  constexpr int TILE = 64 * WS;             // floats per wave
   extern __shared__ __align__(16) float smem[];
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int g = lane >> 4, c16 = lane & 15;
-  float *Ct = smem + (size_t)wave * TILE;
-  const int maxb = tb_maxb(vol);
-  const int nkc = ALIGNED ? (ci >> 5) : nkc_of(ci), nnb = nnb_of(co);
-  const int nb0 = blockIdx.y * NBW;
-  const int64_t tile = blockIdx.x, row0 = tile * 64;
-  const int64_t ntiles = tb_ntiles(V_out);
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(in), 0, (int)in_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(Wp), 0, (int)wp_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwords =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(words), 0, (int)words_bytes, 0x00020000);
-  const int nblk = words[tile];
-  const unsigned kbase = (unsigned)((ntiles + tile * maxb) * 4);                       // byte offset of blk_k
-  const unsigned ebase = (unsigned)((ntiles + ntiles * maxb + tile * maxb * 16) * 4);  // byte offset of ent
-  const unsigned rowbytes = (unsigned)ci * 4u, g32 = (unsigned)g * 32u, lane32 = (unsigned)lane * 32u;
-  const unsigned wk_bytes = (unsigned)nkc * (unsigned)nnb * 2048u;                     // packed bytes per offset
-  const unsigned c16x4 = (unsigned)c16 * 4u;
-  const int nvalid = (nnb - nb0) < NBW ? (nnb - nb0) : NBW;
-
-  for (int i = lane; i < TILE; i += 64) Ct[i] = 0.0f;
-
-  // ADJ (throughput-bound launches): pairs of adjacent blocks dealt round-robin, same-offset pairs share
-  // their weight fragments; else blocks dealt round-robin and a wave pairs its own consecutive ones
-  const int nmine = wave < nblk ? (nblk - wave + WPB - 1) / WPB : 0;
-  const int tpairs = (nblk + 1) >> 1;
-  const int npairs = ADJ ? (wave < tpairs ? (tpairs - wave + WPB - 1) / WPB : 0) : ((nmine + 1) >> 1);
+  const int64_t tile = blockIdx.x;
+  const TileCtx<NBW, 4> c = tile_ctx<NBW, 4>(smem, tile, in, ci, in_bytes, ALIGNED ? (ci >> 5) : nkc_of(ci), co, V_out, words,
+                                             words_bytes, vol, Wp, wp_bytes);
+  const int nkc = c.nkc;
+  const int npairs = pair_count<ADJ, WPB>(c.wave, c.nblk);
   auto load_pair = [&](int pr) {
-    PairEnt p;
-    int bA = ADJ ? 2 * (wave + pr * WPB) : wave + (2 * pr) * WPB;
-    if (bA >= nblk) bA = nblk > 0 ? (ADJ ? ((nblk - 1) & ~1) : nblk - 1) : 0; // past the end: harmless re-read
-    int bB = bA + (ADJ ? 1 : WPB);
-    const bool hasB = bB < nblk;
-    if (!hasB) bB = bA;
-    p.eA = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, c16x4, ebase + (unsigned)bA * 64u, 0);
-    p.eB = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, c16x4, ebase + (unsigned)bB * 64u, 0);
-    if (!hasB) p.eB |= (int)0x80000000;
-    p.kA = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, 0u, kbase + (unsigned)bA * 4u, 0);
-    p.kB = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, 0u, kbase + (unsigned)bB * 4u, 0);
-    return p;
+    int bA, bB;
+    pair_blocks<ADJ, WPB>(c.wave, pr, c.nblk, bA, bB);
+    return load_block_pair(c, bA, bB);
   };
-  auto gather = [&](GStep &q, const PairEnt &p, int kc) {
-    const unsigned va = (((unsigned)p.eA & 0x7fffffffu) >> 6) * rowbytes + g32;
-    const unsigned vb = (((unsigned)p.eB & 0x7fffffffu) >> 6) * rowbytes + g32;
-    const unsigned so = (unsigned)kc * 128u;
-    if (ALIGNED) {
-      q.a0 = __builtin_amdgcn_raw_buffer_load_b128(rin, va, so, 0);
-      q.a1 = __builtin_amdgcn_raw_buffer_load_b128(rin, va + 16u, so, 0);
-      q.b0 = __builtin_amdgcn_raw_buffer_load_b128(rin, vb, so, 0);
-      q.b1 = __builtin_amdgcn_raw_buffer_load_b128(rin, vb + 16u, so, 0);
-    } else {
-      // any plane count (the 9-plane first layer): element loads, planes past ci read as zero (their packed
-      // weights are zero too); rows are ci*4 bytes apart, not 16-byte aligned
-      const int c0 = kc * kKC + g * 8;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const bool ok0 = c0 + t < ci, ok1 = c0 + 4 + t < ci;
-        q.a0[t] = ok0 ? __builtin_amdgcn_raw_buffer_load_b32(rin, va + 4u * t, so, 0) : 0u;
-        q.a1[t] = ok1 ? __builtin_amdgcn_raw_buffer_load_b32(rin, va + 16u + 4u * t, so, 0) : 0u;
-        q.b0[t] = ok0 ? __builtin_amdgcn_raw_buffer_load_b32(rin, vb + 4u * t, so, 0) : 0u;
-        q.b1[t] = ok1 ? __builtin_amdgcn_raw_buffer_load_b32(rin, vb + 16u + 4u * t, so, 0) : 0u;
-      }
-    }
-  };
+  auto gather = [&](GStep &q, const PairEnt &p, int kc) { gather_rows<ALIGNED>(c, ci, p, kc, q.a0, q.a1, q.b0, q.b1); };
   PairEnt p0 = load_pair(0), p1 = load_pair(1), p2 = load_pair(2);
   GStep s0, s1;
   if (npairs > 0) gather(s0, p0, 0);
@@ -558,8 +428,8 @@ __global__ __launch_bounds__(WPB * 64, (NBW <= 2 ? 3 : 2)) void k_conv_blocks_mf
   for (int pr = 0; pr < npairs; ++pr) {
     int kA = __builtin_amdgcn_readfirstlane(p0.kA), kB = __builtin_amdgcn_readfirstlane(p0.kB);
     if (wflip) { kA = vol - 1 - kA; kB = vol - 1 - kB; }
-    const unsigned soA0 = (unsigned)kA * wk_bytes + (unsigned)nb0 * 2048u;
-    const unsigned soB0 = (unsigned)kB * wk_bytes + (unsigned)nb0 * 2048u;
+    const unsigned soA0 = (unsigned)kA * c.wk_bytes + (unsigned)c.nb0 * 2048u;
+    const unsigned soB0 = (unsigned)kB * c.wk_bytes + (unsigned)c.nb0 * 2048u;
 #pragma unroll
     for (int j = 0; j < NBW; ++j) {
       accA[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -569,50 +439,20 @@ __global__ __launch_bounds__(WPB * 64, (NBW <= 2 ? 3 : 2)) void k_conv_blocks_mf
       const bool more = (kc + 1 < nkc) || (pr + 1 < npairs);
       const PairEnt &pn = (kc + 1 < nkc) ? p0 : p1;
       const int kcn = (kc + 1 < nkc) ? kc + 1 : 0;
-      const unsigned so = (unsigned)kc * (unsigned)nnb * 2048u;
+      const unsigned so = (unsigned)kc * c.kc_bytes;
       if (step & 1) {
         if (more) gather(s0, pn, kcn);
-        conv_step_mfma_buf<NBW, ADJ>(s1, rw, lane32, soA0 + so, soB0 + so, nvalid, accA, accB);
+        conv_step_mfma_buf<NBW, ADJ>(s1, c.rw, c.laneofs, soA0 + so, soB0 + so, c.nvalid, accA, accB);
       } else {
         if (more) gather(s1, pn, kcn);
-        conv_step_mfma_buf<NBW, ADJ>(s0, rw, lane32, soA0 + so, soB0 + so, nvalid, accA, accB);
+        conv_step_mfma_buf<NBW, ADJ>(s0, c.rw, c.laneofs, soA0 + so, soB0 + so, c.nvalid, accA, accB);
       }
     }
-    conv_block_accumulate<NBW, WS>(Ct, p0.eA, g, accA);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // A and B may hit the same row
-    conv_block_accumulate<NBW, WS>(Ct, p0.eB, g, accB);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    accumulate_pair<NBW>(c.Ct, p0.eA, p0.eB, c.g, accA, accB);
     p0 = p1; p1 = p2; p2 = load_pair(pr + 3);
   }
   __syncthreads();
-  const int nrows = (int)((V_out - row0) < 64 ? (V_out - row0) : 64);
-  const int wcols = (co - nb0 * 16) < NBW * 16 ? (co - nb0 * 16) : NBW * 16;
-  if ((co & 3) == 0) {
-    const int q = wcols >> 2;
-    for (int i = threadIdx.x; i < nrows * q; i += WPB * 64) {
-      int r = i / q, cq = i % q;
-      float4 v = *reinterpret_cast<const float4 *>(smem + r * WS + cq * 4);
-#pragma unroll
-      for (int w = 1; w < WPB; ++w) {
-        float4 u = *reinterpret_cast<const float4 *>(smem + (size_t)w * TILE + r * WS + cq * 4);
-        v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-      }
-      if (bias) {
-        const float *bb = bias + nb0 * 16 + cq * 4;
-        v.x += bb[0]; v.y += bb[1]; v.z += bb[2]; v.w += bb[3];
-      }
-      *reinterpret_cast<float4 *>(out + (row0 + r) * co + nb0 * 16 + cq * 4) = v;
-    }
-  } else {
-    for (int i = threadIdx.x; i < nrows * wcols; i += WPB * 64) {
-      int r = i / wcols, cc = i % wcols;
-      float v = smem[r * WS + cc];
-#pragma unroll
-      for (int w = 1; w < WPB; ++w) v += smem[(size_t)w * TILE + r * WS + cc];
-      if (bias) v += bias[nb0 * 16 + cc];
-      out[(row0 + r) * co + nb0 * 16 + cc] = v;
-    }
-  }
+  tile_epilogue<NBW, WPB, WPB * 64, true>(smem, threadIdx.x, out, co, V_out, tile * 64, c.nb0, bias);
 }
 
 // packed weights of JG column blocks for the two blocks (A, B) of a step: JG x 4 x 16 B per lane
@@ -638,22 +478,7 @@ __device__ inline void conv_step_mfma_w(const GStep &q, const WSet<JG> &w, int n
   for (int j = 0; j < JG; ++j) {
     if (j < nvalid) {
       f32x4 ca = accA[j], cb = accB[j];
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.a0[j][0]), bcf(q.a0[0]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.b0[j][0]), bcf(q.b0[0]), cb, 0, 0, 0);
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.a0[j][1]), bcf(q.a0[1]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.b0[j][1]), bcf(q.b0[1]), cb, 0, 0, 0);
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.a0[j][2]), bcf(q.a0[2]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.b0[j][2]), bcf(q.b0[2]), cb, 0, 0, 0);
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.a0[j][3]), bcf(q.a0[3]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.b0[j][3]), bcf(q.b0[3]), cb, 0, 0, 0);
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.a1[j][0]), bcf(q.a1[0]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.b1[j][0]), bcf(q.b1[0]), cb, 0, 0, 0);
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.a1[j][1]), bcf(q.a1[1]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.b1[j][1]), bcf(q.b1[1]), cb, 0, 0, 0);
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.a1[j][2]), bcf(q.a1[2]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.b1[j][2]), bcf(q.b1[2]), cb, 0, 0, 0);
-      ca = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.a1[j][3]), bcf(q.a1[3]), ca, 0, 0, 0);
-      cb = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(w.b1[j][3]), bcf(q.b1[3]), cb, 0, 0, 0);
+      AABR_MFMA16(ca, cb, w.a0[j], w.a1[j], w.b0[j], w.b1[j], q.a0, q.a1, q.b0, q.b1);
       accA[j] = ca; accB[j] = cb;
     }
   }
@@ -684,16 +509,6 @@ __device__ inline void conv_load_w_sel(WSet<JG> &w, __amdgpu_buffer_rsrc_t rw, u
   if (ADJ) conv_load_w_shared<JG>(w, rw, lane32, soA, soB, nvalid);
   else conv_load_w<JG>(w, rw, lane32, soA, soB, nvalid);
 }
-
-#define AABR_MFMA8(ACC, W0, W1, X0, X1)                                            \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(W0[0]), bcf(X0[0]), ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(W0[1]), bcf(X0[1]), ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(W0[2]), bcf(X0[2]), ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(W0[3]), bcf(X0[3]), ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(W1[0]), bcf(X1[0]), ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(W1[1]), bcf(X1[1]), ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(W1[2]), bcf(X1[2]), ACC, 0, 0, 0); \
-  ACC = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf(W1[3]), bcf(X1[3]), ACC, 0, 0, 0)
 
 template <int JG>
 __device__ inline void conv_step_mfma_w_shared(const GStep &q, const WSet<JG> &w, bool same, int nvalid, f32x4 *accA,
@@ -740,66 +555,23 @@ __global__ __launch_bounds__(WPB * 64, 2) void k_conv_blocks_mfma_wpipe(
     const float *__restrict__ in, int ci, int64_t in_bytes, float *__restrict__ out, int co, int64_t V_out,
     const int32_t *__restrict__ words, int64_t words_bytes, int vol, int wflip, const float *__restrict__ Wp,
     int64_t wp_bytes, const float *__restrict__ bias) {
-  constexpr int WS = NBW * 16;              // C-tile row stride (floats)
-  constexpr int TILE = 64 * WS;             // floats per wave
   constexpr int JG = NBW >= 2 ? 2 : 1;      // column blocks per weight set
   constexpr int NJG = NBW / JG;             // weight sets (micro-steps) per step
   extern __shared__ __align__(16) float smem[];
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int g = lane >> 4, c16 = lane & 15;
-  float *Ct = smem + (size_t)wave * TILE;
-  const int maxb = tb_maxb(vol);
-  const int nkc = ci >> 5, nnb = nnb_of(co);
-  const int nb0 = blockIdx.y * NBW;
-  const int64_t tile = blockIdx.x, row0 = tile * 64;
-  const int64_t ntiles = tb_ntiles(V_out);
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(in), 0, (int)in_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(Wp), 0, (int)wp_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwords =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(words), 0, (int)words_bytes, 0x00020000);
-  const int nblk = words[tile];
-  const unsigned kbase = (unsigned)((ntiles + tile * maxb) * 4);                       // byte offset of blk_k
-  const unsigned ebase = (unsigned)((ntiles + ntiles * maxb + tile * maxb * 16) * 4);  // byte offset of ent
-  const unsigned rowbytes = (unsigned)ci * 4u, g32 = (unsigned)g * 32u, lane32 = (unsigned)lane * 32u;
-  const unsigned wk_bytes = (unsigned)nkc * (unsigned)nnb * 2048u;                     // packed bytes per offset
-  const unsigned kc_bytes = (unsigned)nnb * 2048u;                                     // packed bytes per chunk
-  const unsigned c16x4 = (unsigned)c16 * 4u;
-  const int nvalid = (nnb - nb0) < NBW ? (nnb - nb0) : NBW;
-
-  for (int i = lane; i < TILE; i += 64) Ct[i] = 0.0f;
-
-  // ADJ: pairs of adjacent blocks (2j, 2j+1) dealt to the waves round-robin; else blocks dealt round-robin
-  // and a wave pairs its own consecutive ones
-  const int tpairs = (nblk + 1) >> 1;
-  const int nmine = wave < nblk ? (nblk - wave + WPB - 1) / WPB : 0;
-  const int npairs = ADJ ? (wave < tpairs ? (tpairs - wave + WPB - 1) / WPB : 0) : ((nmine + 1) >> 1);
+  const int64_t tile = blockIdx.x;
+  const TileCtx<NBW, 4> c = tile_ctx<NBW, 4>(smem, tile, in, ci, in_bytes, ci >> 5, co, V_out, words, words_bytes, vol, Wp,
+                                             wp_bytes);
+  const int npairs = pair_count<ADJ, WPB>(c.wave, c.nblk);
   auto load_pair = [&](int pr) {
-    PairEnt p;
-    int bA = ADJ ? 2 * (wave + pr * WPB) : wave + (2 * pr) * WPB;
-    if (bA >= nblk) bA = nblk > 0 ? (ADJ ? ((nblk - 1) & ~1) : nblk - 1) : 0; // past the end: harmless re-read
-    int bB = bA + (ADJ ? 1 : WPB);
-    const bool hasB = bB < nblk;
-    if (!hasB) bB = bA;
-    p.eA = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, c16x4, ebase + (unsigned)bA * 64u, 0);
-    p.eB = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, c16x4, ebase + (unsigned)bB * 64u, 0);
-    if (!hasB) p.eB |= (int)0x80000000;
-    p.kA = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, 0u, kbase + (unsigned)bA * 4u, 0);
-    p.kB = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, 0u, kbase + (unsigned)bB * 4u, 0);
-    return p;
+    int bA, bB;
+    pair_blocks<ADJ, WPB>(c.wave, pr, c.nblk, bA, bB);
+    return load_block_pair(c, bA, bB);
   };
-  auto gather = [&](GStep &q, const PairEnt &p, int kc) {
-    const unsigned va = (((unsigned)p.eA & 0x7fffffffu) >> 6) * rowbytes + g32;
-    const unsigned vb = (((unsigned)p.eB & 0x7fffffffu) >> 6) * rowbytes + g32;
-    const unsigned so = (unsigned)kc * 128u;
-    q.a0 = __builtin_amdgcn_raw_buffer_load_b128(rin, va, so, 0);
-    q.a1 = __builtin_amdgcn_raw_buffer_load_b128(rin, va + 16u, so, 0);
-    q.b0 = __builtin_amdgcn_raw_buffer_load_b128(rin, vb, so, 0);
-    q.b1 = __builtin_amdgcn_raw_buffer_load_b128(rin, vb + 16u, so, 0);
-  };
+  auto gather = [&](GStep &q, const PairEnt &p, int kc) { gather_rows<true>(c, ci, p, kc, q.a0, q.a1, q.b0, q.b1); };
   // byte offsets (wave-uniform) of a pair's packed weights for this column slab
   auto w_base = [&](int k) {
     if (wflip) k = vol - 1 - k;
-    return (unsigned)k * wk_bytes + (unsigned)nb0 * 2048u;
+    return (unsigned)k * c.wk_bytes + (unsigned)c.nb0 * 2048u;
   };
   // block entries run three pairs ahead: a pair's offsets (wave-uniform, needed one step early for the
   // weight prefetch) have been in flight for two pairs when they are first read, so waiting for them
@@ -816,7 +588,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void k_conv_blocks_mfma_wpipe(
   }
   if (npairs > 0) {
     gather(s0, p0, 0);
-    if (WPIPE) conv_load_w_sel<JG, ADJ>(w0, rw, lane32, soA, soB, nvalid);
+    if (WPIPE) conv_load_w_sel<JG, ADJ>(w0, c.rw, c.laneofs, soA, soB, c.nvalid);
   }
 #pragma unroll
   for (int j = 0; j < NBW; ++j) {
@@ -831,35 +603,32 @@ __global__ __launch_bounds__(WPB * 64, 2) void k_conv_blocks_mfma_wpipe(
     // loop state is wave-uniform; say so (keeps the buffer soffsets in SGPRs, no waterfall loops)
     kc = __builtin_amdgcn_readfirstlane(kc); pr = __builtin_amdgcn_readfirstlane(pr);
     soA = __builtin_amdgcn_readfirstlane(soA); soB = __builtin_amdgcn_readfirstlane(soB);
-    const bool last_kc = kc + 1 == nkc;
+    const bool last_kc = kc + 1 == c.nkc;
     const bool more = !last_kc || (pr + 1 < npairs);
     const PairEnt &pn = last_kc ? p1 : p0;
     const int kcn = last_kc ? 0 : kc + 1;
     if (more) gather(xn, pn, kcn);
-    const unsigned cA = soA + (unsigned)kc * kc_bytes, cB = soB + (unsigned)kc * kc_bytes;
+    const unsigned cA = soA + (unsigned)kc * c.kc_bytes, cB = soB + (unsigned)kc * c.kc_bytes;
     if (!WPIPE) {
       // weights stream from L2 right before their MFMAs (other waves cover the latency)
-      conv_step_mfma_stream<NBW>(xc, rw, lane32, cA, cB, nvalid, accA, accB);
+      conv_step_mfma_stream<NBW>(xc, c.rw, c.laneofs, cA, cB, c.nvalid, accA, accB);
     } else {
       soA1 = __builtin_amdgcn_readfirstlane(soA1); soB1 = __builtin_amdgcn_readfirstlane(soB1);
-      const unsigned nA = last_kc ? soA1 : cA + kc_bytes; // first weight set of the next step
-      const unsigned nB = last_kc ? soB1 : cB + kc_bytes;
+      const unsigned nA = last_kc ? soA1 : cA + c.kc_bytes; // first weight set of the next step
+      const unsigned nB = last_kc ? soB1 : cB + c.kc_bytes;
       const bool same = ADJ && soA == soB; // both blocks of the pair use the same filter offset (wave-uniform)
       if (NJG == 1) {
-        if (more) conv_load_w_sel<JG, ADJ>(wo, rw, lane32, nA, nB, nvalid);
-        conv_step_mfma_w_shared<JG>(xc, wc, same, nvalid, accA, accB);
+        if (more) conv_load_w_sel<JG, ADJ>(wo, c.rw, c.laneofs, nA, nB, c.nvalid);
+        conv_step_mfma_w_shared<JG>(xc, wc, same, c.nvalid, accA, accB);
       } else {
-        conv_load_w_sel<JG, ADJ>(wo, rw, lane32, cA + JG * 2048u, cB + JG * 2048u, nvalid - JG);
-        conv_step_mfma_w_shared<JG>(xc, wc, same, nvalid, accA, accB);
-        if (more) conv_load_w_sel<JG, ADJ>(wc, rw, lane32, nA, nB, nvalid);
-        conv_step_mfma_w_shared<JG>(xc, wo, same, nvalid - JG, accA + JG, accB + JG);
+        conv_load_w_sel<JG, ADJ>(wo, c.rw, c.laneofs, cA + JG * 2048u, cB + JG * 2048u, c.nvalid - JG);
+        conv_step_mfma_w_shared<JG>(xc, wc, same, c.nvalid, accA, accB);
+        if (more) conv_load_w_sel<JG, ADJ>(wc, c.rw, c.laneofs, nA, nB, c.nvalid);
+        conv_step_mfma_w_shared<JG>(xc, wo, same, c.nvalid - JG, accA + JG, accB + JG);
       }
     }
     if (last_kc) {
-      conv_block_accumulate<NBW, WS>(Ct, p0.eA, g, accA);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // A and B may hit the same row
-      conv_block_accumulate<NBW, WS>(Ct, p0.eB, g, accB);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      accumulate_pair<NBW>(c.Ct, p0.eA, p0.eB, c.g, accA, accB);
 #pragma unroll
       for (int j = 0; j < NBW; ++j) {
         accA[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -891,34 +660,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void k_conv_blocks_mfma_wpipe(
     }
   }
   __syncthreads();
-  const int nrows = (int)((V_out - row0) < 64 ? (V_out - row0) : 64);
-  const int wcols = (co - nb0 * 16) < NBW * 16 ? (co - nb0 * 16) : NBW * 16;
-  if ((co & 3) == 0) {
-    const int q = wcols >> 2;
-    for (int i = threadIdx.x; i < nrows * q; i += WPB * 64) {
-      int r = i / q, cq = i % q;
-      float4 v = *reinterpret_cast<const float4 *>(smem + r * WS + cq * 4);
-#pragma unroll
-      for (int w = 1; w < WPB; ++w) {
-        float4 u = *reinterpret_cast<const float4 *>(smem + (size_t)w * TILE + r * WS + cq * 4);
-        v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-      }
-      if (bias) {
-        const float *bb = bias + nb0 * 16 + cq * 4;
-        v.x += bb[0]; v.y += bb[1]; v.z += bb[2]; v.w += bb[3];
-      }
-      *reinterpret_cast<float4 *>(out + (row0 + r) * co + nb0 * 16 + cq * 4) = v;
-    }
-  } else {
-    for (int i = threadIdx.x; i < nrows * wcols; i += WPB * 64) {
-      int r = i / wcols, cc = i % wcols;
-      float v = smem[r * WS + cc];
-#pragma unroll
-      for (int w = 1; w < WPB; ++w) v += smem[(size_t)w * TILE + r * WS + cc];
-      if (bias) v += bias[nb0 * 16 + cc];
-      out[(row0 + r) * co + nb0 * 16 + cc] = v;
-    }
-  }
+  tile_epilogue<NBW, WPB, WPB * 64, true>(smem, threadIdx.x, out, co, V_out, tile * 64, c.nb0, bias);
 }
 
 // ------------------------------------------------------------------ tiny rule books
@@ -928,106 +670,60 @@ __global__ __launch_bounds__(WPB * 64, 2) void k_conv_blocks_mfma_wpipe(
 // 32-channel chunk of one block pair, so a tile's ~15 pairs x 4-8 chunks spread over 8 waves x (co/16)
 // workgroups.  Every item ends with its own LDS accumulate (private tile per wave, summed in wave order:
 // still deterministic).  Gathers and weights are prefetched one item ahead (fixed register sets).
-struct ItemEnt { int eA, eB, kA, kB; };
-
 template <int WPB>
 __global__ __launch_bounds__(WPB * 64, 1) void k_conv_blocks_mfma_small(
     const float *__restrict__ in, int ci, int64_t in_bytes, float *__restrict__ out, int co, int64_t V_out,
     const int32_t *__restrict__ words, int64_t words_bytes, int vol, int wflip, const float *__restrict__ Wp,
     int64_t wp_bytes, const float *__restrict__ bias) {
-  constexpr int WS = 16, TILE = 64 * WS;
   extern __shared__ __align__(16) float smem[];
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int g = lane >> 4, c16 = lane & 15;
-  float *Ct = smem + (size_t)wave * TILE;
-  const int maxb = tb_maxb(vol);
-  const int nkc = ci >> 5, nnb = nnb_of(co);
-  const int nb0 = blockIdx.y;
-  const int64_t tile = blockIdx.x, row0 = tile * 64;
-  const int64_t ntiles = tb_ntiles(V_out);
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(in), 0, (int)in_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(Wp), 0, (int)wp_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwords =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(words), 0, (int)words_bytes, 0x00020000);
-  const int nblk = words[tile];
-  const unsigned kbase = (unsigned)((ntiles + tile * maxb) * 4);
-  const unsigned ebase = (unsigned)((ntiles + ntiles * maxb + tile * maxb * 16) * 4);
-  const unsigned rowbytes = (unsigned)ci * 4u, g32 = (unsigned)g * 32u, lane32 = (unsigned)lane * 32u;
-  const unsigned wk_bytes = (unsigned)nkc * (unsigned)nnb * 2048u, kc_bytes = (unsigned)nnb * 2048u;
-  const unsigned c16x4 = (unsigned)c16 * 4u;
-
-  for (int i = lane; i < TILE; i += 64) Ct[i] = 0.0f;
+  const int64_t tile = blockIdx.x;
+  const TileCtx<1, 4> c = tile_ctx<1, 4>(smem, tile, in, ci, in_bytes, ci >> 5, co, V_out, words, words_bytes, vol, Wp, wp_bytes);
+  const int wave = c.wave, nkc = c.nkc, nblk = c.nblk;
 
   const int nitems = ((nblk + 1) >> 1) * nkc;               // (block pair, channel chunk)
   const int nmine = wave < nitems ? (nitems - wave + WPB - 1) / WPB : 0;
   auto load_item = [&](int j) {                             // this wave's j-th item
-    ItemEnt p;
     int it = wave + j * WPB;
     if (it >= nitems) it = nitems > 0 ? nitems - 1 : 0;     // past the end: harmless re-read, never consumed
     int bA = 2 * (it / nkc);
     if (bA >= nblk) bA = 0;
-    int bB = bA + 1;
-    const bool hasB = bB < nblk;
-    if (!hasB) bB = bA;
-    p.eA = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, c16x4, ebase + (unsigned)bA * 64u, 0);
-    p.eB = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, c16x4, ebase + (unsigned)bB * 64u, 0);
-    if (!hasB) p.eB |= (int)0x80000000;
-    p.kA = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, 0u, kbase + (unsigned)bA * 4u, 0);
-    p.kB = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, 0u, kbase + (unsigned)bB * 4u, 0);
-    return p;
+    return load_block_pair(c, bA, bA + 1);
   };
   auto kc_of = [&](int j) {
     int it = wave + j * WPB;
     if (it >= nitems) it = nitems > 0 ? nitems - 1 : 0;
     return it % nkc;
   };
-  auto fetch = [&](GStep &q, WSet<1> &w, const ItemEnt &p, int kc) {
-    const unsigned va = (((unsigned)p.eA & 0x7fffffffu) >> 6) * rowbytes + g32;
-    const unsigned vb = (((unsigned)p.eB & 0x7fffffffu) >> 6) * rowbytes + g32;
-    const unsigned so = (unsigned)kc * 128u;
-    q.a0 = __builtin_amdgcn_raw_buffer_load_b128(rin, va, so, 0);
-    q.a1 = __builtin_amdgcn_raw_buffer_load_b128(rin, va + 16u, so, 0);
-    q.b0 = __builtin_amdgcn_raw_buffer_load_b128(rin, vb, so, 0);
-    q.b1 = __builtin_amdgcn_raw_buffer_load_b128(rin, vb + 16u, so, 0);
+  auto fetch = [&](GStep &q, WSet<1> &w, const PairEnt &p, int kc) {
+    gather_rows<true>(c, ci, p, kc, q.a0, q.a1, q.b0, q.b1);
     int kA = __builtin_amdgcn_readfirstlane(p.kA), kB = __builtin_amdgcn_readfirstlane(p.kB);
     if (wflip) { kA = vol - 1 - kA; kB = vol - 1 - kB; }
-    const unsigned off = (unsigned)kc * kc_bytes + (unsigned)nb0 * 2048u;
-    conv_load_w<1>(w, rw, lane32, (unsigned)kA * wk_bytes + off, (unsigned)kB * wk_bytes + off, 1);
+    const unsigned off = (unsigned)kc * c.kc_bytes + (unsigned)c.nb0 * 2048u;
+    conv_load_w<1>(w, c.rw, c.laneofs, (unsigned)kA * c.wk_bytes + off, (unsigned)kB * c.wk_bytes + off, 1);
   };
-  auto compute = [&](const GStep &q, const WSet<1> &w, const ItemEnt &p) {
+  auto compute = [&](const GStep &q, const WSet<1> &w, const PairEnt &p) {
     f32x4 accA[1] = {(f32x4){0.f, 0.f, 0.f, 0.f}}, accB[1] = {(f32x4){0.f, 0.f, 0.f, 0.f}};
     conv_step_mfma_w<1>(q, w, 1, accA, accB);
-    conv_block_accumulate<1, WS>(Ct, p.eA, g, accA);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // A and B may hit the same row
-    conv_block_accumulate<1, WS>(Ct, p.eB, g, accB);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    accumulate_pair<1>(c.Ct, p.eA, p.eB, c.g, accA, accB);
   };
-  ItemEnt e0 = load_item(0), e1 = load_item(1), e2 = load_item(2);
+  PairEnt e0 = load_item(0), e1 = load_item(1), e2 = load_item(2);
   GStep s0, s1;
   WSet<1> w0, w1;
   if (nmine > 0) fetch(s0, w0, e0, kc_of(0));
   for (int j = 0; j < nmine; j += 2) {
     if (j + 1 < nmine) fetch(s1, w1, e1, kc_of(j + 1));
     compute(s0, w0, e0);
-    ItemEnt e3 = load_item(j + 3);
+    PairEnt e3 = load_item(j + 3);
     if (j + 1 < nmine) {
       if (j + 2 < nmine) fetch(s0, w0, e2, kc_of(j + 2));
       compute(s1, w1, e1);
     }
-    ItemEnt e4 = load_item(j + 4);
+    PairEnt e4 = load_item(j + 4);
     e0 = e2; e1 = e3; e2 = e4;
   }
   __syncthreads();
-  const int nrows = (int)((V_out - row0) < 64 ? (V_out - row0) : 64);
-  const int wcols = (co - nb0 * 16) < 16 ? (co - nb0 * 16) : 16;
-  for (int i = threadIdx.x; i < nrows * wcols; i += WPB * 64) {
-    const int r = i / wcols, cc = i - r * wcols;
-    float v = smem[r * WS + cc];
-#pragma unroll
-    for (int w = 1; w < WPB; ++w) v += smem[(size_t)w * TILE + r * WS + cc];
-    if (bias) v += bias[nb0 * 16 + cc];
-    out[(row0 + r) * co + nb0 * 16 + cc] = v;
-  }
+  // the scalar path only (VEC = false): this kernel never had the vector one, and its speed is tuned as it is
+  tile_epilogue<1, WPB, WPB * 64, false>(smem, threadIdx.x, out, co, V_out, tile * 64, c.nb0, bias);
 }
 
 // ------------------------------------------------------------------ LDS-resident weights
@@ -1052,22 +748,7 @@ __device__ inline void conv_step_mfma_lds(const GStep &q, const float *__restric
     const f32x4 u0 = *reinterpret_cast<const f32x4 *>(WB + j * 512 + lane * 4);
     const f32x4 u1 = *reinterpret_cast<const f32x4 *>(WB + j * 512 + 256 + lane * 4);
     f32x4 ca = accA[j], cb = accB[j];
-    ca = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[0], bcf(q.a0[0]), ca, 0, 0, 0);
-    cb = __builtin_amdgcn_mfma_f32_16x16x4f32(u0[0], bcf(q.b0[0]), cb, 0, 0, 0);
-    ca = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[1], bcf(q.a0[1]), ca, 0, 0, 0);
-    cb = __builtin_amdgcn_mfma_f32_16x16x4f32(u0[1], bcf(q.b0[1]), cb, 0, 0, 0);
-    ca = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[2], bcf(q.a0[2]), ca, 0, 0, 0);
-    cb = __builtin_amdgcn_mfma_f32_16x16x4f32(u0[2], bcf(q.b0[2]), cb, 0, 0, 0);
-    ca = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[3], bcf(q.a0[3]), ca, 0, 0, 0);
-    cb = __builtin_amdgcn_mfma_f32_16x16x4f32(u0[3], bcf(q.b0[3]), cb, 0, 0, 0);
-    ca = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[0], bcf(q.a1[0]), ca, 0, 0, 0);
-    cb = __builtin_amdgcn_mfma_f32_16x16x4f32(u1[0], bcf(q.b1[0]), cb, 0, 0, 0);
-    ca = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[1], bcf(q.a1[1]), ca, 0, 0, 0);
-    cb = __builtin_amdgcn_mfma_f32_16x16x4f32(u1[1], bcf(q.b1[1]), cb, 0, 0, 0);
-    ca = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[2], bcf(q.a1[2]), ca, 0, 0, 0);
-    cb = __builtin_amdgcn_mfma_f32_16x16x4f32(u1[2], bcf(q.b1[2]), cb, 0, 0, 0);
-    ca = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[3], bcf(q.a1[3]), ca, 0, 0, 0);
-    cb = __builtin_amdgcn_mfma_f32_16x16x4f32(u1[3], bcf(q.b1[3]), cb, 0, 0, 0);
+    AABR_MFMA16(ca, cb, w0, w1, u0, u1, q.a0, q.a1, q.b0, q.b1);
     accA[j] = ca; accB[j] = cb;
   }
 }
@@ -1083,19 +764,15 @@ __global__ __launch_bounds__(512, 1) void k_conv_blocks_mfma_wlds(
     const float *__restrict__ in, int ci, int64_t in_bytes, float *__restrict__ out, int co, int64_t V_out,
     const int32_t *__restrict__ words, int64_t words_bytes, int vol, int wflip, const float *__restrict__ Wp,
     const float *__restrict__ bias) {
-  constexpr int WS = NBW * 16;
-  constexpr int TILE = 64 * WS;
   constexpr int RING = 4;
   extern __shared__ __align__(16) float smem[];
   const int NW = blockDim.x >> 6;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int g = lane >> 4, c16 = lane & 15;
+  const int wave0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nnb = nnb_of(co);
   const int nb0 = blockIdx.y * NBW;
   const int nvalid = (nnb - nb0) < NBW ? (nnb - nb0) : NBW;
   const int wfloats = vol * NKC * NBW * 512;
   float *Wl = smem;
-  float *Ct = smem + wfloats + (size_t)wave * TILE;
   // ---- weight copy: global [k][kc][nb][lane][8] -> LDS [k][kc][j = nb - nb0][half][lane][4]
   for (int i = threadIdx.x; i < vol * NKC * NBW * 128; i += blockDim.x) {
     const int f = i >> 7, r = i & 127, ln = r >> 1, h = r & 1;
@@ -1105,59 +782,23 @@ __global__ __launch_bounds__(512, 1) void k_conv_blocks_mfma_wlds(
     *reinterpret_cast<float4 *>(Wl + ((kk * NBW + j) * 2 + h) * 256 + ln * 4) = v;
   }
   __syncthreads();
-  const int maxb = tb_maxb(vol);
   const int64_t ntiles = tb_ntiles(V_out);
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(in), 0, (int)in_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwords =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(words), 0, (int)words_bytes, 0x00020000);
-  const unsigned rowbytes = (unsigned)ci * 4u, g32 = (unsigned)g * 32u, c16x4 = (unsigned)c16 * 4u;
   constexpr int kstride = NKC * NBW * 512; // floats per offset in the LDS image
 
-  for (int64_t tile = (int64_t)blockIdx.x * NW + wave; tile < ntiles; tile += (int64_t)gridDim.x * NW) {
-    const int64_t row0 = tile * 64;
-    for (int i = lane; i < TILE; i += 64) Ct[i] = 0.0f;
-    const int nblk = __builtin_amdgcn_readfirstlane(words[tile]);
-    const unsigned kbase = (unsigned)((ntiles + tile * maxb) * 4);
-    const unsigned ebase = (unsigned)((ntiles + ntiles * maxb + tile * maxb * 16) * 4);
-    const int npairs = (nblk + 1) >> 1;
+  for (int64_t tile = (int64_t)blockIdx.x * NW + wave0; tile < ntiles; tile += (int64_t)gridDim.x * NW) {
+    // the context of this tile (the weights are in LDS: no descriptor for them); the wave's C tile follows the image
+    TileCtx<NBW, 4> c = tile_ctx<NBW, 4>(smem + wfloats, tile, in, ci, in_bytes, NKC, co, V_out, words, words_bytes, vol,
+                                         (const float *)nullptr, 0);
+    c.nblk = __builtin_amdgcn_readfirstlane(c.nblk);
+    const int npairs = (c.nblk + 1) >> 1;
     auto load_pair = [&](int pr) {
-      PairEnt p;
       int bA = 2 * pr;
-      if (bA >= nblk) bA = nblk > 0 ? nblk - 1 : 0; // past the end: harmless re-read, never consumed
-      int bB = bA + 1;
-      const bool hasB = bB < nblk;
-      if (!hasB) bB = bA;
-      p.eA = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, c16x4, ebase + (unsigned)bA * 64u, 0);
-      p.eB = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, c16x4, ebase + (unsigned)bB * 64u, 0);
-      if (!hasB) p.eB |= (int)0x80000000;
-      p.kA = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, 0u, kbase + (unsigned)bA * 4u, 0);
-      p.kB = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, 0u, kbase + (unsigned)bB * 4u, 0);
-      return p;
+      if (bA >= c.nblk) bA = c.nblk > 0 ? c.nblk - 1 : 0; // past the end: harmless re-read, never consumed
+      return load_block_pair(c, bA, bA + 1);
     };
     auto gather = [&](WStage<NKC> &q, const PairEnt &p) {
-      const unsigned va = (((unsigned)p.eA & 0x7fffffffu) >> 6) * rowbytes + g32;
-      const unsigned vb = (((unsigned)p.eB & 0x7fffffffu) >> 6) * rowbytes + g32;
 #pragma unroll
-      for (int kc = 0; kc < NKC; ++kc) {
-        const unsigned so = (unsigned)kc * 128u;
-        if (ALIGNED) {
-          q.a0[kc] = __builtin_amdgcn_raw_buffer_load_b128(rin, va, so, 0);
-          q.a1[kc] = __builtin_amdgcn_raw_buffer_load_b128(rin, va + 16u, so, 0);
-          q.b0[kc] = __builtin_amdgcn_raw_buffer_load_b128(rin, vb, so, 0);
-          q.b1[kc] = __builtin_amdgcn_raw_buffer_load_b128(rin, vb + 16u, so, 0);
-        } else {
-          // any plane count: element loads, channels past ci read as zero (their weights are zero too)
-          const int c0 = kc * kKC + g * 8;
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            const bool ok0 = c0 + t < ci, ok1 = c0 + 4 + t < ci;
-            q.a0[kc][t] = ok0 ? __builtin_amdgcn_raw_buffer_load_b32(rin, va + 4u * t, so, 0) : 0u;
-            q.a1[kc][t] = ok1 ? __builtin_amdgcn_raw_buffer_load_b32(rin, va + 16u + 4u * t, so, 0) : 0u;
-            q.b0[kc][t] = ok0 ? __builtin_amdgcn_raw_buffer_load_b32(rin, vb + 4u * t, so, 0) : 0u;
-            q.b1[kc][t] = ok1 ? __builtin_amdgcn_raw_buffer_load_b32(rin, vb + 16u + 4u * t, so, 0) : 0u;
-          }
-        }
-      }
+      for (int kc = 0; kc < NKC; ++kc) gather_rows<ALIGNED>(c, ci, p, kc, q.a0[kc], q.a1[kc], q.b0[kc], q.b1[kc]);
     };
     auto compute = [&](const WStage<NKC> &q, const PairEnt &p) {
       int kA = __builtin_amdgcn_readfirstlane(p.kA), kB = __builtin_amdgcn_readfirstlane(p.kB);
@@ -1173,12 +814,9 @@ __global__ __launch_bounds__(512, 1) void k_conv_blocks_mfma_wlds(
       for (int kc = 0; kc < NKC; ++kc) {
         GStep t;
         t.a0 = q.a0[kc]; t.a1 = q.a1[kc]; t.b0 = q.b0[kc]; t.b1 = q.b1[kc];
-        conv_step_mfma_lds<NBW>(t, WA0 + kc * NBW * 512, WB0 + kc * NBW * 512, lane, accA, accB);
+        conv_step_mfma_lds<NBW>(t, WA0 + kc * NBW * 512, WB0 + kc * NBW * 512, c.lane, accA, accB);
       }
-      conv_block_accumulate<NBW, WS>(Ct, p.eA, g, accA);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // A and B may hit the same row
-      conv_block_accumulate<NBW, WS>(Ct, p.eB, g, accB);
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      accumulate_pair<NBW>(c.Ct, p.eA, p.eB, c.g, accA, accB);
     };
     PairEnt p[2 * RING];
     WStage<NKC> st[RING];
@@ -1198,28 +836,8 @@ __global__ __launch_bounds__(512, 1) void k_conv_blocks_mfma_wlds(
         }
       }
     }
-    // the wave's own tile goes out once (+ bias, CPU/Convolution.cpp:59-62)
-    const int nrows = (int)((V_out - row0) < 64 ? (V_out - row0) : 64);
-    const int wcols = (co - nb0 * 16) < NBW * 16 ? (co - nb0 * 16) : NBW * 16;
-    if ((co & 3) == 0) {
-      const int q = wcols >> 2;
-      for (int i = lane; i < nrows * q; i += 64) {
-        const int r = i / q, cq = i - r * q;
-        float4 v = *reinterpret_cast<const float4 *>(Ct + r * WS + cq * 4);
-        if (bias) {
-          const float *bb = bias + nb0 * 16 + cq * 4;
-          v.x += bb[0]; v.y += bb[1]; v.z += bb[2]; v.w += bb[3];
-        }
-        *reinterpret_cast<float4 *>(out + (row0 + r) * co + nb0 * 16 + cq * 4) = v;
-      }
-    } else {
-      for (int i = lane; i < nrows * wcols; i += 64) {
-        const int r = i / wcols, cc = i - r * wcols;
-        float v = Ct[r * WS + cc];
-        if (bias) v += bias[nb0 * 16 + cc];
-        out[(row0 + r) * co + nb0 * 16 + cc] = v;
-      }
-    }
+    // the wave's own tile goes out once: one tile, 64 lanes
+    tile_epilogue<NBW, 1, 64, true>(c.Ct, c.lane, out, co, V_out, tile * 64, c.nb0, bias);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // tile reads done before the next tile's zero fill
   }
 }
@@ -1259,72 +877,41 @@ __global__ __launch_bounds__(WPB * 64, 2) void k_conv_blocks_mfma_bf16(
     const __bf16 *__restrict__ in, int ci, int64_t in_bytes, __bf16 *__restrict__ out, int co, int64_t V_out,
     const int32_t *__restrict__ words, int64_t words_bytes, int vol, int wflip, const __bf16 *__restrict__ Wp,
     int64_t wp_bytes, const float *__restrict__ bias) {
-  constexpr int WS = NBW * 16;
-  constexpr int TILE = 64 * WS;
   extern __shared__ __align__(16) float smem[];
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int g = lane >> 4, c16 = lane & 15;
-  float *Ct = smem + (size_t)wave * TILE;
-  const int maxb = tb_maxb(vol);
-  const int nnb = nnb_of(co), nkc = ci / kKC;
+  const int64_t tile = blockIdx.x;
+  const TileCtx<NBW, 2> c = tile_ctx<NBW, 2>(smem, tile, in, ci, in_bytes, ci / kKC, co, V_out, words, words_bytes, vol, Wp,
+                                             wp_bytes);
+  const int nkc = c.nkc;
   const int ngrp = (nkc + KG - 1) / KG;
-  const int nb0 = blockIdx.y * NBW;
-  const int64_t tile = blockIdx.x, row0 = tile * 64;
-  const int64_t ntiles = tb_ntiles(V_out);
-  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16 *>(in), 0, (int)in_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16 *>(Wp), 0, (int)wp_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rwords =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(words), 0, (int)words_bytes, 0x00020000);
-  const int nblk = words[tile];
-  const unsigned kbase = (unsigned)((ntiles + tile * maxb) * 4);
-  const unsigned ebase = (unsigned)((ntiles + ntiles * maxb + tile * maxb * 16) * 4);
-  const unsigned rowbytes = (unsigned)ci * 2u, g16 = (unsigned)g * 16u, lane16 = (unsigned)lane * 16u;
-  const unsigned wk_bytes = (unsigned)nkc * (unsigned)nnb * 1024u; // packed bytes per offset
-  const unsigned c16x4 = (unsigned)c16 * 4u;
-  const int nvalid = (nnb - nb0) < NBW ? (nnb - nb0) : NBW;
-
-  for (int i = lane; i < TILE; i += 64) Ct[i] = 0.0f;
-
-  // ADJ (throughput-bound launches): pairs of adjacent blocks, same-offset pairs share their weights
-  const int nmine = wave < nblk ? (nblk - wave + WPB - 1) / WPB : 0;
-  const int tpairs = (nblk + 1) >> 1;
-  const int npairs = ADJ ? (wave < tpairs ? (tpairs - wave + WPB - 1) / WPB : 0) : ((nmine + 1) >> 1);
-  const int nitems = npairs * ngrp;
-  struct Item { int eA, eB, kA, kB, kc0; };
+  const int nitems = pair_count<ADJ, WPB>(c.wave, c.nblk) * ngrp;
+  struct Item : PairEnt { int kc0; };
   auto load_item = [&](int it) {
     Item p;
     const int pr = it / ngrp;
+    int bA, bB;
+    pair_blocks<ADJ, WPB>(c.wave, pr, c.nblk, bA, bB);
+    static_cast<PairEnt &>(p) = load_block_pair(c, bA, bB);
     p.kc0 = (it - pr * ngrp) * KG;
-    int bA = ADJ ? 2 * (wave + pr * WPB) : wave + (2 * pr) * WPB;
-    if (bA >= nblk) bA = nblk > 0 ? (ADJ ? ((nblk - 1) & ~1) : nblk - 1) : 0;
-    int bB = bA + (ADJ ? 1 : WPB);
-    const bool hasB = bB < nblk;
-    if (!hasB) bB = bA;
-    p.eA = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, c16x4, ebase + (unsigned)bA * 64u, 0);
-    p.eB = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, c16x4, ebase + (unsigned)bB * 64u, 0);
-    if (!hasB) p.eB |= (int)0x80000000;
-    p.kA = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, 0u, kbase + (unsigned)bA * 4u, 0);
-    p.kB = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, 0u, kbase + (unsigned)bB * 4u, 0);
     return p;
   };
   // the KG channel chunks of an item are gathered together (KG x 2 x 16 B per lane in flight)
   struct G16 { u32x4 a[KG], b[KG]; };
   auto gather = [&](G16 &q, const Item &p) {
-    const unsigned va = (((unsigned)p.eA & 0x7fffffffu) >> 6) * rowbytes + g16;
-    const unsigned vb = (((unsigned)p.eB & 0x7fffffffu) >> 6) * rowbytes + g16;
+    const unsigned va = (((unsigned)p.eA & 0x7fffffffu) >> 6) * c.rowbytes + c.gofs;
+    const unsigned vb = (((unsigned)p.eB & 0x7fffffffu) >> 6) * c.rowbytes + c.gofs;
 #pragma unroll
     for (int t = 0; t < KG; ++t) {
       if (p.kc0 + t < nkc) {
-        q.a[t] = __builtin_amdgcn_raw_buffer_load_b128(rin, va, (unsigned)(p.kc0 + t) * 64u, 0);
-        q.b[t] = __builtin_amdgcn_raw_buffer_load_b128(rin, vb, (unsigned)(p.kc0 + t) * 64u, 0);
+        q.a[t] = __builtin_amdgcn_raw_buffer_load_b128(c.rin, va, (unsigned)(p.kc0 + t) * 64u, 0);
+        q.b[t] = __builtin_amdgcn_raw_buffer_load_b128(c.rin, vb, (unsigned)(p.kc0 + t) * 64u, 0);
       }
     }
   };
   auto compute = [&](const G16 &q, const Item &p) {
     int kA = __builtin_amdgcn_readfirstlane(p.kA), kB = __builtin_amdgcn_readfirstlane(p.kB);
     if (wflip) { kA = vol - 1 - kA; kB = vol - 1 - kB; }
-    const unsigned soA0 = (unsigned)kA * wk_bytes + (unsigned)nb0 * 1024u;
-    const unsigned soB0 = (unsigned)kB * wk_bytes + (unsigned)nb0 * 1024u;
+    const unsigned soA0 = (unsigned)kA * c.wk_bytes + (unsigned)c.nb0 * 1024u;
+    const unsigned soB0 = (unsigned)kB * c.wk_bytes + (unsigned)c.nb0 * 1024u;
     f32x4 accA[NBW], accB[NBW];
 #pragma unroll
     for (int j = 0; j < NBW; ++j) {
@@ -1336,12 +923,12 @@ __global__ __launch_bounds__(WPB * 64, 2) void k_conv_blocks_mfma_bf16(
     const bool same = ADJ && kA == kB; // wave-uniform
     u32x4 wA[2][NBW], wB[2][NBW];
     auto loadw = [&](int set, int t) {
-      const unsigned so = (unsigned)(p.kc0 + t) * (unsigned)nnb * 1024u;
+      const unsigned so = (unsigned)(p.kc0 + t) * c.kc_bytes;
 #pragma unroll
       for (int j = 0; j < NBW; ++j) {
-        if (j < nvalid) {
-          wA[set][j] = __builtin_amdgcn_raw_buffer_load_b128(rw, lane16, soA0 + so + j * 1024, 0);
-          if (!same) wB[set][j] = __builtin_amdgcn_raw_buffer_load_b128(rw, lane16, soB0 + so + j * 1024, 0);
+        if (j < c.nvalid) {
+          wA[set][j] = __builtin_amdgcn_raw_buffer_load_b128(c.rw, c.laneofs, soA0 + so + j * 1024, 0);
+          if (!same) wB[set][j] = __builtin_amdgcn_raw_buffer_load_b128(c.rw, c.laneofs, soB0 + so + j * 1024, 0);
         }
       }
     };
@@ -1353,7 +940,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void k_conv_blocks_mfma_bf16(
         if (same) {
 #pragma unroll
           for (int j = 0; j < NBW; ++j) {
-            if (j < nvalid) {
+            if (j < c.nvalid) {
               accA[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wA[t & 1][j]),
                                                                 __builtin_bit_cast(bf16x8, q.a[t]), accA[j], 0, 0, 0);
               accB[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wA[t & 1][j]),
@@ -1363,7 +950,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void k_conv_blocks_mfma_bf16(
         } else {
 #pragma unroll
           for (int j = 0; j < NBW; ++j) {
-            if (j < nvalid) {
+            if (j < c.nvalid) {
               accA[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wA[t & 1][j]),
                                                                 __builtin_bit_cast(bf16x8, q.a[t]), accA[j], 0, 0, 0);
               accB[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wB[t & 1][j]),
@@ -1373,10 +960,7 @@ __global__ __launch_bounds__(WPB * 64, 2) void k_conv_blocks_mfma_bf16(
         }
       }
     }
-    conv_block_accumulate<NBW, WS>(Ct, p.eA, g, accA);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    conv_block_accumulate<NBW, WS>(Ct, p.eB, g, accB);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    accumulate_pair<NBW>(c.Ct, p.eA, p.eB, c.g, accA, accB);
   };
   Item p0 = load_item(0), p1 = load_item(1), p2 = load_item(2);
   G16 s0, s1;
@@ -1393,37 +977,8 @@ __global__ __launch_bounds__(WPB * 64, 2) void k_conv_blocks_mfma_bf16(
     p0 = p2; p1 = p3; p2 = p4;
   }
   __syncthreads();
-  // combine in wave order, add bias, round to bf16 once, write the tile
-  const int nrows = (int)((V_out - row0) < 64 ? (V_out - row0) : 64);
-  const int wcols = (co - nb0 * 16) < NBW * 16 ? (co - nb0 * 16) : NBW * 16;
-  if ((co & 3) == 0) {
-    const int q = wcols >> 2;
-    for (int i = threadIdx.x; i < nrows * q; i += WPB * 64) {
-      int r = i / q, cq = i % q;
-      float4 v = *reinterpret_cast<const float4 *>(smem + r * WS + cq * 4);
-#pragma unroll
-      for (int w = 1; w < WPB; ++w) {
-        float4 u = *reinterpret_cast<const float4 *>(smem + (size_t)w * TILE + r * WS + cq * 4);
-        v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-      }
-      if (bias) {
-        const float *bb = bias + nb0 * 16 + cq * 4;
-        v.x += bb[0]; v.y += bb[1]; v.z += bb[2]; v.w += bb[3];
-      }
-      typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-      bf16x4 o = {(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
-      *reinterpret_cast<bf16x4 *>(out + (row0 + r) * co + nb0 * 16 + cq * 4) = o;
-    }
-  } else {
-    for (int i = threadIdx.x; i < nrows * wcols; i += WPB * 64) {
-      int r = i / wcols, cc = i % wcols;
-      float v = smem[r * WS + cc];
-#pragma unroll
-      for (int w = 1; w < WPB; ++w) v += smem[(size_t)w * TILE + r * WS + cc];
-      if (bias) v += bias[nb0 * 16 + cc];
-      out[(row0 + r) * co + nb0 * 16 + cc] = (__bf16)v;
-    }
-  }
+  // values are rounded to bf16 once, at the store
+  tile_epilogue<NBW, WPB, WPB * 64, true>(smem, threadIdx.x, out, co, V_out, tile * 64, c.nb0, bias);
 }
 
 // ------------------------------------------------------------------ compiled rule book, part 2

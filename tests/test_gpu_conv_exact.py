@@ -468,6 +468,44 @@ def test_tiles_strided_and_transposed_books(bf):
             check_exact("tiles", run_tiles, bk, 64, 96, 0, bias, 0, bf, prefix="k_conv_blocks_mfma")
 
 
+# Output planes that are no multiple of 4 (the epilogue's scalar stores) together with a last column slab that is only
+# partly filled: (book, bf16, planes in, planes out, knobs, the instance the rule decides, the generic instance the same
+# shape reaches under flags 8 << 8).  bf16 needs plane counts that are multiples of 32: its last slab is short, its
+# stores stay vectors.
+GENERIC = 8 << 8        # steers the decision to the flat-pointer kernel; none of that kernel's dbg & 1 / 2 / 4 branches
+RAGGED = [("large", False, 96, 198, {}, "k_conv_blocks_mfma_wpipe<4,3,true,false>", "k_conv_blocks_mfma<4,3,true>"),
+          ("large", False, 96, 134, {}, "k_conv_blocks_mfma_buf<2,4,true,true>", "k_conv_blocks_mfma<2,4,true>"),
+          ("large", False, 96, 70, {}, "k_conv_blocks_mfma_buf<1,4,true,true>", "k_conv_blocks_mfma<1,4,true>"),
+          ("large", False, 9, 6, {}, "k_conv_blocks_mfma_buf<1,4,true,false>", "k_conv_blocks_mfma<1,4,false>"),
+          ("large", False, 48, 198, {}, "k_conv_blocks_mfma_wlds<1,2,false>", "k_conv_blocks_mfma<4,3,false>"),
+          ("large", False, 96, 6, {}, "k_conv_blocks_mfma_small<16>", None),
+          ("large", True, 96, 160, {}, "k_conv_blocks_mfma_bf16<2,4,4,true>", None),
+          ("large", True, 64, 416, {}, "k_conv_blocks_mfma_bf16<4,2,2,true>", None),
+          ("small", False, 32, 134, {"CONV_WLDS": 2}, "k_conv_blocks_mfma_wlds<2,1,true>", None),
+          ("small", False, 96, 70, {"SMALL_WPB": 8}, "k_conv_blocks_mfma_small<8>", None),
+          ("small", False, 48, 198, {"CONV_WLDS": 0}, "k_conv_blocks_mfma_buf<1,4,true,false>", None)]
+
+
+def run_tiles_generic(bk, x, W, b, r, flags, bf):
+    return run_tiles(bk, x, W, b, r, flags | GENERIC, bf)
+
+
+@pytest.mark.parametrize("book,bf,n_in,n_out,knobs,inst,generic", RAGGED,
+                         ids=["%s-%s%d-%d" % (c[0], "bf16-" if c[1] else "", c[2], c[3]) for c in RAGGED])
+def test_tiles_ragged_columns_are_exact(request, book, bf, n_in, n_out, knobs, inst, generic):
+    """every kernel body's epilogue where co % 4 != 0 and / or the last column slab is partly filled, flags 0 and 3 with
+    bias; the launches of one shape share their operands and reference"""
+    _knobs(request, **{k: knobs.get(k) for k in R.KNOBS})
+    bk = tiles_book(book)
+    sizes = TT._sizes(n_in, n_out, bk.V_out, bk.vol, bf, False)
+    for flags in (0, 3):
+        assert R.name(TT._decide(bf, n_in, n_out, bk.V_out, bk.vol, flags, sizes, knobs)) == inst
+        check_exact("tiles", run_tiles, bk, n_in, n_out, flags, 1, 0, bf, variant=inst)
+        if generic:
+            assert R.name(TT._decide(bf, n_in, n_out, bk.V_out, bk.vol, flags | GENERIC, sizes, knobs)) == generic
+            check_exact("tiles", run_tiles_generic, bk, n_in, n_out, flags, 1, 0, bf, variant=generic)
+
+
 # -------------------------------------------------------------------------------------------------------- wide
 @pytest.mark.parametrize("T", [64, 128])
 @pytest.mark.parametrize("kg,nbuf,bf,ncb,split", TW._instance_cases())
