@@ -51,6 +51,10 @@ _SIGS = {
     "aabr_last_error": (C.c_char_p, []),
     "aabr_set_knob": (C.c_int, [C.c_char_p, C.c_int, C.c_int]),
     "aabr_quantize_points": (C.c_int, [_vp, _i32, _i64, C.c_double, _vp, _vp, _i64, _vp, _vp, _i32, _vp]),
+    "aabr_quantize_scenes_bl": (C.c_int, [_ppv, _ppv, _i64p, _i32, _i32, _i32, C.c_double, _i32p, _i64, _vp, _vp, _vp,
+                                          _vp]),
+    "aabr_bl_input_layer_sites": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aabr_bl_points_prepare": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aabr_input_layer_status_words": (C.c_int64, [_i64]),
     "aabr_input_layer_sites": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aabr_input_layer_pack_bits": (C.c_int, [_i64, _i32p]),

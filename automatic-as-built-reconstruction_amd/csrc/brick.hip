@@ -15,6 +15,7 @@
 // Row order inside a sample differs from the reference's first-seen order: parity is modulo the per-sample permutation
 // SURVEY.md 7 allows; an opt-in of Metadata_3 (site_order="brick"), first-seen stays the default.
 #include "geom.h"
+#include "point_reader.h"
 
 namespace aabr {
 
@@ -261,10 +262,11 @@ __global__ __launch_bounds__(256) void k_brick_remap_points(const int32_t *__res
 // WAVE of a point-per-thread launch was 20 k same-address atomics, 280 us at 320 k points)
 constexpr int kPrepItems = 4;      // points per thread, their loads issued together (a grid-stride loop of dependent
                                    // iterations at 1.2 workgroups per CU took 23 us for 15 MB at 320 k points)
-__global__ __launch_bounds__(256) void k_points_prepare(const int64_t *__restrict__ coords, int64_t n, int ncols,
+// Reader (point_reader.h): where point i's (x, y, z, batch) comes from and when the layer skips it
+template <typename Reader>
+__global__ __launch_bounds__(256) void k_points_prepare(const int64_t *__restrict__ coords, int64_t n, Reader rd,
                                                         int4 *__restrict__ pc, int32_t *meta, int32_t *__restrict__ first_pt,
-                                                        int32_t *__restrict__ cnt_extra, int32_t *__restrict__ head,
-                                                        int vec16) {
+                                                        int32_t *__restrict__ cnt_extra, int32_t *__restrict__ head) {
   int ext[4] = {-1, -1, -1, -1};
   bool bad = false;
   const int64_t base = (int64_t)blockIdx.x * (256 * kPrepItems) + threadIdx.x;
@@ -273,15 +275,7 @@ __global__ __launch_bounds__(256) void k_points_prepare(const int64_t *__restric
   for (int q = 0; q < kPrepItems; ++q) {
     const int64_t i = base + q * 256;
     cx[q] = cy[q] = cz[q] = -1; cb[q] = 0;
-    if (i < n) {
-      const int64_t *c = coords + i * ncols;
-      if (vec16) {             // ncols == 4 and a 16-byte aligned list: 32 bytes per point in two 16-byte loads
-        const longlong2 a = *reinterpret_cast<const longlong2 *>(c), b2 = *reinterpret_cast<const longlong2 *>(c + 2);
-        cx[q] = a.x; cy[q] = a.y; cz[q] = b2.x; cb[q] = b2.y;
-      } else {
-        cx[q] = c[0]; cy[q] = c[1]; cz[q] = c[2]; cb[q] = ncols == 4 ? c[3] : 0;
-      }
-    }
+    if (i < n) rd.load(coords, i, cx[q], cy[q], cz[q], cb[q]);
   }
 #pragma unroll
   for (int q = 0; q < kPrepItems; ++q) {
@@ -289,9 +283,10 @@ __global__ __launch_bounds__(256) void k_points_prepare(const int64_t *__restric
     if (i >= n) continue;
     const int64_t x = cx[q], y = cy[q], z = cz[q], b = cb[q];
     int4 o = make_int4(-1, -1, -1, 0);
-    if (x == -1 && y == -1 && z == -1) {
-      // dropped by aabr_quantize_points (outside FULL_SCALE): skipped silently
-    } else if (x < 0 || y < 0 || z < 0 || b < 0 || x > kMaxCoord || y > kMaxCoord || z > kMaxCoord || b > kMaxCoord) {
+    const int rc = rd.classify(x, y, z, b);
+    if (rc == kPtSkip) {
+      // dropped by aabr_quantize_points (outside FULL_SCALE) / an empty [B, L] row: skipped silently
+    } else if (rc == kPtBad) {
       bad = true;
     } else {
       o = make_int4((int)x, (int)y, (int)z, (int)b);
@@ -520,19 +515,38 @@ extern "C" int aabr_brick_convolution_tables(const int32_t *in_coords, int64_t V
   return AABR_OK;
 }
 
-extern "C" int aabr_points_prepare(const int64_t *coords, int64_t n, int ncols, int32_t *pc, int32_t *meta,
-                                   int32_t *first_pt, int32_t *cnt_extra, int32_t *head, void *stream_) {
+// the conversion pass behind aabr_points_prepare (FlatReader) and aabr_bl_points_prepare (BLReader); the caller has
+// checked n and what describes its layout, `fn` = the entry point's name for the argument messages
+template <typename Reader>
+static int points_prepare(const char *fn, const int64_t *coords, int64_t n, Reader rd, int32_t *pc, int32_t *meta,
+                          int32_t *first_pt, int32_t *cnt_extra, int32_t *head, void *stream_) {
   hipStream_t st = (hipStream_t)stream_;
-  AABR_CHECK_ARG(n >= 0 && n < (1ll << 31) - 65536 && (ncols == 3 || ncols == 4), "0 <= n < 2^31, ncols in {3,4}");
-  AABR_CHECK_ARG(meta && (n == 0 || (coords && pc)) && ((uintptr_t)pc & 15) == 0, "null / misaligned pointer");
-  AABR_CHECK_ARG((first_pt != nullptr) == (cnt_extra != nullptr) && (first_pt != nullptr) == (head != nullptr),
-                 "first_pt / cnt_extra / head: all three or none");
+  AABR_CHECK_ARG_AS(fn, meta && (n == 0 || (coords && pc)) && ((uintptr_t)pc & 15) == 0, "null / misaligned pointer");
+  AABR_CHECK_ARG_AS(fn, (first_pt != nullptr) == (cnt_extra != nullptr) && (first_pt != nullptr) == (head != nullptr),
+                    "first_pt / cnt_extra / head: all three or none");
   AABR_CHECK_HIP(hipMemsetAsync(meta, 0xFF, AABR_META_WORDS * sizeof(int32_t), st));
   if (n > 0)
-    hipLaunchKernelGGL(k_points_prepare, dim3((unsigned)ceil_div(n, 256 * kPrepItems)), dim3(256), 0, st, coords, n, ncols,
-                       (int4 *)pc, meta, first_pt, cnt_extra, head, (ncols == 4 && ((uintptr_t)coords & 15) == 0) ? 1 : 0);
+    hipLaunchKernelGGL(k_points_prepare<Reader>, dim3((unsigned)ceil_div(n, 256 * kPrepItems)), dim3(256), 0, st, coords, n,
+                       rd, (int4 *)pc, meta, first_pt, cnt_extra, head);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
+}
+
+extern "C" int aabr_points_prepare(const int64_t *coords, int64_t n, int ncols, int32_t *pc, int32_t *meta,
+                                   int32_t *first_pt, int32_t *cnt_extra, int32_t *head, void *stream_) {
+  AABR_CHECK_ARG(n >= 0 && n < (1ll << 31) - 65536 && (ncols == 3 || ncols == 4), "0 <= n < 2^31, ncols in {3,4}");
+  if (ncols == 4 && ((uintptr_t)coords & 15) == 0)
+    return points_prepare(__func__, coords, n, FlatReader16{}, pc, meta, first_pt, cnt_extra, head, stream_);
+  return points_prepare(__func__, coords, n, flat_reader(ncols), pc, meta, first_pt, cnt_extra, head, stream_);
+}
+
+// the [B, L, 3] form: point i = flat row b * L + l, pc[i].w = i / L, a row with x < 0 is empty (point_reader.h BLReader)
+extern "C" int aabr_bl_points_prepare(const int64_t *coords, int64_t B, int64_t L, int32_t *pc, int32_t *meta,
+                                      int32_t *first_pt, int32_t *cnt_extra, int32_t *head, void *stream_) {
+  AABR_CHECK_ARG(B >= 0 && L >= 0 && B <= kMaxCoord + 1 && L < (1ll << 31) && B * L < (1ll << 31) - 65536,
+                 "0 <= B <= 65535, 0 <= L, B * L < 2^31");
+  return points_prepare(__func__, coords, B * L, BLReader{(uint32_t)(L > 0 ? L : 1)}, pc, meta, first_pt, cnt_extra, head,
+                        stream_);
 }
 
 extern "C" int aabr_points_sites(const int32_t *pc, int64_t n, const int32_t *dims_host, const void *dir, const void *bricks,

@@ -272,6 +272,93 @@ __global__ __launch_bounds__(256) void k_quantize_points(const T *__restrict__ x
     for (int d = 0; d < 3; ++d) feats[i * fstride + d] = (float)(a[d] / scale);
 }
 
+// A1 for a padded [B, L] batch (BLInputLayer's layout): the same arithmetic per scene, all scenes of a chunk in ONE launch.
+// The scenes' pointers and sizes travel by value in the kernel arguments (no pointer table in device memory); a chunk holds
+// up to kQblScenes scenes.  Two kernels per chunk:
+//   k_qbl_min      : per-scene minimum of xyz.  A minimum is exact in any order, so blocks reduce in registers / LDS and
+//                    meet in one 64-bit atomicMin per block and axis on an ORDER-PRESERVING key of the value as a double
+//                    (a float converts exactly); the keys start at all ones (one fill for the whole batch).
+//   k_qbl_quantize : row l of scene b -> coords[b, l, :3], feats[b, l, :3 + cx] (xyz as a / scale, then the scene's extra
+//                    feature row), rows n_b .. L-1 -> -1 coordinates and zero features: every element of both outputs is
+//                    written here, nothing is filled beforehand.  A point outside full_scale is (-1, -1, -1) -- the same
+//                    row as padding, which is what BLInputLayer skips.
+constexpr int kQblScenes = 32;
+struct QblScenes {
+  const void *xyz[kQblScenes];
+  const float *extra[kQblScenes];
+  int32_t n[kQblScenes];
+  int32_t fs[3];
+};
+__device__ inline unsigned long long qbl_key(double v) {      // a < b  <=>  key(a) < key(b) (finite values)
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ inline double qbl_unkey(unsigned long long k) {
+  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_qbl_min(const QblScenes sc, unsigned long long *__restrict__ keys) {
+  const int s = blockIdx.y;
+  const T *__restrict__ xyz = (const T *)sc.xyz[s];
+  const int64_t n = sc.n[s];
+  unsigned long long m[3] = {~0ull, ~0ull, ~0ull};
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const unsigned long long k = qbl_key((double)xyz[3 * i + d]);
+      m[d] = k < m[d] ? k : m[d];
+    }
+  }
+  __shared__ unsigned long long s_m[4][3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1) {
+      const unsigned long long o = __shfl_xor(m[d], w);
+      m[d] = o < m[d] ? o : m[d];
+    }
+    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6][d] = m[d];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int d = threadIdx.x;
+    unsigned long long v = s_m[0][d];
+    for (int w = 1; w < 4; ++w) v = s_m[w][d] < v ? s_m[w][d] : v;
+    if (v != ~0ull) atomicMin(&keys[3 * s + d], v);
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_qbl_quantize(const QblScenes sc, const unsigned long long *__restrict__ keys,
+                                                      double scale, int64_t L, int cx, int64_t *__restrict__ coords,
+                                                      float *__restrict__ feats) {
+  const int s = blockIdx.y;
+  const int64_t l = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (l >= L) return;
+  const int64_t row = (int64_t)s * L + l;
+  int64_t *c = coords + 3 * row;
+  float *f = feats + (int64_t)(3 + cx) * row;
+  if (l >= sc.n[s]) {                         // padding
+    c[0] = c[1] = c[2] = -1;
+    for (int p = 0; p < 3 + cx; ++p) f[p] = 0.0f;
+    return;
+  }
+  const T *__restrict__ xyz = (const T *)sc.xyz[s];
+  double a[3];
+  bool keep = true;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    a[d] = (double)xyz[3 * l + d] * scale - qbl_unkey(keys[3 * s + d]) * scale;
+    keep = keep && a[d] >= 0.0 && a[d] < (double)sc.fs[d];
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    c[d] = keep ? (int64_t)a[d] : -1;
+    f[d] = (float)(a[d] / scale);
+  }
+  const float *__restrict__ e = sc.extra[s];
+  for (int p = 0; p < cx; ++p) f[3 + p] = e[(int64_t)cx * l + p];
+}
+
 __global__ __launch_bounds__(256) void k_spatial_locations(const int32_t *__restrict__ sc, int64_t n4,
                                                            int64_t *__restrict__ loc) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -485,6 +572,52 @@ extern "C" int aabr_quantize_points(const void *xyz, int is_double, int64_t n, d
     hipLaunchKernelGGL(k_quantize_points<float>, grid1(n, 256), dim3(256), 0, (hipStream_t)stream_,
                        (const float *)xyz, n, scale, (const float *)xyz_min, full_scale_dev, batch_index, locs,
                        feats_xyz, feat_stride);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
+extern "C" int aabr_quantize_scenes_bl(const void *const *xyz_host, const void *const *extra_host,
+                                       const int64_t *n_host, int nscenes, int is_double, int extra_planes, double scale,
+                                       const int32_t *full_scale_host, int64_t L, int64_t *coords, float *feats,
+                                       uint64_t *min_keys, void *stream_) {
+  hipStream_t st = (hipStream_t)stream_;
+  AABR_CHECK_ARG(nscenes >= 0 && nscenes <= kMaxCoord + 1 && L >= 0 && L < (1ll << 31) && extra_planes >= 0 && scale > 0 &&
+                     (int64_t)nscenes * L < (1ll << 31) - 65536,
+                 "0 <= scenes <= 65535, 0 <= L, scenes * L < 2^31, extra_planes >= 0, scale > 0");
+  AABR_CHECK_ARG(full_scale_host && (nscenes == 0 || (xyz_host && n_host)) && (extra_planes == 0 || nscenes == 0 || extra_host),
+                 "null host array");
+  for (int b = 0; b < nscenes; ++b) {
+    AABR_CHECK_ARG(n_host[b] >= 0 && n_host[b] <= L, "a scene holds more than L points");
+    AABR_CHECK_ARG(n_host[b] == 0 || (xyz_host[b] && (extra_planes == 0 || extra_host[b])), "null scene pointer");
+  }
+  if (nscenes == 0 || L == 0) return AABR_OK;
+  AABR_CHECK_ARG(coords && feats && min_keys, "null pointer");
+  AABR_CHECK_HIP(hipMemsetAsync(min_keys, 0xFF, (size_t)3 * nscenes * sizeof(uint64_t), st));
+  for (int b0 = 0; b0 < nscenes; b0 += kQblScenes) {
+    const int ns = nscenes - b0 < kQblScenes ? nscenes - b0 : kQblScenes;
+    QblScenes sc;
+    int64_t nmax = 0;
+    for (int s = 0; s < kQblScenes; ++s) {
+      sc.xyz[s] = s < ns ? xyz_host[b0 + s] : nullptr;
+      sc.extra[s] = (s < ns && extra_planes) ? (const float *)extra_host[b0 + s] : nullptr;
+      sc.n[s] = s < ns ? (int32_t)n_host[b0 + s] : 0;
+      nmax = sc.n[s] > nmax ? sc.n[s] : nmax;
+    }
+    for (int d = 0; d < 3; ++d) sc.fs[d] = full_scale_host[d];
+    unsigned long long *keys = (unsigned long long *)min_keys + 3 * (int64_t)b0;
+    int64_t *c = coords + 3 * (int64_t)b0 * L;
+    float *f = feats + (int64_t)(3 + extra_planes) * b0 * L;
+    if (nmax > 0) {                   // 8 points per thread; at most 64 blocks (192 atomics) per scene
+      int64_t bx = ceil_div(nmax, (int64_t)256 * 8);
+      bx = bx > 64 ? 64 : bx;
+      const dim3 gm((unsigned)bx, (unsigned)ns);
+      if (is_double) hipLaunchKernelGGL(k_qbl_min<double>, gm, dim3(256), 0, st, sc, keys);
+      else hipLaunchKernelGGL(k_qbl_min<float>, gm, dim3(256), 0, st, sc, keys);
+    }
+    const dim3 gq((unsigned)ceil_div(L, (int64_t)256), (unsigned)ns);
+    if (is_double) hipLaunchKernelGGL(k_qbl_quantize<double>, gq, dim3(256), 0, st, sc, keys, scale, L, extra_planes, c, f);
+    else hipLaunchKernelGGL(k_qbl_quantize<float>, gq, dim3(256), 0, st, sc, keys, scale, L, extra_planes, c, f);
+  }
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }

@@ -35,9 +35,13 @@
 //       that fits the L2s) and writes the block's 4096 finished grid entries, empty ones included, with 16-byte
 //       coalesced stores -- the table fill disappears.  Blocks are self-contained because every grid probes inside
 //       its home block (common.h grid_next).
+// BLInputLayer (the padded batch [B, L, 3], IOLayersRules.h:127-297 blRules) runs the GENERIC form and K2 unchanged: K1 and K2
+// take a point reader (point_reader.h) that says where point i's (x, y, z, batch) lies and when the layer skips it; first
+// appearance in ascending flat row b * L + l is blRules' sample-major first-seen numbering.  aabr_bl_input_layer_sites.
 // The packed / binned forms set meta[5] = 0 when a point does not fit the word (coordinate beyond the spatial size,
 // batch index beyond the bits left) or a block overflows; the caller then runs the generic form.
 #include "common.h"
+#include "point_reader.h"
 #include <stdlib.h>
 
 namespace aabr {
@@ -50,7 +54,9 @@ static inline int vs_items(int64_t) { return 4; }
 constexpr int kMetaTicket = 4;                  // meta word used as the chunk ticket counter
 constexpr int kMetaExtent = 8;                  // meta[8..11]: largest x, y, z, batch index over the valid points
 
-__global__ __launch_bounds__(256) void k_voxel_insert(const int64_t *__restrict__ coords, int64_t n, int ncols,
+// Reader (point_reader.h): where point i's (x, y, z, batch) comes from and when the layer skips it
+template <typename Reader>
+__global__ __launch_bounds__(256) void k_voxel_insert(const int64_t *__restrict__ coords, int64_t n, Reader rd,
                                                       GridEnt *keys, uint64_t mask,
                                                       int32_t *__restrict__ slot, int32_t *__restrict__ cnt_extra,
                                                       int32_t *__restrict__ head,
@@ -61,13 +67,13 @@ __global__ __launch_bounds__(256) void k_voxel_insert(const int64_t *__restrict_
   if (i >= n) return;
   cnt_extra[i] = 0;
   head[i] = -1;
-  const int64_t *c = coords + i * ncols;
-  int64_t x = c[0], y = c[1], z = c[2], b = ncols == 4 ? c[3] : 0;
-  if (x == -1 && y == -1 && z == -1) { // dropped by aabr_quantize_points (outside FULL_SCALE): skip silently
+  int64_t x, y, z, b;
+  const int rc = pt_read(rd, coords, i, x, y, z, b);
+  if (rc == kPtSkip) { // dropped by aabr_quantize_points (outside FULL_SCALE) / an empty [B, L] row: skip silently
     slot[i] = -1;
     return;
   }
-  if (x < 0 || y < 0 || z < 0 || b < 0 || x > kMaxCoord || y > kMaxCoord || z > kMaxCoord || b > kMaxCoord) {
+  if (rc == kPtBad) {
     slot[i] = -1;
     atomicAnd(&meta[2], 0); // meta starts at 0xFFFFFFFF (the one fill): 0 = a coordinate was out of range;
     return;                 // K2 rewrites the word as 0 / 1
@@ -86,9 +92,9 @@ __device__ inline unsigned long long st_pack(unsigned flag, unsigned v) {
 // point writes the whole grid entry); 2: binned (slot[i] = slot | first << 31, written by k_voxel_bin_build)
 constexpr int32_t kInfoNone = 0x7fffffff;
 constexpr int32_t kInfoMulti = 0x40000000;      // info bit 30: the point's voxel holds more than one point
-template <int kVsItems, int MODE>
+template <int kVsItems, int MODE, typename Reader>
 __global__ __launch_bounds__(kVsThreads) void k_voxel_number(
-    const int64_t *__restrict__ coords, int64_t n, int ncols, const int32_t *__restrict__ slot,
+    const int64_t *__restrict__ coords, int64_t n, Reader rd, const int32_t *__restrict__ slot,
     GridEnt *grid, int32_t *__restrict__ site_coords,
     int32_t *__restrict__ first_pt, int32_t *__restrict__ point_site, int32_t *cnt_extra, int32_t *head,
     int32_t *__restrict__ nxt, unsigned long long *status, int32_t *meta,
@@ -183,8 +189,9 @@ __global__ __launch_bounds__(kVsThreads) void k_voxel_number(
       const int64_t i = base + j;
       const int v = site_next++;
       mysite[j] = v;
-      const int64_t *cp = coords + i * ncols;
-      const int4 sc = make_int4((int)cp[0], (int)cp[1], (int)cp[2], ncols == 4 ? (int)cp[3] : 0);
+      int64_t cx, cy, cz, cb;
+      rd.load(coords, i, cx, cy, cz, cb);
+      const int4 sc = make_int4((int)cx, (int)cy, (int)cz, (int)cb);
       *reinterpret_cast<int4 *>(site_coords + 4 * (int64_t)v) = sc;
       ext[0] = sc.x > ext[0] ? sc.x : ext[0]; ext[1] = sc.y > ext[1] ? sc.y : ext[1];
       ext[2] = sc.z > ext[2] ? sc.z : ext[2]; ext[3] = sc.w > ext[3] ? sc.w : ext[3];
@@ -196,7 +203,7 @@ __global__ __launch_bounds__(kVsThreads) void k_voxel_number(
       }
       if (MODE == 1) {   // the grid entry is created here: key and first index first, the polled word last
         GridEnt *e = grid + s[j];
-        e->key = pack_key(ncols == 4 ? (int)cp[3] : 0, (int)cp[0], (int)cp[1], (int)cp[2]);
+        e->key = pack_key(sc.w, sc.x, sc.y, sc.z);
         e->first = (uint32_t)i;
       }
       __hip_atomic_store(&grid[s[j]].val, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // self-contained value
@@ -269,10 +276,9 @@ __device__ inline uint64_t pk_canonical(const PackSpec &p, unsigned long long w)
 // load + validate point i; returns 0 ok, 1 dropped silently, 2 out of the generic range, 3 does not fit the word
 __device__ inline int pk_load(const int64_t *__restrict__ coords, int64_t i, int ncols, const PackSpec &p, int &b,
                               int &x, int &y, int &z) {
-  const int64_t *c = coords + i * ncols;
-  const int64_t X = c[0], Y = c[1], Z = c[2], B = ncols == 4 ? c[3] : 0;
-  if (X == -1 && Y == -1 && Z == -1) return 1;
-  if (X < 0 || Y < 0 || Z < 0 || B < 0 || X > kMaxCoord || Y > kMaxCoord || Z > kMaxCoord || B > kMaxCoord) return 2;
+  int64_t X, Y, Z, B;
+  const int rc = pt_read(flat_reader(ncols), coords, i, X, Y, Z, B);   // kPtSkip = 1, kPtBad = 2
+  if (rc) return rc;
   if (X >= (1ll << p.xb) || Y >= (1ll << p.yb) || Z >= (1ll << p.zb) || B >= (1ll << p.bb) - 1) return 3;
   b = (int)B; x = (int)X; y = (int)Y; z = (int)Z;
   return 0;
@@ -686,18 +692,22 @@ extern "C" int64_t aabr_input_layer_status_words(int64_t n) {
   return 2 * ceil_div(n > 0 ? n : 1, (int64_t)kVsThreads * vs_items(n));
 }
 
-extern "C" int aabr_input_layer_sites(const int64_t *coords, int64_t n, int ncols, uint64_t *keys, int64_t cap,
-                                      int32_t *slot, int32_t *point_site, int32_t *site_coords, int32_t *first_pt,
-                                      int32_t *cnt_extra, int32_t *head, int32_t *nxt, int32_t *status, int32_t *meta,
-                                      void *stream_) {
+// the generic form behind aabr_input_layer_sites (FlatReader) and aabr_bl_input_layer_sites (BLReader); the caller has
+// checked n and what describes its layout, `fn` = the entry point's name for the argument messages
+template <typename Reader>
+static int input_layer_sites(const char *fn, const int64_t *coords, int64_t n, Reader rd, uint64_t *keys, int64_t cap,
+                             int32_t *slot, int32_t *point_site, int32_t *site_coords, int32_t *first_pt,
+                             int32_t *cnt_extra, int32_t *head, int32_t *nxt, int32_t *status, int32_t *meta,
+                             void *stream_) {
+#define AABR_CHECK_ARG_HERE(cond, msg) AABR_CHECK_ARG_AS(fn, cond, msg)
   hipStream_t st = (hipStream_t)stream_;
-  AABR_CHECK_ARG(n >= 0 && n < (1ll << 31) - 65536 && (ncols == 3 || ncols == 4), "0 <= n < 2^31, ncols in {3,4}");
-  AABR_CHECK_ARG(is_pow2(cap) && cap >= 2 * n && cap >= 64, "cap must be a power of two >= max(64, 2n)");
-  AABR_CHECK_ARG(keys && slot && point_site && site_coords && first_pt && cnt_extra && head && nxt && status && meta,
-                 "null pointer");
-  AABR_CHECK_ARG(((uintptr_t)status & 7) == 0 && ((uintptr_t)site_coords & 15) == 0 && ((uintptr_t)keys & 15) == 0,
-                 "status 8-, site_coords / grid entries 16-byte aligned");
-  AABR_CHECK_ARG(n == 0 || coords, "null coords");
+  AABR_CHECK_ARG_HERE(is_pow2(cap) && cap >= 2 * n && cap >= 64, "cap must be a power of two >= max(64, 2n)");
+  AABR_CHECK_ARG_HERE(keys && slot && point_site && site_coords && first_pt && cnt_extra && head && nxt && status && meta,
+                      "null pointer");
+  AABR_CHECK_ARG_HERE(((uintptr_t)status & 7) == 0 && ((uintptr_t)site_coords & 15) == 0 && ((uintptr_t)keys & 15) == 0,
+                      "status 8-, site_coords / grid entries 16-byte aligned");
+  AABR_CHECK_ARG_HERE(n == 0 || coords, "null coords");
+#undef AABR_CHECK_ARG_HERE
   GridEnt *grid = reinterpret_cast<GridEnt *>(keys);
   const int items = vs_items(n);
   const int64_t nchunks = ceil_div(n > 0 ? n : 1, (int64_t)kVsThreads * items);
@@ -714,13 +724,33 @@ extern "C" int aabr_input_layer_sites(const int64_t *coords, int64_t n, int ncol
     hipMemsetAsync(meta, 0xFF, AABR_META_WORDS * sizeof(int32_t), st);
   }
   // K1 also clears the chunk status words and the per-site chain heads / counts (consumed by K2 only)
-  hipLaunchKernelGGL(k_voxel_insert, grid1(n > nchunks ? n : nchunks, 256), dim3(256), 0, st, coords, n, ncols, grid,
+  hipLaunchKernelGGL(k_voxel_insert<Reader>, grid1(n > nchunks ? n : nchunks, 256), dim3(256), 0, st, coords, n, rd, grid,
                      (uint64_t)(cap - 1), slot, cnt_extra, head, (unsigned long long *)status, nchunks, meta);
-  hipLaunchKernelGGL((k_voxel_number<4, 0>), dim3((unsigned)nchunks), dim3(kVsThreads), 0, st, coords, n, ncols, slot,
+  hipLaunchKernelGGL((k_voxel_number<4, 0, Reader>), dim3((unsigned)nchunks), dim3(kVsThreads), 0, st, coords, n, rd, slot,
                      grid, site_coords, first_pt, point_site, cnt_extra, head, nxt,
                      (unsigned long long *)status, meta, (const unsigned long long *)nullptr, 0ull);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
+}
+
+extern "C" int aabr_input_layer_sites(const int64_t *coords, int64_t n, int ncols, uint64_t *keys, int64_t cap,
+                                      int32_t *slot, int32_t *point_site, int32_t *site_coords, int32_t *first_pt,
+                                      int32_t *cnt_extra, int32_t *head, int32_t *nxt, int32_t *status, int32_t *meta,
+                                      void *stream_) {
+  AABR_CHECK_ARG(n >= 0 && n < (1ll << 31) - 65536 && (ncols == 3 || ncols == 4), "0 <= n < 2^31, ncols in {3,4}");
+  return input_layer_sites(__func__, coords, n, flat_reader(ncols), keys, cap, slot, point_site, site_coords, first_pt,
+                           cnt_extra, head, nxt, status, meta, stream_);
+}
+
+// the [B, L, 3] form: point i = flat row b * L + l, batch index i / L, a row with x < 0 is empty (point_reader.h BLReader)
+extern "C" int aabr_bl_input_layer_sites(const int64_t *coords, int64_t B, int64_t L, uint64_t *keys, int64_t cap,
+                                         int32_t *slot, int32_t *point_site, int32_t *site_coords, int32_t *first_pt,
+                                         int32_t *cnt_extra, int32_t *head, int32_t *nxt, int32_t *status,
+                                         int32_t *meta, void *stream_) {
+  AABR_CHECK_ARG(B >= 0 && L >= 0 && B <= kMaxCoord + 1 && L < (1ll << 31) && B * L < (1ll << 31) - 65536,
+                 "0 <= B <= 65535, 0 <= L, B * L < 2^31");
+  return input_layer_sites(__func__, coords, B * L, BLReader{(uint32_t)(L > 0 ? L : 1)}, keys, cap, slot, point_site,
+                           site_coords, first_pt, cnt_extra, head, nxt, status, meta, stream_);
 }
 
 static int bits_for(int64_t v) {   // bits that hold 0 .. v-1
@@ -770,7 +800,8 @@ extern "C" int aabr_input_layer_sites_packed(const int64_t *coords, int64_t n, i
     hipLaunchKernelGGL(k_voxel_insert_packed, grid1(n, 256), dim3(256), 0, st, coords, n, ncols, sp,
                        (unsigned long long *)words, (uint64_t)(cap - 1), slot, cnt_extra, head,
                        (unsigned long long *)status, nchunks, meta);
-    hipLaunchKernelGGL((k_voxel_number<4, 1>), dim3((unsigned)nchunks), dim3(kVsThreads), 0, st, coords, n, ncols, slot,
+    hipLaunchKernelGGL((k_voxel_number<4, 1, FlatReader>), dim3((unsigned)nchunks), dim3(kVsThreads), 0, st, coords, n,
+                       flat_reader(ncols), slot,
                        grid, site_coords, first_pt, point_site, cnt_extra, head, nxt, (unsigned long long *)status,
                        meta, (const unsigned long long *)words, imask);
   } else {
@@ -793,7 +824,8 @@ extern "C" int aabr_input_layer_sites_packed(const int64_t *coords, int64_t n, i
 #undef AABR_BIN
     hipLaunchKernelGGL(k_voxel_bin_build, dim3((unsigned)nbins), dim3(256), 0, st, (unsigned long long *)words,
                        (const int32_t *)cursor, (int)kGridBlock, sp, grid, slot, nxt, meta);
-    hipLaunchKernelGGL((k_voxel_number<4, 2>), dim3((unsigned)nchunks), dim3(kVsThreads), 0, st, coords, n, ncols, slot,
+    hipLaunchKernelGGL((k_voxel_number<4, 2, FlatReader>), dim3((unsigned)nchunks), dim3(kVsThreads), 0, st, coords, n,
+                       flat_reader(ncols), slot,
                        grid, site_coords, first_pt, point_site, cnt_extra, head, nxt, (unsigned long long *)status,
                        meta, (const unsigned long long *)words, imask);
   }

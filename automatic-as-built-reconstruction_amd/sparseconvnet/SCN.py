@@ -332,6 +332,13 @@ scatter_stats = {"variant0": 0, "variant1": 0, "variant2": 0, "redone": 0, "bric
 # (Metadata_3._brickify_input, the first round-5 form) -- kept for the A/B and as a second implementation to test against
 brick_scatter = _os.environ.get("AABR_BRICK_SCATTER", "1") != "0"
 
+# BLInputLayer mode -> mode of the voxel-scatter kernels.  The BL rule book is NOT the flat one's twin: inputLayerRules keeps
+# a site's FIRST point in mode 1 and its LAST in mode 2 (.front() / .back(), IOLayersRules.h:100-111; the kernels follow
+# that), blRules overwrites in mode 1 (the LAST point wins) and keeps the FIRST in mode 2.  Mode 0 ("unique and all
+# present") runs the summing path and is checked (V == B * L).
+BL_KERNEL_MODE = {0: 3, 1: 2, 2: 1, 3: 3, 4: 4}
+
+
 def derived_cap(E):
     """slots of a derived (strided-level) grid that receives at most E keys: 1.5 E rounded up to a power of two --
     worst-case load 2/3, typical 0.15-0.35 (a level keeps a half to a sixth of the sites it is derived from).  Round 3
@@ -644,25 +651,53 @@ class Metadata_3(object):
     # ---- builders ---------------------------------------------------------------------------
     def inputLayer(self, spatial_size, coords, batch_size, mode, device):
         """Metadata::inputLayer (Metadata.cpp:405-417)"""
+        return self._input_layer(spatial_size, coords, mode, device, False)
+
+    def blLayer(self, spatial_size, coords, mode, device=None):
+        """Metadata::blLayer (Metadata.cpp:419-428 -> blRules, IOLayersRules.h:127-297): the input layer of a padded batch,
+        coords int64 [B, L, 3] read where they lie (csrc/point_reader.h BLReader); `mode` is the BL mode 0..4 (BL_KERNEL_MODE
+        maps it to the kernels' mode).  Returns V; the object then holds exactly B samples."""
+        if device is None:
+            device = coords.device if coords.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        V = self._input_layer(spatial_size, coords, BL_KERNEL_MODE[int(mode)], device, True)
+        self.input["bl_mode"] = int(mode)       # what blLayerRuleBook reports (input["mode"] is the kernels' mode)
+        return V
+
+    def _input_layer(self, spatial_size, coords, mode, device, bl):
         if self.input is not None:
             src = self.input.get("coords_src")
-            if src is not None and src[0] is coords and src[1] == coords._version and self.input["mode"] == int(mode):
-                return self.inputLayerFinish()  # prepared ahead of time (InputLayer.prepare)
-        self.inputLayerEnqueue(spatial_size, coords, mode, device, asynchronous=False)
+            if src is not None and src[0] is coords and src[1] == coords._version and self.input["mode"] == int(mode) \
+                    and (self.input.get("bl") is not None) == bl:
+                return self.inputLayerFinish()  # prepared ahead of time (InputLayer.prepare / BLInputLayer.prepare)
+        self.inputLayerEnqueue(spatial_size, coords, mode, device, asynchronous=False, bl=bl)
         return self.inputLayerFinish()
 
-    def inputLayerEnqueue(self, spatial_size, coords, mode, device, asynchronous=True):
+    def inputLayerEnqueue(self, spatial_size, coords, mode, device, asynchronous=True, bl=False):
         """enqueue the site-numbering kernels (+ an asynchronous read-back of (V, maxActive, err)
-        when `asynchronous`); all integer state of the input layer lives in ONE device allocation"""
-        assert coords.dim() == 2 and coords.size(1) in (3, 4)
+        when `asynchronous`); all integer state of the input layer lives in ONE device allocation.
+        `bl`: coords is the padded batch [B, L, 3] of a BLInputLayer instead of the flat [n, 3 or 4] list: the same
+        kernels read it in place through the BL reader (point i = flat row b * L + l, batch index i / L, x < 0 = empty);
+        `mode` is the KERNELS' mode either way."""
+        if bl:
+            assert coords.dim() == 3 and coords.size(2) == 3
+        else:
+            assert coords.dim() == 2 and coords.size(1) in (3, 4)
         assert self.input is None and len(self.grids) == 0, "Metadata already holds an input layer"
         coords_src = (coords, coords._version)   # identity + version of the caller's tensor (kept alive here)
         lib = _hip.load()
         self.device = device
         coords = coords.to(device=device, dtype=torch.int64, non_blocking=True).contiguous()
-        n, ncols = coords.shape
+        if bl:
+            B, L = int(coords.shape[0]), int(coords.shape[1])
+            n, ncols, shape = B * L, 3, (B, L)
+            self._batch_size_cache = B          # B samples, empty ones included (the flat form derives it from the sites)
+            sites = lambda *a: lib.aabr_bl_input_layer_sites(ptr(coords), B, L, *a)
+        else:
+            n, ncols = coords.shape
+            shape = None
+            sites = lambda *a: lib.aabr_input_layer_sites(ptr(coords), n, ncols, *a)
         if self.site_order == "brick" and brick_scatter and n > 0:
-            return self._enqueue_brick_scatter(spatial_size, coords, coords_src, mode, device, asynchronous)
+            return self._enqueue_brick_scatter(spatial_size, coords, coords_src, mode, device, asynchronous, shape)
         cap = _hip.next_pow2(2 * n)
         n1 = max(n, 1)
         nst = int(lib.aabr_input_layer_status_words(n))
@@ -671,7 +706,7 @@ class Metadata_3(object):
         # widths from the layer's spatial size and n -- and are only worth their extra launch from a few 10^4 points on;
         # a point that does not fit is reported through meta[5] and the generic form runs instead (inputLayerFinish).
         sp3 = _hip.i32x3(_key(spatial_size))
-        variant = scatter_variant
+        variant = 0 if bl else scatter_variant      # (the packed / LDS-binned inserts read the flat list only)
         if variant and (n < SCATTER_MIN_POINTS or lib.aabr_input_layer_pack_bits(n, sp3) < 2):
             variant = 0
         if variant == 2 and not (4096 <= cap <= (1 << 24)):
@@ -703,9 +738,8 @@ class Metadata_3(object):
                                                         P("first_pt"), P("cnt_extra"), P("head"), P("nxt"), P("status"),
                                                         P("meta"), stream()))
             else:
-                check(lib.aabr_input_layer_sites(ptr(coords), n, ncols, P("keys"), cap, P("slot"),
-                                                 P("point_site"), P("site_coords"), P("first_pt"), P("cnt_extra"),
-                                                 P("head"), P("nxt"), P("status"), P("meta"), stream()))
+                check(sites(P("keys"), cap, P("slot"), P("point_site"), P("site_coords"), P("first_pt"), P("cnt_extra"),
+                            P("head"), P("nxt"), P("status"), P("meta"), stream()))
             if asynchronous:
                 # pinned read-back buffer + event from a small recycling pool (allocating pinned memory
                 # per scene costs more than the whole enqueue)
@@ -718,20 +752,25 @@ class Metadata_3(object):
             meta.zero_()
         self._pending = dict(host=host, event=ev, meta=meta, site_coords=site_coords, keys=keys, vals=vals,
                              cap=cap, coords=coords, buf=buf, variant=variant,
-                             redo=(lambda: check(lib.aabr_input_layer_sites(
-                                 ptr(coords), n, ncols, P("keys"), cap, P("slot"), P("point_site"), P("site_coords"),
+                             redo=(lambda: check(sites(
+                                 P("keys"), cap, P("slot"), P("point_site"), P("site_coords"),
                                  P("first_pt"), P("cnt_extra"), P("head"), P("nxt"), P("status"), P("meta"), stream()))))
         scatter_stats["variant%d" % variant] += 1
         self.input = dict(point_site=piece["point_site"], first_pt=piece["first_pt"], cnt_extra=piece["cnt_extra"],
                           head=piece["head"], nxt=piece["nxt"], last_pt=piece["last_pt"], meta=meta, n=n, V=None,
-                          mode=int(mode), spatial=_key(spatial_size), coords_src=coords_src)
+                          mode=int(mode), spatial=_key(spatial_size), coords_src=coords_src, bl=shape)
 
-    def _enqueue_brick_scatter(self, spatial_size, coords, coords_src, mode, device, asynchronous):
+    def _enqueue_brick_scatter(self, spatial_size, coords, coords_src, mode, device, asynchronous, bl=None):
         """brick-major rows WITHOUT a hash table (csrc/brick.hip "voxel scatter straight into a brick grid"): the points are
         converted and their extent reduced now (one kernel + the asynchronous read of the extent); `inputLayerFinish` sizes
         the directory by it, builds the input level from the points and hands every point its row"""
         lib = _hip.load()
-        n, ncols = coords.shape
+        if bl is not None:                      # the padded batch [B, L, 3] of a BLInputLayer, converted where it lies
+            n = bl[0] * bl[1]
+            prepare = lambda *a: lib.aabr_bl_points_prepare(ptr(coords), bl[0], bl[1], *a)
+        else:
+            n, ncols = coords.shape
+            prepare = lambda *a: lib.aabr_points_prepare(ptr(coords), n, ncols, *a)
         names = [("pc", 4 * n), ("meta", _hip.META_WORDS), ("point_site", n), ("nxt", n), ("first_pt", n), ("head", n),
                  ("cnt_extra", n), ("last_pt", n)]
         offs, tot = {}, 0
@@ -742,8 +781,8 @@ class Metadata_3(object):
         piece = {name: buf[offs[name]:offs[name] + sz] for name, sz in names}
         meta = piece["meta"]
         # (the per-site arrays' starting values ride in this pass: aabr_points_sites(flags = 1) then fills nothing)
-        check(lib.aabr_points_prepare(ptr(coords), n, ncols, piece["pc"].data_ptr(), meta.data_ptr(),
-                                      ptr(piece["first_pt"]), ptr(piece["cnt_extra"]), ptr(piece["head"]), stream()))
+        check(prepare(piece["pc"].data_ptr(), meta.data_ptr(), ptr(piece["first_pt"]), ptr(piece["cnt_extra"]),
+                      ptr(piece["head"]), stream()))
         host = ev = None
         if asynchronous:
             host, ev = _pinned_pool.pop() if _pinned_pool else (
@@ -751,11 +790,11 @@ class Metadata_3(object):
             host.copy_(meta, non_blocking=True)
             ev.record()
         self._pending = dict(kind="brick", host=host, event=ev, meta=meta, coords=coords, buf=buf, piece=piece,
-                             spatial_t=spatial_size, mode=mode, device=device)
+                             spatial_t=spatial_size, mode=mode, device=device, bl=bl)
         scatter_stats["brick"] = scatter_stats.get("brick", 0) + 1
         self.input = dict(point_site=piece["point_site"], first_pt=piece["first_pt"], cnt_extra=piece["cnt_extra"],
                           head=piece["head"], nxt=piece["nxt"], last_pt=piece["last_pt"], meta=meta, n=n, V=None,
-                          mode=int(mode), spatial=_key(spatial_size), coords_src=coords_src)
+                          mode=int(mode), spatial=_key(spatial_size), coords_src=coords_src, bl=bl)
 
     def _brick_scatter_launch(self, piece, n, key, extent, dev):
         """the launches of the brick-native scatter behind the extent read: input level from the points, then every point's
@@ -796,6 +835,8 @@ class Metadata_3(object):
         key, n, dev, piece = il["spatial"], il["n"], pend["device"], pend["piece"]
         if m[2] == 0:
             raise _hip.AabrError("InputLayer: coordinates must lie in [0, 65534] (batch index too)")
+        if il.get("bl") is not None and m[8] >= 0:
+            m[11] = il.get("bl")[0] - 1                    # B samples, trailing empty ones included (flat form: the largest seen)
         if m[8] < 0:                                   # no valid point
             self.grids[key] = _Grid(torch.empty((0, 4), dtype=torch.int32, device=dev), None, None, 0, 0)
             il["V"] = 0
@@ -807,7 +848,8 @@ class Metadata_3(object):
             brick_stats["declined"] += 1
             src = il["coords_src"]
             self.input = None
-            self.inputLayerEnqueue(pend["spatial_t"], pend["coords"], pend["mode"], dev, asynchronous=False)
+            self.inputLayerEnqueue(pend["spatial_t"], pend["coords"], pend["mode"], dev, asynchronous=False,
+                                   bl=pend.get("bl") is not None)
             self.input["coords_src"] = src
             return self.inputLayerFinish()
         brick_stats["built"] += 1
@@ -846,6 +888,8 @@ class Metadata_3(object):
                 raise _hip.AabrError("InputLayer: coordinates must lie in [0, 65534] (batch index too)")
             V = m[0]
             key = self.input["spatial"]
+            if self.input.get("bl") is not None and V > 0:
+                m[11] = self.input.get("bl")[0] - 1        # B samples, trailing empty ones included
             if self.site_order == "brick" and V > 0 and _brick_dir_words(m[8:12]) > BRICK_MAX_DIR_WORDS:
                 # a few sites spread over a huge extent: the dense directory would not pay -- hash grids for this scene
                 self.site_order = "first_seen"
@@ -1272,6 +1316,16 @@ class Metadata_3(object):
                                                       ptr(rules), stream()))
         return [il["mode"], w - 1, il["n"], il["V"]], rules
 
+    def blLayerRuleBook(self):
+        """[[mode, maxActive, B, L, V], rules int32 [V, 1 + maxActive]] (blRules, IOLayersRules.h:127-297): a row holds a
+        count, then the flat point indices b * L + l it lists in ascending order (modes 1 / 2: the one point kept);
+        entries past the count are unspecified.  `mode` is the BL mode the layer was built with."""
+        il = self.input
+        if il is None or il.get("bl") is None:
+            raise _hip.AabrError("blLayerRuleBook: this Metadata was not built by a BLInputLayer (inputLayerRuleBook?)")
+        head, rules = self.inputLayerRuleBook()
+        return [il["bl_mode"], head[1], il["bl"][0], il["bl"][1], il["V"]], rules
+
     @staticmethod
     def tableToRuleBook(table):
         """gather table [vol, V] -> list over offsets of int32 [n_k, 2] (entry, row) pairs"""
@@ -1351,6 +1405,8 @@ def InputLayer_updateGradInput(metadata, d_input_features, d_output_features):
 def OutputLayer_updateOutput(metadata, input_features, output_features):
     inp = _f32c(input_features, "input_features")
     il = metadata.input
+    if il is not None and il.get("bl") is not None:
+        _bl_input(metadata, "OutputLayer_updateOutput", want_bl=False)
     planes = inp.size(1)
     mode = 3 if il["mode"] == 4 else il["mode"]
     output_features.resize_(il["n"], planes)
@@ -1363,6 +1419,95 @@ def OutputLayer_updateGradInput(metadata, d_input_features, d_output_features):
     d_out = _f32c(d_output_features, "d_output_features")
     il = metadata.input
     planes = d_out.size(1)
+    mode = 3 if il["mode"] == 4 else il["mode"]
+    d_input_features.resize_(il["V"], planes)
+    check(_hip.load().aabr_input_layer_forward(ptr(d_out), ptr(d_input_features), il["V"], planes, ptr(il["first_pt"]),
+                                               ptr(il["cnt_extra"]), ptr(il["head"]), ptr(il["nxt"]), None, mode,
+                                               ptr(il["meta"]), stream()))
+
+
+# ------------------------------------------------------------------------------------------------
+# BLInputLayer / BLOutputLayer (pybind.cpp:171-187; SCN/CPU/IOLayers.cpp:138-230; blRules,
+# IOLayersRules.h:127-297).  The site numbering reads the [B, L, 3] coordinates in place (csrc/point_reader.h BLReader);
+# the feature passes are the flat kernels over the [B L, C] VIEW of the features -- nothing is flattened or compacted.
+# ------------------------------------------------------------------------------------------------
+def _bl_check(coords, input_features, mode):
+    """argument refusals of BLInputLayer_updateOutput, before any launch (and before the device is asked for)"""
+    if int(mode) not in BL_KERNEL_MODE:
+        raise ValueError("BLInputLayer mode must be 0..4, got %r" % (mode,))
+    if coords.dtype.is_floating_point or coords.dtype.is_complex or coords.dtype == torch.bool:
+        raise TypeError("BLInputLayer coordinates must be an integer tensor, got %s" % coords.dtype)
+    if coords.dim() != 3 or coords.size(2) != 3:
+        raise ValueError("BLInputLayer coordinates must be [B, L, 3], got %s" % (tuple(coords.shape),))
+    if input_features.dtype != torch.float32:
+        raise TypeError("BLInputLayer features must be float32 (the reference path is fp32-only), got %s"
+                        % input_features.dtype)
+    if input_features.dim() != 3 or tuple(input_features.shape[:2]) != tuple(coords.shape[:2]):
+        raise ValueError("BLInputLayer features must be [B, L, C] with the coordinates' B, L = %s, got %s"
+                         % (tuple(coords.shape[:2]), tuple(input_features.shape)))
+
+
+def _bl_input(metadata, what, want_bl=True):
+    """the input-layer state of `metadata`, refusing the other form's (the reference keeps two separate rule books and
+    would read an empty one)"""
+    il = metadata.input
+    if il is None:
+        raise _hip.AabrError("%s: the Metadata holds no input layer" % what)
+    if (il.get("bl") is not None) != want_bl:
+        raise _hip.AabrError("%s: the Metadata was built by %s -- the two forms keep different rule books; use %s"
+                             % (what, "an InputLayer" if want_bl else "a BLInputLayer",
+                                "OutputLayer" if want_bl else "BLOutputLayer"))
+    return il
+
+
+def _bl_rows_out(il, dst, src, planes, mode):
+    """dst [B, L, planes] <- the site row of every point the rule book lists, zero elsewhere: ONE launch that writes every
+    element (k_voxel_backward); a layer without sites has nothing to launch over and is zeroed"""
+    dst.resize_(il["bl"][0], il["bl"][1], planes)
+    if il["V"] == 0:
+        dst.zero_()
+        return
+    check(_hip.load().aabr_input_layer_backward(ptr(dst), ptr(src), il["n"], planes, ptr(il["point_site"]),
+                                                ptr(il["first_pt"]), ptr(il["last_pt"]), ptr(il["cnt_extra"]), mode,
+                                                stream()))
+
+
+def BLInputLayer_updateOutput(metadata, spatial_size, coords, input_features, output_features, mode):
+    _bl_check(coords, input_features, mode)
+    inp = _f32c(input_features, "input_features")
+    mode = int(mode)
+    B, L, planes = inp.shape
+    V = metadata.blLayer(spatial_size, coords, mode, inp.device)
+    il = metadata.input
+    if mode == 0 and V != B * L:
+        raise _hip.AabrError("BLInputLayer mode 0 requires every row present and unique (%d sites from %d x %d rows)"
+                             % (V, B, L))
+    output_features.resize_(V, planes)
+    check(_hip.load().aabr_input_layer_forward(ptr(inp), ptr(output_features), V, planes, ptr(il["first_pt"]),
+                                               ptr(il["cnt_extra"]), ptr(il["head"]), ptr(il["nxt"]),
+                                               ptr(il["last_pt"]), il["mode"], ptr(il["meta"]), stream()))
+    il["forward_done"] = True
+
+
+def BLInputLayer_updateGradInput(metadata, d_input_features, d_output_features):
+    d_out = _f32c(d_output_features, "d_output_features")
+    il = _bl_input(metadata, "BLInputLayer_updateGradInput")
+    _bl_rows_out(il, d_input_features, d_out, d_out.size(1), il["mode"])
+
+
+# BLOutputLayer (cpu_BLOutputLayer_updateOutput / _updateGradInput): the BL rule book run backwards without averaging -- every
+# point it lists receives its site's row, every other row of [B, L, C] (empty rows included) is written as zero by the same
+# kernel; its gradient is the un-averaged forward pass.
+def BLOutputLayer_updateOutput(metadata, input_features, output_features):
+    inp = _f32c(input_features, "input_features")
+    il = _bl_input(metadata, "BLOutputLayer_updateOutput")
+    _bl_rows_out(il, output_features, inp, inp.size(1), 3 if il["mode"] == 4 else il["mode"])
+
+
+def BLOutputLayer_updateGradInput(metadata, d_input_features, d_output_features):
+    d_out = _f32c(d_output_features, "d_output_features")
+    il = _bl_input(metadata, "BLOutputLayer_updateGradInput")
+    planes = d_out.size(2)
     mode = 3 if il["mode"] == 4 else il["mode"]
     d_input_features.resize_(il["V"], planes)
     check(_hip.load().aabr_input_layer_forward(ptr(d_out), ptr(d_input_features), il["V"], planes, ptr(il["first_pt"]),

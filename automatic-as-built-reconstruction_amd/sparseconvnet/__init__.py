@@ -12,7 +12,8 @@ from .convolution import Convolution  # noqa: E402
 from .deconvolution import Deconvolution  # noqa: E402
 from .fullConvolution import FullConvolution, TransposeConvolution  # noqa: E402
 from .identity import Identity  # noqa: E402
-from .ioLayers import InputLayer, OutputLayer  # noqa: E402
+from .ioLayers import InputLayer, OutputLayer, BLInputLayer, BLOutputLayer, BLInputLayerFunction, \
+    BLOutputLayerFunction  # noqa: E402
 from .maxPooling import MaxPooling  # noqa: E402
 from .metadata import Metadata  # noqa: E402
 from .networkInNetwork import NetworkInNetwork  # noqa: E402

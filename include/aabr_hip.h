@@ -47,7 +47,9 @@ const char *aabr_last_error(void);
  * aabr_roi_targets_coder, aabr_roi_post_detections_coder) likewise: six new symbols, the older entry points being the
  * centroid case of the same code; and fc6 over windows of the convolution rows (aabr_roi_mlp_*_window, AabrMlpWindow):
  * three new symbols and one new record.  The RPN with separated-classifier groups (aabr_rpn_head_grouped_*,
- * aabr_rpn_loss_grouped_*): six new symbols; the plain entry points run the same kernels and give the same bits. */
+ * aabr_rpn_loss_grouped_*): six new symbols; the plain entry points run the same kernels and give the same bits.  The batched
+ * input layer (aabr_bl_input_layer_sites, aabr_bl_points_prepare, aabr_quantize_scenes_bl): three new symbols; the flat
+ * entry points run the same kernel bodies through the flat reader and give the same bits. */
 #define AABR_ABI_VERSION 640
 int aabr_version(void);
 /* Tuning knobs for experiments and tests (no counterpart in the reference; the defaults are what ships): CONV_WIDE,
@@ -82,6 +84,21 @@ int aabr_build_flags(void);
 int aabr_quantize_points(const void *xyz, int is_double, int64_t n, double scale, const void *xyz_min,
                          const int32_t *full_scale_dev, int64_t batch_index, int64_t *locs,
                          float *feats_xyz, int feat_stride, void *stream);
+/* The same quantisation for a PADDED batch -- the [B, L, 3] / [B, L, C] pair BLInputLayer consumes (ioLayers.py:92-136) --
+ * for all scenes at once; replaces the per-scene host loop of the dataset + trainMerge collate (suncg_dataset.py:126-188,
+ * data3d/data.py:25-37) and, on this side, one minimum, one aabr_quantize_points launch and one feature copy per scene.
+ *   xyz_host / extra_host  HOST arrays of `scenes` device pointers: [n_b, 3] float32 or float64 (is_double, one type for
+ *                          the batch) and [n_b, extra_planes] float32 (extra_host may be NULL when extra_planes == 0)
+ *   n_host                 host int64 [scenes], every n_b <= L
+ *   coords int64 [scenes, L, 3], feats float32 [scenes, L, 3 + extra_planes]: every element is written --
+ *     row l < n_b: the scene's quantised point ((-1,-1,-1) outside full_scale; features a / scale, then the extra row);
+ *     rows n_b .. L-1: -1 coordinates, zero features.
+ *   min_keys  uint64 [3 * scenes] device scratch (the per-scene minimum, as order-preserving keys).
+ * The pointers and sizes of up to 32 scenes travel by value in the kernel arguments: one fill + two launches (minimum,
+ * quantise + feature copy) for scenes <= 32, two more launches per further 32.  No host read.  Inputs are finite.      */
+int aabr_quantize_scenes_bl(const void *const *xyz_host, const void *const *extra_host, const int64_t *n_host,
+                            int scenes, int is_double, int extra_planes, double scale, const int32_t *full_scale_host,
+                            int64_t L, int64_t *coords, float *feats, uint64_t *min_keys, void *stream);
 
 /* ---- hash grid ---------------------------------------------------------------------------
  * A grid is an open-addressing table of cap 16-byte entries {uint64 key (packed b,x,y,z), uint32 first, int32 val
@@ -133,6 +150,21 @@ int aabr_input_layer_sites_packed(const int64_t *coords, int64_t n, int ncols, c
                                   int32_t *slot, int32_t *point_site, int32_t *site_coords, int32_t *first_pt,
                                   int32_t *cnt_extra, int32_t *head, int32_t *nxt, int32_t *status, int32_t *meta,
                                   void *stream);
+/* aabr_input_layer_sites for the BATCHED layout -- replaces Metadata<3>::blLayer -> blRules (SCN/Metadata/Metadata.cpp:419-428,
+ * IOLayersRules.h:127-297; pybind.cpp:171-175 BLInputLayer_updateOutput, SCN/CPU/IOLayers.cpp:138-230).  coords is int64
+ * [B, L, 3], read where it lies: point i is the flat row i = b * L + l and its batch index is i / L -- no [B L, 4] copy.
+ *   A row is EMPTY if and only if x < 0, whatever y and z hold (`if (p[0] >= 0)`, IOLayersRules.h:188,203,256): it is
+ *   skipped silently, point_site = -1.  (The flat form's sentinel is x == y == z == -1.)
+ *   A row with x >= 0 and a negative y or z, or any coordinate above 65534, sets the error word meta[2].
+ *   Sites are numbered by first appearance in ascending flat row: sample-major (all sites of sample 0, then sample 1, ...),
+ *   first-seen inside a sample -- blRules' `SGs[I].ctr` + `nAct++`; the same coordinate in two samples is two sites.
+ * Same kernels (the generic hash form), same launches, same outputs and buffer sizes as aabr_input_layer_sites with
+ * n = B * L; the packed and LDS-binned inserts are not offered for this layout.  0 <= B <= 65535, B * L < 2^31;
+ * B * L == 0 launches nothing.                                                                                          */
+int aabr_bl_input_layer_sites(const int64_t *coords, int64_t B, int64_t L, uint64_t *keys, int64_t cap,
+                              int32_t *slot, int32_t *point_site, int32_t *site_coords, int32_t *first_pt,
+                              int32_t *cnt_extra, int32_t *head, int32_t *nxt, int32_t *status, int32_t *meta,
+                              void *stream);
 
 /* Voxel scatter, feature half -- replaces InputLayer_ForwardPass / InputLayer_fp_
  * (SCN/CPU/IOLayers.cpp:11-29, SCN/CUDA/IOLayers.cu:14-41).  mode: 1 keep-first-listed,
@@ -230,6 +262,12 @@ int aabr_points_prepare(const int64_t *coords, int64_t n, int ncols, int32_t *pc
 int aabr_points_sites(const int32_t *pc, int64_t n, const int32_t *dims_host, const void *dir, const void *bricks,
                       int32_t *point_site, int32_t *first_pt, int32_t *cnt_extra, int32_t *head, int32_t *nxt,
                       int32_t *meta, int flags, void *stream);
+/* aabr_points_prepare for the batched layout (blRules, IOLayersRules.h:127-297; see aabr_bl_input_layer_sites for the
+ * empty-row and error rules): coords int64 [B, L, 3] read in place -> pc int32 [B L, 4] with pc[i].w = i / L.  The same
+ * kernel body; aabr_brick_build / aabr_points_sites follow as for the flat list.  meta[11] is the largest NON-EMPTY
+ * sample; the caller that wants B samples (trailing empty ones included) sizes the directory by B itself.          */
+int aabr_bl_points_prepare(const int64_t *coords, int64_t B, int64_t L, int32_t *pc, int32_t *meta, int32_t *first_pt,
+                           int32_t *cnt_extra, int32_t *head, void *stream);
 /* aabr_submanifold_table / aabr_convolution_tables2 over brick levels: same tables, same block counts
  * (Metadata.cpp:429-443,484-510; SubmanifoldConvolutionRules.h:26-45; ConvolutionRules.h:11-34).                       */
 int aabr_brick_submanifold_table(const int32_t *site_coords, int64_t V, const int32_t *dims_host, const void *dir,
