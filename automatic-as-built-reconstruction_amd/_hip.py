@@ -196,6 +196,10 @@ _SIGS = {
                                                            _i32, _i32, _i32, _i32, _vp, _vp]),
     "aabr_roi_align_rotated_3d_sparse_backward": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _f32,
                                                             _i32, _i32, _i32, _i32, _i64, _vp, _vp]),
+    "aabr_roi_align_rotated_3d_sparse_forward_bf16": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _f32,
+                                                                _i32, _i32, _i32, _i32, _vp, _vp]),
+    "aabr_roi_align_rotated_3d_sparse_backward_bf16": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _f32,
+                                                                 _i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp]),
     "aabr_rpn_decode": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _f32, _f32p, _f32p, _f32, _vp, _vp]),
     "aabr_rpn_decode_maps": (C.c_int, [_i32, _vp, _vp, _vp, _i32p, _i32p, _f32p, _vp, _i32, _f32, _f32p, _f32, _f32,
                                        _f32, _vp, _i64, _vp, _vp, _vp, _vp]),
@@ -270,6 +274,9 @@ _SIGS = {
     "aabr_roi_pool_forward": (C.c_int, [_lvp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "aabr_roi_pool_backward": (C.c_int, [_lvp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i64,
                                          _vp]),
+    "aabr_roi_pool_forward_bf16": (C.c_int, [_lvp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "aabr_roi_pool_backward_bf16": (C.c_int, [_lvp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp,
+                                              _vp, _i64, _vp]),
     "aabr_roi_mlp_tile": (C.c_int, [_i64, _i64]),
     "aabr_roi_mlp_dw_splits": (C.c_int, [_i64, _i64, _i64]),
     "aabr_roi_mlp_dw_scratch_floats": (C.c_int64, [_i64, _i64, _i64]),
@@ -289,6 +296,10 @@ _SIGS = {
     "aabr_rpn_head_grouped_scratch_floats": (C.c_int64, [_i64, _i32, _i32, _i32]),
     "aabr_rpn_head_grouped_forward": (C.c_int, [_rmp, _i32, _i32, _i32, _i32] + [_vp] * 8),
     "aabr_rpn_head_grouped_backward": (C.c_int, [_rmp, _i32, _i32, _i32, _i32] + [_vp] * 12),
+    "aabr_rpn_head_forward_bf16": (C.c_int, [_rmp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aabr_rpn_head_backward_bf16": (C.c_int, [_rmp, _i32, _i32, _i32] + [_vp] * 12),
+    "aabr_rpn_head_grouped_forward_bf16": (C.c_int, [_rmp, _i32, _i32, _i32, _i32] + [_vp] * 8),
+    "aabr_rpn_head_grouped_backward_bf16": (C.c_int, [_rmp, _i32, _i32, _i32, _i32] + [_vp] * 12),
     "aabr_sgd_chunk_elems": (C.c_int, []),
     "aabr_sgd_chunk_table": (C.c_int64, [_i64p, _i64p, _i32p, _i64, _i64, _i64p, _i64]),
     "aabr_sgd_momentum_step": (C.c_int, [_vp, _vp, _i64, _vp, _i64p, _i64, _i64, _vp, _vp, _i32, _f32p, _f32p, _i32, _f32,

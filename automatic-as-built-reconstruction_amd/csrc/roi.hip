@@ -256,8 +256,10 @@ __global__ __launch_bounds__(256) void k_roi_cellmap(const int32_t *__restrict__
   if (c.x < X && c.y < Y && c.z < Z && c.w < B) cellmap[(((int64_t)c.w * X + c.x) * Y + c.y) * Z + c.z] = (int32_t)v;
 }
 
-template <bool BACKWARD>
-__global__ __launch_bounds__(256) void k_roi_align_rot3d_sparse(const float *__restrict__ feats, int C,
+// FT: the storage of `feats` (float, __bf16): the forward's corner loads widen (exact), nothing else knows it; the backward
+// never reads `feats` and has the one float instance
+template <bool BACKWARD, typename FT>
+__global__ __launch_bounds__(256) void k_roi_align_rot3d_sparse(const FT *__restrict__ feats, int C,
                                                                 const int32_t *__restrict__ cellmap, int B,
                                                                 const float *__restrict__ rois, RoiGeom g,
                                                                 float *__restrict__ top,
@@ -317,7 +319,7 @@ __global__ __launch_bounds__(256) void k_roi_align_rot3d_sparse(const float *__r
 #pragma unroll
               for (int t = 0; t < 8; ++t) {
                 const int32_t row = b_ok ? cm[q.o[t]] : -1; // workgroup-uniform address: one broadcast load
-                v[t] = (row >= 0 && c_ok) ? feats[(int64_t)row * C + c] : 0.f;
+                v[t] = (row >= 0 && c_ok) ? (float)feats[(int64_t)row * C + c] : 0.f;
               }
               acc += (q.w[0] * v[0] + q.w[1] * v[1] + q.w[2] * v[2] + q.w[3] * v[3] + q.w[4] * v[4] + q.w[5] * v[5] +
                       q.w[6] * v[6] + q.w[7] * v[7]);
@@ -365,24 +367,47 @@ extern "C" int aabr_roi_cellmap(const int32_t *site_coords, int64_t V, const int
   return AABR_OK;
 }
 
+template <typename FT>
+static int roi_sparse_forward(const char *fn, const FT *feats, int channels, const int32_t *cellmap, int batch_size,
+                              int height, int width, int zsize, const float *rois, int64_t num_rois,
+                              float spatial_scale, int pooled_h, int pooled_w, int pooled_z, int sampling_ratio,
+                              float *output, hipStream_t st) {
+  RoiGeom g;
+  AABR_CHECK_ARG_AS(fn, num_rois >= 0 && batch_size >= 0 &&
+                            roi_geom(g, channels, height, width, zsize, pooled_h, pooled_w, pooled_z, sampling_ratio,
+                                     spatial_scale) == 0,
+                    "bad geometry");
+  if (num_rois == 0) return AABR_OK;
+  AABR_CHECK_ARG_AS(fn, feats && cellmap && rois && output && batch_size > 0, "null pointer / empty batch");
+  AABR_CHECK_ARG_AS(fn, ceil_div(channels, kRoiPlanes) <= 65535, "too many planes");
+  hipLaunchKernelGGL((k_roi_align_rot3d_sparse<false, FT>),
+                     dim3((unsigned)num_rois, (unsigned)ceil_div(channels, kRoiPlanes)), dim3(256),
+                     (size_t)kRoiPlanes * kRoiBins * sizeof(float), st, feats, channels, cellmap, batch_size, rois, g,
+                     output, (const float *)nullptr, (float *)nullptr);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
+}
+
 extern "C" int aabr_roi_align_rotated_3d_sparse_forward(const float *feats, int channels, const int32_t *cellmap,
                                                         int batch_size, int height, int width, int zsize,
                                                         const float *rois, int64_t num_rois, float spatial_scale,
                                                         int pooled_h, int pooled_w, int pooled_z, int sampling_ratio,
                                                         float *output, void *stream_) {
-  RoiGeom g;
-  AABR_CHECK_ARG(num_rois >= 0 && batch_size >= 0 &&
-                     roi_geom(g, channels, height, width, zsize, pooled_h, pooled_w, pooled_z, sampling_ratio,
-                              spatial_scale) == 0,
-                 "bad geometry");
-  if (num_rois == 0) return AABR_OK;
-  AABR_CHECK_ARG(feats && cellmap && rois && output && batch_size > 0, "null pointer / empty batch");
-  AABR_CHECK_ARG(ceil_div(channels, kRoiPlanes) <= 65535, "too many planes");
-  hipLaunchKernelGGL(k_roi_align_rot3d_sparse<false>, dim3((unsigned)num_rois, (unsigned)ceil_div(channels, kRoiPlanes)),
-                     dim3(256), (size_t)kRoiPlanes * kRoiBins * sizeof(float), (hipStream_t)stream_, feats, channels,
-                     cellmap, batch_size, rois, g, output, (const float *)nullptr, (float *)nullptr);
-  AABR_CHECK_LAUNCH();
-  return AABR_OK;
+  return roi_sparse_forward<float>(__func__, feats, channels, cellmap, batch_size, height, width, zsize, rois, num_rois,
+                                   spatial_scale, pooled_h, pooled_w, pooled_z, sampling_ratio, output,
+                                   (hipStream_t)stream_);
+}
+
+extern "C" int aabr_roi_align_rotated_3d_sparse_forward_bf16(const void *feats_bf16, int channels,
+                                                             const int32_t *cellmap, int batch_size, int height,
+                                                             int width, int zsize, const float *rois, int64_t num_rois,
+                                                             float spatial_scale, int pooled_h, int pooled_w,
+                                                             int pooled_z, int sampling_ratio, float *output,
+                                                             void *stream_) {
+  AABR_CHECK_ARG(((uintptr_t)feats_bf16 & 3) == 0, "feats must be 4-byte aligned");
+  return roi_sparse_forward<__bf16>(__func__, (const __bf16 *)feats_bf16, channels, cellmap, batch_size, height, width,
+                                    zsize, rois, num_rois, spatial_scale, pooled_h, pooled_w, pooled_z, sampling_ratio,
+                                    output, (hipStream_t)stream_);
 }
 
 extern "C" int aabr_roi_align_rotated_3d_sparse_backward(const float *grad_output, int channels,
@@ -403,9 +428,27 @@ extern "C" int aabr_roi_align_rotated_3d_sparse_backward(const float *grad_outpu
   if (num_rois == 0 || V == 0) return AABR_OK;
   AABR_CHECK_ARG(grad_output && cellmap && rois && batch_size > 0, "null pointer / empty batch");
   AABR_CHECK_ARG(ceil_div(channels, kRoiPlanes) <= 65535, "too many planes");
-  hipLaunchKernelGGL(k_roi_align_rot3d_sparse<true>, dim3((unsigned)num_rois, (unsigned)ceil_div(channels, kRoiPlanes)),
-                     dim3(256), (size_t)kRoiPlanes * kRoiBins * sizeof(float), st, (const float *)nullptr, channels,
-                     cellmap, batch_size, rois, g, (float *)nullptr, grad_output, d_feats);
+  hipLaunchKernelGGL((k_roi_align_rot3d_sparse<true, float>),
+                     dim3((unsigned)num_rois, (unsigned)ceil_div(channels, kRoiPlanes)), dim3(256),
+                     (size_t)kRoiPlanes * kRoiBins * sizeof(float), st, (const float *)nullptr, channels, cellmap,
+                     batch_size, rois, g, (float *)nullptr, grad_output, d_feats);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
+}
+
+// the fp32 backward into `accum_f32` [V, channels], then ONE rounding into the bf16 rows: 1 memset + 2 launches
+extern "C" int aabr_roi_align_rotated_3d_sparse_backward_bf16(const float *grad_output, int channels,
+                                                              const int32_t *cellmap, int batch_size, int height,
+                                                              int width, int zsize, const float *rois,
+                                                              int64_t num_rois, float spatial_scale, int pooled_h,
+                                                              int pooled_w, int pooled_z, int sampling_ratio, int64_t V,
+                                                              float *accum_f32, void *d_feats_bf16, void *stream_) {
+  AABR_CHECK_ARG(V <= 0 || (accum_f32 && d_feats_bf16), "null accum_f32 / d_feats_bf16");
+  AABR_CHECK_ARG((((uintptr_t)accum_f32 | (uintptr_t)d_feats_bf16) & 3) == 0,
+                 "accum_f32 / d_feats_bf16 must be 4-byte aligned");
+  const int rc = aabr_roi_align_rotated_3d_sparse_backward(grad_output, channels, cellmap, batch_size, height, width, zsize,
+                                                           rois, num_rois, spatial_scale, pooled_h, pooled_w, pooled_z,
+                                                           sampling_ratio, V, accum_f32, stream_);
+  if (rc != AABR_OK || V == 0) return rc;
+  return aabr_cast_storage(accum_f32, d_feats_bf16, V * channels, 1, stream_);
 }

@@ -11,6 +11,11 @@
 // and backward one memset of the levels' gradient rows (ONE allocation, sliced per level by the caller) + k_roi_pool<true>.
 // The walk over bins and samples, the LDS staging and the corner arithmetic (roi_shared.h) are k_roi_align_rot3d_sparse's,
 // statement for statement, so the forward result is bit-identical to running that kernel on each level's ROI subset.
+//
+// Feature storage FT (float, __bf16; aabr_roi_pool_*_bf16): the forward's eight corner loads widen a bf16 value (exact),
+// nothing else knows the storage, and the output stays fp32.  The backward kernel never reads the features: the bf16
+// entry runs the SAME k_roi_pool<true> with its fp32 atomics into a caller-provided fp32 buffer and rounds that once
+// into the bf16 gradient rows (aabr_cast_storage): 1 memset + 2 launches.  Nothing is accumulated in bf16.
 #include "common.h"
 #include "roi_shared.h"
 
@@ -69,7 +74,7 @@ __global__ __launch_bounds__(256) void k_roi_pool_prepare(const float *__restric
 }
 
 struct PoolLevel {
-  const float *feats;        // [V, C]; null: a level without sites
+  const void *feats;         // [V, C] in the storage FT of the forward instance; null: a level without sites
   const int32_t *cellmap;    // [nb, height, width, zsize]
   float *d_feats;            // backward: this level's rows of the shared gradient allocation
   int32_t height, width, zsize, nb;
@@ -81,7 +86,7 @@ struct PoolLevels {
   int n;
 };
 
-template <bool BACKWARD>
+template <bool BACKWARD, typename FT>
 __global__ __launch_bounds__(256) void k_roi_pool(PoolLevels lv, int C, const float *__restrict__ rois,
                                                   const int32_t *__restrict__ levels, int ph_, int pw_, int pz_,
                                                   int sampling, float *__restrict__ top,
@@ -107,7 +112,7 @@ __global__ __launch_bounds__(256) void k_roi_pool(PoolLevels lv, int C, const fl
   RoiGeom g;
   g.channels = C; g.height = L.height; g.width = L.width; g.zsize = L.zsize;
   g.ph = ph_; g.pw = pw_; g.pz = pz_; g.sampling = sampling; g.scale = L.scale;
-  const float *__restrict__ feats = L.feats;
+  const FT *__restrict__ feats = (const FT *)L.feats;
   const int32_t *__restrict__ cellmap = L.cellmap;
   float *d_feats = L.d_feats;
   const int B = L.nb;
@@ -161,7 +166,7 @@ __global__ __launch_bounds__(256) void k_roi_pool(PoolLevels lv, int C, const fl
 #pragma unroll
               for (int t = 0; t < 8; ++t) {
                 const int32_t row = b_ok ? cm[q.o[t]] : -1; // workgroup-uniform address: one broadcast load
-                v[t] = (row >= 0 && c_ok) ? feats[(int64_t)row * C + c] : 0.f;
+                v[t] = (row >= 0 && c_ok) ? (float)feats[(int64_t)row * C + c] : 0.f;
               }
               acc += (q.w[0] * v[0] + q.w[1] * v[1] + q.w[2] * v[2] + q.w[3] * v[3] + q.w[4] * v[4] + q.w[5] * v[5] +
                       q.w[6] * v[6] + q.w[7] * v[7]);
@@ -254,21 +259,39 @@ static int pool_levels(PoolLevels &lv, const AabrRoiLevel *d, int n_levels, int 
   return 0;
 }
 
-extern "C" int aabr_roi_pool_forward(const AabrRoiLevel *levels_desc_host, int n_levels, int channels, int batch_size,
-                                     const float *rois, const int32_t *levels, int64_t num_rois, int pooled_h,
-                                     int pooled_w, int pooled_z, int sampling_ratio, float *output, void *stream_) {
+template <typename FT>
+static int roi_pool_forward(const char *fn, const AabrRoiLevel *levels_desc_host, int n_levels, int channels,
+                            int batch_size, const float *rois, const int32_t *levels, int64_t num_rois, int pooled_h,
+                            int pooled_w, int pooled_z, int sampling_ratio, float *output, hipStream_t st) {
   PoolLevels lv;
   const char *why = "";
   const int rc = pool_levels(lv, levels_desc_host, n_levels, channels, batch_size, num_rois, pooled_h, pooled_w,
                              pooled_z, false, nullptr, 0, &why);
-  AABR_CHECK_ARG(rc == 0, why);
+  AABR_CHECK_ARG_AS(fn, rc == 0, why);
   if (num_rois == 0) return AABR_OK;
-  AABR_CHECK_ARG(rois && levels && output, "null pointer");
-  hipLaunchKernelGGL(k_roi_pool<false>, dim3((unsigned)num_rois, (unsigned)ceil_div(channels, kRoiPlanes)), dim3(256),
-                     (size_t)kRoiPlanes * kRoiBins * sizeof(float), (hipStream_t)stream_, lv, channels, rois, levels,
-                     pooled_h, pooled_w, pooled_z, sampling_ratio, output, (const float *)nullptr);
+  AABR_CHECK_ARG_AS(fn, rois && levels && output, "null pointer");
+  hipLaunchKernelGGL((k_roi_pool<false, FT>), dim3((unsigned)num_rois, (unsigned)ceil_div(channels, kRoiPlanes)),
+                     dim3(256), (size_t)kRoiPlanes * kRoiBins * sizeof(float), st, lv, channels, rois, levels, pooled_h,
+                     pooled_w, pooled_z, sampling_ratio, output, (const float *)nullptr);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
+}
+
+extern "C" int aabr_roi_pool_forward(const AabrRoiLevel *levels_desc_host, int n_levels, int channels, int batch_size,
+                                     const float *rois, const int32_t *levels, int64_t num_rois, int pooled_h,
+                                     int pooled_w, int pooled_z, int sampling_ratio, float *output, void *stream_) {
+  return roi_pool_forward<float>(__func__, levels_desc_host, n_levels, channels, batch_size, rois, levels, num_rois,
+                                 pooled_h, pooled_w, pooled_z, sampling_ratio, output, (hipStream_t)stream_);
+}
+
+extern "C" int aabr_roi_pool_forward_bf16(const AabrRoiLevel *levels_desc_host, int n_levels, int channels,
+                                          int batch_size, const float *rois, const int32_t *levels, int64_t num_rois,
+                                          int pooled_h, int pooled_w, int pooled_z, int sampling_ratio, float *output,
+                                          void *stream_) {
+  for (int l = 0; levels_desc_host && l < n_levels && l < kPoolMaxLevels; ++l)
+    AABR_CHECK_ARG(((uintptr_t)levels_desc_host[l].feats & 3) == 0, "feats must be 4-byte aligned");
+  return roi_pool_forward<__bf16>(__func__, levels_desc_host, n_levels, channels, batch_size, rois, levels, num_rois,
+                                  pooled_h, pooled_w, pooled_z, sampling_ratio, output, (hipStream_t)stream_);
 }
 
 extern "C" int aabr_roi_pool_backward(const AabrRoiLevel *levels_desc_host, int n_levels, int channels, int batch_size,
@@ -285,9 +308,23 @@ extern "C" int aabr_roi_pool_backward(const AabrRoiLevel *levels_desc_host, int 
   if (total_rows > 0) hipMemsetAsync(d_feats_all, 0, (size_t)total_rows * channels * sizeof(float), st);
   if (num_rois == 0 || total_rows == 0) return AABR_OK;
   AABR_CHECK_ARG(rois && levels && grad_output, "null pointer");
-  hipLaunchKernelGGL(k_roi_pool<true>, dim3((unsigned)num_rois, (unsigned)ceil_div(channels, kRoiPlanes)), dim3(256),
-                     (size_t)kRoiPlanes * kRoiBins * sizeof(float), st, lv, channels, rois, levels, pooled_h, pooled_w,
-                     pooled_z, sampling_ratio, (float *)nullptr, grad_output);
+  hipLaunchKernelGGL((k_roi_pool<true, float>), dim3((unsigned)num_rois, (unsigned)ceil_div(channels, kRoiPlanes)),
+                     dim3(256), (size_t)kRoiPlanes * kRoiBins * sizeof(float), st, lv, channels, rois, levels, pooled_h,
+                     pooled_w, pooled_z, sampling_ratio, (float *)nullptr, grad_output);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
+}
+
+extern "C" int aabr_roi_pool_backward_bf16(const AabrRoiLevel *levels_desc_host, int n_levels, int channels,
+                                           int batch_size, const float *rois, const int32_t *levels, int64_t num_rois,
+                                           int pooled_h, int pooled_w, int pooled_z, int sampling_ratio,
+                                           const float *grad_output, float *accum_f32, void *d_feats_all_bf16,
+                                           int64_t total_rows, void *stream_) {
+  AABR_CHECK_ARG(total_rows <= 0 || (accum_f32 && d_feats_all_bf16), "null accum_f32 / d_feats_all_bf16");
+  AABR_CHECK_ARG((((uintptr_t)accum_f32 | (uintptr_t)d_feats_all_bf16) & 3) == 0,
+                 "accum_f32 / d_feats_all_bf16 must be 4-byte aligned");
+  const int rc = aabr_roi_pool_backward(levels_desc_host, n_levels, channels, batch_size, rois, levels, num_rois, pooled_h,
+                                        pooled_w, pooled_z, sampling_ratio, grad_output, accum_f32, total_rows, stream_);
+  if (rc != AABR_OK || total_rows == 0) return rc;
+  return aabr_cast_storage(accum_f32, d_feats_all_bf16, total_rows * channels, 1, stream_);
 }

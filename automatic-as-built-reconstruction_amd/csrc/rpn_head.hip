@@ -1,5 +1,6 @@
 // rpn_head.hip -- the RPN head (SingleConvRPNHead_Sparse3D, modeling/rpn/rpn_sparse3d.py:81-131) over the rows of every
-// feature map in ONE launch, gfx950, fp32 storage only, on v_mfma_f32_32x32x2_f32 (an exact fmaf chain per element):
+// feature map in ONE launch, gfx950, on v_mfma_f32_32x32x2_f32 (an exact fmaf chain per element); the feature rows f and
+// their gradient d_f in fp32 or bf16 storage (template parameter FT, aabr_rpn_head_*_bf16), everything else fp32:
 //   t = relu(f W1^T + b1),  obj = t Wc^T + bc  [V, A],  reg = t Wr^T + br  [V, A, 7] (channel a 7 + j: the reference's
 //   permute + reshape 'box_toghter', the [site, yaw] flatten order the rpn_glue consumers read).
 // W1 [C, C], Wc [A, C], Wr [7 A, C] are the Conv2d weights as [out, in].  C in {32, 64, 96, 128}, 1 <= A <= 4.
@@ -38,6 +39,14 @@
 // table (114.3 KiB at C = 128, A G = 16).  Each workgroup then writes ONE partial [C C + NP C + C + NP] to scratch and
 // k_rpn_head_reduce adds the partials in workgroup order: deterministic, no float atomics.
 //
+// Storage FT of the rows (float, __bf16): the one kernel body per pass is instantiated for both.  bf16 rows are widened
+// (exact) on their way into the SAME fp32 LDS images (sA in rpn_hidden_tile, sX in rpn_load_rows), a lane moving
+// kRpnVec<FT> = 2 of them, 4 bytes, as it moves one float; from there on no statement knows the storage, so objectness,
+// box_regression, `hidden` and the six weight gradients are the fp32 instance's bits on the widened rows.  d_f is the one
+// output in FT: the fp32 value the fp32 instance stores is rounded ONCE ((__bf16)x, nearest even).  The bf16 write-out
+// goes through the then idle f image sX (one more barrier per tile) so that a lane stores two values and a wave 256
+// contiguous bytes; every element is still stored exactly once.  No LDS is added.
+//
 // Launches: forward 1; backward 2 (main, reduce) -- whatever n_maps.  No weight pack is needed.  All maps empty: no
 // launch; backward then zeroes the six weight gradients with memsets.
 #include "common.h"
@@ -54,10 +63,10 @@ constexpr int kRpnMaxN2 = 128;     // with groups: 8 A G <= 128 output columns, 
 constexpr int kRpnLDG = kRpnMaxN2 + 2;
 
 struct RpnMaps {
-  const float *f[kRpnMaxMaps];
+  const void *f[kRpnMaxMaps];      // rows in the storage FT of the instance
   float *obj[kRpnMaxMaps];         // forward: outputs; backward: d_obj (read only, may be NULL)
   float *reg[kRpnMaxMaps];
-  float *df[kRpnMaxMaps];          // backward: d_f
+  void *df[kRpnMaxMaps];           // backward: d_f, in FT
   int64_t rows[kRpnMaxMaps];
   int64_t hoff[kRpnMaxMaps];       // first row of the map in `hidden`
   uint32_t first[kRpnMaxMaps + 1]; // first tile of map m; first[n] = total tiles
@@ -65,6 +74,16 @@ struct RpnMaps {
 };
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+// elements of row storage FT a lane moves at once: always 4 bytes
+template <typename FT> constexpr int kRpnVec = sizeof(float) / sizeof(FT);
+
+__device__ __forceinline__ void rpn_ld(const float *p, float (&x)[1]) { x[0] = *p; }
+__device__ __forceinline__ void rpn_ld(const __bf16 *p, float (&x)[2]) {
+  const bf16x2 v = *reinterpret_cast<const bf16x2 *>(p);
+  x[0] = (float)v[0], x[1] = (float)v[1];
+}
 
 __device__ inline int rpn_map_of(const RpnMaps &g, uint32_t tile) {
   int m = 0;
@@ -118,12 +137,27 @@ __device__ __forceinline__ void rpn_mma_sites(f32x16 &acc, const float *pl, int 
   }
 }
 
-// 64 rows of a [.., C] array from `src` -> sX [64][C + 2], zeros from row `left` on
+// 64 rows of a [.., C] array from `src` (fp32 or bf16, widened) -> sX [64][C + 2], zeros from row `left` on
+template <int C, typename T>
+__device__ __forceinline__ void rpn_load_rows(float *sX, const T *__restrict__ src, int64_t left) {
+  constexpr int V = kRpnVec<T>;
+  for (int i = threadIdx.x * V; i < kRpnT * C; i += 256 * V) {
+    const int row = i / C, c = i - row * C;             // C is even: the V elements lie in one row
+    float x[V] = {};
+    if (row < left) rpn_ld(src + (int64_t)row * C + c, x);
+#pragma unroll
+    for (int v = 0; v < V; ++v) sX[row * (C + 2) + c + v] = x[v];
+  }
+}
+
+// bf16 only: rows [0, left) of sX [64][C + 2] -> dst [.., C], each value rounded once, two per lane
 template <int C>
-__device__ __forceinline__ void rpn_load_rows(float *sX, const float *__restrict__ src, int64_t left) {
-  for (int i = threadIdx.x; i < kRpnT * C; i += 256) {
+__device__ __forceinline__ void rpn_store_rows(__bf16 *__restrict__ dst, const float *sX, int64_t left) {
+  for (int i = threadIdx.x * 2; i < kRpnT * C; i += 512) {
     const int row = i / C, c = i - row * C;
-    sX[row * (C + 2) + c] = row < left ? src[(int64_t)row * C + c] : 0.f;
+    if (row < left)
+      *reinterpret_cast<bf16x2 *>(dst + (int64_t)row * C + c) =
+          (bf16x2){(__bf16)sX[row * (C + 2) + c], (__bf16)sX[row * (C + 2) + c + 1]};
   }
 }
 
@@ -132,24 +166,29 @@ __device__ __forceinline__ void rpn_load_rows(float *sX, const float *__restrict
 
 // the first product of a forward tile: t = relu(f W1^T + b1) for the 64 rows from row0 of map m -> sT [hidden unit][row],
 // and to `hidden` when that is not NULL.  sA [32][64 + 2], sB >= [32][C + 2].  Ends WITHOUT a barrier.
-template <int C>
+template <int C, typename FT>
 __device__ __forceinline__ void rpn_hidden_tile(const RpnMaps &g, int m, int64_t row0, const float *__restrict__ W1,
                                                 const float *__restrict__ b1, float *__restrict__ hidden, float *sA,
                                                 float *sB, float *sT) {
   constexpr int NT = C / 32, LDB = C + 2;
+  constexpr int V = kRpnVec<FT>, FK = 32 / V, FR = 256 / FK;  // f chunk: lanes per 32-column row, rows per pass
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave & 1, wn = wave >> 1;
   const int l31 = lane & 31, kh = 16 * (lane >> 5), tk = t & 31, tr = t >> 5;
+  const int fk = (t & (FK - 1)) * V, fr = t / FK;             // fp32: tk, tr
   const int64_t rows = g.rows[m];
-  const float *__restrict__ f = g.f[m];
+  const FT *__restrict__ f = (const FT *)g.f[m];
 
   f32x16 acc[2];
   rpn_zero(acc);
   for (int k0 = 0; k0 < C; k0 += 32) {
     __syncthreads();                                  // the previous chunk's reads are done
 #pragma unroll
-    for (int i = 0; i < kRpnT / 8; ++i) {
-      const int64_t row = row0 + tr + 8 * i;
-      sA[tk * kRpnLD + tr + 8 * i] = row < rows ? f[row * C + k0 + tk] : 0.f;
+    for (int i = 0; i < kRpnT / FR; ++i) {
+      const int64_t row = row0 + fr + FR * i;
+      float x[V] = {};
+      if (row < rows) rpn_ld(f + row * C + k0 + fk, x);
+#pragma unroll
+      for (int v = 0; v < V; ++v) sA[(fk + v) * kRpnLD + fr + FR * i] = x[v];
     }
 #pragma unroll
     for (int i = 0; i < C / 8; ++i) sB[tk * LDB + tr + 8 * i] = W1[(tr + 8 * i) * C + k0 + tk];
@@ -182,7 +221,7 @@ __device__ __forceinline__ void rpn_hidden_tile(const RpnMaps &g, int m, int64_t
   }
 }
 
-template <int C, bool kGroups>
+template <int C, bool kGroups, typename FT>
 __global__ __launch_bounds__(256) void k_rpn_head_fwd(const RpnMaps g, const float *__restrict__ W1,
                                                       const float *__restrict__ b1, const float *__restrict__ Wc,
                                                       const float *__restrict__ bc, const float *__restrict__ Wr,
@@ -198,7 +237,7 @@ __global__ __launch_bounds__(256) void k_rpn_head_fwd(const RpnMaps g, const flo
   const int m = rpn_map_of(g, blockIdx.x);
   const int64_t rows = g.rows[m], row0 = (int64_t)(blockIdx.x - g.first[m]) * kRpnT;
   const int AG = kGroups ? A * G : A, NT2 = kGroups ? (8 * AG + 31) / 32 : 1;
-  rpn_hidden_tile<C>(g, m, row0, W1, b1, hidden, sA, sB, sT);
+  rpn_hidden_tile<C, FT>(g, m, row0, W1, b1, hidden, sA, sB, sT);
 
   f32x16 acc2[NJ];
   rpn_zero(acc2);
@@ -240,7 +279,7 @@ __global__ __launch_bounds__(256) void k_rpn_head_fwd(const RpnMaps g, const flo
 // padded to MFMA tiles: 32 without groups
 __host__ __device__ constexpr int64_t rpn_partial_floats(int C, int np = kRpnN2) { return (int64_t)C * C + np * C + C + np; }
 
-template <int C, bool kGroups>
+template <int C, bool kGroups, typename FT>
 __global__ __launch_bounds__(256) void k_rpn_head_bwd(const RpnMaps g, const float *__restrict__ W1,
                                                       const float *__restrict__ Wc, const float *__restrict__ Wr, int A,
                                                       int G, const float *__restrict__ hidden, uint32_t total_tiles,
@@ -356,7 +395,7 @@ __global__ __launch_bounds__(256) void k_rpn_head_bwd(const RpnMaps g, const flo
     }
     __syncthreads();                    // dt is complete; every read of the t tile and of sB is done
 
-    rpn_load_rows<C>(sX, g.f[m] + row0 * C, left);
+    rpn_load_rows<C>(sX, (const FT *)g.f[m] + row0 * C, left);
     if (t < C) {
       for (int r_ = 0; r_ < kRpnT; ++r_) dbacc += sDT[r_ * LDC + t];
     }
@@ -390,7 +429,10 @@ __global__ __launch_bounds__(256) void k_rpn_head_bwd(const RpnMaps g, const flo
         }
       }
     }
-    float *__restrict__ df = g.df[m] + row0 * C;
+    // fp32: straight from the accumulators.  bf16: through sX -- every wave is past the chunk loop's first barrier, so
+    // past its dW1 reads of the f image, and the next tile writes sX only after its opening barrier -- then two per lane
+    FT *__restrict__ df = (FT *)g.df[m] + row0 * C;
+    constexpr bool kStage = kRpnVec<FT> > 1;
 #pragma unroll
     for (int jj = 0; jj < 2; ++jj) {
       const int j = wn + 2 * jj;
@@ -398,8 +440,13 @@ __global__ __launch_bounds__(256) void k_rpn_head_bwd(const RpnMaps g, const flo
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int row = wm * 32 + rpn_acc_row(r, lane);
-        if (row < left) df[(int64_t)row * C + j * 32 + l31] = acc[jj][r];
+        if constexpr (kStage) sX[row * LDC + j * 32 + l31] = acc[jj][r];
+        else if (row < left) df[(int64_t)row * C + j * 32 + l31] = acc[jj][r];
       }
+    }
+    if constexpr (kStage) {
+      __syncthreads();
+      rpn_store_rows<C>(df, sX, left);
     }
   }
 
@@ -507,6 +554,9 @@ static int rpn_head_table(const AabrRpnMap *maps, int n_maps, int C, int A, bool
       AABR_CHECK_ARG(q.features, "null features");
       if (backward) AABR_CHECK_ARG(q.d_features, "null d_features");
       else AABR_CHECK_ARG(q.objectness && q.box_regression, "null output");
+      // a lane moves 4 bytes of a row whatever the storage (one float, two bf16)
+      AABR_CHECK_ARG((((uintptr_t)q.features | (uintptr_t)(backward ? q.d_features : nullptr)) & 3) == 0,
+                     "features / d_features must be 4-byte aligned");
     }
     g.f[m] = q.features, g.obj[m] = q.objectness, g.reg[m] = q.box_regression, g.df[m] = q.d_features;
     g.rows[m] = q.rows, g.hoff[m] = hoff;
@@ -521,39 +571,42 @@ static int rpn_head_table(const AabrRpnMap *maps, int n_maps, int C, int A, bool
   return AABR_OK;
 }
 
-// one case per C of a launcher template <int C, bool kGroups>, plain or grouped by the run-time flag
+// one case per C of a launcher template <int C, bool kGroups, typename FT>, plain or grouped by the run-time flag, FT the
+// caller's
 #define AABR_RPN_DISPATCH(rc, launcher, ...)                                                                            \
   switch (C) {                                                                                                          \
-  case 32: rc = grouped ? launcher<32, true>(__VA_ARGS__) : launcher<32, false>(__VA_ARGS__); break;                    \
-  case 64: rc = grouped ? launcher<64, true>(__VA_ARGS__) : launcher<64, false>(__VA_ARGS__); break;                    \
-  case 96: rc = grouped ? launcher<96, true>(__VA_ARGS__) : launcher<96, false>(__VA_ARGS__); break;                    \
-  default: rc = grouped ? launcher<128, true>(__VA_ARGS__) : launcher<128, false>(__VA_ARGS__); break;                  \
+  case 32: rc = grouped ? launcher<32, true, FT>(__VA_ARGS__) : launcher<32, false, FT>(__VA_ARGS__); break;           \
+  case 64: rc = grouped ? launcher<64, true, FT>(__VA_ARGS__) : launcher<64, false, FT>(__VA_ARGS__); break;           \
+  case 96: rc = grouped ? launcher<96, true, FT>(__VA_ARGS__) : launcher<96, false, FT>(__VA_ARGS__); break;           \
+  default: rc = grouped ? launcher<128, true, FT>(__VA_ARGS__) : launcher<128, false, FT>(__VA_ARGS__); break;         \
   }
 
-template <int C, bool kGroups>
+template <int C, bool kGroups, typename FT>
 static int rpn_head_fwd_launch(const RpnMaps &g, const float *W1, const float *b1, const float *Wc, const float *bc,
                                const float *Wr, const float *br, int A, int G, float *hidden, int64_t tiles,
                                hipStream_t st) {
-  hipLaunchKernelGGL((k_rpn_head_fwd<C, kGroups>), dim3((unsigned)tiles), dim3(256), 0, st, g, W1, b1, Wc, bc, Wr, br, A, G,
-                     hidden);
+  hipLaunchKernelGGL((k_rpn_head_fwd<C, kGroups, FT>), dim3((unsigned)tiles), dim3(256), 0, st, g, W1, b1, Wc, bc, Wr, br, A,
+                     G, hidden);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }
 
-template <int C, bool kGroups>
+template <int C, bool kGroups, typename FT>
 static int rpn_head_bwd_launch(const RpnMaps &g, const float *W1, const float *Wc, const float *Wr, int A, int G,
                                const float *hidden, int64_t tiles, int groups, float *scratch, hipStream_t st) {
   static DynLdsOnce attr;               // grouped: once, for the widest D; the launch asks for what its A G needs
   const size_t lds_max = kGroups ? rpn_grouped_bwd_lds_bytes(C, kRpnMaxN2) : rpn_bwd_lds_bytes(C);
   const size_t lds = kGroups ? rpn_grouped_bwd_lds_bytes(C, rpn_np(A, G)) : rpn_bwd_lds_bytes(C);
-  AABR_CHECK_HIP(dyn_lds_once(attr, (const void *)(k_rpn_head_bwd<C, kGroups>), (int)lds_max));
-  hipLaunchKernelGGL((k_rpn_head_bwd<C, kGroups>), dim3((unsigned)groups), dim3(256), lds, st, g, W1, Wc, Wr, A, G, hidden,
-                     (uint32_t)tiles, scratch);
+  AABR_CHECK_HIP(dyn_lds_once(attr, (const void *)(k_rpn_head_bwd<C, kGroups, FT>), (int)lds_max));
+  hipLaunchKernelGGL((k_rpn_head_bwd<C, kGroups, FT>), dim3((unsigned)groups), dim3(256), lds, st, g, W1, Wc, Wr, A, G,
+                     hidden, (uint32_t)tiles, scratch);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }
 
-// the forward of both forms (G = 1, grouped = false: the plain entry); the entries have checked A and G
+// the forward of both forms (G = 1, grouped = false: the plain entry) and both row storages; the entries have checked A
+// and G
+template <typename FT>
 static int rpn_head_forward(const char *fn, const AabrRpnMap *maps_host, int n_maps, int C, int A, int G, bool grouped,
                             const float *W1, const float *b1, const float *Wc, const float *bc, const float *Wr,
                             const float *br, float *hidden, hipStream_t st) {
@@ -567,6 +620,7 @@ static int rpn_head_forward(const char *fn, const AabrRpnMap *maps_host, int n_m
   return rc;
 }
 
+template <typename FT>
 static int rpn_head_backward(const char *fn, const AabrRpnMap *maps_host, int n_maps, int C, int A, int G, bool grouped,
                              const float *W1, const float *Wc, const float *Wr, const float *hidden, float *dW1,
                              float *db1, float *dWc, float *dbc, float *dWr, float *dbr, float *scratch, hipStream_t st) {
@@ -601,31 +655,38 @@ static int rpn_head_backward(const char *fn, const AabrRpnMap *maps_host, int n_
   AABR_CHECK_ARG((A) >= 1 && (A) <= 4, "A must be 1..4");                                                               \
   AABR_CHECK_ARG(rpn_groups_ok(A, G), "groups: 2 <= G <= 8 and A G <= 16")
 
-extern "C" int aabr_rpn_head_forward(const AabrRpnMap *maps_host, int n_maps, int C, int A, const float *W1,
-                                     const float *b1, const float *Wc, const float *bc, const float *Wr, const float *br,
-                                     float *hidden, void *stream_) {
-  return rpn_head_forward(__func__, maps_host, n_maps, C, A, 1, false, W1, b1, Wc, bc, Wr, br, hidden, (hipStream_t)stream_);
-}
+// the four entry points of one row storage FT: aabr_rpn_head_{,grouped_}{forward,backward}<SUFFIX>
+#define AABR_RPN_ENTRIES(SUFFIX, FT)                                                                                    \
+  extern "C" int aabr_rpn_head_forward##SUFFIX(const AabrRpnMap *maps_host, int n_maps, int C, int A, const float *W1,  \
+                                               const float *b1, const float *Wc, const float *bc, const float *Wr,      \
+                                               const float *br, float *hidden, void *stream_) {                         \
+    return rpn_head_forward<FT>(__func__, maps_host, n_maps, C, A, 1, false, W1, b1, Wc, bc, Wr, br, hidden,            \
+                                (hipStream_t)stream_);                                                                  \
+  }                                                                                                                     \
+  extern "C" int aabr_rpn_head_backward##SUFFIX(const AabrRpnMap *maps_host, int n_maps, int C, int A, const float *W1, \
+                                                const float *Wc, const float *Wr, const float *hidden, float *dW1,      \
+                                                float *db1, float *dWc, float *dbc, float *dWr, float *dbr,             \
+                                                float *scratch, void *stream_) {                                        \
+    return rpn_head_backward<FT>(__func__, maps_host, n_maps, C, A, 1, false, W1, Wc, Wr, hidden, dW1, db1, dWc, dbc,   \
+                                 dWr, dbr, scratch, (hipStream_t)stream_);                                              \
+  }                                                                                                                     \
+  extern "C" int aabr_rpn_head_grouped_forward##SUFFIX(const AabrRpnMap *maps_host, int n_maps, int C, int A, int G,    \
+                                                       const float *W1, const float *b1, const float *Wc,               \
+                                                       const float *bc, const float *Wr, const float *br,               \
+                                                       float *hidden, void *stream_) {                                  \
+    AABR_RPN_CHECK_GROUPS(A, G);                                                                                        \
+    return rpn_head_forward<FT>(__func__, maps_host, n_maps, C, A, G, true, W1, b1, Wc, bc, Wr, br, hidden,             \
+                                (hipStream_t)stream_);                                                                  \
+  }                                                                                                                     \
+  extern "C" int aabr_rpn_head_grouped_backward##SUFFIX(const AabrRpnMap *maps_host, int n_maps, int C, int A, int G,   \
+                                                        const float *W1, const float *Wc, const float *Wr,              \
+                                                        const float *hidden, float *dW1, float *db1, float *dWc,        \
+                                                        float *dbc, float *dWr, float *dbr, float *scratch,             \
+                                                        void *stream_) {                                                \
+    AABR_RPN_CHECK_GROUPS(A, G);                                                                                        \
+    return rpn_head_backward<FT>(__func__, maps_host, n_maps, C, A, G, true, W1, Wc, Wr, hidden, dW1, db1, dWc, dbc,    \
+                                 dWr, dbr, scratch, (hipStream_t)stream_);                                              \
+  }
 
-extern "C" int aabr_rpn_head_backward(const AabrRpnMap *maps_host, int n_maps, int C, int A, const float *W1,
-                                      const float *Wc, const float *Wr, const float *hidden, float *dW1, float *db1,
-                                      float *dWc, float *dbc, float *dWr, float *dbr, float *scratch, void *stream_) {
-  return rpn_head_backward(__func__, maps_host, n_maps, C, A, 1, false, W1, Wc, Wr, hidden, dW1, db1, dWc, dbc, dWr, dbr,
-                           scratch, (hipStream_t)stream_);
-}
-
-extern "C" int aabr_rpn_head_grouped_forward(const AabrRpnMap *maps_host, int n_maps, int C, int A, int G, const float *W1,
-                                             const float *b1, const float *Wc, const float *bc, const float *Wr,
-                                             const float *br, float *hidden, void *stream_) {
-  AABR_RPN_CHECK_GROUPS(A, G);
-  return rpn_head_forward(__func__, maps_host, n_maps, C, A, G, true, W1, b1, Wc, bc, Wr, br, hidden, (hipStream_t)stream_);
-}
-
-extern "C" int aabr_rpn_head_grouped_backward(const AabrRpnMap *maps_host, int n_maps, int C, int A, int G, const float *W1,
-                                              const float *Wc, const float *Wr, const float *hidden, float *dW1,
-                                              float *db1, float *dWc, float *dbc, float *dWr, float *dbr, float *scratch,
-                                              void *stream_) {
-  AABR_RPN_CHECK_GROUPS(A, G);
-  return rpn_head_backward(__func__, maps_host, n_maps, C, A, G, true, W1, Wc, Wr, hidden, dW1, db1, dWc, dbc, dWr, dbr,
-                           scratch, (hipStream_t)stream_);
-}
+AABR_RPN_ENTRIES(, float)
+AABR_RPN_ENTRIES(_bf16, __bf16) // AabrRpnMap.features / .d_features point at bf16 rows

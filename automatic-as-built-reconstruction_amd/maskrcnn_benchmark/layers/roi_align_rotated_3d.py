@@ -68,7 +68,8 @@ def _cellmap(input_s3d, ext):
 
 
 class _ROIAlignRotated3DSparse(Function):
-    """densify + crop + ROI-align as ONE gather from the sparse feature rows (bit-identical forward)"""
+    """densify + crop + ROI-align as ONE gather from the sparse feature rows (bit-identical forward).  bf16 feature rows
+    are gathered in place (widened per corner, fp32 output); their gradient is summed in an fp32 buffer and rounded once"""
 
     @staticmethod
     def forward(ctx, features, cellmap, roi, output_size, spatial_scale, sampling_ratio):
@@ -79,11 +80,14 @@ class _ROIAlignRotated3DSparse(Function):
         rois = roi.to(device=feats.device, dtype=torch.float32).contiguous()
         b, x, y, z = cellmap.shape
         out = torch.empty((rois.size(0), feats.size(1)) + tuple(output_size), dtype=torch.float32, device=feats.device)
-        check(_hip.load().aabr_roi_align_rotated_3d_sparse_forward(
+        bf16 = feats.dtype == torch.bfloat16
+        lib = _hip.load()
+        forward = lib.aabr_roi_align_rotated_3d_sparse_forward_bf16 if bf16 else lib.aabr_roi_align_rotated_3d_sparse_forward
+        check(forward(
             ptr(feats), feats.size(1), ptr(cellmap), b, x, y, z, ptr(rois), rois.size(0), float(spatial_scale),
             int(output_size[0]), int(output_size[1]), int(output_size[2]), int(sampling_ratio), ptr(out), stream()))
         ctx.save_for_backward(rois, cellmap)
-        ctx.geom = (tuple(output_size), float(spatial_scale), int(sampling_ratio), feats.size(0), feats.size(1))
+        ctx.geom = (tuple(output_size), float(spatial_scale), int(sampling_ratio), feats.size(0), feats.size(1), bf16)
         return out
 
     @staticmethod
@@ -93,13 +97,17 @@ class _ROIAlignRotated3DSparse(Function):
         import _hip
         from _hip import ptr, stream, check
         rois, cellmap = ctx.saved_tensors
-        output_size, scale, sampling, V, C = ctx.geom
+        output_size, scale, sampling, V, C, bf16 = ctx.geom
         b, x, y, z = cellmap.shape
         g = grad_output.contiguous()
         d_feats = torch.empty((V, C), dtype=torch.float32, device=g.device)
-        check(_hip.load().aabr_roi_align_rotated_3d_sparse_backward(
-            ptr(g), C, ptr(cellmap), b, x, y, z, ptr(rois), rois.size(0), scale, output_size[0], output_size[1],
-            output_size[2], sampling, V, ptr(d_feats), stream()))
+        args = (ptr(g), C, ptr(cellmap), b, x, y, z, ptr(rois), rois.size(0), scale, output_size[0], output_size[1],
+                output_size[2], sampling, V, ptr(d_feats))
+        if bf16:                                        # d_feats: the fp32 sums; one rounding into the bf16 rows
+            d_rows = torch.empty((V, C), dtype=torch.bfloat16, device=g.device)
+            check(_hip.load().aabr_roi_align_rotated_3d_sparse_backward_bf16(*args, ptr(d_rows), stream()))
+            return d_rows, None, None, None, None, None
+        check(_hip.load().aabr_roi_align_rotated_3d_sparse_backward(*args, stream()))
         return d_feats, None, None, None, None, None
 
 
@@ -113,7 +121,7 @@ class ROIAlignRotated3D(nn.Module):
 
     def forward(self, input_s3d, rois_3d):
         import torch
-        if self.fused and input_s3d.features.dtype == torch.float32 and input_s3d.features.dim() == 2 \
+        if self.fused and input_s3d.features.dtype in (torch.float32, torch.bfloat16) and input_s3d.features.dim() == 2 \
                 and input_s3d.features.size(0) > 0:
             ext = _occupied_extent(input_s3d)
             return _ROIAlignRotated3DSparse.apply(input_s3d.features, _cellmap(input_s3d, ext), rois_3d,

@@ -95,8 +95,9 @@ class Pooler(nn.Module):
                                       self.box_scale)
         rois, levels = torch_rois_and_levels(bbox3d, self.scales, self.canonical_size, self.box_scale)
         feats0 = x[0].features
-        result = torch.zeros((len(rois), feats0.shape[1]) + tuple(self.output_size), dtype=feats0.dtype,
-                             device=feats0.device)
+        # bf16 levels are gathered into an fp32 result, as the fused form gives it
+        result = torch.zeros((len(rois), feats0.shape[1]) + tuple(self.output_size), device=feats0.device,
+                             dtype=torch.float32 if feats0.dtype == torch.bfloat16 else feats0.dtype)
         for level, (per_level_feature, pooler) in enumerate(zip(x, self.poolers)):
             idx_in_level = torch.nonzero(levels == level).squeeze(1)
             result[idx_in_level] = pooler(per_level_feature, rois[idx_in_level])

@@ -35,7 +35,7 @@ class RPNHead(nn.Module):
     """SingleConvRPNHead_Sparse3D: a 1 x 1 convolution + ReLU, then the objectness and box heads.  The reference's three
     nn.Conv2d parameters under their names, shapes and initialisation, so its state_dict loads.  `fused` (default True):
     rpn_glue.rpn_head, 1 library launch forward and 2 backward for all maps; False: the torch convolutions of the
-    reference, the yardstick."""
+    reference, the yardstick.  Fused, maps in bf16 storage are read in place: fp32 outputs, bf16 gradients to the maps."""
     fused = True
 
     def __init__(self, cfg, in_channels, num_anchors_per_location):
@@ -60,16 +60,19 @@ class RPNHead(nn.Module):
         groups: [G, n A] and [G, n A, 7], group-major, each group's slice in that order"""
         rows = [_rows(f) for f in x]
         A, G = self.num_anchors_per_location, self.seperate_rpn
+        # fused: bf16 rows are read in place (rpn_glue's feature_dtype); the glue refuses a mix of storages
+        storage = torch.bfloat16 if rows and rows[0].dtype == torch.bfloat16 else torch.float32
         if G != 1:
             if self.fused:
                 return rpn_glue.rpn_head_grouped(rows, self.conv.weight, self.conv.bias, self.cls_logits.weight,
-                                                 self.cls_logits.bias, self.bbox_pred.weight, self.bbox_pred.bias, G)
+                                                 self.cls_logits.bias, self.bbox_pred.weight, self.bbox_pred.bias, G,
+                                                 feature_dtype=storage)
             logits, bbox = self._forward_reference(rows)
             return ([l.reshape(-1, A, G).permute(2, 0, 1).reshape(G, -1) for l in logits],
                     [b.reshape(-1, A, G, 7).permute(2, 0, 1, 3).reshape(G, -1, 7) for b in bbox])
         if self.fused:
             return rpn_glue.rpn_head(rows, self.conv.weight, self.conv.bias, self.cls_logits.weight, self.cls_logits.bias,
-                                     self.bbox_pred.weight, self.bbox_pred.bias)
+                                     self.bbox_pred.weight, self.bbox_pred.bias, feature_dtype=storage)
         obj, reg = [], []
         for f in rows:
             if f.shape[0] == 0:         # torch's convolution refuses an empty map: the same layers as matrix products,

@@ -633,9 +633,11 @@ def _pool_check(features, proposals, output_size, scales):
         raise ValueError("1 .. %d levels, got %d" % (POOL_MAX_LEVELS, len(features)))
     if len(tuple(output_size)) != 3:
         raise ValueError("output_size must be (ph, pw, pz)")
+    dtypes = set(x.features.dtype for x in features)
+    if len(dtypes) != 1 or not dtypes <= {torch.float32, torch.bfloat16}:
+        raise TypeError("pool_rois gathers float32 or bfloat16 features, every level in the same storage; got %s"
+                        % sorted(str(d) for d in dtypes))
     for x in features:
-        if x.features.dtype != torch.float32:
-            raise TypeError("pool_rois gathers float32 features, got %s (bf16 is not part of this path)" % x.features.dtype)
         if x.features.dim() != 2:
             raise ValueError("features must be [V, C]")
     chans = set(int(x.features.shape[1]) for x in features)
@@ -675,7 +677,9 @@ def _level_table(descs):
 
 
 class _PoolRois(torch.autograd.Function):
-    """every level's gather in one launch; backward: one gradient allocation for all levels, one memset, one launch"""
+    """every level's gather in one launch; backward: one gradient allocation for all levels, one memset, one launch.
+    bf16 levels are gathered in place; their gradients are summed in an fp32 buffer and rounded once into one bf16
+    allocation (one more launch), sliced per level the same way"""
 
     @staticmethod
     def forward(ctx, rois, levels, geom, cfg, *feats):
@@ -690,9 +694,11 @@ class _PoolRois(torch.autograd.Function):
             off += V
         N = int(rois.shape[0])
         out = torch.empty((N, C_) + tuple(output_size), dtype=torch.float32, device=rois.device)   # every element is written
-        check(lib.aabr_roi_pool_forward(_level_table(descs), len(descs), C_, nb, ptr(rois), ptr(levels), N, output_size[0],
-                                        output_size[1], output_size[2], sampling, ptr(out), _hip.stream()))
-        ctx.descs, ctx.cfg, ctx.total = [(None,) + d[1:] for d in descs], (tuple(output_size), sampling, nb, C_), off
+        bf16 = feats[0].dtype == torch.bfloat16
+        forward = lib.aabr_roi_pool_forward_bf16 if bf16 else lib.aabr_roi_pool_forward
+        check(forward(_level_table(descs), len(descs), C_, nb, ptr(rois), ptr(levels), N, output_size[0],
+                      output_size[1], output_size[2], sampling, ptr(out), _hip.stream()))
+        ctx.descs, ctx.cfg, ctx.total = [(None,) + d[1:] for d in descs], (tuple(output_size), sampling, nb, C_, bf16), off
         ctx.save_for_backward(rois, levels, *feats)
         return out
 
@@ -702,18 +708,23 @@ class _PoolRois(torch.autograd.Function):
         lib = _hip.load()
         rois, levels = ctx.saved_tensors[:2]
         descs = [(f,) + d[1:] for f, d in zip(ctx.saved_tensors[2:], ctx.descs)]
-        output_size, sampling, nb, C_ = ctx.cfg
+        output_size, sampling, nb, C_, bf16 = ctx.cfg
         g = grad_output.contiguous()
         d_all = torch.empty((ctx.total, C_), dtype=torch.float32, device=g.device)                 # zeroed by the library
-        check(lib.aabr_roi_pool_backward(_level_table(descs), len(descs), C_, nb, ptr(rois), ptr(levels),
-                                         int(rois.shape[0]), output_size[0], output_size[1], output_size[2], sampling,
-                                         ptr(g), ptr(d_all), ctx.total, _hip.stream()))
+        args = (_level_table(descs), len(descs), C_, nb, ptr(rois), ptr(levels), int(rois.shape[0]), output_size[0],
+                output_size[1], output_size[2], sampling, ptr(g), ptr(d_all))
+        if bf16:                                        # d_all: the fp32 sums; one rounding into the bf16 rows
+            d_f32, d_all = d_all, torch.empty((ctx.total, C_), dtype=torch.bfloat16, device=g.device)
+            check(lib.aabr_roi_pool_backward_bf16(*args, ptr(d_all), ctx.total, _hip.stream()))
+        else:
+            check(lib.aabr_roi_pool_backward(*args, ctx.total, _hip.stream()))
         grads = tuple(d_all[off:off + V] for (_f, _cm, _ext, V, off, _s) in ctx.descs)
         return (None, None, None, None) + grads
 
 
 def pool_rois(features, proposals, output_size, scales, sampling_ratio, canonical_size, box_scale=1.0, debug=None):
-    """features: list over levels of SparseConvNetTensor (fp32 [V_l, C] features); proposals: list over scenes of [n_b, 7]
+    """features: list over levels of SparseConvNetTensor ([V_l, C] features, all fp32 or all bf16 storage -- bf16 rows are
+    gathered in place, the result stays fp32, each level's gradient is bf16: fp32 sums rounded once); proposals: list over scenes of [n_b, 7]
     yx_zb device tensors; scales: each level's spatial scale relative to the box frame after `box_scale` (the
     reference's POOLER_SCALES; `box_scale` its SPARSE3D.VOXEL_SCALE, convert_metric_to_pixel).
 

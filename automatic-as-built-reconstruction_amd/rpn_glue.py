@@ -719,10 +719,11 @@ class _RpnHead(torch.autograd.Function):
     """SingleConvRPNHead_Sparse3D over every map in one launch (csrc/rpn_head.hip); the hidden activation is written to
     memory only when some input requires a gradient.  G None: aabr_rpn_head_*, outputs [V A] and [V A, 7]; with G
     separated-classifier groups: aabr_rpn_head_grouped_*, Wc [A G, C], Wr [7 A G, C] in the reference's layout, the
-    outputs group-major [G, V A] and [G, V A, 7]"""
+    outputs group-major [G, V A] and [G, V A, 7].  `bf16`: the maps are bf16 rows (aabr_rpn_head_*_bf16): the outputs
+    and parameter gradients stay fp32, the maps' gradients come back as bf16 views of one allocation"""
 
     @staticmethod
-    def forward(ctx, A, G, W1, b1, Wc, bc, Wr, br, *feats):
+    def forward(ctx, A, G, bf16, W1, b1, Wc, bc, Wr, br, *feats):
         lib = _hip.load()
         dev = W1.device
         C, n_maps = int(W1.shape[0]), len(feats)
@@ -738,24 +739,24 @@ class _RpnHead(torch.autograd.Function):
         for m in range(n_maps):
             tab[m].features, tab[m].rows = ptr(feats[m]), rows[m]
             tab[m].objectness, tab[m].box_regression = ptr(obj[m]), ptr(reg[m])
-        forward = lib.aabr_rpn_head_forward if G is None else lib.aabr_rpn_head_grouped_forward
+        forward = getattr(lib, "aabr_rpn_head%s_forward%s" % ("" if G is None else "_grouped", "_bf16" if bf16 else ""))
         check(forward(tab, n_maps, C, A, *lead, *[ptr(p) for p in params], ptr(hidden), stream()))
         if need:
             ctx.save_for_backward(hidden, params[0], params[2], params[4], *feats)
-        ctx.cfg = (A, G, C, n_maps, rows)
+        ctx.cfg = (A, G, C, n_maps, rows, bf16)
         return tuple(obj) + tuple(reg)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, *grads):
         lib = _hip.load()
-        A, G, C, n_maps, rows = ctx.cfg
+        A, G, C, n_maps, rows, bf16 = ctx.cfg
         hidden, W1, Wc, Wr = ctx.saved_tensors[:4]
         feats = ctx.saved_tensors[4:]
         dev = W1.device
         g_obj = [g.contiguous() if g is not None else None for g in grads[:n_maps]]
         g_reg = [g.contiguous() if g is not None else None for g in grads[n_maps:]]
-        d_all = torch.empty((sum(rows), C), dtype=torch.float32, device=dev)           # every element is written
+        d_all = torch.empty((sum(rows), C), dtype=torch.bfloat16 if bf16 else torch.float32, device=dev)  # all written
         d_f = list(torch.split(d_all, rows))
         AG = A * (G or 1)
         sizes = (C * C, C, AG * C, AG, 7 * AG * C, 7 * AG)
@@ -763,11 +764,9 @@ class _RpnHead(torch.autograd.Function):
         t_rows = lib.aabr_rpn_head_tile_rows(C)
         tiles = sum(-(-v // t_rows) for v in rows)
         lead = () if G is None else (G,)
-        if G is None:
-            floats, backward, key = lib.aabr_rpn_head_scratch_floats, lib.aabr_rpn_head_backward, "rpn_head"
-        else:
-            floats, backward = lib.aabr_rpn_head_grouped_scratch_floats, lib.aabr_rpn_head_grouped_backward
-            key = "rpn_head_grouped"
+        key = "rpn_head" if G is None else "rpn_head_grouped"
+        floats = getattr(lib, "aabr_%s_scratch_floats" % key)
+        backward = getattr(lib, "aabr_%s_backward%s" % (key, "_bf16" if bf16 else ""))
         floats = int(floats(tiles, C, A, *lead))
         scr = _hip.workspace(key, floats, torch.float32, dev) if floats else None
         tab = (_hip.AabrRpnMap * n_maps)()
@@ -776,7 +775,7 @@ class _RpnHead(torch.autograd.Function):
             tab[m].objectness, tab[m].box_regression = ptr(g_obj[m]), ptr(g_reg[m])
         check(backward(tab, n_maps, C, A, *lead, ptr(W1), ptr(Wc), ptr(Wr), ptr(hidden), *[ptr(p) for p in d_p],
                        ptr(scr), stream()))
-        return (None, None, d_p[0].view(C, C), d_p[1], d_p[2].view(AG, C), d_p[3], d_p[4].view(7 * AG, C), d_p[5]) + tuple(d_f)
+        return (None, None, None, d_p[0].view(C, C), d_p[1], d_p[2].view(AG, C), d_p[3], d_p[4].view(7 * AG, C), d_p[5]) + tuple(d_f)
 
 
 def _as_out_in(name, w):
@@ -798,17 +797,24 @@ def rpn_head_group_limits_ok(C, A, G):
             and A * G <= RPN_HEAD_MAX_COLUMNS)
 
 
-def _rpn_head(fn, G, features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b):
+def _rpn_head(fn, G, features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b, feature_dtype=torch.float32):
     """the checks and the launch of rpn_head (G None) and rpn_head_grouped; `fn`: the caller's name, for the messages"""
+    if feature_dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("%s: feature_dtype must be torch.float32 or torch.bfloat16, got %s" % (fn, feature_dtype))
     feats = [f.features if hasattr(f, "features") else f for f in features]
     if not 1 <= len(feats) <= RPN_HEAD_MAX_MAPS:
         raise ValueError("%s: 1 to %d maps, got %d" % (fn, RPN_HEAD_MAX_MAPS, len(feats)))
     w1, wc, wr = _as_out_in("conv_w", conv_w), _as_out_in("cls_w", cls_w), _as_out_in("reg_w", reg_w)
-    for k, t in [("conv_w", w1), ("conv_b", conv_b), ("cls_w", wc), ("cls_b", cls_b), ("reg_w", wr), ("reg_b", reg_b)] + \
-            [("features[%d]" % i, f) for i, f in enumerate(feats)]:
+    for k, t in [("conv_w", w1), ("conv_b", conv_b), ("cls_w", wc), ("cls_b", cls_b), ("reg_w", wr), ("reg_b", reg_b)]:
         if t.dtype != torch.float32:
-            raise TypeError("%s: %s must be float32, got %s (bf16 feature storage is not part of this path)"
+            raise TypeError("%s: %s must be float32, got %s (the parameters are fp32 in either feature storage)"
                             % (fn, k, t.dtype))
+    for i, f in enumerate(feats):                       # every map in the one storage the caller names
+        if f.dtype != feature_dtype:
+            want = "float32" if feature_dtype == torch.float32 else "bfloat16 (feature_dtype=torch.bfloat16)"
+            raise TypeError("%s: features[%d] must be %s, got %s; bf16 maps are read in place with the keyword "
+                            "feature_dtype=torch.bfloat16 (default float32), all maps in one storage"
+                            % (fn, i, want, f.dtype))
     C, AG = int(w1.shape[1]), int(wc.shape[0])          # AG: the rows of cls_w, A without groups
     if G is None:
         A = AG
@@ -830,11 +836,11 @@ def _rpn_head(fn, G, features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b):
         if f.dim() != 2 or int(f.shape[1]) != C:
             raise ValueError("%s: features[%d] must be [V, %d], got %s" % (fn, i, C, tuple(f.shape)))
     _hip.require_gpu(feats[0])
-    out = _RpnHead.apply(A, G, w1, conv_b, wc, cls_b, wr, reg_b, *feats)
+    out = _RpnHead.apply(A, G, feature_dtype == torch.bfloat16, w1, conv_b, wc, cls_b, wr, reg_b, *feats)
     return list(out[:len(feats)]), list(out[len(feats):])
 
 
-def rpn_head(features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b):
+def rpn_head(features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b, feature_dtype=torch.float32):
     """SingleConvRPNHead_Sparse3D.forward (modeling/rpn/rpn_sparse3d.py:109-131) for all maps at once:
       t = relu(f conv_w^T + conv_b), objectness = t cls_w^T + cls_b, box_regression = t reg_w^T + reg_b
     features: a list (1..8 maps) of SparseConvNetTensors or of [V_m, C] fp32 tensors; the weights as [out, in] or the
@@ -843,19 +849,23 @@ def rpn_head(features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b):
     [V_m A, 7] in the [site, yaw] flatten order rpn_proposals, rpn_label_matches and rpn_loss read.
     Device work: forward 1 library launch whatever the number of maps (nothing concatenated, the hidden activation
     reaches memory only when a gradient is required); backward 2 (the fused main kernel and the in-order reduction of its
-    per-workgroup partials: deterministic, no atomics).  No host read."""
-    return _rpn_head("rpn_head", None, features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b)
+    per-workgroup partials: deterministic, no atomics).  No host read.
+    `feature_dtype=torch.bfloat16`: every map is bf16 storage, read in place (no widened copy); the parameters and both
+    outputs stay fp32 and are the bits of the fp32 call on `f.float()`; autograd delivers bf16 gradients to the maps, the
+    fp32 call's values rounded once.  The keyword is explicit: a bf16 map without it raises TypeError."""
+    return _rpn_head("rpn_head", None, features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b, feature_dtype)
 
 
-def rpn_head_grouped(features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b, G):
+def rpn_head_grouped(features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b, G, feature_dtype=torch.float32):
     """SingleConvRPNHead_Sparse3D.forward with MODEL.SEPARATE_CLASSES and SEPARATE_RPN (rpn_sparse3d.py:95-131), G =
     len(SEPARATE_CLASSES) + 1 branches on one hidden layer, for all maps at once.  The weights in the reference's layout
     ([out, in] or Conv2d [out, in, 1, 1]): cls_w [A G, C] with row a G + g, reg_w [7 A G, C] with row a 7 G + 7 g + k.
     C in {32, 64, 96, 128}, 1 <= A <= 4, 2 <= G <= 8, A G <= 16.
     Returns (objectness, box_regression): lists over the maps of [G, V_m A] and [G, V_m A, 7]: group g's slice is a
     contiguous tensor in the [site, yaw] order of rpn_head, and holds the bits rpn_head gives on that group's weight rows.
-    Device work as rpn_head: forward 1 library launch, backward 2; nothing is permuted or copied.  No host read."""
-    return _rpn_head("rpn_head_grouped", int(G), features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b)
+    Device work as rpn_head: forward 1 library launch, backward 2; nothing is permuted or copied.  No host read.
+    `feature_dtype` as in rpn_head."""
+    return _rpn_head("rpn_head_grouped", int(G), features, conv_w, conv_b, cls_w, cls_b, reg_w, reg_b, feature_dtype)
 
 
 class _Cfg(object):

@@ -20,7 +20,7 @@ class FPN_Net(torch.nn.Module):
                  feature_dtype=torch.float32):
         """`feature_dtype` (extension, not in the reference): torch.bfloat16 stores every feature
         matrix after the first (raw_elements -> nPlanesF[0]) convolution in bf16; parameters, batch-norm
-        statistics and all accumulation stay fp32, the returned maps are cast back to fp32."""
+        statistics and all accumulation stay fp32, the returned maps are cast back to fp32 (`cast_outputs`)."""
         nn.Module.__init__(self)
         assert feature_dtype in (torch.float32, torch.bfloat16)
         self.feature_dtype = feature_dtype
@@ -28,6 +28,10 @@ class FPN_Net(torch.nn.Module):
         self.prepack_weights = True     # extension: see _refresh_weight_packs
         self.grids_from_input = True    # extension: see _grids_from_input
         self.compiled_graph = False     # extension: planExecutor.run_fpn (one launch list per pass)
+        # extension: False returns the maps in `feature_dtype` -- no cast launch and fp32 copy per map forward, none
+        # backward -- for consumers that read bf16 rows in place (RPNHead, Pooler, ROIAlignRotated3D).  Not with
+        # compiled_graph: the plan's cast records are part of its launch list.
+        self.cast_outputs = True
         self.site_order = "first_seen"  # extension: "brick" = brick-major rows over brick grids (see set_site_order)
         # extension (opt-in, never the default): the reference's forward_fpn runs the whole top-down path to scale 0
         # (fpn_net.py:181-196; the `continue` that would stop it is commented out) although only ups[i], i in
@@ -414,6 +418,9 @@ class FPN_Net(torch.nn.Module):
         return super()._load_from_state_dict(*args, **kwargs)
 
     def forward(self, net0):
+        if self.compiled_graph and not self.cast_outputs:
+            raise ValueError("FPN_Net: compiled_graph = True with cast_outputs = False is not supported: the compiled "
+                             "graph casts the returned maps to fp32 itself")
         self.join_unconsumed()          # ... they read the packed weights and the parameters of the previous pass
         plan = self._refresh_weight_packs() if self.prepack_weights else None
         try:
@@ -436,6 +443,8 @@ class FPN_Net(torch.nn.Module):
         if self.feature_dtype == torch.float32:
             return self.forward_fpn(net1)
         rpn_maps, roi_maps = self.forward_fpn(self._cast(net1, self.feature_dtype))
+        if not self.cast_outputs:
+            return rpn_maps, roi_maps
         return ([self._cast(m, torch.float32) for m in rpn_maps], [self._cast(m, torch.float32) for m in roi_maps])
 
     def _top_down_levels(self):

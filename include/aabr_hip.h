@@ -1034,6 +1034,22 @@ int aabr_roi_align_rotated_3d_sparse_backward(const float *grad_output, int chan
                                               const float *rois, int64_t num_rois, float spatial_scale,
                                               int pooled_h, int pooled_w, int pooled_z, int sampling_ratio,
                                               int64_t V, float *d_feats, void *stream);
+/* bf16 feature storage (same reference lines; mirrors aabr_roi_align_rotated_3d_sparse_forward / _backward).
+ * _forward_bf16: `feats` points at bf16 rows [V, C], 4-byte aligned; each of the eight corner values is widened
+ *   (exact), the arithmetic and the fp32 output are bit for bit the fp32 call's on the widened rows.
+ * _backward_bf16: never accumulates in bf16.  The fp32 call runs into `accum_f32` (caller-provided fp32 [V, channels],
+ *   zeroed here, fp32 atomics) and its sums are rounded once (nearest even) into d_feats_bf16 [V, channels]:
+ *   1 memset + 2 launches.  Both pointers 4-byte aligned.                                                           */
+int aabr_roi_align_rotated_3d_sparse_forward_bf16(const void *feats_bf16, int channels, const int32_t *cellmap,
+                                                  int batch_size, int height, int width, int zsize,
+                                                  const float *rois, int64_t num_rois, float spatial_scale,
+                                                  int pooled_h, int pooled_w, int pooled_z, int sampling_ratio,
+                                                  float *output, void *stream);
+int aabr_roi_align_rotated_3d_sparse_backward_bf16(const float *grad_output, int channels, const int32_t *cellmap,
+                                                   int batch_size, int height, int width, int zsize,
+                                                   const float *rois, int64_t num_rois, float spatial_scale,
+                                                   int pooled_h, int pooled_w, int pooled_z, int sampling_ratio,
+                                                   int64_t V, float *accum_f32, void *d_feats_bf16, void *stream);
 
 /* ---- multi-level ROI pooler (csrc/roi_pool.hip): Pooler.forward of the box head (modeling/poolers_3d.py:73-168)
  * with FPN2MLPFeatureExtractor.convert_metric_to_pixel (roi_box_feature_extractors.py:108-114) in front of it.
@@ -1051,7 +1067,8 @@ int aabr_roi_align_rotated_3d_sparse_backward(const float *grad_output, int chan
  * aabr_roi_pool_backward: d_feats_all [total_rows, channels] holds every level's gradient rows, level l at row
  *   row_offset (row_offset + V <= total_rows); zeroed here, then fp32 atomics on active cells only.                   */
 typedef struct AabrRoiLevel {
-  const float *feats;          /* [V, channels] fp32 feature rows of the level (unused when V == 0)                  */
+  const float *feats;          /* [V, channels] fp32 feature rows of the level (unused when V == 0); the _bf16 entry
+                                  points read this pointer as bf16 rows [V, channels], 4-byte aligned                */
   const int32_t *cellmap;      /* [nb, height, width, zsize] int32, aabr_roi_cellmap over the occupied extent        */
   int32_t height, width, zsize; /* the occupied extent                                                               */
   int32_t nb;                  /* samples the cell map covers: an ROI of scene >= nb names an empty sample           */
@@ -1069,6 +1086,19 @@ int aabr_roi_pool_backward(const AabrRoiLevel *levels_desc_host, int n_levels, i
                            const float *rois, const int32_t *levels, int64_t num_rois, int pooled_h, int pooled_w,
                            int pooled_z, int sampling_ratio, const float *grad_output, float *d_feats_all,
                            int64_t total_rows, void *stream);
+/* bf16 feature storage of every level (Pooler.forward as above; mirrors aabr_roi_pool_forward / _backward).
+ * aabr_roi_pool_forward_bf16: AabrRoiLevel.feats point at bf16 rows; the output stays fp32 and is bit for bit
+ *   aabr_roi_pool_forward's on the widened rows.
+ * aabr_roi_pool_backward_bf16: aabr_roi_pool_backward into `accum_f32` (caller-provided fp32 [total_rows, channels]),
+ *   then ONE rounding (nearest even) into d_feats_all_bf16 [total_rows, channels]: 1 memset + 2 launches, nothing is
+ *   accumulated in bf16.  accum_f32 keeps the fp32 sums.  Both 4-byte aligned.                                       */
+int aabr_roi_pool_forward_bf16(const AabrRoiLevel *levels_desc_host, int n_levels, int channels, int batch_size,
+                               const float *rois, const int32_t *levels, int64_t num_rois, int pooled_h, int pooled_w,
+                               int pooled_z, int sampling_ratio, float *output, void *stream);
+int aabr_roi_pool_backward_bf16(const AabrRoiLevel *levels_desc_host, int n_levels, int channels, int batch_size,
+                                const float *rois, const int32_t *levels, int64_t num_rois, int pooled_h, int pooled_w,
+                                int pooled_z, int sampling_ratio, const float *grad_output, float *accum_f32,
+                                void *d_feats_all_bf16, int64_t total_rows, void *stream);
 
 /* ---- RPN loss (csrc/rpn_loss.hip): RPNLossComputation.__call__ (modeling/rpn/loss_3d.py:201-251), one objectness group.
  * Per example the BalancedPositiveNegativeSampler (modeling/balanced_positive_negative_sampler.py:19-68):
@@ -1483,7 +1513,8 @@ int aabr_roi_mlp_backward_weight_window(const float *dY, const float *Y, const f
                                         int64_t N, int64_t perm_hw, float *dW, float *db, float *scratch, void *stream);
 
 /* ---- the RPN head (csrc/rpn_head.hip): SingleConvRPNHead_Sparse3D (modeling/rpn/rpn_sparse3d.py:81-131) over the rows
- * of every feature map in one launch, fp32 storage only, on v_mfma_f32_32x32x2_f32 (every element an exact fmaf chain):
+ * of every feature map in one launch, on v_mfma_f32_32x32x2_f32 (every element an exact fmaf chain); the feature rows
+ * in fp32 storage, or in bf16 through the _bf16 entry points below:
  *   t = relu(f W1^T + b1),  obj = t Wc^T + bc,  reg = t Wr^T + br
  * with f [rows, C] the rows of a map and W1 [C, C], Wc [A, C], Wr [7 A, C] the Conv2d weights viewed as [out, in].
  * Output channel order is the reference's permute + reshape ('box_toghter'): objectness [rows, A], box_regression
@@ -1508,6 +1539,8 @@ int aabr_roi_mlp_backward_weight_window(const float *dY, const float *Y, const f
  *   aabr_rpn_head_tile_rows(C): 64 for a supported C, else 0.  total_tiles = sum over maps of ceil(rows / tile_rows).
  *   aabr_rpn_head_groups(total_tiles): min(total_tiles, 256); 0 for total_tiles < 1.
  *   aabr_rpn_head_scratch_floats(total_tiles, C, A): groups * (C C + 32 C + C + 32); 0 for an unsupported shape.      */
+/* The _bf16 entry points read `features` and write `d_features` as bf16 rows [rows, C] through the same two pointers
+ * (both 4-byte aligned); every other field, and the record's 40 bytes, are the same.                                  */
 typedef struct AabrRpnMap {
   const float *features;       /* [rows, C] fp32 feature rows of the map                                              */
   int64_t rows;
@@ -1543,6 +1576,24 @@ int aabr_rpn_head_grouped_forward(const AabrRpnMap *maps_host, int n_maps, int C
 int aabr_rpn_head_grouped_backward(const AabrRpnMap *maps_host, int n_maps, int C, int A, int G, const float *W1,
                                    const float *Wc, const float *Wr, const float *hidden, float *dW1, float *db1,
                                    float *dWc, float *dbc, float *dWr, float *dbr, float *scratch, void *stream);
+/* bf16 feature storage (rpn_sparse3d.py:81-131 as above; each mirrors the fp32 entry point of the same name, same
+ * arguments, shapes, scratch and launches).  AabrRpnMap.features / .d_features point at bf16 rows, 4-byte aligned.  The
+ * rows are widened (exact) into the fp32 kernel's own LDS images, so objectness, box_regression, `hidden` and the six
+ * weight gradients -- all fp32 -- are bit for bit the fp32 entry point's on the widened rows.  d_features is the one
+ * output in bf16: each fp32 value the fp32 entry point would store is rounded once (nearest even), every element stored
+ * exactly once.                                                                                                       */
+int aabr_rpn_head_forward_bf16(const AabrRpnMap *maps_host, int n_maps, int C, int A, const float *W1, const float *b1,
+                               const float *Wc, const float *bc, const float *Wr, const float *br, float *hidden,
+                               void *stream);
+int aabr_rpn_head_backward_bf16(const AabrRpnMap *maps_host, int n_maps, int C, int A, const float *W1, const float *Wc,
+                                const float *Wr, const float *hidden, float *dW1, float *db1, float *dWc, float *dbc,
+                                float *dWr, float *dbr, float *scratch, void *stream);
+int aabr_rpn_head_grouped_forward_bf16(const AabrRpnMap *maps_host, int n_maps, int C, int A, int G, const float *W1,
+                                       const float *b1, const float *Wc, const float *bc, const float *Wr,
+                                       const float *br, float *hidden, void *stream);
+int aabr_rpn_head_grouped_backward_bf16(const AabrRpnMap *maps_host, int n_maps, int C, int A, int G, const float *W1,
+                                        const float *Wc, const float *Wr, const float *hidden, float *dW1, float *db1,
+                                        float *dWc, float *dbc, float *dWr, float *dbr, float *scratch, void *stream);
 
 /* ---- the optimizer step (csrc/solver.hip, csrc/solver_segs.h): torch.optim.SGD with momentum and weight decay
  * (dampening 0, no Nesterov form) over all parameters of one flat fp32 buffer in ONE launch.  Per element, fp32, each
