@@ -22,7 +22,9 @@ does not do: change any number -- `tests/test_gpu_fpn.py` holds it bit-equal to 
 (returns None) when a module of the graph carries hooks or is of a type it does not know."""
 import ctypes
 import functools
+import os
 import threading
+from collections import namedtuple
 
 import torch
 from torch.autograd import Function
@@ -49,19 +51,14 @@ BF16 = torch.bfloat16
 stats = {"passes": 0, "fallbacks": 0, "templates": 0}
 # weight gradients on the library's second stream (nothing later in a backward list reads them): they fill the CUs
 # the tails and small launches of the input-gradient chain leave idle
-import os  # noqa: E402
 dw_side_stream = os.environ.get("AABR_PLAN_DW_SIDE", "1") != "0"
-# the lateral 1x1x1 convolutions of the FPN (they read a down-path map long before the up path needs them) can go
-# there too (AABR_PLAN_JOIN in front of their reader); measured on the bench step: 14.65 -> 14.60 ms, inside the
-# noise, so off by default
-lateral_side_stream = os.environ.get("AABR_PLAN_LATERAL_SIDE", "0") != "0"
 # a residual / lateral add whose second operand comes straight from a wide-kernel convolution rides in that
 # convolution's write-out (forward only; the backward list is unchanged)
 fuse_adds = os.environ.get("AABR_PLAN_FUSE_ADDS", "1") != "0"
-# a training-mode BatchNorm right behind a wide-kernel convolution takes its statistics' partial sums from that
-# convolution's write-out (aabr_conv_forward_wide_stats -> aabr_bn_forward_parts): one pass over the matrix less
 # ... the same in bf16 storage (round 6; forward adds, and the gradient sums of the backward list)
 fuse_adds_bf16 = os.environ.get("AABR_PLAN_FUSE_ADDS_BF16", "1") != "0"
+# a training-mode BatchNorm right behind a wide-kernel convolution takes its statistics' partial sums from that
+# convolution's write-out (aabr_conv_forward_wide_stats -> aabr_bn_forward_parts): one pass over the matrix less
 conv_bn_stats = os.environ.get("AABR_PLAN_CONV_BN_STATS", "1") != "0"
 # ... and a BatchNorm backward right behind the wide-kernel input-gradient launch that produced its d_out takes its
 # statistics from that launch's write-out (aabr_conv_forward_wide[_bf16]_bwd_stats -> aabr_bn_backward_parts[_bf16])
@@ -93,15 +90,15 @@ def set_plan_tail(v):
 
 def unconsumed_ops(fops, outs):
     """indices of the forward ops from which no returned buffer is reachable: walking the list backwards, an op is
-    needed when a returned buffer or a needed op reads what it writes.  `fops`: the template's op tuples (("add", a, b,
-    out, ..) / (kind, in, out, ..)); `outs`: [(buffer, ..)] of the returned maps.  A rule over the dataflow, not over
-    level numbers."""
-    need = {o[0] for o in outs}
+    needed when a returned buffer or a needed op reads what it writes.  `fops`: the template's forward op records (`Add`,
+    `Cast`, `Bn`, `Conv`: `.ins` / `.out`); `outs`: [(buffer, ..)] of the returned maps.  A rule over the dataflow, not
+    over level numbers."""
+    need = {b for b, _ in outs}
     dead = set()
     for i in range(len(fops) - 1, -1, -1):
         op = fops[i]
-        if _out_of(op) in need:
-            need.update((op[1], op[2]) if op[0] == "add" else (op[1],))
+        if op.out in need:
+            need.update(op.ins)
         else:
             dead.add(i)
     return frozenset(dead)
@@ -173,8 +170,69 @@ def _dp(t):
     return t.data_ptr() if t is not None else 0
 
 
+def _bf(dt):
+    """the storage flag of a record over matrices of type `dt`"""
+    return F_BF16 if dt == BF16 else 0
+
+
+def _bytes(fbuf, V):
+    """bytes the [rows(level), planes] matrix of a buffer (level, planes, dtype) takes in an arena, padding included"""
+    lvl, planes, dt = fbuf
+    return (V[lvl] * planes * _es(dt) + _ALIGN - 1) // _ALIGN * _ALIGN
+
+
+def _view(arena, o, fbuf, V):
+    """the [rows(level), planes] matrix of a buffer (level, planes, dtype) at byte offset `o` of `arena`"""
+    lvl, planes, dt = fbuf
+    return arena[o:o + V[lvl] * planes * _es(dt)].view(dt).view(V[lvl], planes)
+
+
+def _slot_floats(p):
+    """floats of parameter `p`'s slot in a pass's gradient buffer: padded, so that every slot starts 256-byte aligned"""
+    return (p.numel() + 63) // 64 * 64
+
+
 # buffer references inside a backward list: (space, index); spaces resolved to address lists per pass
 F, G, E = 0, 1, 2      # forward arena (index 0 = the graph input) / gradient arena / external output gradients
+
+
+# ---- The ops of a template: tuples with named fields, `kind` first; the loops over a list unpack a whole op in one
+# statement, everything else goes by field name.  A forward op (`_Template.fops`) answers `.ins`, the buffers it reads,
+# and `.out`, the buffer it writes: indices into `_Template.fbufs` (levels: into `_Template.levels`).
+def _forward_op(name, fields, ins):
+    reads = property(lambda op: tuple(getattr(op, f) for f in ins), doc="the buffers the op reads")
+    return type(name, (namedtuple(name, fields),), {"__slots__": (), "ins": reads})
+
+
+# "add": out = a + b, in this order (utils._sum_features), over [rows(lvl), planes] matrices; flags: F_BF16 in bf16 storage.
+# The backward list holds `Add` and `Cast` too, with (space, index) references in their buffer fields.
+Add = _forward_op("Add", "kind a b out lvl planes flags", ins=("a", "b"))
+# "cast": flags F_TO_BF16 = fp32 -> bf16, 0 = bf16 -> fp32
+Cast = _forward_op("Cast", "kind x out lvl planes flags", ins=("x",))
+# "bn": BatchNorm + LeakyReLU.  flags: F_BF16; train: 1 = batch statistics, 0 = the running ones; stat: float offset of
+# save_mean in the pass's statistics buffer, save_invstd follows at + planes; running_mean .. bias: addresses, 0 = none
+Bn = _forward_op("Bn", "kind x out lvl planes flags train eps momentum leak stat running_mean running_var weight bias "
+                 "module", ins=("x",))
+# "conv": submanifold, strided or transposed.  lvl / lvl_out: level of x / of out; book: index into `_Template.books` and
+# `_Pass.books`; side_fwd: the side of the book that gathers for the forward launch (0 = out, 1 = inn: Deconvolution);
+# weight, pack_fwd, pack_t: addresses of the raw weight, its forward pack and its transposed pack (input gradient);
+# side_din, din_flags: the input-gradient launch's side of the book and convolution flags; side_dw: the weight gradient's
+Conv = _forward_op("Conv", "kind x out lvl lvl_out n_in n_out book side_fwd weight pack_fwd side_din din_flags side_dw "
+                   "pack_t module", ins=("x",))
+
+# ---- backward ops (`_Template._make_backward`): gx, gy, res and tmp are (space, index) references
+# "bn": x, y: forward buffer indices of the BatchNorm's input and output; stat: as `Bn.stat`; weight, bias: addresses, 0 =
+# not affine; d_weight_slot, d_bias_slot: byte offsets into the pass's parameter-gradient buffer, -1 = no gradient wanted;
+# res: None, or the gradient that has arrived at x so far (the apply pass then writes gx = d_in + res)
+BnBwd = namedtuple("BnBwd", "kind x gx y gy lvl planes flags leak stat weight d_weight_slot d_bias_slot bias res")
+# "din": the input gradient of a convolution, a forward-form launch of its own that reads d_out and writes d_in -- so
+# lvl_in / lvl_out and n_in / n_out are the forward op's lvl_out / lvl and n_out / n_in.  side, conv_flags: the forward
+# op's side_din, din_flags; flags: F_BF16; res: as `BnBwd.res`, rides in a wide launch's write-out; tmp (with res): a spare
+# buffer for d_in when the launch is not a wide one (then gx = res + tmp); one_rule: `_one_rule(module, True)`
+Din = namedtuple("Din", "kind gy gx lvl_in lvl_out n_in n_out book side conv_flags weight pack_t flags res tmp one_rule")
+# "dw": the weight gradient of a convolution.  x: forward buffer index of its input; lvl_out: the rows of gy; n_in, n_out,
+# book: as the forward op's; side: its side_dw; slot: byte offset of the gradient in the parameter-gradient buffer
+Dw = namedtuple("Dw", "kind x gy lvl_out n_in n_out book side slot flags")
 
 
 class _Template(object):
@@ -193,7 +251,6 @@ class _Template(object):
         self.hidden = []                     # (level, planes) of every convolution output (hidden-state counter)
         self.macs = []                       # (book, weight) per convolution, in order
         self.bns = []
-        self.branches = []
         self.packs = {id(w): (pf.data_ptr(), pt.data_ptr()) for w, (pf, pt) in zip(plan.weights, plan.packs)}
         self.lib = _hip.load()
         x = (self._new(self._level(x_spatial), x_planes, torch.float32), x_spatial)
@@ -202,33 +259,33 @@ class _Template(object):
         self.n_rpn = len(rpn)
         self.outs = [self.cast(t, torch.float32) for t in rpn] + [self.cast(t, torch.float32) for t in roi]
         self._bwd = {}
-        # forward emission order: a lateral branch (ops that depend on one earlier buffer only) is issued right after
-        # that buffer's producer, on the second stream; its first reader joins
-        self.emit = self._emission()
-        self.fuse = self._fusable_adds() if (fuse_adds and not lateral_side_stream) else {}
+        self.fuse = self._fusable_adds() if fuse_adds else {}
         self.stat_claims = self._stat_claims()
         # the tail form of the list (a training pass with `plan_tail`): consumed records first, then the unconsumed ones
-        self.dead = unconsumed_ops(self.fops, self.outs) if not lateral_side_stream else frozenset()
+        self.dead = unconsumed_ops(self.fops, self.outs)
         self.emit_tail = tail_emission(self.fops, self.dead) if self.dead else None
         self.cross = self._cross_claims() if self.dead else {}
         stats["templates"] += 1
+
+    def _next_on_stream(self, i):
+        """the record behind forward op `i` on its stream in the one-stream list, the add that rides in op i's own
+        write-out aside; None behind the last"""
+        fz = self.fuse.get(id(self.fops[i]))
+        return next((nop for nop in self.fops[i + 1:] if fz is None or nop is not fz[0]), None)
 
     def _stat_claims(self):
         """ids of the convolution ops whose write-out a training-mode BatchNorm may ask for its statistics (`_Pass._forward`):
         the next record on the convolution's stream -- its own fused add aside -- is that BatchNorm, reading what the
         launch writes"""
         out = set()
-        for i, (op, xf) in enumerate(self.emit):
-            if op[0] != "conv":
+        for i, op in enumerate(self.fops):
+            if op.kind != "conv":
                 continue
             fz = self.fuse.get(id(op))
-            wrote = (op[2],) if fz is None else (op[2], fz[0][3])
-            for nop, nxf in self.emit[i + 1:]:
-                if (nxf ^ xf) & F_SIDE or (fz is not None and nop is fz[0]):
-                    continue
-                if nop[0] == "bn" and nop[6] and nop[4] == op[6] and nop[1] in wrote:
-                    out.add(id(op))
-                break
+            wrote = (op.out,) if fz is None else (op.out, fz[0].out)
+            nop = self._next_on_stream(i)
+            if nop is not None and nop.kind == "bn" and nop.train and nop.planes == op.n_out and nop.x in wrote:
+                out.add(id(op))
         return out
 
     def _cross_claims(self):
@@ -238,16 +295,12 @@ class _Template(object):
         buffer of the pair's own, and the BatchNorm record on the tail reads them there: the bits of the one-stream list."""
         idx = {id(op): i for i, op in enumerate(self.fops)}
         out = {}
-        for i, (op, xf) in enumerate(self.emit):
-            if id(op) not in self.stat_claims or idx[id(op)] in self.dead:
+        for i, op in enumerate(self.fops):
+            if id(op) not in self.stat_claims or i in self.dead:
                 continue
-            fz = self.fuse.get(id(op))
-            for nop, nxf in self.emit[i + 1:]:
-                if (nxf ^ xf) & F_SIDE or (fz is not None and nop is fz[0]):
-                    continue
-                if idx[id(nop)] in self.dead:
-                    out[id(nop)] = id(op)
-                break
+            nop = self._next_on_stream(i)        # the BatchNorm of the claim
+            if idx[id(nop)] in self.dead:
+                out[id(nop)] = id(op)
         return out
 
     def _fusable_adds(self):
@@ -258,47 +311,21 @@ class _Template(object):
         value before the sum exactly as the separate add would have read it)"""
         uses, prod = {}, {0: -1}
         for i, op in enumerate(self.fops):
-            ins = (op[1], op[2]) if op[0] == "add" else (op[1],)
-            for b in ins:
+            for b in op.ins:
                 uses[b] = uses.get(b, 0) + 1
-            prod[_out_of(op)] = i
+            prod[op.out] = i
         for b, _ in self.outs:
             uses[b] = uses.get(b, 0) + 1
         out = {}
-        for i, op in enumerate(self.fops):
-            if op[0] != "add" or (op[6] and not fuse_adds_bf16):
+        for op in self.fops:
+            if op.kind != "add" or (op.flags and not fuse_adds_bf16):
                 continue
-            for conv_b, other in ((op[2], op[1]), (op[1], op[2])):
+            for conv_b, other in ((op.b, op.a), (op.a, op.b)):
                 j = prod.get(conv_b, -1)
-                if j >= 0 and self.fops[j][0] == "conv" and uses.get(conv_b) == 1 and prod.get(other, 1 << 30) < j \
+                if j >= 0 and self.fops[j].kind == "conv" and uses.get(conv_b) == 1 and prod.get(other, 1 << 30) < j \
                         and id(self.fops[j]) not in out:
                     out[id(self.fops[j])] = (op, other)
                     break
-        return out
-
-    def branch(self, start, after_buf):
-        """ops fops[start:] so far form a branch that reads only `after_buf`; the NEXT op traced is its reader"""
-        self.branches.append((start, len(self.fops), after_buf))
-
-    def _emission(self):
-        order = [(i, 0) for i in range(len(self.fops))]
-        if not (lateral_side_stream and self.branches):
-            return [(self.fops[i], f) for i, f in order]
-        moved, joins, after = set(), set(), {}
-        for start, end, buf in self.branches:
-            prod = [i for i, op in enumerate(self.fops) if _out_of(op) == buf]
-            if len(prod) != 1 or prod[0] >= start or end >= len(self.fops):
-                continue
-            moved.update(range(start, end))
-            joins.add(end)
-            after.setdefault(prod[0], []).extend(range(start, end))
-        out = []
-        for i in range(len(self.fops)):
-            if i in moved:
-                continue
-            out.append((self.fops[i], F_JOIN if i in joins else 0))
-            for j in after.get(i, ()):
-                out.append((self.fops[j], F_SIDE))
         return out
 
     # ---- bookkeeping -------------------------------------------------------------------------------------------
@@ -365,7 +392,7 @@ class _Template(object):
             lvl, planes, dt = self.fbufs[acc[0]]
             assert self.fbufs[t[0]] == (lvl, planes, dt) and t[1] == acc[1]
             y = self._new(lvl, planes, dt)
-            self.fops.append(("add", acc[0], t[0], y, lvl, planes, F_BF16 if dt == BF16 else 0))
+            self.fops.append(Add("add", acc[0], t[0], y, lvl, planes, _bf(dt)))
             acc = (y, acc[1])
         return acc
 
@@ -374,7 +401,7 @@ class _Template(object):
         if dt == dtype:
             return x
         y = self._new(lvl, planes, dtype)
-        self.fops.append(("cast", x[0], y, lvl, planes, F_TO_BF16 if dtype == BF16 else 0))
+        self.fops.append(Cast("cast", x[0], y, lvl, planes, F_TO_BF16 if dtype == BF16 else 0))
         return (y, x[1])
 
     def bn(self, m, x):
@@ -393,9 +420,8 @@ class _Template(object):
         self.bns.append(m)
         self.bn_floats = max(self.bn_floats, int(self.lib.aabr_bn_scratch_floats(planes)))
         self.max_planes = max(self.max_planes, planes)
-        self.fops.append(("bn", x[0], y, lvl, planes, F_BF16 if dt == BF16 else 0, 1 if m.training else 0,
-                          float(m.eps), float(m.momentum), float(m.leakiness), st, _dp(m.running_mean),
-                          _dp(m.running_var), _dp(w), _dp(b), m))
+        self.fops.append(Bn("bn", x[0], y, lvl, planes, _bf(dt), 1 if m.training else 0, float(m.eps), float(m.momentum),
+                            float(m.leakiness), st, _dp(m.running_mean), _dp(m.running_var), _dp(w), _dp(b), m))
         return (y, x[1])
 
     def _conv_common(self, m, x, out_spatial, book, side_fwd, side_din, din_flags, side_dw):
@@ -412,8 +438,8 @@ class _Template(object):
         self.macs.append((book, w))
         self.hidden.append((lo, m.nOut))
         pf, pt = self.packs[id(w)]
-        self.fops.append(("conv", x[0], y, lvl, lo, m.nIn, m.nOut, book, side_fwd, w.data_ptr(), pf,
-                          side_din, din_flags, side_dw, pt, m))
+        self.fops.append(Conv("conv", x[0], y, lvl, lo, m.nIn, m.nOut, book, side_fwd, w.data_ptr(), pf,
+                              side_din, din_flags, side_dw, pt, m))
         return (y, out_spatial)
 
     def subm(self, m, x):
@@ -445,92 +471,97 @@ class _Template(object):
     def _make_backward(self, pattern, need_dx):
         gbufs, ops = [], []
         poff, ptotal = {}, 0
+        filled = [0]       # filled[i]: floats of the parameter-gradient buffer that are final once ops[:i] have run
+
+        def put(op):
+            ops.append(op)
+            filled.append(ptotal)
 
         def gnew(lvl, planes, dt):
             gbufs.append((lvl, planes, dt))
             return (G, len(gbufs) - 1)
 
         def pslot(p):
+            """byte offset of p's gradient slot; slots are laid out in the order their records appear"""
             nonlocal ptotal
             i = self.pidx[id(p)]
             if i not in poff:
                 poff[i] = ptotal
-                ptotal += (p.numel() + 63) // 64 * 64
+                ptotal += _slot_floats(p)
             return poff[i] * 4
 
         acc = {}           # forward buffer -> the gradient accumulated so far (contributions in arrival order:
                            # autograd's order, the consumer created last delivers first; ((c0 + c1) + c2) ...)
 
-        def arrive(b, ref):
-            """an existing gradient buffer contributes to forward buffer b"""
+        def arrive(b, ref, summed=False):
+            """an existing gradient buffer contributes to forward buffer b (`summed`: the launch that wrote it has
+            already added what had arrived so far)"""
             cur = acc.get(b)
-            if cur is None:
+            if cur is None or summed:
                 acc[b] = ref
                 return
             lvl, planes, dt = self.fbufs[b]
             s = gnew(lvl, planes, dt)
-            ops.append(("add", cur, ref, s, lvl, planes, F_BF16 if dt == BF16 else 0))
+            put(Add("add", cur, ref, s, lvl, planes, _bf(dt)))
             acc[b] = s
+
+        def riding(x, flg):
+            """the gradient that has arrived at forward buffer x so far, when the launch that produces the next
+            contribution can add it in its write-out (the backward side of `fuse_adds`); else None"""
+            return acc.get(x) if (fuse_adds and (not flg or fuse_adds_bf16)) else None
 
         for k, ((b, _), has) in enumerate(zip(self.outs, pattern)):
             if has:
                 arrive(b, (E, k))
-        total = acc.get
-        fuse = fuse_adds
 
         for op in reversed(self.fops):
-            kind = op[0]
+            gy = acc.get(op.out)
+            if gy is None:               # no incoming gradient depends on what this op wrote
+                continue
+            kind = op.kind
             if kind == "add":
                 _, a_, b_, y, lvl, planes, flg = op
-                gy = total(y)
-                if gy is not None:       # same order as autograd's AddBackward: first operand, then second
-                    arrive(a_, gy)
-                    arrive(b_, gy)
+                arrive(a_, gy)           # same order as autograd's AddBackward: first operand, then second
+                arrive(b_, gy)
             elif kind == "cast":
                 _, x, y, lvl, planes, flg = op
-                gy = total(y)
-                if gy is None:
-                    continue
                 dtx = self.fbufs[x][2]
                 gx = gnew(lvl, planes, dtx)
-                ops.append(("cast", gy, gx, lvl, planes, F_TO_BF16 if dtx == BF16 else 0))
+                put(Cast("cast", gy, gx, lvl, planes, F_TO_BF16 if dtx == BF16 else 0))
                 arrive(x, gx)
             elif kind == "bn":
                 _, x, y, lvl, planes, flg, train, eps, mom, leak, st, p_rm, p_rv, p_w, p_b, m = op
-                gy = total(y)
-                if gy is None:
-                    continue
                 gx = gnew(lvl, planes, self.fbufs[x][2])
                 pw = pslot(m.weight) if m.affine and m.weight.requires_grad else -1
                 pb = pslot(m.bias) if m.affine and m.bias.requires_grad else -1
-                res = acc.get(x) if (fuse and (not flg or fuse_adds_bf16)) else None
-                ops.append(("bn", x, gx, y, gy, lvl, planes, flg, leak, st, p_w, pw, pb, p_b, res))
-                if res is not None:      # the sum with what has arrived so far rides in the apply pass
-                    acc[x] = gx
-                else:
-                    arrive(x, gx)
+                res = riding(x, flg)     # the sum with what has arrived so far rides in the apply pass
+                put(BnBwd("bn", x, gx, y, gy, lvl, planes, flg, leak, st, p_w, pw, pb, p_b, res))
+                arrive(x, gx, res is not None)
             else:
                 _, x, y, lvl, lo, n_in, n_out, book, side_fwd, p_w, pf, side_din, din_flags, side_dw, pt, m = op
-                gy = total(y)
-                if gy is None:
-                    continue
                 dt = self.fbufs[x][2]
-                flg = F_BF16 if dt == BF16 else 0
+                flg = _bf(dt)
                 if x != 0 or need_dx:
                     gx = gnew(lvl, n_in, dt)
-                    res = acc.get(x) if (fuse and (not flg or fuse_adds_bf16)) else None
+                    res = riding(x, flg)
                     tmp = gnew(lvl, n_in, dt) if res is not None else None   # used when the launch is not a wide one
                     # the launch reads d_out (n_out planes) and writes d_in (n_in planes)
-                    ops.append(("din", gy, gx, lo, lvl, n_out, n_in, book, side_din, din_flags, p_w, pt, flg, res,
-                                tmp, _one_rule(m, True)))
-                    if res is not None:
-                        acc[x] = gx
-                    else:
-                        arrive(x, gx)
+                    put(Din("din", gy, gx, lo, lvl, n_out, n_in, book, side_din, din_flags, p_w, pt, flg, res, tmp,
+                            _one_rule(m, True)))
+                    arrive(x, gx, res is not None)
                 if m.weight.requires_grad:
-                    ops.append(("dw", x, gy, lo, n_in, n_out, book, side_dw, pslot(m.weight), flg))
-        gx0 = total(0) if need_dx else None
-        return {"gbufs": gbufs, "ops": ops, "poff": poff, "ptotal": ptotal, "gx0": gx0}
+                    put(Dw("dw", x, gy, lo, n_in, n_out, book, side_dw, pslot(m.weight), flg))
+        # input-gradient records whose write-out a BatchNorm backward record may ask for its statistics: the next record,
+        # weight gradients aside, is that BatchNorm, reading their d_in
+        claimed = set()
+        for i, op in enumerate(ops):
+            if op.kind == "din":
+                nxt = next((o for o in ops[i + 1:] if o.kind != "dw"), None)
+                if nxt is not None and nxt.kind == "bn" and nxt.gy == op.gx and nxt.planes == op.n_out:
+                    claimed.add(i)
+        gx0 = acc.get(0) if need_dx else None
+        return {"gbufs": gbufs, "ops": ops, "poff": poff, "ptotal": ptotal, "gx0": gx0, "filled": filled,
+                "claimed": claimed}
 
 
 def _one_rule(m, din):
@@ -547,17 +578,12 @@ def _one_rule(m, din):
     return 0
 
 
-def _out_of(op):
-    return op[3] if op[0] == "add" else op[2]
-
-
 def _offsets(bufs, V, first=0):
     """arena offsets of [rows(level), planes] matrices; bufs[:first] are not in the arena"""
     offs, total = [0] * len(bufs), 0
     for i in range(first, len(bufs)):
-        lvl, planes, dt = bufs[i]
         offs[i] = total
-        total += (V[lvl] * planes * (2 if dt == BF16 else 4) + _ALIGN - 1) // _ALIGN * _ALIGN
+        total += _bytes(bufs[i], V)
     return offs, total
 
 
@@ -607,12 +633,12 @@ class _Pass(object):
         """(route, fused add or None) of a forward convolution record: `SCN.single_route` first where the module's rule
         book has one rule per output row, then `SCN.conv_route`; the add behind the convolution rides in the write-out
         when the route takes a residual"""
-        x, y, lvl, lo, n_in, n_out, book, side = op[1:9]
+        _, x, y, lvl, lo, n_in, n_out, book, side, p_w, pf, side_din, din_flags, side_dw, pt, m = op
         t, V = self.t, self.V
         fz = t.fuse.get(id(op))
         g, bfx = self.books[book][side], t.fbufs[x][2] == BF16
         r = None
-        if _one_rule(op[15], False) == 1:
+        if _one_rule(m, False) == 1:
             r = self.single(n_in, n_out, V[lvl], V[lo], g.vol, bfx, conv_bn_stats and id(op) in t.stat_claims)
         if r is None and fz is not None:
             r = self.route(n_in, n_out, V[lvl], V[lo], g.vol, bfx, residual=True)
@@ -650,38 +676,37 @@ class _Pass(object):
                          src, dst, route.stream(gather).data_ptr(), p3, 0, wpack, scratch)
         return off + R.SIZE, route.stats_parts(rows_out) if (narrow_stats or route.kind != "narrow") else 0
 
-    def _live_offsets(self):
+    def _records(self, emit):
+        """[(op, record flags, route, fused add)]: the records of a forward list, in the order of `emit`.  The one round
+        of route decisions of a pass: a convolution gets its `fwd_route`; an add that rides in its convolution's
+        write-out is not a record, the convolution writes the add's buffer (the add is the convolution's only reader and
+        stands behind it in every emission order)."""
+        out, skip = [], set()
+        for op, xf in emit:
+            if op.kind == "conv":
+                r, fz = self.fwd_route(op)
+                if fz is not None:
+                    skip.add(id(fz[0]))
+                out.append((op, xf, r, fz))
+            elif id(op) not in skip:
+                out.append((op, xf, None, None))
+        return out
+
+    def _live_offsets(self, records):
         """arena offsets for a pass nobody will differentiate (torch.no_grad): a buffer's bytes are handed on once its
         last reader has been recorded -- first fit over a free list, in record order (one stream) -- instead of every
         activation of the network living until the pass object dies.  Returns (offsets, total, total without reuse)."""
         t, V = self.t, self.V
-        fbufs, books, fuse = t.fbufs, self.books, t.fuse
-        steps, skip = [], set()            # (buffers read, buffer written) per emitted record
-        for op, xf in t.emit:
-            if xf & F_SIDE:
-                return None
-            kind = op[0]
-            if kind == "conv":
-                x, y = op[1:3]
-                fz = self.fwd_route(op)[1]
-                if fz is not None:
-                    add_op, other = fz
-                    skip.add(id(add_op))
-                    steps.append(((x, other), add_op[3]))
-                else:
-                    steps.append(((x,), y))
-            elif kind == "add":
-                if id(op) not in skip:
-                    steps.append(((op[1], op[2]), op[3]))
-            else:
-                steps.append(((op[1],), op[2]))
+        fbufs = t.fbufs
+        # (buffers read, buffer written) per record
+        steps = [(op.ins, op.out) if fz is None else ((op.x, fz[1]), fz[0].out) for op, _, _, fz in records]
         last = {}
         for i, (rd, _) in enumerate(steps):
             for b in rd:
                 last[b] = i
         for b, _ in t.outs:
             last[b] = len(steps)
-        size = lambda b: (V[fbufs[b][0]] * fbufs[b][1] * _es(fbufs[b][2]) + _ALIGN - 1) // _ALIGN * _ALIGN
+        size = lambda b: _bytes(fbufs[b], V)
         offs, free, top = [0] * len(fbufs), [], 0      # free: [offset, bytes], sorted by offset
         dying = {}
         for b, i in last.items():
@@ -730,12 +755,12 @@ class _Pass(object):
         # the tail: one slot per activation (nothing of the arena is handed on) and one call per list (the launcher
         # thread has nobody to hand a ticket to)
         use_tail = bool(tail and keep and plan_tail and t.emit_tail is not None and not pipeline_records)
-        packed = None if keep else self._live_offsets()
-        if packed is not None:
-            offs, total, flat = packed
-            stats["arena_bytes_packed"], stats["arena_bytes_flat"] = total, flat
-        else:
+        records = self._records(t.emit_tail if use_tail else [(op, 0) for op in t.fops])
+        if keep:
             offs, total = _offsets(t.fbufs, V, 1)
+        else:
+            offs, total, flat = self._live_offsets(records)
+            stats["arena_bytes_packed"], stats["arena_bytes_flat"] = total, flat
         self.arena = torch.empty(max(total, 1), dtype=torch.uint8, device=self.dev)
         self.stat = torch.empty(max(t.stat_floats, 1), dtype=torch.float32, device=self.dev)
         base, sbase = self.arena.data_ptr(), self.stat.data_ptr()
@@ -750,17 +775,15 @@ class _Pass(object):
         buf = bytearray(len(t.fops) * SZ)
         stats_patch, stats_at = R.CONV_STATS
         books = self.books
-        fbufs = t.fbufs
-        fuse, skip = t.fuse, set()
         # BatchNorm statistics from the producing convolution's write-out: a training-mode BatchNorm that is the NEXT
         # record on its stream after the k_conv_cs launch that wrote its input gets the per-tile partial sums from
         # that launch (record p6 -> BatchNorm p9) and skips its own statistics pass over the matrix
-        last = {0: None, F_SIDE: None, F_TAIL: None}   # per stream: (buffer index written, record offset, parts, planes)
+        last = {0: None, F_TAIL: None}     # per stream: (buffer index written, record offset, parts, planes)
         cstat = {}
         cross = t.cross if use_tail else {}
         cross_convs, xlast = set(cross.values()), {}
         part, start, strm = pipeline_records * SZ, 0, stream()
-        for op, xf in (t.emit_tail if use_tail else t.emit):
+        for op, xf, r, fz in records:
             if part and off - start >= part:
                 # records up to `safe` are final (a convolution record stays open while the BatchNorm behind it may
                 # still claim its write-out for the statistics)
@@ -768,19 +791,15 @@ class _Pass(object):
                 for lw in last.values():
                     if lw is not None and lw[1] < safe:
                         safe = lw[1]
-                if safe > start:
-                    check(self.lib.aabr_plan_submit(bytes(buf[start:safe]), (safe - start) // SZ, strm, 1))
-                    start = safe
-            kind = op[0]
-            sk = xf & (F_SIDE | F_TAIL)
+                start = self._submit(buf, start, safe, strm)
+            kind = op.kind
+            sk = xf & F_TAIL
             if kind == "conv":
-                x, y, lvl, lo, n_in, n_out, book, side, p_w, pf = op[1:11]
+                _, x, y, lvl, lo, n_in, n_out, book, side, p_w, pf, side_din, din_flags, side_dw, pt, m = op
                 g, off0, res = books[book][side], off, 0
-                r, fz = self.fwd_route(op)
                 if fz is not None:
                     add_op, other = fz           # out = conv + other, written where the add would have written
-                    skip.add(id(add_op))
-                    y, res = add_op[3], A[other]
+                    y, res = add_op.out, A[other]
                 off, nparts = self.conv_launch(r, buf, off, A[x], V[lvl], n_in, A[y], V[lo], n_out, g, p_w, pf, 0,
                                                xf, res)
                 last[sk] = (y, off0, nparts, n_out) if nparts else None
@@ -804,11 +823,9 @@ class _Pass(object):
                         stats_patch.pack_into(buf, lw[1] + stats_at, ws)      # the convolution record's `stats`
                     R.BN_FWD.pack_into(buf, off, K_BNF, flg | xf, planes, train, nparts, eps, mom, leak, V[lvl], A[x], A[y],
                                        sbase + st * 4, sbase + (st + planes) * 4, p_rm, p_rv, p_w, p_b,
-                                       bnws_tail if sk & F_TAIL else bnws, parts)
+                                       bnws_tail if sk else bnws, parts)
                     off += SZ
             elif kind == "add":
-                if id(op) in skip:
-                    continue
                 _, a_, b_, y, lvl, planes, flg = op
                 R.ADD.pack_into(buf, off, K_ADD, flg | xf, V[lvl] * planes, A[a_], A[b_], A[y])
                 off += SZ
@@ -819,9 +836,8 @@ class _Pass(object):
             last[sk] = None
         if debug_kinds is not None:
             debug_kinds.append(("fwd", R.kinds(buf, off)))
-        if part:
-            check(self.lib.aabr_plan_submit(bytes(buf[start:off]), (off - start) // SZ, strm, 0))
-            check(self.lib.aabr_plan_drain())      # everything issued: the caller's next launches queue behind the pass
+        if part:                                   # everything issued: the caller's next launches queue behind the pass
+            self._submit_last(buf, start, off, strm)
         elif off and use_tail:
             ticket = ctypes.c_uint64(0)
             self._strm = strm
@@ -832,31 +848,29 @@ class _Pass(object):
                     _tails.append(self)
         elif off:
             check(self.lib.aabr_plan_run(bytes(buf[:off]), off // SZ, strm))
-        res = []
-        for b, _ in t.outs:
-            lvl, planes, dt = fbufs[b]
-            n = V[lvl] * planes * _es(dt)
-            res.append(self.arena[offs[b]:offs[b] + n].view(dt).view(V[lvl], planes))
-        return res
+        return [_view(self.arena, offs[b], t.fbufs[b], V) for b, _ in t.outs]
+
+    def _submit(self, buf, start, safe, strm):
+        """hand records [start, safe) of `buf` (byte offsets), which are final, to the launcher thread, more to come;
+        returns where the next part starts"""
+        if safe <= start:
+            return start
+        check(self.lib.aabr_plan_submit(bytes(buf[start:safe]), (safe - start) // R.SIZE, strm, 1))
+        return safe
+
+    def _submit_last(self, buf, start, off, strm):
+        """hand the last part [start, off) of a list to the launcher thread and wait until it has issued everything"""
+        check(self.lib.aabr_plan_submit(bytes(buf[start:off]), (off - start) // R.SIZE, strm, 0))
+        check(self.lib.aabr_plan_drain())
 
     def buffer(self, b):
         """forward buffer `b` of this pass as a tensor view into the arena (tests)"""
         self.join_tail()                   # an unconsumed stage's buffer is written on the tail stream
-        lvl, planes, dt = self.t.fbufs[b]
-        n = self.V[lvl] * planes * _es(dt)
-        return self.arena[self.offs[b]:self.offs[b] + n].view(dt).view(self.V[lvl], planes)
+        return _view(self.arena, self.offs[b], self.t.fbufs[b], self.V)
 
     def bn_outputs(self):
         """{BatchNorm module: its output matrix of this pass} (tests: the compiled graph runs no module hooks)"""
-        return {op[-1]: self.buffer(op[2]) for op in self.t.fops if op[0] == "bn" and self.V[op[3]]}
-
-    @staticmethod
-    def _pinv(bw, byte_off):
-        """parameter index of a gradient slot (byte offset into the pass's gradient buffer)"""
-        inv = bw.get("pinv")
-        if inv is None:
-            inv = bw["pinv"] = {o * 4: i for i, o in bw["poff"].items()}
-        return inv[byte_off]
+        return {op.module: self.buffer(op.out) for op in self.t.fops if op.kind == "bn" and self.V[op.lvl]}
 
     def backward(self, gouts, need_dx):
         try:
@@ -873,9 +887,11 @@ class _Pass(object):
         gbufs, bops = bw["gbufs"], bw["ops"]
         offs, total = _offsets(gbufs, V)
         garena = torch.empty(max(total, 1), dtype=torch.uint8, device=self.dev)
+        # pieces of the list for the data-parallel hook: cut after every len/S-th record; parameter gradients are laid
+        # out in the order their records appear (pslot), so the ones a piece completes form one slice of `gparams`
+        nseg = grad_segments if (grad_segments > 1 and on_grads_ready is not None) else 1
         # the data-parallel hook all-reduces slices of this buffer, 64-float padding between the slots included
-        hooked = grad_segments > 1 and on_grads_ready is not None
-        gparams = (torch.zeros if hooked else torch.empty)(max(bw["ptotal"], 1), dtype=torch.float32, device=self.dev)
+        gparams = (torch.zeros if nseg > 1 else torch.empty)(max(bw["ptotal"], 1), dtype=torch.float32, device=self.dev)
         gbase, pbase, sbase = garena.data_ptr(), gparams.data_ptr(), self.stat.data_ptr()
         AD = (A, [gbase + o for o in offs], [_dp(g) for g in gouts])
         for (b, _), g in zip(t.outs, gouts):
@@ -886,10 +902,10 @@ class _Pass(object):
         # weight-gradient scratch: the largest of the pass
         dws, dwmc = 0, []
         for op in bops:
-            if op[0] == "dw":
-                mc = books[op[6]][op[7]].max_chunks(op[4], op[5])
+            if op.kind == "dw":
+                mc = books[op.book][op.side].max_chunks(op.n_in, op.n_out)
                 dwmc.append(mc)
-                dws = max(dws, mc * op[4] * op[5])
+                dws = max(dws, mc * op.n_in * op.n_out)
         dwmc.reverse()
         dwws = _hip.workspace("dw", dws, torch.float32, self.dev).data_ptr() if dws else 0
         bnws = _hip.workspace("bn", t.bn_floats, torch.float32, self.dev).data_ptr() if t.bn_floats else 0
@@ -897,49 +913,42 @@ class _Pass(object):
         buf = bytearray((len(bops) * 2 + 1) * SZ)
         (flag_patch, flag_at), (bn_patch, bn_at) = R.CONV_BWD_STATS
         dw_side = F_SIDE if dw_side_stream else 0
-        # pieces of the list for the data-parallel hook: cut after every len/S-th record; parameter gradients are laid
-        # out in the order their records appear (pslot), so the ones a piece completes form one slice of `gparams`
-        nseg = grad_segments if (grad_segments > 1 and on_grads_ready is not None) else 1
         cut = [(len(bops) * (q + 1)) // nseg for q in range(nseg)] if nseg > 1 else []
         inv = sorted((o, i) for i, o in bw["poff"].items()) if nseg > 1 else []
-        done_floats, seg_no, next_inv = 0, 0, 0
-        claimed = bw.get("claimed")
-        if claimed is None:              # input-gradient records whose write-out a BatchNorm backward record may ask for
-            claimed = bw["claimed"] = set()   # its statistics: the next record, weight gradients aside, reads their d_in
-            for i, op in enumerate(bops):
-                if op[0] == "din":
-                    nxt = next((o for o in bops[i + 1:] if o[0] != "dw"), None)
-                    if nxt is not None and nxt[0] == "bn" and nxt[4] == op[2] and nxt[6] == op[6]:
-                        claimed.add(i)
+        seg_no, next_inv = 0, 0
+
+        def grad(i, o):
+            """the gradient of parameter i: its slot at float offset `o` of the pass's gradient buffer"""
+            return gparams[o:o + t.params[i].numel()].view_as(t.params[i])
+
+        def hand_over(piece, upto):
+            """the data-parallel hook receives, as piece `piece`, the parameters whose slots lie below float offset `upto`
+            and have not been handed over yet: final, since every record that writes below `upto` has been issued"""
+            nonlocal next_inv
+            pairs = []
+            while next_inv < len(inv) and inv[next_inv][0] < upto:
+                o, i = inv[next_inv]
+                pairs.append((t.params[i], grad(i, o)))
+                next_inv += 1
+            if pairs:
+                lo = pairs[0][1].data_ptr() - pbase
+                on_grads_ready(piece, nseg, gparams[lo // 4:upto], pairs)
+
+        claimed = bw["claimed"]          # input-gradient records a BatchNorm backward record may ask for its statistics
         last_din, bstat = None, None     # the last wide input-gradient record of the main stream / statistics workspace
         part, start, strm = (pipeline_records * SZ if nseg == 1 else 0), 0, stream()
         for op_no, op in enumerate(bops):
             if part and off - start >= part:
-                safe = last_din[1] if last_din is not None else off    # (that record may still get the statistics)
-                if safe > start:
-                    check(self.lib.aabr_plan_submit(bytes(buf[start:safe]), (safe - start) // SZ, strm, 1))
-                    start = safe
+                # (the last input-gradient record may still get the statistics)
+                start = self._submit(buf, start, last_din[1] if last_din is not None else off, strm)
             if nseg > 1 and seg_no < nseg - 1 and op_no == cut[seg_no]:
                 last_din = None          # its record has been handed over
                 if off:
                     check(self.lib.aabr_plan_run(bytes(buf[:off]), off // SZ, stream()))
                     off = 0
-                pairs = []
-                while next_inv < len(inv) and inv[next_inv][0] < done_floats:
-                    o, i = inv[next_inv]
-                    pairs.append((t.params[i], gparams[o:o + t.params[i].numel()].view_as(t.params[i])))
-                    next_inv += 1
-                if pairs:
-                    lo = pairs[0][1].data_ptr() - pbase
-                    on_grads_ready(seg_no, nseg, gparams[lo // 4:done_floats], pairs)
+                hand_over(seg_no, bw["filled"][op_no])
                 seg_no += 1
-            kind = op[0]
-            if kind == "dw":
-                done_floats = max(done_floats, op[8] // 4 + (t.params[self._pinv(bw, op[8])].numel() + 63) // 64 * 64)
-            elif kind == "bn":
-                for po in (op[11], op[12]):
-                    if po >= 0:
-                        done_floats = max(done_floats, po // 4 + (t.params[self._pinv(bw, po)].numel() + 63) // 64 * 64)
+            kind = op.kind
             if kind == "din":
                 _, gy, gx, lo, lvl, n_in, n_out, book, side, flags, p_w, pt, flg, res, tmp, one_rule = op
                 g = books[book][side]
@@ -1020,32 +1029,21 @@ class _Pass(object):
             R.TAIL_JOIN.pack_into(buf, off, K_TAIL_JOIN, 0, tk)
             off += SZ
         if part:
-            check(self.lib.aabr_plan_submit(bytes(buf[start:off]), (off - start) // SZ, strm, 0))
-            check(self.lib.aabr_plan_drain())
+            self._submit_last(buf, start, off, strm)
         elif off:
             check(self.lib.aabr_plan_run(bytes(buf[:off]), off // SZ, stream()))
         if tk:                            # enqueued on this stream by the record; `join_tail` covers the other cases
             self.join_tail()              # (pipelined backward, another stream than the forward's) and returns the ticket
         if nseg > 1:                      # the last piece's gradients
-            pairs = []
-            while next_inv < len(inv):
-                o, i = inv[next_inv]
-                pairs.append((t.params[i], gparams[o:o + t.params[i].numel()].view_as(t.params[i])))
-                next_inv += 1
-            if pairs:
-                lo = pairs[0][1].data_ptr() - pbase
-                on_grads_ready(nseg - 1, nseg, gparams[lo // 4:bw["ptotal"]], pairs)
+            hand_over(nseg - 1, bw["ptotal"])
         pgrad = [None] * len(t.params)
         for i, o in bw["poff"].items():
-            p = t.params[i]
-            pgrad[i] = gparams[o:o + p.numel()].view_as(p)
+            pgrad[i] = grad(i, o)
         dx = None
         gx0 = bw["gx0"]
         if gx0 is not None:
-            lvl, planes, dt = t.fbufs[0]
             if gx0[0] == G:
-                o = offs[gx0[1]]
-                dx = garena[o:o + V[lvl] * planes * _es(dt)].view(dt).view(V[lvl], planes)
+                dx = _view(garena, offs[gx0[1]], t.fbufs[0], V)
             else:   # the graph input reached an output untouched: its gradient is the incoming one
                 dx = gouts[gx0[1]]
         return dx, pgrad
@@ -1089,9 +1087,7 @@ def _fpn_graph(net, ps, x):
     for k in range(net._top_down_levels()):      # all n - 1 stages (the reference), or up to the last consumed map
         j = n - 1 - k - 1
         x = ps.run(net.m_ups[k], x)
-        mark = len(ps.fops)
         sc = ps.run(net.m_shortcuts[j], downs[j])
-        ps.branch(mark, downs[j][0])
         x = ps.add([x, sc])
         ups.append(ps.run(net.m_mergeds[k], x))
     rpn3d = [ups[i] for i in net.fpn_scales_from_top]

@@ -80,7 +80,7 @@ class _Rig(object):
     def buffers(self, ps):
         """every buffer of the pass's arena that a record writes: a convolution whose add rides in its write-out writes
         the add's buffer, and its own slot stays as the allocator left it"""
-        unwritten = {op[2] for op in ps.t.fops if op[0] == "conv" and ps.fwd_route(op)[1] is not None}
+        unwritten = {op.out for op in ps.t.fops if op.kind == "conv" and ps.fwd_route(op)[1] is not None}
         assert len(unwritten) < len(ps.t.fbufs) // 2
         return [ps.buffer(b).clone() for b in range(1, len(ps.t.fbufs)) if b not in unwritten]
 
@@ -91,7 +91,7 @@ class _Rig(object):
             assert r["in_flight"] == 0
             r["bufs"], r["running"] = self.buffers(r["ps"]), self.running()
             r["bn"] = {m: v.clone() for m, v in r["ps"].bn_outputs().items()}
-            r["dead_bn"] = [op[-1] for i, op in enumerate(r["ps"].t.fops) if op[0] == "bn" and i in r["ps"].t.dead]
+            r["dead_bn"] = [op.module for i, op in enumerate(r["ps"].t.fops) if op.kind == "bn" and i in r["ps"].t.dead]
             del r["ps"]
             self._ref = r
         return self._ref

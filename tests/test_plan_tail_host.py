@@ -16,17 +16,39 @@ def _pe():
     return planExecutor
 
 
-# hand-made op lists in the template's tuple form: (kind, in, out, ...) and ("add", a, b, out, ...); buffer 0 = the input
+# hand-made op lists of the template's own record types, the fields the dataflow rules do not read left empty; buffer 0 =
+# the input
+def _op(record, *head):
+    return record._make(head + (None,) * (len(record._fields) - len(head)))
+
+
 def _conv(x, y):
-    return ("conv", x, y)
+    return _op(_pe().Conv, "conv", x, y)
 
 
 def _bn(x, y):
-    return ("bn", x, y)
+    return _op(_pe().Bn, "bn", x, y)
 
 
 def _add(a, b, y):
-    return ("add", a, b, y)
+    return _op(_pe().Add, "add", a, b, y)
+
+
+# the test's own statement of what an op writes and reads, by tuple position: independent of the records' `.out` / `.ins`
+out_of = lambda op: op[3] if op[0] == "add" else op[2]
+ins_of = lambda op: (op[1], op[2]) if op[0] == "add" else (op[1],)
+
+
+def _reaches_an_output(ops, op, outs):
+    """the definition, by brute force: an op is consumed when some returned buffer is reachable from what it writes"""
+    reach, grew = {out_of(op)}, True
+    while grew:
+        grew = False
+        for o in ops:
+            if out_of(o) not in reach and reach & set(ins_of(o)):
+                reach.add(out_of(o))
+                grew = True
+    return bool(reach & set(outs))
 
 
 CASES = {
@@ -47,18 +69,8 @@ def test_unconsumed_ops_on_hand_made_lists(name):
     ops, outs, want = CASES[name]
     got = _pe().unconsumed_ops(ops, [(b, None) for b in outs])
     assert set(got) == want
-    # the definition, by brute force: an op is consumed when some returned buffer is reachable from what it writes
-    out_of = lambda op: op[3] if op[0] == "add" else op[2]
-    ins_of = lambda op: (op[1], op[2]) if op[0] == "add" else (op[1],)
     for i, op in enumerate(ops):
-        reach, grew = {out_of(op)}, True
-        while grew:
-            grew = False
-            for o in ops:
-                if out_of(o) not in reach and reach & set(ins_of(o)):
-                    reach.add(out_of(o))
-                    grew = True
-        assert (i in got) == (not (reach & set(outs))), (name, i)
+        assert (i in got) == (not _reaches_an_output(ops, op, outs)), (name, i)
 
 
 def test_tail_emission_is_a_stable_partition_that_keeps_fused_pairs_adjacent():
@@ -167,3 +179,90 @@ def test_a_list_without_side_or_tail_records_needs_no_device():
             assert lib.aabr_plan_run_tail(bytes(rec), 1, None, ctypes.byref(ticket)) == 0 and ticket.value == 0
         finally:
             assert lib.aabr_set_knob(b"PLAN_TAIL", 0, 1) == 0
+
+
+_templates = {}
+
+
+def _small_template(bf16):
+    """(network, its real `_Template`) for the small network of tests/test_ref_net_cpu.py in training mode, built without a
+    device: the template only asks the plan object for `weights` and `packs`"""
+    if bf16 not in _templates:
+        import torch
+        import sparseconvnet as scn
+        from sparseconvnet import SCN
+        torch.manual_seed(3)
+        dt = torch.bfloat16 if bf16 else torch.float32
+        net = scn.FPN_Net([64, 64, 16], 3, ["xyz", "color", "normal"], 1, [8, 8, 16], 8, True, [2, 1], [2, 1],
+                          [[[2, 2, 2]] * 2, [[2, 2, 2]] * 2], [[64, 64, 16], [32, 32, 8]], [0, 1, 2, 3], leakiness=0,
+                          voxel_scale=4, bn_momentum=0.95, feature_dtype=dt)
+        net.train(True)
+        plan = type("Plan", (), {})()
+        plan.weights = [m.weight for m in net.modules()
+                        if isinstance(m, (scn.SubmanifoldConvolution, scn.Convolution, scn.Deconvolution))]
+        plan.packs = [(torch.empty(1), torch.empty(1)) for _ in plan.weights]
+        tpl = _pe()._Template(net, SCN._key(net.layers_in[0].spatial_size), net.layers_in[1].nOut, dt, plan)
+        _templates[bf16] = (net, plan, tpl)
+    return _templates[bf16][0], _templates[bf16][2]
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
+def test_the_real_template_by_field_name(bf16):
+    """what the device runs imply about a template, asserted on the CPU through the records' field names"""
+    pe = _pe()
+    net, t = _small_template(bf16)
+    fops, outs = t.fops, [b for b, _ in t.outs]
+    kinds = {"add": pe.Add, "cast": pe.Cast, "bn": pe.Bn, "conv": pe.Conv}
+    assert all(type(op) is kinds[op.kind] for op in fops)
+    assert len(fops) == (39 if bf16 else 32) and {"add", "bn", "conv"} <= {op.kind for op in fops}
+    # every buffer but the graph input has exactly one producer; `.out` / `.ins` say what the positions say
+    assert sorted(op.out for op in fops) == list(range(1, len(t.fbufs)))
+    assert all(op.out == out_of(op) and tuple(op.ins) == ins_of(op) for op in fops)
+    # unconsumed ops: the brute-force definition on the real list, for the returned maps and for the first one alone
+    assert t.dead == pe.unconsumed_ops(fops, t.outs)
+    for some in (outs, outs[:1]):
+        got = pe.unconsumed_ops(fops, [(b, None) for b in some])
+        assert set(got) == {i for i, op in enumerate(fops) if not _reaches_an_output(fops, op, some)}
+    assert pe.unconsumed_ops(fops, [(outs[0], None)])        # (the second case is not an empty one)
+    # every fused add rides on a convolution whose only reader it is
+    at = {id(op): i for i, op in enumerate(fops)}
+    assert len(t.fuse) == 5
+    for conv_id, (add, other) in t.fuse.items():
+        conv = fops[at[conv_id]]
+        assert conv.kind == "conv" and add.kind == "add" and sorted(add.ins) == sorted((conv.out, other))
+        assert [op for op in fops if conv.out in op.ins] == [add] and conv.out not in outs
+        assert at[id(add)] > at[conv_id] and (other == 0 or other in [op.out for op in fops[:at[conv_id]]])
+    # every statistics claim: a convolution directly followed, its fused add aside, by a training BatchNorm that reads
+    # what the launch wrote, with the same plane count
+    assert len(t.stat_claims) == 8
+    for conv_id in t.stat_claims:
+        i = at[conv_id]
+        conv, wrote, nxt = fops[i], [fops[i].out], fops[i + 1]
+        if conv_id in t.fuse:
+            assert nxt is t.fuse[conv_id][0]
+            wrote, nxt = wrote + [nxt.out], fops[i + 2]
+        assert conv.kind == "conv" and nxt.kind == "bn" and nxt.train == 1 and nxt.x in wrote and nxt.planes == conv.n_out
+    assert not t.cross or set(t.cross.values()) <= t.stat_claims
+    # the all-gradients backward list: one slot per trainable parameter, a spare buffer wherever a sum may ride
+    assert t.params and all(p.requires_grad for p in t.params)
+    bw = t.backward(tuple(True for _ in outs), True)
+    bkinds = {"add": pe.Add, "cast": pe.Cast, "bn": pe.BnBwd, "din": pe.Din, "dw": pe.Dw}
+    assert all(type(op) is bkinds[op.kind] for op in bw["ops"])
+    slots = [op.slot for op in bw["ops"] if op.kind == "dw"]
+    slots += [s for op in bw["ops"] if op.kind == "bn" for s in (op.d_weight_slot, op.d_bias_slot) if s >= 0]
+    assert len(slots) == len(set(slots)) == len(t.params) and sorted(bw["poff"]) == list(range(len(t.params)))
+    assert sorted(slots) == sorted(4 * o for o in bw["poff"].values())
+    ends = sorted((o, o + t.params[i].numel()) for i, o in bw["poff"].items())
+    assert all(a[1] <= b[0] for a, b in zip(ends, ends[1:])) and ends[-1][1] <= bw["ptotal"]
+    dins = [op for op in bw["ops"] if op.kind == "din"]
+    assert len(dins) == 17 and any(op.res is not None for op in dins)
+    assert all((op.res is None) == (op.tmp is None) for op in dins)
+    assert all(op.tmp[0] == pe.G and op.tmp != op.gx for op in dins if op.tmp is not None)
+
+
+def test_no_numeric_subscript_of_an_op_in_the_executor():
+    """template ops are read by whole-op unpacking or by field name, never by position"""
+    import re
+    src = open(os.path.join(os.path.dirname(HERE), "automatic-as-built-reconstruction_amd", "sparseconvnet",
+                            "planExecutor.py")).read()
+    assert not re.findall(r"\b(op|nop|nxt|add_op)\[", src)
