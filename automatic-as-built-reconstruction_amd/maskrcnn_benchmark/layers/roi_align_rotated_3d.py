@@ -40,7 +40,7 @@ def _occupied_extent(input_s3d):
     import torch
     md = input_s3d.metadata
     key = tuple(int(v) for v in input_s3d.spatial_size.tolist())
-    cache = md.__dict__.setdefault("_roi_extent", {}) if hasattr(md, "__dict__") else {}
+    cache = md._roi_extent
     ext = cache.get(key)
     if ext is None:
         g = md.grids[key]
@@ -56,7 +56,7 @@ def _cellmap(input_s3d, ext):
     from _hip import ptr, stream, check
     md = input_s3d.metadata
     key = tuple(int(v) for v in input_s3d.spatial_size.tolist())
-    cache = md.__dict__.setdefault("_roi_cellmap", {})
+    cache = md._roi_cellmap
     cm = cache.get(key)
     if cm is None:
         g = md.grids[key]

@@ -11,10 +11,11 @@ runs on the current PyTorch HIP stream.
 """
 import collections
 import ctypes as C
+import os
+import struct as _struct
+import threading as _threading
 
 import torch
-
-import os
 
 import _hip
 from _hip import ptr, stream, check
@@ -166,13 +167,10 @@ def _key(t):
 # Same entry points, same arguments, same order on the same stream -- only the ~10 us of interpreter + ctypes time per
 # launch (x ~250 launches per FPN_Net pass) leave the host's critical path.
 # ------------------------------------------------------------------------------------------------
-import struct as _struct
-
 _GEOM = _struct.Struct("<ii10i4q8Q")
 assert _GEOM.size == 144
 G_SUBM, G_TABLES, G_TILE, G_WIDE, G_PAIRS, G_SITES, G_SOFF, G_BK_BUILD, G_BK_SUBM, G_BK_TABLES = \
     1, 2, 3, 4, 5, 7, 8, 9, 10, 11
-import threading as _threading
 
 
 class _GeomTLS(_threading.local):
@@ -301,13 +299,29 @@ def _brick_build(src_coords, vin_bound, vin_count_ptr, size, stride, out_sp, bk,
     return scratch
 
 
+def _brick_arena(bricks, device):
+    """ONE zeroed allocation (one fill) for the directory, the bricks and the scan's scratch (csrc/brick.hip's sizes) of every
+    `_Brick` in `bricks` (made with alloc=False): gives each its `level`, returns (arena, [scratch slice per brick])"""
+    lib = _hip.load()
+    spans, words = [], 0
+    for bk in bricks:
+        lw = 4 * (bk.nw + bk.nb_cap)
+        sw = (int(lib.aabr_brick_scratch_words(bk.nw, bk.nb_cap)) + 3) // 4 * 4
+        spans.append((words, lw, sw))
+        words += lw + sw
+    arena = torch.zeros(max(words, 4), dtype=torch.int32, device=device)
+    for bk, (o, lw, sw) in zip(bricks, spans):
+        bk.level = arena[o:o + lw]
+    return arena, [arena[o + lw:o + lw + sw] for o, lw, sw in spans]
+
+
 class _Grid(object):
     """one scale of the scene: site list + hash table (replaces SparseGrids, Metadata.h:24-34); with
     Metadata_3(site_order="brick") the hash table is replaced by a brick level (`brick`, keys None)"""
-    __slots__ = ("coords", "keys", "vals", "cap", "V", "batch_size", "sample_off", "brick")
+    __slots__ = ("coords", "keys", "cap", "V", "sample_off", "brick")
 
-    def __init__(self, coords, keys, vals, cap, V, sample_off=None, brick=None):
-        self.coords, self.keys, self.vals, self.cap, self.V = coords, keys, vals, cap, V
+    def __init__(self, coords, keys, cap, V, sample_off=None, brick=None):
+        self.coords, self.keys, self.cap, self.V = coords, keys, cap, V
         self.brick = brick
         # host list: first row of sample b (SparseGrid::ctr, Metadata.h:24-33) for b = 0 .. MAX_SAMPLES, or None
         # when the grid was built without the ride-along read
@@ -323,14 +337,13 @@ class _Grid(object):
 
 # voxel-scatter form (csrc/voxel_scatter.hip): 2 LDS-binned (default), 1 one atomic per point, 0 generic; AABR_SCATTER
 # overrides (the A/B of tools/tools_scatter_kernels.py); below SCATTER_MIN_POINTS the generic form's fewer launches win
-import os as _os
-scatter_variant = int(_os.environ.get("AABR_SCATTER", "2"))
-SCATTER_MIN_POINTS = int(_os.environ.get("AABR_SCATTER_MIN_POINTS", "32768"))
+scatter_variant = int(os.environ.get("AABR_SCATTER", "2"))
+SCATTER_MIN_POINTS = int(os.environ.get("AABR_SCATTER_MIN_POINTS", "32768"))
 scatter_stats = {"variant0": 0, "variant1": 0, "variant2": 0, "redone": 0, "brick": 0}
 # brick-major rows: the voxel scatter straight into the brick grid (csrc/brick.hip aabr_points_prepare / aabr_points_sites:
 # no hash table, no first-seen numbering); False (AABR_BRICK_SCATTER=0): the hash scatter above followed by a renumbering
 # (Metadata_3._brickify_input, the first round-5 form) -- kept for the A/B and as a second implementation to test against
-brick_scatter = _os.environ.get("AABR_BRICK_SCATTER", "1") != "0"
+brick_scatter = os.environ.get("AABR_BRICK_SCATTER", "1") != "0"
 
 # BLInputLayer mode -> mode of the voxel-scatter kernels.  The BL rule book is NOT the flat one's twin: inputLayerRules keeps
 # a site's FIRST point in mode 1 and its LAST in mode 2 (.front() / .back(), IOLayersRules.h:100-111; the kernels follow
@@ -344,6 +357,37 @@ def derived_cap(E):
     worst-case load 2/3, typical 0.15-0.35 (a level keeps a half to a sixth of the sites it is derived from).  Round 3
     used 2 E: every derived grid of a pass was as large as its base grid and was cleared every step."""
     return _hip.next_pow2(max(64, E + (E + 1) // 2))
+
+
+def _max_outputs(size, stride):
+    """output sites one input site can reach under a filter of `size` moved by `stride`"""
+    n = 1
+    for a, b in zip(size, stride):
+        n *= (a + b - 1) // b
+    return n
+
+
+def _derived_level(E, device):
+    """buffers of a derived hash level that receives at most E candidate keys, as aabr_convolution_sites and
+    aabr_full_convolution_sites (csrc/geometry.hip) take them: (keys, cap, scratch, out_coords) -- `cap` 16-byte
+    entries {key, first, val}, a scratch of E + 4 * ceil(max(E, 1) / 256) + 16 words, one site row per candidate key"""
+    cap = derived_cap(E)
+    nblk = (max(E, 1) + 255) // 256
+    keys = torch.empty(2 * cap, dtype=torch.int64, device=device)
+    scratch = torch.empty(E + 4 * nblk + 16, dtype=torch.int32, device=device)
+    out_coords = torch.empty((max(E, 1), 4), dtype=torch.int32, device=device)
+    return keys, cap, scratch, out_coords
+
+
+def _derived_level_now(sites, gi, fs, st, osz, E):
+    """launch at once the library's `sites` builder (aabr_convolution_sites or aabr_full_convolution_sites: same arguments)
+    of the hash level of at most E sites that `gi` reaches; (keys, cap, out_coords, meta): the read of meta[0] sizes the level"""
+    dev = gi.coords.device
+    keys, cap, scratch, out_coords = _derived_level(E, dev)
+    meta = torch.empty(_hip.META_WORDS, dtype=torch.int32, device=dev)
+    check(sites(ptr(gi.coords), gi.V, _hip.i32x3(fs), _hip.i32x3(st), _hip.i32x3(osz), ptr(keys), cap, ptr(scratch),
+                ptr(out_coords), ptr(meta), stream()))
+    return keys, cap, out_coords, meta
 
 
 kMaxSpatial = 65535  # largest spatial size per axis (coordinates <= 65534: csrc/common.h kMaxCoord)
@@ -484,7 +528,68 @@ class _Table(object):
         return float(sum(self.rule_counts()))
 
 
+def _strided_book(gi, go, fs, st, clip):
+    """rule book of a Convolution (filter `fs`, stride `st`, output coordinates clipped to `clip`) from level `gi` onto
+    level `go`: the two tables and their count arrays, filled by the hash or the brick table builder through `_geom`
+    (recorded inside a geom_plan block, launched at once outside)"""
+    vol = fs[0] * fs[1] * fs[2]
+    dev = gi.coords.device
+    t_out = torch.empty((vol, go.V), dtype=torch.int32, device=dev)
+    t_in = torch.empty((vol, gi.V), dtype=torch.int32, device=dev)
+    counts = torch.empty(vol * ((go.V + 255) // 256), dtype=torch.int32, device=dev)
+    counts_in = torch.empty(vol * ((gi.V + 255) // 256), dtype=torch.int32, device=dev)
+    if gi.brick is not None:
+        _geom(G_BK_TABLES, fs + st + clip, (gi.V, go.V, gi.brick.packed, go.brick.packed),
+              (_p(gi.coords), gi.brick.level.data_ptr(), _p(go.coords), go.brick.level.data_ptr(), _p(t_out), _p(t_in),
+               _p(counts), _p(counts_in)))
+    else:
+        _geom(G_TABLES, fs + st + clip, (gi.V, gi.cap, go.V, go.cap),
+              (_p(gi.coords), _p(gi.keys), _p(go.coords), _p(go.keys), _p(t_out), _p(t_in), _p(counts), _p(counts_in)))
+    return _Table(_Gather(t_out, counts, vol, go.V), _Gather(t_in, counts_in, vol, gi.V), vol, go.V, gi.V)
+
+
+def _empty_book(vol, device):
+    """the rule book between two empty levels: vol x 0 tables, no counts"""
+    side = lambda: _Gather(torch.empty((vol, 0), dtype=torch.int32, device=device),
+                           torch.empty(0, dtype=torch.int32, device=device), vol, 0)
+    return _Table(side(), side(), vol, 0, 0)
+
+
+def _carve(names, device, unpadded=(), tail=0):
+    """ONE int32 allocation carved into the pieces `names` = [(name, words)], in that order: each piece starts where the
+    one before it ends rounded up to 16 bytes -- not rounded after a piece named in `unpadded` -- and `tail` words follow
+    the last.  Returns (buffer, {name: piece}, {name: offset in words})."""
+    offs, tot = {}, 0
+    for name, sz in names:
+        offs[name] = tot
+        tot += sz if name in unpadded else (sz + 3) & ~3
+    buf = torch.empty(tot + tail, dtype=torch.int32, device=device)
+    return buf, {name: buf[offs[name]:offs[name] + sz] for name, sz in names}, offs
+
+
 _pinned_pool = []  # (pinned int32[META_WORDS], event) pairs of finished asynchronous read-backs
+
+
+def _post_meta(meta):
+    """enqueue the asynchronous read-back of an input layer's meta block: pinned buffer + event from a small recycling
+    pool (allocating pinned memory per scene costs more than the whole enqueue)"""
+    host, ev = _pinned_pool.pop() if _pinned_pool else (
+        torch.empty(_hip.META_WORDS, dtype=torch.int32, pin_memory=True), torch.cuda.Event())
+    host.copy_(meta, non_blocking=True)
+    ev.record()
+    return host, ev
+
+
+def _collect_meta(pend):
+    """host list of the meta block of a pending input layer: wait for the read-back `_post_meta` enqueued (its buffers
+    go back to the pool), or read it now when none was posted"""
+    if pend["event"] is None:
+        return _hip.read_back(pend["meta"])
+    pend["event"].synchronize()
+    m = pend["host"].tolist()
+    if len(_pinned_pool) < 16:
+        _pinned_pool.append((pend["host"], pend["event"]))
+    return m
 
 
 class Metadata_3(object):
@@ -500,20 +605,43 @@ class Metadata_3(object):
         exact) over hash grids; "brick" = every level numbered brick by brick (csrc/brick.hip): the same sites, rule
         books and features up to a per-sample permutation of the rows, spatial neighbours adjacent in
         memory, no hash tables -- what FPN_Net(site_order="brick") / bench.py run on."""
+        self._handed_over = None    # (consumer stream, tensors) once hand_over() was called: lifetime, not content
         assert site_order in ("first_seen", "brick")
         self.site_order = site_order
+        self.input_spatial = None   # spatial size of the input level (setInputSpatialSize / the input layer); survives clear()
         self.clear()
 
     def clear(self):
-        self.grids = {}
-        self.submanifold = {}
-        self.rulebooks = {}
+        """Metadata::clear (Metadata.cpp:51-65): drop everything derived from an input; the input spatial size stays.
+        Every attribute of the object is assigned here or in __init__ -- nothing is created on first use."""
+        self.grids = {}                       # spatial size -> _Grid
+        self.submanifold = {}                 # spatial + filter -> _Table
+        self.rulebooks = {}                   # input spatial + filter + stride -> _Table
         self.fullConvolutionRuleBook = None   # the one rule book of the FullConvolution that created this object
         self._borrowed = set()                # spatial sizes whose level belongs to another Metadata (getFullConvolutionRuleBook)
         self.input = None  # dict(point_site, first_pt, cnt_extra, head, nxt, last_pt, meta, n, V, mode, spatial)
-        self.device = None
-        self._pregrids = set()
-        self._brick_rows, self._brick_nrows, self._brick_keep = None, 0, []
+        self.device = None                    # device of the input layer
+        self._inb = None                      # incremental input being collected on the host: dict(rows, locs, nsamples)
+        # input layer enqueued, not finished; ONE of two shapes: hash scatter dict(host, event, meta, buf, coords, site_coords,
+        # keys, cap, variant, redo), brick scatter dict(kind="brick", host, event, meta, buf, coords, piece, spatial_t, mode,
+        # device, bl)
+        self._pending = None
+        self._batch_size_cache = None         # number of samples (SCN._batch_size; a BL input layer knows it at once)
+        self._pregrids = set()                # spatial sizes of levels built ahead of the rule book that will claim them
+        self._brick_rows = None               # read-back block of the brick levels: one [V, sample offsets | meta] row each
+        self._brick_nrows = 0                 # rows of it in use
+        self._brick_rows_clean = False        # the unused rows are still zero (allocated zeroed): a pyramid need not fill them
+        self._brick_keep = []                 # device tensors of the brick levels that no _Grid holds (arenas, scratch, rows)
+        self._pyramid_pending = None          # (todo, made, first_row, posted read) of buildBrickPyramid(defer=True)
+        self._fpn_prebuilt = None             # FPN_Net.prebuild: the level sizes whose geometry is already built
+        self._defer_pyramid = False           # FPN_Net.prepare: the next pyramid's read is collected later
+        self._roi_extent = {}                 # spatial size -> occupied extent (roi_align_rotated_3d._occupied_extent)
+        self._roi_cellmap = {}                # spatial size -> cell map tensor (roi_align_rotated_3d._cellmap)
+
+    def _materialised(self):
+        """the device grid of an incremental input, if one is still being collected"""
+        if self._inb is not None:
+            self._materialise_input(torch.device("cuda", torch.cuda.current_device()))
 
     # ---- reference-visible queries ----------------------------------------------------
     def getSpatialLocations(self, spatial_size):
@@ -521,8 +649,7 @@ class Metadata_3(object):
         return self.getSpatialLocationsDevice(spatial_size).cpu()
 
     def getSpatialLocationsDevice(self, spatial_size):
-        if getattr(self, "_inb", None) is not None:
-            self._materialise_input(torch.device("cuda", torch.cuda.current_device()))
+        self._materialised()
         g = self.grids[_key(spatial_size)]
         loc = torch.empty((g.V, 4), dtype=torch.int64, device=g.coords.device)
         check(_hip.load().aabr_spatial_locations(ptr(g.coords), g.V, ptr(loc), stream()))
@@ -543,7 +670,7 @@ class Metadata_3(object):
         self._handed_over = (consumer, self.device_tensors())
 
     def __del__(self):
-        ho = getattr(self, "_handed_over", None)
+        ho = self._handed_over
         if ho is None:
             return
         try:
@@ -557,9 +684,8 @@ class Metadata_3(object):
     def device_tensors(self):
         """every device tensor this object owns (for cross-stream hand-over of geometry prepared ahead of time)"""
         ts = []
-        pend = getattr(self, "_pending", None)
-        if pend is not None:
-            ts += [pend["buf"]]
+        if self._pending is not None:
+            ts += [self._pending["buf"]]
         for g in self.grids.values():
             ts += [g.coords] + ([g.keys] if g.keys is not None else []) + (g.brick.tensors() if g.brick is not None else [])
         ts += list(self._brick_keep)
@@ -576,7 +702,7 @@ class Metadata_3(object):
         return ts
 
     def getNActive(self, spatial_size):
-        if getattr(self, "_inb", None) is not None and _key(spatial_size) == self.input_spatial:
+        if self._inb is not None and _key(spatial_size) == self.input_spatial:
             return len(self._inb["locs"])
         return self.grids[_key(spatial_size)].V
 
@@ -589,10 +715,14 @@ class Metadata_3(object):
     # before in the sample appends a row (first-seen numbering across all calls), a repeated one overwrites its row
     # or is ignored.  Same here, in Python (this is host bookkeeping in the reference too); the DEVICE grid of the
     # collected sites is built at the first geometry query (`_materialise_input`) through the voxel-scatter kernels.
+    def _collecting(self):
+        assert self.input_spatial is not None, "Call setInputSpatialSize first, please!"
+        if self._inb is None:
+            self._inb = dict(rows={}, locs=[], nsamples=0)
+        return self._inb
+
     def batchAddSample(self):
-        assert getattr(self, "input_spatial", None) is not None, "Call setInputSpatialSize first, please!"
-        b = self.__dict__.setdefault("_inb", dict(rows={}, locs=[], nsamples=0))
-        b["nsamples"] += 1
+        self._collecting()["nsamples"] += 1
 
     def _add_point(self, features, key, vec, overwrite, rows_out):
         b = self._inb
@@ -614,15 +744,14 @@ class Metadata_3(object):
             features[r] = vec
 
     def setInputSpatialLocation(self, features, location, vec, overwrite):
-        assert getattr(self, "_inb", None) and self._inb["nsamples"] > 0, "call batchAddSample first"
+        assert self._inb and self._inb["nsamples"] > 0, "call batchAddSample first"
         rows = []
         key = (self._inb["nsamples"] - 1,) + tuple(int(v) for v in location.tolist())
         self._add_point(features, key, vec, overwrite, rows)
         self._flush_rows(features, int(vec.shape[0]), rows)
 
     def setInputSpatialLocations(self, features, locations, vecs, overwrite):
-        assert getattr(self, "input_spatial", None) is not None, "Call setInputSpatialSize first, please!"
-        b = self.__dict__.setdefault("_inb", dict(rows={}, locs=[], nsamples=0))
+        b = self._collecting()
         L = locations.tolist()
         rows = []
         for i, loc in enumerate(L):
@@ -638,7 +767,7 @@ class Metadata_3(object):
     def _materialise_input(self, device):
         """device grid of the incrementally collected sites (unique by construction, sample-major like the
         reference's per-sample grids with their `ctr` offsets)"""
-        b = self.__dict__.pop("_inb", None)
+        b, self._inb = self._inb, None
         if b is None or self.input is not None:
             return
         order = sorted(range(len(b["locs"])), key=lambda i: (b["locs"][i][0], i))   # samples contiguous, first-seen inside
@@ -719,17 +848,14 @@ class Metadata_3(object):
                  ("head", n1), ("last_pt", n1), ("status", nst)]
         if variant:      # scratch of the packed forms: cap 8-byte words + one cursor per 4096-slot block
             names += [("words", 2 * cap), ("cursor", max(cap // 4096, 1))]
-        offs, tot = {}, 0
-        for name, sz in names:
-            offs[name] = tot
-            tot += (sz + 3) & ~3
-        buf = torch.empty(tot, dtype=torch.int32, device=device)
-        piece = {name: buf[offs[name]:offs[name] + sz] for name, sz in names}
+        buf, piece, offs = _carve(names, device)
         keys = piece["keys"].view(torch.int64)    # cap entries of 16 bytes: {uint64 key, uint32 first, int32 val}
-        vals, meta = None, piece["meta"]
+        meta = piece["meta"]
         site_coords = piece["site_coords"].view(n1, 4)
         base = buf.data_ptr()
         P = lambda name: base + 4 * offs[name]
+        generic = lambda: check(sites(P("keys"), cap, P("slot"), P("point_site"), P("site_coords"), P("first_pt"),
+                                      P("cnt_extra"), P("head"), P("nxt"), P("status"), P("meta"), stream()))
         host = ev = None
         if n > 0:
             if variant:
@@ -738,27 +864,22 @@ class Metadata_3(object):
                                                         P("first_pt"), P("cnt_extra"), P("head"), P("nxt"), P("status"),
                                                         P("meta"), stream()))
             else:
-                check(sites(P("keys"), cap, P("slot"), P("point_site"), P("site_coords"), P("first_pt"), P("cnt_extra"),
-                            P("head"), P("nxt"), P("status"), P("meta"), stream()))
+                generic()
             if asynchronous:
-                # pinned read-back buffer + event from a small recycling pool (allocating pinned memory
-                # per scene costs more than the whole enqueue)
-                host, ev = _pinned_pool.pop() if _pinned_pool else (
-                    torch.empty(_hip.META_WORDS, dtype=torch.int32, pin_memory=True), torch.cuda.Event())
-                host.copy_(meta, non_blocking=True)
-                ev.record()
+                host, ev = _post_meta(meta)
         else:  # empty scene: an empty grid (all keys EMPTY), nothing to launch
             keys.fill_(-1)
             meta.zero_()
-        self._pending = dict(host=host, event=ev, meta=meta, site_coords=site_coords, keys=keys, vals=vals,
-                             cap=cap, coords=coords, buf=buf, variant=variant,
-                             redo=(lambda: check(sites(
-                                 P("keys"), cap, P("slot"), P("point_site"), P("site_coords"),
-                                 P("first_pt"), P("cnt_extra"), P("head"), P("nxt"), P("status"), P("meta"), stream()))))
+        self._pending = dict(host=host, event=ev, meta=meta, site_coords=site_coords, keys=keys,
+                             cap=cap, coords=coords, buf=buf, variant=variant, redo=generic)
         scatter_stats["variant%d" % variant] += 1
+        self._set_input(piece, n, mode, spatial_size, coords_src, shape)
+
+    def _set_input(self, piece, n, mode, spatial_size, coords_src, bl):
+        """the input layer's record over the carved pieces of either scatter (`bl`: (B, L) of a padded batch, or None)"""
         self.input = dict(point_site=piece["point_site"], first_pt=piece["first_pt"], cnt_extra=piece["cnt_extra"],
-                          head=piece["head"], nxt=piece["nxt"], last_pt=piece["last_pt"], meta=meta, n=n, V=None,
-                          mode=int(mode), spatial=_key(spatial_size), coords_src=coords_src, bl=shape)
+                          head=piece["head"], nxt=piece["nxt"], last_pt=piece["last_pt"], meta=piece["meta"], n=n, V=None,
+                          mode=int(mode), spatial=_key(spatial_size), coords_src=coords_src, bl=bl)
 
     def _enqueue_brick_scatter(self, spatial_size, coords, coords_src, mode, device, asynchronous, bl=None):
         """brick-major rows WITHOUT a hash table (csrc/brick.hip "voxel scatter straight into a brick grid"): the points are
@@ -773,48 +894,29 @@ class Metadata_3(object):
             prepare = lambda *a: lib.aabr_points_prepare(ptr(coords), n, ncols, *a)
         names = [("pc", 4 * n), ("meta", _hip.META_WORDS), ("point_site", n), ("nxt", n), ("first_pt", n), ("head", n),
                  ("cnt_extra", n), ("last_pt", n)]
-        offs, tot = {}, 0
-        for name, sz in names:
-            offs[name] = tot
-            tot += (sz + 3) & ~3 if name != "first_pt" else sz          # first_pt | head contiguous: ONE fill for the two
-        buf = torch.empty(tot + 4, dtype=torch.int32, device=device)
-        piece = {name: buf[offs[name]:offs[name] + sz] for name, sz in names}
+        buf, piece, _ = _carve(names, device, unpadded=("first_pt",), tail=4)   # first_pt | head contiguous: ONE fill for the two
         meta = piece["meta"]
         # (the per-site arrays' starting values ride in this pass: aabr_points_sites(flags = 1) then fills nothing)
         check(prepare(piece["pc"].data_ptr(), meta.data_ptr(), ptr(piece["first_pt"]), ptr(piece["cnt_extra"]),
                       ptr(piece["head"]), stream()))
-        host = ev = None
-        if asynchronous:
-            host, ev = _pinned_pool.pop() if _pinned_pool else (
-                torch.empty(_hip.META_WORDS, dtype=torch.int32, pin_memory=True), torch.cuda.Event())
-            host.copy_(meta, non_blocking=True)
-            ev.record()
+        host, ev = _post_meta(meta) if asynchronous else (None, None)
         self._pending = dict(kind="brick", host=host, event=ev, meta=meta, coords=coords, buf=buf, piece=piece,
                              spatial_t=spatial_size, mode=mode, device=device, bl=bl)
         scatter_stats["brick"] = scatter_stats.get("brick", 0) + 1
-        self.input = dict(point_site=piece["point_site"], first_pt=piece["first_pt"], cnt_extra=piece["cnt_extra"],
-                          head=piece["head"], nxt=piece["nxt"], last_pt=piece["last_pt"], meta=meta, n=n, V=None,
-                          mode=int(mode), spatial=_key(spatial_size), coords_src=coords_src, bl=bl)
+        self._set_input(piece, n, mode, spatial_size, coords_src, bl)
 
     def _brick_scatter_launch(self, piece, n, key, extent, dev):
         """the launches of the brick-native scatter behind the extent read: input level from the points, then every point's
         row / first point / chain (no host read in here -- bench.py times exactly this)"""
         lib = _hip.load()
-        # the rows of every level's read-back block (sample offsets + meta) start at zero: ONE fill here covers the meta words
-        # of the input level and of the pyramid built later (round 5: a memset per level build + a fill per pyramid)
-        rows = self._brick_rows = torch.zeros((_BK_MAX_LEVELS, _BK_ROW), dtype=torch.int32, device=dev)
-        self._brick_rows_clean = True
-        self._brick_nrows = 1
-        bk = _Brick([e + 1 for e in extent[:3]], extent[3] + 1, n, n, dev, rows[0, 64:64 + _hip.META_WORDS], alloc=False)
+        # read-back rows allocated zeroed: ONE fill covers the meta words of the input level and of the pyramid built later
+        bk = _Brick([e + 1 for e in extent[:3]], extent[3] + 1, n, n, dev, self._new_brick_rows(dev, clean=True), alloc=False)
         # ONE allocation and ONE fill for the directory, the bricks and the scan's scratch (round 5: two memsets)
-        lw = 4 * (bk.nw + bk.nb_cap)
-        sw = (int(lib.aabr_brick_scratch_words(bk.nw, bk.nb_cap)) + 3) // 4 * 4
-        arena = torch.zeros(lw + sw, dtype=torch.int32, device=dev)
-        bk.level = arena[:lw]
+        _, (scratch,) = _brick_arena([bk], dev)
         # the level is clamped to the EXTENT of the points, not to the layer's spatial size: a coordinate beyond
         # spatial_size (<= 65534) is a site here as it is for the hash form and the reference's InputLayer
         out_sp = tuple(max(int(k), int(e) + 1) for k, e in zip(key, extent[:3]))
-        scratch = _brick_build(piece["pc"], n, 0, (1, 1, 1), (1, 1, 1), out_sp, bk, 1, arena[lw:])
+        _brick_build(piece["pc"], n, 0, (1, 1, 1), (1, 1, 1), out_sp, bk, 1, scratch)
         flush_geom()
         check(lib.aabr_points_sites(piece["pc"].data_ptr(), n, bk.dims_c(), bk.dir_ptr(), bk.bricks_ptr(),
                                     ptr(piece["point_site"]), ptr(piece["first_pt"]), ptr(piece["cnt_extra"]),
@@ -822,14 +924,7 @@ class Metadata_3(object):
         return bk, scratch
 
     def _finish_brick_scatter(self, pend):
-        lib = _hip.load()
-        if pend["event"] is not None:
-            pend["event"].synchronize()
-            m = pend["host"].tolist()
-            if len(_pinned_pool) < 16:
-                _pinned_pool.append((pend["host"], pend["event"]))
-        else:
-            m = _hip.read_back(pend["meta"])
+        m = _collect_meta(pend)
         self._pending = None
         il = self.input
         key, n, dev, piece = il["spatial"], il["n"], pend["device"], pend["piece"]
@@ -838,7 +933,7 @@ class Metadata_3(object):
         if il.get("bl") is not None and m[8] >= 0:
             m[11] = il.get("bl")[0] - 1                    # B samples, trailing empty ones included (flat form: the largest seen)
         if m[8] < 0:                                   # no valid point
-            self.grids[key] = _Grid(torch.empty((0, 4), dtype=torch.int32, device=dev), None, None, 0, 0)
+            self.grids[key] = _Grid(torch.empty((0, 4), dtype=torch.int32, device=dev), None, 0, 0)
             il["V"] = 0
             self.input_spatial = key
             return
@@ -860,29 +955,23 @@ class Metadata_3(object):
                                  "overflow (meta %s)" % (bm[:4],))
         V = bm[0]
         self._brick_keep = [pend["buf"], self._brick_rows, scratch]
-        self.grids[key] = _Grid(bk.coords_full[:V], None, None, 0, V, None, bk)
+        self.grids[key] = _Grid(bk.coords_full[:V], None, 0, V, None, bk)
         il["V"] = V
         self.input_spatial = key
 
     def inputLayerFinish(self):
         """wait for the read-back (the one host sync of the input layer: V sizes every later tensor)"""
-        pend = getattr(self, "_pending", None)
+        pend = self._pending
         if pend is not None and pend.get("kind") == "brick":
             self._finish_brick_scatter(pend)
             return self.input["V"]
         if pend is not None:
-            if pend["event"] is not None:
-                pend["event"].synchronize()
-                m = pend["host"].tolist()
-                if len(_pinned_pool) < 16:
-                    _pinned_pool.append((pend["host"], pend["event"]))
-            else:
-                m = pend["meta"].tolist()  # synchronous read-back
+            m = _collect_meta(pend)
             if pend["variant"] and m[5] == 0:
                 # a point did not fit the packed word (or a hash block overflowed): the generic form on the same buffers
                 scatter_stats["redone"] += 1
                 pend["redo"]()
-                m = pend["meta"].tolist()
+                m = _hip.read_back(pend["meta"])
             self._pending = None
             if m[2]:
                 raise _hip.AabrError("InputLayer: coordinates must lie in [0, 65534] (batch index too)")
@@ -898,7 +987,7 @@ class Metadata_3(object):
                 brick_stats["built"] += 1
                 self.grids[key] = self._brickify_input(pend, V, m[8:12])
             else:
-                self.grids[key] = _Grid(pend["site_coords"][:V], pend["keys"], pend["vals"], pend["cap"], V)
+                self.grids[key] = _Grid(pend["site_coords"][:V], pend["keys"], pend["cap"], V)
             self.input["V"] = V   # maxActive (meta[1]) is produced by the forward kernel: read lazily (max_active())
             self.input_spatial = key
         return self.input["V"]
@@ -915,9 +1004,8 @@ class Metadata_3(object):
         n = il["n"]
         ext = [e + 1 for e in extent[:3]]
         nsamples = extent[3] + 1
-        rows = self._brick_rows = torch.empty((_BK_MAX_LEVELS, _BK_ROW), dtype=torch.int32, device=dev)
-        self._brick_nrows = 1
-        bk = _Brick(ext, nsamples, V, V, dev, rows[0, 64:64 + _hip.META_WORDS])
+        # (rows NOT zeroed: `buildBrickPyramid` fills the ones it takes)
+        bk = _Brick(ext, nsamples, V, V, dev, self._new_brick_rows(dev, clean=False))
         old_coords = pend["site_coords"]
         out_sp = tuple(max(int(k), int(e)) for k, e in zip(il["spatial"], ext))       # see _brick_scatter_launch
         scratch = _brick_build(old_coords, V, 0, (1, 1, 1), (1, 1, 1), out_sp, bk)
@@ -931,9 +1019,16 @@ class Metadata_3(object):
                                       bk.meta.data_ptr(), stream()))
         il.update(point_site=ps2, first_pt=first2, cnt_extra=extra2, head=head2, new_of_old=new_of_old,
                   old_of_new=old_of_new)
-        self._brick_keep = [nb, rows, scratch]
-        g = _Grid(bk.coords_full[:V], None, None, 0, V, None, bk)
-        return g
+        self._brick_keep = [nb, self._brick_rows, scratch]
+        return _Grid(bk.coords_full[:V], None, 0, V, None, bk)
+
+    def _new_brick_rows(self, device, clean):
+        """allocate the read-back block of this object's brick levels (`clean`: zeroed, so that no later level has to fill
+        its row) and take row 0 for the level about to be built; returns that row's meta block"""
+        self._brick_rows = (torch.zeros if clean else torch.empty)((_BK_MAX_LEVELS, _BK_ROW), dtype=torch.int32,
+                                                                   device=device)
+        self._brick_nrows, self._brick_rows_clean = 1, clean
+        return self._brick_rows[0, 64:64 + _hip.META_WORDS]
 
     def _brick_read(self, post_only=False, posted=None):
         """ONE host read for every brick level enqueued since the last one: [V, per-sample offsets (64 words), meta (16)]
@@ -965,7 +1060,7 @@ class Metadata_3(object):
 
     def finishBrickPyramid(self):
         """collect a pyramid enqueued with `buildBrickPyramid(.., defer=True)` (no-op when there is none)"""
-        pend = self.__dict__.pop("_pyramid_pending", None)
+        pend, self._pyramid_pending = self._pyramid_pending, None
         if pend is not None:
             self._pyramid_collect(*pend)
 
@@ -978,7 +1073,6 @@ class Metadata_3(object):
         if not todo:
             return
         dev = self._brick_rows.device
-        lib = _hip.load()
         made = {}
         first_row = self._brick_nrows
         plan = []
@@ -986,29 +1080,20 @@ class Metadata_3(object):
             gs = made.get(src) or self.grids[src]
             bs = gs.brick
             ext = [min(o, (e - 1) // st_ + 1) for o, e, st_ in zip(osz, bs.ext, stride)]
-            maxout = 1
-            for a, b in zip(size, stride):
-                maxout *= (a + b - 1) // b
+            maxout = _max_outputs(size, stride)
             row = self._brick_rows[self._brick_nrows]
             self._brick_nrows += 1
             assert self._brick_nrows <= _BK_MAX_LEVELS
             bk = _Brick(ext, bs.dims[3], bs.nb_cap * maxout, bs.v_cap * maxout, dev, row[64:64 + _hip.META_WORDS], alloc=False)
-            made[osz] = _Grid(None, None, None, 0, None, None, bk)
+            made[osz] = _Grid(None, None, 0, None, None, bk)
             plan.append((osz, bs, size, stride, bk, row))
         # ONE allocation and ONE fill for the directories, bricks and scan scratch of all the levels built here
-        words, offs = 0, []
-        for osz, bs, size, stride, bk, row in plan:
-            lw = 4 * (bk.nw + bk.nb_cap)
-            sw = (int(lib.aabr_brick_scratch_words(bk.nw, bk.nb_cap)) + 3) // 4 * 4
-            offs.append((words, lw, sw))
-            words += lw + sw
-        arena = torch.zeros(max(words, 4), dtype=torch.int32, device=dev)
-        if not self.__dict__.get("_brick_rows_clean"):      # (rows allocated zeroed by the brick-native scatter: nothing to do)
+        arena, scratch = _brick_arena([p[4] for p in plan], dev)
+        if not self._brick_rows_clean:      # (rows allocated zeroed by the brick-native scatter: nothing to do)
             self._brick_rows[first_row:self._brick_nrows].zero_()
         self._brick_keep.append(arena)
-        for (osz, bs, size, stride, bk, row), (o, lw, sw) in zip(plan, offs):
-            bk.level = arena[o:o + lw]
-            _brick_build(bs.coords_full, bs.v_cap, bs.meta.data_ptr(), size, stride, osz, bk, 1, arena[o + lw:o + lw + sw])
+        for (osz, bs, size, stride, bk, row), scr in zip(plan, scratch):
+            _brick_build(bs.coords_full, bs.v_cap, bs.meta.data_ptr(), size, stride, osz, bk, 1, scr)
             _geom(G_SOFF, (MAX_SAMPLES + 1,), (bk.v_cap,), (_p(bk.coords_full), bk.meta.data_ptr(), row.data_ptr()))
         if defer:        # the levels are being built; the host collects their counts later (finishBrickPyramid)
             self._pyramid_pending = (todo, made, first_row, self._brick_read(post_only=True))
@@ -1016,8 +1101,7 @@ class Metadata_3(object):
         self._pyramid_collect(todo, made, first_row, None)
 
     def _pyramid_collect(self, todo, made, first_row, posted):
-        rows = self._brick_read(posted=posted) if posted is not None else self._brick_read()
-        pre = self.__dict__.setdefault("_pregrids", set())
+        rows = self._brick_read(posted=posted)
         for (osz, src, size, stride), r in zip(todo, rows[first_row:]):
             g = made[osz]
             V = r[0]
@@ -1025,15 +1109,14 @@ class Metadata_3(object):
             g.V, g.coords = V, g.brick.coords_full[:V]
             g.sample_off = off if off[-1] == V else None
             self.grids[osz] = g
-            pre.add(osz)
+            self._pregrids.add(osz)
 
     def getSubmanifoldRuleBook(self, spatial_size, filter_size):
         """Metadata::getSubmanifoldRuleBook (Metadata.cpp:429-443) -> cached gather table"""
         k = _key(spatial_size) + _key(filter_size)
         tb = self.submanifold.get(k)
         if tb is None:
-            if getattr(self, "_inb", None) is not None:
-                self._materialise_input(torch.device("cuda", torch.cuda.current_device()))
+            self._materialised()
             g = self.grids[_key(spatial_size)]
             fs = _key(filter_size)
             vol = fs[0] * fs[1] * fs[2]
@@ -1061,54 +1144,43 @@ class Metadata_3(object):
         level k is (x >> ..) of its level-0 sites and is numbered at its first level-0 site, which is also where the
         level-by-level construction numbers it: same site lists, same order (tests compare them with the oracle's).
         `getRuleBook` picks the grids up by their spatial size."""
-        lib = _hip.load()
         gi = self.grids[_key(in_spatial)]
         if gi.brick is not None:       # brick grids: each level from the round's base with the composed stride
             return self.buildBrickPyramid([(_key(o), _key(in_spatial), _key(c), _key(c)) for o, c in specs])
         dev = gi.keys.device
         E = gi.V
-        cap = derived_cap(E)
-        nblk = (max(E, 1) + 255) // 256
         metas = torch.empty((max(len(specs), 1), _hip.META_WORDS), dtype=torch.int32, device=dev)
         ext = torch.empty((max(len(specs), 1), MAX_SAMPLES + 3), dtype=torch.int32, device=dev)
         pend = []
         for i, (osz, comp) in enumerate(specs):
             osz, comp = _key(osz), _key(comp)
-            keys = torch.empty(2 * cap, dtype=torch.int64, device=dev)   # cap 16-byte entries {key, first, val}
-            vals = None
-            scratch = torch.empty(E + 4 * nblk + 16, dtype=torch.int32, device=dev)
-            out_coords = torch.empty((max(E, 1), 4), dtype=torch.int32, device=dev)
+            keys, cap, scratch, out_coords = _derived_level(E, dev)
             _geom(G_SITES, comp + comp + osz, (gi.V, cap),
                   (_p(gi.coords), _p(keys), _p(scratch), _p(out_coords), metas[i].data_ptr()))
             # V and the per-sample row offsets (SparseGrid::ctr) of the new grid into one row of `ext`
             _geom(G_SOFF, (MAX_SAMPLES + 1,), (max(E, 1),), (_p(out_coords), metas[i].data_ptr(), ext[i].data_ptr()))
             _keep(scratch)
-            pend.append((osz, out_coords, keys, vals))
+            pend.append((osz, out_coords, keys, cap))
         if not pend:
             return
         _keep(metas)
         flush_geom()
         rows = ext[:len(pend)].tolist()  # the one host sync: site counts + per-sample offsets of every grid
-        pre = self.__dict__.setdefault("_pregrids", set())
-        for (osz, out_coords, keys, vals), row in zip(pend, rows):
+        for (osz, out_coords, keys, cap), row in zip(pend, rows):
             V_out = row[0]
             off = row[1:]
-            self.grids[osz] = _Grid(out_coords[:V_out], keys, vals, cap, V_out,
+            self.grids[osz] = _Grid(out_coords[:V_out], keys, cap, V_out,
                                     off if off[-1] == V_out else None)   # more than MAX_SAMPLES samples: no list
-            pre.add(osz)
+            self._pregrids.add(osz)
 
     def getRuleBook(self, in_spatial, out_spatial, filter_size, filter_stride):
         """Metadata::getRuleBook (Metadata.cpp:484-510): builds the output grid on first use."""
         k = _key(in_spatial) + _key(filter_size) + _key(filter_stride)
         tb = self.rulebooks.get(k)
         if tb is None:
-            lib = _hip.load()
-            if getattr(self, "_inb", None) is not None:
-                self._materialise_input(torch.device("cuda", torch.cuda.current_device()))
+            self._materialised()
             gi = self.grids[_key(in_spatial)]
             fs, st, osz = _key(filter_size), _key(filter_stride), _key(out_spatial)
-            dev = gi.coords.device
-            vol = fs[0] * fs[1] * fs[2]
             if osz in self._borrowed and osz != _key(in_spatial):
                 # the input level a FullConvolution shared with this object: a convolution onto that spatial size reaches
                 # other sites than the level holds, and builds its own (the reference clears and rebuilds it too,
@@ -1116,17 +1188,14 @@ class Metadata_3(object):
                 self._borrowed.discard(osz)
                 del self.grids[osz]
             have = self.grids.get(osz)
-            if gi.brick is not None and gi.V > 0 and osz not in self.__dict__.get("_pregrids", ()) and \
+            if gi.brick is not None and gi.V > 0 and osz not in self._pregrids and \
                     not (have is not None and have.brick is not None):
                 self.buildBrickPyramid([(osz, _key(in_spatial), fs, st)])       # (one host read)
             elif self.site_order == "brick" and gi.V == 0:                      # an empty level under an empty level
-                self.grids[osz] = _Grid(gi.coords[:0], None, None, 0, 0)
-                e = lambda r: torch.empty((vol, 0), dtype=torch.int32, device=dev)
-                tb = _Table(_Gather(e(0), torch.empty(0, dtype=torch.int32, device=dev), vol, 0),
-                            _Gather(e(0), torch.empty(0, dtype=torch.int32, device=dev), vol, 0), vol, 0, 0)
-                self.rulebooks[k] = tb
+                self.grids[osz] = _Grid(gi.coords[:0], None, 0, 0)
+                tb = self.rulebooks[k] = _empty_book(fs[0] * fs[1] * fs[2], gi.coords.device)
                 return tb
-            go = self.grids.get(osz) if osz in self.__dict__.get("_pregrids", ()) else None
+            go = self.grids.get(osz) if osz in self._pregrids else None
             if go is None and gi.brick is not None:
                 # brick order: an output level that already exists (a second rule book onto the same output size, with
                 # another filter or stride) is served from that level, as the reference serves it from its existing grid
@@ -1136,51 +1205,14 @@ class Metadata_3(object):
                 if go is None or go.brick is None:
                     raise RuntimeError("site_order='brick': no brick level for output size %r" % (osz,))
             if go is not None:         # built ahead by buildGridsFromInput / buildBrickPyramid
-                self.__dict__.setdefault("_pregrids", set()).discard(osz)
-                V_out = go.V
-                t_out = torch.empty((vol, V_out), dtype=torch.int32, device=dev)
-                t_in = torch.empty((vol, gi.V), dtype=torch.int32, device=dev)
-                counts = torch.empty(vol * ((V_out + 255) // 256), dtype=torch.int32, device=dev)
-                counts_in = torch.empty(vol * ((gi.V + 255) // 256), dtype=torch.int32, device=dev)
-                if gi.brick is not None:
-                    _geom(G_BK_TABLES, fs + st + osz, (gi.V, V_out, gi.brick.packed, go.brick.packed),
-                          (_p(gi.coords), gi.brick.level.data_ptr(), _p(go.coords), go.brick.level.data_ptr(), _p(t_out),
-                           _p(t_in), _p(counts), _p(counts_in)))
-                else:
-                    _geom(G_TABLES, fs + st + osz, (gi.V, gi.cap, V_out, go.cap),
-                          (_p(gi.coords), _p(gi.keys), _p(go.coords), _p(go.keys), _p(t_out), _p(t_in), _p(counts),
-                           _p(counts_in)))
-                tb = _Table(_Gather(t_out, counts, vol, V_out), _Gather(t_in, counts_in, vol, gi.V), vol, V_out, gi.V)
-                self.rulebooks[k] = tb
-                return tb
-            flush_geom()           # the calls below launch (and read) right away
-            maxout = 1
-            for a, b in zip(fs, st):
-                maxout *= (a + b - 1) // b
-            E = gi.V * maxout
-            cap = derived_cap(E)
-            nblk = (max(E, 1) + 255) // 256
-            keys = torch.empty(2 * cap, dtype=torch.int64, device=dev)   # cap 16-byte entries {key, first, val}
-            vals = None
-            scratch = torch.empty(E + 4 * nblk + 16, dtype=torch.int32, device=dev)
-            out_coords = torch.empty((max(E, 1), 4), dtype=torch.int32, device=dev)
-            meta = torch.empty(_hip.META_WORDS, dtype=torch.int32, device=dev)
-            check(lib.aabr_convolution_sites(ptr(gi.coords), gi.V, _hip.i32x3(fs), _hip.i32x3(st),
-                                             _hip.i32x3(osz), ptr(keys), cap, ptr(scratch),
-                                             ptr(out_coords), ptr(meta), stream()))
-            V_out = meta.tolist()[0]  # host sync: sizes the output feature tensor
-            go = _Grid(out_coords[:V_out], keys, vals, cap, V_out)
-            self.grids[osz] = go
-            t_out = torch.empty((vol, V_out), dtype=torch.int32, device=dev)
-            t_in = torch.empty((vol, gi.V), dtype=torch.int32, device=dev)
-            counts = torch.empty(vol * ((V_out + 255) // 256), dtype=torch.int32, device=dev)
-            counts_in = torch.empty(vol * ((gi.V + 255) // 256), dtype=torch.int32, device=dev)
-            check(lib.aabr_convolution_tables2(ptr(gi.coords), gi.V, ptr(gi.keys), gi.cap,
-                                               ptr(go.coords), V_out, ptr(go.keys), go.cap,
-                                               _hip.i32x3(fs), _hip.i32x3(st), _hip.i32x3(osz), ptr(t_out),
-                                               ptr(t_in), ptr(counts), ptr(counts_in), stream()))
-            tb = _Table(_Gather(t_out, counts, vol, V_out), _Gather(t_in, counts_in, vol, gi.V), vol, V_out, gi.V)
-            self.rulebooks[k] = tb
+                self._pregrids.discard(osz)
+            else:                      # a hash level built now: the sites kernel and the host read of its site count
+                flush_geom()
+                keys, cap, out_coords, meta = _derived_level_now(_hip.load().aabr_convolution_sites, gi, fs, st, osz,
+                                                                 gi.V * _max_outputs(fs, st))
+                V_out = meta.tolist()[0]  # host sync: sizes the output feature tensor
+                go = self.grids[osz] = _Grid(out_coords[:V_out], keys, cap, V_out)
+            tb = self.rulebooks[k] = _strided_book(gi, go, fs, st, osz)
         return tb
 
     def getFullConvolutionRuleBook(self, in_spatial, out_spatial, filter_size, filter_stride, new_metadata):
@@ -1197,8 +1229,7 @@ class Metadata_3(object):
         if tb is not None:
             return tb
         lib = _hip.load()
-        if getattr(self, "_inb", None) is not None:
-            self._materialise_input(torch.device("cuda", torch.cuda.current_device()))
+        self._materialised()
         isz, osz, fs, st = _key(in_spatial), _key(out_spatial), _key(filter_size), _key(filter_stride)
         assert len(fs) == 3 and len(st) == 3, "dimension 3 only"
         if osz != tuple((i - 1) * s_ + f for i, f, s_ in zip(isz, fs, st)):
@@ -1218,82 +1249,49 @@ class Metadata_3(object):
         new_metadata.grids[isz] = gi     # (size 1 / stride 1: the new level below takes this key over, with the same rows)
         new_metadata._borrowed = {isz}   # not a level of its own making: getRuleBook does not build onto it
         big = (kMaxSpatial,) * 3         # the tables clip nothing: every site of the new level has its parent
-        empty = lambda rows: torch.empty((vol, rows), dtype=torch.int32, device=dev)
         if gi.V == 0:
-            new_metadata.grids[osz] = _Grid(gi.coords[:0], None, None, 0, 0) if gi.keys is None else \
+            new_metadata.grids[osz] = _Grid(gi.coords[:0], None, 0, 0) if gi.keys is None else \
                 self._full_hash_level(gi, fs, st, osz, 0)
-            z = lambda: torch.empty(0, dtype=torch.int32, device=dev)
-            tb = _Table(_Gather(empty(0), z(), vol, 0), _Gather(empty(0), z(), vol, 0), vol, 0, 0)
-            new_metadata.fullConvolutionRuleBook = tb
+            tb = new_metadata.fullConvolutionRuleBook = _empty_book(vol, dev)
             return tb
         if gi.brick is not None:
             bs = gi.brick
-            rows = new_metadata._brick_rows = torch.zeros((_BK_MAX_LEVELS, _BK_ROW), dtype=torch.int32, device=dev)
-            new_metadata._brick_rows_clean = True
-            new_metadata._brick_nrows = 1
             ext = [(e - 1) * s_ + f for e, f, s_ in zip(bs.ext, fs, st)]
             # bricks: bounded by the candidates, not by parent bricks * vol (a dilated 4^3 brick with size == stride == 2 touches
             # up to 27 bricks); _Brick clips both bounds to what the directory's extent can hold
-            bk = _Brick(ext, bs.dims[3], E, E, dev, rows[0, 64:64 + _hip.META_WORDS], alloc=False)
-            lw = 4 * (bk.nw + bk.nb_cap)
-            sw = (int(lib.aabr_brick_scratch_words(bk.nw, bk.nb_cap)) + 3) // 4 * 4
-            arena = torch.zeros(lw + sw, dtype=torch.int32, device=dev)       # ONE fill: directory, bricks, scan scratch
-            bk.level = arena[:lw]
+            bk = _Brick(ext, bs.dims[3], E, E, dev, new_metadata._new_brick_rows(dev, clean=True), alloc=False)
+            arena, (scratch,) = _brick_arena([bk], dev)                       # ONE fill: directory, bricks, scan scratch
             check(lib.aabr_brick_full_build(ptr(gi.coords), gi.V, None, _hip.i32x3(fs), _hip.i32x3(st), _hip.i32x3(osz),
                                             bk.dims_c(), bk.dir_ptr(), bk.bricks_ptr(), bk.nb_cap, bk.bcoord.data_ptr(),
                                             bk.coords_full.data_ptr(), bk.v_cap, bk.meta.data_ptr(),
-                                            arena[lw:].data_ptr(), 1, stream()))
+                                            scratch.data_ptr(), 1, stream()))
             bm = _hip.read_back(bk.meta)         # host sync: the site count sizes the output feature tensor
             if bm[2]:
                 raise _hip.AabrError("FullConvolution: a site outside the output spatial size %s, or a brick level "
                                      "overflow (meta %s)" % (osz, bm[:4]))
             V_new = bm[0]
-            new_metadata._brick_keep = [rows, arena]
-            go = _Grid(bk.coords_full[:V_new], None, None, 0, V_new, None, bk)
+            new_metadata._brick_keep = [new_metadata._brick_rows, arena]
+            go = _Grid(bk.coords_full[:V_new], None, 0, V_new, None, bk)
         else:
             go = self._full_hash_level(gi, fs, st, osz, E)
-            V_new = go.V
         new_metadata.grids[osz] = go
         new_metadata._borrowed.discard(osz)
-        t_out, t_in = empty(gi.V), empty(V_new)
-        counts = torch.empty(vol * ((gi.V + 255) // 256), dtype=torch.int32, device=dev)
-        counts_in = torch.empty(vol * ((V_new + 255) // 256), dtype=torch.int32, device=dev)
         # a Convolution's tables with the NEW level as the input side and this level as the output side
-        if gi.brick is not None:
-            check(lib.aabr_brick_convolution_tables(ptr(go.coords), V_new, go.brick.dims_c(), go.brick.dir_ptr(),
-                                                    go.brick.bricks_ptr(), ptr(gi.coords), gi.V, gi.brick.dims_c(),
-                                                    gi.brick.dir_ptr(), gi.brick.bricks_ptr(), _hip.i32x3(fs),
-                                                    _hip.i32x3(st), _hip.i32x3(big), ptr(t_out), ptr(t_in), ptr(counts),
-                                                    ptr(counts_in), stream()))
-        else:
-            check(lib.aabr_convolution_tables2(ptr(go.coords), V_new, ptr(go.keys), go.cap, ptr(gi.coords), gi.V,
-                                               ptr(gi.keys), gi.cap, _hip.i32x3(fs), _hip.i32x3(st), _hip.i32x3(big),
-                                               ptr(t_out), ptr(t_in), ptr(counts), ptr(counts_in), stream()))
-        tb = _Table(_Gather(t_out, counts, vol, gi.V), _Gather(t_in, counts_in, vol, V_new), vol, gi.V, V_new)
-        new_metadata.fullConvolutionRuleBook = tb
+        tb = new_metadata.fullConvolutionRuleBook = _strided_book(go, gi, fs, st, big)
         return tb
 
     @staticmethod
     def _full_hash_level(gi, fs, st, osz, E):
         """the hash grid of the level a FullConvolution grows to, numbered first-seen (aabr_full_convolution_sites); the
         one host read of its site count (none for an empty input level)"""
-        lib = _hip.load()
-        dev = gi.coords.device
-        cap = derived_cap(E)
-        nblk = (max(E, 1) + 255) // 256
-        keys = torch.empty(2 * cap, dtype=torch.int64, device=dev)   # cap 16-byte entries {key, first, val}
-        scratch = torch.empty(E + 4 * nblk + 16, dtype=torch.int32, device=dev)
-        out_coords = torch.empty((max(E, 1), 4), dtype=torch.int32, device=dev)
-        meta = torch.empty(_hip.META_WORDS, dtype=torch.int32, device=dev)
-        check(lib.aabr_full_convolution_sites(ptr(gi.coords), gi.V, _hip.i32x3(fs), _hip.i32x3(st), _hip.i32x3(osz),
-                                              ptr(keys), cap, ptr(scratch), ptr(out_coords), ptr(meta), stream()))
+        keys, cap, out_coords, meta = _derived_level_now(_hip.load().aabr_full_convolution_sites, gi, fs, st, osz, E)
         V_new = 0
         if E > 0:
             m = meta.tolist()            # host sync: sizes the output feature tensor
             if m[2]:
                 raise _hip.AabrError("FullConvolution: an input site reaches outside the output spatial size %s" % (osz,))
             V_new = m[0]
-        return _Grid(out_coords[:V_new], keys, None, cap, V_new)
+        return _Grid(out_coords[:V_new], keys, cap, V_new)
 
     # ---- reference-format views (tests / API parity) ------------------------------------------
     def max_active(self):
@@ -1988,7 +1986,7 @@ def BatchNormalization_backward(input_features, d_input_features, output_feature
 def _batch_size(metadata):
     """number of samples = size of the per-sample grid vector in the reference
     (`m.grids.begin()->second.size()`, SparseToDense.cpp:43); one small read-back, cached"""
-    bs = getattr(metadata, "_batch_size_cache", None)
+    bs = metadata._batch_size_cache
     if bs is None:
         g = metadata.grids[metadata.input_spatial]
         bs = int(g.coords[:, 3].max().item()) + 1 if g.V else 0
@@ -2102,8 +2100,7 @@ def AveragePooling_updateGradInput(inputSize, outputSize, poolSize, poolStride, 
 
 def _unpool_book(outputSize, inputSize, poolSize, poolStride, metadata):
     """the book (fine, coarse, size, stride) an UnPooling from the coarse level `inputSize` reads; the fine level must exist"""
-    if getattr(metadata, "_inb", None) is not None:
-        metadata._materialise_input(torch.device("cuda", torch.cuda.current_device()))
+    metadata._materialised()
     if _key(outputSize) not in metadata.grids:
         raise RuntimeError("UnPooling: the metadata holds no level of spatial size %s to unpool onto (UnPooling returns to "
                            "a level that a pooling or a strided convolution has come from)" % (list(_key(outputSize)),))

@@ -163,7 +163,7 @@ class FPN_Net(torch.nn.Module):
         Same rule books, same cache keys (Metadata caches by (spatial, filter[, stride])): the layers find them."""
         from . import SCN
         md = net.metadata
-        if getattr(md, "_fpn_prebuilt", None) is not None:
+        if md._fpn_prebuilt is not None:
             return md._fpn_prebuilt
         sp = self._size_plan(net.spatial_size)
         sizes = sp["sizes"]
@@ -279,7 +279,7 @@ class FPN_Net(torch.nn.Module):
         if g0 is not None and g0.brick is not None:
             # brick grids: every level from its PARENT level with device-side counts, the z-collapse grids from their own
             # level -- ONE host read for the whole pyramid (Metadata_3.buildBrickPyramid)
-            md.buildBrickPyramid(self._brick_specs(sp), defer=bool(getattr(md, "_defer_pyramid", False)))
+            md.buildBrickPyramid(self._brick_specs(sp), defer=md._defer_pyramid)
             return
         if sp["rounds"] is None:
             return

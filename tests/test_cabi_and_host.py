@@ -220,6 +220,63 @@ def test_metadata_incremental_input_is_host_bookkeeping_like_the_reference():
     assert feats.shape == (5, 2) and md._inb["nsamples"] == 3
 
 
+def test_metadata_clear_returns_to_the_declared_state():
+    """Metadata.clear() (Metadata.cpp:51-65) drops everything derived from an input and keeps the input spatial size:
+    after it `vars(md)` equals, key for key, that of a new object given the same spatial size -- whatever the layers,
+    FPN_Net and the ROI-align glue had left on it.  (Host twin of test_gpu_edge_cases.py::
+    test_metadata_reused_after_clear_sees_only_the_new_input.)"""
+    import sparseconvnet as scn
+    from sparseconvnet import SCN
+    new = set(vars(scn.Metadata(3)))
+    for order in ("first_seen", "brick"):
+        md = scn.Metadata(3, order)
+        md.setInputSpatialSize(torch.LongTensor([8, 8, 8]))
+        feats = torch.FloatTensor()
+        md.batchAddSample()
+        md.setInputSpatialLocation(feats, torch.LongTensor([1, 2, 3]), torch.FloatTensor([1, 10]), False)
+        md.setInputSpatialLocation(feats, torch.LongTensor([4, 4, 4]), torch.FloatTensor([2, 20]), False)
+        assert md.getNActive(torch.LongTensor([8, 8, 8])) == 2
+        g = SCN._Grid(torch.zeros((0, 4), dtype=torch.int32), None, 0, 0)
+        book = SCN._empty_book(27, "cpu")
+        md.grids[(8, 8, 8)], md.submanifold[(8, 8, 8, 3, 3, 3)], md.rulebooks[(8, 8, 8, 2, 2, 2, 2, 2, 2)] = g, book, book
+        md.fullConvolutionRuleBook, md._borrowed, md.device = book, {(8, 8, 8)}, torch.device("cpu")
+        md.input = dict(point_site=torch.zeros(0, dtype=torch.int32), V=0)
+        md._pending = dict(kind="brick", buf=torch.zeros(4, dtype=torch.int32))
+        md._batch_size_cache = 3
+        md._pregrids.add((4, 4, 4))
+        md._brick_rows, md._brick_nrows, md._brick_rows_clean = torch.zeros((2, 80), dtype=torch.int32), 2, True
+        md._brick_keep.append(md._brick_rows)
+        md._pyramid_pending = ([], {}, 1, None)
+        md._fpn_prebuilt, md._defer_pyramid = [(8, 8, 8)], True
+        md._roi_extent[(8, 8, 8)] = (5, 5, 5, 1)
+        md._roi_cellmap[(8, 8, 8)] = torch.zeros((1, 5, 5, 5), dtype=torch.int32)
+        assert set(vars(md)) == new                    # nothing above created an attribute
+        md.clear()
+        fresh = scn.Metadata(3, order)
+        fresh.setInputSpatialSize(torch.LongTensor([8, 8, 8]))
+        assert vars(md) == vars(fresh) and list(vars(md)) == list(vars(fresh))
+        assert md.input_spatial == (8, 8, 8) and md.device_tensors() == []
+        md.batchAddSample()                            # (the spatial size is still set) a new batch starts from nothing
+        assert md._inb == dict(rows={}, locs=[], nsamples=1)
+
+
+def test_metadata_declares_its_state():
+    """every attribute of Metadata_3 is assigned in __init__ / clear(): no method, and neither of the two modules that
+    keep caches on the object, creates or probes one on first use"""
+    import inspect
+    from sparseconvnet import SCN
+    src = inspect.getsource(SCN.Metadata_3)
+    assert "getattr(self," not in src and "self.__dict__" not in src and "setattr(self," not in src
+    pkg = os.path.join(REPO, "automatic-as-built-reconstruction_amd")
+    for rel in ("sparseconvnet/SCN.py", "sparseconvnet/fpn_net.py", "maskrcnn_benchmark/layers/roi_align_rotated_3d.py"):
+        text = open(os.path.join(pkg, rel)).read()
+        assert not re.search(r"\b(md|metadata)\.__dict__", text), rel
+        assert not re.search(r"getattr\((md|metadata), \"_", text), rel
+    assigned = set(re.findall(r"self\.(\w+)(?:, self\.\w+)* = ", inspect.getsource(SCN.Metadata_3.__init__)
+                              + inspect.getsource(SCN.Metadata_3.clear)))
+    assert assigned == set(vars(SCN.Metadata_3()))
+
+
 def test_bench_roofline_traffic_lookup_matches_the_committed_pmc_profile():
     """bench.pmc_traffic: the (kernel, grid) instance named by aabr_conv_last_variant() is found in the committed PMC
     profile although the profiler prints every template argument; a different grid or kernel gives (None, reason),

@@ -775,3 +775,78 @@ def test_rpn_proposals_fall_back_when_the_cut_is_tied_en_masse():
     finally:
         rpn_glue.fused_topk = True
     assert len(a) == len(b) == 1 and a[0][0].shape == b[0][0].shape and a[0][0].shape[0] > 0
+
+
+def _second_input():
+    """a flat two-sample list on 8^3 (five points, four sites), none of them a site of the first input below"""
+    return np.array([[7, 7, 7, 0], [6, 6, 6, 0], [7, 7, 7, 0], [0, 7, 0, 1], [5, 5, 5, 1]], np.int64)
+
+
+def _assert_equals_a_fresh_metadata(scn, md, order, coords):
+    from sparseconvnet import SCN
+    sp, three = torch.LongTensor([8, 8, 8]), torch.LongTensor([3, 3, 3])
+    fresh = scn.Metadata(3, order)
+    fresh.inputLayer(sp, _t(coords), 2, 3, torch.device(DEV))
+    assert md.getNActive(sp) == fresh.getNActive(sp) == 4
+    assert torch.equal(md.getSpatialLocations(sp), fresh.getSpatialLocations(sp))
+    a, b = md.getSubmanifoldRuleBook(sp, three), fresh.getSubmanifoldRuleBook(sp, three)
+    SCN.flush_geom()
+    assert torch.equal(a.out.table, b.out.table) and torch.equal(a.out.counts, b.out.counts)
+    assert a.rule_counts() == b.rule_counts() and sum(a.rule_counts()) > 4
+
+
+@pytest.mark.parametrize("order", ["first_seen", "brick"])
+def test_metadata_reused_after_clear_sees_only_the_new_input(order):
+    """Metadata.clear() (Metadata.cpp:51-65) drops everything derived from an input: an object that held a BLInputLayer's
+    padded batch of three samples (the last one empty), ROI-align caches, an FPN marker, a deferred pyramid and a
+    half-finished input layer is, after clear(), given a flat two-sample list and must equal a fresh object given that
+    list -- sample count, site list, submanifold book.  (Before every attribute was declared in clear(), the sample count
+    cached by the BL layer survived it: the first assertion after the new input failed with a stale 3.)"""
+    scn = _scn()
+    import types
+    from sparseconvnet import SCN
+    from maskrcnn_benchmark.layers.roi_align_rotated_3d import _cellmap, _occupied_extent
+    sp = torch.LongTensor([8, 8, 8])
+    bl = np.full((3, 4, 3), -1, np.int64)
+    bl[0] = [[1, 2, 3], [4, 4, 4], [1, 2, 3], [0, 0, 7]]
+    bl[1, :3] = [[2, 2, 2], [3, 3, 3], [2, 2, 2]]
+    md = scn.Metadata(3, order)
+    assert md.blLayer(sp, _t(bl), 3) == 5
+    assert SCN._batch_size(md) == 3
+    x = types.SimpleNamespace(metadata=md, spatial_size=sp)
+    _cellmap(x, _occupied_extent(x))
+    md._fpn_prebuilt = [(8, 8, 8)]
+    if order == "brick":
+        md.buildBrickPyramid([((4, 4, 4), (8, 8, 8), (2, 2, 2), (2, 2, 2))], defer=True)
+        assert md._pyramid_pending is not None
+    assert md._roi_extent and md._roi_cellmap
+    md.clear()
+    md.inputLayerEnqueue(sp, _t(_second_input()[:2]), 3, torch.device(DEV))    # enqueued, never finished
+    assert md._pending is not None
+    md.clear()
+    md.inputLayer(sp, _t(_second_input()), 2, 3, torch.device(DEV))
+    assert SCN._batch_size(md) == 2
+    _assert_equals_a_fresh_metadata(scn, md, order, _second_input())
+    assert md._roi_extent == {} and md._roi_cellmap == {} and md._fpn_prebuilt is None
+    assert md._pending is None and md._pyramid_pending is None and md._inb is None
+    assert sorted(md.grids) == [(8, 8, 8)] and not md.rulebooks and len(md.submanifold) == 1
+
+
+@pytest.mark.parametrize("order", ["first_seen", "brick"])
+def test_incremental_input_dropped_by_clear_does_not_materialise(order):
+    """points collected through batchAddSample / setInputSpatialLocation and then dropped by clear() are gone: the input
+    layer built afterwards is the only input the object knows"""
+    scn = _scn()
+    sp = torch.LongTensor([8, 8, 8])
+    md = scn.Metadata(3, order)
+    md.setInputSpatialSize(sp)
+    feats = torch.FloatTensor()
+    md.batchAddSample()
+    md.setInputSpatialLocation(feats, torch.LongTensor([1, 2, 3]), torch.FloatTensor([1, 10]), False)
+    md.setInputSpatialLocation(feats, torch.LongTensor([4, 4, 4]), torch.FloatTensor([2, 20]), False)
+    assert md.getNActive(sp) == 2
+    md.clear()
+    assert md._inb is None and md.input_spatial == (8, 8, 8)
+    md.inputLayer(sp, _t(_second_input()), 2, 3, torch.device(DEV))
+    _assert_equals_a_fresh_metadata(scn, md, order, _second_input())
+    assert md._inb is None

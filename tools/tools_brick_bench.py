@@ -76,7 +76,6 @@ def run(kind):
             def bfn():
                 md2 = SCN.Metadata_3("brick")
                 md2.input = dict(mdf.input)
-                md2._brick_rows = None
                 keep.append(md2._brickify_input(pend, m[0], m[8:12]))
                 keep.append(md2)
                 del keep[:-8]
