@@ -526,6 +526,7 @@ extern "C" int aabr_convolution_tables2(const int32_t *in_coords, int64_t V_in, 
   ConvGeom g;
   AABR_CHECK_ARG(make_geom(size_host, stride_host, out_spatial_host, g) == 0, "bad filter geometry");
   int vol = g.size[0] * g.size[1] * g.size[2];
+  AABR_CHECK_ARG(vol <= 65535, "filter volume too large");     // the offsets are the launches' gridDim.y
   if (V_out > 0 && table_out) {
     AABR_CHECK_ARG(out_coords && in_keys && ((uintptr_t)in_keys & 15) == 0, "null / misaligned pointer");
     hipLaunchKernelGGL(k_conv_table_out<HashFinder>, dim3((unsigned)ceil_div(V_out, 256), (unsigned)vol), dim3(256), 0,

@@ -310,7 +310,8 @@ int aabr_full_convolution_sites(const int32_t *in_coords, int64_t V_in, const in
                                 int64_t out_cap, int32_t *scratch, int32_t *out_site_coords, int32_t *meta, void *stream);
 /* counts (optional): int32 [vol * ceil(V_out/256)] per-block rule counts, as above.
  * table_out[k*V_out + o] = input row at offset k of output o's window (or -1);
- * table_in [k*V_in  + u] = output row whose window holds input u at offset k (or -1).       */
+ * table_in [k*V_in  + u] = output row whose window holds input u at offset k (or -1).
+ * A filter volume above 65535 is refused (AABR_EINVAL), as by aabr_submanifold_table.       */
 int aabr_convolution_tables(const int32_t *in_coords, int64_t V_in, const uint64_t *in_keys,
                             int64_t in_cap,
                             const int32_t *out_coords, int64_t V_out, const uint64_t *out_keys,

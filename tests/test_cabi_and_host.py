@@ -38,6 +38,13 @@ def test_argument_validation_without_gpu():
                                       None, None) == -1
     assert b"ncols" in lib.aabr_last_error()
     assert lib.aabr_conv_forward(None, 0, 10, None, 4, 10, None, 27, None, None, 0, None, None) == -1
+    # a filter volume beyond the launch grid's y limit is refused by both hash table builders, empty levels included
+    big, one = _hip.i32x3((64, 64, 64)), _hip.i32x3((1, 1, 1))
+    assert lib.aabr_submanifold_table(None, 0, None, 64, big, None, None, None) == -1
+    assert b"aabr_submanifold_table: filter volume too large" in lib.aabr_last_error()
+    assert lib.aabr_convolution_tables2(None, 0, None, 64, None, 0, None, 64, big, one, one, None, None, None, None,
+                                        None) == -1
+    assert b"aabr_convolution_tables2: filter volume too large" in lib.aabr_last_error()
     assert lib.aabr_conv_wpack_floats(27, 32, 32) == 27 * 1 * 2 * 512
     assert lib.aabr_conv_wpack_floats(27, 9, 32) == 27 * 1 * 2 * 512
     assert lib.aabr_bn_scratch_floats(32) > 0
