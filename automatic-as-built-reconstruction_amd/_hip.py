@@ -277,6 +277,10 @@ _SIGS = {
     "aabr_roi_pool_forward_bf16": (C.c_int, [_lvp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp]),
     "aabr_roi_pool_backward_bf16": (C.c_int, [_lvp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp,
                                               _vp, _i64, _vp]),
+    "aabr_roi_pool_forward_pooled_bf16": (C.c_int, [_lvp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32,
+                                                    _vp, _vp]),
+    "aabr_roi_pool_backward_pooled_bf16": (C.c_int, [_lvp, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32,
+                                                     _vp, _vp, _vp, _i64, _vp]),
     "aabr_roi_mlp_tile": (C.c_int, [_i64, _i64]),
     "aabr_roi_mlp_dw_splits": (C.c_int, [_i64, _i64, _i64]),
     "aabr_roi_mlp_dw_scratch_floats": (C.c_int64, [_i64, _i64, _i64]),
@@ -285,6 +289,10 @@ _SIGS = {
     "aabr_roi_mlp_backward_weight": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
                                                _vp]),
     "aabr_roi_mlp_pack_fc6": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
+    "aabr_roi_mlp_forward_pooled_bf16": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _vp]),
+    "aabr_roi_mlp_backward_input_pooled_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp]),
+    "aabr_roi_mlp_backward_weight_pooled_bf16": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
+                                                           _vp]),
     "aabr_roi_mlp_forward_window": (C.c_int, [_vp, _mwp, _vp, _vp, _i32, _i64, _vp, _vp]),
     "aabr_roi_mlp_backward_input_window": (C.c_int, [_vp, _vp, _vp, _mwp, _i64, _i32, _i32, _vp, _vp]),
     "aabr_roi_mlp_backward_weight_window": (C.c_int, [_vp, _vp, _vp, _mwp, _i64, _i64, _vp, _vp, _vp, _vp]),

@@ -1,6 +1,10 @@
 // roi_mlp.hip -- the dense layers of the box head (FPN2MLPFeatureExtractor after its pooler, roi_box_feature_extractors.py:
 // 46-169, and FPNPredictor, roi_box_predictors.py:34-109), gfx950: a dense fp32 GEMM family on v_mfma_f32_32x32x2_f32 with
-// LDS-tiled operands and fused epilogues.  fp32 storage only.
+// LDS-tiled operands and fused epilogues.  fp32 storage, except the pooled tensor and its gradient, which the
+// _pooled_bf16 entry points read and write in place in bf16 (template parameter PT of the kernel: the loader's fetch
+// widens one element, the LDS image and everything after it are the fp32 form's, the pooled write-out of the input
+// gradient rounds once on store).  Only the instances with a pooled layout exist in bf16: plain rows, windows, dY, Y, W,
+// dW and db are fp32.
 //
 // ONE kernel template, k_mlp_gemm<BT, LA, LB, DW>, serves the four products of a layer Y = act(A W^T + bias), W [N, K]:
 //   forward          Y  [M, N] = A (rows m, reduce k)        x  W (cols n, reduce k)      + bias, ReLU
@@ -47,6 +51,7 @@
 //
 // Launches: forward 1; input gradient 1; weight + bias gradient 1, or 2 when split; fc6's weight pack 1.
 #include "common.h"
+#include <type_traits>
 
 namespace aabr {
 
@@ -72,7 +77,9 @@ __device__ inline int64_t mlp_win_col(const MlpWindow &w, uint32_t k, uint32_t &
 }
 
 struct MlpOperand {
-  const float *p;
+  const float *p;          // fp32 elements -- EXCEPT the pooled operand of a PT = __bf16 instance (k_mlp_gemm), where the
+                           // _pooled_bf16 entry points pass bf16 elements through this pointer and MlpLoader::fetch reads
+                           // it as const ST *.  Nothing else may dereference p: a new (vectorised) load goes through ST
   const float *mask;       // same layout as p, or NULL: the element counts where mask > 0
   int64_t ld;              // kRed: outer stride; kOut: reduce stride
   uint32_t hw, pz;         // pooled layouts
@@ -85,7 +92,8 @@ struct MlpArgs {
   int64_t rows, cols, red;        // the output is [rows, cols]
   int64_t red_per_split;          // multiple of kBK
   uint32_t tiles_c, tiles_r, splits;
-  float *out;
+  float *out;                     // fp32 -- except the pooled input gradient of a PT = __bf16 instance: bf16 elements,
+                                  // stored as (PT *)out at the kernel's one write-out statement (kOutPT)
   int64_t ldo;
   uint32_t o_hw, o_pz;            // o_pz > 0: the output is stored in the pooled layout (rows m, cols k)
   int64_t o_hwpz, o_nstride;
@@ -131,7 +139,8 @@ template <int L> __device__ inline int64_t mlp_off_red(const MlpOperand &q, uint
 // One operand's BT x kBK tile: global -> registers -> LDS image [kBK][BT + 2].  Thread t serves, for i < NI,
 //   reduce-fast layouts (kRed, kPoolM, kWinM):  reduce t & 31, outer (t >> 5) + 8 i
 //   outer-fast layouts  (kOut, kPoolK, kWinK):  outer t % BT,  reduce t / BT + (256 / BT) i
-template <int BT, int L> struct MlpLoader {
+// ST is the storage of the operand's elements: float, or __bf16 for the pooled layouts (q.p then points at bf16)
+template <int BT, int L, typename ST = float> struct MlpLoader {
   static constexpr int NI = BT * kBK / 256;
   static constexpr bool kRedFast = (L == kRed || L == kPoolM || L == kWinM);
   static constexpr bool kOutTab = (L == kPoolM || L == kWinM);   // one off_out per outer index of the thread
@@ -159,7 +168,7 @@ template <int BT, int L> struct MlpLoader {
     }
   }
   __device__ inline float fetch(const MlpOperand &q, int64_t off) const {
-    float x = q.p[off];
+    float x = (float)((const ST *)q.p)[off];           // bf16: widened here (exact), fp32 from here on
     if (q.mask) x = q.mask[off] > 0.f ? x : 0.f;
     return x;
   }
@@ -192,9 +201,14 @@ template <int BT, int L> struct MlpLoader {
   }
 };
 
-template <int BT, int LA, int LB, bool DW, bool OW = false>
+// PT: the storage of whatever is in a pooled layout in this instance -- the kPoolM / kPoolK operand, or, in an instance
+// without one, the pooled write-out (g.o_pz > 0: the input gradient).  float everywhere but in the _pooled_bf16 entries.
+template <int BT, int LA, int LB, bool DW, bool OW = false, typename PT = float>
 __global__ __launch_bounds__(256) void k_mlp_gemm(const MlpArgs g) {
   constexpr int LDT = BT + 2, TW = BT / 64;          // TW x TW MFMA tiles of 32 x 32 per wave
+  constexpr bool kPoolA = LA == kPoolM || LA == kPoolK, kPoolB = LB == kPoolM || LB == kPoolK;
+  constexpr bool kOutPT = !std::is_same<PT, float>::value && !kPoolA && !kPoolB;
+  static_assert(std::is_same<PT, float>::value || (!OW && (kPoolA || kPoolB || !DW)), "bf16: pooled layouts only");
   __shared__ float sA[kBK * LDT];
   __shared__ float sB[kBK * LDT];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wm = wave >> 1, wn = wave & 1;
@@ -206,8 +220,8 @@ __global__ __launch_bounds__(256) void k_mlp_gemm(const MlpArgs g) {
   const int64_t r_begin = (int64_t)split * g.red_per_split;
   const int64_t r_end = r_begin + g.red_per_split < g.red ? r_begin + g.red_per_split : g.red;
 
-  MlpLoader<BT, LA> la;
-  MlpLoader<BT, LB> lb;
+  MlpLoader<BT, LA, typename std::conditional<kPoolA, PT, float>::type> la;
+  MlpLoader<BT, LB, typename std::conditional<kPoolB, PT, float>::type> lb;
   la.init(g.a, row0, g.rows, t);
   lb.init(g.b, col0, g.cols, t);
 
@@ -301,7 +315,8 @@ __global__ __launch_bounds__(256) void k_mlp_gemm(const MlpArgs g) {
         } else {
           ro = row * (to_scratch ? g.cols : g.ldo);
         }
-        outp[ro + co] = x;
+        if (kOutPT) ((PT *)outp)[ro + co] = (PT)x;   // the pooled input gradient in bf16: one rounding of x
+        else outp[ro + co] = x;
       }
     }
   }
@@ -350,10 +365,11 @@ constexpr int kMlpDwRowsPerSplit = 256, kMlpDwMaxSplits = 64;
 
 static int64_t mlp_tiles(int64_t rows, int64_t cols, int bt) { return ceil_div(rows, bt) * ceil_div(cols, bt); }
 
-template <int LA, int LB, bool DW, bool OW = false> static void mlp_launch(int bt, const MlpArgs &g, hipStream_t st) {
+template <int LA, int LB, bool DW, bool OW = false, typename PT = float>
+static void mlp_launch(int bt, const MlpArgs &g, hipStream_t st) {
   const unsigned grid = g.tiles_c * g.tiles_r * g.splits;
-  if (bt == 128) hipLaunchKernelGGL((k_mlp_gemm<128, LA, LB, DW, OW>), dim3(grid), dim3(256), 0, st, g);
-  else hipLaunchKernelGGL((k_mlp_gemm<64, LA, LB, DW, OW>), dim3(grid), dim3(256), 0, st, g);
+  if (bt == 128) hipLaunchKernelGGL((k_mlp_gemm<128, LA, LB, DW, OW, PT>), dim3(grid), dim3(256), 0, st, g);
+  else hipLaunchKernelGGL((k_mlp_gemm<64, LA, LB, DW, OW, PT>), dim3(grid), dim3(256), 0, st, g);
 }
 
 static bool mlp_set_grid(MlpArgs &g, int bt, int64_t splits) {
@@ -387,16 +403,20 @@ static bool mlp_window(const AabrMlpWindow *v, MlpWindow &w, int64_t &M, int64_t
 
 using namespace aabr;
 
-#define MLP_CHECK_SHAPE(M, N, K)                                                                      \
-  AABR_CHECK_ARG((M) >= 0 && (N) >= 1 && (K) >= 4, "need M >= 0, N >= 1, K >= 4");                    \
-  AABR_CHECK_ARG((K) % 4 == 0, "K must be a multiple of 4");                                          \
-  AABR_CHECK_ARG((M) <= kMlpMaxDim && (N) <= kMlpMaxDim && (K) <= kMlpMaxDim, "M, N, K must stay below 2^31 - 256")
-#define MLP_CHECK_LAYOUT(layout, M, K, hw, pz)                                                                   \
-  AABR_CHECK_ARG((layout) == AABR_MLP_ROWS || (layout) == AABR_MLP_POOLED, "a_layout must be AABR_MLP_ROWS or _POOLED"); \
-  if ((layout) == AABR_MLP_POOLED) {                                                                             \
-    AABR_CHECK_ARG((hw) >= 1 && (pz) >= 1 && (hw) <= kMlpMaxDim, "pooled layout: hw >= 1 and pz >= 1");          \
-    AABR_CHECK_ARG((K) % (pz) == 0 && (M) % (hw) == 0, "pooled layout: K = C pz and M = n hw");                  \
+// the _AS forms: the same checks inside a helper, reported under the entry point's name `fn` (AABR_CHECK_ARG_AS)
+#define MLP_CHECK_SHAPE_AS(fn, M, N, K)                                                                   \
+  AABR_CHECK_ARG_AS(fn, (M) >= 0 && (N) >= 1 && (K) >= 4, "need M >= 0, N >= 1, K >= 4");                 \
+  AABR_CHECK_ARG_AS(fn, (K) % 4 == 0, "K must be a multiple of 4");                                       \
+  AABR_CHECK_ARG_AS(fn, (M) <= kMlpMaxDim && (N) <= kMlpMaxDim && (K) <= kMlpMaxDim, "M, N, K must stay below 2^31 - 256")
+#define MLP_CHECK_SHAPE(M, N, K) MLP_CHECK_SHAPE_AS(__func__, M, N, K)
+#define MLP_CHECK_LAYOUT_AS(fn, layout, M, K, hw, pz)                                                                    \
+  AABR_CHECK_ARG_AS(fn, (layout) == AABR_MLP_ROWS || (layout) == AABR_MLP_POOLED, "a_layout must be AABR_MLP_ROWS or _POOLED"); \
+  if ((layout) == AABR_MLP_POOLED) {                                                                                     \
+    AABR_CHECK_ARG_AS(fn, (hw) >= 1 && (pz) >= 1 && (hw) <= kMlpMaxDim, "pooled layout: hw >= 1 and pz >= 1");           \
+    AABR_CHECK_ARG_AS(fn, (K) % (pz) == 0 && (M) % (hw) == 0, "pooled layout: K = C pz and M = n hw");                   \
   }
+// a bf16 operand of a _pooled_bf16 entry point: named, and 4-byte aligned, before anything else is looked at
+#define MLP_CHECK_BF16(p, name) AABR_CHECK_ARG(((uintptr_t)(p) & 3) == 0, name " must be 4-byte aligned")
 
 extern "C" int aabr_roi_mlp_tile(int64_t rows, int64_t cols) {
   if (rows < 1 || cols < 1) return 0;
@@ -420,35 +440,54 @@ extern "C" int64_t aabr_roi_mlp_dw_scratch_floats(int64_t M, int64_t N, int64_t 
   return s > 1 ? (int64_t)s * (N * K + N) : 0;
 }
 
-extern "C" int aabr_roi_mlp_forward(const float *A, int a_layout, int64_t hw, int pz, const float *W, const float *bias,
-                                    int relu, int64_t M, int64_t N, int64_t K, float *Y, void *stream_) {
-  MLP_CHECK_SHAPE(M, N, K);
-  MLP_CHECK_LAYOUT(a_layout, M, K, hw, pz);
+// The three products; PT = the storage of the pooled tensor (A forward and weight gradient, dA input gradient): float
+// for the fp32 entry points (either a_layout), __bf16 for the _pooled_bf16 ones (a_layout pooled; the pointer is passed
+// as const float * and read as bf16 by the instance).  `fn`: the entry point's name for the error text.
+template <typename PT>
+static int mlp_forward(const char *fn, const float *A, int a_layout, int64_t hw, int pz, const float *W, const float *bias,
+                       int relu, int64_t M, int64_t N, int64_t K, float *Y, void *stream_) {
+  MLP_CHECK_SHAPE_AS(fn, M, N, K);
+  MLP_CHECK_LAYOUT_AS(fn, a_layout, M, K, hw, pz);
   if (M == 0) return AABR_OK;
-  AABR_CHECK_ARG(A && W && Y, "null pointer");
+  AABR_CHECK_ARG_AS(fn, A && W && Y, "null pointer");
   MlpArgs g = {};
   g.a.p = A, g.a.ld = K;
   g.b.p = W, g.b.ld = K;
   g.rows = M, g.cols = N, g.red = K, g.red_per_split = ceil_div(K, kBK) * kBK;
   g.out = Y, g.ldo = N, g.bias = bias, g.relu = relu != 0;
   const int bt = aabr_roi_mlp_tile(M, N);
-  AABR_CHECK_ARG(mlp_set_grid(g, bt, 1), "too many tiles");
+  AABR_CHECK_ARG_AS(fn, mlp_set_grid(g, bt, 1), "too many tiles");
   if (a_layout == AABR_MLP_POOLED) {
     mlp_pooled(g.a, K, hw, pz);
-    mlp_launch<kPoolM, kRed, false>(bt, g, (hipStream_t)stream_);
-  } else {
+    mlp_launch<kPoolM, kRed, false, false, PT>(bt, g, (hipStream_t)stream_);
+  } else if (std::is_same<PT, float>::value) {
     mlp_launch<kRed, kRed, false>(bt, g, (hipStream_t)stream_);
   }
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }
 
-extern "C" int aabr_roi_mlp_backward_input(const float *dY, const float *Y, const float *W, int64_t M, int64_t N,
-                                           int64_t K, int a_layout, int64_t hw, int pz, float *dA, void *stream_) {
-  MLP_CHECK_SHAPE(M, N, K);
-  MLP_CHECK_LAYOUT(a_layout, M, K, hw, pz);
+extern "C" int aabr_roi_mlp_forward(const float *A, int a_layout, int64_t hw, int pz, const float *W, const float *bias,
+                                    int relu, int64_t M, int64_t N, int64_t K, float *Y, void *stream_) {
+  return mlp_forward<float>(__func__, A, a_layout, hw, pz, W, bias, relu, M, N, K, Y, stream_);
+}
+
+extern "C" int aabr_roi_mlp_forward_pooled_bf16(const void *A_bf16, int64_t hw, int pz, const float *W, const float *bias,
+                                                int relu, int64_t M, int64_t N, int64_t K, float *Y, void *stream_) {
+  MLP_CHECK_BF16(A_bf16, "A_bf16");
+  AABR_CHECK_ARG(M <= 0 || A_bf16, "null A_bf16");
+  AABR_CHECK_ARG(M <= 0 || W, "null W");
+  AABR_CHECK_ARG(M <= 0 || Y, "null Y");
+  return mlp_forward<__bf16>(__func__, (const float *)A_bf16, AABR_MLP_POOLED, hw, pz, W, bias, relu, M, N, K, Y, stream_);
+}
+
+template <typename PT>
+static int mlp_backward_input(const char *fn, const float *dY, const float *Y, const float *W, int64_t M, int64_t N,
+                              int64_t K, int a_layout, int64_t hw, int pz, float *dA, void *stream_) {
+  MLP_CHECK_SHAPE_AS(fn, M, N, K);
+  MLP_CHECK_LAYOUT_AS(fn, a_layout, M, K, hw, pz);
   if (M == 0) return AABR_OK;
-  AABR_CHECK_ARG(dY && W && dA, "null pointer");
+  AABR_CHECK_ARG_AS(fn, dY && W && dA, "null pointer");
   MlpArgs g = {};
   g.a.p = dY, g.a.mask = Y, g.a.ld = N;
   g.b.p = W, g.b.ld = K;
@@ -458,28 +497,44 @@ extern "C" int aabr_roi_mlp_backward_input(const float *dY, const float *Y, cons
     g.o_hw = (uint32_t)hw, g.o_pz = (uint32_t)pz, g.o_hwpz = hw * pz, g.o_nstride = K * hw;
   }
   const int bt = aabr_roi_mlp_tile(M, K);
-  AABR_CHECK_ARG(mlp_set_grid(g, bt, 1), "too many tiles");
-  mlp_launch<kRed, kOut, false>(bt, g, (hipStream_t)stream_);
+  AABR_CHECK_ARG_AS(fn, mlp_set_grid(g, bt, 1), "too many tiles");
+  mlp_launch<kRed, kOut, false, false, PT>(bt, g, (hipStream_t)stream_);   // PT = __bf16: the pooled write-out in bf16
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }
 
-extern "C" int aabr_roi_mlp_backward_weight(const float *dY, const float *Y, const float *A, int a_layout, int64_t hw,
-                                            int pz, int64_t M, int64_t N, int64_t K, int64_t perm_hw, float *dW,
-                                            float *db, float *scratch, void *stream_) {
-  MLP_CHECK_SHAPE(M, N, K);
-  MLP_CHECK_LAYOUT(a_layout, M, K, hw, pz);
-  AABR_CHECK_ARG(perm_hw >= 0 && (perm_hw == 0 || K % perm_hw == 0), "perm_hw must be 0 or divide K");
-  AABR_CHECK_ARG(dW, "null pointer");
+extern "C" int aabr_roi_mlp_backward_input(const float *dY, const float *Y, const float *W, int64_t M, int64_t N,
+                                           int64_t K, int a_layout, int64_t hw, int pz, float *dA, void *stream_) {
+  return mlp_backward_input<float>(__func__, dY, Y, W, M, N, K, a_layout, hw, pz, dA, stream_);
+}
+
+extern "C" int aabr_roi_mlp_backward_input_pooled_bf16(const float *dY, const float *Y, const float *W, int64_t M,
+                                                       int64_t N, int64_t K, int64_t hw, int pz, void *dA_bf16,
+                                                       void *stream_) {
+  MLP_CHECK_BF16(dA_bf16, "dA_bf16");
+  AABR_CHECK_ARG(M <= 0 || dA_bf16, "null dA_bf16");
+  AABR_CHECK_ARG(M <= 0 || dY, "null dY");
+  AABR_CHECK_ARG(M <= 0 || W, "null W");
+  return mlp_backward_input<__bf16>(__func__, dY, Y, W, M, N, K, AABR_MLP_POOLED, hw, pz, (float *)dA_bf16, stream_);
+}
+
+template <typename PT>
+static int mlp_backward_weight(const char *fn, const float *dY, const float *Y, const float *A, int a_layout, int64_t hw,
+                               int pz, int64_t M, int64_t N, int64_t K, int64_t perm_hw, float *dW, float *db,
+                               float *scratch, void *stream_) {
+  MLP_CHECK_SHAPE_AS(fn, M, N, K);
+  MLP_CHECK_LAYOUT_AS(fn, a_layout, M, K, hw, pz);
+  AABR_CHECK_ARG_AS(fn, perm_hw >= 0 && (perm_hw == 0 || K % perm_hw == 0), "perm_hw must be 0 or divide K");
+  AABR_CHECK_ARG_AS(fn, dW, "null pointer");
   hipStream_t st = (hipStream_t)stream_;
   if (M == 0) {                                       // an empty sum: zeros, no kernel
     AABR_CHECK_HIP(hipMemsetAsync(dW, 0, sizeof(float) * N * K, st));
     if (db) AABR_CHECK_HIP(hipMemsetAsync(db, 0, sizeof(float) * N, st));
     return AABR_OK;
   }
-  AABR_CHECK_ARG(dY && A, "null pointer");
+  AABR_CHECK_ARG_AS(fn, dY && A, "null pointer");
   const int splits = aabr_roi_mlp_dw_splits(M, N, K);
-  AABR_CHECK_ARG(splits == 1 || scratch, "null scratch");
+  AABR_CHECK_ARG_AS(fn, splits == 1 || scratch, "null scratch");
   MlpArgs g = {};
   g.a.p = dY, g.a.mask = Y, g.a.ld = N;
   g.b.p = A, g.b.ld = K;
@@ -488,22 +543,39 @@ extern "C" int aabr_roi_mlp_backward_weight(const float *dY, const float *Y, con
   g.out = dW, g.ldo = K, g.db = db, g.scratch = scratch;
   if (perm_hw) g.perm_hw = (uint32_t)perm_hw, g.perm_R = (uint32_t)(K / perm_hw);
   const int bt = aabr_roi_mlp_tile(N, K);
-  AABR_CHECK_ARG(mlp_set_grid(g, bt, splits), "too many tiles");
+  AABR_CHECK_ARG_AS(fn, mlp_set_grid(g, bt, splits), "too many tiles");
   if (a_layout == AABR_MLP_POOLED) {
     mlp_pooled(g.b, K, hw, pz);
-    mlp_launch<kOut, kPoolK, true>(bt, g, st);
-  } else {
+    mlp_launch<kOut, kPoolK, true, false, PT>(bt, g, st);
+  } else if (std::is_same<PT, float>::value) {
     mlp_launch<kOut, kOut, true>(bt, g, st);
   }
   AABR_CHECK_LAUNCH();
   if (splits > 1) {
     const int64_t per = N * K + N;
-    AABR_CHECK_ARG(ceil_div(per, 256) < (1LL << 31), "too many elements");
+    AABR_CHECK_ARG_AS(fn, ceil_div(per, 256) < (1LL << 31), "too many elements");
     hipLaunchKernelGGL(k_mlp_dw_reduce, dim3((unsigned)ceil_div(per, 256)), dim3(256), 0, st, scratch, splits, N, K,
                        g.perm_R, g.perm_hw, K, dW, db);
     AABR_CHECK_LAUNCH();
   }
   return AABR_OK;
+}
+
+extern "C" int aabr_roi_mlp_backward_weight(const float *dY, const float *Y, const float *A, int a_layout, int64_t hw,
+                                            int pz, int64_t M, int64_t N, int64_t K, int64_t perm_hw, float *dW,
+                                            float *db, float *scratch, void *stream_) {
+  return mlp_backward_weight<float>(__func__, dY, Y, A, a_layout, hw, pz, M, N, K, perm_hw, dW, db, scratch, stream_);
+}
+
+extern "C" int aabr_roi_mlp_backward_weight_pooled_bf16(const float *dY, const float *Y, const void *A_bf16, int64_t hw,
+                                                        int pz, int64_t M, int64_t N, int64_t K, int64_t perm_hw,
+                                                        float *dW, float *db, float *scratch, void *stream_) {
+  MLP_CHECK_BF16(A_bf16, "A_bf16");
+  AABR_CHECK_ARG(M <= 0 || A_bf16, "null A_bf16");
+  AABR_CHECK_ARG(M <= 0 || dY, "null dY");
+  AABR_CHECK_ARG(dW, "null dW");
+  return mlp_backward_weight<__bf16>(__func__, dY, Y, (const float *)A_bf16, AABR_MLP_POOLED, hw, pz, M, N, K, perm_hw, dW,
+                                     db, scratch, stream_);
 }
 
 extern "C" int aabr_roi_mlp_pack_fc6(const float *W, int64_t N, int64_t R, int64_t hw, float *Wp, void *stream_) {

@@ -16,6 +16,10 @@
 // nothing else knows the storage, and the output stays fp32.  The backward kernel never reads the features: the bf16
 // entry runs the SAME k_roi_pool<true> with its fp32 atomics into a caller-provided fp32 buffer and rounds that once
 // into the bf16 gradient rows (aabr_cast_storage): 1 memset + 2 launches.  Nothing is accumulated in bf16.
+//
+// Pooled storage OT (float, __bf16; aabr_roi_pool_*_pooled_bf16) of top / top_diff: the forward's final store out of
+// stage[] (and the zero fill of a missing level) rounds the fp32 value once, nearest even; the backward's staging loads
+// of top_diff widen (exact).  Forward instances FT x OT = 4, backward OT = 2 (FT plays no part there).
 #include "common.h"
 #include "roi_shared.h"
 
@@ -86,11 +90,11 @@ struct PoolLevels {
   int n;
 };
 
-template <bool BACKWARD, typename FT>
+template <bool BACKWARD, typename FT, typename OT>
 __global__ __launch_bounds__(256) void k_roi_pool(PoolLevels lv, int C, const float *__restrict__ rois,
                                                   const int32_t *__restrict__ levels, int ph_, int pw_, int pz_,
-                                                  int sampling, float *__restrict__ top,
-                                                  const float *__restrict__ top_diff) {
+                                                  int sampling, OT *__restrict__ top,
+                                                  const OT *__restrict__ top_diff) {
   extern __shared__ float stage[]; // [kRoiPlanes][kRoiBins] bins of this pass (forward: results; backward: top_diff)
   const int64_t n = blockIdx.x;
   const int c0 = blockIdx.y * kRoiPlanes;
@@ -104,7 +108,7 @@ __global__ __launch_bounds__(256) void k_roi_pool(PoolLevels lv, int C, const fl
     if (!BACKWARD) {
       for (int i = threadIdx.x; i < kRoiPlanes * nbins; i += 256) {
         const int pc = i / nbins, pb = i - pc * nbins;
-        if (c0 + pc < C) top[obase + (int64_t)pc * nbins + pb] = 0.f;
+        if (c0 + pc < C) top[obase + (int64_t)pc * nbins + pb] = (OT)0.f;
       }
     }
     return;
@@ -141,7 +145,7 @@ __global__ __launch_bounds__(256) void k_roi_pool(PoolLevels lv, int C, const fl
     if (BACKWARD) { // stage this pass's output gradients: contiguous runs per plane
       for (int i = threadIdx.x; i < kRoiPlanes * nb; i += 256) {
         const int pc = i / nb, pb = i - pc * nb;
-        stage[pc * kRoiBins + pb] = (c0 + pc < C) ? top_diff[obase + (int64_t)pc * nbins + bin0 + pb] : 0.f;
+        stage[pc * kRoiBins + pb] = (c0 + pc < C) ? (float)top_diff[obase + (int64_t)pc * nbins + bin0 + pb] : 0.f;
       }
       __syncthreads();
     }
@@ -186,7 +190,7 @@ __global__ __launch_bounds__(256) void k_roi_pool(PoolLevels lv, int C, const fl
     if (!BACKWARD) {
       for (int i = threadIdx.x; i < kRoiPlanes * nb; i += 256) {
         const int pc = i / nb, pb = i - pc * nb;
-        if (c0 + pc < C) top[obase + (int64_t)pc * nbins + bin0 + pb] = stage[pc * kRoiBins + pb];
+        if (c0 + pc < C) top[obase + (int64_t)pc * nbins + bin0 + pb] = (OT)stage[pc * kRoiBins + pb];
       }
       __syncthreads();
     }
@@ -259,10 +263,10 @@ static int pool_levels(PoolLevels &lv, const AabrRoiLevel *d, int n_levels, int 
   return 0;
 }
 
-template <typename FT>
+template <typename FT, typename OT>
 static int roi_pool_forward(const char *fn, const AabrRoiLevel *levels_desc_host, int n_levels, int channels,
                             int batch_size, const float *rois, const int32_t *levels, int64_t num_rois, int pooled_h,
-                            int pooled_w, int pooled_z, int sampling_ratio, float *output, hipStream_t st) {
+                            int pooled_w, int pooled_z, int sampling_ratio, OT *output, hipStream_t st) {
   PoolLevels lv;
   const char *why = "";
   const int rc = pool_levels(lv, levels_desc_host, n_levels, channels, batch_size, num_rois, pooled_h, pooled_w,
@@ -270,9 +274,9 @@ static int roi_pool_forward(const char *fn, const AabrRoiLevel *levels_desc_host
   AABR_CHECK_ARG_AS(fn, rc == 0, why);
   if (num_rois == 0) return AABR_OK;
   AABR_CHECK_ARG_AS(fn, rois && levels && output, "null pointer");
-  hipLaunchKernelGGL((k_roi_pool<false, FT>), dim3((unsigned)num_rois, (unsigned)ceil_div(channels, kRoiPlanes)),
+  hipLaunchKernelGGL((k_roi_pool<false, FT, OT>), dim3((unsigned)num_rois, (unsigned)ceil_div(channels, kRoiPlanes)),
                      dim3(256), (size_t)kRoiPlanes * kRoiBins * sizeof(float), st, lv, channels, rois, levels, pooled_h,
-                     pooled_w, pooled_z, sampling_ratio, output, (const float *)nullptr);
+                     pooled_w, pooled_z, sampling_ratio, output, (const OT *)nullptr);
   AABR_CHECK_LAUNCH();
   return AABR_OK;
 }
@@ -280,7 +284,7 @@ static int roi_pool_forward(const char *fn, const AabrRoiLevel *levels_desc_host
 extern "C" int aabr_roi_pool_forward(const AabrRoiLevel *levels_desc_host, int n_levels, int channels, int batch_size,
                                      const float *rois, const int32_t *levels, int64_t num_rois, int pooled_h,
                                      int pooled_w, int pooled_z, int sampling_ratio, float *output, void *stream_) {
-  return roi_pool_forward<float>(__func__, levels_desc_host, n_levels, channels, batch_size, rois, levels, num_rois,
+  return roi_pool_forward<float, float>(__func__, levels_desc_host, n_levels, channels, batch_size, rois, levels, num_rois,
                                  pooled_h, pooled_w, pooled_z, sampling_ratio, output, (hipStream_t)stream_);
 }
 
@@ -290,29 +294,39 @@ extern "C" int aabr_roi_pool_forward_bf16(const AabrRoiLevel *levels_desc_host, 
                                           void *stream_) {
   for (int l = 0; levels_desc_host && l < n_levels && l < kPoolMaxLevels; ++l)
     AABR_CHECK_ARG(((uintptr_t)levels_desc_host[l].feats & 3) == 0, "feats must be 4-byte aligned");
-  return roi_pool_forward<__bf16>(__func__, levels_desc_host, n_levels, channels, batch_size, rois, levels, num_rois,
+  return roi_pool_forward<__bf16, float>(__func__, levels_desc_host, n_levels, channels, batch_size, rois, levels, num_rois,
                                   pooled_h, pooled_w, pooled_z, sampling_ratio, output, (hipStream_t)stream_);
+}
+
+// the memset + launch of the backward entry points; OT: the storage of grad_output
+template <typename OT>
+static int roi_pool_backward(const char *fn, const AabrRoiLevel *levels_desc_host, int n_levels, int channels,
+                             int batch_size, const float *rois, const int32_t *levels, int64_t num_rois, int pooled_h,
+                             int pooled_w, int pooled_z, int sampling_ratio, const OT *grad_output, float *d_feats_all,
+                             int64_t total_rows, hipStream_t st) {
+  PoolLevels lv;
+  const char *why = "";
+  const int rc = pool_levels(lv, levels_desc_host, n_levels, channels, batch_size, num_rois, pooled_h, pooled_w,
+                             pooled_z, true, d_feats_all, total_rows, &why);
+  AABR_CHECK_ARG_AS(fn, rc == 0, why);
+  AABR_CHECK_ARG_AS(fn, d_feats_all || total_rows == 0, "null d_feats_all");
+  if (total_rows > 0) hipMemsetAsync(d_feats_all, 0, (size_t)total_rows * channels * sizeof(float), st);
+  if (num_rois == 0 || total_rows == 0) return AABR_OK;
+  AABR_CHECK_ARG_AS(fn, rois && levels && grad_output, "null pointer");
+  hipLaunchKernelGGL((k_roi_pool<true, float, OT>), dim3((unsigned)num_rois, (unsigned)ceil_div(channels, kRoiPlanes)),
+                     dim3(256), (size_t)kRoiPlanes * kRoiBins * sizeof(float), st, lv, channels, rois, levels, pooled_h,
+                     pooled_w, pooled_z, sampling_ratio, (OT *)nullptr, grad_output);
+  AABR_CHECK_LAUNCH();
+  return AABR_OK;
 }
 
 extern "C" int aabr_roi_pool_backward(const AabrRoiLevel *levels_desc_host, int n_levels, int channels, int batch_size,
                                       const float *rois, const int32_t *levels, int64_t num_rois, int pooled_h,
                                       int pooled_w, int pooled_z, int sampling_ratio, const float *grad_output,
                                       float *d_feats_all, int64_t total_rows, void *stream_) {
-  hipStream_t st = (hipStream_t)stream_;
-  PoolLevels lv;
-  const char *why = "";
-  const int rc = pool_levels(lv, levels_desc_host, n_levels, channels, batch_size, num_rois, pooled_h, pooled_w,
-                             pooled_z, true, d_feats_all, total_rows, &why);
-  AABR_CHECK_ARG(rc == 0, why);
-  AABR_CHECK_ARG(d_feats_all || total_rows == 0, "null d_feats_all");
-  if (total_rows > 0) hipMemsetAsync(d_feats_all, 0, (size_t)total_rows * channels * sizeof(float), st);
-  if (num_rois == 0 || total_rows == 0) return AABR_OK;
-  AABR_CHECK_ARG(rois && levels && grad_output, "null pointer");
-  hipLaunchKernelGGL((k_roi_pool<true, float>), dim3((unsigned)num_rois, (unsigned)ceil_div(channels, kRoiPlanes)),
-                     dim3(256), (size_t)kRoiPlanes * kRoiBins * sizeof(float), st, lv, channels, rois, levels, pooled_h,
-                     pooled_w, pooled_z, sampling_ratio, (float *)nullptr, grad_output);
-  AABR_CHECK_LAUNCH();
-  return AABR_OK;
+  return roi_pool_backward<float>(__func__, levels_desc_host, n_levels, channels, batch_size, rois, levels, num_rois,
+                                  pooled_h, pooled_w, pooled_z, sampling_ratio, grad_output, d_feats_all, total_rows,
+                                  (hipStream_t)stream_);
 }
 
 extern "C" int aabr_roi_pool_backward_bf16(const AabrRoiLevel *levels_desc_host, int n_levels, int channels,
@@ -327,4 +341,50 @@ extern "C" int aabr_roi_pool_backward_bf16(const AabrRoiLevel *levels_desc_host,
                                         pooled_w, pooled_z, sampling_ratio, grad_output, accum_f32, total_rows, stream_);
   if (rc != AABR_OK || total_rows == 0) return rc;
   return aabr_cast_storage(accum_f32, d_feats_all_bf16, total_rows * channels, 1, stream_);
+}
+
+// ---- the pooled side in bf16 (OT = __bf16): the forward's last store rounds once, the backward widens top_diff ----
+
+extern "C" int aabr_roi_pool_forward_pooled_bf16(const AabrRoiLevel *levels_desc_host, int n_levels, int channels,
+                                                 int batch_size, const float *rois, const int32_t *levels,
+                                                 int64_t num_rois, int pooled_h, int pooled_w, int pooled_z,
+                                                 int sampling_ratio, int feats_bf16, void *output_bf16, void *stream_) {
+  AABR_CHECK_ARG(levels_desc_host, "null levels_desc_host");
+  AABR_CHECK_ARG(num_rois <= 0 || rois, "null rois");
+  AABR_CHECK_ARG(num_rois <= 0 || levels, "null levels");
+  AABR_CHECK_ARG(num_rois <= 0 || output_bf16, "null output_bf16");
+  AABR_CHECK_ARG(((uintptr_t)output_bf16 & 3) == 0, "output_bf16 must be 4-byte aligned");
+  for (int l = 0; feats_bf16 && l < n_levels && l < kPoolMaxLevels; ++l)
+    AABR_CHECK_ARG(((uintptr_t)levels_desc_host[l].feats & 3) == 0, "feats must be 4-byte aligned");
+  if (feats_bf16)
+    return roi_pool_forward<__bf16, __bf16>(__func__, levels_desc_host, n_levels, channels, batch_size, rois, levels,
+                                            num_rois, pooled_h, pooled_w, pooled_z, sampling_ratio,
+                                            (__bf16 *)output_bf16, (hipStream_t)stream_);
+  return roi_pool_forward<float, __bf16>(__func__, levels_desc_host, n_levels, channels, batch_size, rois, levels,
+                                         num_rois, pooled_h, pooled_w, pooled_z, sampling_ratio, (__bf16 *)output_bf16,
+                                         (hipStream_t)stream_);
+}
+
+extern "C" int aabr_roi_pool_backward_pooled_bf16(const AabrRoiLevel *levels_desc_host, int n_levels, int channels,
+                                                  int batch_size, const float *rois, const int32_t *levels,
+                                                  int64_t num_rois, int pooled_h, int pooled_w, int pooled_z,
+                                                  int sampling_ratio, int feats_bf16, const void *grad_output_bf16,
+                                                  float *accum_f32, void *d_feats_all_bf16_or_null, int64_t total_rows,
+                                                  void *stream_) {
+  AABR_CHECK_ARG(levels_desc_host, "null levels_desc_host");
+  AABR_CHECK_ARG(num_rois <= 0 || rois, "null rois");
+  AABR_CHECK_ARG(num_rois <= 0 || levels, "null levels");
+  AABR_CHECK_ARG(num_rois <= 0 || total_rows <= 0 || grad_output_bf16, "null grad_output_bf16");
+  AABR_CHECK_ARG(((uintptr_t)grad_output_bf16 & 3) == 0, "grad_output_bf16 must be 4-byte aligned");
+  AABR_CHECK_ARG(total_rows <= 0 || accum_f32, "null accum_f32");
+  AABR_CHECK_ARG(((uintptr_t)accum_f32 & 3) == 0, "accum_f32 must be 4-byte aligned");
+  if (feats_bf16) {
+    AABR_CHECK_ARG(total_rows <= 0 || d_feats_all_bf16_or_null, "null d_feats_all_bf16 (feats_bf16 = 1)");
+    AABR_CHECK_ARG(((uintptr_t)d_feats_all_bf16_or_null & 3) == 0, "d_feats_all_bf16 must be 4-byte aligned");
+  }
+  const int rc = roi_pool_backward<__bf16>(__func__, levels_desc_host, n_levels, channels, batch_size, rois, levels,
+                                           num_rois, pooled_h, pooled_w, pooled_z, sampling_ratio,
+                                           (const __bf16 *)grad_output_bf16, accum_f32, total_rows, (hipStream_t)stream_);
+  if (rc != AABR_OK || total_rows <= 0 || !feats_bf16) return rc;
+  return aabr_cast_storage(accum_f32, d_feats_all_bf16_or_null, total_rows * channels, 1, stream_);
 }

@@ -6,6 +6,8 @@ in PostProcessor.forward (`.bbox3d` [n, 7] yx_zb).  `fused = True` (the default)
 levels in one launch, every level's gather in a second one, no host read.  `fused = False` is the reference's loop --
 torch expressions for the ROI rows and the levels, then per level nonzero / ROIAlignRotated3D / indexed write into a
 zero-filled result -- kept as the yardstick and the A/B switch, like ROIAlignRotated3D.fused.
+`pooled_dtype` (torch.float32, the default, or torch.bfloat16) is the storage of the result: the fused form writes bf16
+from its gather launch (roi_glue.pool_rois(pooled_dtype=...)), the loop casts its fp32 result once -- the same bytes.
 
 `box_scale` is an extension: the reference multiplies the boxes by SPARSE3D.VOXEL_SCALE in the feature extractor
 (convert_metric_to_pixel) before it calls the pooler; here the pooler can take the metric boxes and do it in the same
@@ -77,6 +79,7 @@ class Pooler(nn.Module):
         self.box_scale = box_scale
         self.map_levels = LevelMapper_3d(scales, canonical_size)
         self.fused = True   # False: the reference's loop (torch ROI rows / levels, per-level nonzero + ROIAlignRotated3D)
+        self.pooled_dtype = torch.float32   # torch.bfloat16: the pooled tensor (and its gradient) in bf16 storage
 
     def convert_to_roi_format(self, boxes):
         """[N, 8] ROI rows (scene, center_w, center_h, center_z, width, height, zsize, theta in degrees)"""
@@ -84,15 +87,19 @@ class Pooler(nn.Module):
             return roi_glue.roi_rows_and_levels(_bbox3d(boxes), self.scales, self.canonical_size, self.box_scale)[0]
         return torch_rois_and_levels(_bbox3d(boxes), self.scales, self.canonical_size, self.box_scale)[0]
 
-    def forward(self, x, boxes):
+    def forward(self, x, boxes, pooled_dtype=None):
+        """`pooled_dtype`: this call's storage of the result; None = the module's own `pooled_dtype`"""
+        pooled_dtype = self.pooled_dtype if pooled_dtype is None else pooled_dtype
         if len(x) != len(self.poolers):
             raise ValueError("%d feature levels for a pooler of %d" % (len(x), len(self.poolers)))
+        if pooled_dtype not in roi_glue.POOLED_DTYPES:
+            raise TypeError("Pooler: pooled_dtype must be torch.float32 or torch.bfloat16, got %r" % (pooled_dtype,))
         bbox3d = _bbox3d(boxes)
-        if len(self.poolers) == 1:
+        if len(self.poolers) == 1 and pooled_dtype == torch.float32:
             return self.poolers[0](x[0], self.convert_to_roi_format(boxes))
         if self.fused:
             return roi_glue.pool_rois(x, bbox3d, self.output_size, self.scales, self.sampling_ratio, self.canonical_size,
-                                      self.box_scale)
+                                      self.box_scale, pooled_dtype=pooled_dtype)
         rois, levels = torch_rois_and_levels(bbox3d, self.scales, self.canonical_size, self.box_scale)
         feats0 = x[0].features
         # bf16 levels are gathered into an fp32 result, as the fused form gives it
@@ -101,4 +108,4 @@ class Pooler(nn.Module):
         for level, (per_level_feature, pooler) in enumerate(zip(x, self.poolers)):
             idx_in_level = torch.nonzero(levels == level).squeeze(1)
             result[idx_in_level] = pooler(per_level_feature, rois[idx_in_level])
-        return result
+        return result.to(pooled_dtype)               # bf16: one rounding of the loop's fp32 result

@@ -6,6 +6,10 @@ shapes and initialisation are the reference's and checkpoints load by name.  `fu
 roi_glue.box_head_mlp / box_head_mlp_corner (csrc/roi_mlp.hip: dense fp32 MFMA GEMMs reading the pooled tensor, and in
 the corner form the windows of the convolution rows, in place) on those parameters; `fused = False` runs the torch
 modules themselves, the yardstick and the A/B switch, as Pooler.fused.
+`pooled_dtype` (torch.float32, the default, or torch.bfloat16) is handed to the pooler with every call -- it decides
+for the extractor's calls whatever `pooler.pooled_dtype` says, and the pooler's own attribute is left as it is --: the
+pooled tensor and its gradient in bf16 storage, read and written in place by the convolution's GEMMs; everything behind
+it stays fp32.  The torch modules are fp32, so `fused = False` refuses a bf16 pooled tensor.
 The pooler takes the metric proposals and SPARSE3D.VOXEL_SCALE (`box_scale`): convert_metric_to_pixel in its own launch.
 Not part of this package: ResNet50Conv5ROIFeatureExtractor."""
 import torch
@@ -63,6 +67,7 @@ class FPN2MLPFeatureExtractor(nn.Module):
             nn.init.kaiming_uniform_(l.weight, a=1)
             nn.init.constant_(l.bias, 0)
         self.fused = True    # False: the torch modules themselves (rocBLAS / MIOpen), the yardstick
+        self.pooled_dtype = torch.float32    # torch.bfloat16: the pooler's result in bf16 storage (fused only)
 
     @staticmethod
     def roi_separate(roi_2d):
@@ -72,6 +77,9 @@ class FPN2MLPFeatureExtractor(nn.Module):
     def head(self, x1_):
         """pooled [N, C, ph, pw, pz] -> x4 [N, MLP_HEAD_DIM]; corner form: [x_cor0, x_cor1, x_body], each that shape"""
         if not self.fused:
+            if x1_.dtype == torch.bfloat16:
+                raise TypeError("FPN2MLPFeatureExtractor.fused = False runs the torch modules on float32 parameters: a "
+                                "bfloat16 pooled tensor (pooled_dtype) needs fused = True")
             x1 = self.conv3d(x1_)
             if self.corner_roi:
                 # the reference's statements; squeeze(-1) where it has squeeze(), which also drops the ROI axis at N = 1
@@ -99,7 +107,8 @@ class FPN2MLPFeatureExtractor(nn.Module):
                                      self.fc6.bias, self.fc7.weight, self.fc7.bias)
 
     def forward(self, x0, proposals):
-        return self.head(self.pooler(x0, proposals))
+        # the extractor's attribute is the knob for its own calls: handed over per call, the pooler module is not changed
+        return self.head(self.pooler(x0, proposals, pooled_dtype=self.pooled_dtype))
 
 
 _ROI_BOX_FEATURE_EXTRACTORS = {"FPN2MLPFeatureExtractor": FPN2MLPFeatureExtractor}

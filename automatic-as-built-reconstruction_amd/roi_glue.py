@@ -679,12 +679,13 @@ def _level_table(descs):
 class _PoolRois(torch.autograd.Function):
     """every level's gather in one launch; backward: one gradient allocation for all levels, one memset, one launch.
     bf16 levels are gathered in place; their gradients are summed in an fp32 buffer and rounded once into one bf16
-    allocation (one more launch), sliced per level the same way"""
+    allocation (one more launch), sliced per level the same way.  A bf16 pooled tensor (cfg's fourth entry) is written by
+    the same launch, rounded once on its store; its bf16 gradient is widened by the backward's staging loads"""
 
     @staticmethod
     def forward(ctx, rois, levels, geom, cfg, *feats):
         lib = _hip.load()
-        output_size, sampling, nb = cfg
+        output_size, sampling, nb, pooled_dtype = cfg
         feats = [f.contiguous() for f in feats]
         C_ = int(feats[0].shape[1])
         descs, off = [], 0
@@ -693,12 +694,18 @@ class _PoolRois(torch.autograd.Function):
             descs.append((f, cm, ext, V, off, scale))
             off += V
         N = int(rois.shape[0])
-        out = torch.empty((N, C_) + tuple(output_size), dtype=torch.float32, device=rois.device)   # every element is written
+        out = torch.empty((N, C_) + tuple(output_size), dtype=pooled_dtype, device=rois.device)    # every element is written
         bf16 = feats[0].dtype == torch.bfloat16
-        forward = lib.aabr_roi_pool_forward_bf16 if bf16 else lib.aabr_roi_pool_forward
-        check(forward(_level_table(descs), len(descs), C_, nb, ptr(rois), ptr(levels), N, output_size[0],
-                      output_size[1], output_size[2], sampling, ptr(out), _hip.stream()))
-        ctx.descs, ctx.cfg, ctx.total = [(None,) + d[1:] for d in descs], (tuple(output_size), sampling, nb, C_, bf16), off
+        out16 = pooled_dtype == torch.bfloat16
+        args = (_level_table(descs), len(descs), C_, nb, ptr(rois), ptr(levels), N, output_size[0], output_size[1],
+                output_size[2], sampling)
+        if out16:
+            check(lib.aabr_roi_pool_forward_pooled_bf16(*args, int(bf16), ptr(out), _hip.stream()))
+        else:
+            forward = lib.aabr_roi_pool_forward_bf16 if bf16 else lib.aabr_roi_pool_forward
+            check(forward(*args, ptr(out), _hip.stream()))
+        ctx.descs, ctx.total = [(None,) + d[1:] for d in descs], off
+        ctx.cfg = (tuple(output_size), sampling, nb, C_, bf16, out16)
         ctx.save_for_backward(rois, levels, *feats)
         return out
 
@@ -708,12 +715,21 @@ class _PoolRois(torch.autograd.Function):
         lib = _hip.load()
         rois, levels = ctx.saved_tensors[:2]
         descs = [(f,) + d[1:] for f, d in zip(ctx.saved_tensors[2:], ctx.descs)]
-        output_size, sampling, nb, C_, bf16 = ctx.cfg
+        output_size, sampling, nb, C_, bf16, out16 = ctx.cfg
         g = grad_output.contiguous()
+        if g.dtype != (torch.bfloat16 if out16 else torch.float32):
+            raise TypeError("pool_rois backward: the gradient must have the pooled tensor's dtype, got %s" % g.dtype)
         d_all = torch.empty((ctx.total, C_), dtype=torch.float32, device=g.device)                 # zeroed by the library
-        args = (_level_table(descs), len(descs), C_, nb, ptr(rois), ptr(levels), int(rois.shape[0]), output_size[0],
-                output_size[1], output_size[2], sampling, ptr(g), ptr(d_all))
-        if bf16:                                        # d_all: the fp32 sums; one rounding into the bf16 rows
+        head = (_level_table(descs), len(descs), C_, nb, ptr(rois), ptr(levels), int(rois.shape[0]), output_size[0],
+                output_size[1], output_size[2], sampling)
+        args = head + (ptr(g), ptr(d_all))
+        if out16:                                       # the bf16 gradient is widened on load; sums as below
+            d_f32 = d_all
+            if bf16:
+                d_all = torch.empty((ctx.total, C_), dtype=torch.bfloat16, device=g.device)
+            check(lib.aabr_roi_pool_backward_pooled_bf16(*head, int(bf16), ptr(g), ptr(d_f32), ptr(d_all) if bf16 else None,
+                                                         ctx.total, _hip.stream()))
+        elif bf16:                                      # d_all: the fp32 sums; one rounding into the bf16 rows
             d_f32, d_all = d_all, torch.empty((ctx.total, C_), dtype=torch.bfloat16, device=g.device)
             check(lib.aabr_roi_pool_backward_bf16(*args, ptr(d_all), ctx.total, _hip.stream()))
         else:
@@ -722,7 +738,11 @@ class _PoolRois(torch.autograd.Function):
         return (None, None, None, None) + grads
 
 
-def pool_rois(features, proposals, output_size, scales, sampling_ratio, canonical_size, box_scale=1.0, debug=None):
+POOLED_DTYPES = (torch.float32, torch.bfloat16)      # storage of the pooled tensor and of its gradient
+
+
+def pool_rois(features, proposals, output_size, scales, sampling_ratio, canonical_size, box_scale=1.0, debug=None,
+              pooled_dtype=torch.float32):
     """features: list over levels of SparseConvNetTensor ([V_l, C] features, all fp32 or all bf16 storage -- bf16 rows are
     gathered in place, the result stays fp32, each level's gradient is bf16: fp32 sums rounded once); proposals: list over scenes of [n_b, 7]
     yx_zb device tensors; scales: each level's spatial scale relative to the box frame after `box_scale` (the
@@ -735,8 +755,14 @@ def pool_rois(features, proposals, output_size, scales, sampling_ratio, canonica
     sites, get an all-zero gradient of their own shape.  Two launches forward, a memset and one launch backward, whatever
     the level count; no host read once each grid's occupied extent and cell map are cached on its metadata (the first
     call per grid reads 16 bytes, as ROIAlignRotated3D does).  At most 8 levels and 16 scenes.  `debug` (a dict) receives
-    `rois` [N, 8] and `levels` [N] int32."""
+    `rois` [N, 8] and `levels` [N] int32.
+
+    `pooled_dtype=torch.bfloat16` (fp32 or bf16 levels alike; any dtype but these two raises TypeError): the result is
+    stored in bf16, each element the fp32 value rounded once (nearest even) by the same launch, and the backward takes a
+    bf16 gradient, widened on load -- the sums, the atomics and the levels' gradients are as above."""
     from maskrcnn_benchmark.layers.roi_align_rotated_3d import _cellmap, _occupied_extent
+    if pooled_dtype not in POOLED_DTYPES:
+        raise TypeError("pool_rois: pooled_dtype must be torch.float32 or torch.bfloat16, got %r" % (pooled_dtype,))
     _pool_check(features, proposals, output_size, scales)
     if len(proposals) == 0:
         raise ValueError("no scenes")
@@ -753,7 +779,7 @@ def pool_rois(features, proposals, output_size, scales, sampling_ratio, canonica
         ext = _occupied_extent(x)                                       # (x, y, z, batch), cached per grid
         geom.append((_cellmap(x, ext), tuple(int(v) for v in ext), float(scale)))
     nb = max([len(proposals)] + [g[1][3] for g in geom])             # scenes: the proposals' or the maps', whichever is more
-    cfg = (tuple(int(v) for v in output_size), int(sampling_ratio), nb)
+    cfg = (tuple(int(v) for v in output_size), int(sampling_ratio), nb, pooled_dtype)
     return _PoolRois.apply(rois, levels, geom, cfg, *[x.features for x in features])
 
 
@@ -761,12 +787,16 @@ class _Mlp(torch.autograd.Function):
     """one dense layer act(A W^T + bias) over csrc/roi_mlp.hip.  `pooled` = (hw, pz): A is the pooler's [n, C, ..., pz]
     tensor read in place (rows n hw + s, columns c pz + z).  `perm_hw` > 0: `weight` is fc6's [N, R hw] in the reference's
     column order r hw + s while A's columns are s R + r -- the weight is packed once (one launch), both GEMMs that read it
-    run on the packed copy, and the weight gradient is stored through the inverse permutation."""
+    run on the packed copy, and the weight gradient is stored through the inverse permutation.  A bf16 `a` (pooled
+    only) is read in place by the _pooled_bf16 entry points and its gradient is written in bf16; all else stays fp32."""
 
     @staticmethod
     def forward(ctx, a, weight, bias, relu, pooled, perm_hw):
         lib = _hip.load()
         dev = a.device
+        a16 = a.dtype == torch.bfloat16
+        if a16 and pooled is None:
+            raise TypeError("a bfloat16 operand is taken in the pooled layout only")
         a, weight = a.contiguous(), weight.contiguous()
         bias = bias.contiguous() if bias is not None else None
         N, K = int(weight.shape[0]), int(weight.shape[1])
@@ -780,10 +810,14 @@ class _Mlp(torch.autograd.Function):
             w_used = torch.empty_like(weight)
             check(lib.aabr_roi_mlp_pack_fc6(ptr(weight), N, K // perm_hw, perm_hw, ptr(w_used), _hip.stream()))
         y = torch.empty((M, N), dtype=torch.float32, device=dev)                      # every element is written
-        check(lib.aabr_roi_mlp_forward(ptr(a), layout, hw, pz, ptr(w_used), ptr(bias), int(relu), M, N, K, ptr(y),
-                                       _hip.stream()))
+        if a16:
+            check(lib.aabr_roi_mlp_forward_pooled_bf16(ptr(a), hw, pz, ptr(w_used), ptr(bias), int(relu), M, N, K, ptr(y),
+                                                       _hip.stream()))
+        else:
+            check(lib.aabr_roi_mlp_forward(ptr(a), layout, hw, pz, ptr(w_used), ptr(bias), int(relu), M, N, K, ptr(y),
+                                           _hip.stream()))
         ctx.save_for_backward(a, w_used, y if relu else None)
-        ctx.cfg = (layout, hw, pz, M, N, K, int(perm_hw), bias is not None)
+        ctx.cfg = (layout, hw, pz, M, N, K, int(perm_hw), bias is not None, a16)
         return y
 
     @staticmethod
@@ -791,21 +825,29 @@ class _Mlp(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _hip.load()
         a, w_used, y = ctx.saved_tensors
-        layout, hw, pz, M, N, K, perm_hw, has_bias = ctx.cfg
+        layout, hw, pz, M, N, K, perm_hw, has_bias, a16 = ctx.cfg
         dy = dy.contiguous()
         dev = dy.device
         d_a = d_w = d_b = None
         if ctx.needs_input_grad[0]:
             d_a = torch.empty_like(a)                                                  # every element is written
-            check(lib.aabr_roi_mlp_backward_input(ptr(dy), ptr(y), ptr(w_used), M, N, K, layout, hw, pz, ptr(d_a),
-                                                  _hip.stream()))
+            if a16:
+                check(lib.aabr_roi_mlp_backward_input_pooled_bf16(ptr(dy), ptr(y), ptr(w_used), M, N, K, hw, pz, ptr(d_a),
+                                                                  _hip.stream()))
+            else:
+                check(lib.aabr_roi_mlp_backward_input(ptr(dy), ptr(y), ptr(w_used), M, N, K, layout, hw, pz, ptr(d_a),
+                                                      _hip.stream()))
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
             d_w = torch.empty((N, K), dtype=torch.float32, device=dev)
             d_b = torch.empty(N, dtype=torch.float32, device=dev) if has_bias else None
             floats = int(lib.aabr_roi_mlp_dw_scratch_floats(M, N, K))
             scr = _hip.workspace("roi_mlp_dw", floats, torch.float32, dev) if floats else None
-            check(lib.aabr_roi_mlp_backward_weight(ptr(dy), ptr(y), ptr(a), layout, hw, pz, M, N, K, perm_hw, ptr(d_w),
-                                                   ptr(d_b), ptr(scr), _hip.stream()))
+            if a16:
+                check(lib.aabr_roi_mlp_backward_weight_pooled_bf16(ptr(dy), ptr(y), ptr(a), hw, pz, M, N, K, perm_hw,
+                                                                   ptr(d_w), ptr(d_b), ptr(scr), _hip.stream()))
+            else:
+                check(lib.aabr_roi_mlp_backward_weight(ptr(dy), ptr(y), ptr(a), layout, hw, pz, M, N, K, perm_hw, ptr(d_w),
+                                                       ptr(d_b), ptr(scr), _hip.stream()))
         return d_a, d_w, d_b, None, None, None
 
 
@@ -813,6 +855,19 @@ def _mlp_f32(name, **tensors):
     for k, t in tensors.items():
         if t is not None and t.dtype != torch.float32:
             raise TypeError("%s: %s must be float32, got %s (bf16 is not part of this path)" % (name, k, t.dtype))
+
+
+def _pooled_f32_or_bf16(name, pooled):
+    """the one tensor of the head that may be bf16: the device pooler's result (pool_rois(pooled_dtype=torch.bfloat16)).
+    A bf16 tensor that is not on the device is no such result and is refused as a dtype error, before the GPU is needed.
+    This is a device condition reported as a TypeError on purpose: without it a host bf16 tensor would get as far as
+    require_gpu and fail there with a RuntimeError, as a host fp32 tensor does, and the package's rule that bf16 outside
+    the device path is a dtype error raised before the GPU is needed (tests/test_roi_mlp_host.py) would no longer hold"""
+    if pooled.dtype not in POOLED_DTYPES:
+        raise TypeError("%s: pooled must be float32 or bfloat16, got %s" % (name, pooled.dtype))
+    if pooled.dtype == torch.bfloat16 and not pooled.is_cuda:
+        raise TypeError("%s: a bfloat16 pooled tensor is taken from the device pooler only "
+                        "(pool_rois(pooled_dtype=torch.bfloat16)); got one on %s" % (name, pooled.device))
 
 
 def dense_linear(x, weight, bias=None, relu=False):
@@ -842,9 +897,11 @@ def box_head_mlp(pooled, conv_w, conv_b, bn_w, bn_b, bn_state, fc6_w, fc6_b, fc7
     value, so it receives 1 - momentum), `training`, `track_running_stats`, and `running_mean` / `running_var` (updated
     in place in training; None without tracking).  Without tracking the batch statistics serve in both modes.
     6 launches forward (GEMM, BatchNorm 2, pack, GEMM, GEMM; box_predictions adds a seventh and two torch.cat copies),
-    whatever N."""
-    _mlp_f32("box_head_mlp", pooled=pooled, conv_w=conv_w, conv_b=conv_b, bn_w=bn_w, bn_b=bn_b, fc6_w=fc6_w, fc6_b=fc6_b,
+    whatever N.  `pooled` may be bf16 (pool_rois(pooled_dtype=torch.bfloat16)): the convolution's GEMMs read it and write
+    its gradient in place in bf16; every other tensor, the parameters and the result stay fp32."""
+    _mlp_f32("box_head_mlp", conv_w=conv_w, conv_b=conv_b, bn_w=bn_w, bn_b=bn_b, fc6_w=fc6_w, fc6_b=fc6_b,
              fc7_w=fc7_w, fc7_b=fc7_b)
+    _pooled_f32_or_bf16("box_head_mlp", pooled)
     n, ph, pw, R = _conv_shape(pooled, conv_w)
     hw = ph * pw
     if tuple(fc6_w.shape) != (int(fc6_w.shape[0]), R * hw):
@@ -881,7 +938,7 @@ def _conv_bn_rows(pooled, conv_w, conv_b, bn_w, bn_b, bn_state):
     else:                                                  # the kernel's running-statistics update lands in scratch
         rm = _hip.workspace("roi_mlp_bn", 2 * R, torch.float32, pooled.device)
         rm, rv = rm[:R], rm[R:2 * R]
-    empty = pooled.new_empty(0)
+    empty = x1.new_empty(0)
     return BatchNormFunction.apply(x1, empty if bn_w is None else bn_w, empty if bn_b is None else bn_b, rm, rv,
                                    (float(bn_state["eps"]), 1.0 - float(bn_state["momentum"]), train, 0))
 
@@ -969,9 +1026,10 @@ def box_head_mlp_corner(pooled, conv_w, conv_b, bn_w, bn_b, bn_state, fc6_cor_w,
     of `.contiguous().view(N, -1)`).  Convolution and BatchNorm as box_head_mlp; the windows are never made contiguous.
     9 launches forward (GEMM, BatchNorm 2, pack 2, fc6 2, fc7 2), whatever N; N = 1 is the unsqueezed case (the
     reference's squeeze() drops the ROI axis there)."""
-    _mlp_f32("box_head_mlp_corner", pooled=pooled, conv_w=conv_w, conv_b=conv_b, bn_w=bn_w, bn_b=bn_b,
+    _mlp_f32("box_head_mlp_corner", conv_w=conv_w, conv_b=conv_b, bn_w=bn_w, bn_b=bn_b,
              fc6_cor_w=fc6_cor_w, fc6_cor_b=fc6_cor_b, fc6_body_w=fc6_body_w, fc6_body_b=fc6_body_b, fc7_cor_w=fc7_cor_w,
              fc7_cor_b=fc7_cor_b, fc7_body_w=fc7_body_w, fc7_body_b=fc7_body_b)
+    _pooled_f32_or_bf16("box_head_mlp_corner", pooled)
     n, ph, pw, R = _conv_shape(pooled, conv_w)
     if pw != CORNER_PW:
         raise ValueError("the corner windows need pw == %d, got pooled %s" % (CORNER_PW, tuple(pooled.shape)))

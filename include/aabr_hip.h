@@ -49,7 +49,9 @@ const char *aabr_last_error(void);
  * three new symbols and one new record.  The RPN with separated-classifier groups (aabr_rpn_head_grouped_*,
  * aabr_rpn_loss_grouped_*): six new symbols; the plain entry points run the same kernels and give the same bits.  The batched
  * input layer (aabr_bl_input_layer_sites, aabr_bl_points_prepare, aabr_quantize_scenes_bl): three new symbols; the flat
- * entry points run the same kernel bodies through the flat reader and give the same bits. */
+ * entry points run the same kernel bodies through the flat reader and give the same bits.  bf16 storage of the pooled ROI
+ * tensor and its gradient (aabr_roi_pool_*_pooled_bf16, aabr_roi_mlp_*_pooled_bf16): five new symbols, AabrRoiLevel
+ * unchanged; the fp32 entry points run the instances they ran before. */
 #define AABR_ABI_VERSION 640
 int aabr_version(void);
 /* Tuning knobs for experiments and tests (no counterpart in the reference; the defaults are what ships): CONV_WIDE,
@@ -1100,6 +1102,26 @@ int aabr_roi_pool_backward_bf16(const AabrRoiLevel *levels_desc_host, int n_leve
                                 const float *rois, const int32_t *levels, int64_t num_rois, int pooled_h, int pooled_w,
                                 int pooled_z, int sampling_ratio, const float *grad_output, float *accum_f32,
                                 void *d_feats_all_bf16, int64_t total_rows, void *stream);
+/* bf16 storage of the POOLED tensor and of its gradient (the same kernel, the pooled side's storage a template
+ * parameter); feats_bf16 = 0 / 1 tells the storage of AabrRoiLevel.feats, as the two pairs above.
+ * aabr_roi_pool_forward_pooled_bf16: output_bf16 [num_rois, channels, ph, pw, pz] in bf16 = ONE rounding (nearest even)
+ *   of each fp32 value aabr_roi_pool_forward / _forward_bf16 stores; the zeros of a missing level are bf16 zeros; every
+ *   element is written.                                                                                  1 launch.
+ * aabr_roi_pool_backward_pooled_bf16: grad_output_bf16 in the same layout is widened on load (exact); atomics, their
+ *   operands and the fp32 accumulation into accum_f32 [total_rows, channels] are aabr_roi_pool_backward's.
+ *   feats_bf16 = 0: accum_f32 is the result, d_feats_all_bf16_or_null is not read.            1 memset + 1 launch.
+ *   feats_bf16 = 1: the sums are rounded once into d_feats_all_bf16_or_null [total_rows, channels], as
+ *   aabr_roi_pool_backward_bf16 does.                                                       1 memset + 2 launches.
+ * A null pointer, or a bf16 pointer that is not 4-byte aligned, is AABR_EINVAL before any launch.                    */
+int aabr_roi_pool_forward_pooled_bf16(const AabrRoiLevel *levels_desc_host, int n_levels, int channels, int batch_size,
+                                      const float *rois, const int32_t *levels, int64_t num_rois, int pooled_h,
+                                      int pooled_w, int pooled_z, int sampling_ratio, int feats_bf16, void *output_bf16,
+                                      void *stream);
+int aabr_roi_pool_backward_pooled_bf16(const AabrRoiLevel *levels_desc_host, int n_levels, int channels, int batch_size,
+                                       const float *rois, const int32_t *levels, int64_t num_rois, int pooled_h,
+                                       int pooled_w, int pooled_z, int sampling_ratio, int feats_bf16,
+                                       const void *grad_output_bf16, float *accum_f32, void *d_feats_all_bf16_or_null,
+                                       int64_t total_rows, void *stream);
 
 /* ---- RPN loss (csrc/rpn_loss.hip): RPNLossComputation.__call__ (modeling/rpn/loss_3d.py:201-251), one objectness group.
  * Per example the BalancedPositiveNegativeSampler (modeling/balanced_positive_negative_sampler.py:19-68):
@@ -1432,7 +1454,8 @@ int aabr_roi_post_detections_grouped(const float *class_logits, const float *box
 
 /* ---- the box head's dense layers (csrc/roi_mlp.hip): FPN2MLPFeatureExtractor after its pooler
  * (roi_box_feature_extractors.py:46-169: Conv3d([1,1,pz]) + BatchNorm3d + ReLU, fc6 + ReLU, fc7 + ReLU) and FPNPredictor
- * (roi_box_predictors.py:34-109) as a dense fp32 GEMM family on v_mfma_f32_32x32x2_f32 (fp32 storage only, exact fp32:
+ * (roi_box_predictors.py:34-109) as a dense fp32 GEMM family on v_mfma_f32_32x32x2_f32 (fp32 storage, the pooled operand
+ * also in bf16 through the _pooled_bf16 entry points below; exact fp32:
  * every result element is an fmaf chain over its reduction).  A layer is Y [M, N] = act(A W^T + bias) with W [N, K]
  * row-major, the reference's parameter layout (nn.Linear.weight; Conv3d.weight viewed as [R, C pz]).
  *   shapes: any M >= 0 (M == 0 launches no kernel and succeeds; the weight gradient of M == 0 is a memset to zero), any
@@ -1481,6 +1504,19 @@ int aabr_roi_mlp_backward_weight(const float *dY, const float *Y, const float *A
                                  int64_t M, int64_t N, int64_t K, int64_t perm_hw, float *dW, float *db, float *scratch,
                                  void *stream);
 int aabr_roi_mlp_pack_fc6(const float *W, int64_t N, int64_t R, int64_t hw, float *Wp, void *stream);
+/* The pooled operand in bf16 storage, read and written in place: each mirrors its namesake above with a_layout fixed to
+ * AABR_MLP_POOLED.  A_bf16 / dA_bf16 are the pooler's [n, C, hw, pz] tensor in bf16 (aabr_roi_pool_*_pooled_bf16), 4-byte
+ * aligned; an element is widened on load (exact), the LDS image, the MFMA chain, the mask, the bias and the ReLU are the
+ * fp32 form's, so Y, dW and db are bit for bit what the fp32 form gives on the widened tensor, and dA_bf16 is ONE rounding
+ * (nearest even) of the fp32 form's dA, every element written once.  dY, Y, W, dW, db and scratch stay fp32.  Tile,
+ * splits, scratch size, launch counts and shape checks are those of the fp32 forms at the same (M, N, K).            */
+int aabr_roi_mlp_forward_pooled_bf16(const void *A_bf16, int64_t hw, int pz, const float *W, const float *bias, int relu,
+                                     int64_t M, int64_t N, int64_t K, float *Y, void *stream);
+int aabr_roi_mlp_backward_input_pooled_bf16(const float *dY, const float *Y, const float *W, int64_t M, int64_t N,
+                                            int64_t K, int64_t hw, int pz, void *dA_bf16, void *stream);
+int aabr_roi_mlp_backward_weight_pooled_bf16(const float *dY, const float *Y, const void *A_bf16, int64_t hw, int pz,
+                                             int64_t M, int64_t N, int64_t K, int64_t perm_hw, float *dW, float *db,
+                                             float *scratch, void *stream);
 /* fc6 over WINDOWS of the convolution rows: the corner form of the box head (MODEL.CORNER_ROI,
  * roi_box_feature_extractors.py:122-147).  X is the convolution + BatchNorm result kept as rows [n_rois ph pw, R]; the
  * extractor cuts the pw (= 11) axis into cor0 = w 0..2, body = w 2..8, cor1 = w 8..10 and runs an fc6 on each part made
