@@ -319,6 +319,8 @@ _SIGS = {
     "aabr_det_eval_scan_chunk": (C.c_int, []),
     "aabr_pool_gather": (C.c_int, [_vp, _i32, _i64, _i32, _i32, _vp, _i32, _i64, _i32, _f32, _vp, _i64, _i32, _i32, _vp]),
     "aabr_pool_max_backward": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _i32, _i64, _vp, _vp]),
+    "aabr_merge_corners_max_walls": (C.c_int, []),
+    "aabr_merge_walls_by_corners": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _vp]),
 }
 MLP_ROWS, MLP_POOLED = 0, 1     # include/aabr_hip.h AABR_MLP_ROWS / AABR_MLP_POOLED
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))

@@ -3,8 +3,10 @@ class logits, box regression and the proposals of a batch -> per scene the final
 The reference loops over scenes and classes in Python; here the whole batch is one call of roi_glue.box_detections
 (csrc/roi_post.hip).  `boxes` is duck-typed (`.bbox3d` [n, 7] yx_zb, `.size3d`, `len()`); the result is a small list
 object with the surface structures/boxlist_ops_3d.py names -- not a port of BoxList3D.  The coder may be the centroid or
-the corner form (MODEL.CORNER_ROI): the kernel decodes in the form of the BoxCoder3D it is given.  `merge_by_corners`
-(MERGE_BY_CORNER = 0 upstream) is not part of this path."""
+the corner form (MODEL.CORNER_ROI): the kernel decodes in the form of the BoxCoder3D it is given.  `merge_by_corner=True`
+(the reference's MERGE_BY_CORNER switch, inference.py:15,82-83; here the optional key MODEL.ROI_HEADS.MERGE_BY_CORNER, off by
+default) passes the detections of the whole batch through roi_glue.merge_by_corners (csrc/merge_corners.hip), one more
+launch, before the lists are built."""
 import torch
 from torch import nn
 
@@ -47,7 +49,7 @@ class DetectionList3D(object):
 
 class PostProcessor(nn.Module):
     def __init__(self, score_thresh=0.05, nms=0.5, nms_aug_thickness=None, detections_per_img=100, box_coder=None,
-                 class_specific=True):
+                 class_specific=True, merge_by_corner=False):
         super(PostProcessor, self).__init__()
         self.score_thresh = score_thresh
         self.nms = nms
@@ -60,6 +62,7 @@ class PostProcessor(nn.Module):
         self.box_coder = box_coder
         self.nms_aug_thickness = nms_aug_thickness
         self.class_specific = class_specific
+        self.merge_by_corner = bool(merge_by_corner)
 
     def forward(self, x, boxes):
         """x = (class_logits [N, C], box_regression [N, 7 C] or [N, 7], corners_semantic (unused, as upstream));
@@ -69,6 +72,10 @@ class PostProcessor(nn.Module):
             class_logits, box_regression, [b.bbox3d for b in boxes], score_thresh=self.score_thresh, nms=self.nms,
             nms_aug_thickness=self.nms_aug_thickness, detections_per_img=self.detections_per_img,
             class_specific=bool(self.class_specific), box_coder=self.box_coder)
+        if self.merge_by_corner:
+            merged = roi_glue.merge_by_corners([d["bbox3d"] for d in dets], [d["labels"] for d in dets])
+            for d, m in zip(dets, merged):
+                d["bbox3d"] = m
         return [DetectionList3D(d["bbox3d"], b.size3d, {"scores": d["scores"], "labels": d["labels"], "rows": d["rows"]})
                 for d, b in zip(dets, boxes)]
 
@@ -79,4 +86,5 @@ def make_roi_box_post_processor(cfg):
     return PostProcessor(cfg.MODEL.ROI_HEADS.SCORE_THRESH, cfg.MODEL.ROI_HEADS.NMS,
                          nms_aug_thickness=cfg.MODEL.ROI_HEADS.NMS_AUG_THICKNESS_Y_Z,
                          detections_per_img=cfg.MODEL.ROI_HEADS.DETECTIONS_PER_IMG, box_coder=box_coder,
-                         class_specific=cfg.MODEL.CLASS_SPECIFIC)
+                         class_specific=cfg.MODEL.CLASS_SPECIFIC,
+                         merge_by_corner=bool(getattr(cfg.MODEL.ROI_HEADS, "MERGE_BY_CORNER", False)))

@@ -12,6 +12,8 @@ roi_box_predictors.py:105-109).  The corner form of the head (MODEL.CORNER_ROI):
 of the convolution rows, forward_corner_box, roi_box_feature_extractors.py:122-147) and `box_predictions_corner`
 (roi_box_predictors.py:79-103); `box_head_targets` / `box_detections` take the coder's form from the BoxCoder3D they are
 given."""
+import itertools
+
 import torch
 
 import _hip
@@ -172,6 +174,60 @@ def _detections(class_logits, box_regression, proposals, sep_id, tables, class_s
         return out
 
     return finish if defer else finish()
+
+
+def merge_corners_max_walls():
+    """walls (and, the wall count being known on the device only, rows) per scene that csrc/merge_corners.hip is built for"""
+    return int(_hip.load().aabr_merge_corners_max_walls())
+
+
+def merge_by_corners(bbox3d_list, labels_list=None, threshold=0.1, wall_label=1, return_merged=False):
+    """merge_by_corners of the reference (maskrcnn_benchmark/structures/bounding_box_3d.py:843-923) for a list of scenes in
+    ONE launch (csrc/merge_corners.hip, aabr_merge_walls_by_corners; the definition is in include/aabr_hip.h).
+
+    bbox3d_list: per scene [n_b, 7] yx_zb; labels_list: per scene [n_b] labels -- the rows with `wall_label` are the
+    scene's walls -- or None: every row is a wall (merge_walls_by_corners).  Wall ends closer than `threshold` are
+    snapped to their mean in the reference's sequential order and the walls rebuilt from the snapped corners; every wall
+    of a scene takes the scene's mean z0, as upstream.  Returns the list of new [n_b, 7] tensors (other rows: the
+    input's bits); with return_merged also the list of [n_b, 2] int32 flags (1: that corner of the wall was merged).
+    No host read.  ValueError before any device call for lists of different length, a shape that is not [n, 7], labels
+    that do not match their boxes, or a scene with more rows than merge_corners_max_walls()."""
+    bbox3d_list = list(bbox3d_list)
+    if labels_list is not None:
+        labels_list = list(labels_list)
+        if len(labels_list) != len(bbox3d_list):
+            raise ValueError("merge_by_corners: %d box lists and %d label lists" % (len(bbox3d_list), len(labels_list)))
+    n_b = []
+    for b, boxes in enumerate(bbox3d_list):
+        if boxes.dim() != 2 or boxes.shape[1] != 7:
+            raise ValueError("merge_by_corners: scene %d: boxes must be [n, 7] yx_zb, got %s" % (b, tuple(boxes.shape)))
+        if labels_list is not None and labels_list[b].numel() != boxes.shape[0]:
+            raise ValueError("merge_by_corners: scene %d has %d boxes and %d labels"
+                             % (b, boxes.shape[0], labels_list[b].numel()))
+        n_b.append(int(boxes.shape[0]))
+    limit = merge_corners_max_walls()
+    if n_b and max(n_b) > limit:
+        raise ValueError("merge_by_corners: scene %d has %d rows; the kernel is built for at most %d walls per scene, and "
+                         "a scene's wall count is known on the device only, so its row count is held to that limit"
+                         % (n_b.index(max(n_b)), max(n_b), limit))
+    if not n_b:
+        return ([], []) if return_merged else []
+    _hip.require_gpu(bbox3d_list[0])
+    dev = bbox3d_list[0].device
+    N = sum(n_b)
+    boxes = torch.cat([b.reshape(-1, 7) for b in bbox3d_list]).to(device=dev, dtype=torch.float32).contiguous()
+    labels = None
+    if labels_list is not None:
+        labels = torch.cat([l.reshape(-1) for l in labels_list]).to(device=dev, dtype=torch.int64).contiguous()
+    out = torch.empty_like(boxes)
+    merged = torch.empty((N, 2), dtype=torch.int32, device=dev) if return_merged else None
+    if N > 0:
+        begin = torch.tensor([0] + list(itertools.accumulate(n_b)), dtype=torch.int64).to(dev)   # host lengths: no read
+        check(_hip.load().aabr_merge_walls_by_corners(ptr(boxes), ptr(labels), N, ptr(begin), len(n_b), max(n_b),
+                                                      int(wall_label), float(threshold), ptr(out), ptr(merged),
+                                                      _hip.stream()))
+    outs = list(torch.split(out, n_b))
+    return (outs, list(torch.split(merged, n_b))) if return_merged else outs
 
 
 def _targets_inputs(proposals, targets, target_labels, aug_thickness, weights, box_coder, seed):

@@ -1745,6 +1745,33 @@ int aabr_pool_gather(const void *src, int bf16, int64_t src_stride, int col0, in
 int aabr_pool_max_backward(const void *x, const void *y, const void *dy, int bf16, int64_t x_stride, int col0, int planes,
                            const int32_t *table_in, int vol, int64_t rows_in, void *dx, void *stream);
 
+/* ---- merging wall detections by their corners (csrc/merge_corners.hip, csrc/merge_corners.h): merge_by_corners /
+ * merge_walls_by_corners of the reference (maskrcnn_benchmark/structures/bounding_box_3d.py:843-923) for every scene of
+ * a call in ONE launch, one workgroup per scene; no host read; no atomics: bit-identical run to run.
+ *
+ * boxes fp32 [n, 7] yx_zb, scene-major; labels int64 [n] (NULL: every row is a wall); scene_begin: DEVICE int64 array of
+ * n_scenes + 1 ascending row offsets (first 0, last n), formed by the caller from list lengths it knows on the host;
+ * max_scene_rows: the largest scene's row count (host).  The rows of a scene with labels == wall_label are its walls, in
+ * ascending row order; wall w has corners 2w and 2w+1.
+ *   1. per wall yxzb_to_2corners and corners_top_offseted: the two top corners pulled in by half the thickness;
+ *   2. for i = 0 .. 2W-1 on the corners as the earlier steps left them: S = every corner closer to corner i than
+ *      `threshold` (distance sqrt(fma(dz,dz,fma(dy,dy,dx*dx))), strict <), without the other corner of i's wall; a wall
+ *      with both corners in S skips the step; otherwise, with |S| > 1, every corner of S takes the mean of S (summed in
+ *      ascending corner index from 0, one fp32 addition at a time, one division by |S|) and is flagged merged;
+ *   3. per wall both corners are pushed outward from their midpoint by half the thickness; x0 y0 x1 y1 from the pushed
+ *      corners, z1 = the mean of their z, z0 of EVERY wall = the scene's mean z0 (summed in ascending wall order),
+ *      corners_to_yxzb.  A wall whose corners end at one point divides by zero and gives the IEEE result.
+ * boxes_out fp32 [n, 7] (not boxes itself): the walls rebuilt, every other row copied bit for bit.  merged (optional, NULL)
+ * int32 [n, 2]: 1 where a wall's corner 0 / 1 was merged, 0 elsewhere and for rows that are no wall.  W = 1 runs 1 and 3.
+ * aabr_merge_corners_max_walls(): the walls per scene the kernel's LDS image is built for (2048).  A scene's wall count is
+ * known on the device only, so its ROW count is held to that limit: max_scene_rows beyond it is refused, never truncated.
+ * Refused with AABR_EINVAL before any launch: that, a negative count, 2^28 or more rows, max_scene_rows > n, rows without
+ * a scene, a null pointer with rows > 0, boxes_out == boxes.  n_scenes == 0: AABR_OK without a launch.                   */
+int aabr_merge_corners_max_walls(void);
+int aabr_merge_walls_by_corners(const float *boxes, const int64_t *labels, int64_t n, const int64_t *scene_begin,
+                                int64_t n_scenes, int64_t max_scene_rows, int64_t wall_label, float threshold,
+                                float *boxes_out, int32_t *merged, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
