@@ -24,7 +24,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
   X(CONV_WLDS) X(CONV_SMALL) X(CONV_NBW) X(CONV_WPB) X(WIDE_ROWS) X(CONV_WIDE) X(WIDE_NBUF) X(CONV_WIDE_BF16)         \
   X(VOXEL_MEAN) X(WIDE_NCB) X(BN_SMALL) X(WIDE_PRIO) X(PLAN_SIDE_BATCH) X(PLAN_SIDE_PRIO) X(SMALL_WPB) X(SMALL_MAX)   \
   X(WIDE_SPLIT) X(SPLIT_TARGET) X(SPLIT_NBUF) X(SPLIT_MIN_ITEMS) X(CONV_NARROW) X(DW_FULL) X(DW_FULL_MIN) X(DW_FULL_WGS) X(DW_VEC) X(SPLIT_ROWS) X(GEOM_JOBS)      \
-  X(CONV_SINGLE) X(SINGLE_ROWS) X(SINGLE_CHUNK) X(SINGLE_BWD_STATS) X(PLAN_TAIL)
+  X(CONV_SINGLE) X(SINGLE_ROWS) X(SINGLE_CHUNK) X(SINGLE_BWD_STATS) X(PLAN_TAIL) X(WIDE_XOFF)
 #define AABR_KNOB_ENUM(n) K_##n,
 enum Knob { AABR_KNOB_LIST(AABR_KNOB_ENUM) K_COUNT };
 #undef AABR_KNOB_ENUM

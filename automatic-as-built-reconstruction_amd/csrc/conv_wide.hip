@@ -24,6 +24,7 @@
 #include "common.h"
 #include "conv_wide_tiles.h"   // kWS, kMaxVol, kMaxTileRows, wide_words and the launch decision
 #include <stdlib.h>
+#include <type_traits>
 
 namespace aabr {
 
@@ -132,8 +133,10 @@ struct BnBwdStats {
 // a three-term split (profiles/r03_conv_x3_ab.txt), a fourth resident workgroup through a two-slot operand ring
 // (r04_conv_occ4_ab.txt), the tile rows as the MFMA chains' starting accumulators (r04_conv_bf16_defer_ab.txt), eight-wave
 // workgroups on 128-column slabs (r04_conv_bf16_w8_ab.txt), the row-stationary kernel (r03_conv_rs_ab.txt).
-template <int KG, int DBG, int NBUF, bool BF = false, int NCB = 1, int NSET = 2>
-__global__ __launch_bounds__(256, NBUF == 2 ? 2 : 3) void k_conv_cs(const float *__restrict__ in, int ci, int64_t in_bytes,
+// XO (fp32, KG <= 2, plain launches; WIDE_XOFF knob): a step takes the tile's blocks (b, b + 1) whatever their offsets --
+// see the step loop below and DESIGN.md section 3.  The compiled stream, the tile, the grid and the LDS are the same.
+template <int KG, int DBG, int NBUF, bool BF = false, int NCB = 1, int NSET = 2, bool XO = false>
+__global__ __launch_bounds__(256, XO ? 4 : NBUF == 2 ? 2 : 3) void k_conv_cs(const float *__restrict__ in, int ci, int64_t in_bytes,
                                                     float *__restrict__ out, int co, int64_t V_out,
                                                     const int32_t *__restrict__ words, int64_t words_bytes, int vol,
                                                     int wflip, const float *__restrict__ Wp, int64_t wp_bytes,
@@ -292,10 +295,151 @@ __global__ __launch_bounds__(256, NBUF == 2 ? 2 : 3) void k_conv_cs(const float 
   };
   int par = 0;
   long long dbg_t[5] = {0, 0, 0, 0, 0};
+  // XO: steps over the tile's block list.  On the 64-plane levels a 112-row tile holds ~8 pairs per non-centre offset: one
+  // half-full block each, and a step per offset pays the whole skeleton (entry loads, gather, stage store, read-add-write,
+  // barrier) for 16 MFMAs per wave.  Here step s takes blocks (2s, 2s + 1) of the stream as k_build_tileT wrote it; block
+  // b's offset is the k with pre[k] <= b < pre[k + 1], so empty offsets vanish and only the tile's last block can lack a
+  // partner (block A again with the discard bit, as above).  One channel group (KG = nkc), one part.
+  //   weights: two register sets with fixed roles, block A's offset and block B's.  Each is refilled with the NEXT step's
+  //   offset right after its last MFMA of this step, unconditionally (where the offset stays, the same bytes again from
+  //   L2): A's refill has B's MFMAs, the step's tail and the next step's start to arrive, B's the next A's MFMAs on top.
+  //   One step body per gather set, every load unconditional and into named registers: exact vmcnt waits.  (A ring of
+  //   three sets with the body copied per set and kind of step was built first: the compiler joined the 24 copies in one
+  //   latch and moved every just-loaded set behind s_waitcnt vmcnt(0); profiles/conv_wide_instances.txt.)
+  //   accumulate: two blocks of different offsets can name the same output row (a submanifold book: usually do), so A's
+  //   read-add-write goes before B's; LDS operations of a wave retire in order.  Per output element the sum order is
+  //   still offset ascending, each term one MFMA chain from zero: the same bits as the loop below.
+  //   entries: the step's 32 words are 128 contiguous bytes: one load (word lane & 31), three cross-lane reads.
+  if constexpr (XO) {
+    static_assert(!BF && NCB == 1 && NSET == 2 && DBG == 0 && KG <= 2, "the cross-offset step exists for fp32, KG <= 2");
+    const int nblk = nblk_all;
+    struct XPos { int b, ka, kb; };        // blocks (b, b + 1) and their offsets; b >= nblk: past the end
+    auto off_from = [&](int k, int b) { while (pre_of(k + 1) <= b) ++k; return k; };   // b < nblk
+    auto xadv = [&](XPos q) {
+      if (q.b >= nblk) return q;
+      q.b += 2;
+      if (q.b >= nblk) { q.b = nblk; return q; }
+      q.ka = off_from(q.kb, q.b);
+      q.kb = q.b + 1 < nblk ? off_from(q.ka, q.b + 1) : q.ka;
+      return q;
+    };
+    struct XEnt { int w, hb; };            // word (lane & 31) of the step's 32 entries; hb (wave-uniform): block B exists
+    XPos pp[NSET + 2];
+    XEnt ee[NSET + 2];
+    auto xent_of = [&](const XPos &q) {
+      const int b = q.b < nblk ? q.b : pp[0].b;
+      XEnt e;
+      e.w = (int)__builtin_amdgcn_raw_buffer_load_b32(rwords, (unsigned)(lane & 31) * 4u, ebase + (unsigned)b * 64u, 0);
+      e.hb = b + 1 < nblk ? 1 : 0;
+      return e;
+    };
+    // an unpaired block: the upper 16 rows of the pair are block A's again
+    auto eg_of = [&](const XEnt &e) { return __builtin_amdgcn_ds_bpermute((e.hb ? pr : (pr & 15)) << 2, e.w); };
+    auto accumulate1 = [&](int e, const f32x4 &acc) {
+      const int r = e >= 0 ? (e & 255) : kT2;
+      f32x4 *d = reinterpret_cast<f32x4 *>(Ct + r * WS + (((wave * 4 + g) ^ (r & 15)) << 2));
+      *d = *d + acc;
+    };
+    if (nblk > 0) {
+      pp[0].b = 0;
+      pp[0].ka = off_from(0, 0);
+      pp[0].kb = 1 < nblk ? off_from(pp[0].ka, 1) : pp[0].ka;
+#pragma unroll
+      for (int i = 1; i < NSET + 2; ++i) pp[i] = xadv(pp[i - 1]);
+#pragma unroll
+      for (int i = 0; i <= NSET; ++i) ee[i] = xent_of(pp[i]);
+      ee[NSET + 1] = ee[0];
+      GReg gq[NSET];
+      gather(gq[0], eg_of(ee[0]), 0);
+      __syncthreads();                     // zero fill done
+      stage_store(gq[0], 0);
+      gather(gq[1], eg_of(ee[1]), 0);
+      __syncthreads();
+      // weights of the next step's two blocks; past the tile's last step the current ones again (loaded, never used)
+      auto kA_next = [&]() { return pp[1].b < nblk ? pp[1].ka : pp[0].ka; };
+      auto kB_next = [&]() { return pp[1].b < nblk ? pp[1].kb : pp[0].kb; };
+      WReg WA, WB;
+      load_w(WA, pp[0].ka, 0);
+      load_w(WB, pp[0].kb, 0);
+      auto step = [&](GReg &g_issue, GReg &g_store) __attribute__((always_inline)) {
+        gather(g_issue, eg_of(ee[NSET]), 0);                   // pair i + NSET; its entries were loaded an iteration ago
+        ee[NSET + 1] = xent_of(pp[NSET + 1]);
+        const XEnt e0 = ee[0];
+        const int ea = __builtin_amdgcn_ds_bpermute(c16 << 2, e0.w);
+        const int eb = __builtin_amdgcn_ds_bpermute((e0.hb ? 16 + c16 : c16) << 2, e0.w) | (e0.hb ? 0 : (int)0x80000000);
+        __builtin_amdgcn_sched_barrier(0);                     // the prefetches are issued HERE, ahead of the MFMAs
+        const float *sa_ = St + (NBUF == 2 ? par : 0) * STAGE + c16 * RF;
+        const float *sb_ = sa_ + 16 * RF;
+        f32x4 accA = {0.f, 0.f, 0.f, 0.f}, accB = accA;
+        if (wflip & 2) __builtin_amdgcn_s_setprio(3);
+        {
+          u32x4 a0[KG], a1[KG], b0[KG], b1[KG];
+#pragma unroll
+          for (int c = 0; c < KG; ++c) {
+            const int q0 = ((c * 8 + g * 2) ^ (c16 & SWZ)) << 2, q1 = ((c * 8 + g * 2 + 1) ^ (c16 & SWZ)) << 2;
+            a0[c] = *reinterpret_cast<const u32x4 *>(sa_ + q0);
+            b0[c] = *reinterpret_cast<const u32x4 *>(sb_ + q0);
+            a1[c] = *reinterpret_cast<const u32x4 *>(sa_ + q1);
+            b1[c] = *reinterpret_cast<const u32x4 *>(sb_ + q1);
+          }
+#pragma unroll
+          for (int c = 0; c < KG; ++c) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+              accA = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf_(WA.w0[0][0][c][t]), bcf_(a0[c][t]), accA, 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+              accA = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf_(WA.w1[0][0][c][t]), bcf_(a1[c][t]), accA, 0, 0, 0);
+          }
+          // (scheduling barriers: a refill hoisted above the MFMAs that read the set would need registers of its own)
+          __builtin_amdgcn_sched_barrier(0);
+          load_w(WA, kA_next(), 0);
+          __builtin_amdgcn_sched_barrier(0);
+          if (e0.hb) {                                         // wave-uniform, around MFMAs only
+#pragma unroll
+            for (int c = 0; c < KG; ++c) {
+#pragma unroll
+              for (int t = 0; t < 4; ++t)
+                accB = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf_(WB.w0[0][0][c][t]), bcf_(b0[c][t]), accB, 0, 0, 0);
+#pragma unroll
+              for (int t = 0; t < 4; ++t)
+                accB = __builtin_amdgcn_mfma_f32_16x16x4f32(bcf_(WB.w1[0][0][c][t]), bcf_(b1[c][t]), accB, 0, 0, 0);
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          load_w(WB, kB_next(), 0);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (wflip & 2) __builtin_amdgcn_s_setprio(0);
+        if (pp[0].kb != pp[0].ka) {                            // wave-uniform, around LDS traffic only
+          accumulate1(ea, accA);
+          accumulate1(eb, accB);
+        } else {
+          const f32x4 aA[1] = {accA}, aB[1] = {accB};
+          accumulate2(ea, aA, eb, aB);
+        }
+        if (NBUF == 1) wg_barrier();                           // single stage: every wave is done reading it
+        if (pp[1].b < nblk) stage_store(g_store, par ^ 1);     // the next pair, gathered a step ago
+        wg_barrier();
+        par ^= 1;
+#pragma unroll
+        for (int i = 0; i < NSET + 1; ++i) { pp[i] = pp[i + 1]; ee[i] = ee[i + 1]; }
+        pp[NSET + 1] = xadv(pp[NSET + 1]);
+      };
+      for (;;) {                                               // the gather sets alternate: two steps per turn
+        step(gq[0], gq[1]);
+        if (pp[0].b >= nblk) break;
+        step(gq[1], gq[0]);
+        if (pp[0].b >= nblk) break;
+      }
+    }
+  }
+  if constexpr (!XO)
   for (int kg = 0; kg < ngroups; ++kg) {
     // NSET register sets of gathered rows: the rows of pair i + NSET are requested while pair i is multiplied (fp32:
     // NSET = 2 -- a pair's MFMAs take ~1 us, a random-row gather ~2 us; bf16 storage: the MFMAs of a pair take 0.1 us,
-    // so the workgroup's pace is NSET pairs per gather latency and NSET = 4 nearly doubles it, measured).  Entries run
+    // so the workgroup's pace would be NSET pairs per gather latency -- but NSET = 4 measured SLOWER there, 111-114 us
+    // against 100-104 us with two sets, profiles/r03_conv_bf16_ab.txt, and no instance uses four).  Entries run
     // one pair further ahead.  Pair i lives in set i % NSET; the step body exists once per set (static registers).
     Pos pp[NSET + 2];
     pp[0].k = next_offset(k_lo - 1);
@@ -696,13 +840,18 @@ struct WideInst {
   WideKernel k;                    // (split = false: a split launch runs the same instance)
   const char *name, *split_name;   // what aabr_conv_last_variant reports; split_name == nullptr: no split launch uses it
   WideFn fn;
+  WideFn fn_xoff = nullptr;        // the same instance with steps across filter offsets (plain launches, WIDE_XOFF != 0)
 };
 static const WideInst kWide[] = {
     // fp32 storage: channel groups of 32 .. 128, one or two stage buffers
-    {{1, 0, 1, false, 1, false}, "k_conv_cs<1,0,1>", nullptr, k_conv_cs<1, 0, 1>},
-    {{1, 0, 2, false, 1, false}, "k_conv_cs<1,0,2>", nullptr, k_conv_cs<1, 0, 2>},
-    {{2, 0, 1, false, 1, false}, "k_conv_cs<2,0,1>", "k_conv_cs<2,0,1,split>", k_conv_cs<2, 0, 1>},
-    {{2, 0, 2, false, 1, false}, "k_conv_cs<2,0,2>", "k_conv_cs<2,0,2,split>", k_conv_cs<2, 0, 2>},
+    {{1, 0, 1, false, 1, false}, "k_conv_cs<1,0,1>", nullptr, k_conv_cs<1, 0, 1>,
+     k_conv_cs<1, 0, 1, false, 1, 2, true>},
+    {{1, 0, 2, false, 1, false}, "k_conv_cs<1,0,2>", nullptr, k_conv_cs<1, 0, 2>,
+     k_conv_cs<1, 0, 2, false, 1, 2, true>},
+    {{2, 0, 1, false, 1, false}, "k_conv_cs<2,0,1>", "k_conv_cs<2,0,1,split>", k_conv_cs<2, 0, 1>,
+     k_conv_cs<2, 0, 1, false, 1, 2, true>},
+    {{2, 0, 2, false, 1, false}, "k_conv_cs<2,0,2>", "k_conv_cs<2,0,2,split>", k_conv_cs<2, 0, 2>,
+     k_conv_cs<2, 0, 2, false, 1, 2, true>},
     {{3, 0, 1, false, 1, false}, "k_conv_cs<3,0,1>", "k_conv_cs<3,0,1,split>", k_conv_cs<3, 0, 1>},
     {{3, 0, 2, false, 1, false}, "k_conv_cs<3,0,2>", "k_conv_cs<3,0,2,split>", k_conv_cs<3, 0, 2>},
     {{4, 0, 1, false, 1, false}, "k_conv_cs<4,0,1>", "k_conv_cs<4,0,1,split>", k_conv_cs<4, 0, 1>},
@@ -737,7 +886,7 @@ static const WideInst kWide[] = {
 #endif
 };
 constexpr int kWideCount = sizeof(kWide) / sizeof(kWide[0]);
-static DynLdsOnce kWideLds[kWideCount];
+static DynLdsOnce kWideLds[kWideCount], kWideLdsX[kWideCount];
 
 // One launch as an entry point hands it over.  Feature pointers are typed as the kernel types them (fp32); with bf16
 // storage they point at bf16 rows.  parts != 0: the offset split through `scratch`.
@@ -786,7 +935,11 @@ static int wide_run(const WideArgs &a) {
   for (int i = 0; i < kWideCount && !e; ++i)
     if (kWide[i].k == k) e = &kWide[i];
   AABR_CHECK_ARG_AS(a.fn, e && (!a.split || e->split_name), "no kernel instance for this launch");
-  AABR_CHECK_HIP(dyn_lds_once(kWideLds[e - kWide], (const void *)e->fn, 80 * 1024));
+  // WIDE_XOFF: 0 = the per-offset step loop; otherwise (the default) the fp32 instances of up to 64 input channels step
+  // over the tile's block list.  Same instance key, same reported name, same bits.
+  const bool xoff = !a.split && e->fn_xoff && knob(K_WIDE_XOFF) != 0;
+  const WideFn fn = xoff ? e->fn_xoff : e->fn;
+  AABR_CHECK_HIP(dyn_lds_once(xoff ? kWideLdsX[e - kWide] : kWideLds[e - kWide], (const void *)fn, 80 * 1024));
   g_last_variant = a.split ? e->split_name : e->name;
   const dim3 grid((unsigned)t.grid_x, (unsigned)t.grid_y);
   const float *in = static_cast<const float *>(a.in), *wp = static_cast<const float *>(a.wpack);
@@ -802,7 +955,7 @@ static int wide_run(const WideArgs &a) {
     else
       hipLaunchKernelGGL((k_split_reduce<false>), rgrid, dim3(256), 0, st, a.scratch, a.parts, n4, a.n_out / 4, a.bias, res, a.out);
   } else {
-    hipLaunchKernelGGL(e->fn, grid, dim3(256), (size_t)t.lds_bytes, st, in, a.n_in, t.in_bytes, static_cast<float *>(a.out),
+    hipLaunchKernelGGL(fn, grid, dim3(256), (size_t)t.lds_bytes, st, in, a.n_in, t.in_bytes, static_cast<float *>(a.out),
                        a.n_out, a.V_out, a.blocks, t.words_bytes, a.vol, t.wflip, wp, t.wp_bytes, a.bias, a.tile_rows,
                        static_cast<const float *>(a.residual), a.stats, a.bn);
   }

@@ -56,7 +56,9 @@ const char *aabr_last_error(void);
 int aabr_version(void);
 /* Tuning knobs for experiments and tests (no counterpart in the reference; the defaults are what ships): CONV_WIDE,
  * CONV_WIDE_BF16 (0 = never / 1 = whenever supported), WIDE_ROWS, WIDE_NBUF, CONV_WLDS,
- * CONV_SMALL, CONV_NBW, CONV_WPB, VOXEL_MEAN, GEOM_JOBS (0: aabr_geom_run issues its stream builders book by book).  PLAN_TAIL
+ * CONV_SMALL, CONV_NBW, CONV_WPB, VOXEL_MEAN, GEOM_JOBS (0: aabr_geom_run issues its stream builders book by book), WIDE_XOFF
+ * (0: k_conv_cs never lets a step straddle a filter offset; otherwise, the default, its fp32 instances of up to 64 input
+ * channels step over the tile's block list: same bits).  PLAN_TAIL
  * (0 / 1 / 2: where AABR_PLAN_TAIL records run, see the compiled launch plans below; 2 ships).  A knob takes its value from the environment variable AABR_<NAME>,
  * read ONCE at its first use in the process; aabr_set_knob overrides it (unset != 0: back to "no value").  No entry
  * point reads the environment on its launch path.                                                              */
